@@ -213,10 +213,12 @@ def infer_bench(args, model, rank, world, dev, dist):
         dist.barrier()
     t0 = time.perf_counter()
     done = 0
+    last = None                                                   # the fingerprints of the last extraction call
     if big is not None:
         while done < hi - lo:
             n = min(big.shape[0], hi - lo - done)
             graphed(big[:n], big_out[:n])
+            last = big_out[:n]
             done += n
     for i in range(n_mb if big is None else 0):
         n = min(mb, hi - lo - done)
@@ -224,14 +226,18 @@ def infer_bench(args, model, rank, world, dev, dist):
         if front is not None:                                     # waveform -> log-mel segments inside the timed region
             segs = front(waves[i % 4])
             extract(segs[:n], out[:n])
+            last = out[:n]
             done += n
             continue
         extract(pool[s:s + n], out[:n])
+        last = out[:n]
         done += n
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and last is not None:
+        dump_outputs(args.dump_outputs, {"fingerprints": last})
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)          # host-side group (gloo): max over ranks
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -493,6 +499,70 @@ def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_MAX_ELEMS = 1 << 22        # per array (16 MB of float32): a run's dump stays far under 64 MB
+DUMP_SAMPLE_SEED = 20240611
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor of `arrays` as DIR/<name>.npy in float32 (float64 stays float64). An array of more than DUMP_MAX_ELEMS
+    elements is replaced by a fixed seeded sample of its rows (of its elements when 1-D), in ascending order: the positions depend on the
+    shape alone, so two builds of the project are compared element for element."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.dim() == 0:
+            t = t.reshape(1)
+        note = ""
+        if t.numel() > DUMP_MAX_ELEMS:
+            rows = max(1, DUMP_MAX_ELEMS // max(1, t[0].numel()))
+            note = f" (seeded sample of {rows} of {t.shape[0]} rows)"
+            idx = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(DUMP_SAMPLE_SEED))[:rows].sort().values
+            t = t[idx.to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), a)
+        total += a.nbytes
+        log(f"dumped {name} {tuple(a.shape)} {a.dtype}{note}")
+    assert total <= 64 << 20, f"--dump-outputs wrote {total} bytes (limit 64 MB)"
+
+
+def train_state(model, opt, loss_buf):
+    """every tensor a training step carries from one step to the next: parameters (the bf16 shadows are derived from them inside the
+    step), both Adam moments, the step count, the gradient norm, the model's buffers (BatchNorm running statistics), the gradient and the
+    loss"""
+    return [opt.flat_p, opt.exp_avg, opt.exp_avg_sq, opt.step_count, opt.grad_norm, opt.flat_g, loss_buf, *model.buffers()]
+
+
+def dump_timed_step(dirname, run, state, seeded, loss_buf, last, grads):
+    """--dump-outputs for the training step. The timed steps train the model, and the step is not bitwise reproducible (its backward
+    accumulates with fp32 atomics; a gradient that differs in the last bit moves Adam's first update by 2 lr), so after many steps two runs
+    hold different weights. What is dumped is therefore the timed step itself (`run`: the same hipGraph replay or eager step) applied to
+    the SEEDED state and the bench's seeded clips, and of it what reproduces to rounding: the loss and the encoder embeddings h of both
+    views. z and the gradient are not dumped: the head's split-K fp32 atomics reach z through a bf16 rounding (a few 1e-4 of max |z|
+    from run to run), the gradient through the atomics of the whole backward (up to 2e-2 of max |g|). The step runs twice and the spread
+    of all six arrays between the two is logged; the state the timed steps left behind is put back afterwards, so nothing else in the
+    bench line changes. dirname None: run the steps (every rank must, they hold collectives) but write nothing."""
+    end = [t.clone() for t in state]
+
+    def once():
+        for t, s in zip(state, seeded):
+            t.copy_(s)
+        run()
+        torch.cuda.synchronize()
+        return {"loss": loss_buf.clone(), **{k: v.detach().clone() for k, v in last.items()}, "grads": grads.clone()}
+
+    a, b = once(), once()
+    for t, s in zip(state, end):
+        t.copy_(s)
+    torch.cuda.synchronize()
+    if dirname is None:
+        return
+    spread = {k: float((a[k].float() - b[k].float()).abs().max()) / max(1e-30, float(a[k].float().abs().max())) for k in a}
+    log("step from the seeded state, run twice: max|a-b| / max|a| " + ", ".join(f"{k} {v:.1e}" for k, v in spread.items()))
+    dump_outputs(dirname, {k: a[k] for k in ("loss", "h_i", "h_j")})
+
+
 def _run_rank_job(n: int, deadline: float, extra_env: dict):
     """one attempt: n FRESH child ranks through torch.distributed.run; returns (exit code, JSON lines, stdout); 124 = deadline overrun"""
     import signal
@@ -593,13 +663,20 @@ def run_config(args, ctx, side=False):
     one = torch.ones((), device=dev)          # static grad_output of loss.backward(): autograd then launches no fill kernel
     reducer = parallel.GradReducer(opt.params, opt.flat_g, opt.offsets, bucket_bytes=16 << 20).install()
     parallel.ASYNC_LOSS_REDUCE = True        # reducer.finish() joins the communicator's stream before the loss is read
+    # --dump-outputs: the step's embeddings, kept by reference (a graph replay rewrites the captured ones in place); only then, so the
+    # step that is timed without the flag allocates exactly as before
+    last = {} if args.dump_outputs else None
 
     def step():
         opt.zero_grad()
         reducer.start_step()
         if model._side_stream is not None:
             reducer.streams = [torch.cuda.current_stream(), model._side_stream]
-        _, _, z_i, z_j = model(x_i, x_j)
+        outs = model(x_i, x_j)
+        if last is not None:
+            last.update(zip(("h_i", "h_j", "z_i", "z_j"), outs))
+        _, _, z_i, z_j = outs
+        del outs                                             # without the flag nothing holds h_i past this point
         loss = parallel.dist_ntxent_loss(z_i, z_j, CFG)      # z all-gather; NT-Xent over the global batch
         loss.backward(one)                                   # bucketed all-reduce fires as buckets complete
         reducer.finish()
@@ -614,6 +691,9 @@ def run_config(args, ctx, side=False):
         parallel.sync_with_deadline(what="the bench step")
 
     # ---- warm-up (eager), then capture the whole step in a hipGraph (launch-bound inner loop: ~1.2k kernels/step)
+    # --dump-outputs: the state the step reads and writes, as seeded, before any step runs (dump_timed_step)
+    state = train_state(model, opt, loss_buf) if last is not None else None
+    seeded = [t.clone() for t in state] if state is not None else None
     n_eager = max(1, min(args.warmup, 3))
     for i in range(n_eager):
         step()
@@ -672,6 +752,8 @@ def run_config(args, ctx, side=False):
     elapsed = time.perf_counter() - t0
     if rank == 0:
         log(f"timed {args.steps} steps: {1e3 * elapsed / args.steps:.2f} ms/step")
+    if last is not None:
+        dump_timed_step(args.dump_outputs if rank == 0 else None, run, state, seeded, loss_buf, last, opt.flat_g)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64)             # host-side group (gloo)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -891,10 +973,17 @@ def main():
     ap.add_argument("--flag", action="append", default=[], metavar="MODULE.NAME=VALUE",
                     help="set a module-level switch of the host side for this run, e.g. ops.FUSE_BN_BWD_APPLY=0 (one-box A/B); "
                          "recorded in config.flags")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path computes as DIR/<name>.npy (float32; large arrays as a "
+                         "fixed seeded sample). train: the timed step once more, from the seeded weights and optimiser state on the "
+                         "seeded clips (loss, h_i, h_j); the state the timed steps reached is restored afterwards. "
+                         "infer: the fingerprints of the last extraction call. Same arguments, same outputs up to rounding")
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="set a tuning key of the kernel library (include/nsid.h nsid_set_tuning) for this run; recorded in "
                          "config.tuning. The library never reads the environment.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 
@@ -952,6 +1041,7 @@ def main():
                               ("config4_deep_step", {"deep": True}),
                               ("config5_fingerprint_100k", {"mode": "infer", "clips": 100000})):
             a2 = copy.copy(args)
+            a2.dump_outputs = None           # --dump-outputs is the headline's
             for k_, v_ in changes.items():
                 setattr(a2, k_, v_)
             log(f"other configuration: {name}")

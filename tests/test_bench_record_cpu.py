@@ -94,3 +94,30 @@ def test_the_committed_bench_line_agrees_with_the_committed_rocprof_trace():
         if us > 100.0:
             assert abs(us - trace[k]) <= 0.25 * trace[k], (k, us, trace[k])
     assert line["config"]["workload"].startswith("B=256 bf16 k=3 hipGraph 2-stream")      # the distinguishing facts survive a truncation
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones_the_same_way(tmp_path):
+    """bench.py --dump-outputs: float32 .npy files (float64 kept), a scalar as shape (1,), an array over DUMP_MAX_ELEMS elements as a seeded
+    sample of its rows that depends on the shape alone (two runs, two builds: the same positions), the whole dump under 64 MB"""
+    import numpy as np
+    import torch
+    n = bench.DUMP_MAX_ELEMS + 1000
+    flat = torch.arange(n, dtype=torch.float32)
+    rows = torch.randn(bench.DUMP_MAX_ELEMS // 64 + 7, 128).to(torch.bfloat16)
+    arrays = {"loss": torch.tensor(1.5), "z": torch.randn(8, 4).to(torch.bfloat16), "x64": torch.randn(3, dtype=torch.float64),
+              "flat": flat, "rows": rows}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in arrays}
+    assert a["loss"].shape == (1,) and a["loss"][0] == 1.5 and a["loss"].dtype == np.float32
+    assert a["z"].dtype == np.float32 and np.array_equal(a["z"], arrays["z"].float().numpy())
+    assert a["x64"].dtype == np.float64
+    assert a["flat"].shape == (bench.DUMP_MAX_ELEMS,) and np.all(np.diff(a["flat"]) > 0)       # ascending positions of the source
+    assert a["rows"].shape == (bench.DUMP_MAX_ELEMS // 128, 128)
+    full = rows.float().numpy()
+    hit = [int(np.nonzero((full == r).all(1))[0][0]) for r in a["rows"][:50]]
+    assert hit == sorted(hit)                                                                  # rows of the source, in order
+    for k in arrays:
+        assert np.array_equal(a[k], b[k])
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
