@@ -1502,12 +1502,15 @@ extern "C" int nsid_linear_bwd_weight_grouped(const nsid_wgrad_problem* problems
   const long rows_target = std::max<long>(128, nsid_tune(NSID_T_wgg_rows));
   const long rows_sq = std::max<long>(128, nsid_tune(NSID_T_wgg_rows_sq)), rows_gen = std::max<long>(32, nsid_tune(NSID_T_wgg_rows_gen));
   const bool use_w3 = nsid_tune(NSID_T_wgg_w3) != 0;
+  const bool use_w4 = nsid_tune(NSID_T_wgrad256) != 0;
+  const long rows_w4 = std::max<long>(128, nsid_tune(NSID_T_wgg_rows256));
   // classes: 0 = 128x64 full tiles (64-deep stages), 1 = 64x64 full tiles, 2 = 64x64 predicated (any shape),
   //          3 / 4 = 128x128 tiles, 8 waves (wgrad.hip), without / with the producer affine on x,
-  //          5 = Downsample (64x64 predicated over the padded 3-tap view of x), 6 = fp32 storage (64x64 predicated; the projector head)
-  constexpr int NCLS = 7;
+  //          5 = Downsample (64x64 predicated over the padded 3-tap view of x), 6 = fp32 storage (64x64 predicated; the projector head),
+  //          7 = 256x256 tiles, LDS-DMA staging (wgrad256.hip), with and without the producer affine on x
+  constexpr int NCLS = 8;
   WgGroupArgs ga[NCLS];
-  long wgs[NCLS] = {0, 0, 0, 0, 0, 0, 0};
+  long wgs[NCLS] = {0, 0, 0, 0, 0, 0, 0, 0};
   const bool half = g_gemm_precision == NSID_GEMM_BF16 || st16;
   for (int c = 0; c < NCLS; ++c) ga[c].n = 0;
   auto flush = [&](int c) -> int {
@@ -1523,6 +1526,14 @@ extern "C" int nsid_linear_bwd_weight_grouped(const nsid_wgrad_problem* problems
       ga[c].n = 0;
       wgs[c] = 0;
       return rc3;
+    }
+    if (c == 7) {
+      nsid_count(NSID_C_wgrad_grouped);
+      nsid_count(NSID_C_wgrad_grouped_256);
+      const int rc4 = nsid_wgrad4_grouped_launch(ga[c], (int)gsz, s);
+      ga[c].n = 0;
+      wgs[c] = 0;
+      return rc4;
     }
     if (c == 0) NSID_LAUNCH((wgrad_grouped_kernel<128, 64, true>), grid, block, 0, s, ga[c]);
     else if (c == 1) NSID_LAUNCH((wgrad_grouped_kernel<64, 64, true>), grid, block, 0, s, ga[c]);
@@ -1553,10 +1564,14 @@ extern "C" int nsid_linear_bwd_weight_grouped(const nsid_wgrad_problem* problems
     const bool rows_ok = q.M % 128 == 0;
     int cls = (rows_ok && q.Nout % 128 == 0 && q.K % 64 == 0) ? 0 : ((rows_ok && q.Nout % 64 == 0 && q.K % 64 == 0) ? 1 : 2);
     if (cls == 0 && use_w3 && q.K % 128 == 0) cls = q.in_scale[0] != nullptr ? 4 : 3;
+    if (cls == 0 || cls == 3 || cls == 4) {
+      if (use_w4 && q.Nout % 256 == 0 && q.K % 256 == 0) cls = 7;
+    }
     if (ds) cls = 5;
     if (!st16) cls = 6;
-    const int bm = (cls == 0 || cls == 3 || cls == 4) ? 128 : 64, bn = (cls == 3 || cls == 4) ? 128 : 64;
-    const long rows_cls = (cls == 1 || cls == 5) ? rows_sq : ((cls == 2 || cls == 6) ? rows_gen : rows_target);
+    const bool w4 = cls == 7;
+    const int bm = w4 ? 256 : ((cls == 0 || cls == 3 || cls == 4) ? 128 : 64), bn = w4 ? 256 : ((cls == 3 || cls == 4) ? 128 : 64);
+    const long rows_cls = (cls == 1 || cls == 5) ? rows_sq : ((cls == 2 || cls == 6) ? rows_gen : (w4 ? rows_w4 : rows_target));
     WgProb w{};
     for (int v = 0; v < 2; ++v) {
       w.A[v] = q.dout[v]; w.B[v] = q.x[v]; w.bsc[v] = q.in_scale[v]; w.bsh[v] = q.in_shift[v];

@@ -176,6 +176,8 @@ static inline bool nsid_aligned16(const void* p) { return (reinterpret_cast<uint
   X(wgg_rows_gen, 512)         /* and for its predicated class (stem, the 32-channel grouped conv) */ \
   X(bn_fin_tiles, 0)           /* BatchNorm finalize kernels: from this many row tiles on a workgroup covers 16 channels x 64 tile groups instead of 64 x 16 (0: never; 256 measured equal within noise, docs/experiments.md round 6) */ \
   X(wgg_w3, 1)                 /* grouped problems with Nout % 128 == 0 and K % 128 == 0 on 128x128 tiles, 8 waves (wgrad.hip) */ \
+  X(wgrad256, 1)               /* grouped problems with Nout % 256 == 0 and K % 256 == 0 on 256x256 tiles with LDS-DMA staging (wgrad256.hip) */ \
+  X(wgg_rows256, 4096)         /* rows per work item of that class (a multiple of 128); the phase's main lane alone, cold: 1.10 ms (128x128) -> 0.91 / 1.12 ms at 4096 / 8192 rows (docs/experiments.md round 7) */ \
   X(ws_gemm, 7)                /* weight-stationary streaming GEMMs (wsgemm.hip) for the small-K layers: bit 0 forward, bit 1 backward-data, bit 2 backward-data with the BatchNorm backward on its operand load */
 
 enum NsidTuneKey {
@@ -203,7 +205,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(gemm_bn_apply_load)   /* backward-data applies a BatchNorm backward on its operand load */  \
   X(gemm256)              /* gemm256.hip */                                                     \
   X(ws_fwd) X(ws_bwd_data) X(ws_bwd_bnapply) /* wsgemm.hip: weight-stationary streaming forms */                   \
-  X(wgrad_rect) X(wgrad_square) X(wgrad3) X(wgrad_grouped) X(wgrad_grouped_w3)                                                       \
+  X(wgrad_rect) X(wgrad_square) X(wgrad3) X(wgrad_grouped) X(wgrad_grouped_w3) X(wgrad_grouped_256)                                                 \
   X(bn_bwd_apply) X(bn_bwd_apply_capped)                                                        \
   X(knn2) X(knn2_pair) X(knn2_raw) X(knn_rank) X(knn_sel) X(knn_strips) X(knn_big)                                                  \
   X(mr_fwd_lds) X(mr_fwd_grid) X(mr_fwd_key) X(mr_bwd_sorted)                                                                  \
@@ -272,6 +274,9 @@ __device__ __forceinline__ bool wgg_decode(const WgGroupArgs& ga, const int w, i
 }
 // wgrad.hip: the 8-wave 128x128-tile form of a grouped launch (Nout % 128 == 0, K % 128 == 0, whole 128-row chunks)
 int nsid_wgrad3_grouped_launch(const WgGroupArgs& ga, int grid, bool affine, hipStream_t stream);
+// wgrad256.hip: the 256x256-tile LDS-DMA form (Nout % 256 == 0, K % 256 == 0, row chunks of a multiple of 128; plain and affine
+// problems in one launch)
+int nsid_wgrad4_grouped_launch(const WgGroupArgs& ga, int grid, hipStream_t stream);
 
 // wgrad.hip: 128x128-tile form of the bf16 weight-gradient GEMM; returns 1 when the shape is outside its preconditions
 int nsid_wgrad2_launch(const void* dout, int ldd, const void* x, int ldx, float* dw, int M, int Nout, int K, int groups,
