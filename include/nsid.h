@@ -76,7 +76,8 @@ int nsid_row_tiles(int M);
  * "linear_bwd_weight", "downsample3", "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused")
  * except: "bn_stat" (rows x cols layer: the [2][nsid_row_tiles(rows)][cols] fp32 partial sums between a GEMM's statistics
  * epilogue / nsid_bn_bwd_reduce and the finalize kernels), "ntxent" (rows = pairs of the global batch: nsid_ntxent_ws_floats),
- * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums). */
+ * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
+ * per-split top-64 lists of its first phase). */
 long nsid_workspace_bytes(const char* op, long rows, long cols);
 
 /* ---- 1x1 convolution / Linear as a row GEMM on MFMA (fp32 accumulate) ------------------------------------
@@ -345,6 +346,23 @@ int nsid_scale_f32(const float* x, const float* scale, long n, float* out, void*
 /* ---- layout plumbing at the module boundary: (B, C, N) <-> node-major rows ------------------------------*/
 int nsid_bcn_to_rows(const float* x, int B, int C, int N, void* rows, int ld, int rows_dtype, void* stream);
 int nsid_rows_to_bcn(const void* rows, int ld, int B, int C, int N, float* x, int rows_dtype, void* stream);
+
+/* ---- exact flat-L2 fingerprint search (eval.py:198-367 eval_faiss with index_type='l2': faiss.IndexFlatL2 + the sequence score of
+ * every candidate, eval.py:318-331). fp32, row-major with leading dimensions, rows 16-byte aligned (ld % 4 == 0); d % 16 == 0 and
+ * 16 <= d <= 256, 1 <= k <= 64, row counts below 2^31; NSID_EINVAL (nothing launched) otherwise.
+ * row_sqnorm: out[i] = ||x_i||^2 in one fixed summation order (the index computes its rows' norms once, on add).
+ * flat_l2_topk: per query row the k database rows of smallest key ||x_j||^2 - 2 q.x_j (the dot on v_mfma_f32_32x32x2_f32: one
+ *   k-ordered fp32 fmaf chain), sorted ascending, equal keys smaller id first; D (nq x k) = max(0, ||q||^2 + key) (squared L2, as
+ *   FAISS reports it), I (nq x k, int64) the row ids; k > nx: the tail is I = -1, D = +inf. A row's result is bitwise independent of
+ *   the other rows of the call; no atomics. ws: nsid_workspace_bytes("flat_l2_topk", nq, nx) bytes (enough for any k <= 64).
+ * seq_scores: for pair p = (s = starts[p], L = lens[p]) (device int32; the caller guarantees s + L <= the rows of q and of I) and
+ *   candidate j < L*k with cid = I[s + j/k][j%k]: out[p*ldo + j] = mean over i < min(L, nx - cid) of q[s+i].x[cid+i] (fp32),
+ *   NaN when cid < 0 and for L*k <= j < ldo (eval.py:325-331, the window truncated at the end of the index). ldo <= 262140. */
+int nsid_row_sqnorm(const float* x, int ldx, int n, int d, float* out, void* stream);
+int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm, const float* q_sqnorm,
+                      int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream);
+int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, int d, const int64_t* I, int k, const int* starts,
+                    const int* lens, int npairs, float* out, int ldo, void* stream);
 
 #ifdef __cplusplus
 }

@@ -65,6 +65,9 @@ SIGNATURES = {
     "nsid_batched_index_select_bwd": "ppiiiiips",
     "nsid_fill_zero": "pzs",
     "nsid_scale_f32": "pplps",
+    "nsid_row_sqnorm": "piiips",
+    "nsid_flat_l2_topk": "piipiippiipppzs",
+    "nsid_seq_scores": "pipiiipippipis",
 }
 
 class WgradProblem(ctypes.Structure):

@@ -210,7 +210,8 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(knn2) X(knn2_pair) X(knn2_raw) X(knn_rank) X(knn_sel) X(knn_strips) X(knn_big)                                                  \
   X(mr_fwd_lds) X(mr_fwd_grid) X(mr_fwd_key) X(mr_bwd_sorted)                                                                  \
   X(ffn_fused)            /* eval-mode FFN in one launch (ffn_fused.hip) */                     \
-  X(mrconv_fused)         /* eval-mode max-relative aggregation + grouped conv in one launch (mrconv_fused.hip) */
+  X(mrconv_fused)         /* eval-mode max-relative aggregation + grouped conv in one launch (mrconv_fused.hip) */ \
+  X(row_sqnorm) X(flat_l2_topk) X(seq_scores)   /* search.hip: exact flat-L2 fingerprint search */
 
 enum NsidCounterKey {
 #define NSID_CNT_ENUM(name) NSID_C_##name,
@@ -299,4 +300,7 @@ int nsid_ws_bwd_data_launch(const void* dout, int ldd, const void* w, const void
 // ffn256_fused.hip: eval-mode FFN of the C = 256 stage in one launch; returns 1 outside C = 256, H = 1024, M % 256 == 0
 int nsid_ffn256_fused_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int M, int C,
                              int H, hipStream_t stream);
+// search.hip: the database split of nsid_flat_l2_topk's first phase, and its workspace for k entries per (row, split)
+void nsid_l2_plan(long nq, long nx, int* splits, int* chunk);
+long nsid_l2_ws_bytes(long nq, long nx, int k);
 extern void* g_gemm_trace_host;        // gemm.hip: the buffer installed by nsid_debug_gemm_trace (nullptr = none)

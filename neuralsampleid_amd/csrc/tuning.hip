@@ -82,5 +82,7 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
     return (long)(nsid_ntxent_ws_floats((int)rows) * sizeof(float));
   if (strcmp(op, "sumsq") == 0)              // rows = elements of the flat gradient
     return (long)nsid_sumsq_blocks(rows) * (long)sizeof(float);
+  if (strcmp(op, "flat_l2_topk") == 0)       // rows = query rows, cols = database rows; for k = 64
+    return nsid_l2_ws_bytes(rows, cols, 64);
   return -1;
 }

@@ -1202,3 +1202,92 @@ def rows_to_bcn(rows, B, N) -> torch.Tensor:
     x = torch.empty((B, C, N), device=rows.device, dtype=torch.float32)
     call("nsid_rows_to_bcn", _p(rows), C, B, C, N, _p(x), _act(rows), _stream())
     return x
+
+
+# ------------------------------------------------------------------------------------------------ exact flat-L2 search (csrc/search.hip)
+SEARCH_MAX_K = 64
+
+
+def _search_rows(t, name):
+    """a (n, d) fp32 matrix on the GPU with unit column stride and 16-byte rows; d % 16 == 0, 16 <= d <= 256"""
+    if not t.is_cuda:
+        raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        raise RuntimeError(f"{name}: expected a (rows, d) float32 matrix with unit column stride and 16-byte aligned rows")
+    d = t.shape[1]
+    if d % 16 or not 16 <= d <= 256:
+        raise ValueError(f"{name}: d = {d} is outside the search kernels' limits (d % 16 == 0, 16 <= d <= 256)")
+    return max(t.stride(0), d)
+
+
+def row_sqnorm(x) -> torch.Tensor:
+    """(n, d) fp32 -> (n,) fp32 squared row norms in one fixed summation order"""
+    ldx = _search_rows(x, "row_sqnorm")
+    n, d = x.shape
+    out = torch.empty((n,), device=x.device, dtype=torch.float32)
+    _tk("row_sqnorm_kernel", 4.0 * n * (d + 1), lambda: call("nsid_row_sqnorm", _p(x), ldx, n, d, _p(out), _stream()), (n, d, 0, 1))
+    return out
+
+
+def flat_l2_topk(q, x, x_sqnorm, k, q_sqnorm=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """exhaustive squared-L2 top-k of every row of q (nq, d) over the rows of x (nx, d) with their norms x_sqnorm (row_sqnorm):
+    D (nq, k) fp32 ascending, I (nq, k) int64, equal distances smaller id first, k > nx padded with I = -1, D = +inf"""
+    k = int(k)
+    if not 1 <= k <= SEARCH_MAX_K:
+        raise ValueError(f"flat_l2_topk: k = {k} is outside [1, {SEARCH_MAX_K}]")
+    ldq, ldx = _search_rows(q, "flat_l2_topk q"), _search_rows(x, "flat_l2_topk x")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"flat_l2_topk: query d = {q.shape[1]} != database d = {x.shape[1]}")
+    _chk(x_sqnorm)
+    nq, d = q.shape
+    nx = x.shape[0]
+    if x_sqnorm.numel() != nx:
+        raise ValueError("flat_l2_topk: x_sqnorm must hold one norm per database row")
+    if q_sqnorm is None:
+        q_sqnorm = row_sqnorm(q)
+    D = torch.empty((nq, k), device=q.device, dtype=torch.float32)
+    I = torch.empty((nq, k), device=q.device, dtype=torch.int64)
+    if nq == 0:
+        return D, I
+    wsb = int(lib.nsid_workspace_bytes(b"flat_l2_topk", nq, nx))
+    ws = torch.empty((max(wsb, 16),), device=q.device, dtype=torch.uint8)
+    # phase 1 streams the database once per split pass (512 B per row at d = 128) and runs 2 nq nx d flop on the fp32 matrix pipe
+    _timed("flat_l2_topk", 2.0 * nq * nx * d, 4.0 * nx * d + 4.0 * nq * d + 12.0 * nq * k, lambda: call(
+        "nsid_flat_l2_topk", _p(q), ldq, nq, _p(x) if nx else None, ldx, nx, _p(x_sqnorm) if nx else None, _p(q_sqnorm), d, k,
+        _p(D), _p(I), _p(ws), ws.numel(), _stream()), (nq, nx, d, k))
+    return D, I
+
+
+def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:
+    """eval.py:325-331 for every (start, length) pair at once: out[p, j] = mean over i < min(L, nx - cid) of q[s+i].x[cid+i] with
+    cid = I[s + j // k, j % k] (j < L k), NaN for cid < 0 and for j >= L k. starts / lens: host integer sequences (checked here
+    against the rows of q and I, then copied to the GPU)."""
+    import numpy as np
+    ldq, ldx = _search_rows(q, "seq_scores q"), _search_rows(x, "seq_scores x")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError("seq_scores: query and database d differ")
+    if I.dtype != torch.int64 or I.dim() != 2 or not I.is_contiguous() or not I.is_cuda:
+        raise RuntimeError("seq_scores: I must be a contiguous (rows, k) int64 tensor on the GPU")
+    k = I.shape[1]
+    if not 1 <= k <= SEARCH_MAX_K:
+        raise ValueError(f"seq_scores: k = {k} is outside [1, {SEARCH_MAX_K}]")
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if starts.shape != lens.shape:
+        raise ValueError("seq_scores: starts and lens differ in length")
+    ldo = int(ldo)
+    npairs = starts.size
+    if npairs and (starts.min() < 0 or lens.min() < 1 or (starts + lens).max() > min(q.shape[0], I.shape[0])):
+        raise ValueError("seq_scores: every pair needs 0 <= start, 1 <= length and start + length <= the rows of q and I")
+    if not 0 <= ldo <= 4 * 65535:
+        raise ValueError(f"seq_scores: ldo = {ldo} is outside [0, 262140]")
+    out = torch.empty((npairs, ldo), device=q.device, dtype=torch.float32)
+    if npairs == 0 or ldo == 0:
+        return out
+    st = torch.from_numpy(starts.astype(np.int32)).to(q.device)
+    ln = torch.from_numpy(lens.astype(np.int32)).to(q.device)
+    nx, d = x.shape
+    _tk("seq_scores_kernel", 8.0 * float(lens.sum()) * k * d, lambda: call(
+        "nsid_seq_scores", _p(q), ldq, _p(x), ldx, nx, d, _p(I), k, _p(st), _p(ln), npairs, _p(out), ldo, _stream()),
+        (npairs, ldo, d, 1))
+    return out
