@@ -364,6 +364,22 @@ int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, 
 int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, int d, const int64_t* I, int k, const int* starts,
                     const int* lens, int npairs, float* out, int ldo, void* stream);
 
+/* ---- classifier re-rank (downstream.py:30-78 CrossAttentionClassifier in eval mode, as eval_hr.py::eval_faiss_clf and
+ * eval_map.py::eval_faiss_map_clf call it). fp32; C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing
+ * launched) otherwise.
+ * clf_node_rows: rows[(s N + n) C + c] = x[(s C + c) N + n] + pos[n C + c] ((S, C, N) node matrices to node rows; pos may be NULL;
+ *   C % 32 == 0).
+ * clf_pair_scores: q (nq_seg N x 512): the queries' projected rows Q / sqrt(128) (pos and bias included); kp (nc_seg N x 1024): the
+ *   candidates' [K | P] rows, P_h = V_h G_h^T with G = W1 Wo (the folded tail); tail = {g = W1 bo + b1 (128), w2 (128), b2}.
+ *   Group i = groups[4i .. 4i+3] = {first query segment, query segments, offset into cidx, candidates}; its scores go row-major
+ *   (query x candidate) to out + out_off[i]. tile_off: ngroups + 1 prefix sums of candidates x ceil(query segments / 64), ntiles =
+ *   tile_off[ngroups]. The caller guarantees the lists are in range (the kernel skips, never writes, an out-of-range entry). A
+ *   pair's score is bitwise independent of the rest of the call; no atomics. q, kp 16-byte aligned. */
+int nsid_clf_node_rows(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream);
+int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups, const int64_t* out_off,
+                         const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail, float* out,
+                         int64_t out_len, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

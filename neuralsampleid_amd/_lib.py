@@ -68,6 +68,8 @@ SIGNATURES = {
     "nsid_row_sqnorm": "piiips",
     "nsid_flat_l2_topk": "piipiippiipppzs",
     "nsid_seq_scores": "pipiiipippipis",
+    "nsid_clf_node_rows": "piiipps",
+    "nsid_clf_pair_scores": "pipiipppiipppls",
 }
 
 class WgradProblem(ctypes.Structure):

@@ -211,7 +211,8 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(mr_fwd_lds) X(mr_fwd_grid) X(mr_fwd_key) X(mr_bwd_sorted)                                                                  \
   X(ffn_fused)            /* eval-mode FFN in one launch (ffn_fused.hip) */                     \
   X(mrconv_fused)         /* eval-mode max-relative aggregation + grouped conv in one launch (mrconv_fused.hip) */ \
-  X(row_sqnorm) X(flat_l2_topk) X(seq_scores)   /* search.hip: exact flat-L2 fingerprint search */
+  X(row_sqnorm) X(flat_l2_topk) X(seq_scores)   /* search.hip: exact flat-L2 fingerprint search */ \
+  X(clf_node_rows) X(clf_pair_scores)           /* rerank.hip: classifier re-rank pair scores */
 
 enum NsidCounterKey {
 #define NSID_CNT_ENUM(name) NSID_C_##name,

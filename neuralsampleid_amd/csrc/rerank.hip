@@ -1,0 +1,190 @@
+// Classifier re-rank pair scores (include/nsid.h nsid_clf_node_rows / nsid_clf_pair_scores).
+//
+// Reference: downstream.py:30-78 CrossAttentionClassifier in eval mode, called per candidate by eval_hr.py::eval_faiss_clf and
+// eval_map.py::eval_faiss_map_clf. For one pair (query x_i, candidate x_j, both (N, C) node rows, C = 512, H = 4 heads of dh = 128):
+//   A_h = softmax(Q_h K_h^T / sqrt(dh)),  m = mean_n (concat_h A_h V_h) Wo^T + bo,  s = sigmoid(w2 . relu(W1 m + b1) + b2).
+// Nothing between out_proj, the node mean and fc.0 is nonlinear, so with a_h = the column mean of A_h (length N) and G = W1 Wo:
+//   W1 m + b1 = g + sum_h G_h V_h^T a_h,   g = W1 bo + b1,   G_h = G[:, h dh : (h+1) dh].
+// The candidate side is folded one step further: P_h = V_h G_h^T = X_j (G_h Wv_h)^T + G_h bv_h is a plain linear of the candidate's
+// node rows, computed once per segment next to K (the caller's GEMM). Per pair this kernel then does Q K^T on the fp32 MFMA, the row
+// softmax, the column mean, hidden = g + sum_h a_h^T P_h (16 k MAC), relu, the w2 dot and the sigmoid; only the score reaches HBM.
+//
+// One workgroup (8 waves) per (group, candidate, chunk of query segments): the candidate's K and P rows are staged into LDS once
+// (128 KB); each wave takes query segments of the chunk in turn and streams their Q rows from global memory as MFMA B fragments.
+// Every sum runs in one fixed order that depends on nothing but the pair, so a pair's score is bitwise independent of the rest of the
+// call; there are no atomics.
+#include "nsid_common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int RR_C = 512;            // node channels
+constexpr int RR_DH = 128;           // head dim (4 heads)
+constexpr int RR_H = 4;
+constexpr int RR_N = 32;             // nodes per segment at most (one 32x32 MFMA tile)
+constexpr int RR_HID = 128;          // fc.0 width
+constexpr int RR_WAVES = 8;
+constexpr int RR_QCH = 64;           // query segments per workgroup
+constexpr int RR_KLD = RR_C + 4;     // LDS row of K: +16 B so that the 32 rows of a fragment read start in different banks
+constexpr int RR_LDKP = 2 * RR_C;    // the candidates' projected rows: [K | P]
+
+__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// group g: {first query segment, query segments, offset into cidx, candidates}; its scores are the row-major (q count x c count)
+// block at out + out_off[g]. tile_off: prefix sums of the groups' workgroups (c count x query chunks), ngroups + 1 entries.
+__global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kp,
+                                                       int nc_seg, int N, const int* __restrict__ grp,
+                                                       const int64_t* __restrict__ out_off, const int* __restrict__ tile_off,
+                                                       int ngroups, const int* __restrict__ cidx, const float* __restrict__ tail,
+                                                       float* __restrict__ out, int64_t out_len) {
+  __shared__ __attribute__((aligned(16))) float ks[RR_N][RR_KLD];
+  __shared__ __attribute__((aligned(16))) float ps[RR_N][RR_C];
+  __shared__ float abar[RR_WAVES][RR_N];
+
+  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+
+  // the group of this workgroup: the last g with tile_off[g] <= blockIdx.x
+  int lo = 0, hi = ngroups - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tile_off[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const int g = lo;
+  const int q0 = grp[4 * g], qn = grp[4 * g + 1], coff = grp[4 * g + 2], cn = grp[4 * g + 3];
+  const int t = b - tile_off[g];
+  const int jpos = t % cn, qc = t / cn;
+  const int cand = cidx[coff + jpos];
+  if (cand < 0 || cand >= nc_seg) return;              // the host checks the lists; this only keeps a bad list in bounds
+
+  // stage K and P of the candidate (rows >= N are zero)
+  const float* kc = kp + (size_t)cand * N * RR_LDKP;
+  for (int i = tid; i < RR_N * (RR_C / 4); i += 512) {
+    const int n = i / (RR_C / 4), c = 4 * (i % (RR_C / 4));
+    f32x4 kv = {0.f, 0.f, 0.f, 0.f}, pv = {0.f, 0.f, 0.f, 0.f};
+    if (n < N) {
+      kv = ld4(kc + (size_t)n * RR_LDKP + c);
+      pv = ld4(kc + (size_t)n * RR_LDKP + RR_C + c);
+    }
+    *reinterpret_cast<f32x4*>(&ks[n][c]) = kv;
+    *reinterpret_cast<f32x4*>(&ps[n][c]) = pv;
+  }
+  __syncthreads();
+
+  const float invN = 1.0f / (float)N;
+  const int s_end = min(qn, (qc + 1) * RR_QCH);
+  // the register this lane holds after the column reduce-scatter below, and its key
+  const int gf = (((r >> 4) & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 1) & 1);
+  const int jf = (gf & 3) + 8 * (gf >> 2) + 4 * hh;
+
+  for (int s = qc * RR_QCH + w; s < s_end; s += RR_WAVES) {
+    const int qseg = q0 + s;
+    if (qseg < 0 || qseg >= nq_seg) continue;
+    const int64_t o = out_off[g] + (int64_t)s * cn + jpos;
+    if (o < 0 || o >= out_len) continue;
+    const float* qp = q + ((size_t)qseg * N + (r < N ? r : 0)) * RR_C + 4 * hh;
+    float part0 = 0.f, part1 = 0.f;             // hidden[lane], hidden[64 + lane] without g
+
+    f32x4 qf[RR_DH / 8];
+#pragma unroll
+    for (int bb = 0; bb < RR_DH / 8; ++bb) qf[bb] = r < N ? ld4(qp + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
+
+#pragma unroll
+    for (int h = 0; h < RR_H; ++h) {
+      // S^T[key][query]: A = K rows (LDS), B = Q rows; lane (r, hh) supplies dims 8 bb + 4 hh + e of row r at step (bb, e)
+      f32x16 acc = {};
+#pragma unroll
+      for (int bb = 0; bb < RR_DH / 8; ++bb) {
+        const f32x4 ka = *reinterpret_cast<const f32x4*>(&ks[r][h * RR_DH + 8 * bb + 4 * hh]);
+        const f32x4 qb = qf[bb];
+        if (h + 1 < RR_H) qf[bb] = r < N ? ld4(qp + (h + 1) * RR_DH + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[e], qb[e], acc, 0, 0, 0);
+      }
+      // acc[i] of lane (r, hh) = score of query node r against key (i & 3) + 8 (i >> 2) + 4 hh: softmax over the keys of query r
+      float mx = -__builtin_inff();
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if ((i & 3) + 8 * (i >> 2) + 4 * hh < N) mx = fmaxf(mx, acc[i]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      float v[16];
+      float sum = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        v[i] = (i & 3) + 8 * (i >> 2) + 4 * hh < N ? expf(acc[i] - mx) : 0.f;
+        sum += v[i];
+      }
+      sum += __shfl_xor(sum, 32);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) v[i] = r < N ? v[i] / sum : 0.f;
+      // column sums over the 32 query lanes of each half: reduce-scatter, halving the registers at every step
+#pragma unroll
+      for (int c = 16, off = 16; c > 1; c >>= 1, off >>= 1) {
+        const bool up = (r & off) != 0;
+#pragma unroll
+        for (int i = 0; i < c / 2; ++i) {
+          const float keep = up ? v[i + c / 2] : v[i];
+          const float send = up ? v[i] : v[i + c / 2];
+          v[i] = keep + __shfl_xor(send, off);
+        }
+      }
+      v[0] += __shfl_xor(v[0], 1);
+      if ((r & 1) == 0) abar[w][jf] = v[0] * invN;
+      __builtin_amdgcn_wave_barrier();
+      // hidden += a_h^T P_h
+      for (int m = 0; m < N; ++m) {
+        const float a = abar[w][m];
+        part0 = fmaf(a, ps[m][h * RR_DH + lane], part0);
+        part1 = fmaf(a, ps[m][h * RR_DH + 64 + lane], part1);
+      }
+      __builtin_amdgcn_wave_barrier();
+    }
+    const float h0 = fmaxf(part0 + tail[lane], 0.f), h1 = fmaxf(part1 + tail[64 + lane], 0.f);
+    float z = fmaf(tail[RR_HID + 64 + lane], h1, tail[RR_HID + lane] * h0);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off);
+    if (lane == 0) out[o] = 1.0f / (1.0f + expf(-(z + tail[2 * RR_HID])));
+  }
+}
+
+// (S, C, N) node matrices -> (S N, C) node rows (+ pos[n][c]); 32 channels per workgroup through an LDS tile
+__global__ __launch_bounds__(256) void clf_node_rows_kernel(const float* __restrict__ x, int C, int N, const float* __restrict__ pos,
+                                                            float* __restrict__ rows) {
+  __shared__ float tile[32][RR_N + 1];
+  const int s = blockIdx.x, c0 = blockIdx.y * 32;
+  for (int i = threadIdx.x; i < 32 * N; i += 256) {
+    const int c = i / N, n = i % N;
+    tile[c][n] = x[((size_t)s * C + c0 + c) * N + n];
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 32 * N; i += 256) {
+    const int n = i / 32, c = i % 32;
+    rows[((size_t)s * N + n) * C + c0 + c] = tile[c][n] + (pos ? pos[(size_t)n * C + c0 + c] : 0.f);
+  }
+}
+
+}  // namespace
+
+extern "C" int nsid_clf_node_rows(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream) {
+  NSID_REQUIRE(S >= 0 && C > 0 && C % 32 == 0 && C <= 32 * 65535 && N >= 1 && N <= RR_N);
+  if (S == 0) return NSID_OK;
+  NSID_REQUIRE(x && rows);
+  nsid_count(NSID_C_clf_node_rows);
+  hipLaunchKernelGGL(clf_node_rows_kernel, dim3(S, C / 32), dim3(256), 0, static_cast<hipStream_t>(stream), x, C, N, pos, rows);
+  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+}
+
+extern "C" int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups,
+                                    const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
+                                    const float* tail, float* out, int64_t out_len, void* stream) {
+  NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= RR_N && ngroups >= 0 && ntiles >= 0 && out_len >= 0);
+  if (ngroups == 0 || ntiles == 0) return NSID_OK;
+  NSID_REQUIRE(q && kp && groups && out_off && tile_off && cidx && tail && out && nsid_aligned16(q) && nsid_aligned16(kp));
+  nsid_count(NSID_C_clf_pair_scores);
+  hipLaunchKernelGGL(clf_pair_kernel, dim3(ntiles), dim3(512), 0, static_cast<hipStream_t>(stream), q, nq_seg, kp, nc_seg, N, groups,
+                     out_off, tile_off, ngroups, cidx, tail, out, out_len);
+  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+}

@@ -115,3 +115,54 @@ def _to_numpy(x) -> np.ndarray:
     if hasattr(x, "detach"):
         x = x.detach().cpu().numpy()
     return np.ascontiguousarray(x, dtype=np.float32)
+
+
+# ------------------------------------------------------------------------------------------------ node matrices (classifier re-rank)
+def extract_node_matrices(model, specs, batch: int = 1024):
+    """specs (S, n_mels, n_frames) fp32 on the GPU -> (S, C, N) fp32 pre-projection node matrices of the eval-mode encoder
+    (the reference's model.encoder(p, return_pre_proj=True)[0], test_fp.py:233-236), on the HIP path"""
+    import torch
+    from . import functional, ops
+    was_training = model.training
+    model.eval()
+    if functional.ACT_DTYPE == torch.bfloat16:
+        ops.register_weight_shadows(model)
+    try:
+        pe = model.peak_extractor
+        out = []
+        with torch.no_grad():
+            for lo in range(0, specs.shape[0], batch):
+                x = specs[lo:lo + batch].contiguous()
+                B, H, W = x.shape
+                N = (H // pe.patch_bins) * (W // pe.patch_frames)
+                rows, n_last, _ = model.encoder.forward_rows(pe.forward_rows(x), B, N, return_nodes=True)
+                out.append(functional.from_rows(rows, B, n_last).float())
+        if not out:
+            return None
+        return torch.cat(out, 0)
+    finally:
+        model.train(was_training)
+
+
+def build_node_matrices(model, songs: Iterable[Tuple[str, "object"]], save_dir: str, batch: int = 1024) -> Dict[str, Tuple[int, ...]]:
+    """test_fp.py:219-248 create_ref_nmatrix: `{save_dir}/{song}.npy` = (S, C, N) float32 per song (the eval_hr / eval_map
+    ref_nmatrix directory). songs: iterable of (name, specs (S, n_mels, n_frames) on the GPU). Returns the shapes written."""
+    os.makedirs(save_dir, exist_ok=True)
+    shapes = {}
+    for nm, specs in songs:
+        m = extract_node_matrices(model, specs, batch)
+        a = _to_numpy(m)
+        np.save(os.path.join(save_dir, f"{nm}.npy"), a)
+        shapes[nm] = a.shape
+    return shapes
+
+
+def build_query_node_matrices(model, songs: Iterable[Tuple[str, "object"]], save_path: str, batch: int = 1024) -> Dict[str, Tuple[int, ...]]:
+    """test_fp.py:252-277 create_query_nmatrix: np.save of {song: (S, C, N) float32} to save_path (query_nmatrix.npy /
+    query_full_nmatrix.npy; read back with np.load(..., allow_pickle=True).item())"""
+    d = {nm: _to_numpy(extract_node_matrices(model, specs, batch)) for nm, specs in songs}
+    parent = os.path.dirname(save_path)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    np.save(save_path, d)
+    return {k: v.shape for k, v in d.items()}

@@ -1291,3 +1291,73 @@ def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:
         "nsid_seq_scores", _p(q), ldq, _p(x), ldx, nx, d, _p(I), k, _p(st), _p(ln), npairs, _p(out), ldo, _stream()),
         (npairs, ldo, d, 1))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ classifier re-rank (csrc/rerank.hip)
+CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = 512, 1024, 32, 64
+
+
+def clf_node_rows(x, pos=None) -> torch.Tensor:
+    """(S, C, N) fp32 node matrices -> (S N, C) node rows, plus pos (N, C) on every segment when given"""
+    _chk(x, pos)
+    if x.dim() != 3:
+        raise ValueError(f"clf_node_rows: expected (S, C, N) node matrices, got {tuple(x.shape)}")
+    S, C, N = x.shape
+    if C % 32 or not 1 <= N <= CLF_MAX_N:
+        raise ValueError(f"clf_node_rows: C = {C}, N = {N} outside C % 32 == 0, 1 <= N <= {CLF_MAX_N}")
+    if pos is not None and tuple(pos.shape) != (N, C):
+        raise ValueError(f"clf_node_rows: pos must be ({N}, {C}), got {tuple(pos.shape)}")
+    rows = torch.empty((S * N, C), device=x.device, dtype=torch.float32)
+    _tk("clf_node_rows_kernel", 8.0 * S * C * N, lambda: call("nsid_clf_node_rows", _p(x), S, C, N, _p(pos), _p(rows), _stream()),
+        (S, C, N, 1))
+    return rows
+
+
+def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_count):
+    """Scores of blocked pair lists on the classifier's folded form (csrc/rerank.hip).
+
+    q (nq_seg N, 512): projected query rows; kp (nc_seg N, 1024): the candidates' [K | P] rows; tail (257,): {g, w2, b2}.
+    Group i pairs query segments [q_start[i], q_start[i] + q_count[i]) with the candidate segments cand_idx[cand_off[i] :
+    cand_off[i] + cand_count[i]] (repeats allowed). Host integer sequences, checked here. Returns (out, out_off): the flat fp32
+    score tensor and, per group, the int64 offset of its row-major (q_count x cand_count) block."""
+    import numpy as np
+    _chk(q, kp, tail)
+    N = int(N)
+    if not 1 <= N <= CLF_MAX_N:
+        raise ValueError(f"clf_pair_scores: N = {N} is outside [1, {CLF_MAX_N}]")
+    if q.dim() != 2 or q.shape[1] != CLF_C or q.shape[0] % N or kp.dim() != 2 or kp.shape[1] != CLF_KP or kp.shape[0] % N:
+        raise ValueError(f"clf_pair_scores: expected q (S N, {CLF_C}) and kp (S N, {CLF_KP}), got {tuple(q.shape)}, {tuple(kp.shape)}")
+    if tail.numel() != 257:
+        raise ValueError("clf_pair_scores: tail must hold g (128), w2 (128) and b2")
+    nq_seg, nc_seg = q.shape[0] // N, kp.shape[0] // N
+    qs, qn = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (q_start, q_count))
+    co, cn = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (cand_off, cand_count))
+    ci = np.asarray(cand_idx, dtype=np.int64).reshape(-1)
+    G = qs.size
+    if not qn.size == co.size == cn.size == G:
+        raise ValueError("clf_pair_scores: q_start, q_count, cand_off and cand_count differ in length")
+    if G and (qs.min() < 0 or qn.min() < 0 or (qs + qn).max() > nq_seg or co.min() < 0 or cn.min() < 0
+              or (co + cn).max() > ci.size):
+        raise ValueError("clf_pair_scores: a group's query range or candidate list is out of range")
+    if ci.size and (ci.min() < 0 or ci.max() >= nc_seg):
+        raise ValueError(f"clf_pair_scores: candidate indices must lie in [0, {nc_seg})")
+    sizes = qn * cn
+    out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    tiles = cn * ((qn + CLF_QCHUNK - 1) // CLF_QCHUNK)
+    tile_off = np.concatenate([[0], np.cumsum(tiles)]).astype(np.int64)
+    if tile_off[-1] >= 2 ** 31 or max(nq_seg, nc_seg) * N >= 2 ** 31:
+        raise ValueError("clf_pair_scores: too many pairs for one call")
+    out = torch.empty((int(out_off[-1]),), device=q.device, dtype=torch.float32)
+    if G == 0 or tile_off[-1] == 0:
+        return out, out_off[:-1]
+    dev = q.device
+    grp = torch.from_numpy(np.stack([qs, qn, co, cn], 1).astype(np.int32).reshape(-1)).to(dev)
+    oo = torch.from_numpy(out_off[:-1].copy()).to(dev)
+    to = torch.from_numpy(tile_off.astype(np.int32)).to(dev)
+    cit = torch.from_numpy((ci if ci.size else np.zeros(1, np.int64)).astype(np.int32)).to(dev)
+    npairs = float(sizes.sum())
+    # 1.2 MFLOP per pair (Q K^T on the matrix pipe, softmax, a V, the folded tail); bytes: the scores and K / P staged per workgroup
+    _timed("clf_pair_kernel", 1.2e6 * npairs, 4.0 * npairs + 8.0 * CLF_C * N * float(tile_off[-1]),
+           lambda: call("nsid_clf_pair_scores", _p(q), nq_seg, _p(kp), nc_seg, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
+                        _p(cit), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
+    return out, out_off[:-1]

@@ -1,0 +1,138 @@
+"""Times the classifier re-rank (csrc/rerank.hip) at the evaluations' block shapes, the projection GEMMs, a torch-eager fp32
+comparison and the whole eval_map_clf on a synthetic sample100-sized emb_dir.
+
+    python tools/rerank_bench.py [--reps 5] [--quick]
+
+Pair kernel: ms (median of --reps after a warm-up), pairs/s and TFLOP/s on 1.2 MFLOP per pair, with its fraction of the fp32 matrix
+peak (155 TF, MI355X_MICROARCH). The eager comparison scores the same pairs with a batched fp32 nn.MultiheadAttention written here
+(the reference's forward: one classifier call per candidate, batched over query segments, as eval_map.py does)."""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from neuralsampleid_amd import fpdb  # noqa: E402
+from neuralsampleid_amd.classifier import CrossAttentionClassifier  # noqa: E402
+from neuralsampleid_amd.rerank import eval_map_clf  # noqa: E402
+
+PEAK_TF, FLOP_PER_PAIR = 155.0, 1.2e6
+
+
+def _median_ms(fn, reps):
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return float(np.median(ms))
+
+
+def _clf():
+    torch.manual_seed(0)
+    clf = CrossAttentionClassifier(in_dim=512, num_nodes=32).cuda().eval()
+    return clf
+
+
+class EagerClf(nn.Module):
+    """the reference's forward in torch-eager fp32 (downstream.py:59-78)"""
+
+    def __init__(self, clf):
+        super().__init__()
+        self.attn, self.fc, self.pos = clf.attn, clf.fc, clf.positional_embedding
+
+    def forward(self, x_i, x_j):
+        x_i, x_j = x_i.permute(0, 2, 1), x_j.permute(0, 2, 1)
+        pos = self.pos[:, :x_i.shape[1], :]
+        a, _ = self.attn(x_i + pos, x_j + pos, x_j + pos)
+        return self.fc(a.mean(dim=1))
+
+
+def time_block(name, sq, sc, groups, reps, eager_groups=1):
+    clf = _clf()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    q = torch.randn(groups * sq, 512, 32, device="cuda", generator=g)
+    c = torch.randn(sc * 4, 512, 32, device="cuda", generator=g)
+    with torch.no_grad():
+        qp, kp = clf.project_queries(q), clf.project_candidates(c)
+        rng = np.random.default_rng(0)
+        lists = [rng.integers(0, c.shape[0], size=sc) for _ in range(groups)]
+        args = (qp, kp, 32, np.arange(groups) * sq, [sq] * groups, np.concatenate(lists), np.arange(groups) * sc, [sc] * groups)
+        t = _median_ms(lambda: clf.score_blocks(*args), reps)
+        tq = _median_ms(lambda: clf.project_queries(q), reps)
+        tc = _median_ms(lambda: clf.project_candidates(c), reps)
+        pairs = groups * sq * sc
+        tf = FLOP_PER_PAIR * pairs / t / 1e9
+        print(f"{name}: {groups} x ({sq} x {sc}) pairs: kernel {t:9.3f} ms  {pairs / t / 1e3:8.2f} Mpairs/s  {tf:6.1f} TF/s "
+              f"({tf / PEAK_TF:5.3f} of 155)", flush=True)
+        print(f"{name}: projections: queries {groups * sq} segs {tq:7.3f} ms, candidates {c.shape[0]} segs {tc:7.3f} ms", flush=True)
+        # eager comparison: one batched classifier call per candidate (eval_map.py:146-153), over eager_groups groups, scaled
+        eager = EagerClf(clf)
+        qe = q[:sq]
+
+        def run_eager():
+            for gi in range(eager_groups):
+                for j in lists[gi].tolist():
+                    eager(qe, c[j:j + 1].expand(sq, -1, -1))
+        te = _median_ms(run_eager, max(1, reps // 2)) * groups / eager_groups
+        print(f"{name}: torch-eager fp32 (batched nn.MultiheadAttention per candidate): {te:10.1f} ms (scaled from {eager_groups} "
+              f"group(s)) -> kernel speed-up {te / t:7.1f}x", flush=True)
+
+
+def time_eval_map(n_songs, segs, n_tests, q_segs, n_dummy, k_probe=3):
+    rng = np.random.default_rng(0)
+    d, C, N = 128, 512, 32
+
+    def unit(n):
+        x = rng.standard_normal((n, d)).astype(np.float32)
+        return x / np.linalg.norm(x, axis=1, keepdims=True)
+
+    clf = _clf()
+    with tempfile.TemporaryDirectory() as tmp:
+        ref = unit(n_songs * segs)
+        names = [f"s{i}" for i in range(n_songs)]
+        fpdb.write_fp_db(tmp, "ref_db", ref, [n for n in names for _ in range(segs)])
+        fpdb.write_fp_db(tmp, "dummy_db", unit(n_dummy), ["dummy"] * n_dummy)
+        fpdb.write_node_matrices(os.path.join(tmp, "ref_nmatrix"),
+                                 {n: rng.standard_normal((segs, C, N), dtype=np.float32) for n in names})
+        qrows = unit(n_tests * q_segs)
+        fpdb.write_fp_db(tmp, "query_full_db", qrows, [f"q{i // q_segs}" for i in range(n_tests * q_segs)])
+        np.save(os.path.join(tmp, "query_full_nmatrix.npy"),
+                {f"q{i}": rng.standard_normal((q_segs, C, N), dtype=np.float32) for i in range(n_tests)})
+        gt = {n: [f"q{i}"] for i, n in enumerate(names)}
+        with torch.no_grad():
+            eval_map_clf(tmp, clf, gt, k_probe=k_probe, save=False)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            m, _ = eval_map_clf(tmp, clf, gt, k_probe=k_probe, save=False)
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+    print(f"eval_map_clf: {n_tests} tests x {q_segs} query segments, {n_songs} x {segs} ref + {n_dummy} dummy rows, k_probe "
+          f"{k_probe}: {t * 1e3:.1f} ms (MAP {float(m):.3f})", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--quick", action="store_true", help="8 MAP-like groups instead of 64, a small evaluation")
+    a = ap.parse_args()
+    time_block("map block", 350, 1024, 8 if a.quick else 64, a.reps)
+    time_block("hit-rate block", 19, 95, 64, a.reps, eager_groups=8)
+    if a.quick:
+        time_eval_map(20, 350, 10, 350, 20_000)
+    else:
+        time_eval_map(75, 350, 100, 350, 100_000)
+
+
+if __name__ == "__main__":
+    main()
