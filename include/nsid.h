@@ -380,6 +380,34 @@ int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg
                          const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail, float* out,
                          int64_t out_len, void* stream);
 
+/* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
+ * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed
+ * order and no entry uses atomics: a pair's score and its per-pair gradients depend on nothing but the pair.
+ * clf_mine_hard_negatives: out[i k + r - 1] (int64) = the index of rank r = 1..k of row i of zq (nq x d) . za^T (na x d) in
+ *   descending order, ties to the smaller index; fp32 dots, each a sequential fma chain over d. 4 <= d <= 512, d % 4 == 0,
+ *   na <= 8192, 1 <= k <= na - 1; za 16-byte aligned.
+ * clf_attn_fwd: q (nq_seg N x 512) = Q rows (x + pos) Wq^T + bq; kv (nc_seg N x 1024) = [K | V] rows. Pair p = (query segment qi[p],
+ *   candidate segment ci[p]): obar[p] (512) = concat_h a_h^T V_h with a_h = the mean over query nodes of softmax(Q_h K_h^T / sqrt(128));
+ *   attn (P x 4 x 16 x 64) = the softmax in the kernel's register layout (the backward's input); abar (P x 4 x 32) = a_h, zero
+ *   past N. The caller guarantees the lists are in range (the kernel skips, never writes, an out-of-range pair).
+ * clf_head_fwd: s[p] = sigmoid(w2 . (relu(hid[p]) keep[p]) + b2[0]); hid, keep P x 128 (keep = the dropout mask / (1 - p)).
+ * clf_head_bwd: dz[p] = ds[p] (1 - s[p]) s[p]; dh[p][j] = dz[p] w2[j] keep[p][j] where hid[p][j] > 0, else 0; dw2[j] = sum_p dz[p]
+ *   relu(hid[p][j]) keep[p][j] and db2[0] = sum_p dz[p], in a fixed order: 8 interleaved partial sums in pair order, added in
+ *   order (written, not accumulated).
+ * clf_attn_bwd: from dobar (P x 512) = dL/dobar: dq, dk (P x N x 512) = the per-pair dL/dQ and dL/dK of the query and candidate rows.
+ * clf_seg_reduce: dq_seg (nq_seg N x 512) = sum over the pairs with qi[p] == seg of dq[p]; dkv_seg (nc_seg N x 1024) = [sum dk[p] |
+ *   sum abar[p] (x) dobar[p]] over the pairs with ci[p] == seg; both in pair order, zeros for a segment without pairs. */
+int nsid_clf_mine_hard_negatives(const float* zq, int nq, const float* za, int na, int d, int k, int64_t* out, void* stream);
+int nsid_clf_attn_fwd(const float* q, int nq_seg, const float* kv, int nc_seg, int N, const int* qi, const int* ci, int P, float* obar,
+                      float* attn, float* abar, void* stream);
+int nsid_clf_head_fwd(const float* hid, const float* keep, const float* w2, const float* b2, int P, float* s, void* stream);
+int nsid_clf_head_bwd(const float* ds, const float* s, const float* hid, const float* keep, const float* w2, int P, float* dh, float* dz,
+                      float* dw2, float* db2, void* stream);
+int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int N,
+                      const int* qi, const int* ci, int P, float* dq, float* dk, void* stream);
+int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi, const int* ci, int P,
+                        int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

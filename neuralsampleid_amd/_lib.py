@@ -70,6 +70,12 @@ SIGNATURES = {
     "nsid_seq_scores": "pipiiipippipis",
     "nsid_clf_node_rows": "piiipps",
     "nsid_clf_pair_scores": "pipiipppiipppls",
+    "nsid_clf_mine_hard_negatives": "pipiiips",
+    "nsid_clf_attn_fwd": "pipiippippps",
+    "nsid_clf_head_fwd": "ppppips",
+    "nsid_clf_head_bwd": "pppppipppps",
+    "nsid_clf_attn_bwd": "pppipiippipps",
+    "nsid_clf_seg_reduce": "ppppppiiiipps",
 }
 
 class WgradProblem(ctypes.Structure):

@@ -1,4 +1,4 @@
-"""Mirror of downstream.py:30-78 CrossAttentionClassifier, scored on the MI355X (csrc/rerank.hip). Inference only.
+"""Mirror of downstream.py:30-78 CrossAttentionClassifier, scored on the MI355X (csrc/rerank.hip).
 
 Same constructor, module tree and state_dict as the reference (`positional_embedding` buffer, `attn.in_proj_*`, `attn.out_proj.*`,
 `fc.0.*`, `fc.3.*`), so a clf_*.pth written by downstream.py loads with strict=True. The forward is the reference's eval-mode forward
@@ -13,7 +13,9 @@ nsid_clf_pair_scores.
         s = clf.pair_scores(nm_query, nm_cand)        # (Sq, 512, N), (Sc, 512, N) -> (Sq, Sc)
 
 Supported: in_dim 512, 4 heads, hidden_dim 128, N <= 32 (and N <= num_nodes with pos_embed), fp32 contiguous inputs; anything else
-raises before a launch. Training (downstream.py's loop, a backward) is not implemented here."""
+raises before a launch. This module's forward stays the eval-mode re-rank path and refuses training mode and grad. Training
+(downstream.py's loop) runs through neuralsampleid_amd.downstream: clf_train_scores is the training-mode forward and backward on
+csrc/clf_train.hip, and train() / train_step() drive it; the trained state_dict loads here as it is."""
 import math
 
 import numpy as np

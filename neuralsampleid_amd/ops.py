@@ -1361,3 +1361,108 @@ def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_c
            lambda: call("nsid_clf_pair_scores", _p(q), nq_seg, _p(kp), nc_seg, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
                         _p(cit), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
     return out, out_off[:-1]
+
+
+# ------------------------------------------------------------------------------------------------ classifier training (csrc/clf_train.hip)
+CLF_HID, CLF_H, CLF_MINE_MAX_ROWS, CLF_MINE_MAX_D = 128, 4, 8192, 512
+
+
+def _clf_idx(t, name):
+    if t.dtype != torch.int32 or t.dim() != 1 or not t.is_cuda or not t.is_contiguous():
+        raise RuntimeError(f"{name}: expected a contiguous 1-D int32 device tensor")
+
+
+def clf_mine_hard_negatives(zq, za, k) -> torch.Tensor:
+    """(nq, d) x (na, d) fp32 -> (nq, k) int64: ranks 1..k of each row of zq za^T in descending order, ties to the smaller index"""
+    _chk(zq, za)
+    if zq.dim() != 2 or za.dim() != 2 or zq.shape[1] != za.shape[1]:
+        raise ValueError(f"clf_mine_hard_negatives: expected (nq, d) and (na, d), got {tuple(zq.shape)}, {tuple(za.shape)}")
+    nq, d = zq.shape
+    na, k = za.shape[0], int(k)
+    if not (4 <= d <= CLF_MINE_MAX_D and d % 4 == 0):
+        raise ValueError(f"clf_mine_hard_negatives: d = {d} is outside 4 <= d <= {CLF_MINE_MAX_D}, d % 4 == 0")
+    if not 1 <= na <= CLF_MINE_MAX_ROWS:
+        raise ValueError(f"clf_mine_hard_negatives: {na} pool rows are outside [1, {CLF_MINE_MAX_ROWS}]")
+    if not 1 <= k <= na - 1:
+        raise ValueError(f"clf_mine_hard_negatives: ranks 1..{k} need at least {k + 1} pool rows, got {na}")
+    out = torch.empty((nq, k), device=zq.device, dtype=torch.int64)
+    _timed("clf_mine_kernel", 2.0 * nq * na * d, 4.0 * (nq * d + float(nq) * na * d) + 8.0 * nq * k, lambda: call(
+        "nsid_clf_mine_hard_negatives", _p(zq), nq, _p(za), na, d, k, _p(out), _stream()), (nq, na, d, 1))
+    return out
+
+
+def clf_attn_fwd(q, kv, N, qi, ci):
+    """per pair (qi[p], ci[p]): (obar (P, 512), attn (P, 4, 16, 64), abar (P, 4, 32)); q (Sq N, 512) Q rows, kv (Sc N, 1024) [K | V]
+    rows; qi, ci int32 device lists, in range (checked by the caller)"""
+    _chk(q, kv)
+    _clf_idx(qi, "clf_attn_fwd")
+    _clf_idx(ci, "clf_attn_fwd")
+    P = qi.numel()
+    dev = q.device
+    obar = torch.empty((P, CLF_C), device=dev, dtype=torch.float32)
+    attn = torch.empty((P, CLF_H, 16, 64), device=dev, dtype=torch.float32)
+    abar = torch.empty((P, CLF_H, CLF_MAX_N), device=dev, dtype=torch.float32)
+    # 2 N^2 C (Q K^T) + 2 N C (a V) per pair; bytes: Q, K, V rows read per pair (from L2 mostly), obar, attn, abar written
+    _timed("clf_attn_fwd_kernel", float(P) * (2.0 * N * N * CLF_C + 2.0 * N * CLF_C),
+           float(P) * (12.0 * N * CLF_C + 4.0 * CLF_C + 4.0 * CLF_H * 16 * 64 + 4.0 * CLF_H * CLF_MAX_N), lambda: call(
+               "nsid_clf_attn_fwd", _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, N, _p(qi), _p(ci), P, _p(obar), _p(attn),
+               _p(abar), _stream()), (P, N, CLF_C, 1))
+    return obar, attn, abar
+
+
+def clf_head_fwd(hid, keep, w2, b2) -> torch.Tensor:
+    """(P, 128) pre-activations and keep mask -> (P,) sigmoid(w2 . (relu(hid) keep) + b2)"""
+    _chk(hid, keep, w2, b2)
+    P = hid.shape[0]
+    s = torch.empty((P,), device=hid.device, dtype=torch.float32)
+    _tk("clf_head_fwd_kernel", 8.0 * P * CLF_HID + 4.0 * P, lambda: call(
+        "nsid_clf_head_fwd", _p(hid), _p(keep), _p(w2), _p(b2), P, _p(s), _stream()), (P, CLF_HID, 1, 1))
+    return s
+
+
+def clf_head_bwd(ds, s, hid, keep, w2):
+    """-> (dH (P, 128), dz (P,), dw2 (128,), db2 (1,)), the weight gradients in pair order"""
+    _chk(ds, s, hid, keep, w2)
+    P = hid.shape[0]
+    dev = hid.device
+    dh = torch.empty((P, CLF_HID), device=dev, dtype=torch.float32)
+    dz = torch.empty((P,), device=dev, dtype=torch.float32)
+    dw2 = torch.empty((CLF_HID,), device=dev, dtype=torch.float32)
+    db2 = torch.empty((1,), device=dev, dtype=torch.float32)
+    _tk("clf_head_bwd_kernel", 20.0 * P * CLF_HID + 12.0 * P, lambda: call(
+        "nsid_clf_head_bwd", _p(ds), _p(s), _p(hid), _p(keep), _p(w2), P, _p(dh), _p(dz), _p(dw2), _p(db2), _stream()),
+        (P, CLF_HID, 1, 1))
+    return dh, dz, dw2, db2
+
+
+def clf_attn_bwd(dobar, attn, q, kv, N, qi, ci):
+    """per-pair (dQ (P, N, 512), dK (P, N, 512)) from dobar = dL/dobar and the forward's attn"""
+    _chk(dobar, attn, q, kv)
+    _clf_idx(qi, "clf_attn_bwd")
+    _clf_idx(ci, "clf_attn_bwd")
+    P = qi.numel()
+    dev = q.device
+    dq = torch.empty((P, N, CLF_C), device=dev, dtype=torch.float32)
+    dk = torch.empty((P, N, CLF_C), device=dev, dtype=torch.float32)
+    # 2 N C (da) + 2 N^2 C (dQ) + 2 N^2 C (dK) per pair on the matrix side; bytes: Q, K, V, attn read, dQ, dK written
+    _timed("clf_attn_bwd_kernel", float(P) * (4.0 * N * N * CLF_C + 2.0 * N * CLF_C),
+           float(P) * (12.0 * N * CLF_C + 4.0 * CLF_C + 4.0 * CLF_H * 16 * 64 + 8.0 * N * CLF_C), lambda: call(
+               "nsid_clf_attn_bwd", _p(dobar), _p(attn), _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, N, _p(qi), _p(ci), P,
+               _p(dq), _p(dk), _stream()), (P, N, CLF_C, 1))
+    return dq, dk
+
+
+def clf_seg_reduce(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
+    """per-segment sums in pair order: (dQ (nq_seg N, 512), [dK | dV] (nc_seg N, 1024))"""
+    _chk(dq, dk, abar, dobar)
+    _clf_idx(qi, "clf_seg_reduce")
+    _clf_idx(ci, "clf_seg_reduce")
+    P = qi.numel()
+    dev = dq.device
+    dq_seg = torch.empty((nq_seg * N, CLF_C), device=dev, dtype=torch.float32)
+    dkv_seg = torch.empty((nc_seg * N, 2 * CLF_C), device=dev, dtype=torch.float32)
+    _tk("clf_seg_reduce_kernel", float(P) * (8.0 * N * CLF_C + 4.0 * CLF_C) + 4.0 * (nq_seg + nc_seg) * (P + N * CLF_C)
+        + 4.0 * nc_seg * N * CLF_C, lambda: call(
+            "nsid_clf_seg_reduce", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, N, nq_seg, nc_seg, _p(dq_seg), _p(dkv_seg),
+            _stream()), (P, N, nq_seg + nc_seg, 1))
+    return dq_seg, dkv_seg
