@@ -11,7 +11,10 @@ x2 views -> projector -> NT-Xent (global batch) -> backward -> clip_grad_norm_(1
 the autograd tape and torch.distributed.  Per-GPU batch is fixed (weak scaling); world > 1 adds the z all-gather and
 a SUM all-reduce of the flat gradient buffer over RCCL.
 
-Prints ONE JSON line on rank 0 (fields: the driver's contract + `roofline` + `cpu_baseline`)."""
+Prints ONE JSON line on rank 0. A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints the
+headline (metric, value, unit, ms_per_step, dtype, config). --full adds what takes runs of its own: the kernel table and `roofline`
+(an instrumented step, plus live rocprofv3 child runs where rocprofv3 is installed), the other precision, `cpu_baseline` and, on a
+default run, `other_configs` (k = 5, config 4 and config 5 at their named sizes)."""
 import argparse
 import json
 import os
@@ -760,7 +763,7 @@ def run_config(args, ctx, side=False):
         elapsed = float(t)
     final_loss = float(loss_buf)
     per_step_calls = None
-    if parallel.COMM is not None:          # collectives one step enqueues (all-gather of z, loss, gradient buckets)
+    if parallel.COMM is not None and args.full:      # collectives one step enqueues (all-gather of z, loss, gradient buckets)
         c0 = parallel.COMM.calls
         step()
         parallel.sync_with_deadline(what="the collective-count step")
@@ -904,7 +907,7 @@ def run_config(args, ctx, side=False):
         }
         st = measured_step_traffic("_deep" if args.deep else "") if args.storage == "bf16" else None
         out["kernel_timing"] = ("rocprofv3 (live child run)" if (kernels and any("rocprofv3" in e.get("timing", "") for e in kernels.values()))
-                                else "hip events")
+                                else "hip events" if kernels else None)
         lt = locals().get("live_traffic")
         if lt:
             out["step_traffic_GB"] = round(lt["step_GB"], 3)
@@ -929,12 +932,8 @@ def run_config(args, ctx, side=False):
     return None
 
 
-def main():
-    try:      # past four hardware queues the step's streams share a pipe and the two view branches stop overlapping (docs/experiments.md)
-        if int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) > 4:
-            print("[bench] GPU_MAX_HW_QUEUES > 4 in the environment: expect ~2.4x the step time (measured 7.9 -> 19 ms)", file=sys.stderr)
-    except ValueError:
-        pass
+def parse_args(argv=None):
+    """the command line; a plain run (no --full) turns every measurement beyond the headline off"""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -963,13 +962,18 @@ def main():
                     help="--mode infer: concurrent hipGraph replays (one HIP stream each, the caller's stream among them, micro-batches "
                          "dealt round-robin); measured 386 k / 413 k / 403 k / 408 k clips/s with 1 / 2 / 3 / 4")
     ap.add_argument("--no-graph", action="store_true", help="do not capture the step in a hipGraph")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own after the timed steps: kernel table and roofline (with a live rocprofv3 "
+                         "profile), the other precision, the CPU baseline, the collective count of a multi-rank step and, on a default "
+                         "run, the k = 5 step and configs 4 and 5; --no-cpu-baseline / --no-roofline / --no-live-profile / --no-other leave parts "
+                         "out. Without it these are all off")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-live-profile", action="store_true",
                     help="do not re-run the eager step under rocprofv3 for the kernel table / traffic figures (HIP events and the committed "
                          "PMC summaries are used instead; also NSID_BENCH_LIVE_PROFILE=0)")
     ap.add_argument("--no-other", action="store_true",
-                    help="skip the side measurements of a default run (other precision, configs 4 and 5): A/B sweeps use this")
+                    help="with --full: skip the side measurements of a default run (other precision, configs 4 and 5)")
     ap.add_argument("--flag", action="append", default=[], metavar="MODULE.NAME=VALUE",
                     help="set a module-level switch of the host side for this run, e.g. ops.FUSE_BN_BWD_APPLY=0 (one-box A/B); "
                          "recorded in config.flags")
@@ -981,9 +985,21 @@ def main():
     ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE",
                     help="set a tuning key of the kernel library (include/nsid.h nsid_set_tuning) for this run; recorded in "
                          "config.tuning. The library never reads the environment.")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:        # a plain run: the headline line alone
+        args.no_cpu_baseline = args.no_roofline = args.no_live_profile = args.no_other = True
+    return args
+
+
+def main():
+    try:      # past four hardware queues the step's streams share a pipe and the two view branches stop overlapping (docs/experiments.md)
+        if int(os.environ.get("GPU_MAX_HW_QUEUES", "4")) > 4:
+            print("[bench] GPU_MAX_HW_QUEUES > 4 in the environment: expect ~2.4x the step time (measured 7.9 -> 19 ms)", file=sys.stderr)
+    except ValueError:
+        pass
+    args = parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
 

@@ -121,3 +121,16 @@ def test_dump_outputs_writes_float_arrays_and_samples_large_ones_the_same_way(tm
     for k in arrays:
         assert np.array_equal(a[k], b[k])
     assert sum(v.nbytes for v in a.values()) <= 64 << 20
+
+
+def test_a_plain_run_measures_the_headline_alone_and_full_keeps_the_rest():
+    """`bench.py --steps N --warmup W` turns every measurement beyond the headline off (kernel table, roofline, live profile, other
+    precision and configurations, CPU baseline); --full turns them back on, and the --no-* switches still leave parts of it out"""
+    off = ("no_cpu_baseline", "no_roofline", "no_live_profile", "no_other")
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and all(getattr(plain, k) for k in off)
+    assert (plain.steps, plain.warmup, plain.gpus, plain.dump_outputs) == (20, 5, 1, None)
+    full = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"])
+    assert full.full and not any(getattr(full, k) for k in off)
+    part = bench.parse_args(["--full", "--no-other", "--no-live-profile"])
+    assert part.no_other and part.no_live_profile and not part.no_roofline and not part.no_cpu_baseline

@@ -34,6 +34,6 @@ for mode in $modes; do
   fi
   rm -rf $out/stats$tag
   [ $mode = infer ] && flags="--mode infer"
-  python3 bench.py --no-other $flags > $out/bench$tag.json 2> $out/bench$tag.log
+  python3 bench.py --full --no-other $flags > $out/bench$tag.json 2> $out/bench$tag.log
   tail -c 400 $out/bench$tag.json; echo
 done
