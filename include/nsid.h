@@ -272,6 +272,26 @@ int nsid_pack_ds_weight_bwd(const float* w, int Cout, int Cin, float* w_odd, voi
 int nsid_im2col3_fwd(const void* x, int B, int N, int C, void* col, int dtype, void* stream);
 int nsid_im2col3_bwd(const void* dcol, int B, int N, int C, void* dx, int dtype, void* stream);
 int nsid_pack_ds_weight(const float* w, int Cout, int Cin, float* wp, void* stream);
+/* ---- Downsample chain of the DGL-variant encoder (encoder/dgl/graph_encoder.py :8-31): Conv1d k3 s2 p1 + BatchNorm1d + ReLU, -----
+ * three in a row behind the stem. w is the Conv1d weight (Cout, C, 3) as stored, fp32; x / out / dout / dx / r_prev share act_dtype;
+ * No = (N - 1) / 2 + 1. The conv reads a zero-padded strided view of its ACTIVATED input (no im2col); padding stays exactly 0.
+ *   dsact_fwd       : out[b*No+n][o] = bias[o] + sum_{t,c} w[o][c][t] act_in(in_scale[c] x[b*N+2n-1+t][c] + in_shift[c]) (in_scale
+ *                     NULL: no affine); then either stat (2, nsid_row_tiles(B*No), Cout) = per-128-row-tile column sums / sums of
+ *                     squares of the stored values (training BatchNorm, may be NULL), or out = act_out(out_scale * out + out_shift)
+ *                     (eval-mode BatchNorm folded into the epilogue; out_scale NULL: none). C % 16 == 0. No atomics.
+ *   dsact_bwd_weight: dw[o][c][t] += sum_m dout[m][o] act_in(in_scale x + in_shift)[view] (fp32 atomics over row splits).
+ *   dsact_bwd_data  : dx[b*N+p][c] = (sum over the taps that read row p of dout . w) * act'(scale r_prev + shift) (r_prev NULL: no
+ *                     factor); with partial (2, nsid_dsact_part_rows(B, N), C) also the column sums of g and g * (r_prev - mean) *
+ *                     invstd over fixed row tiles: the input of nsid_bn_bwd_finalize for r_prev's BatchNorm. Cout % 16 == 0. */
+int nsid_dsact_fwd(const void* x, int B, int N, int C, const float* in_scale, const float* in_shift, int act_in, const float* w,
+                   const float* bias, void* out, int Cout, float* stat, const float* out_scale, const float* out_shift, int act_out,
+                   int act_dtype, void* stream);
+int nsid_dsact_bwd_weight(const void* dout, const void* x, const float* in_scale, const float* in_shift, int act_in,
+                          float* dw /* += */, int B, int N, int C, int Cout, int act_dtype, void* stream);
+int nsid_dsact_bwd_data(const void* dout, const float* w, void* dx, int B, int N, int C, int Cout, const void* r_prev,
+                        const float* scale, const float* shift, const float* mean, const float* invstd, int act, float* partial,
+                        int act_dtype, void* stream);
+int nsid_dsact_part_rows(int B, int N);
 /* All Downsample layers of a model at once (n <= 8; the pointer arrays live in host memory), once per training step instead of per layer
  * and view: nsid_ds_prepack writes the packed forward weight (Cout, 3*Cin) and the packed backward weight [W_2 ; W_0] (2*Cout, Cin) of
  * every layer straight to bf16 and zeroes its packed gradient buffers dwp (TWO of them, contiguous: (2, Cout, 3*Cin) fp32, one per view of a

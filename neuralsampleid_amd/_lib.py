@@ -38,6 +38,9 @@ SIGNATURES = {
     "nsid_im2col3_fwd": "piiipis",
     "nsid_im2col3_bwd": "piiipis",
     "nsid_pack_ds_weight": "piips",
+    "nsid_dsact_fwd": "piiippipppipppiis",
+    "nsid_dsact_bwd_weight": "ppppipiiiiis",
+    "nsid_dsact_bwd_data": "pppiiiipppppipis",
     "nsid_pack_ds_weight_bwd": "piips",
     "nsid_downsample3_fwd": "piiipippipis",
     "nsid_downsample3_bwd_weight": "pppiiiiis",
@@ -142,6 +145,8 @@ def _load():
     lib.nsid_mrconv_fused_fwd.restype = ctypes.c_int
     lib.nsid_row_tiles.argtypes = [ctypes.c_int]
     lib.nsid_row_tiles.restype = ctypes.c_int
+    lib.nsid_dsact_part_rows.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.nsid_dsact_part_rows.restype = ctypes.c_int
     lib.nsid_sumsq_blocks.argtypes = [ctypes.c_long]
     lib.nsid_sumsq_blocks.restype = ctypes.c_int
     lib.nsid_ntxent_ws_floats.argtypes = [ctypes.c_int]
@@ -150,7 +155,7 @@ def _load():
 
 
 lib = _load()
-EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_workspace_bytes"]
+EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_workspace_bytes"]
 
 _ERR = {-1: "NSID_EINVAL (unsupported shape, misaligned pointer or bad argument)",
         -2: "NSID_ELAUNCH (HIP runtime refused the launch)"}

@@ -8,6 +8,8 @@ from typing import Dict, Mapping
 import torch
 
 DATA_PARALLEL_PREFIX = "module."
+# stem width -> encoder size (the size tables of encoder/graph_encoder.py:113-128 and encoder/dgl/graph_encoder.py:72-83)
+_SIZE_BY_STEM = {64: "t", 80: "s", 96: "m", 128: "b"}
 
 
 def strip_data_parallel_prefix(state_dict: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -46,6 +48,14 @@ def load_reference_checkpoint(model: torch.nn.Module, path_or_dict, strict: bool
     reference's loss and hit-rate logs contain. `trusted=True` is the caller's statement that the file is local and theirs: only
     then does a file the restricted unpickler rejects get the unrestricted `torch.load` the reference itself uses
     (util.py:149-158, generate.py:88-97) — which executes whatever the pickle says. Never set it for a downloaded file."""
+    ckpt = read_reference_checkpoint(path_or_dict, map_location, trusted)
+    sd = ckpt["state_dict"] if "state_dict" in ckpt and isinstance(ckpt["state_dict"], Mapping) else ckpt
+    model.load_state_dict(strip_data_parallel_prefix(sd), strict=strict)
+    return ckpt if sd is not ckpt else {"state_dict": sd}
+
+
+def read_reference_checkpoint(path_or_dict, map_location="cpu", trusted: bool = False) -> Mapping:
+    """the checkpoint as load_reference_checkpoint reads it (same unpickler rules), not yet loaded into a model"""
     ckpt = path_or_dict
     if not isinstance(ckpt, Mapping):
         import pickle
@@ -59,9 +69,40 @@ def load_reference_checkpoint(model: torch.nn.Module, path_or_dict, strict: bool
                     "(e.g. a checkpoint the reference's train.py wrote on this machine), pass trusted=True to "
                     "load_reference_checkpoint; that runs an unrestricted pickle load, which can execute arbitrary code.") from safe_err
             ckpt = torch.load(path_or_dict, map_location=map_location, weights_only=False)
-    sd = ckpt["state_dict"] if "state_dict" in ckpt and isinstance(ckpt["state_dict"], Mapping) else ckpt
-    model.load_state_dict(strip_data_parallel_prefix(sd), strict=strict)
-    return ckpt if sd is not ckpt else {"state_dict": sd}
+    return ckpt
+
+
+def encoder_variant(state_dict: Mapping[str, torch.Tensor]) -> str:
+    """'dgl' for the module tree of encoder/dgl/graph_encoder.py (Conv1d Downsample weights (C', C, 3)), 'gcn_lib' for the one of
+    encoder/graph_encoder.py (Conv2d Downsample weights (C', C, 3, 3)); keys with or without the DataParallel prefix"""
+    import re
+    sd = strip_data_parallel_prefix(state_dict)
+    dims = {tuple(v.shape[2:]) for k, v in sd.items() if re.fullmatch(r"encoder\.backbone\.\d+\.conv\.0\.weight", k)}
+    if dims == {(3,)}:
+        return "dgl"
+    if dims == {(3, 3)}:
+        return "gcn_lib"
+    raise KeyError("not a SimCLR(GraphEncoder) / SimCLR(GraphEncoderDGL) state_dict: no Downsample weights "
+                   "encoder.backbone.<i>.conv.0.weight of one kind")
+
+
+def simclr_for_checkpoint(cfg: dict, path_or_dict, k: int = 3, map_location="cpu", trusted: bool = False, **encoder_kw):
+    """The SimCLR model a reference checkpoint was saved from, its weights loaded strictly. The encoder class comes from the key set
+    (encoder_variant: PassthroughGraphEncoderDGL for the DGL tree, GraphEncoder for the gcn_lib one), the size and the input / output
+    widths from the stem and proj shapes. k leaves no trace in the weights: pass the value the model was trained with."""
+    from .encoder.dgl.passthrough import PassthroughGraphEncoderDGL
+    from .encoder.graph_encoder import GraphEncoder
+    from .simclr.simclr import SimCLR
+    ckpt = read_reference_checkpoint(path_or_dict, map_location, trusted)
+    sd = strip_data_parallel_prefix(ckpt["state_dict"] if "state_dict" in ckpt and isinstance(ckpt["state_dict"], Mapping) else ckpt)
+    stem = sd["encoder.stem.0.weight"]
+    kw = dict(size=_SIZE_BY_STEM.get(int(stem.shape[0]), "b"), in_channels=int(stem.shape[1]),
+              emb_dims=int(sd["encoder.proj.weight"].shape[0]))
+    kw.update(encoder_kw)
+    cls = PassthroughGraphEncoderDGL if encoder_variant(sd) == "dgl" else GraphEncoder
+    model = SimCLR(cfg, cls(cfg, k=k, **kw))
+    model.load_state_dict(sd, strict=True)
+    return model
 
 
 def save_reference_checkpoint(path, model: torch.nn.Module, epoch: int = 0, loss=None, optimizer=None, scheduler=None,

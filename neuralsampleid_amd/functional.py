@@ -591,6 +591,66 @@ def downsample_backward(dout: Tensor, P, S, G) -> Tensor:
     return ops.im2col3_bwd(dcol, B, N, C)
 
 
+# ------------------------------------------------------------------------------------------------ DGL-variant live network
+# encoder/dgl/graph_encoder.py: every graph block returns its input unchanged (reference :149-160), so what reaches the output is
+# the stem (1x1 conv without bias, BatchNorm2d, LeakyReLU 0.2) and DGL_DOWNSAMPLES Downsample layers (Conv1d k3 s2 p1 + bias,
+# BatchNorm1d, ReLU). P keys: "stem.*" and "ds<l>.conv.*" (encoder.dgl.passthrough builds them). Each layer keeps its raw conv
+# output; the next Downsample applies its BatchNorm + activation on the operand load (ops.dsact_fwd). Weight gradients are
+# computed in the chain's own backward (never deferred).
+DGL_DOWNSAMPLES = 3
+
+
+def dgl_chain_forward(nodes: Tensor, P, S: Optional[dict], B: int, N: int, training: bool) -> Tensor:
+    """nodes (B*N, in_channels) -> the last Downsample's activated output (B*N_last, C_last)"""
+    if S is not None and not training:
+        raise NotImplementedError("backward through the eval-mode DGL passthrough encoder is not implemented: run it under "
+                                  "torch.no_grad() in eval mode, or train() it")
+    M, K = nodes.shape
+    C = P["stem.0.weight"].shape[0]
+    r, aff = conv_bn(nodes, M, K, C, P["stem.0.weight"], None, _bn(P, S, "stem.1."), training)
+    layers = [(r, aff, ACT_LEAKY, N, C)]          # (raw output, its BatchNorm, its activation, node count, channels) per layer
+    act = ACT_LEAKY
+    for l_ in range(DGL_DOWNSAMPLES):
+        pre = f"ds{l_}.conv."
+        w = P[pre + "0.weight"]
+        Co, No = w.shape[0], ops.ds_out_nodes(N)
+        gamma, beta, rm, rv, nbt, _ = _bn(P, S, pre + "1.")
+        if training:
+            r, stat = ops.dsact_fwd(r, B, N, C, w, P[pre + "0.bias"], Co, aff, act, want_stat=True)
+            aff = bn_affine_from(stat, B * No, gamma, beta, rm, rv, nbt, True)
+        else:     # eval-mode BatchNorm + ReLU in the epilogue: the next layer reads activated values
+            r, _ = ops.dsact_fwd(r, B, N, C, w, P[pre + "0.bias"], Co, aff, act,
+                                 out_aff=ops.bn_eval_affine(gamma, beta, rm, rv), act_out=ACT_RELU)
+            aff = None
+        act, N, C = (ACT_RELU if training else ACT_NONE), No, Co
+        layers.append((r, aff, act, N, C))
+    if not training:
+        return r
+    out = ops.bn_apply(r, aff, ACT_RELU)
+    if S is not None:
+        S.update(nodes=nodes, layers=layers, B=B)
+    return out
+
+
+def dgl_chain_backward(dout: Tensor, P, S, G) -> Tensor:
+    layers, B, nodes = S["layers"], S["B"], S["nodes"]
+    last = f"ds{DGL_DOWNSAMPLES - 1}.conv.1."
+    dr = ops.bn_backward(dout, layers[-1][0], layers[-1][1], ACT_RELU, G[last + "weight"], G[last + "bias"])
+    for l_ in reversed(range(DGL_DOWNSAMPLES)):
+        pre = f"ds{l_}.conv."
+        r, aff, act, N, C = layers[l_]             # the input of Downsample l_: the previous layer's raw output
+        Co = dr.shape[1]
+        _bias_grad_before_bn(dr, G[pre + "0.bias"])
+        ops.dsact_bwd_weight(dr, r, G[pre + "0.weight"], B, N, C, Co, aff, act)
+        g, part = ops.dsact_bwd_data(dr, P[pre + "0.weight"], B, N, C, Co, r, aff, act, want_partial=True)
+        bn = "stem.1." if l_ == 0 else f"ds{l_ - 1}.conv.1."
+        dr = ops.bn_backward(g, r, aff, ACT_NONE, G[bn + "weight"], G[bn + "bias"], inplace=True, partial=part)
+    M, K = nodes.shape
+    C = dr.shape[1]
+    ops.linear_bwd_weight(dr, nodes, ops.w2d(G["stem.0.weight"]), M, C, K)
+    return ops.linear_bwd_data(dr, ops.w2d(P["stem.0.weight"]), M, C, K)
+
+
 # ------------------------------------------------------------------------------------------------ proj + node mean
 HEAD_FC1_KSPLIT = 1     # reduction split of the projector's first linear: measured 2 / 4 against 1: 7.787 / 7.787 against 7.773 ms (x3): off
 HEAD_KSPLIT = True      # split the 512-deep reduction of the B-row projection GEMM (one-box A/B: docs/experiments.md, round 5)

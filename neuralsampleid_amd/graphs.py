@@ -26,6 +26,10 @@ class GraphedTrainStep:
                  loss_fn: Optional[Callable] = None, reducer=None, warmup: int = 2, capture_error_mode: str = "global"):
         if not hasattr(optimizer, "flat_g"):
             raise TypeError("GraphedTrainStep needs optim.FusedClipAdam (device-side lr / step / NaN-batch skip)")
+        from .encoder.dgl.passthrough import PassthroughGraphEncoderDGL
+        if isinstance(getattr(model, "encoder", None), PassthroughGraphEncoderDGL):
+            raise NotImplementedError("GraphedTrainStep does not capture the DGL passthrough encoder's training step: train it eagerly "
+                                      "(model(x_i, x_j), ntxent_loss, backward, optimiser step)")
         self.model, self.opt, self.cfg, self.reducer = model, optimizer, cfg, reducer
         self.loss_fn = loss_fn or parallel.dist_ntxent_loss
         self.x_i, self.x_j = x_i.clone(), x_j.clone()

@@ -1035,6 +1035,57 @@ def unpack_ds_wgrad(dwp, dw) -> None:
     call("nsid_unpack_ds_wgrad", _p(dwp), dw.shape[0], dw.shape[1], _p(dw), _stream())
 
 
+# ------------------------------------------------------------------------------------------------ DGL-variant Downsample chain
+# Conv1d(k = 3, stride 2, pad 1) with the BatchNorm + activation of the layer in front applied on the operand load (csrc/dsact.hip).
+# w: the Conv1d weight (Cout, C, 3) as stored, fp32. x / r_prev: that layer's raw conv output rows (B*N, C).
+def dsact_fwd(x, B, N, C, w, bias, Cout, in_aff: Optional["BNAffine"] = None, act_in=ACT_NONE, want_stat=False,
+              out_aff: Optional["BNAffine"] = None, act_out=ACT_NONE):
+    """-> (out (B*No, Cout), stat (2, row_tiles(B*No), Cout) or None). out_aff: the eval-mode BatchNorm of THIS layer, applied with
+    act_out in the epilogue (out is then the activated output)"""
+    dt = _act(x)
+    _chk(w, bias, *((in_aff.scale, in_aff.shift) if in_aff is not None else ()),
+         *((out_aff.scale, out_aff.shift) if out_aff is not None else ()))
+    No = ds_out_nodes(N)
+    M = B * No
+    out = torch.empty((M, Cout), device=x.device, dtype=x.dtype)
+    stat = torch.empty((2, row_tiles(M), Cout), device=x.device, dtype=torch.float32) if want_stat else None
+    _timed("dsact_fwd_kernel", 2.0 * M * Cout * 3 * C, float(x.element_size()) * (B * N * C + M * Cout), lambda: call(
+        "nsid_dsact_fwd", _p(x), B, N, C, _p(in_aff.scale) if in_aff else None, _p(in_aff.shift) if in_aff else None, act_in,
+        _p(w), _p(bias), _p(out), Cout, _p(stat), _p(out_aff.scale) if out_aff else None, _p(out_aff.shift) if out_aff else None,
+        act_out, dt, _stream()), (M, Cout, 3 * C, 1))
+    return out, stat
+
+
+def dsact_bwd_weight(dout, x, dw, B, N, C, Cout, in_aff: Optional["BNAffine"] = None, act_in=ACT_NONE) -> None:
+    """dw (Cout, C, 3) += dout^T . col(act_in(in_aff(x)))"""
+    dt = _act(dout, x)
+    _chk(dw, *((in_aff.scale, in_aff.shift) if in_aff is not None else ()))
+    M = dout.shape[0]
+    _timed("dsact_wgrad_kernel", 2.0 * M * Cout * 3 * C, float(x.element_size()) * (B * N * C + M * Cout), lambda: call(
+        "nsid_dsact_bwd_weight", _p(dout), _p(x), _p(in_aff.scale) if in_aff else None, _p(in_aff.shift) if in_aff else None,
+        act_in, _p(dw), B, N, C, Cout, dt, _stream()), (Cout, 3 * C, M, 1))
+
+
+def dsact_bwd_data(dout, w, B, N, C, Cout, r_prev=None, aff: Optional["BNAffine"] = None, act=ACT_NONE, want_partial=False):
+    """-> (g (B*N, C), partial or None): g = (conv-transpose of dout) * act'(aff(r_prev)), i.e. the gradient w.r.t. the pre-activation
+    of the layer in front; partial (2, rows, C): that layer's BatchNorm-backward column sums (bn_backward(g, ..., ACT_NONE, partial=))"""
+    dt = _act(dout, r_prev)
+    _chk(w)
+    if r_prev is not None:
+        _chk(aff.scale, aff.shift)
+    if want_partial:
+        _chk(aff.mean, aff.invstd)
+    dx = torch.empty((B * N, C), device=dout.device, dtype=dout.dtype)
+    partial = torch.empty((2, int(lib.nsid_dsact_part_rows(B, N)), C), device=dout.device, dtype=torch.float32) \
+        if want_partial else None
+    M = dout.shape[0]
+    _timed("dsact_dgrad_kernel", 2.0 * M * Cout * 3 * C, float(dout.element_size()) * (M * Cout + 2 * B * N * C), lambda: call(
+        "nsid_dsact_bwd_data", _p(dout), _p(w), _p(dx), B, N, C, Cout, _p(r_prev), _p(aff.scale) if aff else None,
+        _p(aff.shift) if aff else None, _p(aff.mean) if want_partial else None, _p(aff.invstd) if want_partial else None, act,
+        _p(partial), dt, _stream()), (B * N, C, 3 * Cout, 1))
+    return dx, partial
+
+
 # ------------------------------------------------------------------------------------------------ peak extractor
 def peak_patchify_fwd(spec, w, bias, pb, pf, out_dtype=torch.float32):
     _chk(spec, w, bias)

@@ -5,6 +5,7 @@ import torch.nn as nn
 from .. import functional as F_
 from .. import ops
 from ..encoder.gcn_lib.torch_vertex import _split
+from ..encoder.dgl.passthrough import PassthroughGraphEncoderDGL
 from ..encoder.graph_encoder import GraphEncoder
 from ..peak_extractor import GPUPeakExtractorv2
 
@@ -28,7 +29,7 @@ class SimCLR(nn.Module):
         return F_.run_block(F_.projector_forward, F_.projector_backward, params, buffers, h)
 
     def _embed(self, x):
-        if isinstance(self.encoder, GraphEncoder):      # node-major all the way: no layout round trip
+        if isinstance(self.encoder, (GraphEncoder, PassthroughGraphEncoderDGL)):      # node-major all the way: no layout round trip
             B, H, W = x.shape
             N = (H // self.peak_extractor.patch_bins) * (W // self.peak_extractor.patch_frames)
             h = self.encoder.forward_rows(self.peak_extractor.forward_rows(x), B, N)
