@@ -333,6 +333,16 @@ int nsid_reflect_pad(const float* x, long L, int pad, float* out, void* stream);
 int nsid_power_mel_db(const float* spec, long ld, int n_freq, const float* fb, const int* band, int n_mels, int T,
                       float* out, void* stream);
 int nsid_unfold_segments(const float* logmel, int n_mels, int T, int n_frames, int step, int S, float* out, void* stream);
+/* the same waveform -> log-mel map for a BATCH of clips in ONE launch, with a real FFT instead of the DFT GEMM (csrc/frontend.hip;
+ * train.py:58 `augment` = GPUTransformSampleID(train=True), and with B = 1 the evaluation branch): wave (B, L) with clip stride
+ * in_stride -> out[b*out_clip_stride + m*out_mel_stride + t], m < n_mels, t < T = 1 + L/hop. Reflection by index arithmetic,
+ * frames, spectrum and power stay in LDS and registers; no workspace, no atomics (clip b of a batch is bit-equal to the clip alone).
+ * window: n_fft floats (periodic Hann for the reference); twiddle: n_fft (cos, sin) pairs of -2 pi j / n_fft evaluated in fp64,
+ * 8-byte aligned; fb / band as nsid_power_mel_db takes them. n_fft == 1024 (win_length == n_fft), 1 <= hop <= n_fft,
+ * L > n_fft/2 (torch's reflect pad raises below that); anything else is NSID_EINVAL before any launch. */
+int nsid_logmel_fft(const float* wave, long in_stride, int B, long L, int n_fft, int hop, const float* window,
+                    const float* twiddle, const float* fb, const int* band, int n_mels, float* out, long out_clip_stride,
+                    long out_mel_stride, void* stream);
 
 /* bf16 shadow of fp32 weights: dst[i] = bf16_rne(src[i]), n % 8 == 0, both 16-byte aligned (operand `w` of
  * nsid_linear_fwd / nsid_linear_bwd_data with w_dtype = NSID_BF16). */

@@ -8,7 +8,12 @@ Mirrors the evaluation branch of the reference's GPUTransformSampleID (modules/t
 
 MI355X form: the STFT is one exact-fp32 MFMA GEMM — frames are overlapping rows of the reflect-padded waveform (row stride
 = hop, no frame matrix is materialised) against the constant matrix [hann*cos ; -hann*sin] — followed by a per-frame
-power/mel/dB kernel and the segment gather (csrc/misc.hip). Everything is stream-ordered; no host sync."""
+power/mel/dB kernel and the segment gather (csrc/misc.hip). Everything is stream-ordered; no host sync.
+
+stft="fft" takes the fused kernel instead (csrc/frontend.hip, nsid_logmel_fft): reflection by index arithmetic, a real FFT in
+LDS and registers, power, mel sums and dB in one launch for a whole batch of clips — `batch(waves)`, the `augment` of the
+reference's train.py:58 (GPUTransformSampleID(train=True)); `logmel()` and `__call__` go through it with B = 1. The default
+stays "gemm": the two modes differ by fp32 rounding, which stored fingerprints would see."""
 import math
 
 import torch
@@ -35,17 +40,27 @@ def mel_filterbank(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample
 class LogMelFrontEnd:
     """front = LogMelFrontEnd(cfg, device); segs = front(wave)  — wave (L,) fp32 on the GPU, segs (S, n_mels, n_frames)."""
 
-    def __init__(self, cfg: dict, device="cuda"):
+    def __init__(self, cfg: dict, device="cuda", stft: str = "gemm"):
+        if stft not in ("gemm", "fft"):
+            raise ValueError(f"stft must be 'gemm' or 'fft', got {stft!r}")
+        self.stft = stft
         self.fs, self.n_fft, self.hop = int(cfg["fs"]), int(cfg["n_fft"]), int(cfg["hop_len"])
         self.win = int(cfg.get("win_len", self.n_fft))
         self.n_mels, self.n_frames = int(cfg["n_mels"]), int(cfg["n_frames"])
         self.step = int(self.n_frames * (1 - float(cfg["overlap"])))          # transformations.py:102
         if self.win != self.n_fft:
             raise NotImplementedError("win_length != n_fft (the reference config uses 1024/1024)")
-        if self.n_fft % 4 or self.hop % 4:
+        if stft == "gemm" and (self.n_fft % 4 or self.hop % 4):
             raise NotImplementedError("n_fft and hop_len must be multiples of 4 (16-byte rows of the framing GEMM)")
+        if stft == "fft" and (self.n_fft != 1024 or not 1 <= self.hop <= self.n_fft):
+            raise NotImplementedError("stft='fft' is built for n_fft = 1024 with 1 <= hop_len <= n_fft (csrc/frontend.hip)")
         self.n_freq = self.n_fft // 2 + 1
         self.device = torch.device(device)
+        # tables of the fused kernel, evaluated in fp64: the periodic Hann window and the twiddles e^(-2 pi i j / n_fft)
+        j = torch.arange(self.n_fft, dtype=torch.float64)
+        self.window = torch.hann_window(self.n_fft, periodic=True, dtype=torch.float64).to(torch.float32).to(self.device)
+        ang = -2.0 * math.pi * j / self.n_fft
+        self.twiddle = torch.stack((torch.cos(ang), torch.sin(ang)), 1).to(torch.float32).contiguous().to(self.device)
         # DFT matrix with the periodic Hann window folded in, built in fp64: rows [0, n_freq) = w*cos, then -w*sin
         n = torch.arange(self.n_fft, dtype=torch.float64)
         k = torch.arange(self.n_freq, dtype=torch.float64).unsqueeze(1)
@@ -56,7 +71,7 @@ class LogMelFrontEnd:
         W = torch.zeros(self.ld, self.n_fft, dtype=torch.float64)
         W[:self.n_freq] = win * torch.cos(ang)
         W[self.n_freq:rows] = -win * torch.sin(ang)
-        self.W = W.to(torch.float32).to(self.device).contiguous()
+        self.W = W.to(torch.float32).to(self.device).contiguous() if stft == "gemm" else None     # 4 MB the fused kernel never reads
         fb = mel_filterbank(self.n_freq, 0.0, float(self.fs // 2), self.n_mels, self.fs).t().contiguous()   # (n_mels, n_freq)
         nz = fb > 0
         lo = torch.where(nz.any(1), nz.float().argmax(1), torch.zeros(self.n_mels, dtype=torch.long))
@@ -67,10 +82,18 @@ class LogMelFrontEnd:
     def n_frames_of(self, L: int) -> int:
         return 1 + L // self.hop                                             # torch.stft, center=True
 
+    def batch(self, waves: torch.Tensor) -> torch.Tensor:
+        """(B, L) fp32 on the GPU -> (B, n_mels, T) dB in one launch of the fused kernel, whatever `stft` says for the
+        single-waveform calls; stream-ordered, no allocation besides the result, capture-safe. Clip b of the result is
+        bit-equal to the same clip in a call of its own."""
+        return ops.logmel_fft(waves, self.n_fft, self.hop, self.window, self.twiddle, self.fb, self.band)
+
     def logmel(self, wave: torch.Tensor) -> torch.Tensor:
         """(L,) fp32 on the GPU -> (n_mels, T) dB"""
         if wave.dim() != 1 or not wave.is_cuda or wave.dtype != torch.float32:
             raise RuntimeError("the front end takes one mono fp32 waveform on the MI355X device")
+        if self.stft == "fft":
+            return self.batch(wave.contiguous().unsqueeze(0))[0]
         wave = wave.contiguous()
         L, pad = wave.numel(), self.n_fft // 2
         T = self.n_frames_of(L)

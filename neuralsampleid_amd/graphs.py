@@ -1,6 +1,8 @@
 """Whole-step hipGraph capture for training: the contrastive step is ~1 000 kernel launches of 5-40 us each, so an eager
 Python loop is host-bound (~80 ms/step against ~9 ms of GPU work at batch 256). `GraphedTrainStep` captures
 zero_grad -> forward (two views) -> NT-Xent -> backward -> [gradient all-reduce] -> clip + Adam once and replays it.
+With a front end (`front=`) the step starts from waveforms: the log-mel launch of each view (train.py:58 `augment`) is
+captured in front of it, so the whole train.py:53-75 iteration from audio is one replay.
 
 Everything inside the step is capture-safe by construction: the kernels never allocate or synchronise, the optimiser's
 learning rate / step counter / NaN-batch skip live on the device (optim.FusedClipAdam), and the data-parallel collectives
@@ -23,7 +25,8 @@ class GraphedTrainStep:
     eager loop (tests/test_e2e_gpu.py::test_graphed_train_step_equals_eager)."""
 
     def __init__(self, model, optimizer, cfg: dict, x_i: torch.Tensor, x_j: torch.Tensor,
-                 loss_fn: Optional[Callable] = None, reducer=None, warmup: int = 2, capture_error_mode: str = "global"):
+                 loss_fn: Optional[Callable] = None, reducer=None, warmup: int = 2, capture_error_mode: str = "global",
+                 front=None):
         if not hasattr(optimizer, "flat_g"):
             raise TypeError("GraphedTrainStep needs optim.FusedClipAdam (device-side lr / step / NaN-batch skip)")
         from .encoder.dgl.passthrough import PassthroughGraphEncoderDGL
@@ -31,6 +34,7 @@ class GraphedTrainStep:
             raise NotImplementedError("GraphedTrainStep does not capture the DGL passthrough encoder's training step: train it eagerly "
                                       "(model(x_i, x_j), ntxent_loss, backward, optimiser step)")
         self.model, self.opt, self.cfg, self.reducer = model, optimizer, cfg, reducer
+        self.front = front                       # frontend.LogMelFrontEnd: x_i / x_j are (B, L) waveforms, not mels
         self.loss_fn = loss_fn or parallel.dist_ntxent_loss
         self.x_i, self.x_j = x_i.clone(), x_j.clone()
         self.loss = torch.zeros((), device=x_i.device)
@@ -74,7 +78,11 @@ class GraphedTrainStep:
             side = getattr(self.model, "_side_stream", None)
             if side is not None:
                 self.reducer.streams = [torch.cuda.current_stream(), side]
-        _, _, z_i, z_j = self.model(self.x_i, self.x_j)
+        x_i, x_j = self.x_i, self.x_j
+        if self.front is not None:
+            with torch.no_grad():                # train.py:58-59
+                x_i, x_j = self.front.batch(x_i), self.front.batch(x_j)
+        _, _, z_i, z_j = self.model(x_i, x_j)
         loss = self.loss_fn(z_i, z_j, self.cfg)
         loss.backward()
         if self.reducer is not None:

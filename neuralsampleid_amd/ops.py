@@ -1202,6 +1202,24 @@ def scale_f32(x: torch.Tensor, scale: Optional[torch.Tensor] = None, out: Option
     return out
 
 
+def logmel_fft(waves: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, twiddle: torch.Tensor, fb: torch.Tensor,
+               band: torch.Tensor) -> torch.Tensor:
+    """waves (B, L) fp32 (last dimension contiguous, any clip stride) -> log-mel dB (B, n_mels, 1 + L // hop) in ONE launch
+    (nsid_logmel_fft, csrc/frontend.hip): reflect framing, real FFT, power, mel sums and dB without a temporary in HBM.
+    window (n_fft,), twiddle (n_fft, 2) = (cos, sin)(-2 pi j / n_fft) from fp64, fb (n_mels, n_fft/2+1), band (n_mels, 2) int32"""
+    _chk(window, twiddle, fb)
+    if waves.dim() != 2 or not waves.is_cuda or waves.dtype != torch.float32 or waves.stride(1) != 1:
+        raise RuntimeError("logmel_fft takes (B, L) float32 waveforms on the MI355X device with a contiguous last dimension")
+    B, L = waves.shape
+    if L <= n_fft // 2:
+        raise RuntimeError(f"waveforms of {L} samples are too short for reflect padding by n_fft/2 = {n_fft // 2}")
+    n_mels, T = fb.shape[0], 1 + L // hop
+    out = torch.empty((B, n_mels, T), device=waves.device, dtype=torch.float32)
+    call("nsid_logmel_fft", _p(waves), waves.stride(0) if B > 1 else L, B, L, n_fft, hop, _p(window), _p(twiddle), _p(fb),
+         _p(band), n_mels, _p(out), n_mels * T, T, _stream())
+    return out
+
+
 def batched_index_select_fwd(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """x (B, C, N) fp32, idx (B, Nq, k) int32 -> (B, C, Nq, k) — the reference's batched_index_select (torch_nn.py:79-98)"""
     _chk(x)

@@ -4,6 +4,7 @@ its audio pipeline (audio decoding / augmentation are outside this path). Shows 
 
     python tools/train_synthetic.py --steps 50                       # reference-style loop: torch.optim.Adam + clip_grad_norm_
     python tools/train_synthetic.py --steps 50 --fused --bf16        # FusedClipAdam, bf16 activation storage, two-stream views
+    python tools/train_synthetic.py --steps 50 --fused --graph --from-wave   # train.py:58 too: waveforms -> log-mel on the GPU
 """
 import argparse
 import os
@@ -30,6 +31,22 @@ def batches(n, batch, device):
         yield x_i.to(device), (x_i + 3.0 * torch.randn(x_i.shape, generator=g)).to(device)
 
 
+FCFG = {"fs": 16000, "n_fft": 1024, "win_len": 1024, "hop_len": 512, "overlap": 0.875, "arch": "grafp"}
+N_SAMPLES = 65280                                     # 4.08 s at 16 kHz (grafp.yaml): 128 frames
+
+
+def wave_batches(n, batch, device):
+    """synthetic 16 kHz waveforms: noise plus two tones per clip; view j is view i under a gain and more noise"""
+    g = torch.Generator().manual_seed(0)
+    t = torch.arange(N_SAMPLES) / FCFG["fs"]
+    for _ in range(n):
+        f = 200.0 + 3000.0 * torch.rand(batch, 2, generator=g)
+        x_i = 0.05 * torch.randn(batch, N_SAMPLES, generator=g)
+        x_i += 0.3 * torch.sin(2 * torch.pi * f[:, :1] * t) + 0.1 * torch.sin(2 * torch.pi * f[:, 1:] * t)
+        x_j = 0.7 * x_i + 0.05 * torch.randn(batch, N_SAMPLES, generator=g)
+        yield x_i.to(device), x_j.to(device)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
@@ -38,8 +55,15 @@ def main():
     ap.add_argument("--fused", action="store_true", help="FusedClipAdam instead of clip_grad_norm_ + torch.optim.Adam")
     ap.add_argument("--graph", action="store_true", help="capture the step in a hipGraph (graphs.GraphedTrainStep; needs --fused)")
     ap.add_argument("--bf16", action="store_true", help="bf16 activation storage + bf16 MFMA operands (BASELINE config 2)")
+    ap.add_argument("--from-wave", action="store_true",
+                    help="start every step from waveforms: GPUTransformSampleID(train=True) as train.py:58 `augment`")
     args = ap.parse_args()
     device = torch.device("cuda")
+    source, augment = batches, None
+    if args.from_wave:
+        from neuralsampleid_amd.modules.transformations import GPUTransformSampleID   # (reference: modules.transformations)
+        augment = GPUTransformSampleID(cfg={**CFG, **FCFG}, train=True).to(device)    # train.py:100
+        source = wave_batches
     if args.bf16:
         ops.set_gemm_precision("bf16")
         F_.set_activation_dtype("bf16")
@@ -53,8 +77,8 @@ def main():
         optimizer = torch.optim.Adam(model.parameters(), lr=CFG["lr"])                    # train.py:126
     if args.graph:
         from neuralsampleid_amd.graphs import GraphedTrainStep
-        data = list(batches(args.steps, args.batch, device))
-        step = GraphedTrainStep(model, optimizer, CFG, *data[0])
+        data = list(source(args.steps, args.batch, device))
+        step = GraphedTrainStep(model, optimizer, CFG, *data[0], front=augment.front(device) if augment else None)
         torch.cuda.synchronize()
         t0 = time.time()
         for idx, (x_i, x_j) in enumerate(data):
@@ -65,8 +89,11 @@ def main():
         print(f"{args.steps} graph replays in {time.time() - t0:.2f} s")
         return
     t0 = time.time()
-    for idx, (x_i, x_j) in enumerate(batches(args.steps, args.batch, device)):           # train.py:53
+    for idx, (x_i, x_j) in enumerate(source(args.steps, args.batch, device)):            # train.py:53
         optimizer.zero_grad()                                                             # :58
+        if augment is not None:
+            with torch.no_grad():
+                x_i, x_j = augment(x_i, x_j)                                              # :58-59
         h_i, h_j, z_i, z_j = model(x_i, x_j)                                              # :61
         loss = ntxent_loss(z_i, z_j, CFG)                                                 # :63
         if torch.isnan(loss):                                                             # :65-68
