@@ -73,7 +73,8 @@ int nsid_row_tiles(int M);
 /* Bytes of caller-provided scratch an op needs, or -1 for an unknown op name ("a nsid_workspace_bytes(op, dims)
  * query per op"; the reference has no counterpart — its ops allocate through torch). No entry point allocates; the kernels keep
  * their working sets in LDS and registers, so every op answers 0 ("knn_graph", "mr_aggregate", "linear", "linear_bwd_data",
- * "linear_bwd_weight", "downsample3", "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused")
+ * "linear_bwd_weight", "downsample3", "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused", "conv2d",
+ * "ibn_relu", "stem7_pool", "gem_pool")
  * except: "bn_stat" (rows x cols layer: the [2][nsid_row_tiles(rows)][cols] fp32 partial sums between a GEMM's statistics
  * epilogue / nsid_bn_bwd_reduce and the finalize kernels), "ntxent" (rows = pairs of the global batch: nsid_ntxent_ws_floats),
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
@@ -437,6 +438,32 @@ int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int
                       const int* qi, const int* ci, int P, float* dq, float* dk, void* stream);
 int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi, const int* ci, int P,
                         int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream);
+
+/* ---- ResNet-IBN baseline, eval-mode forward (encoder/resnet_ibn.py; simclr/triplet.py:65-83 BaselineModel). Activations are
+ * channels-last rows: a (B, C, H, W) reference tensor is the matrix X[B*H*W][C], row = (b*H + h)*W + w. csrc/resnet.hip.
+ * conv2d_fwd: Conv2d ksize x ksize (3: pad 1; 1: pad 0), stride 1 or 2, no im2col tensor (implicit GEMM on MFMA):
+ *   out[(b*Ho + ho)*Wo + wo][o] = act_out( bias[o] + addend[same row][o] + sum_{kh,kw,c} x[b][ho*stride - pad + kh][wo*stride - pad + kw][c]
+ *   * w[o][(kh*ksize + kw)*C + c] ), Ho = (H + 2 pad - ksize)/stride + 1 (Wo alike); a tap outside the image reads 0 in both
+ *   dimensions. w: (Cout, ksize*ksize*C) packed, the eval-mode BatchNorm folded in; w_dtype must equal act_dtype (bf16 weights with
+ *   bf16 activations on v_mfma_f32_16x16x32_bf16; fp32 weights on v_mfma_f32_16x16x4_f32, the parity path). bias (fp32, Cout) and
+ *   addend (out's storage and layout: the residual) may be NULL; act_out: NSID_ACT_NONE or NSID_ACT_RELU. C % 32 == 0 (bf16) /
+ *   % 16 == 0 (fp32), Cout % 128 == 0, any H, W >= 1; NSID_EINVAL otherwise. out must not alias x.
+ * ibn_relu_fwd: IBN + ReLU on rows (B*HW, C): channels [0, C/2) instance-normalised per (clip, channel) over the clip's HW rows
+ *   (biased variance around the mean, two passes over the stored values, eps inside the root) with the affine (in_gamma, in_beta);
+ *   channels [C/2, C) through bn_scale * x + bn_shift (C/2 each: the eval-mode BatchNorm); then ReLU. C % 128 == 0. No atomics: a
+ *   clip's result is bitwise independent of the batch around it. out may alias x.
+ * stem7_pool_fwd: Conv2d 7x7 stride 2 pad 3 from ONE channel to 64 (w: (64, 49) with the BatchNorm folded in, bias (64)) + ReLU +
+ *   MaxPool 3x3 stride 2 pad 1 (-inf padding) in one launch: x (B, H, W) fp32 -> out (B*Hp*Wp, 64) rows, Hc = (H - 1)/2 + 1,
+ *   Hp = (Hc - 1)/2 + 1 (W alike).
+ * gem_pool_fwd: out[b][c] = (mean over the HW rows of clip b of max(x, eps)^p)^(1/p), fp32; p[0] is read from DEVICE memory by the
+ *   kernel (a learned parameter: no host read on the path). C % 64 == 0. */
+int nsid_conv2d_fwd(const void* x, int B, int H, int W, int C, const void* w, int w_dtype, const float* bias, const void* addend,
+                    void* out, int Cout, int ksize, int stride, int act_out, int act_dtype, void* stream);
+int nsid_ibn_relu_fwd(const void* x, int B, int HW, int C, const float* in_gamma, const float* in_beta, float eps,
+                      const float* bn_scale, const float* bn_shift, void* out, int dtype, void* stream);
+int nsid_stem7_pool_fwd(const float* x, int B, int H, int W, const float* w, const float* bias, void* out, int out_dtype,
+                        void* stream);
+int nsid_gem_pool_fwd(const void* x, int B, int HW, int C, const float* p, float eps, float* out, int x_dtype, void* stream);
 
 #ifdef __cplusplus
 }

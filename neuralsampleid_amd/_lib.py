@@ -80,6 +80,10 @@ SIGNATURES = {
     "nsid_clf_head_bwd": "pppppipppps",
     "nsid_clf_attn_bwd": "pppipiippipps",
     "nsid_clf_seg_reduce": "ppppppiiiipps",
+    "nsid_conv2d_fwd": "piiiipipppiiiiis",
+    "nsid_ibn_relu_fwd": "piiippfpppis",
+    "nsid_stem7_pool_fwd": "piiipppis",
+    "nsid_gem_pool_fwd": "piiipfpis",
 }
 
 class WgradProblem(ctypes.Structure):

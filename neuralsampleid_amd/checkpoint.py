@@ -86,8 +86,16 @@ def encoder_variant(state_dict: Mapping[str, torch.Tensor]) -> str:
                    "encoder.backbone.<i>.conv.0.weight of one kind")
 
 
+def is_baseline_state(state_dict: Mapping[str, torch.Tensor]) -> bool:
+    """the key tree of BaselineModel(cfg, ResNetIBN()) (simclr/triplet.py:65, encoder/resnet_ibn.py:100): residual layers and an
+    embedding head under `encoder.`, no graph stem; keys with or without the DataParallel prefix"""
+    sd = strip_data_parallel_prefix(state_dict)
+    return ("encoder.layer1.0.conv1.weight" in sd and "encoder.embedding_head.weight" in sd and "encoder.stem.0.weight" not in sd)
+
+
 def simclr_for_checkpoint(cfg: dict, path_or_dict, k: int = 3, map_location="cpu", trusted: bool = False, **encoder_kw):
-    """The SimCLR model a reference checkpoint was saved from, its weights loaded strictly. The encoder class comes from the key set
+    """The SimCLR model a reference checkpoint was saved from, its weights loaded strictly (a checkpoint of the ResNet-IBN baseline,
+    recognised by its key tree, gives a BaselineModel(cfg, ResNetIBN()) instead). The encoder class comes from the key set
     (encoder_variant: PassthroughGraphEncoderDGL for the DGL tree, GraphEncoder for the gcn_lib one), the size and the input / output
     widths from the stem and proj shapes. k leaves no trace in the weights: pass the value the model was trained with."""
     from .encoder.dgl.passthrough import PassthroughGraphEncoderDGL
@@ -95,6 +103,14 @@ def simclr_for_checkpoint(cfg: dict, path_or_dict, k: int = 3, map_location="cpu
     from .simclr.simclr import SimCLR
     ckpt = read_reference_checkpoint(path_or_dict, map_location, trusted)
     sd = strip_data_parallel_prefix(ckpt["state_dict"] if "state_dict" in ckpt and isinstance(ckpt["state_dict"], Mapping) else ckpt)
+    if is_baseline_state(sd):
+        from .encoder.resnet_ibn import ResNetIBN
+        from .simclr.triplet import BaselineModel
+        if k != 3 or encoder_kw:
+            raise TypeError("a BaselineModel(ResNetIBN) checkpoint takes no encoder arguments (ResNetIBN() has none)")
+        model = BaselineModel(cfg, ResNetIBN())
+        model.load_state_dict(sd, strict=True)
+        return model
     stem = sd["encoder.stem.0.weight"]
     kw = dict(size=_SIZE_BY_STEM.get(int(stem.shape[0]), "b"), in_channels=int(stem.shape[1]),
               emb_dims=int(sd["encoder.proj.weight"].shape[0]))

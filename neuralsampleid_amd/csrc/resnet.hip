@@ -1,0 +1,478 @@
+// Eval-mode forward of the ResNet-IBN baseline (encoder/resnet_ibn.py of the reference): the first 2-D convolutional network of
+// this library. Activations are channels-last rows (B*H*W, C), fp32 or bf16 storage, fp32 accumulation.
+//
+//   conv2d_fwd_kernel  : Conv2d 3x3 (pad 1) / 1x1 (pad 0), stride 1 / 2, as an IMPLICIT GEMM on MFMA: out[m][o] = bias[o] +
+//                        sum_{kh, kw, c} x[b][ho*s - pad + kh][wo*s - pad + kw][c] * wp[o][(kh*KW + kw)*C + c] (+ addend) (ReLU).
+//                        The im2col matrix is never formed: a thread keeps the (clip, row, column) of its two operand rows and
+//                        steps through (tap, channel chunk); a tap outside the image is staged as zeros (top, bottom, left and
+//                        right edge of every clip, so nothing leaks between image rows or between the clips of a batch).
+//                        128 x 128 output tile over the FLATTENED rows of the batch (layer4 has 84 pixels per clip: tiles are
+//                        filled from the batch), 4 waves of 64 x 64, 64-byte reduction stages (32 bf16 / 16 fp32) double
+//                        buffered in LDS, the global loads of the next stage (bf16) / next two stages (fp32) in flight under the MFMA block.
+//                        bf16 storage: v_mfma_f32_16x16x32_bf16 with bf16 weights. fp32 storage: v_mfma_f32_16x16x4_f32 with
+//                        fp32 weights (the parity path); its accumulators are flushed into a second set every 256 reduction
+//                        elements, so the rounding error of a K = 9 216 sum grows like that of a K = 256 one.
+//                        The MFMA operands are swapped (weights first): a lane then holds 4 consecutive output CHANNELS of one
+//                        row and stores 16 (fp32) / 8 (bf16) contiguous bytes.
+//   ibn_relu_kernel    : IBN + ReLU. One workgroup per (clip, 64 channels). Instance-norm half: mean, then the biased variance
+//                        around it (two passes over the stored values, fixed summation order, no atomics), then the apply;
+//                        BatchNorm half: the given per-channel affine. A clip's result depends on that clip only.
+//   stem7_pool_kernel  : Conv 7x7 s2 p3 (1 -> 64) + folded BatchNorm + ReLU + MaxPool 3x3 s2 p1. One workgroup per (clip, pooled
+//                        row, 16 pooled columns): the 3 x 33 conv pixels under them are computed into LDS (64 channels = the 64
+//                        lanes of a wave, the 49 weights of a channel in registers, the input patch broadcast from LDS) and pooled
+//                        from there; a conv pixel outside the conv map is -inf for the pool.
+//   gem_pool_kernel    : (mean over HW of max(x, eps)^p)^(1/p) per (clip, channel); p is read from device memory.
+#include "nsid_common.h"
+
+namespace {
+
+constexpr int CV_BM = 128, CV_BN = 128;
+constexpr int CV_ROWB = 64;       // bytes of one operand row in one reduction stage
+constexpr int CV_LD = 80;         // its LDS stride: 16-byte aligned, 20 banks apart (the 16 rows of a fragment read hit 16 distinct bank quads)
+constexpr int CV_FLUSH = 16;      // fp32 path: stages (of 16 elements) per accumulator flush
+
+struct ConvArgs {
+  const void* x; const void* w; const float* bias; const void* addend; void* out;
+  int B, H, W, C, Ho, Wo, Co, KW, taps, stride, pad, relu, M, tiles_n;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void conv2d_fwd_kernel(const ConvArgs a) {
+  constexpr bool BF = sizeof(T) == 2;
+  constexpr int EPC = 16 / (int)sizeof(T);            // elements of a 16-byte chunk
+  constexpr int BKE = CV_ROWB / (int)sizeof(T);       // reduction elements of a stage
+  constexpr int STAGE = (CV_BM + CV_BN) * CV_LD;
+  __shared__ __attribute__((aligned(16))) char lds[2 * STAGE];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, rq = lane >> 4;
+  const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+  const int tn = blockIdx.x % a.tiles_n, tm = blockIdx.x / a.tiles_n;
+  const int m0 = tm * CV_BM, n0 = tn * CV_BN;
+  const int C = a.C, K = a.taps * C;
+  const T* x = static_cast<const T*>(a.x);
+  const T* w = static_cast<const T*>(a.w);
+
+  // the two operand chunks of this thread per stage: rows (tid >> 2) and 64 + (tid >> 2), 16-byte chunk tid & 3 of the 64-byte row
+  const int ch = tid & 3;
+  long abase[2];          // element offset of (clip, hi0, wi0, channel chunk); only used where the tap is inside the image
+  int hi0[2], wi0[2];
+  bool aok[2];
+  const T* wrow[2];
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const int row = (tid >> 2) + 64 * q, m = m0 + row;
+    aok[q] = m < a.M;
+    int b = 0, ho = 0, wo = 0;
+    if (aok[q]) {
+      b = m / (a.Ho * a.Wo);
+      const int r = m - b * (a.Ho * a.Wo);
+      ho = r / a.Wo;
+      wo = r - ho * a.Wo;
+    }
+    hi0[q] = ho * a.stride - a.pad;
+    wi0[q] = wo * a.stride - a.pad;
+    abase[q] = (((long)b * a.H + hi0[q]) * a.W + wi0[q]) * C + ch * EPC;
+    wrow[q] = w + (long)(n0 + row) * K + ch * EPC;
+  }
+
+  // Global loads go to registers one (bf16) or two (fp32) stages ahead of the MFMA block that uses them. Past the last stage the
+  // load state stops advancing, so a phantom stage re-reads the last one (valid addresses) and is never computed on.
+  f32x4 ra[2][2], rb[2][2];
+  const int nstage = K / BKE;
+  int ld_st = 0, ld_k0 = 0, ld_c0 = 0, ld_kh = 0, ld_kw = 0;      // the stage the next issue() loads (uniform)
+  auto issue = [&](f32x4 (&sa)[2], f32x4 (&sb)[2]) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int hi = hi0[q] + ld_kh, wi = wi0[q] + ld_kw;
+      const bool ok = aok[q] && hi >= 0 && hi < a.H && wi >= 0 && wi < a.W;      // the conv's zero padding, in both dimensions
+      sa[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (ok) sa[q] = *reinterpret_cast<const f32x4*>(x + abase[q] + ((long)ld_kh * a.W + ld_kw) * C + ld_c0);
+      sb[q] = *reinterpret_cast<const f32x4*>(wrow[q] + ld_k0);
+    }
+    if (++ld_st < nstage) {
+      ld_k0 += BKE;
+      ld_c0 += BKE;
+      if (ld_c0 == C) {
+        ld_c0 = 0;
+        if (++ld_kw == a.KW) { ld_kw = 0; ++ld_kh; }
+      }
+    }
+  };
+  auto commit = [&](const f32x4 (&sa)[2], const f32x4 (&sb)[2], int buf) {
+    char* dst = lds + buf * STAGE;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int row = (tid >> 2) + 64 * q;
+      *reinterpret_cast<f32x4*>(dst + row * CV_LD + ch * 16) = sa[q];
+      *reinterpret_cast<f32x4*>(dst + (CV_BM + row) * CV_LD + ch * 16) = sb[q];
+    }
+  };
+
+  f32x4 acc[4][4], tot[BF ? 1 : 4][BF ? 1 : 4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (!BF) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+  auto compute = [&](int st) {
+    const char* la = lds + (st & 1) * STAGE;
+    const char* lb = la + CV_BM * CV_LD;
+    if constexpr (BF) {
+      bf16x8 fa[4], fb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const bf16x8*>(la + (wm0 + 16 * i + lr) * CV_LD + 16 * rq);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const bf16x8*>(lb + (wn0 + 16 * j + lr) * CV_LD + 16 * rq);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
+    } else {
+      f32x4 fa[4], fb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const f32x4*>(la + (wm0 + 16 * i + lr) * CV_LD + 16 * rq);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const f32x4*>(lb + (wn0 + 16 * j + lr) * CV_LD + 16 * rq);
+#pragma unroll
+      for (int s = 0; s < 4; ++s)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j][s], fa[i][s], acc[i][j], 0, 0, 0);
+      if ((st % CV_FLUSH) == CV_FLUSH - 1) {           // uniform
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            tot[i][j] += acc[i][j];
+            acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+      }
+    }
+  };
+
+  if constexpr (BF) {
+    // bf16: ONE stage in flight. Measured at batch 256 (18 launches of one forward): 5.14 ms against 5.44 ms with two stages in
+    // flight; the loop is bound by LDS traffic (8 KB of fragment reads per wave and stage against 16 MFMAs), not by load latency.
+    issue(ra[0], rb[0]);
+    commit(ra[0], rb[0], 0);
+    __syncthreads();
+    for (int st = 0; st < nstage; ++st) {
+      const bool more = st + 1 < nstage;
+      if (more) issue(ra[0], rb[0]);                      // lands under the MFMA block below
+      compute(st);
+      if (more) commit(ra[0], rb[0], (st + 1) & 1);
+      __syncthreads();
+    }
+  } else {
+    // fp32: TWO stages in flight (+15 % over one). Invariant at the top of sub-step u of an iteration: LDS[s & 1] holds stage
+    // s = st + u, register set u is free (it held stage s), the other set holds stage s + 1 in flight.
+    issue(ra[0], rb[0]);
+    commit(ra[0], rb[0], 0);
+    issue(ra[1], rb[1]);
+    __syncthreads();
+    int st = 0;
+    for (; st + 1 < nstage; st += 2) {
+      issue(ra[0], rb[0]);                                // stage st + 2
+      __builtin_amdgcn_sched_barrier(0);
+      compute(st);
+      __builtin_amdgcn_sched_barrier(0);
+      commit(ra[1], rb[1], 1);                            // stage st + 1
+      __syncthreads();
+      issue(ra[1], rb[1]);                                // stage st + 3
+      __builtin_amdgcn_sched_barrier(0);
+      compute(st + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      commit(ra[0], rb[0], 0);                            // stage st + 2 (a phantom past the end: never computed on)
+      __syncthreads();
+    }
+    if (st < nstage) compute(st);                         // an odd stage count: the last stage sits in LDS[0]
+  }
+
+  // epilogue. Operands swapped: lane (lr, rq), register r of acc[i][j] is row m = 16 i + lr, channel n = 16 j + 4 rq + r
+  T* out = static_cast<T*>(a.out);
+  const T* add = static_cast<const T*>(a.addend);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int n = n0 + wn0 + 16 * j + 4 * rq;
+    f32x4 bj = {0.f, 0.f, 0.f, 0.f};
+    if (a.bias != nullptr) bj = *reinterpret_cast<const f32x4*>(a.bias + n);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int m = m0 + wm0 + 16 * i + lr;
+      if (m >= a.M) continue;
+      f32x4 v = acc[i][j];
+      if constexpr (!BF) v += tot[i][j];
+      v += bj;
+      const long o = (long)m * a.Co + n;
+      if (add != nullptr) {
+        if constexpr (BF) {
+          const bf16x4 h = *reinterpret_cast<const bf16x4*>(add + o);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] += (float)h[r];
+        } else {
+          v += *reinterpret_cast<const f32x4*>(add + o);
+        }
+      }
+      if (a.relu) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = nsid_act(v[r], NSID_ACT_RELU);
+      }
+      if constexpr (BF) {
+        *reinterpret_cast<bf16x4*>(out + o) = __builtin_convertvector(v, bf16x4);
+      } else {
+        *reinterpret_cast<f32x4*>(out + o) = v;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- IBN + ReLU
+struct IbnArgs {
+  const void* x; void* out;
+  const float* gamma; const float* beta; const float* sc; const float* sh;
+  int HW, C;
+  float eps;
+};
+constexpr int IBN_CW = 64;        // channels per workgroup
+constexpr int IBN_U = 4;          // independent row loads in flight per thread (a pass is a chain of load latencies otherwise)
+
+// rows r, r + RL, ... (IBN_U of them) of this thread's chunk column; rows past the end read as zeros
+template <typename T, int RL>
+__device__ __forceinline__ void load_rows(const T* x, int r, int HW, int C, float (&v)[IBN_U][Chunk<T>::N]) {
+#pragma unroll
+  for (int u = 0; u < IBN_U; ++u) {
+    const int ru = r + u * RL;
+    Chunk<T>::load(x + (long)min(ru, HW - 1) * C, v[u]);        // unconditional (clamped): the IBN_U loads issue back to back
+    if (ru >= HW) {
+#pragma unroll
+      for (int e = 0; e < Chunk<T>::N; ++e) v[u][e] = 0.f;
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ibn_relu_kernel(const IbnArgs a) {
+  constexpr int N = Chunk<T>::N;
+  constexpr int CPR = IBN_CW / N;          // chunks per row of the workgroup's channel block
+  constexpr int RL = 256 / CPR;            // row lanes
+  __shared__ float red[RL][IBN_CW];
+  __shared__ float stat[2][IBN_CW];
+  const int tid = threadIdx.x, cc = (tid % CPR) * N, rl = tid / CPR;
+  const int c0 = blockIdx.x * IBN_CW, half = a.C / 2;
+  const long base = (long)blockIdx.y * a.HW * a.C + c0 + cc;
+  const T* x = static_cast<const T*>(a.x) + base;
+  T* out = static_cast<T*>(a.out) + base;
+  float mu[N], scale[N], shift[N];
+  if (c0 < half) {                           // (uniform) instance norm: statistics of this clip's HW rows, two passes
+    float s[N];
+#pragma unroll
+    for (int e = 0; e < N; ++e) s[e] = 0.f;
+    for (int r = rl; r < a.HW; r += IBN_U * RL) {
+      float v[IBN_U][N];
+      load_rows<T, RL>(x, r, a.HW, a.C, v);
+#pragma unroll
+      for (int u = 0; u < IBN_U; ++u)
+#pragma unroll
+        for (int e = 0; e < N; ++e) s[e] += v[u][e];           // rows past the end were loaded as zeros
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) red[rl][cc + e] = s[e];
+    __syncthreads();
+    if (tid < IBN_CW) {
+      float t = 0.f;
+      for (int g = 0; g < RL; ++g) t += red[g][tid];
+      stat[0][tid] = t / (float)a.HW;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < N; ++e) { mu[e] = stat[0][cc + e]; s[e] = 0.f; }
+    for (int r = rl; r < a.HW; r += IBN_U * RL) {
+      float v[IBN_U][N];
+      load_rows<T, RL>(x, r, a.HW, a.C, v);
+#pragma unroll
+      for (int u = 0; u < IBN_U; ++u) {
+        if (r + u * RL >= a.HW) break;
+#pragma unroll
+        for (int e = 0; e < N; ++e) { const float d = v[u][e] - mu[e]; s[e] = fmaf(d, d, s[e]); }
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < N; ++e) red[rl][cc + e] = s[e];
+    __syncthreads();
+    if (tid < IBN_CW) {
+      float t = 0.f;
+      for (int g = 0; g < RL; ++g) t += red[g][tid];
+      stat[1][tid] = 1.f / sqrtf(t / (float)a.HW + a.eps);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      scale[e] = a.gamma[c0 + cc + e] * stat[1][cc + e];
+      shift[e] = a.beta[c0 + cc + e];
+    }
+  } else {                                   // eval-mode BatchNorm half: the given affine
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      mu[e] = 0.f;
+      scale[e] = a.sc[c0 - half + cc + e];
+      shift[e] = a.sh[c0 - half + cc + e];
+    }
+  }
+  for (int r = rl; r < a.HW; r += IBN_U * RL) {
+    float v[IBN_U][N];
+    load_rows<T, RL>(x, r, a.HW, a.C, v);
+#pragma unroll
+    for (int u = 0; u < IBN_U; ++u) {
+      if (r + u * RL >= a.HW) break;
+#pragma unroll
+      for (int e = 0; e < N; ++e) v[u][e] = nsid_act(fmaf(v[u][e] - mu[e], scale[e], shift[e]), NSID_ACT_RELU);
+      Chunk<T>::store(out + (long)(r + u * RL) * a.C, v[u]);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- stem
+struct StemArgs {
+  const float* x; const float* w; const float* bias; void* out;
+  int H, W, Hc, Wc, Hp, Wp;
+};
+constexpr int ST_PW = 16;                    // pooled columns per workgroup
+constexpr int ST_CW = 2 * ST_PW + 1;         // conv columns under them
+constexpr int ST_PR = 11, ST_PC = 2 * (ST_CW - 1) + 7;     // input patch: 11 rows x 71 columns
+
+template <typename T>
+__global__ __launch_bounds__(256) void stem7_pool_kernel(const StemArgs a) {
+  __shared__ float patch[ST_PR][ST_PC + 1];
+  __shared__ float cmap[3 * ST_CW][64];
+  const int tid = threadIdx.x, chn = tid & 63, g = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wp0 = blockIdx.x * ST_PW, hp = blockIdx.y, b = blockIdx.z;
+  // conv pixel (i, j) of the workgroup is (2 hp - 1 + i, 2 wp0 - 1 + j); its tap (kh, kw) reads input (4 hp - 5 + 2 i + kh, 4 wp0 - 5 + 2 j + kw)
+  const int r0 = 4 * hp - 5, q0 = 4 * wp0 - 5;
+  const float* xb = a.x + (long)b * a.H * a.W;
+  for (int idx = tid; idx < ST_PR * ST_PC; idx += 256) {
+    const int pr = idx / ST_PC, pc = idx - pr * ST_PC;
+    const int r = r0 + pr, q = q0 + pc;
+    patch[pr][pc] = (r >= 0 && r < a.H && q >= 0 && q < a.W) ? xb[(long)r * a.W + q] : 0.f;      // the conv's zero padding
+  }
+  float wk[49];
+#pragma unroll
+  for (int t = 0; t < 49; ++t) wk[t] = a.w[chn * 49 + t];
+  const float bias = a.bias[chn];
+  __syncthreads();
+  for (int pix = g; pix < 3 * ST_CW; pix += 4) {           // uniform per wave: the patch reads are broadcasts
+    const int i = pix / ST_CW, j = pix - i * ST_CW;
+    const int hc = 2 * hp - 1 + i, wc = 2 * wp0 - 1 + j;
+    float v = -INFINITY;                                    // the pool's padding
+    if (hc >= 0 && hc < a.Hc && wc >= 0 && wc < a.Wc) {
+      float s = 0.f;
+#pragma unroll
+      for (int kh = 0; kh < 7; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 7; ++kw) s = fmaf(patch[2 * i + kh][2 * j + kw], wk[kh * 7 + kw], s);
+      v = nsid_act(s + bias, NSID_ACT_RELU);
+    }
+    cmap[pix][chn] = v;
+  }
+  __syncthreads();
+  T* out = static_cast<T*>(a.out);
+  for (int pw = g; pw < ST_PW; pw += 4) {
+    const int wp = wp0 + pw;
+    if (wp >= a.Wp) break;
+    float m = -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int j = 0; j < 3; ++j) m = fmaxf(m, cmap[i * ST_CW + 2 * pw + j][chn]);
+    out[(((long)b * a.Hp + hp) * a.Wp + wp) * 64 + chn] = (T)m;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- GeM
+template <typename T>
+__global__ __launch_bounds__(256) void gem_pool_kernel(const T* __restrict__ x, int HW, int C, const float* __restrict__ p_dev,
+                                                       float eps, float* __restrict__ out) {
+  __shared__ float red[4][64];
+  const int tid = threadIdx.x, c = tid & 63, g = tid >> 6;
+  const int c0 = blockIdx.x * 64, b = blockIdx.y;
+  const float p = p_dev[0];
+  const T* xb = x + (long)b * HW * C + c0 + c;
+  float s = 0.f;
+  for (int r = g; r < HW; r += 4) s += powf(fmaxf((float)xb[(long)r * C], eps), p);
+  red[g][c] = s;
+  __syncthreads();
+  if (tid < 64) {
+    const float t = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    out[(long)b * C + c0 + tid] = powf(t / (float)HW, 1.f / p);
+  }
+}
+
+}  // namespace
+
+extern "C" int nsid_conv2d_fwd(const void* x, int B, int H, int W, int C, const void* w, int w_dtype, const float* bias,
+                               const void* addend, void* out, int Cout, int ksize, int stride, int act_out, int act_dtype,
+                               void* stream) {
+  NSID_REQUIRE(x && w && out && B > 0 && H > 0 && W > 0 && C > 0 && Cout > 0 && NSID_DTYPE_OK(act_dtype));
+  NSID_REQUIRE(w_dtype == act_dtype);              // bf16 weights with bf16 activations, fp32 weights on the fp32 MFMA
+  NSID_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2));
+  NSID_REQUIRE(act_out == NSID_ACT_NONE || act_out == NSID_ACT_RELU);
+  NSID_REQUIRE(C % (act_dtype == NSID_BF16 ? 32 : 16) == 0 && Cout % CV_BN == 0);
+  NSID_REQUIRE(nsid_aligned16(x) && nsid_aligned16(w) && nsid_aligned16(out) && nsid_aligned16(bias) && nsid_aligned16(addend));
+  ConvArgs a{};
+  a.x = x; a.w = w; a.bias = bias; a.addend = addend; a.out = out;
+  a.B = B; a.H = H; a.W = W; a.C = C; a.Co = Cout;
+  a.KW = ksize; a.taps = ksize * ksize; a.stride = stride; a.pad = ksize / 2;
+  a.Ho = (H + 2 * a.pad - ksize) / stride + 1;
+  a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
+  a.relu = act_out == NSID_ACT_RELU;
+  const long M = (long)B * a.Ho * a.Wo;
+  NSID_REQUIRE(M < (1L << 31) / 2 && (long)B * H * W < (1L << 31) / 2);
+  a.M = (int)M;
+  a.tiles_n = Cout / CV_BN;
+  const long wgs = ((M + CV_BM - 1) / CV_BM) * a.tiles_n;
+  NSID_REQUIRE(wgs < (1L << 31) - 1);
+  nsid_count(ksize == 3 ? NSID_C_conv2d_3x3 : NSID_C_conv2d_1x1);
+  NSID_DISPATCH_DTYPE(act_dtype, T,
+                      NSID_LAUNCH(conv2d_fwd_kernel<T>, dim3((unsigned)wgs), dim3(256), 0, static_cast<hipStream_t>(stream), a));
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_ibn_relu_fwd(const void* x, int B, int HW, int C, const float* in_gamma, const float* in_beta, float eps,
+                                 const float* bn_scale, const float* bn_shift, void* out, int dtype, void* stream) {
+  NSID_REQUIRE(x && out && in_gamma && in_beta && bn_scale && bn_shift && B > 0 && B <= 65535 && HW > 0 && C > 0);
+  NSID_REQUIRE(NSID_DTYPE_OK(dtype) && C % (2 * IBN_CW) == 0 && eps >= 0.f && nsid_aligned16(x) && nsid_aligned16(out));
+  IbnArgs a{};
+  a.x = x; a.out = out; a.gamma = in_gamma; a.beta = in_beta; a.sc = bn_scale; a.sh = bn_shift;
+  a.HW = HW; a.C = C; a.eps = eps;
+  nsid_count(NSID_C_ibn_relu);
+  NSID_DISPATCH_DTYPE(dtype, T,
+                      NSID_LAUNCH(ibn_relu_kernel<T>, dim3(C / IBN_CW, B), dim3(256), 0, static_cast<hipStream_t>(stream), a));
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_stem7_pool_fwd(const float* x, int B, int H, int W, const float* w, const float* bias, void* out, int out_dtype,
+                                   void* stream) {
+  NSID_REQUIRE(x && w && bias && out && B > 0 && B <= 65535 && H > 0 && W > 0 && NSID_DTYPE_OK(out_dtype));
+  StemArgs a{};
+  a.x = x; a.w = w; a.bias = bias; a.out = out;
+  a.H = H; a.W = W;
+  a.Hc = (H - 1) / 2 + 1; a.Wc = (W - 1) / 2 + 1;          // (H + 6 - 7) / 2 + 1
+  a.Hp = (a.Hc - 1) / 2 + 1; a.Wp = (a.Wc - 1) / 2 + 1;    // (Hc + 2 - 3) / 2 + 1
+  NSID_REQUIRE(a.Hp <= 65535 && (long)B * a.Hp * a.Wp < (1L << 31) / 64);
+  nsid_count(NSID_C_stem7_pool);
+  const dim3 grid((a.Wp + ST_PW - 1) / ST_PW, a.Hp, B);
+  NSID_DISPATCH_DTYPE(out_dtype, T, NSID_LAUNCH(stem7_pool_kernel<T>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a));
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_gem_pool_fwd(const void* x, int B, int HW, int C, const float* p, float eps, float* out, int x_dtype,
+                                 void* stream) {
+  NSID_REQUIRE(x && p && out && B > 0 && B <= 65535 && HW > 0 && C > 0 && C % 64 == 0 && eps > 0.f && NSID_DTYPE_OK(x_dtype));
+  nsid_count(NSID_C_gem_pool);
+  NSID_DISPATCH_DTYPE(x_dtype, T, NSID_LAUNCH(gem_pool_kernel<T>, dim3(C / 64, B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                                              static_cast<const T*>(x), HW, C, p, eps, out));
+  return nsid_launch_status();
+}

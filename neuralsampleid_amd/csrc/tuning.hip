@@ -73,7 +73,8 @@ extern "C" size_t nsid_ntxent_ws_floats(int Bg);
 extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
   if (op == nullptr || rows < 0 || cols < 0) return -1;
   static const char* const kNone[] = {"knn_graph", "mr_aggregate", "linear", "linear_bwd_data", "linear_bwd_weight", "downsample3",
-                                      "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused"};
+                                      "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused",
+                                      "conv2d", "ibn_relu", "stem7_pool", "gem_pool"};
   for (const char* n : kNone)
     if (strcmp(op, n) == 0) return 0;
   if (strcmp(op, "bn_stat") == 0)            // [2][row tiles][cols] fp32 partial sums of a rows x cols layer (forward and backward)

@@ -1,0 +1,181 @@
+"""Module shells of the ResNet-IBN baseline (reference: encoder/resnet_ibn.py): the reference's constructor signatures, construction
+order (a seeded default initialisation draws the reference's values) and state_dict (193 keys), with the EVAL-MODE forward on the
+HIP kernels of csrc/resnet.hip.
+
+Activations are channels-last rows (B*H*W, C) from the stem to the pooling, fp32 or bf16 storage (functional.ACT_DTYPE). Per
+ResidualIBN block:
+    identity = downsample conv 1x1 (stride s) with its BatchNorm folded     nsid_linear_fwd (s = 1) / nsid_conv2d_fwd (s = 2)
+    conv1 1x1 (raw)                                                         nsid_linear_fwd
+    IBN + ReLU                                                              nsid_ibn_relu_fwd (in place)
+    conv2 3x3 stride s, bn2 folded (no activation)                          nsid_conv2d_fwd
+    relu(conv3 1x1 with bn3 folded + identity)                              nsid_conv2d_fwd (1x1 form: addend + ReLU epilogue)
+Packed / folded weights and their bf16 shadows are cached by ops.folded_conv_bn (parameter versions and state epochs in the key), so
+a load_state_dict is seen by the next forward. Training mode and CPU tensors raise: the backward of these kernels does not exist."""
+import torch
+import torch.nn as nn
+
+from .. import functional as F_
+from .. import ops
+
+N_BINS = 84          # CQT bins of the baseline's input (config/resnet_ibn.yaml: (84, 216) segments)
+
+
+def _bn_args(bn):
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps
+
+
+def _require_eval_gpu(module, x, what):
+    if module.training:
+        raise NotImplementedError(f"{what}: only the eval-mode forward is implemented on the MI355X path (no backward of the 2-D "
+                                  "convolution, instance norm and GeM kernels exists): call eval() and run under torch.no_grad()")
+    if not x.is_cuda:
+        raise NotImplementedError(f"{what}: there is no CPU path; move the model and its input to the GPU")
+
+
+class IBN(nn.Module):
+    """first half of the channels through InstanceNorm2d(affine), second half through BatchNorm2d"""
+
+    def __init__(self, channels):
+        super().__init__()
+        half1 = int(channels * 0.5)
+        self.IN = nn.InstanceNorm2d(half1, affine=True)
+        self.BN = nn.BatchNorm2d(channels - half1)
+
+    def relu_rows(self, r, B, HW):
+        """relu(IBN(r)) on rows (B*HW, C), in place"""
+        C = r.shape[1]
+        if self.IN.num_features != C // 2 or self.IN.track_running_stats:
+            raise NotImplementedError("IBN on the MI355X path: InstanceNorm2d over the first C/2 channels, without running statistics")
+        aff = ops.bn_eval_affine(*_bn_args(self.BN))
+        return ops.ibn_relu_fwd(r, B, HW, C, self.IN.weight, self.IN.bias, aff, self.IN.eps, out=r)
+
+    def forward(self, x):
+        raise NotImplementedError("IBN without the ReLU behind it is not a kernel of this library (nsid_ibn_relu_fwd fuses the two): "
+                                  "run it through ResidualIBN / ResNetIBN")
+
+
+class _Bottleneck(nn.Module):
+    """conv1 1x1 -> norm -> ReLU -> conv2 3x3 (stride) -> bn2 -> conv3 1x1 -> bn3 -> + identity -> ReLU"""
+
+    def _build(self, in_channels, out_channels, stride, norm1):
+        self.conv1 = nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=1, bias=False)
+        self.bn1 = norm1(out_channels)
+        self.conv2 = nn.Conv2d(out_channels, out_channels, kernel_size=3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(out_channels)
+        self.conv3 = nn.Conv2d(out_channels, out_channels, kernel_size=1, stride=1, bias=False)
+        self.bn3 = nn.BatchNorm2d(out_channels)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = None
+        if stride != 1 or in_channels != out_channels:
+            self.downsample = nn.Sequential(nn.Conv2d(in_channels, out_channels, kernel_size=1, stride=stride, bias=False),
+                                            nn.BatchNorm2d(out_channels))
+
+    def forward_rows(self, x, B, H, W):
+        """x (B*H*W, Cin) rows -> (rows (B*Ho*Wo, Cout), Ho, Wo)"""
+        Cin, Cout, s = self.conv1.in_channels, self.conv1.out_channels, self.conv2.stride[0]
+        M = B * H * W
+        identity = x
+        if self.downsample is not None:
+            dconv, dbn = self.downsample[0], self.downsample[1]
+            if s == 1:      # a row GEMM
+                wf, bf = ops.folded_conv_bn(ops.w2d(dconv.weight), None, *_bn_args(dbn))
+                identity, _ = ops.linear_fwd(x, wf, bf, M, Cout, Cin)
+            else:
+                wf, bf = ops.packed_conv_bn(dconv.weight, *_bn_args(dbn))
+                identity = ops.conv2d_fwd(x, B, H, W, Cin, wf, bf, Cout, 1, s)
+        if isinstance(self.bn1, IBN):
+            r, _ = ops.linear_fwd(x, ops.w2d(self.conv1.weight), None, M, Cout, Cin)
+            y = self.bn1.relu_rows(r, B, H * W)
+        else:
+            w1, b1 = ops.folded_conv_bn(ops.w2d(self.conv1.weight), None, *_bn_args(self.bn1))
+            y, _ = ops.linear_fwd(x, w1, b1, M, Cout, Cin, act_out=ops.ACT_RELU)
+        w2, b2 = ops.packed_conv_bn(self.conv2.weight, *_bn_args(self.bn2))
+        y = ops.conv2d_fwd(y, B, H, W, Cout, w2, b2, Cout, 3, s)
+        Ho, Wo = ops.conv_out_size(H, 3, s), ops.conv_out_size(W, 3, s)
+        w3, b3 = ops.packed_conv_bn(self.conv3.weight, *_bn_args(self.bn3))
+        return ops.conv2d_fwd(y, B, Ho, Wo, Cout, w3, b3, Cout, 1, 1, addend=identity, relu=True), Ho, Wo
+
+    def forward(self, x):
+        _require_eval_gpu(self, x, type(self).__name__)
+        B, C, H, W = x.shape
+        rows = x.permute(0, 2, 3, 1).reshape(B * H * W, C).to(F_.ACT_DTYPE).contiguous()
+        out, Ho, Wo = self.forward_rows(rows, B, H, W)
+        return rows_to_bchw(out, B, Ho, Wo)
+
+
+class ResidualIBN(_Bottleneck):
+    def __init__(self, in_channels, out_channels, stride=1):
+        super().__init__()
+        self._build(in_channels, out_channels, stride, IBN)
+
+
+class ResidualBlock(_Bottleneck):
+    def __init__(self, in_channels, out_channels, stride=1):
+        super().__init__()
+        self._build(in_channels, out_channels, stride, nn.BatchNorm2d)
+
+
+class GeMPooling(nn.Module):
+    def __init__(self, p=3, eps=1e-6):
+        super().__init__()
+        self.p = nn.Parameter(torch.ones(1) * p)
+        self.eps = eps
+
+    def pool_rows(self, rows, B, HW):
+        """rows (B*HW, C) -> (B, C) fp32; p is read by the kernel from device memory (no host read: capturable)"""
+        return ops.gem_pool_fwd(rows, B, HW, rows.shape[1], self.p, self.eps)
+
+    def forward(self, x):
+        _require_eval_gpu(self, x, "GeMPooling")
+        B, C, H, W = x.shape
+        rows = x.permute(0, 2, 3, 1).reshape(B * H * W, C).to(F_.ACT_DTYPE).contiguous()
+        return self.pool_rows(rows, B, H * W).view(B, C, 1, 1)
+
+
+def rows_to_bchw(rows, B, H, W):
+    """channels-last rows (B*H*W, C) -> the reference's (B, C, H, W) fp32 tensor (module boundary / tests: off the hot path)"""
+    return rows.float().view(B, H, W, rows.shape[1]).permute(0, 3, 1, 2).contiguous()
+
+
+class ResNetIBN(nn.Module):
+    def __init__(self):
+        super().__init__()
+        self.conv1 = nn.Conv2d(1, 64, kernel_size=7, stride=2, padding=3, bias=False)
+        self.bn1 = nn.BatchNorm2d(64)
+        self.relu = nn.ReLU(inplace=True)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.layer1 = self._make_layer(ResidualIBN, 64, 128, 2, stride=1)
+        self.layer2 = self._make_layer(ResidualIBN, 128, 256, 2, stride=1)
+        self.layer3 = self._make_layer(ResidualIBN, 256, 512, 2, stride=2)
+        self.layer4 = self._make_layer(ResidualIBN, 512, 1024, 2, stride=2)
+        self.global_pool = GeMPooling()
+        self.embedding_head = nn.Linear(1024, 2048)
+
+    def _make_layer(self, block, in_channels, out_channels, blocks, stride):
+        layers = [block(in_channels, out_channels, stride)]
+        layers += [block(out_channels, out_channels) for _ in range(1, blocks)]
+        return nn.Sequential(*layers)
+
+    def forward_rows(self, x, stages=None):
+        """x (B, 84, T) fp32 on the GPU -> h (B, 2048) fp32. stages: a dict that receives the stem / layer1..4 outputs as
+        (rows, H, W) (tests)"""
+        _require_eval_gpu(self, x, "ResNetIBN")
+        if x.dim() != 3:
+            raise ValueError(f"ResNetIBN takes (B, bins, frames) segments, got {tuple(x.shape)}")
+        B = x.shape[0]
+        w49, b49 = ops.packed_conv_bn(self.conv1.weight, *_bn_args(self.bn1))
+        rows, H, W = ops.stem7_pool_fwd(x.float().contiguous(), w49, b49, F_.ACT_DTYPE)
+        if stages is not None:
+            stages["stem"] = (rows, H, W)
+        for name in ("layer1", "layer2", "layer3", "layer4"):
+            for blk in getattr(self, name):
+                rows, H, W = blk.forward_rows(rows, B, H, W)
+            if stages is not None:
+                stages[name] = (rows, H, W)
+        pooled = self.global_pool.pool_rows(rows, B, H * W)
+        head = self.embedding_head
+        h, _ = ops.linear_fwd(pooled, head.weight, head.bias, B, head.out_features, head.in_features)
+        return h
+
+    def forward(self, x):
+        return self.forward_rows(x)

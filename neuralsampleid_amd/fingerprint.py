@@ -18,6 +18,25 @@ def shard_bounds(n: int, rank: int, world: int) -> Tuple[int, int]:
     return lo, lo + base + (1 if rank < extra else 0)
 
 
+def embedding_dim(model) -> int:
+    """width of the fingerprints `model._embed` returns: the projector's last layer (SimCLR), or the encoder's embedding head when
+    the projector is the identity (simclr/triplet.py BaselineModel: 2048)"""
+    proj = model.projector
+    if isinstance(proj, torch.nn.Sequential):
+        return proj[-1].out_features
+    return model.encoder.embedding_head.out_features
+
+
+def input_shape(model) -> Tuple[int, int]:
+    """(bins, frames) of one segment: (n_mels, n_frames) of the cfg for the log-mel models, (84, n_frames) for the baseline's CQT
+    segments (config/resnet_ibn.yaml: 216 frames)"""
+    from .encoder.resnet_ibn import N_BINS, ResNetIBN
+    cfg = model.cfg
+    if isinstance(model.encoder, ResNetIBN):
+        return N_BINS, int(cfg.get("n_frames", 216))
+    return cfg["n_mels"], cfg["n_frames"]
+
+
 @torch.no_grad()
 def extract_fingerprints(model, specs: torch.Tensor, batch: int = 1024, out: torch.Tensor = None) -> torch.Tensor:
     """specs (S, n_mels, n_frames) fp32 on the GPU -> (S, d) L2-normalised fingerprints (fp32).
@@ -29,7 +48,7 @@ def extract_fingerprints(model, specs: torch.Tensor, batch: int = 1024, out: tor
         ops.register_weight_shadows(model)          # bf16 copies of the weights, converted once (version-checked)
     try:
         S = specs.shape[0]
-        d = model.projector[-1].out_features
+        d = embedding_dim(model)
         if out is None:
             out = torch.empty((S, d), device=specs.device, dtype=torch.float32)
         for lo in range(0, S, batch):
@@ -73,11 +92,11 @@ class GraphedFingerprinter:
         self.model, self.mb = model, int(micro_batch)
         dev = next(model.parameters()).device
         cfg = model.cfg
-        shape = (self.mb, cfg["n_mels"], cfg["n_frames"]) if example is None else (self.mb,) + tuple(example.shape[1:])
+        shape = (self.mb,) + (input_shape(model) if example is None else tuple(example.shape[1:]))
         self.n_streams = max(1, int(streams))
         self.xs = [torch.zeros(shape, device=dev) for _ in range(self.n_streams)]
         self.x = self.xs[0]
-        self.d = model.projector[-1].out_features
+        self.d = embedding_dim(model)
         self.epochs = (ops.WEIGHT_EPOCH, ops.STATS_EPOCH)
         self._held = None
         was_training = model.training
@@ -184,5 +203,5 @@ def fingerprints_from_waveform(model, front, wave: torch.Tensor, batch: int = 10
     MelSpectrogram + AmplitudeToDB + 87.5 %-overlap unfold) fused ahead of the encoder — SURVEY.md §8f-4."""
     segs = front(wave)
     if segs.shape[0] == 0:
-        return torch.empty((0, model.projector[-1].out_features), device=wave.device)
+        return torch.empty((0, embedding_dim(model)), device=wave.device)
     return extract_fingerprints(model, segs, batch)

@@ -76,11 +76,11 @@ def build_fp_db(model, songs: Iterable[Tuple[str, "object"]], output_root_dir: s
     writes them into the shared memmap; rank 0 writes the shape and lookup files (`barrier`: torch.distributed's by
     default). Call a barrier before reading."""
     import torch
-    from .fingerprint import extract_fingerprints
+    from .fingerprint import embedding_dim, extract_fingerprints
     songs = list(songs)
     counts = [int(s.shape[0]) for _, s in songs]
     n = sum(counts)
-    d = model.projector[-1].out_features
+    d = embedding_dim(model)
     lookup: List[str] = []
     for idx, ((nm, _), c) in enumerate(zip(songs, counts)):
         lookup.extend([f"{nm}_{idx}" if query_style else nm] * c)          # test_fp.py:110-115

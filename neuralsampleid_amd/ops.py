@@ -1535,3 +1535,90 @@ def clf_seg_reduce(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
             "nsid_clf_seg_reduce", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, N, nq_seg, nc_seg, _p(dq_seg), _p(dkv_seg),
             _stream()), (P, N, nq_seg + nc_seg, 1))
     return dq_seg, dkv_seg
+
+
+# ------------------------------------------------------------------------------------------------ ResNet-IBN baseline (csrc/resnet.hip)
+GEM_EPS = 1e-6
+IN_EPS = 1e-5
+
+
+def conv_out_size(n: int, ksize: int, stride: int) -> int:
+    """output extent of Conv2d(ksize, stride, padding=ksize // 2) (and of MaxPool2d(3, 2, 1), Conv2d(7, 2, 3)) on an extent of n"""
+    return (n + 2 * (ksize // 2) - ksize) // stride + 1
+
+
+def pack_conv_bn(w, gamma=None, beta=None, running_mean=None, running_var=None, eps=BN_EPS):
+    """Host routine (torch ops on whatever device the tensors live on; once per checkpoint, off the hot path): conv weight
+    (Cout, C, KH, KW) -> the packed (Cout, KH*KW*C) matrix nsid_conv2d_fwd reads (tap-major, channel fastest), with the eval-mode
+    BatchNorm behind the conv folded in: BN(conv(x)) = conv_{s w}(x) + (beta - mean s), s = gamma / sqrt(var + eps).
+    Returns (packed weight, bias); gamma None: no BatchNorm, bias None."""
+    with torch.no_grad():
+        wp = w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1)
+        if gamma is None:
+            return wp.contiguous(), None
+        s = gamma.detach() / torch.sqrt(running_var + eps)
+        return (wp * s[:, None]).contiguous(), (beta.detach() - running_mean * s).contiguous()
+
+
+def packed_conv_bn(conv_w, gamma, beta, running_mean, running_var, eps=BN_EPS):
+    """pack_conv_bn through the _FOLDED cache (keyed by the versions of the five tensors and the state epochs; bf16 shadow included)"""
+    return folded_conv_bn(lambda: pack_conv_bn(conv_w)[0], None, gamma, beta, running_mean, running_var, eps, source=conv_w)
+
+
+def conv2d_fwd(x, B, H, W, C, wp, bias, Cout, ksize, stride=1, addend=None, relu=False) -> torch.Tensor:
+    """x (B*H*W, C) rows -> (B*Ho*Wo, Cout) rows; wp (Cout, ksize*ksize*C) fp32 packed (pack_conv_bn): its bf16 shadow is the
+    operand under bf16 storage"""
+    _chk(wp, bias)
+    dt = _act(x, addend)
+    Ho, Wo = conv_out_size(H, ksize, stride), conv_out_size(W, ksize, stride)
+    M, K = B * Ho * Wo, ksize * ksize * C
+    if tuple(x.shape) != (B * H * W, C) or tuple(wp.shape) != (Cout, K) or (addend is not None and tuple(addend.shape) != (M, Cout)):
+        raise ValueError(f"conv2d_fwd: x {tuple(x.shape)} / wp {tuple(wp.shape)} do not match B={B} H={H} W={W} C={C} Cout={Cout} k={ksize}")
+    out = torch.empty((M, Cout), device=x.device, dtype=x.dtype)
+    wop = SHADOWS.operand(wp) if dt == BF16 else wp
+    esz = x.element_size()
+    _timed("conv2d_fwd_kernel<%dx%d,s%d>" % (ksize, ksize, stride), 2.0 * M * Cout * K,
+           esz * (B * H * W * C + M * Cout * (2 if addend is not None else 1)) + float(wop.element_size()) * Cout * K,
+           lambda: call("nsid_conv2d_fwd", _p(x), B, H, W, C, _p(wop), dt, _p(bias), _p(addend), _p(out), Cout, ksize, stride,
+                        ACT_RELU if relu else ACT_NONE, dt, _stream()), (M, Cout, K, 1))
+    return out
+
+
+def ibn_relu_fwd(x, B, HW, C, in_gamma, in_beta, bn_aff: "BNAffine", eps=IN_EPS, out=None) -> torch.Tensor:
+    """relu(IBN(x)) on rows (B*HW, C): instance norm (this clip's statistics) on channels [0, C/2), the eval BatchNorm affine on the rest"""
+    _chk(in_gamma, in_beta, bn_aff.scale, bn_aff.shift)
+    dt = _act(x, out)
+    if tuple(x.shape) != (B * HW, C) or in_gamma.numel() != C // 2 or bn_aff.scale.numel() != C - C // 2:
+        raise ValueError("ibn_relu_fwd: shapes do not match")
+    if out is None:
+        out = torch.empty_like(x)
+    _tk("ibn_relu_kernel", 4.0 * x.element_size() * x.numel(), lambda: call(
+        "nsid_ibn_relu_fwd", _p(x), B, HW, C, _p(in_gamma), _p(in_beta), eps, _p(bn_aff.scale), _p(bn_aff.shift), _p(out), dt,
+        _stream()), (B * HW, C, 0, 1))
+    return out
+
+
+def stem7_pool_fwd(x, w49, bias, out_dtype=torch.float32):
+    """x (B, H, W) fp32 -> (rows (B*Hp*Wp, 64), Hp, Wp): Conv 7x7 s2 p3 (w49: (64, 49), BatchNorm folded) + ReLU + MaxPool 3x3 s2 p1"""
+    _chk(x, w49, bias)
+    B, H, W = x.shape
+    Hp, Wp = conv_out_size(conv_out_size(H, 7, 2), 3, 2), conv_out_size(conv_out_size(W, 7, 2), 3, 2)
+    if tuple(w49.shape) != (64, 49) or bias.numel() != 64:
+        raise ValueError("stem7_pool_fwd: the stem is Conv2d(1, 64, 7)")
+    out = torch.empty((B * Hp * Wp, 64), device=x.device, dtype=out_dtype)
+    _timed("stem7_pool_kernel", 2.0 * 49 * 64 * B * conv_out_size(H, 7, 2) * conv_out_size(W, 7, 2),
+           4.0 * x.numel() + float(out.element_size()) * out.numel(), lambda: call(
+        "nsid_stem7_pool_fwd", _p(x), B, H, W, _p(w49), _p(bias), _p(out), _act(out), _stream()), (B * Hp * Wp, 64, 49, 1))
+    return out, Hp, Wp
+
+
+def gem_pool_fwd(x, B, HW, C, p, eps=GEM_EPS) -> torch.Tensor:
+    """rows (B*HW, C) -> (B, C) fp32 generalised-mean pooling; p: the (1,) parameter, read on the device"""
+    _chk(p)
+    dt = _act(x)
+    if tuple(x.shape) != (B * HW, C) or p.numel() != 1:
+        raise ValueError("gem_pool_fwd: shapes do not match")
+    out = torch.empty((B, C), device=x.device, dtype=torch.float32)
+    _tk("gem_pool_kernel", float(x.element_size()) * x.numel(), lambda: call(
+        "nsid_gem_pool_fwd", _p(x), B, HW, C, _p(p), eps, _p(out), dt, _stream()), (B * HW, C, 0, 1))
+    return out
