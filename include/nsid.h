@@ -380,12 +380,15 @@ int nsid_rows_to_bcn(const void* rows, int ld, int B, int C, int N, float* x, in
 
 /* ---- exact flat-L2 fingerprint search (eval.py:198-367 eval_faiss with index_type='l2': faiss.IndexFlatL2 + the sequence score of
  * every candidate, eval.py:318-331). fp32, row-major with leading dimensions, rows 16-byte aligned (ld % 4 == 0); d % 16 == 0 and
- * 16 <= d <= 256, 1 <= k <= 64, row counts below 2^31; NSID_EINVAL (nothing launched) otherwise.
+ * 16 <= d <= 256 (GraFP's fingerprints), or d % 64 == 0 and 256 < d <= 2048 (the ResNet-IBN baseline's: flat_l2_topk then runs its
+ * LDS-staged wide kernel, launch counter "flat_l2_topk_wide", under the same contract); 1 <= k <= 64, row counts below 2^31;
+ * NSID_EINVAL (nothing launched) otherwise.
  * row_sqnorm: out[i] = ||x_i||^2 in one fixed summation order (the index computes its rows' norms once, on add).
  * flat_l2_topk: per query row the k database rows of smallest key ||x_j||^2 - 2 q.x_j (the dot on v_mfma_f32_32x32x2_f32: one
  *   k-ordered fp32 fmaf chain), sorted ascending, equal keys smaller id first; D (nq x k) = max(0, ||q||^2 + key) (squared L2, as
  *   FAISS reports it), I (nq x k, int64) the row ids; k > nx: the tail is I = -1, D = +inf. A row's result is bitwise independent of
- *   the other rows of the call; no atomics. ws: nsid_workspace_bytes("flat_l2_topk", nq, nx) bytes (enough for any k <= 64).
+ *   the other rows of the call and of how the database is split; no atomics. ws: nsid_workspace_bytes("flat_l2_topk", nq, nx)
+ *   bytes (enough for any supported d and any k <= 64).
  * seq_scores: for pair p = (s = starts[p], L = lens[p]) (device int32; the caller guarantees s + L <= the rows of q and of I) and
  *   candidate j < L*k with cid = I[s + j/k][j%k]: out[p*ldo + j] = mean over i < min(L, nx - cid) of q[s+i].x[cid+i] (fp32),
  *   NaN when cid < 0 and for L*k <= j < ldo (eval.py:325-331, the window truncated at the end of the index). ldo <= 262140. */

@@ -11,6 +11,8 @@
 //     entry is the threshold, so almost every score is rejected by one compare. Survivors are appended to a per-row LDS queue, which
 //     is merged into the list (rank by the total order (key, id, slot)) when it fills. The list goes to the workspace.
 //  2. one workgroup per query row merges the splits' lists the same way and writes D = max(0, ||q||^2 + key) and int64 ids.
+// Above d = 256 (the ResNet-IBN baseline's 2048-d fingerprints) phase 1 is l2_topk_wide_kernel, which stages both operands through
+// LDS per K chunk; lists, queues, phase 2 and every invariant are the same.
 // No atomics anywhere on the ranking path.
 #include "nsid_common.h"
 
@@ -64,6 +66,54 @@ __device__ __forceinline__ void merge_queue(KI* list, const KI* queue, int cnt, 
 }
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// one wave, one finished 32x32 tile: accumulator register g of lane (r, h) = (lane & 31, lane >> 5) is query row
+// (g & 3) + 8 (g >> 2) + 4 h of the tile against database row `col` (cv: the row exists, xv its squared norm). Scores that pass
+// their row's threshold (the k-th list entry) go to the row's queue, which is merged into the list when it would overflow.
+__device__ __forceinline__ void offer_tile(KI (*list)[L2_LIST], KI (*queue)[L2_Q1], int* cnt, const f32x16& acc, int col, bool cv,
+                                           float xv, int k, int lane) {
+  const int h = lane >> 5;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
+    const KI c{xv - (acc[g] + acc[g]), col};
+    const bool pass = cv && ki_before(c, list[row][k - 1]);
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
+    if (m == 0) continue;
+    const int n0 = __builtin_popcountll(m & 0xffffffffull), n1 = __builtin_popcountll(m >> 32);
+    const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) - (h ? n0 : 0);
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int n = hh ? n1 : n0;
+      if (n == 0) continue;
+      const int rr = (g & 3) + 8 * (g >> 2) + 4 * hh;
+      int c0 = __builtin_amdgcn_readfirstlane(cnt[rr]);
+      if (c0 + n > L2_Q1) {
+        merge_queue(list[rr], queue[rr], c0, k, lane);
+        c0 = 0;
+      }
+      if (pass && h == hh) queue[rr][c0 + pos] = c;
+      __builtin_amdgcn_wave_barrier();
+      if (lane == 0) cnt[rr] = c0 + n;
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+}
+
+// the wave's lists of query rows q0.. go to workspace slot `slot` of `nslot` per row
+__device__ __forceinline__ void flush_lists(KI (*list)[L2_LIST], KI (*queue)[L2_Q1], const int* cnt, int q0, int nq, int nslot, int slot,
+                                            int k, int lane, float* __restrict__ wkey, int* __restrict__ wid) {
+  for (int rr = 0; rr < L2_QT; ++rr) {
+    if (q0 + rr >= nq) break;
+    const int c0 = __builtin_amdgcn_readfirstlane(cnt[rr]);
+    if (c0 > 0) merge_queue(list[rr], queue[rr], c0, k, lane);
+    if (lane < k) {
+      const size_t o = ((size_t)(q0 + rr) * nslot + slot) * k + lane;
+      wkey[o] = list[rr][lane].k;
+      wid[o] = list[rr][lane].i;
+    }
+  }
+}
 
 // ---- phase 1 ----------------------------------------------------------------------------------------------------------------
 // Lane (r, h) = (lane & 31, lane >> 5). MFMA step (b, e) pairs k = 8b + e (h = 0) with k = 8b + 4 + e (h = 1), so a lane reads
@@ -125,44 +175,159 @@ __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restri
 
     const int col = lo + tile * 32 + r;
     const bool cv = col < hi;
-    const float xv = cv ? xn[col] : 0.f;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) {
-      const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
-      const KI c{xv - (acc[g] + acc[g]), col};
-      const bool pass = cv && ki_before(c, list[row][k - 1]);
-      const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
-      if (m == 0) continue;
-      const int n0 = __builtin_popcountll(m & 0xffffffffull), n1 = __builtin_popcountll(m >> 32);
-      const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)) - (h ? n0 : 0);
-#pragma unroll
-      for (int hh = 0; hh < 2; ++hh) {
-        const int n = hh ? n1 : n0;
-        if (n == 0) continue;
-        const int rr = (g & 3) + 8 * (g >> 2) + 4 * hh;
-        int c0 = __builtin_amdgcn_readfirstlane(cnt[rr]);
-        if (c0 + n > L2_Q1) {
-          merge_queue(list[rr], queue[rr], c0, k, lane);
-          c0 = 0;
-        }
-        if (pass && h == hh) queue[rr][c0 + pos] = c;
-        __builtin_amdgcn_wave_barrier();
-        if (lane == 0) cnt[rr] = c0 + n;
-        __builtin_amdgcn_wave_barrier();
-      }
-    }
+    offer_tile(list, queue, cnt, acc, col, cv, cv ? xn[col] : 0.f, k, lane);
   }
 
-  for (int rr = 0; rr < L2_QT; ++rr) {
-    if (q0 + rr >= nq) break;
-    const int c0 = __builtin_amdgcn_readfirstlane(cnt[rr]);
-    if (c0 > 0) merge_queue(list[rr], queue[rr], c0, k, lane);
-    if (lane < k) {
-      const size_t o = ((size_t)(q0 + rr) * S + s) * k + lane;
-      wkey[o] = list[rr][lane].k;
-      wid[o] = list[rr][lane].i;
+  flush_lists(list, queue, cnt, q0, nq, S, s, k, lane, wkey, wid);
+}
+
+// ---- phase 1, wide rows (256 < d <= 2048) -------------------------------------------------------------------------------------
+// A 32-row query tile no longer fits in registers (d / 8 f32x4 per lane), so a workgroup of 4 waves walks K in chunks of 32 floats
+// and stages a block of query rows and a block of database rows per chunk through LDS. Wave w = (wq, wc) owns query rows
+// 32 wq.. of the block and NACC column tiles of 32 database rows, one accumulator each: NACC independent MFMA chains keep the
+// 64-cycle v_mfma_f32_32x32x2_f32 issuing back to back, and the accumulator of an (i, j) pair stays in one lane for the whole
+// K loop. MFMA step t of chunk c pairs k = 32c + 2t (h = 0) with k = 32c + 2t + 1 (h = 1): the chain runs k = 0 .. d-1 in order
+// whatever block, wave or split holds the pair.
+//   WQ = 4: 128 query rows x 128 database rows, every wave 4 accumulators over the whole column block.
+//   WQ = 1 (nq <= 32, nx > 128): 32 query rows x 256 database rows, every wave 2 accumulators over its own 64 columns; the four
+//     waves keep separate lists, which phase 2 merges like splits (workspace slot 4 s + wc).
+// Stages are k-major, [32][rows + 1] floats: the MFMA operand is one float per lane, A[i = l & 31][k = l >> 5], so a half-wave
+// reads 32 consecutive floats of one k (32 banks; a row-major [row][32] stage would put them all on one). The +1 pad serves the
+// transposing store: a thread holds 4 consecutive k of one row, 8 threads share a row, and with a stride = 1 mod 32 the 32 lanes of
+// a half-wave (4 rows x 8 k-quads) write 32 different banks. One stage per operand, the next two chunks prefetched in registers.
+// LDS: the lists, queues and counters of the narrow kernel per wave (4 x 24.1 KB) + 2 x 16.1 KB (WQ = 4) or 4.1 + 32.1 KB of stages.
+constexpr int L2W_KC = 32;           // floats of K per stage
+constexpr int L2W_UNITS = 512;       // workgroups phase 1 aims at: one per CU fits (LDS), two rounds of 256
+template <int WQ>
+struct L2Wide {
+  static constexpr int WC = 4 / WQ, NACC = WQ == 4 ? 4 : 2;
+  static constexpr int BQ = 32 * WQ, BC = 32 * WC * NACC;
+  static constexpr int QS = BQ + 1, XS = BC + 1;
+  static constexpr size_t lds = 4 * (sizeof(KI) * L2_QT * (L2_LIST + L2_Q1) + sizeof(int) * L2_QT) + sizeof(float) * L2W_KC * (QS + XS);
+};
+
+template <int WQ>
+__global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x,
+                                                           int ldx, int nx, const float* __restrict__ xn, int d, int k, int nqb, int S,
+                                                           int chunk, float* __restrict__ wkey, int* __restrict__ wid) {
+  using C = L2Wide<WQ>;
+  constexpr int WC = C::WC, NACC = C::NACC, BQ = C::BQ, BC = C::BC, QS = C::QS, XS = C::XS;
+  constexpr int QL = BQ / 32, XL = BC / 32;      // f32x4 per thread and chunk
+  extern __shared__ __attribute__((aligned(16))) char l2w_smem[];
+  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  KI(*list)[L2_LIST] = reinterpret_cast<KI(*)[L2_LIST]>(l2w_smem) + w * L2_QT;
+  KI(*queue)[L2_Q1] = reinterpret_cast<KI(*)[L2_Q1]>(l2w_smem + 4 * sizeof(KI) * L2_QT * L2_LIST) + w * L2_QT;
+  int* cnt = reinterpret_cast<int*>(l2w_smem + 4 * sizeof(KI) * L2_QT * (L2_LIST + L2_Q1)) + w * L2_QT;
+  float* qs = reinterpret_cast<float*>(l2w_smem + 4 * (sizeof(KI) * L2_QT * (L2_LIST + L2_Q1) + sizeof(int) * L2_QT));
+  float* xs = qs + L2W_KC * QS;
+
+  const int r = lane & 31, h = lane >> 5;
+  const int wq = w % WQ, wc = w / WQ;
+  const int qb = blockIdx.x % nqb, s = blockIdx.x / nqb;
+  const int q0 = qb * BQ, wq0 = q0 + 32 * wq;
+  const int lo = s * chunk, hi = min(nx, lo + chunk);
+  const bool active = wq0 < nq;                  // a wave whose rows all lie past nq only helps staging
+
+  for (int t = lane; t < L2_QT * L2_LIST; t += 64) list[t / L2_LIST][t % L2_LIST] = ki_pad();
+  if (lane < L2_QT) cnt[lane] = 0;
+  if (lane < L2_QT && wq0 + lane >= nq) list[lane][k - 1] = KI{-__builtin_inff(), 0};
+  __builtin_amdgcn_wave_barrier();
+
+  const int nblk = hi > lo ? (hi - lo + BC - 1) / BC : 0;
+  const int nkc = d / L2W_KC;                    // even: d % 64 == 0
+  const int ng = nblk * nkc;                     // chunks in all; two are in flight in registers (g0 / g1: even / odd chunks)
+  const int kq = tid & 7, rb = tid >> 3;         // the thread's k-quad of the chunk and its row (+ 32 i) of the block
+  f32x4 gq0[QL], gx0[XL], gq1[QL], gx1[XL];
+  int lblk = 0, lc = 0;                          // the next chunk to load
+  auto gload = [&](f32x4* gq, f32x4* gx) {
+    const int ko = L2W_KC * lc + 4 * kq;
+#pragma unroll
+    for (int i = 0; i < QL; ++i)                 // rows past nq: any valid row, their scores meet a threshold nothing passes
+      gq[i] = ld4(q + (size_t)min(q0 + rb + 32 * i, nq - 1) * ldq + ko);
+#pragma unroll
+    for (int i = 0; i < XL; ++i) gx[i] = ld4(x + (size_t)min(lo + lblk * BC + rb + 32 * i, hi - 1) * ldx + ko);
+    if (++lc == nkc) {
+      lc = 0;
+      ++lblk;
     }
+  };
+  auto stage = [&](const f32x4* gq, const f32x4* gx) {
+    __syncthreads();                             // every wave has read the previous chunk
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+#pragma unroll
+      for (int i = 0; i < QL; ++i) qs[(4 * kq + e) * QS + rb + 32 * i] = gq[i][e];
+#pragma unroll
+      for (int i = 0; i < XL; ++i) xs[(4 * kq + e) * XS + rb + 32 * i] = gx[i][e];
+    }
+    __syncthreads();
+  };
+
+  f32x16 acc[NACC];
+#pragma unroll
+  for (int n = 0; n < NACC; ++n) acc[n] = f32x16{};
+  const float* ap = qs + h * QS + 32 * wq + r;
+  const float* bp = xs + h * XS + 32 * NACC * wc + r;
+  // one staged chunk: 16 MFMA steps; the operands of step t + AHEAD are read from LDS before the MFMAs of step t issue, and the
+  // fences keep the compiler from gathering the reads in front of the chunk (registers) or behind their use (LDS latency exposed).
+  // The first AHEAD steps are read (first_reads) before the next chunk's global loads are issued, the rest inside run_chunk.
+  constexpr int NT = L2W_KC / 2, AHEAD = 4;
+  float a[2 * AHEAD], b[2 * AHEAD][NACC];
+  auto rd = [&](int t) {
+    a[t % (2 * AHEAD)] = ap[2 * t * QS];
+#pragma unroll
+    for (int n = 0; n < NACC; ++n) b[t % (2 * AHEAD)][n] = bp[2 * t * XS + 32 * n];
+  };
+  auto first_reads = [&]() {
+#pragma unroll
+    for (int t = 0; t < AHEAD; ++t) rd(t);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto run_chunk = [&]() {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      if (t + AHEAD < NT) rd(t + AHEAD);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int n = 0; n < NACC; ++n)
+        acc[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[t % (2 * AHEAD)], b[t % (2 * AHEAD)][n], acc[n], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+  if (ng > 0) {
+    gload(gq0, gx0);
+    gload(gq1, gx1);
   }
+  for (int g = 0; g < ng; g += 2) {
+    stage(gq0, gx0);
+    if (active) first_reads();
+    if (g + 2 < ng) gload(gq0, gx0);
+    if (active) run_chunk();
+    stage(gq1, gx1);
+    if (active) first_reads();
+    if (g + 3 < ng) gload(gq1, gx1);
+    if (active) run_chunk();
+    if ((g + 2) % nkc != 0) continue;
+    const int blk = g / nkc;                     // the block's last chunk: its tiles meet the lists
+    if (active) {
+      auto offer_n = [&](const f32x16& tile, int n) {
+        const int col = lo + blk * BC + 32 * (NACC * wc + n) + r;
+        const bool cv = col < hi;
+        offer_tile(list, queue, cnt, tile, col, cv, cv ? xn[col] : 0.f, k, lane);
+      };
+      offer_n(acc[0], 0);                        // spelled out: a loop the compiler declines to unroll would index acc through scratch
+      offer_n(acc[1], 1);
+      if constexpr (NACC == 4) {
+        offer_n(acc[2], 2);
+        offer_n(acc[3], 3);
+      }
+    }
+#pragma unroll
+    for (int n = 0; n < NACC; ++n) acc[n] = f32x16{};
+  }
+
+  if (active) flush_lists(list, queue, cnt, wq0, nq, S * WC, s * WC + wc, k, lane, wkey, wid);
 }
 
 // ---- phase 2: one workgroup of 4 waves per query row ---------------------------------------------------------------------------
@@ -269,7 +434,8 @@ __global__ __launch_bounds__(256) void seq_scores_kernel(const float* __restrict
   if (lane == 0) out[(size_t)p * ldo + j] = v;
 }
 
-bool l2_shape_ok(int d) { return d % 16 == 0 && d >= 16 && d <= 256; }
+bool l2_wide(int d) { return d > 256; }
+bool l2_shape_ok(int d) { return (d % 16 == 0 && d >= 16 && d <= 256) || (d % 64 == 0 && l2_wide(d) && d <= 2048); }
 
 template <int D>
 int launch_split(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int k, int nqt, int S, int chunk,
@@ -289,6 +455,42 @@ int dispatch_split(int d, const float* q, int ldq, int nq, const float* x, int l
   return rc;
 }
 
+// split plan of the wide phase 1: query blocks of 128 rows (32 in the WQ = 1 form), splits of whole column blocks;
+// *slots = lists per query row in the workspace
+// the 32 x 256 form spreads the database over the four waves' columns; up to one 128-row column block there is nothing to spread
+bool l2_wide_one(long nq, long nx) { return nq <= L2_QT && nx > L2Wide<4>::BC; }
+
+void l2_plan_wide(long nq, long nx, int* splits, int* chunk, int* slots) {
+  const bool one = l2_wide_one(nq, nx);
+  const long bq = one ? L2Wide<1>::BQ : L2Wide<4>::BQ, bc = one ? L2Wide<1>::BC : L2Wide<4>::BC;
+  const long nqb = (nq + bq - 1) / bq;
+  long S = nqb > 0 ? (L2W_UNITS + nqb - 1) / nqb : 1;
+  S = std::min(S, std::max(1L, nx / L2_MIN_SPLIT));
+  long c = (nx + S - 1) / S;
+  c = (c + bc - 1) / bc * bc;
+  if (c == 0) c = bc;
+  S = std::max(1L, (nx + c - 1) / c);
+  *splits = (int)S;
+  *chunk = (int)c;
+  *slots = (int)(S * (one ? L2Wide<1>::WC : L2Wide<4>::WC));
+}
+
+template <int WQ>
+int launch_wide(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int d, int k, int S, int chunk,
+                float* wkey, int* wid, hipStream_t st) {
+  static bool configured = false;
+  if (!configured) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(l2_topk_wide_kernel<WQ>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)L2Wide<WQ>::lds) != hipSuccess)
+      return NSID_ELAUNCH;
+    configured = true;
+  }
+  const int nqb = (nq + L2Wide<WQ>::BQ - 1) / L2Wide<WQ>::BQ;
+  hipLaunchKernelGGL((l2_topk_wide_kernel<WQ>), dim3(nqb * S), dim3(256), L2Wide<WQ>::lds, st, q, ldq, nq, x, ldx, nx, xn, d, k, nqb, S,
+                     chunk, wkey, wid);
+  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+}
+
 }  // namespace
 
 // split plan of phase 1: enough waves for 256 CUs x 8, splits of at least L2_MIN_SPLIT rows, each a multiple of 32 rows
@@ -304,10 +506,12 @@ void nsid_l2_plan(long nq, long nx, int* splits, int* chunk) {
   *chunk = (int)c;
 }
 
+// enough for either plan: the caller of nsid_workspace_bytes does not say d
 long nsid_l2_ws_bytes(long nq, long nx, int k) {
-  int S, c;
+  int S, c, Sw, slots;
   nsid_l2_plan(nq, nx, &S, &c);
-  return (long)S * nq * k * (long)(sizeof(float) + sizeof(int));
+  l2_plan_wide(nq, nx, &Sw, &c, &slots);
+  return (long)std::max(S, slots) * nq * k * (long)(sizeof(float) + sizeof(int));
 }
 
 extern "C" int nsid_row_sqnorm(const float* x, int ldx, int n, int d, float* out, void* stream) {
@@ -325,19 +529,31 @@ extern "C" int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x
   if (nq == 0) return NSID_OK;
   NSID_REQUIRE(q && q_sqnorm && D && I && ws && ldq >= d && ldq % 4 == 0 && nsid_aligned16(q) && nsid_aligned16(ws));
   NSID_REQUIRE(nx == 0 || (x && x_sqnorm && ldx >= d && ldx % 4 == 0 && nsid_aligned16(x)));
-  int S, chunk;
-  nsid_l2_plan(nq, nx, &S, &chunk);
-  const size_t per = (size_t)S * nq * k;
+  int S, chunk, slots;
+  if (l2_wide(d)) {
+    l2_plan_wide(nq, nx, &S, &chunk, &slots);
+  } else {
+    nsid_l2_plan(nq, nx, &S, &chunk);
+    slots = S;
+  }
+  const size_t per = (size_t)slots * nq * k;
   NSID_REQUIRE(ws_bytes >= per * (sizeof(float) + sizeof(int)));
   float* wkey = static_cast<float*>(ws);
   int* wid = reinterpret_cast<int*>(wkey + per);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nqt = (nq + L2_QT - 1) / L2_QT;
   nsid_count(NSID_C_flat_l2_topk);
-  const int rc = dispatch_split<16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
-      d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, st);
+  int rc;
+  if (l2_wide(d)) {
+    nsid_count(NSID_C_flat_l2_topk_wide);
+    rc = l2_wide_one(nq, nx) ? launch_wide<1>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, st)
+                     : launch_wide<4>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, st);
+  } else {
+    rc = dispatch_split<16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
+        d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, st);
+  }
   if (rc != NSID_OK) return rc;
-  hipLaunchKernelGGL(l2_topk_merge_kernel, dim3(nq), dim3(256), 0, st, wkey, wid, S, k, q_sqnorm, D, I);
+  hipLaunchKernelGGL(l2_topk_merge_kernel, dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
   return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
 }
 

@@ -1275,17 +1275,24 @@ def rows_to_bcn(rows, B, N) -> torch.Tensor:
 
 # ------------------------------------------------------------------------------------------------ exact flat-L2 search (csrc/search.hip)
 SEARCH_MAX_K = 64
+SEARCH_D_LIMITS = "d % 16 == 0 and 16 <= d <= 256, or d % 64 == 0 and 256 < d <= 2048"
+
+
+def search_d_ok(d) -> bool:
+    """the row widths csrc/search.hip takes (l2_shape_ok): above 256 flat_l2_topk runs its LDS-staged wide kernel"""
+    return (d % 16 == 0 and 16 <= d <= 256) or (d % 64 == 0 and 256 < d <= 2048)
 
 
 def _search_rows(t, name):
-    """a (n, d) fp32 matrix on the GPU with unit column stride and 16-byte rows; d % 16 == 0, 16 <= d <= 256"""
+    """a (n, d) fp32 matrix on the GPU with unit column stride and 16-byte rows; d % 16 == 0 and 16 <= d <= 256, or d % 64 == 0
+    and 256 < d <= 2048 (SEARCH_D_LIMITS)"""
     if not t.is_cuda:
         raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
     if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
         raise RuntimeError(f"{name}: expected a (rows, d) float32 matrix with unit column stride and 16-byte aligned rows")
     d = t.shape[1]
-    if d % 16 or not 16 <= d <= 256:
-        raise ValueError(f"{name}: d = {d} is outside the search kernels' limits (d % 16 == 0, 16 <= d <= 256)")
+    if not search_d_ok(d):
+        raise ValueError(f"{name}: d = {d} is outside the search kernels' limits ({SEARCH_D_LIMITS})")
     return max(t.stride(0), d)
 
 
@@ -1320,7 +1327,7 @@ def flat_l2_topk(q, x, x_sqnorm, k, q_sqnorm=None) -> Tuple[torch.Tensor, torch.
         return D, I
     wsb = int(lib.nsid_workspace_bytes(b"flat_l2_topk", nq, nx))
     ws = torch.empty((max(wsb, 16),), device=q.device, dtype=torch.uint8)
-    # phase 1 streams the database once per split pass (512 B per row at d = 128) and runs 2 nq nx d flop on the fp32 matrix pipe
+    # phase 1 streams the database once per query block (32 rows; 128 at d > 256) and runs 2 nq nx d flop on the fp32 matrix pipe
     _timed("flat_l2_topk", 2.0 * nq * nx * d, 4.0 * nx * d + 4.0 * nq * d + 12.0 * nq * k, lambda: call(
         "nsid_flat_l2_topk", _p(q), ldq, nq, _p(x) if nx else None, ldx, nx, _p(x_sqnorm) if nx else None, _p(q_sqnorm), d, k,
         _p(D), _p(I), _p(ws), ws.numel(), _stream()), (nq, nx, d, k))

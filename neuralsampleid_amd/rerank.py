@@ -28,8 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .search import FlatL2Index, _load_gt, _open_rows, _slabs, extract_test_ids, format_hit_rates, parse_seq_len
-from . import fpdb
+from .search import _load_db, _load_gt, extract_test_ids, format_hit_rates, parse_seq_len
 
 OUT_BLOCK = 1 << 26           # scores per clf_pair_scores call at most (256 MB of output)
 PROJ_BLOCK = 4096             # segments per projection call
@@ -264,30 +263,6 @@ def score_tests(classifier, tests, query_nm: Dict[str, np.ndarray], ref_nmatrix_
                 results[t] = (tests[t][2], host[o:o + rows * ci.size].reshape(rows, ci.size))
             a = b
     return results
-
-
-def _load_db(emb_dir, emb_dummy_dir, query_name, device):
-    query = _open_rows(emb_dir, query_name)
-    ref = _open_rows(emb_dir, "ref_db")
-    dummy = _open_rows(emb_dummy_dir, "dummy_db")
-    d = query.shape[1]
-    if ref.shape[1] != d or dummy.shape[1] != d:
-        raise ValueError(f"dimension mismatch: query {query.shape}, ref {ref.shape}, dummy {dummy.shape}")
-    query_lookup = fpdb.load_lookup(emb_dir, query_name)
-    ref_lookup = fpdb.load_lookup(emb_dir, "ref_db")
-    if len(query_lookup) != query.shape[0] or len(ref_lookup) != ref.shape[0]:
-        raise ValueError("a lookup table does not have one entry per database row")
-    index = FlatL2Index(d, device)
-    for s in _slabs(dummy, d):
-        index.add(s)
-    for s in _slabs(ref, d):
-        index.add(s)
-    qt = torch.empty((query.shape[0], d), device=index.device, dtype=torch.float32)
-    row = 0
-    for s in _slabs(query, d):
-        qt[row:row + s.shape[0]].copy_(torch.from_numpy(s))
-        row += s.shape[0]
-    return index, qt, query_lookup, ref_lookup, dummy.shape[0]
 
 
 def _load_query_nm(path):

@@ -29,8 +29,8 @@ class FlatL2Index:
 
     def __init__(self, d: int, device="cuda"):
         d = int(d)
-        if d % 16 or not 16 <= d <= 256:
-            raise ValueError(f"FlatL2Index: d = {d} is outside the search kernels' limits (d % 16 == 0, 16 <= d <= 256)")
+        if not ops.search_d_ok(d):
+            raise ValueError(f"FlatL2Index: d = {d} is outside the search kernels' limits ({ops.SEARCH_D_LIMITS})")
         self.d = d
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -226,6 +226,32 @@ def _slabs(mm, d):
         yield s
 
 
+def _load_db(emb_dir, emb_dummy_dir, query_name, device):
+    """the databases of one evaluation: (FlatL2Index over dummy ++ ref, the query rows on its device, query lookup, ref lookup,
+    rows of dummy_db). Shared by eval_hit_rates, rerank.py and baseline_eval.py."""
+    query = _open_rows(emb_dir, query_name)
+    ref = _open_rows(emb_dir, "ref_db")
+    dummy = _open_rows(emb_dummy_dir, "dummy_db")
+    d = query.shape[1]
+    if ref.shape[1] != d or dummy.shape[1] != d:
+        raise ValueError(f"dimension mismatch: query {query.shape}, ref {ref.shape}, dummy {dummy.shape}")
+    query_lookup = fpdb.load_lookup(emb_dir, query_name)
+    ref_lookup = fpdb.load_lookup(emb_dir, "ref_db")
+    if len(query_lookup) != query.shape[0] or len(ref_lookup) != ref.shape[0]:
+        raise ValueError("a lookup table does not have one entry per database row")
+    index = FlatL2Index(d, device)
+    for s in _slabs(dummy, d):                                        # index.add(dummy_db); index.add(db): eval.py:243-244
+        index.add(s)
+    for s in _slabs(ref, d):
+        index.add(s)
+    qt = torch.empty((query.shape[0], d), device=index.device, dtype=torch.float32)
+    row = 0
+    for s in _slabs(query, d):
+        qt[row:row + s.shape[0]].copy_(torch.from_numpy(s))
+        row += s.shape[0]
+    return index, qt, query_lookup, ref_lookup, dummy.shape[0]
+
+
 def eval_hit_rates(emb_dir: str, gt: Union[str, Dict[str, Sequence[str]]], emb_dummy_dir: Optional[str] = None,
                    test_seq_len='1 3 5 9 11 19', k_probe: int = 20, save: bool = True, device="cuda"):
     """eval.py eval_faiss(emb_dir, emb_dummy_dir, index_type='l2', test_seq_len=..., k_probe=...) on the GPU.
@@ -240,27 +266,7 @@ def eval_hit_rates(emb_dir: str, gt: Union[str, Dict[str, Sequence[str]]], emb_d
     if not 1 <= k_probe <= ops.SEARCH_MAX_K:
         raise ValueError(f"k_probe = {k_probe} is outside [1, {ops.SEARCH_MAX_K}]")
     emb_dummy_dir = emb_dir if emb_dummy_dir is None else emb_dummy_dir
-    query = _open_rows(emb_dir, "query_db")
-    ref = _open_rows(emb_dir, "ref_db")
-    dummy = _open_rows(emb_dummy_dir, "dummy_db")
-    d = query.shape[1]
-    if ref.shape[1] != d or dummy.shape[1] != d:
-        raise ValueError(f"dimension mismatch: query {query.shape}, ref {ref.shape}, dummy {dummy.shape}")
-    query_lookup = fpdb.load_lookup(emb_dir, "query_db")
-    ref_lookup = fpdb.load_lookup(emb_dir, "ref_db")
-    if len(query_lookup) != query.shape[0] or len(ref_lookup) != ref.shape[0]:
-        raise ValueError("a lookup table does not have one entry per database row")
-
-    index = FlatL2Index(d, device)
-    for s in _slabs(dummy, d):                                        # index.add(dummy_db); index.add(db): eval.py:243-244
-        index.add(s)
-    for s in _slabs(ref, d):
-        index.add(s)
-    qt = torch.empty((query.shape[0], d), device=index.device, dtype=torch.float32)
-    row = 0
-    for s in _slabs(query, d):
-        qt[row:row + s.shape[0]].copy_(torch.from_numpy(s))
-        row += s.shape[0]
+    index, qt, query_lookup, ref_lookup, n_dummy = _load_db(emb_dir, emb_dummy_dir, "query_db", device)
 
     # every query row is searched once: a (test, length) pair uses rows [start, start + length) of the one result
     _, I = index.search(qt, k_probe)
@@ -268,7 +274,7 @@ def eval_hit_rates(emb_dir: str, gt: Union[str, Dict[str, Sequence[str]]], emb_d
     _, _, ps, pl = make_pairs(starts, lens, sl)
     scores = ops.seq_scores(qt, index.xb, I, ps, pl, int(sl.max()) * k_probe)
     hit_rates, raw_score, test_ids = aggregate_hit_rates(I.cpu().numpy(), scores.cpu().numpy(), query_lookup, ref_lookup,
-                                                         dummy.shape[0], gt, sl)
+                                                         n_dummy, gt, sl)
     if save:
         np.save(os.path.join(emb_dir, "hit_rates.npy"), hit_rates)
         np.save(os.path.join(emb_dir, "raw_score.npy"), raw_score)
