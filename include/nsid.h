@@ -400,7 +400,9 @@ int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, in
 
 /* ---- classifier re-rank (downstream.py:30-78 CrossAttentionClassifier in eval mode, as eval_hr.py::eval_faiss_clf and
  * eval_map.py::eval_faiss_map_clf call it). fp32; C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing
- * launched) otherwise.
+ * launched) otherwise. The entries with a _c suffix carry the width: C in {512, 640, 768, 1024} (the four encoder sizes), 4 heads
+ * of C / 4; every "512" below reads C, the softmax scale 1 / sqrt(C / 4), and the [K | P] rows C + 512 floats (P stays 4 x 128);
+ * any other C is NSID_EINVAL. The entries without the suffix are the _c entries at C = 512.
  * clf_node_rows: rows[(s N + n) C + c] = x[(s C + c) N + n] + pos[n C + c] ((S, C, N) node matrices to node rows; pos may be NULL;
  *   C % 32 == 0).
  * clf_pair_scores: q (nq_seg N x 512): the queries' projected rows Q / sqrt(128) (pos and bias included); kp (nc_seg N x 1024): the
@@ -413,10 +415,16 @@ int nsid_clf_node_rows(const float* x, int S, int C, int N, const float* pos, fl
 int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups, const int64_t* out_off,
                          const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail, float* out,
                          int64_t out_len, void* stream);
+int nsid_clf_pair_scores_c(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
+                           const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail,
+                           float* out, int64_t out_len, void* stream);
 
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed
  * order and no entry uses atomics: a pair's score and its per-pair gradients depend on nothing but the pair.
+ * clf_attn_fwd_c, clf_attn_bwd_c and clf_seg_reduce_c carry the width: C in {512, 640, 768, 1024}, 4 heads of C / 4, scale
+ *   1 / sqrt(C / 4), [K | V] rows of 2 C floats, obar / dobar P x C, dq / dk P x N x C; attn and abar keep their layouts. Any other C is
+ *   NSID_EINVAL. The entries without the suffix are the _c entries at C = 512.
  * clf_mine_hard_negatives: out[i k + r - 1] (int64) = the index of rank r = 1..k of row i of zq (nq x d) . za^T (na x d) in
  *   descending order, ties to the smaller index; fp32 dots, each a sequential fma chain over d. 4 <= d <= 512, d % 4 == 0,
  *   na <= 8192, 1 <= k <= na - 1; za 16-byte aligned.
@@ -441,6 +449,12 @@ int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int
                       const int* qi, const int* ci, int P, float* dq, float* dk, void* stream);
 int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi, const int* ci, int P,
                         int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream);
+int nsid_clf_attn_fwd_c(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci, int P,
+                        float* obar, float* attn, float* abar, void* stream);
+int nsid_clf_attn_bwd_c(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N,
+                        const int* qi, const int* ci, int P, float* dq, float* dk, void* stream);
+int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi, const int* ci, int P,
+                          int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream);
 
 /* ---- ResNet-IBN baseline, eval-mode forward (encoder/resnet_ibn.py; simclr/triplet.py:65-83 BaselineModel). Activations are
  * channels-last rows: a (B, C, H, W) reference tensor is the matrix X[B*H*W][C], row = (b*H + h)*W + w. csrc/resnet.hip.

@@ -74,12 +74,16 @@ SIGNATURES = {
     "nsid_seq_scores": "pipiiipippipis",
     "nsid_clf_node_rows": "piiipps",
     "nsid_clf_pair_scores": "pipiipppiipppls",
+    "nsid_clf_pair_scores_c": "pipiiipppiipppls",
     "nsid_clf_mine_hard_negatives": "pipiiips",
     "nsid_clf_attn_fwd": "pipiippippps",
     "nsid_clf_head_fwd": "ppppips",
     "nsid_clf_head_bwd": "pppppipppps",
     "nsid_clf_attn_bwd": "pppipiippipps",
     "nsid_clf_seg_reduce": "ppppppiiiipps",
+    "nsid_clf_attn_fwd_c": "pipiiippippps",
+    "nsid_clf_attn_bwd_c": "pppipiiippipps",
+    "nsid_clf_seg_reduce_c": "ppppppiiiiipps",
     "nsid_conv2d_fwd": "piiiipipppiiiiis",
     "nsid_ibn_relu_fwd": "piiippfpppis",
     "nsid_stem7_pool_fwd": "piiipppis",

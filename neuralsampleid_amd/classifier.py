@@ -7,12 +7,13 @@ g + sum_h G_h V_h^T a_h (a_h = the column mean of head h's attention), and the c
 is one linear per segment. The per-segment projections run on the project's fp32 GEMM (ops.linear_fwd), the per-pair work in
 nsid_clf_pair_scores.
 
-    clf = CrossAttentionClassifier(512, num_nodes=32).cuda().eval()
+    clf = CrossAttentionClassifier(C, num_nodes=32).cuda().eval()      # C = the encoder's last width: 512, 640, 768 or 1024
     clf.load_state_dict(torch.load("clf.pth"))
     with torch.no_grad():
-        s = clf.pair_scores(nm_query, nm_cand)        # (Sq, 512, N), (Sc, 512, N) -> (Sq, Sc)
+        s = clf.pair_scores(nm_query, nm_cand)        # (Sq, C, N), (Sc, C, N) -> (Sq, Sc)
 
-Supported: in_dim 512, 4 heads, hidden_dim 128, N <= 32 (and N <= num_nodes with pos_embed), fp32 contiguous inputs; anything else
+Supported: in_dim 512, 640, 768 or 1024 (the encoder sizes 't', 's', 'm' and the default; head dim in_dim / 4), 4 heads, hidden_dim
+128, N <= 32 (and N <= num_nodes with pos_embed), fp32 contiguous inputs whose channel count is the module's in_dim; anything else
 raises before a launch. This module's forward stays the eval-mode re-rank path and refuses training mode and grad. Training
 (downstream.py's loop) runs through neuralsampleid_amd.downstream: clf_train_scores is the training-mode forward and backward on
 csrc/clf_train.hip, and train() / train_step() drive it; the trained state_dict loads here as it is."""
@@ -38,9 +39,9 @@ class CrossAttentionClassifier(nn.Module):
     # ---------------------------------------------------------------------------------------------------- checks
     def _check_module(self):
         C, H = self.attn.embed_dim, self.attn.num_heads
-        if C != ops.CLF_C or H != 4 or self.fc[0].out_features != 128:
-            raise NotImplementedError(f"the re-rank kernel covers in_dim 512, 4 heads and hidden_dim 128 (got in_dim {C}, {H} heads, "
-                                      f"hidden_dim {self.fc[0].out_features})")
+        if C not in ops.CLF_WIDTHS or H != 4 or self.fc[0].out_features != 128:
+            raise NotImplementedError(f"the re-rank kernel covers in_dim {', '.join(map(str, ops.CLF_WIDTHS))}, 4 heads and hidden_dim "
+                                      f"128 (got in_dim {C}, {H} heads, hidden_dim {self.fc[0].out_features})")
         if self.attn.in_proj_weight is None or self.attn.in_proj_bias is None or self.attn.bias_k is not None:
             raise NotImplementedError("the re-rank kernel needs the packed in_proj weight and bias of nn.MultiheadAttention")
 
@@ -49,8 +50,9 @@ class CrossAttentionClassifier(nn.Module):
             raise TypeError(f"{name}: expected a torch tensor")
         if x.dtype != torch.float32:
             raise ValueError(f"{name}: only float32 node matrices are supported, got {x.dtype}")
-        if x.dim() != 3 or x.shape[1] != ops.CLF_C:
-            raise ValueError(f"{name}: expected (S, {ops.CLF_C}, N) node matrices, got {tuple(x.shape)}")
+        C = self.attn.embed_dim
+        if x.dim() != 3 or x.shape[1] != C:
+            raise ValueError(f"{name}: expected (S, {C}, N) node matrices for a classifier of in_dim {C}, got {tuple(x.shape)}")
         if not x.is_contiguous():
             raise ValueError(f"{name}: node matrices must be contiguous (S, C, N)")
         if not x.is_cuda:
@@ -73,7 +75,7 @@ class CrossAttentionClassifier(nn.Module):
         return tuple((t.data_ptr(), t._version) for t in ts) + (ops.WEIGHT_EPOCH,)
 
     def folded(self):
-        """(wq, bq, wkp, bkp, tail, pos): Wq / sqrt(dh) and its bias; [Wk ; Wp] (1024 x 512) and [bk ; bp] with Wp_h = G_h Wv_h,
+        """(wq, bq, wkp, bkp, tail, pos): Wq / sqrt(dh) and its bias, dh = C / 4; [Wk ; Wp] ((C + 512) x C) and [bk ; bp] with Wp_h = G_h Wv_h,
         bp_h = G_h bv_h, G = W1 Wo; tail = {g = W1 bo + b1, w2, b2}; pos (num_nodes, C) or None. Built once per parameter version
         (fp64 on the device, stored fp32)."""
         self._check_module()
@@ -118,14 +120,14 @@ class CrossAttentionClassifier(nn.Module):
         return out
 
     def project_queries(self, nm: torch.Tensor) -> torch.Tensor:
-        """(S, C, N) query node matrices -> (S N, 512) rows of (x + pos) Wq^T / sqrt(dh) + bq / sqrt(dh)"""
+        """(S, C, N) query node matrices -> (S N, C) rows of (x + pos) Wq^T / sqrt(dh) + bq / sqrt(dh)"""
         self._check_mode()
         N = self._check_nodes(nm, "project_queries")
         wq, bq, _, _, _, pos = self.folded()
         return self._linear(ops.clf_node_rows(nm, None if pos is None else pos[:N].contiguous()), wq, bq)
 
     def project_candidates(self, nm: torch.Tensor) -> torch.Tensor:
-        """(S, C, N) candidate node matrices -> (S N, 1024) rows [K | P]"""
+        """(S, C, N) candidate node matrices -> (S N, C + 512) rows [K | P]"""
         self._check_mode()
         N = self._check_nodes(nm, "project_candidates")
         _, _, wkp, bkp, _, pos = self.folded()

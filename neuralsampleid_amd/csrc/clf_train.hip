@@ -12,26 +12,32 @@
 //   da_h = V_h do_h,  dV_p = a_h (x) do_h,  dS = A o (da / N - rowsum(A o da / N)),  dQ_p = dS K_h / sqrt(dh),  dK_p = dS^T Q_h / sqrt(dh)
 // dQ_p and dK_p go to HBM per pair; nsid_clf_seg_reduce sums them (and forms dV) per segment in pair order, so every result here is
 // a fixed-order sum: no atomics, and a pair's scores and per-pair gradients depend on nothing but the pair.
+//
+// Widths: the attention kernels and the per-segment sums are templates on <C, DH>, C = 4 DH in {512, 640, 768, 1024}; the saved
+// attention layout (P, 4, 16, 64) and abar (P, 4, 32) do not depend on C. Mining and the head (fc.0 width 128) are the same at every C.
 #include "nsid_common.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int CT_C = 512;            // node channels
-constexpr int CT_DH = 128;           // head dim
-constexpr int CT_H = 4;              // heads
+constexpr int CT_H = 4;              // heads; node channels C = 4 DH are template parameters
 constexpr int CT_N = 32;             // nodes per segment at most (one 32x32 MFMA tile)
 constexpr int CT_HID = 128;          // fc.0 width
-constexpr int CT_KV = 2 * CT_C;      // the candidates' projected rows: [K | V]
 constexpr int CT_MINE_MAXN = 8192;   // rows of the mining pool (2B) at most: their dots live in LDS
 constexpr int CT_MINE_MAXD = 512;
-constexpr int CT_RED_THREADS = 512;  // nsid_clf_seg_reduce: one workgroup per segment, 8 float4 per thread cover N x 512
+constexpr int CT_RED_THREADS = 512;  // nsid_clf_seg_reduce: one workgroup per segment, C / 64 float4 per thread cover N x C
 
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // key row of accumulator register i on lane half hh (the 32x32 C/D map)
 __device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
+// 1 / sqrt(DH), rounded to fp32
+template <int DH> struct ct_scale;
+template <> struct ct_scale<128> { static constexpr float v = 0.08838834764831845f; };
+template <> struct ct_scale<160> { static constexpr float v = 0.07905694150420949f; };
+template <> struct ct_scale<192> { static constexpr float v = 0.07216878364870323f; };
+template <> struct ct_scale<256> { static constexpr float v = 0.0625f; };
 
 // ------------------------------------------------------------------------------------------------ hard-negative mining
 // (v, j) precedes (w, k) in the descending order with ties to the smaller index
@@ -93,11 +99,16 @@ __global__ __launch_bounds__(256) void clf_mine_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------------ attention forward
 // One wave per pair, 4 pairs per workgroup. S^T[key][query] on the fp32 MFMA as rerank.hip does (A = K rows, B = Q rows, both
 // streamed from global memory as fragments); the softmax runs over the keys of each query lane. A is stored in its register layout,
-// (P, 4, 16, 64): the backward reloads the same registers. abar (P, 4, 32) = a_h; obar (P, 512) = concat_h a_h^T V_h.
+// (P, 4, 16, 64): the backward reloads the same registers. abar (P, 4, 32) = a_h; obar (P, C) = concat_h a_h^T V_h, 64 columns of
+// a head at a time (the last block of DH = 160 is half full).
+template <int C, int DH>
 __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kv,
                                                            int nc_seg, int N, const int* __restrict__ qi, const int* __restrict__ ci,
                                                            int P, float* __restrict__ obar, float* __restrict__ attn,
                                                            float* __restrict__ abar) {
+  static_assert(C == CT_H * DH && DH % 32 == 0, "4 heads of DH channels");
+  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;        // [K | V] rows
+  constexpr int OB = (DH + 63) / 64;                         // 64-column blocks of a head's output
   __shared__ float abs_[4][CT_N];
   const int lane = lane_id(), w = threadIdx.x >> 6;
   const int r = lane & 31, hh = lane >> 5;
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restri
   if (p >= P) return;
   const int qs = qi[p], cs = ci[p];
   if (qs < 0 || qs >= nq_seg || cs < 0 || cs >= nc_seg) return;      // the host checks the lists; this only keeps a bad one in bounds
-  const float scale = 0.08838834764831845f;                          // 1 / sqrt(128)
+  const float scale = ct_scale<DH>::v;
   const float invN = 1.0f / (float)N;
   const bool rin = r < N;
   const float* qp = q + ((size_t)qs * N + (rin ? r : 0)) * CT_C + 4 * hh;
@@ -159,14 +170,18 @@ __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restri
       abar[((size_t)p * CT_H + h) * CT_N + jf] = v[0] * invN;
     }
     __builtin_amdgcn_wave_barrier();
-    float o0 = 0.f, o1 = 0.f;
+    float o[OB];
+#pragma unroll
+    for (int t = 0; t < OB; ++t) o[t] = 0.f;
     for (int m = 0; m < N; ++m) {
       const float a = abs_[w][m];
-      o0 = fmaf(a, vb[(size_t)m * CT_KV + h * CT_DH + lane], o0);
-      o1 = fmaf(a, vb[(size_t)m * CT_KV + h * CT_DH + 64 + lane], o1);
+#pragma unroll
+      for (int t = 0; t < OB; ++t)
+        if (DH % 64 == 0 || 64 * t + lane < DH) o[t] = fmaf(a, vb[(size_t)m * CT_KV + h * CT_DH + 64 * t + lane], o[t]);
     }
-    obar[(size_t)p * CT_C + h * CT_DH + lane] = o0;
-    obar[(size_t)p * CT_C + h * CT_DH + 64 + lane] = o1;
+#pragma unroll
+    for (int t = 0; t < OB; ++t)
+      if (DH % 64 == 0 || 64 * t + lane < DH) obar[(size_t)p * CT_C + h * CT_DH + 64 * t + lane] = o[t];
     __builtin_amdgcn_wave_barrier();
   }
 }
@@ -233,13 +248,16 @@ __global__ __launch_bounds__(CT_WG_GROUPS * CT_HID) void clf_head_wgrad_kernel(c
 }
 
 // ------------------------------------------------------------------------------------------------ attention backward
-// One wave per pair, 4 pairs per workgroup. Per head: da (VALU: a 32 x 128 matrix-vector product), dS in the forward's register
+// One wave per pair, 4 pairs per workgroup. Per head: da (VALU: a 32 x DH matrix-vector product), dS in the forward's register
 // layout (query on the lane, keys in the registers), dQ = dS K on the fp32 MFMA with dS as the A operand as it stands, then dS
 // through LDS once (key on the lane) for dK = dS^T Q. 1 / sqrt(dh) is applied to dS. Rows >= N are neither read nor written.
+template <int C, int DH>
 __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restrict__ dobar, const float* __restrict__ attn,
                                                            const float* __restrict__ q, int nq_seg, const float* __restrict__ kv,
                                                            int nc_seg, int N, const int* __restrict__ qi, const int* __restrict__ ci,
                                                            int P, float* __restrict__ dq, float* __restrict__ dk) {
+  static_assert(C == CT_H * DH && DH % 32 == 0, "4 heads of DH channels");
+  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C, HALF = DH / 2;
   __shared__ float dsT[4][CT_N][CT_N + 1];
   __shared__ float das[4][CT_N];
   const int lane = lane_id(), w = threadIdx.x >> 6;
@@ -248,24 +266,24 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
   if (p >= P) return;
   const int qs = qi[p], cs = ci[p];
   if (qs < 0 || qs >= nq_seg || cs < 0 || cs >= nc_seg) return;
-  const float scale = 0.08838834764831845f;
+  const float scale = ct_scale<DH>::v;
   const float invN = 1.0f / (float)N;
   const bool rin = r < N;
-  const float* qrow = q + (size_t)qs * N * CT_C;              // Q of the query segment (N x 512)
-  const float* krow = kv + (size_t)cs * N * CT_KV;            // [K | V] of the candidate (N x 1024)
+  const float* qrow = q + (size_t)qs * N * CT_C;              // Q of the query segment (N x C)
+  const float* krow = kv + (size_t)cs * N * CT_KV;            // [K | V] of the candidate (N x 2C)
   const float* dop = dobar + (size_t)p * CT_C;
   float* dqp = dq + (size_t)p * N * CT_C;
   float* dkp = dk + (size_t)p * N * CT_C;
 
 #pragma unroll 1
   for (int h = 0; h < CT_H; ++h) {
-    // da[key r] = V[r][h] . do[h]: half hh of the 128 dims on each lane half, halves added in one order on both
+    // da[key r] = V[r][h] . do[h]: half hh of the DH dims on each lane half, halves added in one order on both
     float part = 0.f;
     if (rin) {
-      const float* vr = krow + (size_t)r * CT_KV + CT_C + h * CT_DH + 64 * hh;
-      const float* dr = dop + h * CT_DH + 64 * hh;
+      const float* vr = krow + (size_t)r * CT_KV + CT_C + h * CT_DH + HALF * hh;
+      const float* dr = dop + h * CT_DH + HALF * hh;
 #pragma unroll 4
-      for (int e = 0; e < 64; e += 4) {
+      for (int e = 0; e < HALF; e += 4) {
         const f32x4 a = ld4(vr + e), b = ld4(dr + e);
         part = fmaf(a[0], b[0], part);
         part = fmaf(a[1], b[1], part);
@@ -336,17 +354,20 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
 // One workgroup per segment: blocks [0, nq_seg) sum dQ_p over the pairs with qi[p] == seg, blocks [nq_seg, nq_seg + nc_seg) sum
 // dK_p and dV_p = a_h (x) do_h over the pairs with ci[p] == seg. The pair list is scanned in chunks of 512 (a ballot per wave), the
 // matches are added in pair order; a segment with no pairs gets zeros.
+template <int C, int DH>
 __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const float* __restrict__ dq, const float* __restrict__ dk,
                                                                         const float* __restrict__ abar, const float* __restrict__ dobar,
                                                                         const int* __restrict__ qi, const int* __restrict__ ci, int P,
                                                                         int N, int nq_seg, float* __restrict__ dq_seg,
                                                                         float* __restrict__ dkv_seg) {
+  static_assert(C == CT_H * DH && DH % 4 == 0 && (CT_N * C) % (4 * CT_RED_THREADS) == 0, "4 heads of DH channels");
+  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;
   __shared__ uint64_t masks[CT_RED_THREADS / 64];
   const int tid = threadIdx.x, w = tid >> 6;
   const bool isq = (int)blockIdx.x < nq_seg;
   const int seg = isq ? (int)blockIdx.x : (int)blockIdx.x - nq_seg;
   const int* idx = isq ? qi : ci;
-  const int nel = N * CT_C;                                  // elements of one segment's gradient (a multiple of 512)
+  const int nel = N * CT_C;                                  // elements of one segment's gradient (a multiple of 128)
   constexpr int U = CT_N * CT_C / (4 * CT_RED_THREADS);      // float4 per thread
   f32x4 acc[U], accv[U];
 #pragma unroll
@@ -415,15 +436,31 @@ extern "C" int nsid_clf_mine_hard_negatives(const float* zq, int nq, const float
   return nsid_launch_status();
 }
 
-extern "C" int nsid_clf_attn_fwd(const float* q, int nq_seg, const float* kv, int nc_seg, int N, const int* qi, const int* ci, int P,
-                                 float* obar, float* attn, float* abar, void* stream) {
+// one launch of KERNEL<C, C / 4> for the supported widths
+#define CT_LAUNCH_C(KERNEL, grid, block, st, ...)                                        \
+  switch (C) {                                                                           \
+    case 512: NSID_LAUNCH((KERNEL<512, 128>), grid, block, 0, st, __VA_ARGS__); break;   \
+    case 640: NSID_LAUNCH((KERNEL<640, 160>), grid, block, 0, st, __VA_ARGS__); break;   \
+    case 768: NSID_LAUNCH((KERNEL<768, 192>), grid, block, 0, st, __VA_ARGS__); break;   \
+    default: NSID_LAUNCH((KERNEL<1024, 256>), grid, block, 0, st, __VA_ARGS__); break;   \
+  }
+static inline bool ct_width_ok(int C) { return C == 512 || C == 640 || C == 768 || C == 1024; }
+
+extern "C" int nsid_clf_attn_fwd_c(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
+                                   int P, float* obar, float* attn, float* abar, void* stream) {
+  NSID_REQUIRE(ct_width_ok(C));
   NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CT_N && P >= 0 && P <= (1 << 28));
   if (P == 0) return NSID_OK;
   NSID_REQUIRE(q && kv && qi && ci && obar && attn && abar && nsid_aligned16(q) && nsid_aligned16(kv));
   nsid_count(NSID_C_clf_attn_fwd);
-  NSID_LAUNCH(clf_attn_fwd_kernel, dim3((P + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), q, nq_seg, kv, nc_seg, N, qi,
-              ci, P, obar, attn, abar);
+  CT_LAUNCH_C(clf_attn_fwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), q, nq_seg, kv, nc_seg, N, qi, ci,
+              P, obar, attn, abar);
   return nsid_launch_status();
+}
+
+extern "C" int nsid_clf_attn_fwd(const float* q, int nq_seg, const float* kv, int nc_seg, int N, const int* qi, const int* ci, int P,
+                                 float* obar, float* attn, float* abar, void* stream) {
+  return nsid_clf_attn_fwd_c(q, nq_seg, kv, nc_seg, 512, N, qi, ci, P, obar, attn, abar, stream);
 }
 
 extern "C" int nsid_clf_head_fwd(const float* hid, const float* keep, const float* w2, const float* b2, int P, float* s, void* stream) {
@@ -449,25 +486,38 @@ extern "C" int nsid_clf_head_bwd(const float* ds, const float* s, const float* h
   return nsid_launch_status();
 }
 
-extern "C" int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int N,
-                                 const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+extern "C" int nsid_clf_attn_bwd_c(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
+                                   int C, int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+  NSID_REQUIRE(ct_width_ok(C));
   NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CT_N && P >= 0 && P <= (1 << 28));
   if (P == 0) return NSID_OK;
   NSID_REQUIRE(dobar && attn && q && kv && qi && ci && dq && dk && nsid_aligned16(dobar) && nsid_aligned16(kv));
   nsid_count(NSID_C_clf_attn_bwd);
-  NSID_LAUNCH(clf_attn_bwd_kernel, dim3((P + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), dobar, attn, q, nq_seg, kv,
-              nc_seg, N, qi, ci, P, dq, dk);
+  CT_LAUNCH_C(clf_attn_bwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), dobar, attn, q, nq_seg, kv, nc_seg,
+              N, qi, ci, P, dq, dk);
   return nsid_launch_status();
 }
 
-extern "C" int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
-                                   const int* ci, int P, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream) {
+extern "C" int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int N,
+                                 const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+  return nsid_clf_attn_bwd_c(dobar, attn, q, nq_seg, kv, nc_seg, 512, N, qi, ci, P, dq, dk, stream);
+}
+
+extern "C" int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
+                                     const int* ci, int P, int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg,
+                                     void* stream) {
+  NSID_REQUIRE(ct_width_ok(C));
   NSID_REQUIRE(P >= 0 && P <= (1 << 28) && N >= 1 && N <= CT_N && nq_seg >= 0 && nc_seg >= 0 && nq_seg + nc_seg <= (1 << 30));
   if (nq_seg + nc_seg == 0) return NSID_OK;
   NSID_REQUIRE((P == 0 || (dq && dk && abar && dobar && qi && ci)) && dq_seg && dkv_seg);
   NSID_REQUIRE(nsid_aligned16(dq) && nsid_aligned16(dk) && nsid_aligned16(dobar) && nsid_aligned16(dq_seg) && nsid_aligned16(dkv_seg));
   nsid_count(NSID_C_clf_seg_reduce);
-  NSID_LAUNCH(clf_seg_reduce_kernel, dim3(nq_seg + nc_seg), dim3(CT_RED_THREADS), 0, static_cast<hipStream_t>(stream), dq, dk, abar,
+  CT_LAUNCH_C(clf_seg_reduce_kernel, dim3(nq_seg + nc_seg), dim3(CT_RED_THREADS), static_cast<hipStream_t>(stream), dq, dk, abar,
               dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg);
   return nsid_launch_status();
+}
+
+extern "C" int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
+                                   const int* ci, int P, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream) {
+  return nsid_clf_seg_reduce_c(dq, dk, abar, dobar, qi, ci, P, 512, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
 }

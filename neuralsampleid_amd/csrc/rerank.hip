@@ -13,34 +13,45 @@
 // (128 KB); each wave takes query segments of the chunk in turn and streams their Q rows from global memory as MFMA B fragments.
 // Every sum runs in one fixed order that depends on nothing but the pair, so a pair's score is bitwise independent of the rest of the
 // call; there are no atomics.
+//
+// Widths: the kernel is a template on <C, DH> with C = 4 DH in {512, 640, 768, 1024}; P stays 4 x 128 (fc.0's width per head), so a
+// candidate row is [K | P] of C + 512 floats. K (32 x (C + 4) floats) next to P (64 KB) fits the 160 KB of a workgroup up to C = 640
+// (148 KB); at 768 and 1024 (164 / 197 KB) P alone is staged and every wave reads its K fragments from global memory, as it reads Q:
+// the candidate's K rows are shared by the 64 segments of the chunk and stay in L2. The order of every sum is the same in both forms.
 #include "nsid_common.h"
 
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int RR_C = 512;            // node channels
-constexpr int RR_DH = 128;           // head dim (4 heads)
-constexpr int RR_H = 4;
+constexpr int RR_H = 4;              // heads; node channels C = 4 DH are template parameters
 constexpr int RR_N = 32;             // nodes per segment at most (one 32x32 MFMA tile)
 constexpr int RR_HID = 128;          // fc.0 width
 constexpr int RR_WAVES = 8;
 constexpr int RR_QCH = 64;           // query segments per workgroup
-constexpr int RR_KLD = RR_C + 4;     // LDS row of K: +16 B so that the 32 rows of a fragment read start in different banks
-constexpr int RR_LDKP = 2 * RR_C;    // the candidates' projected rows: [K | P]
+constexpr int RR_PW = RR_H * RR_HID;  // P row: one fc.0-wide block per head
+constexpr int RR_LDS_MAX = 160 * 1024;
+// K next to P in LDS (rows of C + 4 floats: +16 B so that the 32 rows of a fragment read start in different banks), else P alone
+constexpr bool rr_k_in_lds(int C) { return (RR_N * (C + 4) + RR_N * RR_PW + RR_WAVES * RR_N) * 4 <= RR_LDS_MAX; }
 
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // group g: {first query segment, query segments, offset into cidx, candidates}; its scores are the row-major (q count x c count)
 // block at out + out_off[g]. tile_off: prefix sums of the groups' workgroups (c count x query chunks), ngroups + 1 entries.
+template <int C, int DH>
 __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kp,
                                                        int nc_seg, int N, const int* __restrict__ grp,
                                                        const int64_t* __restrict__ out_off, const int* __restrict__ tile_off,
                                                        int ngroups, const int* __restrict__ cidx, const float* __restrict__ tail,
                                                        float* __restrict__ out, int64_t out_len) {
-  __shared__ __attribute__((aligned(16))) float ks[RR_N][RR_KLD];
-  __shared__ __attribute__((aligned(16))) float ps[RR_N][RR_C];
+  static_assert(C == RR_H * DH && DH % 8 == 0, "4 heads of DH channels");
+  constexpr bool KLDS = rr_k_in_lds(C);
+  static_assert(KLDS || DH % 64 == 0, "the streamed form loads K and Q eight k-steps at a time");
+  constexpr int KLD = C + 4;           // LDS row of K
+  constexpr int LDKP = C + RR_PW;      // the candidates' projected rows: [K | P]
+  __shared__ __attribute__((aligned(16))) float ks[KLDS ? RR_N : 1][KLDS ? KLD : 4];
+  __shared__ __attribute__((aligned(16))) float ps[RR_N][RR_PW];
   __shared__ float abar[RR_WAVES][RR_N];
 
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
@@ -61,16 +72,29 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
   if (cand < 0 || cand >= nc_seg) return;              // the host checks the lists; this only keeps a bad list in bounds
 
   // stage K and P of the candidate (rows >= N are zero)
-  const float* kc = kp + (size_t)cand * N * RR_LDKP;
-  for (int i = tid; i < RR_N * (RR_C / 4); i += 512) {
-    const int n = i / (RR_C / 4), c = 4 * (i % (RR_C / 4));
-    f32x4 kv = {0.f, 0.f, 0.f, 0.f}, pv = {0.f, 0.f, 0.f, 0.f};
-    if (n < N) {
-      kv = ld4(kc + (size_t)n * RR_LDKP + c);
-      pv = ld4(kc + (size_t)n * RR_LDKP + RR_C + c);
+  const float* kc = kp + (size_t)cand * N * LDKP;
+  if constexpr (KLDS && C == RR_PW) {
+    for (int i = tid; i < RR_N * (C / 4); i += 512) {
+      const int n = i / (C / 4), c = 4 * (i % (C / 4));
+      f32x4 kv = {0.f, 0.f, 0.f, 0.f}, pv = {0.f, 0.f, 0.f, 0.f};
+      if (n < N) {
+        kv = ld4(kc + (size_t)n * LDKP + c);
+        pv = ld4(kc + (size_t)n * LDKP + C + c);
+      }
+      *reinterpret_cast<f32x4*>(&ks[n][c]) = kv;
+      *reinterpret_cast<f32x4*>(&ps[n][c]) = pv;
     }
-    *reinterpret_cast<f32x4*>(&ks[n][c]) = kv;
-    *reinterpret_cast<f32x4*>(&ps[n][c]) = pv;
+  } else {
+    if constexpr (KLDS) {
+      for (int i = tid; i < RR_N * (C / 4); i += 512) {
+        const int n = i / (C / 4), c = 4 * (i % (C / 4));
+        *reinterpret_cast<f32x4*>(&ks[n][c]) = n < N ? ld4(kc + (size_t)n * LDKP + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    for (int i = tid; i < RR_N * (RR_PW / 4); i += 512) {
+      const int n = i / (RR_PW / 4), c = 4 * (i % (RR_PW / 4));
+      *reinterpret_cast<f32x4*>(&ps[n][c]) = n < N ? ld4(kc + (size_t)n * LDKP + C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
   }
   __syncthreads();
 
@@ -85,24 +109,45 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
     if (qseg < 0 || qseg >= nq_seg) continue;
     const int64_t o = out_off[g] + (int64_t)s * cn + jpos;
     if (o < 0 || o >= out_len) continue;
-    const float* qp = q + ((size_t)qseg * N + (r < N ? r : 0)) * RR_C + 4 * hh;
+    const float* qp = q + ((size_t)qseg * N + (r < N ? r : 0)) * C + 4 * hh;
     float part0 = 0.f, part1 = 0.f;             // hidden[lane], hidden[64 + lane] without g
 
-    f32x4 qf[RR_DH / 8];
+    // K in LDS: the next head's Q fragments are fetched while this head's run (DH / 8 f32x4 in flight)
+    f32x4 qf[KLDS ? DH / 8 : 1];
+    if constexpr (KLDS) {
 #pragma unroll
-    for (int bb = 0; bb < RR_DH / 8; ++bb) qf[bb] = r < N ? ld4(qp + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int bb = 0; bb < DH / 8; ++bb) qf[bb] = r < N ? ld4(qp + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
 
 #pragma unroll
     for (int h = 0; h < RR_H; ++h) {
       // S^T[key][query]: A = K rows (LDS), B = Q rows; lane (r, hh) supplies dims 8 bb + 4 hh + e of row r at step (bb, e)
       f32x16 acc = {};
+      if constexpr (KLDS) {
 #pragma unroll
-      for (int bb = 0; bb < RR_DH / 8; ++bb) {
-        const f32x4 ka = *reinterpret_cast<const f32x4*>(&ks[r][h * RR_DH + 8 * bb + 4 * hh]);
-        const f32x4 qb = qf[bb];
-        if (h + 1 < RR_H) qf[bb] = r < N ? ld4(qp + (h + 1) * RR_DH + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int bb = 0; bb < DH / 8; ++bb) {
+          const f32x4 ka = *reinterpret_cast<const f32x4*>(&ks[r][h * DH + 8 * bb + 4 * hh]);
+          const f32x4 qb = qf[bb];
+          if (h + 1 < RR_H) qf[bb] = r < N ? ld4(qp + (h + 1) * DH + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[e], qb[e], acc, 0, 0, 0);
+          for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[e], qb[e], acc, 0, 0, 0);
+        }
+      } else {
+        // K from global memory (L2): both fragments are loaded 8 steps at a time, which bounds the registers in flight
+        const float* kr = kc + (size_t)(r < N ? r : 0) * LDKP + h * DH + 4 * hh;
+#pragma unroll 1
+        for (int b0 = 0; b0 < DH / 8; b0 += 8) {
+          f32x4 ka[8], qb[8];
+#pragma unroll
+          for (int bb = 0; bb < 8; ++bb) {
+            ka[bb] = r < N ? ld4(kr + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+            qb[bb] = r < N ? ld4(qp + h * DH + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+#pragma unroll
+          for (int bb = 0; bb < 8; ++bb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[bb][e], qb[bb][e], acc, 0, 0, 0);
+        }
       }
       // acc[i] of lane (r, hh) = score of query node r against key (i & 3) + 8 (i >> 2) + 4 hh: softmax over the keys of query r
       float mx = -__builtin_inff();
@@ -137,8 +182,8 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
       // hidden += a_h^T P_h
       for (int m = 0; m < N; ++m) {
         const float a = abar[w][m];
-        part0 = fmaf(a, ps[m][h * RR_DH + lane], part0);
-        part1 = fmaf(a, ps[m][h * RR_DH + 64 + lane], part1);
+        part0 = fmaf(a, ps[m][h * RR_HID + lane], part0);
+        part1 = fmaf(a, ps[m][h * RR_HID + 64 + lane], part1);
       }
       __builtin_amdgcn_wave_barrier();
     }
@@ -177,14 +222,31 @@ extern "C" int nsid_clf_node_rows(const float* x, int S, int C, int N, const flo
   return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
 }
 
-extern "C" int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups,
-                                    const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
-                                    const float* tail, float* out, int64_t out_len, void* stream) {
+extern "C" int nsid_clf_pair_scores_c(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
+                                      const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
+                                      const float* tail, float* out, int64_t out_len, void* stream) {
+  NSID_REQUIRE(C == 512 || C == 640 || C == 768 || C == 1024);
   NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= RR_N && ngroups >= 0 && ntiles >= 0 && out_len >= 0);
   if (ngroups == 0 || ntiles == 0) return NSID_OK;
   NSID_REQUIRE(q && kp && groups && out_off && tile_off && cidx && tail && out && nsid_aligned16(q) && nsid_aligned16(kp));
   nsid_count(NSID_C_clf_pair_scores);
-  hipLaunchKernelGGL(clf_pair_kernel, dim3(ntiles), dim3(512), 0, static_cast<hipStream_t>(stream), q, nq_seg, kp, nc_seg, N, groups,
-                     out_off, tile_off, ngroups, cidx, tail, out, out_len);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define RR_LAUNCH(CC)                                                                                                             \
+  hipLaunchKernelGGL((clf_pair_kernel<CC, CC / RR_H>), dim3(ntiles), dim3(512), 0, st, q, nq_seg, kp, nc_seg, N, groups, out_off, \
+                     tile_off, ngroups, cidx, tail, out, out_len)
+  switch (C) {
+    case 512: RR_LAUNCH(512); break;
+    case 640: RR_LAUNCH(640); break;
+    case 768: RR_LAUNCH(768); break;
+    default: RR_LAUNCH(1024); break;
+  }
+#undef RR_LAUNCH
   return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+}
+
+extern "C" int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups,
+                                    const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
+                                    const float* tail, float* out, int64_t out_len, void* stream) {
+  return nsid_clf_pair_scores_c(q, nq_seg, kp, nc_seg, 512, N, groups, out_off, tile_off, ngroups, ntiles, cidx, tail, out, out_len,
+                                stream);
 }

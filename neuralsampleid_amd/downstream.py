@@ -117,7 +117,7 @@ def _wgrad(dout, x, Nout):
 class _TrainScores(torch.autograd.Function):
     @staticmethod
     def forward(ctx, nodes_q, nodes_c, qi, ci, keep, pos, w_in, b_in, w_o, b_o, w1, b1, w2, b2):
-        C = ops.CLF_C
+        C = w_o.shape[0]                    # the classifier's in_dim (checked by clf_train_scores)
         N = nodes_q.shape[2]
         with _Fp32Gemm():
             xq = ops.clf_node_rows(nodes_q, pos)
@@ -136,7 +136,7 @@ class _TrainScores(torch.autograd.Function):
     def backward(ctx, ds):
         xq, xc, q, kv, obar, attn, abar, m, hid, s, keep, qi, ci, w_o, w1, w2 = ctx.saved_tensors
         N, Sq, Sc = ctx.dims
-        C = ops.CLF_C
+        C = w_o.shape[0]
         P = s.shape[0]
         ds = ds.reshape(-1).float().contiguous()
         with _Fp32Gemm():
@@ -164,8 +164,8 @@ def _host_index(a, name):
 
 def clf_train_scores(classifier: CrossAttentionClassifier, nodes_q, nodes_c, q_idx, c_idx, keep) -> torch.Tensor:
     """(P, 1) training-mode scores of the pairs (nodes_q[q_idx[p]], nodes_c[c_idx[p]]), differentiable in the classifier's eight
-    parameters (attn.in_proj_*, attn.out_proj.*, fc.0.*, fc.3.*). nodes_q (Sq, 512, N), nodes_c (Sc, 512, N): fp32 contiguous device
-    node matrices that do not require grad (the encoder is frozen). q_idx, c_idx: integer sequences of length P (host or device; they
+    parameters (attn.in_proj_*, attn.out_proj.*, fc.0.*, fc.3.*). nodes_q (Sq, C, N), nodes_c (Sc, C, N), C = the classifier's in_dim
+    (512, 640, 768 or 1024): fp32 contiguous device node matrices that do not require grad (the encoder is frozen). q_idx, c_idx: integer sequences of length P (host or device; they
     are checked on the host). keep (P, 128): the dropout keep mask scaled by 1 / (1 - p) (draw_keep); all ones = no dropout. The
     classifier's own forward (eval-mode re-rank) is not used."""
     classifier._check_module()

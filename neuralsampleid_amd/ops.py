@@ -1371,6 +1371,15 @@ def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:
 
 # ------------------------------------------------------------------------------------------------ classifier re-rank (csrc/rerank.hip)
 CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = 512, 1024, 32, 64
+CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
+CLF_PW = 512                            # the folded candidate block P: 4 heads x fc.0's 128, at every width
+
+
+def _clf_width(C, name) -> int:
+    C = int(C)
+    if C not in CLF_WIDTHS:
+        raise ValueError(f"{name}: width C = {C} is not one of {CLF_WIDTHS}")
+    return C
 
 
 def clf_node_rows(x, pos=None) -> torch.Tensor:
@@ -1392,7 +1401,8 @@ def clf_node_rows(x, pos=None) -> torch.Tensor:
 def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_count):
     """Scores of blocked pair lists on the classifier's folded form (csrc/rerank.hip).
 
-    q (nq_seg N, 512): projected query rows; kp (nc_seg N, 1024): the candidates' [K | P] rows; tail (257,): {g, w2, b2}.
+    q (nq_seg N, C): projected query rows; kp (nc_seg N, C + 512): the candidates' [K | P] rows; tail (257,): {g, w2, b2}. C is
+    q's width, one of CLF_WIDTHS.
     Group i pairs query segments [q_start[i], q_start[i] + q_count[i]) with the candidate segments cand_idx[cand_off[i] :
     cand_off[i] + cand_count[i]] (repeats allowed). Host integer sequences, checked here. Returns (out, out_off): the flat fp32
     score tensor and, per group, the int64 offset of its row-major (q_count x cand_count) block."""
@@ -1401,8 +1411,11 @@ def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_c
     N = int(N)
     if not 1 <= N <= CLF_MAX_N:
         raise ValueError(f"clf_pair_scores: N = {N} is outside [1, {CLF_MAX_N}]")
-    if q.dim() != 2 or q.shape[1] != CLF_C or q.shape[0] % N or kp.dim() != 2 or kp.shape[1] != CLF_KP or kp.shape[0] % N:
-        raise ValueError(f"clf_pair_scores: expected q (S N, {CLF_C}) and kp (S N, {CLF_KP}), got {tuple(q.shape)}, {tuple(kp.shape)}")
+    if q.dim() != 2 or kp.dim() != 2:
+        raise ValueError(f"clf_pair_scores: expected q (S N, C) and kp (S N, C + {CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
+    C = _clf_width(q.shape[1], "clf_pair_scores")
+    if q.shape[0] % N or kp.shape[1] != C + CLF_PW or kp.shape[0] % N:
+        raise ValueError(f"clf_pair_scores: expected q (S N, {C}) and kp (S N, {C + CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
     if tail.numel() != 257:
         raise ValueError("clf_pair_scores: tail must hold g (128), w2 (128) and b2")
     nq_seg, nc_seg = q.shape[0] // N, kp.shape[0] // N
@@ -1432,9 +1445,11 @@ def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_c
     to = torch.from_numpy(tile_off.astype(np.int32)).to(dev)
     cit = torch.from_numpy((ci if ci.size else np.zeros(1, np.int64)).astype(np.int32)).to(dev)
     npairs = float(sizes.sum())
-    # 1.2 MFLOP per pair (Q K^T on the matrix pipe, softmax, a V, the folded tail); bytes: the scores and K / P staged per workgroup
-    _timed("clf_pair_kernel", 1.2e6 * npairs, 4.0 * npairs + 8.0 * CLF_C * N * float(tile_off[-1]),
-           lambda: call("nsid_clf_pair_scores", _p(q), nq_seg, _p(kp), nc_seg, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
+    # per pair 2 N^2 C (Q K^T on the matrix pipe) + softmax, a P and the folded tail: 1.2 MFLOP at C = 512; bytes: the scores and
+    # K / P staged per workgroup
+    _timed("clf_pair_kernel", (1.2e6 + 2.0 * CLF_MAX_N * CLF_MAX_N * (C - CLF_C)) * npairs,
+           4.0 * npairs + 4.0 * (C + CLF_PW) * N * float(tile_off[-1]),
+           lambda: call("nsid_clf_pair_scores_c", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
                         _p(cit), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
     return out, out_off[:-1]
 
@@ -1467,22 +1482,36 @@ def clf_mine_hard_negatives(zq, za, k) -> torch.Tensor:
     return out
 
 
+def _clf_qkv_width(q, kv, N, name) -> int:
+    """C of Q rows (S N, C) and [K | V] rows (S N, 2 C), checked against the supported widths before any launch"""
+    N = int(N)
+    if not 1 <= N <= CLF_MAX_N:
+        raise ValueError(f"{name}: N = {N} is outside [1, {CLF_MAX_N}]")
+    if q.dim() != 2 or kv.dim() != 2 or kv.shape[1] % 2:
+        raise ValueError(f"{name}: expected q (S N, C) and kv (S N, 2 C), got {tuple(q.shape)}, {tuple(kv.shape)}")
+    C = _clf_width(kv.shape[1] // 2, name)
+    if q.shape[1] != C or q.shape[0] % N or kv.shape[0] % N:
+        raise ValueError(f"{name}: expected q (S N, {C}) and kv (S N, {2 * C}), got {tuple(q.shape)}, {tuple(kv.shape)}")
+    return C
+
+
 def clf_attn_fwd(q, kv, N, qi, ci):
-    """per pair (qi[p], ci[p]): (obar (P, 512), attn (P, 4, 16, 64), abar (P, 4, 32)); q (Sq N, 512) Q rows, kv (Sc N, 1024) [K | V]
-    rows; qi, ci int32 device lists, in range (checked by the caller)"""
+    """per pair (qi[p], ci[p]): (obar (P, C), attn (P, 4, 16, 64), abar (P, 4, 32)); q (Sq N, C) Q rows, kv (Sc N, 2 C) [K | V]
+    rows, C one of CLF_WIDTHS; qi, ci int32 device lists, in range (checked by the caller)"""
     _chk(q, kv)
     _clf_idx(qi, "clf_attn_fwd")
     _clf_idx(ci, "clf_attn_fwd")
+    C = _clf_qkv_width(q, kv, N, "clf_attn_fwd")
     P = qi.numel()
     dev = q.device
-    obar = torch.empty((P, CLF_C), device=dev, dtype=torch.float32)
+    obar = torch.empty((P, C), device=dev, dtype=torch.float32)
     attn = torch.empty((P, CLF_H, 16, 64), device=dev, dtype=torch.float32)
     abar = torch.empty((P, CLF_H, CLF_MAX_N), device=dev, dtype=torch.float32)
     # 2 N^2 C (Q K^T) + 2 N C (a V) per pair; bytes: Q, K, V rows read per pair (from L2 mostly), obar, attn, abar written
-    _timed("clf_attn_fwd_kernel", float(P) * (2.0 * N * N * CLF_C + 2.0 * N * CLF_C),
-           float(P) * (12.0 * N * CLF_C + 4.0 * CLF_C + 4.0 * CLF_H * 16 * 64 + 4.0 * CLF_H * CLF_MAX_N), lambda: call(
-               "nsid_clf_attn_fwd", _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, N, _p(qi), _p(ci), P, _p(obar), _p(attn),
-               _p(abar), _stream()), (P, N, CLF_C, 1))
+    _timed("clf_attn_fwd_kernel", float(P) * (2.0 * N * N * C + 2.0 * N * C),
+           float(P) * (12.0 * N * C + 4.0 * C + 4.0 * CLF_H * 16 * 64 + 4.0 * CLF_H * CLF_MAX_N), lambda: call(
+               "nsid_clf_attn_fwd_c", _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P, _p(obar), _p(attn),
+               _p(abar), _stream()), (P, N, C, 1))
     return obar, attn, abar
 
 
@@ -1512,35 +1541,48 @@ def clf_head_bwd(ds, s, hid, keep, w2):
 
 
 def clf_attn_bwd(dobar, attn, q, kv, N, qi, ci):
-    """per-pair (dQ (P, N, 512), dK (P, N, 512)) from dobar = dL/dobar and the forward's attn"""
+    """per-pair (dQ (P, N, C), dK (P, N, C)) from dobar (P, C) = dL/dobar and the forward's attn"""
     _chk(dobar, attn, q, kv)
     _clf_idx(qi, "clf_attn_bwd")
     _clf_idx(ci, "clf_attn_bwd")
+    C = _clf_qkv_width(q, kv, N, "clf_attn_bwd")
     P = qi.numel()
+    if tuple(dobar.shape) != (P, C) or attn.numel() != P * CLF_H * 16 * 64:
+        raise ValueError(f"clf_attn_bwd: expected dobar ({P}, {C}) and attn ({P}, 4, 16, 64), got {tuple(dobar.shape)}, "
+                         f"{tuple(attn.shape)}")
     dev = q.device
-    dq = torch.empty((P, N, CLF_C), device=dev, dtype=torch.float32)
-    dk = torch.empty((P, N, CLF_C), device=dev, dtype=torch.float32)
+    dq = torch.empty((P, N, C), device=dev, dtype=torch.float32)
+    dk = torch.empty((P, N, C), device=dev, dtype=torch.float32)
     # 2 N C (da) + 2 N^2 C (dQ) + 2 N^2 C (dK) per pair on the matrix side; bytes: Q, K, V, attn read, dQ, dK written
-    _timed("clf_attn_bwd_kernel", float(P) * (4.0 * N * N * CLF_C + 2.0 * N * CLF_C),
-           float(P) * (12.0 * N * CLF_C + 4.0 * CLF_C + 4.0 * CLF_H * 16 * 64 + 8.0 * N * CLF_C), lambda: call(
-               "nsid_clf_attn_bwd", _p(dobar), _p(attn), _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, N, _p(qi), _p(ci), P,
-               _p(dq), _p(dk), _stream()), (P, N, CLF_C, 1))
+    _timed("clf_attn_bwd_kernel", float(P) * (4.0 * N * N * C + 2.0 * N * C),
+           float(P) * (12.0 * N * C + 4.0 * C + 4.0 * CLF_H * 16 * 64 + 8.0 * N * C), lambda: call(
+               "nsid_clf_attn_bwd_c", _p(dobar), _p(attn), _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P,
+               _p(dq), _p(dk), _stream()), (P, N, C, 1))
     return dq, dk
 
 
 def clf_seg_reduce(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
-    """per-segment sums in pair order: (dQ (nq_seg N, 512), [dK | dV] (nc_seg N, 1024))"""
+    """per-segment sums in pair order: (dQ (nq_seg N, C), [dK | dV] (nc_seg N, 2 C)); C is dobar's width (P, C)"""
     _chk(dq, dk, abar, dobar)
     _clf_idx(qi, "clf_seg_reduce")
     _clf_idx(ci, "clf_seg_reduce")
     P = qi.numel()
+    N = int(N)
+    if not 1 <= N <= CLF_MAX_N:
+        raise ValueError(f"clf_seg_reduce: N = {N} is outside [1, {CLF_MAX_N}]")
+    if dobar.dim() != 2:
+        raise ValueError(f"clf_seg_reduce: expected dobar (P, C), got {tuple(dobar.shape)}")
+    C = _clf_width(dobar.shape[1], "clf_seg_reduce")
+    if dobar.shape[0] != P or dq.numel() != P * N * C or dk.numel() != P * N * C or abar.numel() != P * CLF_H * CLF_MAX_N:
+        raise ValueError(f"clf_seg_reduce: expected dq, dk ({P}, {N}, {C}), abar ({P}, 4, 32) and dobar ({P}, {C}), got "
+                         f"{tuple(dq.shape)}, {tuple(dk.shape)}, {tuple(abar.shape)}, {tuple(dobar.shape)}")
     dev = dq.device
-    dq_seg = torch.empty((nq_seg * N, CLF_C), device=dev, dtype=torch.float32)
-    dkv_seg = torch.empty((nc_seg * N, 2 * CLF_C), device=dev, dtype=torch.float32)
-    _tk("clf_seg_reduce_kernel", float(P) * (8.0 * N * CLF_C + 4.0 * CLF_C) + 4.0 * (nq_seg + nc_seg) * (P + N * CLF_C)
-        + 4.0 * nc_seg * N * CLF_C, lambda: call(
-            "nsid_clf_seg_reduce", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, N, nq_seg, nc_seg, _p(dq_seg), _p(dkv_seg),
-            _stream()), (P, N, nq_seg + nc_seg, 1))
+    dq_seg = torch.empty((nq_seg * N, C), device=dev, dtype=torch.float32)
+    dkv_seg = torch.empty((nc_seg * N, 2 * C), device=dev, dtype=torch.float32)
+    _tk("clf_seg_reduce_kernel", float(P) * (8.0 * N * C + 4.0 * C) + 4.0 * (nq_seg + nc_seg) * (P + N * C)
+        + 4.0 * nc_seg * N * C, lambda: call(
+            "nsid_clf_seg_reduce_c", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, C, N, nq_seg, nc_seg, _p(dq_seg),
+            _p(dkv_seg), _stream()), (P, N, nq_seg + nc_seg, 1))
     return dq_seg, dkv_seg
 
 

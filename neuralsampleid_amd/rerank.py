@@ -181,8 +181,18 @@ def _ref_rows(ref_nmatrix_dir: str, songs) -> Dict[str, int]:
 
 def _check_nm(a: np.ndarray, what: str, C: int = ops.CLF_C) -> int:
     if a.ndim != 3 or a.shape[1] != C:
-        raise ValueError(f"{what}: node matrices must be (segments, {C}, N), got {a.shape}")
+        raise ValueError(f"{what}: node matrices must be (segments, {C}, N) for a classifier of in_dim {C}, got {a.shape}: the "
+                         "classifier checkpoint and the node matrices come from encoders of different sizes")
     return int(a.shape[2])
+
+
+def checkpoint_in_dim(state) -> int:
+    """in_dim of a CrossAttentionClassifier state_dict: the columns of attn.in_proj_weight (3 in_dim x in_dim)"""
+    w = state.get("attn.in_proj_weight") if hasattr(state, "get") else None
+    if w is None or len(w.shape) != 2 or w.shape[0] != 3 * w.shape[1]:
+        raise ValueError("the classifier checkpoint has no packed attn.in_proj_weight of shape (3 in_dim, in_dim): not a "
+                         "CrossAttentionClassifier state_dict")
+    return int(w.shape[1])
 
 
 def _project(fn, arrays: List[np.ndarray], device) -> torch.Tensor:
@@ -206,6 +216,7 @@ def score_tests(classifier, tests, query_nm: Dict[str, np.ndarray], ref_nmatrix_
     once (a ref song's file is loaded once, and only if it has a candidate) and scores all tests' (rows x candidates) blocks.
     Returns the list of (cand_ids, S (rows, candidates) float32 numpy)."""
     run_start = ref_run_starts(ref_lookup) if len(ref_lookup) else np.zeros(0, np.int64)
+    C = int(classifier.attn.embed_dim)
     # query segments: one block per q_id, as many rows as its tests need
     q_rows = {}
     for q_id, rows, _ in tests:
@@ -213,7 +224,7 @@ def score_tests(classifier, tests, query_nm: Dict[str, np.ndarray], ref_nmatrix_
     q_off, q_arrays, N = {}, [], None
     for q_id, rows in q_rows.items():
         a = query_nm[q_id]
-        n = _check_nm(a, f"query node matrices of {q_id!r}")
+        n = _check_nm(a, f"query node matrices of {q_id!r}", C)
         if N is not None and n != N:
             raise ValueError(f"node matrices disagree on N ({N} vs {n})")
         N = n
@@ -230,7 +241,7 @@ def score_tests(classifier, tests, query_nm: Dict[str, np.ndarray], ref_nmatrix_
     seg_rows = [None] * all_c.size
     for song, items in by_song.items():
         a = np.load(os.path.join(ref_nmatrix_dir, f"{song}.npy"))       # once per song with a candidate
-        n = _check_nm(a, f"ref_nmatrix/{song}.npy")
+        n = _check_nm(a, f"ref_nmatrix/{song}.npy", C)
         if N is not None and n != N:
             raise ValueError(f"node matrices disagree on N ({N} vs {n})")
         N = n
@@ -379,8 +390,12 @@ def main(argv=None) -> None:
     ap.add_argument("--no-save", action="store_true", help="do not write the result files")
     a = ap.parse_args(argv)
     from .classifier import CrossAttentionClassifier
-    clf = CrossAttentionClassifier(in_dim=512, num_nodes=32).cuda()
-    clf.load_state_dict(torch.load(a.clf_ckpt, map_location="cuda"))
+    state = torch.load(a.clf_ckpt, map_location="cuda")
+    in_dim = checkpoint_in_dim(state)
+    if in_dim not in ops.CLF_WIDTHS:
+        ap.error(f"--clf-ckpt: a classifier of in_dim {in_dim}; the re-rank covers in_dim {', '.join(map(str, ops.CLF_WIDTHS))}")
+    clf = CrossAttentionClassifier(in_dim=in_dim, num_nodes=32).cuda()
+    clf.load_state_dict(state)
     clf.eval()
     hr = eval_hit_rates_clf(a.emb_dir, clf, a.gt, a.dummy_dir, a.test_seq_len, a.k_probe or 5, save=not a.no_save)
     print(format_hit_rates(hr, a.test_seq_len))

@@ -2,7 +2,7 @@
 reference's step in torch-eager fp32 on the same GPU with the same pairs and dropout masks, and the encoder forward that supplies the
 features.
 
-    python tools/clf_train_bench.py [--sizes 32,256,1024] [--reps 7] [--only-ours]
+    python tools/clf_train_bench.py [--sizes 32,256,1024] [--reps 7] [--only-ours] [--in-dim 512|640|768|1024]
 
 Per size: ms per step (median of --reps after two warm-up steps, device events around each step), the step's FLOPs from shapes
 (per pair 1.05 MFLOP attention forward + 2.2 MFLOP backward: A is stored, not recomputed, plus the per-segment projections and the tail's linears and their
@@ -26,11 +26,11 @@ from neuralsampleid_amd import downstream  # noqa: E402
 from neuralsampleid_amd.classifier import CrossAttentionClassifier  # noqa: E402
 
 PEAK_TF = 155.0
-C, N, K = 512, 32, 3
+N, K = 32, 3
 
 
-def step_flops(B):
-    """forward + backward FLOPs of one step at batch B (mining excluded: 2 B 2B d)"""
+def step_flops(B, C):
+    """forward + backward FLOPs of one step at batch B and width C (mining excluded: 2 B 2B d)"""
     P, Sq, Sc = (1 + K) * B, B, 2 * B
     proj = 2.0 * (Sq * N * C * C + Sc * N * 2 * C * C)                  # Q, [K | V]
     tail = 2.0 * P * (C * C + C * 128)                                   # out_proj, fc.0
@@ -86,7 +86,7 @@ def eager_step(model, opt, ni, nj, zi, zj, keep):
     return loss
 
 
-def features(B, seed=0):
+def features(B, C, seed=0):
     g = torch.Generator().manual_seed(seed)
     ni = torch.randn(B, C, N, generator=g)
     nj = ni + 0.5 * torch.randn(B, C, N, generator=g)
@@ -111,16 +111,18 @@ def main():
     ap.add_argument("--sizes", default="32,256,1024")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--only-ours", action="store_true")
+    ap.add_argument("--in-dim", type=int, default=512, choices=(512, 640, 768, 1024), help="the classifier's width C")
     args = ap.parse_args()
+    C = args.in_dim
     for B in [int(s) for s in args.sizes.split(",")]:
         torch.manual_seed(0)
         clf = CrossAttentionClassifier(in_dim=C, num_nodes=N).cuda()
-        ni, nj, zi, zj = features(B)
+        ni, nj, zi, zj = features(B, C)
         keep = downstream.draw_keep((1 + K) * B, 0.3, "cuda")
         opt = torch.optim.Adam(clf.parameters(), lr=1e-4)
         ours, ours_all = timed(lambda: downstream.train_step(clf, opt, None, ni, nj, zi, zj, num_negatives=K, keep=keep), args.reps)
-        rec = {"B": B, "pairs": (1 + K) * B, "step_gflop": round(step_flops(B) / 1e9, 2), "hip_ms": round(ours, 3), "hip_all": ours_all,
-               "hip_tflops": round(step_flops(B) / ours / 1e9, 2)}
+        rec = {"in_dim": C, "B": B, "pairs": (1 + K) * B, "step_gflop": round(step_flops(B, C) / 1e9, 2), "hip_ms": round(ours, 3), "hip_all": ours_all,
+               "hip_tflops": round(step_flops(B, C) / ours / 1e9, 2)}
         if not args.only_ours:
             torch.manual_seed(0)
             clf_e = CrossAttentionClassifier(in_dim=C, num_nodes=N).cuda().train()

@@ -1,10 +1,10 @@
 """Times the classifier re-rank (csrc/rerank.hip) at the evaluations' block shapes, the projection GEMMs, a torch-eager fp32
 comparison and the whole eval_map_clf on a synthetic sample100-sized emb_dir.
 
-    python tools/rerank_bench.py [--reps 5] [--quick]
+    python tools/rerank_bench.py [--reps 5] [--quick] [--in-dim 512|640|768|1024]
 
-Pair kernel: ms (median of --reps after a warm-up), pairs/s and TFLOP/s on 1.2 MFLOP per pair, with its fraction of the fp32 matrix
-peak (155 TF, MI355X_MICROARCH). The eager comparison scores the same pairs with a batched fp32 nn.MultiheadAttention written here
+Pair kernel: ms (median of --reps after a warm-up), pairs/s and TFLOP/s on 1.2 MFLOP per pair at in_dim 512 (2 N^2 C more per
+channel of a wider classifier), with its fraction of the fp32 matrix peak (155 TF, MI355X_MICROARCH). The eager comparison scores the same pairs with a batched fp32 nn.MultiheadAttention written here
 (the reference's forward: one classifier call per candidate, batched over query segments, as eval_map.py does)."""
 import argparse
 import os
@@ -21,7 +21,11 @@ from neuralsampleid_amd import fpdb  # noqa: E402
 from neuralsampleid_amd.classifier import CrossAttentionClassifier  # noqa: E402
 from neuralsampleid_amd.rerank import eval_map_clf  # noqa: E402
 
-PEAK_TF, FLOP_PER_PAIR = 155.0, 1.2e6
+PEAK_TF = 155.0
+
+
+def flop_per_pair(C):
+    return 1.2e6 + 2.0 * 32 * 32 * (C - 512)
 
 
 def _median_ms(fn, reps):
@@ -38,9 +42,9 @@ def _median_ms(fn, reps):
     return float(np.median(ms))
 
 
-def _clf():
+def _clf(C):
     torch.manual_seed(0)
-    clf = CrossAttentionClassifier(in_dim=512, num_nodes=32).cuda().eval()
+    clf = CrossAttentionClassifier(in_dim=C, num_nodes=32).cuda().eval()
     return clf
 
 
@@ -58,11 +62,11 @@ class EagerClf(nn.Module):
         return self.fc(a.mean(dim=1))
 
 
-def time_block(name, sq, sc, groups, reps, eager_groups=1):
-    clf = _clf()
+def time_block(C, name, sq, sc, groups, reps, eager_groups=1):
+    clf = _clf(C)
     g = torch.Generator(device="cuda").manual_seed(1)
-    q = torch.randn(groups * sq, 512, 32, device="cuda", generator=g)
-    c = torch.randn(sc * 4, 512, 32, device="cuda", generator=g)
+    q = torch.randn(groups * sq, C, 32, device="cuda", generator=g)
+    c = torch.randn(sc * 4, C, 32, device="cuda", generator=g)
     with torch.no_grad():
         qp, kp = clf.project_queries(q), clf.project_candidates(c)
         rng = np.random.default_rng(0)
@@ -72,7 +76,7 @@ def time_block(name, sq, sc, groups, reps, eager_groups=1):
         tq = _median_ms(lambda: clf.project_queries(q), reps)
         tc = _median_ms(lambda: clf.project_candidates(c), reps)
         pairs = groups * sq * sc
-        tf = FLOP_PER_PAIR * pairs / t / 1e9
+        tf = flop_per_pair(C) * pairs / t / 1e9
         print(f"{name}: {groups} x ({sq} x {sc}) pairs: kernel {t:9.3f} ms  {pairs / t / 1e3:8.2f} Mpairs/s  {tf:6.1f} TF/s "
               f"({tf / PEAK_TF:5.3f} of 155)", flush=True)
         print(f"{name}: projections: queries {groups * sq} segs {tq:7.3f} ms, candidates {c.shape[0]} segs {tc:7.3f} ms", flush=True)
@@ -89,15 +93,15 @@ def time_block(name, sq, sc, groups, reps, eager_groups=1):
               f"group(s)) -> kernel speed-up {te / t:7.1f}x", flush=True)
 
 
-def time_eval_map(n_songs, segs, n_tests, q_segs, n_dummy, k_probe=3):
+def time_eval_map(C, n_songs, segs, n_tests, q_segs, n_dummy, k_probe=3):
     rng = np.random.default_rng(0)
-    d, C, N = 128, 512, 32
+    d, N = 128, 32
 
     def unit(n):
         x = rng.standard_normal((n, d)).astype(np.float32)
         return x / np.linalg.norm(x, axis=1, keepdims=True)
 
-    clf = _clf()
+    clf = _clf(C)
     with tempfile.TemporaryDirectory() as tmp:
         ref = unit(n_songs * segs)
         names = [f"s{i}" for i in range(n_songs)]
@@ -125,13 +129,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="8 MAP-like groups instead of 64, a small evaluation")
+    ap.add_argument("--in-dim", type=int, default=512, choices=(512, 640, 768, 1024), help="the classifier's width")
     a = ap.parse_args()
-    time_block("map block", 350, 1024, 8 if a.quick else 64, a.reps)
-    time_block("hit-rate block", 19, 95, 64, a.reps, eager_groups=8)
+    C = a.in_dim           # the classifier's width: the encoder sizes 't', 's', 'm' and the default end in 512 .. 1024
+    print(f"in_dim {C}", flush=True)
+    time_block(C, "map block", 350, 1024, 8 if a.quick else 64, a.reps)
+    time_block(C, "hit-rate block", 19, 95, 64, a.reps, eager_groups=8)
     if a.quick:
-        time_eval_map(20, 350, 10, 350, 20_000)
+        time_eval_map(C, 20, 350, 10, 350, 20_000)
     else:
-        time_eval_map(75, 350, 100, 350, 100_000)
+        time_eval_map(C, 75, 350, 100, 350, 100_000)
 
 
 if __name__ == "__main__":
