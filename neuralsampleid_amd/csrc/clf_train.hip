@@ -28,8 +28,6 @@ constexpr int CT_MINE_MAXN = 8192;   // rows of the mining pool (2B) at most: th
 constexpr int CT_MINE_MAXD = 512;
 constexpr int CT_RED_THREADS = 512;  // nsid_clf_seg_reduce: one workgroup per segment, C / 64 float4 per thread cover N x C
 
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 // key row of accumulator register i on lane half hh (the 32x32 C/D map)
 __device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
 // 1 / sqrt(DH), rounded to fp32

@@ -42,18 +42,6 @@ constexpr int F_NS = 4;                       // ring slots: chunk ch (GEMM 1), 
 // image C rows x 32 hidden = C / 16 sub-blocks: a ring slot is C / 8 KB (32 KB at C = 256)
 constexpr int F_PF = 1;            // fragment prefetch distance in steps (one step = 2 LDS reads, 4 MFMAs)
 
-template <int N>
-__device__ __forceinline__ void f_wait_vm() {
-  static_assert(N >= 0 && N < 64, "6-bit counter");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (7 << 4) | (0xF << 8));
-}
-// one LDS-DMA: 64 lanes x 16 B from (uniform base) + (lane offset) to LDS bytes [dst, dst + 1 KB)   (gemm256.hip glds16)
-__device__ __forceinline__ void f_glds16(const char* sbase, unsigned voff, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
-}
-
 // acc += A B with the accumulator in AGPRs. With one wave per SIMD a wave owns 256 VGPRs + 256 AGPRs; left to itself the register
 // allocator spreads x fragments and accumulators over both files and pays for it in v_accvgpr moves inside the chunk loop (measured:
 // 187 us against 147 us for the 8-wave form). The constraint settles it: all 64 output accumulator tiles live in a[0:255] for the whole
@@ -138,10 +126,10 @@ void ffn256_fused_kernel(const F256Args p) {
       const int q = PW * wave + i;            // 0 .. CT - 1: W1 sub-block (hidden tile a, k-step ks); CT .. 2 CT - 1: W2 sub-block (channel tile c)
       if (q < CT) {
         const int a = q / KS1, ks = q % KS1;
-        f_glds16(reinterpret_cast<const char*>(p.w1 + (long)(h0 + 16 * a) * F_C + 32 * ks), voff1, dst + q * 1024);
+        glds16(reinterpret_cast<const char*>(p.w1 + (long)(h0 + 16 * a) * F_C + 32 * ks), voff1, dst + q * 1024);
       } else {
         const int c = q - CT;
-        f_glds16(reinterpret_cast<const char*>(p.w2 + (long)(32 * (c >> 1) + 4 * (c & 1)) * F_H + h0), voff2, dst + W2OFF + c * 1024);
+        glds16(reinterpret_cast<const char*>(p.w2 + (long)(32 * (c >> 1) + 4 * (c & 1)) * F_H + h0), voff2, dst + W2OFF + c * 1024);
       }
     }
   };
@@ -182,9 +170,9 @@ void ffn256_fused_kernel(const F256Args p) {
       // tile before issued EP operations -- the next x fragments and the output stores -- AFTER chunks 0 and 1: they are younger than
       // what iterations 0 and 1 wait for and stay in flight; waiting them out here would put every tile's store tail on the critical
       // path)
-      if (ch < 2 && !first) f_wait_vm<(PW + EP < 63 ? PW + EP : 63)>();
-      else if (ch + 1 < F_NCH) f_wait_vm<PW>();
-      else f_wait_vm<0>();
+      if (ch < 2 && !first) wait_vm<(PW + EP < 63 ? PW + EP : 63)>();
+      else if (ch + 1 < F_NCH) wait_vm<PW>();
+      else wait_vm<0>();
       __builtin_amdgcn_s_barrier();
       if (ch + 2 < F_NCH) issue(ch + 2, tile);
       else if (!g1 && more) { issue(0, tile + gridDim.x); issue(1, tile + gridDim.x); }

@@ -64,7 +64,8 @@ template <bool H> struct Prec { static constexpr int BK = H ? 32 : 16; static co
 // KS: 32-deep MFMA sub-steps per stage of the bf16 path (BK = 32*KS). KS = 2 doubles the bytes a workgroup keeps in flight
 // and halves the barriers per reduction element: the GEMMs with <= 2 workgroups per CU (the C = 256 / 512 stages: 256-512
 // tiles) were fetching at 16 GB/s per CU against the 60-70 GB/s the L2 -> LDS path delivers (round-2 shape table).
-template <int ROWS, bool RMAJOR, bool H, bool SRC16 = false, int KS = 1, int NT = 256>
+constexpr int NT = 256;      // threads per workgroup: 4 waves in a 2x2 grid over the tile
+template <int ROWS, bool RMAJOR, bool H, bool SRC16 = false, int KS = 1>
 struct TileGeom {
   static_assert(KS == 1 || H, "deeper stages exist on the bf16 path only");
   static constexpr int BK = Prec<H>::BK * KS, ESZ = Prec<H>::ESZ;
@@ -104,19 +105,19 @@ struct TileGeom {
 // (issue early / write late): stage_load only ISSUES the 16-byte loads; stage_store, which runs after the MFMAs,
 // applies affine + activation, zero-fills out-of-range chunks, rounds to bf16 in the H path, and writes LDS.
 // A bf16-stored operand without affine is copied chunk-for-chunk (its HBM image IS the LDS image).
-template <int ROWS, bool RMAJOR, bool H, bool SRC16, int KS = 1, int NT = 256>
+template <int ROWS, bool RMAJOR, bool H, bool SRC16, int KS = 1>
 struct StageRegs {
-  static constexpr int VEC = TileGeom<ROWS, RMAJOR, H, SRC16, KS, NT>::VEC;
+  static constexpr int VEC = TileGeom<ROWS, RMAJOR, H, SRC16, KS>::VEC;
   f32x4 v[VEC];      // raw 16-byte chunks (4 fp32 or 8 bf16)
   bool ok[VEC];
 };
 
 // FULL: the tile and every stage lie inside the operand (host-checked), so there is no predication at all — the bounds
 // logic (compare, select, zero-fill per chunk) is a third of the instructions of a K = 256 tile otherwise.
-template <int ROWS, bool RMAJOR, bool H, bool SRC16, bool FULL, int KS = 1, bool PAD = false, int NT = 256>
-__device__ __forceinline__ void stage_load(StageRegs<ROWS, RMAJOR, H, SRC16, KS, NT>& s, const char* __restrict__ base, long ld,
+template <int ROWS, bool RMAJOR, bool H, bool SRC16, bool FULL, int KS = 1, bool PAD = false>
+__device__ __forceinline__ void stage_load(StageRegs<ROWS, RMAJOR, H, SRC16, KS>& s, const char* __restrict__ base, long ld,
                                            int row0, int nrows, int r0, int rend, const GemmArgs* pad = nullptr) {
-  using G = TileGeom<ROWS, RMAJOR, H, SRC16, KS, NT>;
+  using G = TileGeom<ROWS, RMAJOR, H, SRC16, KS>;
   static_assert(!PAD || !FULL, "padded views take the predicated path");
   const int t = threadIdx.x;
 #pragma unroll
@@ -141,10 +142,10 @@ __device__ __forceinline__ void stage_load(StageRegs<ROWS, RMAJOR, H, SRC16, KS,
 // reduction-indexed affine (producer BatchNorm) of an R-major operand for the stage that starts at r0. VMEM completes in
 // order, so these small loads must be issued BEFORE the operand loads of a later stage: issued after them, the first
 // use would wait for the whole prefetch (vmcnt is positional) and collapse the pipeline.
-template <int ROWS, bool H, bool SRC16, int KS = 1, int NT = 256>
+template <int ROWS, bool H, bool SRC16, int KS = 1>
 __device__ __forceinline__ void affine_prefetch(f32x4* sc, f32x4* sh, int r0, int rend, const float* scale,
                                                 const float* shift) {
-  using G = TileGeom<ROWS, true, H, SRC16, KS, NT>;
+  using G = TileGeom<ROWS, true, H, SRC16, KS>;
 #pragma unroll
   for (int q = 0; q < G::VEC; ++q) {
     const int gr = r0 + ((threadIdx.x + NT * q) % G::CPR) * G::EPC;
@@ -158,10 +159,10 @@ __device__ __forceinline__ void affine_prefetch(f32x4* sc, f32x4* sh, int r0, in
 }
 
 // column-indexed affine of an i/j-major operand is the same for every stage: fetched once per kernel
-template <int ROWS, bool H, bool SRC16, int KS = 1, int NT = 256>
+template <int ROWS, bool H, bool SRC16, int KS = 1>
 __device__ __forceinline__ void colaffine_load(f32x4* sc, f32x4* sh, int row0, int nrows, const float* scale,
                                                const float* shift) {
-  using G = TileGeom<ROWS, false, H, SRC16, KS, NT>;
+  using G = TileGeom<ROWS, false, H, SRC16, KS>;
 #pragma unroll
   for (int q = 0; q < G::VEC; ++q) {
     const int cv = ((threadIdx.x + NT * q) % G::CPC) * G::EPC;
@@ -184,10 +185,10 @@ __device__ __forceinline__ f32x4 relu_bf16x8(f32x4 raw) {
   return __builtin_bit_cast(f32x4, h);
 }
 
-template <int ROWS, bool RMAJOR, bool H, bool SRC16, bool RELU16 = false, int KS = 1, int NT = 256>
-__device__ __forceinline__ void stage_store(char* lds, const StageRegs<ROWS, RMAJOR, H, SRC16, KS, NT>& s, bool affine,
+template <int ROWS, bool RMAJOR, bool H, bool SRC16, bool RELU16 = false, int KS = 1>
+__device__ __forceinline__ void stage_store(char* lds, const StageRegs<ROWS, RMAJOR, H, SRC16, KS>& s, bool affine,
                                             float slope, const f32x4* csc, const f32x4* csh) {
-  using G = TileGeom<ROWS, RMAJOR, H, SRC16, KS, NT>;
+  using G = TileGeom<ROWS, RMAJOR, H, SRC16, KS>;
   const int t = threadIdx.x;
 #pragma unroll
   for (int q = 0; q < G::VEC; ++q) {
@@ -242,11 +243,11 @@ __device__ __forceinline__ void stage_store(char* lds, const StageRegs<ROWS, RMA
 // ABN staging of an R-major bf16 tile: dr = sc*g + (P*r + Q), g = z > 0 ? dy : dy*slope, z = sc*r + sh, rounded to bf16 once (the value
 // bn_bwd_apply would have stored), written to the LDS image and — for the workgroups of column tile 0 — to the dr side output.
 // Every chunk of a thread covers the SAME 8 reduction channels (NT % CPR == 0), so the four coefficient vectors are 8 registers each.
-template <int ROWS, int KS, int NT>
-__device__ __forceinline__ void stage_store_abn(char* lds, const StageRegs<ROWS, true, true, true, KS, NT>& dy,
-                                                const StageRegs<ROWS, true, true, true, KS, NT>& rr, const f32x4* cf, float slope,
+template <int ROWS, int KS>
+__device__ __forceinline__ void stage_store_abn(char* lds, const StageRegs<ROWS, true, true, true, KS>& dy,
+                                                const StageRegs<ROWS, true, true, true, KS>& rr, const f32x4* cf, float slope,
                                                 char* side, long side_ld) {
-  using G = TileGeom<ROWS, true, true, true, KS, NT>;
+  using G = TileGeom<ROWS, true, true, true, KS>;
   static_assert(NT % G::CPR == 0, "a thread keeps its reduction channels over the chunks of a stage");
   const int t = threadIdx.x;
   const bool masked = slope != 1.f;          // uniform: a BatchNorm without an activation behind it needs no mask (g = dy)
@@ -337,16 +338,13 @@ __device__ unsigned long long* g_gemm_trace = nullptr;
 
 // ARELU: the left operand is a bf16 activation that only needs ReLU on load (an eval-mode BatchNorm folded into the producer's
 // weights leaves no affine): applied on the packed bf16 values, no conversion, no per-channel vectors.
-// KS / PD: 32-deep sub-steps per stage and register sets (= stages in flight) of the pipelined loop; PD = 0 keeps the round-1
-// rule (2 sets, 1 for the full-tile forward kernel). The deep forms (KS = 2 and/or PD = 4) are FULL-tile bf16 variants for the
-// shapes that put <= 2 workgroups on a CU, where only bytes in flight per workgroup hide the memory latency.
-// NW: waves per workgroup, laid out (NW/2) x 2 over the tile. NW = 8 on 256x128 tiles gives every wave the 64x64 sub-tile
-// of the 4-wave 128x128 kernel while a stage moves a quarter fewer operand bytes per flop, at two workgroups = 16 waves
-// per CU (the 4-wave 256x128 form needs 201 registers: 8 waves per CU).
+// KS: 32-deep sub-steps per stage of the pipelined loop. The deep form (KS = 2, always two register sets = stages in flight) is a
+// FULL-tile bf16 variant for the shapes that put <= 2 workgroups on a CU, where only bytes in flight per workgroup hide the memory
+// latency.
 // The body is a device function of (arguments, tile index, split index, group): gemm_kernel derives the three from its own grid,
 // wgrad_grouped_kernel (below) from a table of many weight-gradient problems served by ONE launch.
 template <int BM, int BN, bool A_RMAJOR, bool B_RMAJOR, bool H, bool ST, bool AAFF, bool WB = false, bool FULL = false,
-          bool ARELU = false, int KS = 1, int PD = 0, bool EC = false, int PADX = 0, int NW = 4, bool ABN = false>
+          bool ARELU = false, int KS = 1, int PADX = 0, bool ABN = false>
 __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, const int split, const int g) {
   unsigned long long* const trace = g_gemm_trace;
   unsigned long long t_start = 0, t_loop = 0;
@@ -354,28 +352,21 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
   constexpr bool SA = ST, SB = (ST && !A_RMAJOR && !B_RMAJOR) || WB, SC = ST && A_RMAJOR;
   static_assert(!WB || (ST && A_RMAJOR), "bf16 weights ride with bf16 activations in the forward/backward-data GEMMs");
   static_assert(!ARELU || (ST && A_RMAJOR && B_RMAJOR && !AAFF && FULL), "ReLU-on-load is a forward, full-tile, bf16 variant");
-  static_assert((KS == 1 && PD == 0) || (FULL && H && ST), "the deep pipelines are full-tile bf16-storage variants");
-  static_assert(!EC || PD >= 2, "early commit rides with the deep pipelines");
-  static_assert(NW == 4 || NW == 8, "4 waves as 2x2 or 8 waves as 4x2");
-  static_assert(!ABN || (FULL && H && ST && WB && A_RMAJOR && !B_RMAJOR && !AAFF && !ARELU && !EC && PADX == 0 && NW == 4),
+  static_assert(KS == 1 || (FULL && H && ST), "the deep pipeline is a full-tile bf16-storage variant");
+  static_assert(!ABN || (FULL && H && ST && WB && A_RMAJOR && !B_RMAJOR && !AAFF && !ARELU && PADX == 0),
                 "the BatchNorm-backward operand load is a full-tile bf16 backward-data variant");
-  constexpr int NT = 64 * NW, WROWS = NW / 2;
-  using GA = TileGeom<BM, A_RMAJOR, H, SA, KS, NT>;
-  using GB = TileGeom<BN, B_RMAJOR, H, SB, KS, NT>;
+  constexpr int WAVES = NT / 64, WROWS = 2;            // waves laid out WROWS x 2 over the tile
+  using GA = TileGeom<BM, A_RMAJOR, H, SA, KS>;
+  using GB = TileGeom<BN, B_RMAJOR, H, SB, KS>;
   constexpr int BK = Prec<H>::BK * KS;
   constexpr int WM = BM / WROWS, WN = BN / 2, TM = WM / 16, TN = WN / 16;
   // BatchNorm partial sums are per NSID_ROW_TILE = 128 rows: a tile of BM rows covers STILES of them, each made of WPT wave-rows
   constexpr int STILES = BM >= 128 ? BM / 128 : 1, WPT = WROWS / STILES;
   constexpr int STAGE = GA::BYTES + GB::BYTES;
-  constexpr int RB = NW == 8 ? 16 : 32;                // rows a wave transposes through LDS at a time (epilogue)
-  constexpr int OUT_STAGE = NW * RB * (WN + 4) * 4     // epilogue transpose buffers (one per wave x RB rows), bytes
+  constexpr int RB = 32;                               // rows a wave transposes through LDS at a time (epilogue)
+  constexpr int OUT_STAGE = WAVES * RB * (WN + 4) * 4  // epilogue transpose buffers (one per wave x RB rows), bytes
                             + 2 * WROWS * 4 * BN * 4;  // + parked BatchNorm sums [2][wave-rows][4 row groups][BN]
-  // EC (early commit): THREE stage buffers, so that stage s+1 can be written to LDS while stage s is still being read: the
-  // loop then issues the fragment reads of stage s, commits stage s+1 (its waits and ds_writes run under the read latency)
-  // and only then starts the MFMAs — in the two-buffer order (MFMA, then commit, then barrier) a wave's LDS-read latency,
-  // its ds_write completion and the barrier were all exposed: ~800 cycles per 32-deep slab against 256 cycles of MFMA.
-  constexpr int NBUF = EC ? 3 : 2;
-  constexpr int LDS_BYTES = NBUF * STAGE > OUT_STAGE ? NBUF * STAGE : OUT_STAGE;
+  constexpr int LDS_BYTES = 2 * STAGE > OUT_STAGE ? 2 * STAGE : OUT_STAGE;
   __shared__ __attribute__((aligned(16))) char lds_raw[LDS_BYTES];
   float* lds = reinterpret_cast<float*>(lds_raw);
 
@@ -411,7 +402,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
   constexpr bool a_aff = AAFF;
   const bool b_aff = !B_RMAJOR && b_sc != nullptr;
   f32x4 bcs[GB::VEC * GB::EPC / 4], bch[GB::VEC * GB::EPC / 4];
-  if (b_aff) colaffine_load<BN, H, SB, KS, NT>(bcs, bch, j0, p.J, b_sc, b_sh);
+  if (b_aff) colaffine_load<BN, H, SB, KS>(bcs, bch, j0, p.J, b_sc, b_sh);
   const int nstage = (rend - rbeg + BK - 1) / BK;
 
   // Register prefetch depth: fp32 MFMA blocks (64 x 32 cycles) cover one memory round trip, so one stage in flight
@@ -420,11 +411,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
   // Exception: the full-tile forward kernel with bf16 weights and no operand affine keeps ONE stage in flight: measured
   // 7-10 % faster than the deeper prefetch when introduced and equal to it now (tools/gemm_trace.py: 3 workgroups per CU
   // are resident either way, the loop is bound by the L2 -> LDS rate, ~53 GB/s per CU, not by load latency).
-  constexpr int DEPTH = PD > 0 ? PD : ((H && !(FULL && WB && !AAFF && BN == 128 && A_RMAJOR && B_RMAJOR)) ? 2 : 1);
-  static_assert(DEPTH == 1 || DEPTH == 2 || DEPTH == 4, "the unrolled loop body needs an even number of register sets");
-  StageRegs<BM, A_RMAJOR, H, SA, KS, NT> ra[DEPTH];
-  StageRegs<BN, B_RMAJOR, H, SB, KS, NT> rb[DEPTH];
-  StageRegs<BM, A_RMAJOR, H, SA, KS, NT> ra2[ABN ? DEPTH : 1];     // ABN: the second source tensor (r) of the left operand
+  // The deep form (KS = 2) always keeps two.
+  constexpr int DEPTH = (KS == 2 || (H && !(FULL && WB && !AAFF && BN == 128 && A_RMAJOR && B_RMAJOR))) ? 2 : 1;
+  StageRegs<BM, A_RMAJOR, H, SA, KS> ra[DEPTH];
+  StageRegs<BN, B_RMAJOR, H, SB, KS> rb[DEPTH];
+  StageRegs<BM, A_RMAJOR, H, SA, KS> ra2[ABN ? DEPTH : 1];     // ABN: the second source tensor (r) of the left operand
   f32x4 abn_cf[ABN ? 8 : 1];                                        // ABN: {sc, sh, P, Q} x 8 channels of the stage being committed
   const char* A2 = ABN ? reinterpret_cast<const char*>(p.abn_r) + g * p.a_goff * GA::SSZ : nullptr;
 
@@ -470,12 +461,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         sb.ok[q] = true;
       }
     } else {
-      stage_load<BM, A_RMAJOR, H, SA, FULL, KS, PADX == 1, NT>(sa, A, p.lda, i0, p.I, r0, rend, &p);
-      stage_load<BN, B_RMAJOR, H, SB, FULL, KS, PADX == 2, NT>(sb, B, p.ldb, j0, p.J, r0, rend, &p);
+      stage_load<BM, A_RMAJOR, H, SA, FULL, KS, PADX == 1>(sa, A, p.lda, i0, p.I, r0, rend, &p);
+      stage_load<BN, B_RMAJOR, H, SB, FULL, KS, PADX == 2>(sb, B, p.ldb, j0, p.J, r0, rend, &p);
     }
   };
   auto aff_fetch = [&](int st) {
-    if constexpr (AAFF) affine_prefetch<BM, H, SA, KS, NT>(acs, ach, rbeg + st * BK, rend, a_sc, a_sh);
+    if constexpr (AAFF) affine_prefetch<BM, H, SA, KS>(acs, ach, rbeg + st * BK, rend, a_sc, a_sh);
     if constexpr (ABN) {       // the 8 channels of this thread's chunks in stage st (past the end: the last stage again, unused)
       const int r0 = min(rbeg + st * BK, rend - BK) + (int)(threadIdx.x % GA::CPR) * 8;
       const float* c = p.abn_coef + g * p.a_goff + r0;
@@ -487,51 +478,15 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     }
   };
   auto commit = [&](const auto& sa, const auto& sb, const auto& sa2, int st) {
-    char* dst = lds_raw + (EC ? st % 3 : (st & 1)) * STAGE;
+    char* dst = lds_raw + (st & 1) * STAGE;
     if constexpr (ABN) {
       // column tile 0 of every row panel also stores dr (each stage exactly once: phantom stages past the end write LDS only)
       char* side = (tj == 0 && st < nstage && p.abn_dr != nullptr)
                        ? reinterpret_cast<char*>(p.abn_dr) + ((long)i0 * p.abn_lddr + g * p.a_goff + rbeg + st * BK) * 2 : nullptr;
-      stage_store_abn<BM, KS, NT>(dst, sa, sa2, abn_cf, p.abn_slope, side, p.abn_lddr);
+      stage_store_abn<BM, KS>(dst, sa, sa2, abn_cf, p.abn_slope, side, p.abn_lddr);
     } else
-    stage_store<BM, A_RMAJOR, H, SA, ARELU, KS, NT>(dst, sa, a_aff, p.a_slope, acs, ach);
-    stage_store<BN, B_RMAJOR, H, SB, false, KS, NT>(dst + GA::BYTES, sb, b_aff, p.b_slope, bcs, bch);
-  };
-  // early-commit form of one stage: the fragment reads of stage st, the global loads of stage st+DEPTH (`loads()`), the commit
-  // of stage st+1 (`between()`) and the MFMAs of stage st are ONE scheduling region, and the sched_group_barrier sequence
-  // asks for: all fragment reads first, then {2 MFMAs, 1 global load, 1 ds_write} repeated — a wave that issues its 16
-  // global loads back to back sits in the memory pipeline's issue queue for hundreds of cycles (a 1 KB wave-load takes the
-  // CU's vector memory path >= 16 cycles) and, alone on its SIMD, issues no MFMA meanwhile.
-  auto compute_ec = [&](int st, auto&& loads, auto&& between) {
-    const char* la = lds_raw + (st % 3) * STAGE;
-    const char* lb = la + GA::BYTES;
-    bf16x8 fa[KS][TM], fb[KS][TN];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-#pragma unroll
-      for (int a = 0; a < TM; ++a) fa[ks][a] = frag_read_bf16<BM, A_RMAJOR, KS>(la, wm0 + 16 * a, lr, rq, ks);
-#pragma unroll
-      for (int b = 0; b < TN; ++b) fb[ks][b] = frag_read_bf16<BN, B_RMAJOR, KS>(lb, wn0 + 16 * b, lr, rq, ks);
-    }
-    loads();
-    between();
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int a = 0; a < TM; ++a)
-#pragma unroll
-        for (int b = 0; b < TN; ++b)
-          acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[ks][a], fb[ks][b], acc[a][b], 0, 0, 0);
-    constexpr int NMFMA = KS * TM * TN, NLOAD = GA::VEC + GB::VEC;
-    constexpr int NDSR = KS * (TM * (A_RMAJOR ? 1 : 2) + TN * (B_RMAJOR ? 1 : 2));
-    __builtin_amdgcn_sched_group_barrier(0x100, NDSR, 0);
-    constexpr int PER = NMFMA / NLOAD > 0 ? NMFMA / NLOAD : 1;
-#pragma unroll
-    for (int i = 0; i < NLOAD; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
-      __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-    }
+    stage_store<BM, A_RMAJOR, H, SA, ARELU, KS>(dst, sa, a_aff, p.a_slope, acs, ach);
+    stage_store<BN, B_RMAJOR, H, SB, false, KS>(dst + GA::BYTES, sb, b_aff, p.b_slope, bcs, bch);
   };
   auto compute = [&](int st) {
     const char* la = lds_raw + (st & 1) * STAGE;
@@ -602,18 +557,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     for (int st = 0; st < nstage; st += DEPTH) {
 #pragma unroll
       for (int u = 0; u < DEPTH; ++u) {
-        if constexpr (EC) {
-          aff_fetch(st + u + 1);
-          compute_ec(st + u, [&] { issue(ra[u], rb[u], ra2[ABN ? (u) : 0], st + u + DEPTH); },
-                     [&] { commit(ra[(u + 1) % DEPTH], rb[(u + 1) % DEPTH], ra2[ABN ? ((u + 1) % DEPTH) : 0], st + u + 1); });
-        } else {
-          aff_fetch(st + u + 1);
-          issue(ra[u], rb[u], ra2[ABN ? (u) : 0], st + u + DEPTH);
-          __builtin_amdgcn_sched_barrier(0);
-          compute(st + u);
-          __builtin_amdgcn_sched_barrier(0);
-          commit(ra[(u + 1) % DEPTH], rb[(u + 1) % DEPTH], ra2[ABN ? ((u + 1) % DEPTH) : 0], st + u + 1);
-        }
+        aff_fetch(st + u + 1);
+        issue(ra[u], rb[u], ra2[ABN ? (u) : 0], st + u + DEPTH);
+        __builtin_amdgcn_sched_barrier(0);
+        compute(st + u);
+        __builtin_amdgcn_sched_barrier(0);
+        commit(ra[(u + 1) % DEPTH], rb[(u + 1) % DEPTH], ra2[ABN ? ((u + 1) % DEPTH) : 0], st + u + 1);
         __syncthreads();
       }
     }
@@ -666,7 +615,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     if (p.stat != nullptr) {
       // BatchNorm partial statistics of (acc + bias) from the accumulator registers, parked in LDS behind the transpose
       // buffers BEFORE the store loop: its barrier publishes them and the stores hide the LDS latency
-      float* red = lds + NW * RB * OLD;      // [2 sums][wave-rows][4 row groups][BN]
+      float* red = lds + WAVES * RB * OLD;      // [2 sums][wave-rows][4 row groups][BN]
 #pragma unroll
       for (int b = 0; b < TN; ++b) {
         const bool jok = FULL || j0 + wn0 + 16 * b + lr < p.J;
@@ -803,11 +752,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     __syncthreads();                // every wave is done with its transpose buffer; publishes the parked statistics
     if (CAN_BNRED) {
       if (bnred) {                  // uniform; the stage / transpose buffers are free (barrier above)
-        float* red2 = lds;          // [2][NW waves][ROWS_PER_PASS][WN]
+        float* red2 = lds;          // [2][waves][ROWS_PER_PASS][WN]
 #pragma unroll
         for (int e = 0; e < OE; ++e) {
-          red2[((0 * NW + wave) * ROWS_PER_PASS + orow) * WN + oq + e] = s0[e / 2][e & 1];
-          red2[((1 * NW + wave) * ROWS_PER_PASS + orow) * WN + oq + e] = s1[e / 2][e & 1];
+          red2[((0 * WAVES + wave) * ROWS_PER_PASS + orow) * WN + oq + e] = s0[e / 2][e & 1];
+          red2[((1 * WAVES + wave) * ROWS_PER_PASS + orow) * WN + oq + e] = s1[e / 2][e & 1];
         }
         __syncthreads();
         if (threadIdx.x < BN) {
@@ -822,8 +771,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
               for (int wr = WPT * t2; wr < WPT * (t2 + 1); ++wr)
 #pragma unroll
                 for (int o = 0; o < ROWS_PER_PASS; ++o) {   // unrolled: the LDS reads pipeline instead of one round trip each
-                  a0 += red2[((0 * NW + (2 * wr + half)) * ROWS_PER_PASS + o) * WN + cw];
-                  a1 += red2[((1 * NW + (2 * wr + half)) * ROWS_PER_PASS + o) * WN + cw];
+                  a0 += red2[((0 * WAVES + (2 * wr + half)) * ROWS_PER_PASS + o) * WN + cw];
+                  a1 += red2[((1 * WAVES + (2 * wr + half)) * ROWS_PER_PASS + o) * WN + cw];
                 }
               p.bn_partial[((long)ti * STILES + t2) * p.bn_ld + col] = a0;
               p.bn_partial[p.bn_plane + ((long)ti * STILES + t2) * p.bn_ld + col] = a1;
@@ -834,7 +783,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     }
   }
   if (p.stat != nullptr) {   // uniform branch: the column sums were parked in LDS before the store loop (see above)
-    const float* red = lds + NW * RB * ((BN / 2) + 4);
+    const float* red = lds + WAVES * RB * ((BN / 2) + 4);
     if (threadIdx.x < BN) {
       const int j = j0 + threadIdx.x;
       if (FULL || j < p.J) {
@@ -866,8 +815,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
 }
 
 template <int BM, int BN, bool A_RMAJOR, bool B_RMAJOR, bool H, bool ST, bool AAFF, bool WB = false, bool FULL = false,
-          bool ARELU = false, int KS = 1, int PD = 0, bool EC = false, int PADX = 0, int NW = 4, bool ABN = false>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 4 : ((KS > 1 || PD > 2) ? 1 : ((FULL && WB && BM == 128 && BN == 128 && !AAFF && !ABN) ? 3 : 2)))   // waves per SIMD
+          bool ARELU = false, int KS = 1, int PADX = 0, bool ABN = false>
+__global__ __launch_bounds__(NT, KS > 1 ? 1 : ((FULL && WB && BM == 128 && BN == 128 && !AAFF && !ABN) ? 3 : 2))   // waves per SIMD
 void gemm_kernel(const GemmArgs p) {
   int bid = p.split_major ? blockIdx.y : blockIdx.x;
   const int split = p.split_major ? blockIdx.x : blockIdx.y;
@@ -877,7 +826,7 @@ void gemm_kernel(const GemmArgs p) {
     const int nwg = gridDim.x;
     if ((nwg & 7) == 0) bid = (bid & 7) * (nwg >> 3) + (bid >> 3);
   }
-  gemm_body<BM, BN, A_RMAJOR, B_RMAJOR, H, ST, AAFF, WB, FULL, ARELU, KS, PD, EC, PADX, NW, ABN>(p, bid, split, blockIdx.z);
+  gemm_body<BM, BN, A_RMAJOR, B_RMAJOR, H, ST, AAFF, WB, FULL, ARELU, KS, PADX, ABN>(p, bid, split, blockIdx.z);
 }
 
 // ---- many weight-gradient problems in ONE launch (the deferred phase of a training step: nsid_linear_bwd_weight_grouped) ----------
@@ -918,7 +867,7 @@ __device__ __forceinline__ void wgrad_grouped_item(const WgGroupArgs& ga, const 
   if constexpr (PADX == 2) {
     p.pad_period = q.pad_period; p.pad_phase = 0; p.pad_c0 = 0; p.pad_c1 = q.pad_c1; p.pad_safe = q.pad_c1;
   }
-  gemm_body<BM, BN, false, false, H, ST, false, false, FULL, false, FULL ? 2 : 1, FULL ? 2 : 0, false, PADX>(p, bid, split, g);
+  gemm_body<BM, BN, false, false, H, ST, false, false, FULL, false, FULL ? 2 : 1, PADX>(p, bid, split, g);
   // (the body's reduction loop ends with a workgroup barrier behind the last fragment reads and its atomic epilogue does not touch
   // LDS: the next item of a capped launch may stage its first operands right away)
 }
@@ -940,7 +889,7 @@ int g_gemm_precision = NSID_GEMM_FP32;     // process-wide (nsid_set_gemm_precis
 // so that the arithmetic of a training step does not depend on the batch size.
 long g_g256_launches = 0;     // launches that took gemm256.hip (tests check that the kernel under test really ran)
 
-template <int BM, int BN, bool AR, bool BR, int NW = 4>
+template <int BM, int BN, bool AR, bool BR>
 int launch(GemmArgs p, int groups, hipStream_t s, int act_dtype, bool w_bf16 = false) {
   const int tiles = ((p.I + BM - 1) / BM) * ((p.J + BN - 1) / BN);
   const bool st16 = act_dtype == NSID_BF16;
@@ -961,41 +910,26 @@ int launch(GemmArgs p, int groups, hipStream_t s, int act_dtype, bool w_bf16 = f
   } while (0)
   // FULL: whole tiles and an even number of whole stages per split -> the predication-free instantiation
   const bool full = st16 && p.I % BM == 0 && p.J % BN == 0 && p.rchunk % (2 * bk) == 0 && p.R % p.rchunk == 0;
-  // Deep pipeline (KS = 2: 64-deep stages; PD = 4: four stages in flight) for launches that put at most ~2 workgroups on a
-  // CU: there the round-1 loop kept 16-32 KB per workgroup in flight and fetched at ~16 GB/s per CU (shape table of round 2:
-  // the 256-tile GEMMs of the C = 256 stage ran 32 us against a 7 us HBM/MFMA bound). Tuning keys gemm_deep_{ks,pd,max_wg,ec,kinds}.
+  // Deep pipeline (KS = 2: 64-deep stages, two of them in flight) for launches that put at most ~2 workgroups on a CU: there the
+  // round-1 loop kept 16-32 KB per workgroup in flight and fetched at ~16 GB/s per CU (shape table of round 2: the 256-tile
+  // GEMMs of the C = 256 stage ran 32 us against a 7 us HBM/MFMA bound). Tuning keys gemm_deep_{ks,max_wg,kinds}.
   // Measured on MI355X with cold operands (tools/gemm_bench.py --cold, round 2), 256-512 workgroups per launch:
-  //   forward        : KS = 2, two register sets, early commit with the interleaved schedule: 26.4 -> 18.2 us (16384x256x1024),
-  //                    44.5 -> 27.0 us (8192x512x2048), 15.7 -> 11.9 us (16384x256x512);
-  //   weight gradient: KS = 2 without early commit: 16.4 -> 12.9 us (16384x256x256), 20.8 -> 18.7 us; early commit loses 30 %;
+  //   forward        : 26.4 -> 20.4 us (16384x256x1024), 44.5 -> 32.1 us (8192x512x2048), 15.7 -> 13.1 us (16384x256x512);
+  //   weight gradient: 16.4 -> 12.9 us (16384x256x256), 20.8 -> 18.7 us;
   //   backward-data  : no deep form wins (the epilogue with addend / BatchNorm sums dominates): round-1 loop kept.
-  // In the TWO-STREAM training step the isolated gains mostly vanish: a workgroup that owns a CU's LDS (120 KB with three
-  // stage buffers) keeps the other view's kernels off that CU, and what the step rewards is little resource-time per
-  // tile, not latency. One-box A/B of the whole step (two repetitions each): round-1 loops 8.52 / 8.52 ms, KS = 2 for
-  // forward + weight gradient 8.41 / 8.43 ms, the same with early commit 8.55 / 8.57 ms -> KS = 2 without early commit is the
-  // default; early commit (tuning key gemm_deep_ec = 1) remains for single-stream use (inference, microbenchmarks).
-  const int deep_ks = (int)nsid_tune(NSID_T_gemm_deep_ks), deep_pd = (int)nsid_tune(NSID_T_gemm_deep_pd);
+  // In the TWO-STREAM training step the isolated gains mostly vanish: what the step rewards is little resource-time per tile,
+  // not latency. One-box A/B of the whole step (two repetitions each): round-1 loops 8.52 / 8.52 ms, KS = 2 for forward +
+  // weight gradient 8.41 / 8.43 ms -> the default. (Three LDS stage buffers with an early commit, and four register sets, were
+  // measured as well, lost that A/B twice, and were removed: docs/experiments.md.)
   const long deep_maxwg = nsid_tune(NSID_T_gemm_deep_max_wg);
-  const int deep_ec = (int)nsid_tune(NSID_T_gemm_deep_ec);
   // which GEMM kinds take the deep form: bit 0 forward, bit 1 backward-data, bit 2 weight gradient
   const int deep_kinds = (int)nsid_tune(NSID_T_gemm_deep_kinds);
   constexpr int kind_bit = AR ? (BR ? 1 : 2) : 4;
   const long wgs = (long)tiles * p.rsplit * groups;
-  int ks = 1, pd = 0;
-  if (NW == 4 && full && wgs <= deep_maxwg && (deep_ks > 1 || deep_pd > 2) && (deep_kinds & kind_bit)) {
-    ks = deep_ks == 2 ? 2 : 1;
-    pd = deep_pd == 4 ? 4 : (ks == 2 ? 2 : 0);
-    const int need = 32 * ks * (pd ? pd : 2);                     // whole register-set rounds of whole stages
-    if (p.rchunk % need != 0) {                                   // fall back one notch at a time
-      if (pd == 4 && p.rchunk % (32 * ks * 2) == 0) pd = ks == 2 ? 2 : 0;
-      else if (ks == 2 && p.rchunk % (32 * (pd ? pd : 2)) == 0) ks = 1;
-      else { ks = 1; pd = 0; }
-      if (ks == 1 && pd == 2) pd = 0;
-    }
-  }
-  const bool ec = deep_ec != 0 && BM * BN <= 128 * 128 && (AR && BR);   // forward only; three buffers of a 256x128 tile do not fit LDS
+  // (rchunk % 128: whole rounds of two 64-deep stages)
+  const int ks = (full && wgs <= deep_maxwg && nsid_tune(NSID_T_gemm_deep_ks) == 2 && (deep_kinds & kind_bit) && p.rchunk % 128 == 0) ? 2 : 1;
   if (p.abn_r != nullptr) {     // outside the fused BatchNorm-backward form: 1 = nothing launched, the caller runs the unfused pair
-    if (!(AR && !BR && NW == 4 && BM == 128)) return NSID_EINVAL;
+    if (!(AR && !BR && BM == 128)) return NSID_EINVAL;
     if (!(st16 && w_bf16 && full)) return 1;
   }
   nsid_count(AR ? (BR ? NSID_C_gemm_fwd : NSID_C_gemm_bwd_data) : NSID_C_gemm_bwd_weight);
@@ -1008,38 +942,22 @@ int launch(GemmArgs p, int groups, hipStream_t s, int act_dtype, bool w_bf16 = f
     const bool deep_path = st16 && full && (AR ? w_bf16 : true);
     if (deep_path) {
       nsid_count(NSID_C_gemm_full);
-      if (NW == 4 && ks == 2) nsid_count(NSID_C_gemm_ks2);
-      if (NW == 4 && pd == 4) nsid_count(NSID_C_gemm_pd4);
-      if (NW == 4 && ec && (ks == 2 || pd == 4)) nsid_count(NSID_C_gemm_ec);
+      if (ks == 2) nsid_count(NSID_C_gemm_ks2);
     }
   }
-#define NSID_GEMM_DEEP_GO(AFF_, WB_, RELU_)                                                                       \
-  do {                                                                                                            \
-    if constexpr (NW == 8) {                                                                                      \
-      NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 1, 0, false, 0, 8>), grid, dim3(512), 0, s, p); \
-      break;                                                                                                      \
-    }                                                                                                             \
-    if constexpr (BM * BN <= 128 * 128) {                                                                         \
-      if (ec && ks == 2 && pd == 4) { NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 2, 4, true>), grid, dim3(256), 0, s, p); break; } \
-      if (ec && ks == 2) { NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 2, 2, true>), grid, dim3(256), 0, s, p); break; }            \
-      if (ec && pd == 4) { NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 1, 4, true>), grid, dim3(256), 0, s, p); break; }            \
-    }                                                                                                             \
-    if (ks == 2 && pd == 4) NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 2, 4>), grid, dim3(256), 0, s, p); \
-    else if (ks == 2) NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 2, 2>), grid, dim3(256), 0, s, p);       \
-    else if (pd == 4) NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 1, 4>), grid, dim3(256), 0, s, p);       \
-    else NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_>), grid, dim3(256), 0, s, p);                           \
+#define NSID_GEMM_DEEP_GO(AFF_, WB_, RELU_)                                                                                  \
+  do {                                                                                                                       \
+    if (ks == 2) NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_, 2>), grid, dim3(256), 0, s, p); \
+    else NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, AFF_, WB_, true, RELU_>), grid, dim3(256), 0, s, p);           \
   } while (0)
   if (p.abn_r != nullptr) {     // backward-data with the BatchNorm backward on the operand load: one full-tile bf16 form
-    if constexpr (AR && !BR && NW == 4 && BM == 128) {
+    if constexpr (AR && !BR && BM == 128) {
       nsid_count(NSID_C_gemm_bn_apply_load);
-      NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, false, true, true, false, 1, 0, false, 0, 4, true>), grid, dim3(256), 0, s, p);
+      NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, false, true, true, false, 1, 0, true>), grid, dim3(256), 0, s, p);
       return nsid_launch_status();
     } else {
       return NSID_EINVAL;
     }
-  }
-  if constexpr (NW == 8) {
-    if (!(st16 && full && (w_bf16 || !AR))) return NSID_EINVAL;      // the 8-wave form exists for full bf16 tiles only
   }
   if constexpr (AR) {
     if (st16 && w_bf16) {
@@ -1087,13 +1005,13 @@ int launch_pad(GemmArgs p, int groups, hipStream_t s, int act_dtype, bool w_bf16
   if (w_bf16 && !(st16 && AR)) return NSID_EINVAL;
   if (st16 && w_bf16) {
     if constexpr (AR)
-      NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, false, true, false, false, 1, 0, false, PADX>), grid, dim3(256), 0, s, p);
+      NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, false, true, false, false, 1, PADX>), grid, dim3(256), 0, s, p);
   } else if (st16) {
-    NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, false, false, false, false, 1, 0, false, PADX>), grid, dim3(256), 0, s, p);
+    NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, true, false, false, false, false, 1, PADX>), grid, dim3(256), 0, s, p);
   } else if (half) {
-    NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, false, false, false, false, false, 1, 0, false, PADX>), grid, dim3(256), 0, s, p);
+    NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, true, false, false, false, false, false, 1, PADX>), grid, dim3(256), 0, s, p);
   } else {
-    NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, false, false, false, false, false, false, 1, 0, false, PADX>), grid, dim3(256), 0, s, p);
+    NSID_LAUNCH((gemm_kernel<BM, BN, AR, BR, false, false, false, false, false, false, 1, PADX>), grid, dim3(256), 0, s, p);
   }
   return nsid_launch_status();
 }

@@ -111,6 +111,31 @@ __device__ __forceinline__ float wave_min(float v) {
   return v;
 }
 
+// lane index from the hardware lane count (no threadIdx register kept live), and one 16-byte load of four floats
+__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
+__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// s_waitcnt with the builtin, not inline asm: the compiler's own wait-count bookkeeping then knows what has been waited for
+// (simm16 on gfx9: vmcnt [3:0] and [15:14], expcnt [6:4], lgkmcnt [11:8]; the fields not meant are left at their maximum)
+template <int VM, int LGKM = 0xF>
+__device__ __forceinline__ void nsid_waitcnt() {
+  static_assert(VM >= 0 && VM < 64 && LGKM >= 0 && LGKM < 16, "6-bit vmcnt, 4-bit lgkmcnt");
+  __builtin_amdgcn_s_waitcnt((VM & 0xF) | ((VM >> 4) << 14) | (7 << 4) | (LGKM << 8));
+}
+template <int N> __device__ __forceinline__ void wait_vm() { nsid_waitcnt<N>(); }
+__device__ __forceinline__ void wait_lgkm0() { nsid_waitcnt<63, 0>(); }
+
+// One LDS-DMA in the saddr form: 64 lanes x 16 B from (uniform 64-bit base) + (32-bit lane offset) to LDS bytes [dst, dst + 1 KB).
+// Inline asm because the builtin's address, once the compiler has hoisted base + offset out of the loop, becomes a 64-bit vector
+// add per instruction: 16 registers the 256-register budget of gemm256.hip does not have (they spilled INTO the main loop).
+// M0 (the LDS destination) is written in the statement that reads it and restored (cdna_hip_programming.md, inline-asm rules).
+// The compiler does not count this load in its vmcnt bookkeeping: used only inside main loops whose waits are all explicit.
+__device__ __forceinline__ void glds16(const char* sbase, unsigned voff, unsigned dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
+}
+
 // hipGetLastError() reports the last error of ANY earlier runtime call on this thread (torch's own included), so the
 // error state is cleared right before a launch and read right after it.
 #define NSID_LAUNCH(kernel, grid, block, shmem, stream, ...)                \
@@ -139,9 +164,7 @@ static inline bool nsid_aligned16(const void* p) { return (reinterpret_cast<uint
   X(stream_max_wg, 2048)       /* workgroup cap of the grid-stride streaming kernels (bn_apply, ...) */                       \
   X(bn_bwd_apply_max_wg, 384)  /* BatchNorm-backward apply pass: 1.5 workgroups per CU leave room for the other view */      \
   X(gemm_deep_ks, 2)           /* 32-deep MFMA sub-steps per LDS stage for launches of <= gemm_deep_max_wg workgroups */      \
-  X(gemm_deep_pd, 2)           /* register sets (= stages in flight) of those launches: 2 or 4 */                             \
   X(gemm_deep_max_wg, 1024)    /* round 5 re-sweep (weight-stationary kernels in): 512 -> 1024 = -0.8 % of the step (x3), deep plan neutral */ \
-  X(gemm_deep_ec, 0)           /* early commit (three LDS stage buffers): wins alone, loses in the two-stream step */         \
   X(gemm_deep_kinds, 5)        /* which GEMM kinds take the deep form: bit 0 forward, bit 1 backward-data, bit 2 weight gradient */ \
   X(bwd_split_max_tiles, 64)   /* fp32-storage backward-data launches of at most this many tiles and Nout >= 1024 split their reduction (atomics); 0 = never */ \
   X(fwd_narrow, -1)            /* -1: shape heuristic; 0 / 1 force 128- / 64-wide forward tiles */                             \
@@ -196,7 +219,6 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(gemm_fwd) X(gemm_bwd_data) X(gemm_bwd_weight)        /* launches of gemm.hip by kind */      \
   X(gemm_full)            /* predication-free full-tile instantiation */                        \
   X(gemm_ks2)             /* 64-deep LDS stages */                                              \
-  X(gemm_pd4) X(gemm_ec)                                                \
   X(gemm_bwd_split)       /* backward-data with a split reduction (the projector head) */   \
   X(gemm_split_major)     /* split index fastest in the grid (a split stays on one XCD) */      \
   X(gemm_affine_load)     /* producer BatchNorm + activation applied on the operand load */     \

@@ -34,9 +34,6 @@ constexpr int RR_LDS_MAX = 160 * 1024;
 // K next to P in LDS (rows of C + 4 floats: +16 B so that the 32 rows of a fragment read start in different banks), else P alone
 constexpr bool rr_k_in_lds(int C) { return (RR_N * (C + 4) + RR_N * RR_PW + RR_WAVES * RR_N) * 4 <= RR_LDS_MAX; }
 
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-
 // group g: {first query segment, query segments, offset into cidx, candidates}; its scores are the row-major (q count x c count)
 // block at out + out_off[g]. tile_off: prefix sums of the groups' workgroups (c count x query chunks), ngroups + 1 entries.
 template <int C, int DH>

@@ -41,8 +41,6 @@ __device__ __forceinline__ bool ki_less(KI a, int sa, KI b, int sb) {
 }
 __device__ __forceinline__ bool ki_before(KI a, KI thr) { return a.k < thr.k || (a.k == thr.k && a.i < thr.i); }
 
-__device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
-
 // one wave: list[0..k) <- the k smallest of list[0..k) and queue[0..cnt) (cnt <= 64). Every lane reads everything before any
 // lane writes: the LDS operations of one wave complete in order.
 __device__ __forceinline__ void merge_queue(KI* list, const KI* queue, int cnt, int k, int lane) {
@@ -64,8 +62,6 @@ __device__ __forceinline__ void merge_queue(KI* list, const KI* queue, int cnt, 
   if (lane < cnt && r1 < k) list[r1] = e1;
   __builtin_amdgcn_wave_barrier();
 }
-
-__device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 
 // one wave, one finished 32x32 tile: accumulator register g of lane (r, h) = (lane & 31, lane >> 5) is query row
 // (g & 3) + 8 (g >> 2) + 4 h of the tile against database row `col` (cv: the row exists, xv its squared norm). Scores that pass

@@ -31,22 +31,8 @@ static_assert(W4_RING <= 160 * 1024, "one workgroup per CU");
 
 typedef __attribute__((address_space(3))) void* w4_lds_ptr;
 
-// s_waitcnt vmcnt(N) with the builtin (the other counters at their maximum; gemm256.hip wait_vm)
-template <int N>
-__device__ __forceinline__ void w4_wait_vm() {
-  static_assert(N >= 0 && N < 64, "6-bit counter");
-  __builtin_amdgcn_s_waitcnt((N & 0xF) | ((N >> 4) << 14) | (7 << 4) | (0xF << 8));
-}
-__device__ __forceinline__ void w4_wait_lgkm0() { __builtin_amdgcn_s_waitcnt(0xC07F); }
-
-// one LDS-DMA in the saddr form: 64 lanes x 16 B from (uniform base) + (lane offset) to LDS bytes [dst, dst + 1 KB) (gemm256.hip glds16).
-// Not in the compiler's vmcnt bookkeeping: every wait on these loads is explicit.
-__device__ __forceinline__ void w4_glds16(const char* sbase, unsigned voff, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
-}
-
+// (the LDS-DMA and its explicit waits, wait_vm / wait_lgkm0: nsid_common.h. The DMA is not in the compiler's vmcnt bookkeeping:
+// every wait on these loads is explicit.)
 __device__ __forceinline__ bf16x8 w4_frag(const char* p) {
   typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
   const bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(p));
@@ -84,7 +70,7 @@ __device__ __forceinline__ void wgrad4_item(const WgProb& q, const int split, co
   auto issue = [&](int st, int slot) {           // stage st (clamped by the caller) -> ring slot
     const char* s = gbase + (long)st * W4_BK * ld2;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) w4_glds16(s + 2 * i * ld2, voff[i & 1], lds0 + slot * W4_SLOT + 2 * i * W4_ROW);
+    for (int i = 0; i < 4; ++i) glds16(s + 2 * i * ld2, voff[i & 1], lds0 + slot * W4_SLOT + 2 * i * W4_ROW);
   };
 
   // ---- fragment addressing: lane (lr, rq) reads row 8 rq + (lr >> 2) (+ 4), columns 4 (lr & 3) .. + 3 of a 16-column unit
@@ -150,8 +136,8 @@ __device__ __forceinline__ void wgrad4_item(const WgProb& q, const int split, co
   issue(min(2, last), 2);
 #define NSID_W4_STEP(U)                                        \
   do {                                                         \
-    w4_wait_vm<8>();                                           \
-    w4_wait_lgkm0();                                           \
+    wait_vm<8>();                                           \
+    wait_lgkm0();                                           \
     __builtin_amdgcn_s_barrier();                              \
     __builtin_amdgcn_sched_barrier(0);                         \
     issue(min(st + (U) + 3, last), ((U) + 3) & 3);             \
@@ -167,7 +153,7 @@ __device__ __forceinline__ void wgrad4_item(const WgProb& q, const int split, co
 #undef NSID_W4_STEP
   // the three clamped stages still in flight target slots 0-2, which the next item's prologue writes: drain them (this thread's own;
   // every wave stages its own region of a slot). Slot 3 (the last stage, possibly still being read by other waves) is not touched.
-  w4_wait_vm<0>();
+  wait_vm<0>();
 
   // ---- epilogue: lane (lr, rq), reg r of acc[a][b] = dW[i0 + 128 wr + 16 a + 4 rq + r][j0 + 64 wc + 16 b + lr]
   float* C = q.C + (long)g * q.I * q.J;

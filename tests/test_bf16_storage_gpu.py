@@ -39,8 +39,8 @@ CASES = [(512, 64, 64, 1, False, 0), (200, 256, 64, 1, True, 1), (384, 32, 32, 4
          (640, 64, 8, 1, False, 0), (2048, 1024, 256, 1, True, 1), (136, 192, 384, 1, False, 0),
          (512, 2048, 512, 1, True, 1), (256, 1024, 1024, 1, False, 0),   # >= 64 tiles of 128x128: the 8-wave wgrad form
          (16384, 256, 512, 1, True, 1), (16384, 1024, 256, 1, False, 0),  # 128x64 weight-gradient tiles (>= 256 workgroups of 1024 rows)
-         (16384, 1024, 256, 1, True, 1), (16384, 256, 1024, 1, True, 1),  # >= 1024 tiles of 128x128: 8-wave 256x128 forward (affine
-         (32768, 512, 128, 1, False, 0)]                                  # + statistics: two 128-row tiles per workgroup) / backward-data
+         (16384, 1024, 256, 1, True, 1), (16384, 256, 1024, 1, True, 1),  # >= 1024 tiles of 128x128, forward (affine + statistics)
+         (32768, 512, 128, 1, False, 0)]                                  # and backward-data
 
 
 @pytest.mark.parametrize("M,Nout,K,groups,affine,act", CASES)
@@ -216,7 +216,7 @@ def test_training_curve_bf16_storage_tracks_fp32(ops):
 @pytest.mark.parametrize("M,Nout,K,groups,act,add", [(512, 256, 1024, 1, 1, False), (640, 64, 128, 1, 1, True),
                                                        (384, 128, 64, 1, 0, False), (200, 64, 256, 1, 2, True),
                                                        (256, 32, 32, 4, 1, False),
-                                                       (16384, 256, 1024, 1, 1, True),      # 8-wave 256x128 tiles: two partial rows each
+                                                       (16384, 256, 1024, 1, 1, True),      # 1024 tiles of 128x128: 128 rows of partial sums
                                                        (16384, 128, 1024, 1, 0, False)])
 def test_bwd_data_emits_bn_backward_sums(ops, M, Nout, K, groups, act, add):
     """linear_bwd_data(bn=...) = the plain GEMM plus the column sums nsid_bn_bwd_reduce computes from its stored output"""

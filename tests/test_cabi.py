@@ -51,6 +51,9 @@ def test_tuning_table_roundtrip(libpath):
     assert {k: _lib.get_tuning(k) for k in keys} == defaults
     with pytest.raises(KeyError):
         _lib.set_tuning("no_such_key", 1)
+    for key, value in (("gemm_deep_ec", 1), ("gemm_deep_pd", 4)):      # removed with the pipeline forms they selected
+        with pytest.raises(KeyError):
+            _lib.set_tuning(key, value)
     # no getenv left in the kernel library
     syms = subprocess.run(["nm", "-D", "--undefined-only", libpath], capture_output=True, text=True).stdout
     assert "getenv" not in syms

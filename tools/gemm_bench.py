@@ -2,9 +2,12 @@
 """GEMM-family microbench on the shapes of the 't' encoder at B=256 (one view): per shape and direction, average
 device time (the repetitions are captured in one hipGraph), TFLOP/s and algorithmic GB/s.
 Usage: python tools/gemm_bench.py [--reps 20] [--only fwd] [--shapes MxNxKxG,...]
-Tuning keys of the kernel library (--tune key=value; the defaults are the measured winners): fwd_narrow=0/1,
-bwd_narrow=0/1 (64- vs 128-wide tiles), wgrad_wide=0 (never use the 8-wave 128x128 weight-gradient form),
-w3_wgs / w3_min_tiles (its workgroup target / smallest layer), knn_strips=1 (strip kNN kernel)."""
+Tuning keys of the kernel library that bear on these launches (--tune key=value; the table with every key and its default is
+NSID_TUNING_TABLE in csrc/nsid_common.h, the defaults are the measured winners): fwd_narrow / bwd_narrow = 0 / 1 (128- / 64-wide
+tiles; -1 = shape heuristic), gemm_deep_ks = 1 / 2, gemm_deep_max_wg, gemm_deep_kinds (64-deep stages: off / on, largest launch,
+which GEMM kinds), bwd_split_max_tiles, g256_min / g256_train / g256_grid (gemm256.hip), ws_gemm (wsgemm.hip, bit mask),
+wgrad_wide = 0 (never the 8-wave 128x128 weight-gradient form), w3_wgs / w3_min_tiles (its workgroup target / smallest layer),
+wgrad_rect, wgrad_wgs_rect, wgrad_wgs_sq, wgrad_rect_min, wgrad_sq_min (128x64 and square weight-gradient tiles and their splits)."""
 import argparse
 import os
 import sys
