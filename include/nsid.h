@@ -410,12 +410,23 @@ int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, in
  *   Group i = groups[4i .. 4i+3] = {first query segment, query segments, offset into cidx, candidates}; its scores go row-major
  *   (query x candidate) to out + out_off[i]. tile_off: ngroups + 1 prefix sums of candidates x ceil(query segments / 64), ntiles =
  *   tile_off[ngroups]. The caller guarantees the lists are in range (the kernel skips, never writes, an out-of-range entry). A
- *   pair's score is bitwise independent of the rest of the call; no atomics. q, kp 16-byte aligned. */
+ *   pair's score is bitwise independent of the rest of the call; no atomics. q, kp 16-byte aligned.
+ * clf_node_rows_n, clf_pair_scores_n: the same two operations for 1 <= N <= 128 nodes (evaluation of the 256-mel configuration, whose
+ *   last stage has 128 nodes); arguments as clf_node_rows and clf_pair_scores_c, C in {512, 640, 768, 1024} for both. A head's
+ *   attention is up to 4 x 4 tiles of 32 x 32: keys >= N get no weight, query rows >= N no share in the column mean, which divides
+ *   by N, and no row at or beyond nq_seg N of q or nc_seg N of kp is read. Same guarantees: fixed summation order, no atomics, a
+ *   pair's score bitwise independent of the rest of the call. N = 0, N > 128, another C, a null or (q, kp) misaligned pointer:
+ *   NSID_EINVAL before anything is read or launched. Launches count on their own counters (clf_node_rows_n, clf_pair_scores_n); the
+ *   entries above keep their bound N <= 32 and their kernels. */
 int nsid_clf_node_rows(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream);
 int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups, const int64_t* out_off,
                          const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail, float* out,
                          int64_t out_len, void* stream);
 int nsid_clf_pair_scores_c(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
+                           const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail,
+                           float* out, int64_t out_len, void* stream);
+int nsid_clf_node_rows_n(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream);
+int nsid_clf_pair_scores_n(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
                            const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail,
                            float* out, int64_t out_len, void* stream);
 

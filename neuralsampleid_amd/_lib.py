@@ -75,6 +75,8 @@ SIGNATURES = {
     "nsid_clf_node_rows": "piiipps",
     "nsid_clf_pair_scores": "pipiipppiipppls",
     "nsid_clf_pair_scores_c": "pipiiipppiipppls",
+    "nsid_clf_node_rows_n": "piiipps",
+    "nsid_clf_pair_scores_n": "pipiiipppiipppls",
     "nsid_clf_mine_hard_negatives": "pipiiips",
     "nsid_clf_attn_fwd": "pipiippippps",
     "nsid_clf_head_fwd": "ppppips",

@@ -13,10 +13,12 @@ nsid_clf_pair_scores.
         s = clf.pair_scores(nm_query, nm_cand)        # (Sq, C, N), (Sc, C, N) -> (Sq, Sc)
 
 Supported: in_dim 512, 640, 768 or 1024 (the encoder sizes 't', 's', 'm' and the default; head dim in_dim / 4), 4 heads, hidden_dim
-128, N <= 32 (and N <= num_nodes with pos_embed), fp32 contiguous inputs whose channel count is the module's in_dim; anything else
-raises before a launch. This module's forward stays the eval-mode re-rank path and refuses training mode and grad. Training
+128, N <= 128 (and N <= num_nodes with pos_embed), fp32 contiguous inputs whose channel count is the module's in_dim; anything else
+raises before a launch. N <= 32 runs on the single-tile kernel (nsid_clf_pair_scores_c), 33 <= N <= 128 (the 256-mel configuration's
+128-node matrices; num_nodes=128, or the reference's default 100 for N <= 100) on the multi-tile one (nsid_clf_pair_scores_n); the
+dispatch is by N alone, in ops.clf_node_rows / ops.clf_pair_scores. This module's forward stays the eval-mode re-rank path and refuses training mode and grad. Training
 (downstream.py's loop) runs through neuralsampleid_amd.downstream: clf_train_scores is the training-mode forward and backward on
-csrc/clf_train.hip, and train() / train_step() drive it; the trained state_dict loads here as it is."""
+csrc/clf_train.hip, and train() / train_step() drive it (N <= 32 only); the trained state_dict loads here as it is."""
 import math
 
 import numpy as np
@@ -58,8 +60,8 @@ class CrossAttentionClassifier(nn.Module):
         if not x.is_cuda:
             raise RuntimeError(f"{name}: the classifier runs on the MI355X (cuda) device; there is no CPU path")
         N = x.shape[2]
-        if not 1 <= N <= ops.CLF_MAX_N:
-            raise ValueError(f"{name}: N = {N} nodes is outside [1, {ops.CLF_MAX_N}]")
+        if not 1 <= N <= ops.CLF_MAX_N_EVAL:
+            raise ValueError(f"{name}: N = {N} nodes is outside [1, {ops.CLF_MAX_N_EVAL}]")
         if self.pos_embed and N > self.positional_embedding.shape[1]:
             raise ValueError(f"{name}: N = {N} exceeds the positional embedding's {self.positional_embedding.shape[1]} nodes")
         return N

@@ -235,6 +235,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(mrconv_fused)         /* eval-mode max-relative aggregation + grouped conv in one launch (mrconv_fused.hip) */ \
   X(row_sqnorm) X(flat_l2_topk) X(flat_l2_topk_wide) X(seq_scores)   /* search.hip: exact flat-L2 fingerprint search (_wide: the d > 256 kernel) */ \
   X(clf_node_rows) X(clf_pair_scores)           /* rerank.hip: classifier re-rank pair scores */ \
+  X(clf_node_rows_n) X(clf_pair_scores_n)       /* rerank.hip: the same at up to 128 nodes (multi-tile attention) */ \
   X(clf_mine) X(clf_attn_fwd) X(clf_head_fwd) X(clf_head_bwd) X(clf_attn_bwd) X(clf_seg_reduce)   /* clf_train.hip: classifier training */ \
   X(logmel_fft)           /* frontend.hip: batched log-mel front end in one launch */ \
   X(conv2d_3x3) X(conv2d_1x1) X(ibn_relu) X(stem7_pool) X(gem_pool)   /* resnet.hip: the ResNet-IBN baseline's eval-mode forward */

@@ -1,4 +1,4 @@
-// Classifier re-rank pair scores (include/nsid.h nsid_clf_node_rows / nsid_clf_pair_scores).
+// Classifier re-rank pair scores (include/nsid.h nsid_clf_node_rows / nsid_clf_pair_scores, and their _n forms for up to 128 nodes).
 //
 // Reference: downstream.py:30-78 CrossAttentionClassifier in eval mode, called per candidate by eval_hr.py::eval_faiss_clf and
 // eval_map.py::eval_faiss_map_clf. For one pair (query x_i, candidate x_j, both (N, C) node rows, C = 512, H = 4 heads of dh = 128):
@@ -18,6 +18,9 @@
 // candidate row is [K | P] of C + 512 floats. K (32 x (C + 4) floats) next to P (64 KB) fits the 160 KB of a workgroup up to C = 640
 // (148 KB); at 768 and 1024 (164 / 197 KB) P alone is staged and every wave reads its K fragments from global memory, as it reads Q:
 // the candidate's K rows are shared by the 64 segments of the chunk and stay in L2. The order of every sum is the same in both forms.
+//
+// Nodes: clf_pair_kernel covers N <= 32 (one 32 x 32 tile per head). 33 <= N <= 128 (evaluation only) is clf_pair_wide_kernel below:
+// up to 4 x 4 tiles per head, P staged one head at a time; it has its own entries and leaves the N <= 32 kernels and scores alone.
 #include "nsid_common.h"
 
 namespace {
@@ -192,10 +195,193 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
   }
 }
 
-// (S, C, N) node matrices -> (S N, C) node rows (+ pos[n][c]); 32 channels per workgroup through an LDS tile
+// ---- 33 <= N <= 128 (nsid_clf_pair_scores_n): the attention of a head is up to 4 x 4 tiles of 32 x 32 --------------------------------
+// One workgroup (8 waves) per (group, candidate, chunk of 64 query segments), as above, and the same arithmetic. The candidate's P
+// (N x 512 floats, 256 KB at N = 128) no longer fits the LDS, one head's P_h (128 x 128 floats, 64 KB) does: the waves walk the four
+// heads together, P_h is staged per head, and every wave runs its segments of the chunk (at most 8) against it. K and Q fragments
+// stream from global memory (L2), as in the C >= 768 form above: one query tile's fragment is used against the up to four key tiles
+// (4 x 16 accumulator registers), so a row's max and sum are in registers; the column sums of a key tile accumulate over the query
+// tiles in their order. A pair's partial hidden vector waits in LDS between two heads (lane-private slots). Keys >= N get no weight,
+// query rows >= N no share in the column mean, which divides by N; no row >= N of a segment is addressed.
+constexpr int RW_N = 128;            // nodes per segment at most
+constexpr int RW_T = RW_N / 32;      // tiles per side
+constexpr int RW_SLOTS = RR_QCH / RR_WAVES;   // segments of a chunk per wave
+
+// column sums of a 32 (keys, registers x lane half) x 32 (queries, lanes) tile: reduce-scatter over the 32 query lanes of each half,
+// halving the registers at every step; the even lanes return the sum of key jf (clf_pair_kernel's comment) of their half
+__device__ __forceinline__ float rw_colsum(float* v, int r) {
+#pragma unroll
+  for (int c = 16, off = 16; c > 1; c >>= 1, off >>= 1) {
+    const bool up = (r & off) != 0;
+#pragma unroll
+    for (int i = 0; i < c / 2; ++i) {
+      const float keep = up ? v[i + c / 2] : v[i];
+      const float send = up ? v[i] : v[i + c / 2];
+      v[i] = keep + __shfl_xor(send, off);
+    }
+  }
+  return v[0] + __shfl_xor(v[0], 1);
+}
+
+template <int C, int DH>
+__global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kp,
+                                                            int nc_seg, int N, const int* __restrict__ grp,
+                                                            const int64_t* __restrict__ out_off, const int* __restrict__ tile_off,
+                                                            int ngroups, const int* __restrict__ cidx,
+                                                            const float* __restrict__ tail, float* __restrict__ out,
+                                                            int64_t out_len) {
+  static_assert(C == RR_H * DH && DH % 32 == 0, "4 heads of DH channels; K and Q are loaded four k-steps of 8 at a time");
+  constexpr int LDKP = C + RR_PW;      // the candidates' projected rows: [K | P]
+  __shared__ __attribute__((aligned(16))) float ps[RW_N][RR_HID];          // P_h of the candidate
+  __shared__ float hacc[RR_QCH][RR_HID];                                   // the pairs' hidden vectors between two heads
+  __shared__ float abar[RR_WAVES][RW_N];
+
+  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+
+  // the group of this workgroup: the last g with tile_off[g] <= blockIdx.x
+  int lo = 0, hi = ngroups - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tile_off[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const int g = lo;
+  const int q0 = grp[4 * g], qn = grp[4 * g + 1], coff = grp[4 * g + 2], cn = grp[4 * g + 3];
+  const int t = b - tile_off[g];
+  const int jpos = t % cn, qc = t / cn;
+  const int cand = cidx[coff + jpos];
+  if (cand < 0 || cand >= nc_seg) return;              // the host checks the lists; this only keeps a bad list in bounds (uniform)
+
+  const float* kc = kp + (size_t)cand * N * LDKP;
+  const int nT = (N + 31) >> 5;
+  const float invN = 1.0f / (float)N;
+  const int s_end = min(qn, (qc + 1) * RR_QCH);
+  const int gf = (((r >> 4) & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 1) & 1);
+  const int jf = (gf & 3) + 8 * (gf >> 2) + 4 * hh;
+
+#pragma unroll 1
+  for (int h = 0; h < RR_H; ++h) {
+    __syncthreads();                                   // every wave is done with the last head's P_h
+    for (int i = tid; i < N * (RR_HID / 4); i += 512) {
+      const int n = i / (RR_HID / 4), c = 4 * (i % (RR_HID / 4));
+      *reinterpret_cast<f32x4*>(&ps[n][c]) = ld4(kc + (size_t)n * LDKP + C + h * RR_HID + c);
+    }
+    __syncthreads();
+
+#pragma unroll 1
+    for (int slot = 0; slot < RW_SLOTS; ++slot) {
+      const int s = qc * RR_QCH + w + slot * RR_WAVES;
+      if (s >= s_end) break;
+      const int qseg = q0 + s;
+      if (qseg < 0 || qseg >= nq_seg) continue;
+      const int64_t o = out_off[g] + (int64_t)s * cn + jpos;
+      if (o < 0 || o >= out_len) continue;
+      const float* qs = q + (size_t)qseg * N * C + h * DH + 4 * hh;
+      const float* kh = kc + h * DH + 4 * hh;
+
+      float cs[RW_T] = {0.f, 0.f, 0.f, 0.f};           // column sums of the key tiles (even lanes: key 32 kt + jf)
+#pragma unroll 1
+      for (int qt = 0; qt < nT; ++qt) {
+        // S^T[key][query] of query tile qt against every key tile: A = K rows, B = Q rows; lane (r, hh) supplies dims
+        // 8 bb + 4 hh + e of its row at step (bb, e)
+        const int qrow = 32 * qt + r;
+        const bool qok = qrow < N;
+        const float* qp = qs + (size_t)(qok ? qrow : 0) * C;
+        f32x16 acc[RW_T] = {};
+#pragma unroll 1
+        for (int b0 = 0; b0 < DH / 8; b0 += 4) {
+          f32x4 qb[4], ka[RW_T][4];
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb) qb[bb] = qok ? ld4(qp + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int kt = 0; kt < RW_T; ++kt) {
+            if (kt < nT) {
+              const int krow = 32 * kt + r;
+              const float* kr = kh + (size_t)(krow < N ? krow : 0) * LDKP;
+#pragma unroll
+              for (int bb = 0; bb < 4; ++bb) ka[kt][bb] = krow < N ? ld4(kr + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+          }
+#pragma unroll
+          for (int kt = 0; kt < RW_T; ++kt) {
+            if (kt < nT) {
+#pragma unroll
+              for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                  acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kt][bb][e], qb[bb][e], acc[kt], 0, 0, 0);
+            }
+          }
+        }
+        // acc[kt][i] of lane (r, hh) = score of query node qrow against key 32 kt + (i & 3) + 8 (i >> 2) + 4 hh: the softmax of
+        // query qrow runs over the registers of all key tiles and the two lane halves
+        float mx = -__builtin_inff();
+#pragma unroll
+        for (int kt = 0; kt < RW_T; ++kt) {
+          if (kt < nT) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i)
+              if (32 * kt + (i & 3) + 8 * (i >> 2) + 4 * hh < N) mx = fmaxf(mx, acc[kt][i]);
+          }
+        }
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        float sum = 0.f;
+#pragma unroll
+        for (int kt = 0; kt < RW_T; ++kt) {
+          if (kt < nT) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              acc[kt][i] = 32 * kt + (i & 3) + 8 * (i >> 2) + 4 * hh < N ? expf(acc[kt][i] - mx) : 0.f;
+              sum += acc[kt][i];
+            }
+          }
+        }
+        sum += __shfl_xor(sum, 32);
+#pragma unroll
+        for (int kt = 0; kt < RW_T; ++kt) {
+          if (kt < nT) {
+            float v[16];
+#pragma unroll
+            for (int i = 0; i < 16; ++i) v[i] = qok ? acc[kt][i] / sum : 0.f;
+            cs[kt] += rw_colsum(v, r);
+          }
+        }
+      }
+      if ((r & 1) == 0) {
+#pragma unroll
+        for (int kt = 0; kt < RW_T; ++kt)
+          if (kt < nT) abar[w][32 * kt + jf] = cs[kt] * invN;
+      }
+      __builtin_amdgcn_wave_barrier();
+      // hidden += a_h^T P_h
+      const int pair = w * RW_SLOTS + slot;
+      float part0 = h ? hacc[pair][lane] : 0.f, part1 = h ? hacc[pair][64 + lane] : 0.f;      // hidden[lane], hidden[64 + lane] without g
+      for (int m = 0; m < N; ++m) {
+        const float a = abar[w][m];
+        part0 = fmaf(a, ps[m][lane], part0);
+        part1 = fmaf(a, ps[m][64 + lane], part1);
+      }
+      __builtin_amdgcn_wave_barrier();
+      if (h + 1 < RR_H) {
+        hacc[pair][lane] = part0;
+        hacc[pair][64 + lane] = part1;
+        continue;
+      }
+      const float h0 = fmaxf(part0 + tail[lane], 0.f), h1 = fmaxf(part1 + tail[64 + lane], 0.f);
+      float z = fmaf(tail[RR_HID + 64 + lane], h1, tail[RR_HID + lane] * h0);
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off);
+      if (lane == 0) out[o] = 1.0f / (1.0f + expf(-(z + tail[2 * RR_HID])));
+    }
+  }
+}
+
+// (S, C, N) node matrices -> (S N, C) node rows (+ pos[n][c]); 32 channels per workgroup through an LDS tile of NMAX nodes
+template <int NMAX>
 __global__ __launch_bounds__(256) void clf_node_rows_kernel(const float* __restrict__ x, int C, int N, const float* __restrict__ pos,
                                                             float* __restrict__ rows) {
-  __shared__ float tile[32][RR_N + 1];
+  __shared__ float tile[32][NMAX + 1];
   const int s = blockIdx.x, c0 = blockIdx.y * 32;
   for (int i = threadIdx.x; i < 32 * N; i += 256) {
     const int c = i / N, n = i % N;
@@ -215,7 +401,39 @@ extern "C" int nsid_clf_node_rows(const float* x, int S, int C, int N, const flo
   if (S == 0) return NSID_OK;
   NSID_REQUIRE(x && rows);
   nsid_count(NSID_C_clf_node_rows);
-  hipLaunchKernelGGL(clf_node_rows_kernel, dim3(S, C / 32), dim3(256), 0, static_cast<hipStream_t>(stream), x, C, N, pos, rows);
+  hipLaunchKernelGGL(clf_node_rows_kernel<RR_N>, dim3(S, C / 32), dim3(256), 0, static_cast<hipStream_t>(stream), x, C, N, pos, rows);
+  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+}
+
+extern "C" int nsid_clf_node_rows_n(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream) {
+  NSID_REQUIRE(C == 512 || C == 640 || C == 768 || C == 1024);
+  NSID_REQUIRE(S >= 0 && N >= 1 && N <= RW_N);
+  if (S == 0) return NSID_OK;
+  NSID_REQUIRE(x && rows);
+  nsid_count(NSID_C_clf_node_rows_n);
+  hipLaunchKernelGGL(clf_node_rows_kernel<RW_N>, dim3(S, C / 32), dim3(256), 0, static_cast<hipStream_t>(stream), x, C, N, pos, rows);
+  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+}
+
+extern "C" int nsid_clf_pair_scores_n(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
+                                      const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
+                                      const float* tail, float* out, int64_t out_len, void* stream) {
+  NSID_REQUIRE(C == 512 || C == 640 || C == 768 || C == 1024);
+  NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= RW_N && ngroups >= 0 && ntiles >= 0 && out_len >= 0);
+  if (ngroups == 0 || ntiles == 0) return NSID_OK;
+  NSID_REQUIRE(q && kp && groups && out_off && tile_off && cidx && tail && out && nsid_aligned16(q) && nsid_aligned16(kp));
+  nsid_count(NSID_C_clf_pair_scores_n);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+#define RW_LAUNCH(CC)                                                                                                            \
+  hipLaunchKernelGGL((clf_pair_wide_kernel<CC, CC / RR_H>), dim3(ntiles), dim3(512), 0, st, q, nq_seg, kp, nc_seg, N, groups,    \
+                     out_off, tile_off, ngroups, cidx, tail, out, out_len)
+  switch (C) {
+    case 512: RW_LAUNCH(512); break;
+    case 640: RW_LAUNCH(640); break;
+    case 768: RW_LAUNCH(768); break;
+    default: RW_LAUNCH(1024); break;
+  }
+#undef RW_LAUNCH
   return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
 }
 

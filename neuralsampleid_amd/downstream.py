@@ -172,6 +172,9 @@ def clf_train_scores(classifier: CrossAttentionClassifier, nodes_q, nodes_c, q_i
     if classifier.attn.dropout != 0.0:
         raise NotImplementedError("clf_train_scores: attention dropout is not supported (the reference's is 0)")
     N = classifier._check_nodes(nodes_q, "clf_train_scores nodes_q")
+    if N > ops.CLF_MAX_N:
+        raise ValueError(f"clf_train_scores: N = {N} nodes: eval-mode scoring covers N <= {ops.CLF_MAX_N_EVAL}, training covers "
+                         f"N <= {ops.CLF_MAX_N} only")
     if classifier._check_nodes(nodes_c, "clf_train_scores nodes_c") != N:
         raise ValueError(f"clf_train_scores: query and candidate node counts differ ({N} vs {nodes_c.shape[2]})")
     if nodes_q.requires_grad or nodes_c.requires_grad:

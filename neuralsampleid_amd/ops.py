@@ -1373,6 +1373,7 @@ def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:
 CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = 512, 1024, 32, 64
 CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
 CLF_PW = 512                            # the folded candidate block P: 4 heads x fc.0's 128, at every width
+CLF_MAX_N_EVAL = 128                    # eval-mode scoring (the _n entries: multi-tile attention); training stays at CLF_MAX_N
 
 
 def _clf_width(C, name) -> int:
@@ -1383,16 +1384,23 @@ def _clf_width(C, name) -> int:
 
 
 def clf_node_rows(x, pos=None) -> torch.Tensor:
-    """(S, C, N) fp32 node matrices -> (S N, C) node rows, plus pos (N, C) on every segment when given"""
+    """(S, C, N) fp32 node matrices -> (S N, C) node rows, plus pos (N, C) on every segment when given. N <= 32: nsid_clf_node_rows;
+    33 <= N <= 128 (C one of CLF_WIDTHS): nsid_clf_node_rows_n"""
     _chk(x, pos)
     if x.dim() != 3:
         raise ValueError(f"clf_node_rows: expected (S, C, N) node matrices, got {tuple(x.shape)}")
     S, C, N = x.shape
-    if C % 32 or not 1 <= N <= CLF_MAX_N:
-        raise ValueError(f"clf_node_rows: C = {C}, N = {N} outside C % 32 == 0, 1 <= N <= {CLF_MAX_N}")
+    if C % 32 or not 1 <= N <= CLF_MAX_N_EVAL:
+        raise ValueError(f"clf_node_rows: C = {C}, N = {N} outside C % 32 == 0, 1 <= N <= {CLF_MAX_N_EVAL}")
+    if N > CLF_MAX_N:
+        _clf_width(C, "clf_node_rows (N > 32)")
     if pos is not None and tuple(pos.shape) != (N, C):
         raise ValueError(f"clf_node_rows: pos must be ({N}, {C}), got {tuple(pos.shape)}")
     rows = torch.empty((S * N, C), device=x.device, dtype=torch.float32)
+    if N > CLF_MAX_N:
+        _tk("clf_node_rows_kernel<128>", 8.0 * S * C * N,
+            lambda: call("nsid_clf_node_rows_n", _p(x), S, C, N, _p(pos), _p(rows), _stream()), (S, C, N, 1))
+        return rows
     _tk("clf_node_rows_kernel", 8.0 * S * C * N, lambda: call("nsid_clf_node_rows", _p(x), S, C, N, _p(pos), _p(rows), _stream()),
         (S, C, N, 1))
     return rows
@@ -1402,15 +1410,16 @@ def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_c
     """Scores of blocked pair lists on the classifier's folded form (csrc/rerank.hip).
 
     q (nq_seg N, C): projected query rows; kp (nc_seg N, C + 512): the candidates' [K | P] rows; tail (257,): {g, w2, b2}. C is
-    q's width, one of CLF_WIDTHS.
+    q's width, one of CLF_WIDTHS. 1 <= N <= CLF_MAX_N_EVAL nodes per segment: N <= 32 runs nsid_clf_pair_scores_c (one 32 x 32 tile per
+    head), 33 .. 128 nsid_clf_pair_scores_n (up to 4 x 4 tiles); the lists and the result have the same form in both.
     Group i pairs query segments [q_start[i], q_start[i] + q_count[i]) with the candidate segments cand_idx[cand_off[i] :
     cand_off[i] + cand_count[i]] (repeats allowed). Host integer sequences, checked here. Returns (out, out_off): the flat fp32
     score tensor and, per group, the int64 offset of its row-major (q_count x cand_count) block."""
     import numpy as np
     _chk(q, kp, tail)
     N = int(N)
-    if not 1 <= N <= CLF_MAX_N:
-        raise ValueError(f"clf_pair_scores: N = {N} is outside [1, {CLF_MAX_N}]")
+    if not 1 <= N <= CLF_MAX_N_EVAL:
+        raise ValueError(f"clf_pair_scores: N = {N} is outside [1, {CLF_MAX_N_EVAL}]")
     if q.dim() != 2 or kp.dim() != 2:
         raise ValueError(f"clf_pair_scores: expected q (S N, C) and kp (S N, C + {CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
     C = _clf_width(q.shape[1], "clf_pair_scores")
@@ -1445,6 +1454,16 @@ def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_c
     to = torch.from_numpy(tile_off.astype(np.int32)).to(dev)
     cit = torch.from_numpy((ci if ci.size else np.zeros(1, np.int64)).astype(np.int32)).to(dev)
     npairs = float(sizes.sum())
+    if N > CLF_MAX_N:
+        # 33 <= N <= 128, per pair: Q K^T 2 N^2 C on the matrix pipe, the softmax (about 8 per attention weight) and the column sums
+        # 4 N^2 each, a P 2 N 512, the tail 512. Bytes: the scores; per workgroup the candidate's P once; per pair the Q rows once per
+        # head and the K rows once per query tile (both stream from L2)
+        nt = (N + 31) // 32
+        _timed("clf_pair_wide_kernel", (2.0 * N * N * C + 12.0 * 4 * N * N + 2.0 * N * CLF_PW + 512.0) * npairs,
+               4.0 * npairs + 4.0 * CLF_PW * N * float(tile_off[-1]) + 4.0 * N * C * (1 + nt) * npairs,
+               lambda: call("nsid_clf_pair_scores_n", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G,
+                            int(tile_off[-1]), _p(cit), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
+        return out, out_off[:-1]
     # per pair 2 N^2 C (Q K^T on the matrix pipe) + softmax, a P and the folded tail: 1.2 MFLOP at C = 512; bytes: the scores and
     # K / P staged per workgroup
     _timed("clf_pair_kernel", (1.2e6 + 2.0 * CLF_MAX_N * CLF_MAX_N * (C - CLF_C)) * npairs,

@@ -195,6 +195,17 @@ def checkpoint_in_dim(state) -> int:
     return int(w.shape[1])
 
 
+def checkpoint_num_nodes(state):
+    """(num_nodes, pos_embed) of a CrossAttentionClassifier state_dict: the rows of its positional_embedding buffer (1, num_nodes,
+    in_dim); a checkpoint written with pos_embed=False has no such key and gives (the constructor's default 100, False)"""
+    pe = state.get("positional_embedding") if hasattr(state, "get") else None
+    if pe is None:
+        return 100, False
+    if len(pe.shape) != 3 or pe.shape[0] != 1 or pe.shape[1] < 1:
+        raise ValueError(f"the classifier checkpoint's positional_embedding has shape {tuple(pe.shape)}, not (1, num_nodes, in_dim)")
+    return int(pe.shape[1]), True
+
+
 def _project(fn, arrays: List[np.ndarray], device) -> torch.Tensor:
     """concatenated projections of a list of (S_i, C, N) arrays, PROJ_BLOCK segments per call"""
     parts, buf, nbuf = [], [], 0
@@ -394,7 +405,8 @@ def main(argv=None) -> None:
     in_dim = checkpoint_in_dim(state)
     if in_dim not in ops.CLF_WIDTHS:
         ap.error(f"--clf-ckpt: a classifier of in_dim {in_dim}; the re-rank covers in_dim {', '.join(map(str, ops.CLF_WIDTHS))}")
-    clf = CrossAttentionClassifier(in_dim=in_dim, num_nodes=32).cuda()
+    num_nodes, pos_embed = checkpoint_num_nodes(state)
+    clf = CrossAttentionClassifier(in_dim=in_dim, num_nodes=num_nodes, pos_embed=pos_embed).cuda()
     clf.load_state_dict(state)
     clf.eval()
     hr = eval_hit_rates_clf(a.emb_dir, clf, a.gt, a.dummy_dir, a.test_seq_len, a.k_probe or 5, save=not a.no_save)

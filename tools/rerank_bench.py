@@ -1,10 +1,11 @@
 """Times the classifier re-rank (csrc/rerank.hip) at the evaluations' block shapes, the projection GEMMs, a torch-eager fp32
 comparison and the whole eval_map_clf on a synthetic sample100-sized emb_dir.
 
-    python tools/rerank_bench.py [--reps 5] [--quick] [--in-dim 512|640|768|1024]
+    python tools/rerank_bench.py [--reps 5] [--quick] [--in-dim 512|640|768|1024] [--nodes N]
 
 Pair kernel: ms (median of --reps after a warm-up), pairs/s and TFLOP/s on 1.2 MFLOP per pair at in_dim 512 (2 N^2 C more per
-channel of a wider classifier), with its fraction of the fp32 matrix peak (155 TF, MI355X_MICROARCH). The eager comparison scores the same pairs with a batched fp32 nn.MultiheadAttention written here
+channel of a wider classifier) for --nodes <= 32 (the default 32), and on ops.clf_pair_scores' model in N above that (the multi-tile
+kernel, up to 128 nodes: 2 N^2 C + 48 N^2 + 1024 N + 512, 17.7 MFLOP at N = 128, C = 512), with its fraction of the fp32 matrix peak (155 TF, MI355X_MICROARCH). The eager comparison scores the same pairs with a batched fp32 nn.MultiheadAttention written here
 (the reference's forward: one classifier call per candidate, batched over query segments, as eval_map.py does)."""
 import argparse
 import os
@@ -24,8 +25,10 @@ from neuralsampleid_amd.rerank import eval_map_clf  # noqa: E402
 PEAK_TF = 155.0
 
 
-def flop_per_pair(C):
-    return 1.2e6 + 2.0 * 32 * 32 * (C - 512)
+def flop_per_pair(C, N=32):
+    if N <= 32:
+        return 1.2e6 + 2.0 * 32 * 32 * (C - 512)
+    return 2.0 * N * N * C + 12.0 * 4 * N * N + 2.0 * N * 512 + 512.0
 
 
 def _median_ms(fn, reps):
@@ -42,9 +45,9 @@ def _median_ms(fn, reps):
     return float(np.median(ms))
 
 
-def _clf(C):
+def _clf(C, N=32):
     torch.manual_seed(0)
-    clf = CrossAttentionClassifier(in_dim=C, num_nodes=32).cuda().eval()
+    clf = CrossAttentionClassifier(in_dim=C, num_nodes=N).cuda().eval()
     return clf
 
 
@@ -62,22 +65,22 @@ class EagerClf(nn.Module):
         return self.fc(a.mean(dim=1))
 
 
-def time_block(C, name, sq, sc, groups, reps, eager_groups=1):
-    clf = _clf(C)
+def time_block(C, name, sq, sc, groups, reps, eager_groups=1, N=32):
+    clf = _clf(C, N)
     g = torch.Generator(device="cuda").manual_seed(1)
-    q = torch.randn(groups * sq, C, 32, device="cuda", generator=g)
-    c = torch.randn(sc * 4, C, 32, device="cuda", generator=g)
+    q = torch.randn(groups * sq, C, N, device="cuda", generator=g)
+    c = torch.randn(sc * 4, C, N, device="cuda", generator=g)
     with torch.no_grad():
         qp, kp = clf.project_queries(q), clf.project_candidates(c)
         rng = np.random.default_rng(0)
         lists = [rng.integers(0, c.shape[0], size=sc) for _ in range(groups)]
-        args = (qp, kp, 32, np.arange(groups) * sq, [sq] * groups, np.concatenate(lists), np.arange(groups) * sc, [sc] * groups)
+        args = (qp, kp, N, np.arange(groups) * sq, [sq] * groups, np.concatenate(lists), np.arange(groups) * sc, [sc] * groups)
         t = _median_ms(lambda: clf.score_blocks(*args), reps)
         tq = _median_ms(lambda: clf.project_queries(q), reps)
         tc = _median_ms(lambda: clf.project_candidates(c), reps)
         pairs = groups * sq * sc
-        tf = flop_per_pair(C) * pairs / t / 1e9
-        print(f"{name}: {groups} x ({sq} x {sc}) pairs: kernel {t:9.3f} ms  {pairs / t / 1e3:8.2f} Mpairs/s  {tf:6.1f} TF/s "
+        tf = flop_per_pair(C, N) * pairs / t / 1e9
+        print(f"{name}: N {N}: {groups} x ({sq} x {sc}) pairs: kernel {t:9.3f} ms  {pairs / t / 1e3:8.2f} Mpairs/s  {tf:6.1f} TF/s "
               f"({tf / PEAK_TF:5.3f} of 155)", flush=True)
         print(f"{name}: projections: queries {groups * sq} segs {tq:7.3f} ms, candidates {c.shape[0]} segs {tc:7.3f} ms", flush=True)
         # eager comparison: one batched classifier call per candidate (eval_map.py:146-153), over eager_groups groups, scaled
@@ -93,15 +96,15 @@ def time_block(C, name, sq, sc, groups, reps, eager_groups=1):
               f"group(s)) -> kernel speed-up {te / t:7.1f}x", flush=True)
 
 
-def time_eval_map(C, n_songs, segs, n_tests, q_segs, n_dummy, k_probe=3):
+def time_eval_map(C, n_songs, segs, n_tests, q_segs, n_dummy, k_probe=3, N=32):
     rng = np.random.default_rng(0)
-    d, N = 128, 32
+    d = 128
 
     def unit(n):
         x = rng.standard_normal((n, d)).astype(np.float32)
         return x / np.linalg.norm(x, axis=1, keepdims=True)
 
-    clf = _clf(C)
+    clf = _clf(C, N)
     with tempfile.TemporaryDirectory() as tmp:
         ref = unit(n_songs * segs)
         names = [f"s{i}" for i in range(n_songs)]
@@ -130,15 +133,20 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--quick", action="store_true", help="8 MAP-like groups instead of 64, a small evaluation")
     ap.add_argument("--in-dim", type=int, default=512, choices=(512, 640, 768, 1024), help="the classifier's width")
+    ap.add_argument("--nodes", type=int, default=32, help="nodes per segment, 1 .. 128 (above 32: the multi-tile kernel)")
     a = ap.parse_args()
     C = a.in_dim           # the classifier's width: the encoder sizes 't', 's', 'm' and the default end in 512 .. 1024
-    print(f"in_dim {C}", flush=True)
-    time_block(C, "map block", 350, 1024, 8 if a.quick else 64, a.reps)
-    time_block(C, "hit-rate block", 19, 95, 64, a.reps, eager_groups=8)
+    N = a.nodes
+    if not 1 <= N <= 128:
+        ap.error("--nodes must lie in [1, 128]")
+    print(f"in_dim {C}, nodes {N}", flush=True)
+    time_block(C, "map block", 350, 1024, 8 if a.quick else 64, a.reps, N=N)
+    time_block(C, "hit-rate block", 19, 95, 64, a.reps, eager_groups=8, N=N)
+    # node-matrix files grow with N: above 32 nodes the synthetic emb_dir has fewer, shorter songs
     if a.quick:
-        time_eval_map(C, 20, 350, 10, 350, 20_000)
+        time_eval_map(C, *((20, 350, 10, 350) if N <= 32 else (10, 100, 10, 100)), 20_000, N=N)
     else:
-        time_eval_map(C, 75, 350, 100, 350, 100_000)
+        time_eval_map(C, *((75, 350, 100, 350) if N <= 32 else (75, 100, 100, 100)), 100_000, N=N)
 
 
 if __name__ == "__main__":
