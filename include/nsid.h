@@ -345,6 +345,23 @@ int nsid_logmel_fft(const float* wave, long in_stride, int B, long L, int n_fft,
                     const float* twiddle, const float* fb, const int* band, int n_mels, float* out, long out_clip_stride,
                     long out_mel_stride, void* stream);
 
+/* ---- constant-Q front end of the ResNet-IBN baseline (modules/transformations.py:36,48: nnAudio CQT(sr, hop_length), i.e.
+ * CQT1992v2 with fmin 32.70, 84 bins, 12 per octave, norm 1, Hann, center=True / reflect, magnitude, 'librosa' normalisation)
+ * for a BATCH of clips in ONE launch (csrc/cqt.hip): wave (B, L) with clip stride in_stride ->
+ * out[b*out_clip_stride + k*out_bin_stride + t] = sqrt(l_k) |sum_n x_b[reflect(t*hop + n - width/2)] taps_k[n]|, k < n_bins,
+ * t < T = 1 + L/hop. Exact fp32 products and sums on the matrix cores, banded: `groups` is a HOST array of n_groups x 5 ints
+ * {first bin, bins (1..8), first tap, extent, offset of the group's rows in `taps` (floats, a multiple of 4)}; the groups cover
+ * the bins once and in order, and a group's reduction runs over [first tap, first tap + extent) only. `taps` (device, taps_len
+ * floats, 16-byte aligned) holds per group Q = ceil(extent/hop) x hopP rows (hopP = hop rounded up to 256; row q*hopP + r is tap
+ * first tap + q*hop + r, rows with r >= hop are zero) of 16 columns (re, im of bin 0 of the group, re, im of bin 1, ...; unused
+ * ones zero), stored as [row/4][column][row%4]. scale: n_bins floats, sqrt(l_k). No workspace, no atomics (clip b of a batch is
+ * bit-equal to the clip alone), stream-ordered. NSID_EINVAL before any launch: null pointers, B < 1, hop < 1, L <= width/2
+ * (torch's reflect pad raises there), in_stride < L, groups that do not cover n_bins or leave the table, a misaligned table, and a
+ * hop so small that a group's longest bin spans more than 24 hops (the staged rows would not fit 64 KB of LDS). */
+int nsid_cqt(const float* wave, long in_stride, int B, long L, int hop, int width, int n_bins, const int* groups, int n_groups,
+             const float* taps, long taps_len, const float* scale, float* out, long out_clip_stride, long out_bin_stride,
+             void* stream);
+
 /* bf16 shadow of fp32 weights: dst[i] = bf16_rne(src[i]), n % 8 == 0, both 16-byte aligned (operand `w` of
  * nsid_linear_fwd / nsid_linear_bwd_data with w_dtype = NSID_BF16). */
 int nsid_f32_to_bf16(const float* src, void* dst, long n, void* stream);

@@ -63,6 +63,7 @@ SIGNATURES = {
     "nsid_power_mel_db": "plippiips",
     "nsid_unfold_segments": "piiiiips",
     "nsid_logmel_fft": "pliliippppiplls",
+    "nsid_cqt": "pliliiipiplpplls",
     "nsid_bcn_to_rows": "piiipiis",
     "nsid_rows_to_bcn": "piiiipis",
     "nsid_batched_index_select_fwd": "ppiiiiips",

@@ -238,6 +238,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(clf_node_rows_n) X(clf_pair_scores_n)       /* rerank.hip: the same at up to 128 nodes (multi-tile attention) */ \
   X(clf_mine) X(clf_attn_fwd) X(clf_head_fwd) X(clf_head_bwd) X(clf_attn_bwd) X(clf_seg_reduce)   /* clf_train.hip: classifier training */ \
   X(logmel_fft)           /* frontend.hip: batched log-mel front end in one launch */ \
+  X(cqt)                  /* cqt.hip: batched constant-Q front end in one launch */ \
   X(conv2d_3x3) X(conv2d_1x1) X(ibn_relu) X(stem7_pool) X(gem_pool)   /* resnet.hip: the ResNet-IBN baseline's eval-mode forward */
 
 enum NsidCounterKey {

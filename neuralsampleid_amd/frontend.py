@@ -13,9 +13,14 @@ power/mel/dB kernel and the segment gather (csrc/misc.hip). Everything is stream
 stft="fft" takes the fused kernel instead (csrc/frontend.hip, nsid_logmel_fft): reflection by index arithmetic, a real FFT in
 LDS and registers, power, mel sums and dB in one launch for a whole batch of clips — `batch(waves)`, the `augment` of the
 reference's train.py:58 (GPUTransformSampleID(train=True)); `logmel()` and `__call__` go through it with B = 1. The default
-stays "gemm": the two modes differ by fp32 rounding, which stored fingerprints would see."""
+stays "gemm": the two modes differ by fp32 rounding, which stored fingerprints would see.
+
+CQTFrontEnd is the same surface for the ResNet-IBN baseline (GPUTransformSampleID(arch='resnet-ibn'), transformations.py:36,48:
+nnAudio CQT(sr=fs, hop_length=hop_len)): waveform -> constant-Q magnitudes (84, T) -> (S, 84, n_frames) segments, one launch of
+the banded kernel (csrc/cqt.hip, nsid_cqt) for a whole batch of clips."""
 import math
 
+import numpy as np
 import torch
 
 from . import ops
@@ -122,5 +127,91 @@ class LogMelFrontEnd:
         out = torch.empty((S, self.n_mels, self.n_frames), device=wave.device, dtype=torch.float32)
         if S > 0:
             call("nsid_unfold_segments", ops._p(lm), self.n_mels, T, self.n_frames, self.step, S, ops._p(out),
+                 ops._stream())
+        return out
+
+
+CQT_FMIN, CQT_BINS, CQT_BPO = 32.70, 84, 12          # nnAudio CQT defaults (filter_scale 1, norm 1, Hann)
+CQT_GROUP = 8                                        # bins per group of the banded kernel: 16 re/im columns of one MFMA tile
+CQT_RC = 256                                         # csrc/cqt.hip CQ_RC: the table pads the hop to a multiple of it
+
+
+def cqt_kernels(fs: float):
+    """nnAudio create_cqt_kernels(Q, fs, fmin 32.70, n_bins 84, bins_per_octave 12, norm 1, window 'hann') restated in fp64:
+    -> (freqs (84,), lengths (84,) int, starts (84,) int, width, taps: list of 84 complex128 arrays of l_k entries). Bin k's taps
+    occupy [starts[k], starts[k] + lengths[k]) of a zero row of `width` entries."""
+    Q = 1.0 / (2.0 ** (1.0 / CQT_BPO) - 1.0)
+    freqs = CQT_FMIN * 2.0 ** (np.arange(CQT_BINS, dtype=np.float64) / float(CQT_BPO))
+    if freqs.max() > fs / 2:
+        raise ValueError(f"The top bin {freqs.max():.2f}Hz has exceeded the Nyquist frequency {fs / 2}Hz")
+    lengths = np.ceil(Q * fs / freqs).astype(np.int64)
+    width = int(2 ** math.ceil(math.log2(int(lengths.max()))))
+    starts, taps = np.zeros(CQT_BINS, dtype=np.int64), []
+    for k in range(CQT_BINS):
+        l = int(lengths[k])
+        starts[k] = int(math.ceil(width / 2.0 - l / 2.0)) - l % 2
+        m = np.arange(-(l // 2) - l % 2, l // 2, dtype=np.float64)            # np.r_[-l//2 : l//2] on the float l
+        n = np.arange(l, dtype=np.float64)
+        w = 0.5 - 0.5 * np.cos(2.0 * np.pi * n / l)                            # periodic Hann
+        ph = m * 2.0 * np.pi * freqs[k] / fs
+        sig = w * (np.cos(ph) + 1j * np.sin(ph)) / l
+        taps.append(sig / np.abs(sig).sum())
+    return freqs, lengths, starts, width, taps
+
+
+class CQTFrontEnd:
+    """front = CQTFrontEnd(cfg, device); segs = front(wave)  — wave (L,) fp32 on the GPU, segs (S, 84, n_frames) magnitudes."""
+
+    def __init__(self, cfg: dict, device="cuda"):
+        self.fs, self.hop = int(cfg["fs"]), int(cfg["hop_len"])
+        self.n_frames = int(cfg["n_frames"])
+        self.step = int(self.n_frames * (1 - float(cfg["overlap"])))          # transformations.py:102
+        if self.hop < 1:
+            raise ValueError("hop_len must be positive")
+        self.n_bins = CQT_BINS
+        self.device = torch.device(device)
+        self.freqs, self.lengths, self.starts, self.width, taps = cqt_kernels(self.fs)
+        taps32 = [t.astype(np.complex64) for t in taps]                       # nnAudio stores complex64: one rounding from fp64
+        hopP = (self.hop + CQT_RC - 1) // CQT_RC * CQT_RC
+        groups, blocks, off = [], [], 0
+        for b0 in range(0, self.n_bins, CQT_GROUP):
+            nb = min(CQT_GROUP, self.n_bins - b0)
+            tap0 = int(min(self.starts[b0:b0 + nb]))
+            extent = int(max(self.starts[b0:b0 + nb] + self.lengths[b0:b0 + nb])) - tap0
+            Q = (extent - 1) // self.hop + 1
+            P = np.zeros((Q * hopP, 2 * CQT_GROUP), dtype=np.float32)         # row q*hopP + r = tap tap0 + q*hop + r
+            for j in range(nb):
+                n = np.arange(int(self.lengths[b0 + j])) + int(self.starts[b0 + j]) - tap0
+                row = n // self.hop * hopP + n % self.hop
+                P[row, 2 * j], P[row, 2 * j + 1] = taps32[b0 + j].real, taps32[b0 + j].imag
+            blocks.append(P.reshape(-1, 4, 2 * CQT_GROUP).transpose(0, 2, 1).reshape(-1))    # [row/4][column][row%4]
+            groups.append((b0, nb, tap0, extent, off))
+            off += P.size
+        self.groups = np.ascontiguousarray(np.array(groups, dtype=np.int32))  # host: the entry point reads it before the launch
+        self.taps = torch.from_numpy(np.concatenate(blocks)).to(self.device)
+        self.scale = torch.sqrt(torch.from_numpy(self.lengths.astype(np.float32))).to(self.device)     # fp32 sqrt of float32(l_k)
+
+    def n_frames_of(self, L: int) -> int:
+        return 1 + L // self.hop                                             # conv1d with stride hop over L + width samples
+
+    def batch(self, waves: torch.Tensor) -> torch.Tensor:
+        """(B, L) fp32 on the GPU -> (B, 84, T) magnitudes in one launch; stream-ordered, no allocation besides the result,
+        capture-safe. Clip b of the result is bit-equal to the same clip in a call of its own."""
+        return ops.cqt(waves, self.hop, self.width, self.groups, self.taps, self.scale)
+
+    def cqt(self, wave: torch.Tensor) -> torch.Tensor:
+        """(L,) fp32 on the GPU -> (84, T) magnitudes"""
+        if wave.dim() != 1 or not wave.is_cuda or wave.dtype != torch.float32:
+            raise RuntimeError("the front end takes one mono fp32 waveform on the MI355X device")
+        return self.batch(wave.contiguous().unsqueeze(0))[0]
+
+    def __call__(self, wave: torch.Tensor) -> torch.Tensor:
+        """(L,) -> (S, 84, n_frames); S = 0 rows when the audio is shorter than one segment"""
+        spec = self.cqt(wave)
+        T = spec.shape[1]
+        S = (T - self.n_frames) // self.step + 1 if T >= self.n_frames else 0
+        out = torch.empty((S, self.n_bins, self.n_frames), device=wave.device, dtype=torch.float32)
+        if S > 0:
+            call("nsid_unfold_segments", ops._p(spec), self.n_bins, T, self.n_frames, self.step, S, ops._p(out),
                  ops._stream())
         return out

@@ -4,6 +4,7 @@ Every function enqueues HIP kernels from libnsid_hip.so on torch's current strea
 import os
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from ._lib import call, get_tuning, launch_counters, lib, reset_tuning, set_tuning  # noqa: F401  (tuning, counters: re-exported)
@@ -1217,6 +1218,26 @@ def logmel_fft(waves: torch.Tensor, n_fft: int, hop: int, window: torch.Tensor, 
     out = torch.empty((B, n_mels, T), device=waves.device, dtype=torch.float32)
     call("nsid_logmel_fft", _p(waves), waves.stride(0) if B > 1 else L, B, L, n_fft, hop, _p(window), _p(twiddle), _p(fb),
          _p(band), n_mels, _p(out), n_mels * T, T, _stream())
+    return out
+
+
+def cqt(waves: torch.Tensor, hop: int, width: int, groups, taps: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """waves (B, L) fp32 (last dimension contiguous, any clip stride) -> constant-Q magnitudes (B, n_bins, 1 + L // hop) in ONE
+    launch (nsid_cqt, csrc/cqt.hip): reflect framing, banded exact-fp32 MFMA correlation, sqrt(l_k) and the magnitude without a
+    temporary in HBM. groups: host int32 array (n_groups, 5) = {first bin, bins, first tap, extent, table offset}; taps: the packed
+    table; scale (n_bins,) = sqrt(l_k) — frontend.CQTFrontEnd builds all three."""
+    _chk(taps, scale)
+    if waves.dim() != 2 or not waves.is_cuda or waves.dtype != torch.float32 or waves.stride(1) != 1:
+        raise RuntimeError("cqt takes (B, L) float32 waveforms on the MI355X device with a contiguous last dimension")
+    B, L = waves.shape
+    if L <= width // 2:
+        raise RuntimeError(f"waveforms of {L} samples are too short for reflect padding by width/2 = {width // 2}")
+    if groups.dtype != np.int32 or groups.ndim != 2 or groups.shape[1] != 5 or not groups.flags["C_CONTIGUOUS"]:
+        raise RuntimeError("groups must be a C-contiguous int32 host array of shape (n_groups, 5)")
+    n_bins, T = scale.numel(), 1 + L // hop
+    out = torch.empty((B, n_bins, T), device=waves.device, dtype=torch.float32)
+    call("nsid_cqt", _p(waves), waves.stride(0) if B > 1 else L, B, L, hop, width, n_bins, groups.ctypes.data, groups.shape[0],
+         _p(taps), taps.numel(), _p(scale), _p(out), n_bins * T, T, _stream())
     return out
 
 
