@@ -440,9 +440,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     }
   }
   auto issue = [&](auto& sa, auto& sb, auto& sa2, int st) {
-    int r0 = rbeg + st * BK;
-    if constexpr (FULL) {
-      r0 = min(r0, rend - BK);      // the two prefetches past the last stage re-read it (never computed on)
+    const int r0 = rbeg + st * BK;
+    if constexpr (FULL) {           // st < nstage always: the full-tile loops request no stage past the last one
       const char* pa = A + (A_RMAJOR ? (long)i0 * p.lda + r0 : (long)r0 * p.lda + i0) * GA::SSZ;
       const char* pb = B + (B_RMAJOR ? (long)j0 * p.ldb + r0 : (long)r0 * p.ldb + j0) * GB::SSZ;
 #pragma unroll
@@ -467,8 +466,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
   };
   auto aff_fetch = [&](int st) {
     if constexpr (AAFF) affine_prefetch<BM, H, SA, KS>(acs, ach, rbeg + st * BK, rend, a_sc, a_sh);
-    if constexpr (ABN) {       // the 8 channels of this thread's chunks in stage st (past the end: the last stage again, unused)
-      const int r0 = min(rbeg + st * BK, rend - BK) + (int)(threadIdx.x % GA::CPR) * 8;
+    if constexpr (ABN) {       // the 8 channels of this thread's chunks in stage st
+      const int r0 = rbeg + st * BK + (int)(threadIdx.x % GA::CPR) * 8;
       const float* c = p.abn_coef + g * p.a_goff + r0;
 #pragma unroll
       for (int v = 0; v < 4; ++v) {
@@ -480,8 +479,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
   auto commit = [&](const auto& sa, const auto& sb, const auto& sa2, int st) {
     char* dst = lds_raw + (st & 1) * STAGE;
     if constexpr (ABN) {
-      // column tile 0 of every row panel also stores dr (each stage exactly once: phantom stages past the end write LDS only)
-      char* side = (tj == 0 && st < nstage && p.abn_dr != nullptr)
+      // column tile 0 of every row panel also stores dr (each stage is committed exactly once)
+      char* side = (tj == 0 && p.abn_dr != nullptr)
                        ? reinterpret_cast<char*>(p.abn_dr) + ((long)i0 * p.abn_lddr + g * p.a_goff + rbeg + st * BK) * 2 : nullptr;
       stage_store_abn<BM, KS>(dst, sa, sa2, abn_cf, p.abn_slope, side, p.abn_lddr);
     } else
@@ -521,6 +520,34 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     }
   };
 
+  // Geometry of the store epilogue (below), needed here because the full-tile pipelined loop requests the epilogue's cold operand
+  // from its tail. CAN_BNRED: fused BatchNorm-backward column sums (backward-data, bf16 output).
+  constexpr bool CAN_BNRED = A_RMAJOR && !B_RMAJOR && SC;
+  constexpr int OE = SC ? 8 : 4;               // output elements per lane per store (16 bytes either way)
+  constexpr int OSZ = SC ? 2 : 4;
+  constexpr int Q_PER_ROW = WN / OE, ROWS_PER_PASS = 64 / Q_PER_ROW;
+  constexpr int PPH = RB / ROWS_PER_PASS, NPASS = (WM / RB) * PPH;
+  static_assert(RB % ROWS_PER_PASS == 0 && WM % RB == 0, "a transpose batch is whole store passes");
+  const int orow = lane / Q_PER_ROW, oq = (lane % Q_PER_ROW) * OE;
+  const int jq = j0 + wn0 + oq;
+  const bool jqok = FULL || jq < p.J;          // J % OE == 0: a chunk is all-in or all-out
+  const bool bnred = CAN_BNRED && p.bn_r != nullptr;        // wave-uniform
+  const unsigned lo_r = (unsigned)((orow * (int)p.bn_ldr + oq) * 2);
+  // The BatchNorm input r of every store pass, all at once (see the epilogue). EARLY_R: the full-tile pipelined loop issues these
+  // loads in its tail, where the round-1 loop re-read the last stage twice: r is cold (nobody touched it since the forward pass), and
+  // vmcnt is positional, so behind two dead stage loads it started only after the last MFMA block.
+  constexpr bool EARLY_R = CAN_BNRED && FULL && DEPTH == 2;
+  f32x4 pre_r[CAN_BNRED ? NPASS : 1];
+  auto fetch_r = [&]() {
+#pragma unroll
+    for (int q = 0; q < NPASS; ++q) {
+      const int ib = i0 + wm0 + RB * (q / PPH) + (q % PPH) * ROWS_PER_PASS;
+      const bool ok = (FULL || ib + orow < p.I) && jqok;
+      pre_r[q] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(p.bn_r) +
+                                                 (ok ? ((long)ib * p.bn_ldr + g * p.c_goff + (j0 + wn0)) * 2 + lo_r : 0));
+    }
+  };
+
   if (DEPTH == 1) {
     if (nstage > 0) {
       aff_fetch(0);
@@ -554,7 +581,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
 #pragma unroll
     for (int d = 1; d < DEPTH; ++d) issue(ra[d], rb[d], ra2[ABN ? (d) : 0], d);
     __syncthreads();
-    for (int st = 0; st < nstage; st += DEPTH) {
+    // FULL: the host guarantees an even number (>= 2) of whole stages, so the last DEPTH sub-steps are peeled at compile time: the
+    // steady loop stops DEPTH stages early and the tail requests no operands, commits nothing past stage nstage - 1 and still has no
+    // control flow between a load and its wait. The predicated forms (ragged shapes) keep their zero-filled phantom stages.
+    const int nsteady = FULL ? nstage - DEPTH : nstage;
+    int st = 0;
+    for (; st < nsteady; st += DEPTH) {
 #pragma unroll
       for (int u = 0; u < DEPTH; ++u) {
         aff_fetch(st + u + 1);
@@ -565,6 +597,28 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         commit(ra[(u + 1) % DEPTH], rb[(u + 1) % DEPTH], ra2[ABN ? ((u + 1) % DEPTH) : 0], st + u + 1);
         __syncthreads();
       }
+    }
+    if constexpr (FULL && DEPTH == 2) {
+      // tail: LDS[st&1] holds stage st = nstage - 2, register set 1 holds the last stage (in flight), set 0 is free
+      aff_fetch(st + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      compute(st);
+      __builtin_amdgcn_sched_barrier(0);
+      commit(ra[1], rb[1], ra2[ABN ? 1 : 0], st + 1);
+      // nothing is in flight any more and both register sets are free: the epilogue's cold operand travels under the last MFMA block
+      // (a uniform branch here sits between no load and its wait). The explicit vmcnt(0) costs nothing -- the commit above has waited
+      // for every load -- but it is what tells the compiler's wait-count bookkeeping so on both sides of the branch: without it the join
+      // behind the branch carried a stale entry for the last stage register and put an s_waitcnt vmcnt(0) in front of the last MFMA
+      // block, i.e. waited for r there (seen in the ISA of the 128x128 and the deep instantiation alike).
+      if constexpr (EARLY_R) {
+        wait_vm<0>();
+        if (bnred) fetch_r();
+      }
+      __syncthreads();
+      __builtin_amdgcn_sched_barrier(0);
+      compute(st + 1);
+      __builtin_amdgcn_sched_barrier(0);
+      __syncthreads();              // the epilogue (and the next item of a grouped launch) reuses the stage buffers
     }
   }
 
@@ -604,12 +658,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     // accumulator layout are store-issue bound). Each wave transposes its own 64 x WN sub-tile, 32 rows at a time.
     constexpr int OLD = WN + 4;                  // staggers rq groups over the banks, keeps rows 16-B aligned
     float* ost = lds + wave * (RB * OLD);        // one RB x (WN+4) float buffer per wave
-    constexpr int OE = SC ? 8 : 4;               // output elements per lane per store (16 bytes either way)
-    constexpr int OSZ = SC ? 2 : 4;
-    constexpr int Q_PER_ROW = WN / OE, ROWS_PER_PASS = 64 / Q_PER_ROW;
-    const int orow = lane / Q_PER_ROW, oq = (lane % Q_PER_ROW) * OE;
-    const int jq = j0 + wn0 + oq;
-    const bool jqok = FULL || jq < p.J;          // J % OE == 0: a chunk is all-in or all-out
     char* Cb = reinterpret_cast<char*>(p.C) + g * p.c_goff * OSZ;
     const char* Ab = reinterpret_cast<const char*>(p.addend) + g * p.c_goff * OSZ;
     if (p.stat != nullptr) {
@@ -638,8 +686,6 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
       }
     }
     // fused BatchNorm-backward column sums (backward-data, bf16 output): g = dy * act'(scale*r+shift), xhat = (r-mean)*invstd
-    constexpr bool CAN_BNRED = A_RMAJOR && !B_RMAJOR && SC;
-    const bool bnred = CAN_BNRED && p.bn_r != nullptr;        // wave-uniform
     const bool bn_unit = p.bn_slope == 1.f;                   // no activation between the BatchNorm and this gradient
     float bsc[OE], bsh[OE], bmu[OE], bis[OE];
     f32x2 s0[OE / 2], s1[OE / 2];
@@ -659,14 +705,12 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
     // lane offsets inside a pass are fixed; a pass starts at a uniform row
     const unsigned lo_c = (unsigned)((orow * (int)p.ldc + oq) * OSZ);
     const unsigned lo_a = (unsigned)((orow * (int)p.ldadd + oq) * OSZ);
-    const unsigned lo_r = (unsigned)((orow * (int)p.bn_ldr + oq) * 2);
-    // Backward-data only: the residual-gradient addend and the BatchNorm input of every store pass are fetched NOW, all at
-    // once. Loaded inside the pass they were two dependent HBM round trips per pass: 8 passes, one workgroup per CU and cold
+    // Backward-data only: the residual-gradient addend and the BatchNorm input of every store pass are fetched all at once: the
+    // addend (written by the previous kernel: warm) NOW, the BatchNorm input here too unless the loop's tail has already asked for it
+    // (EARLY_R). Loaded inside the pass they were two dependent HBM round trips per pass: 8 passes, one workgroup per CU and cold
     // caches made that epilogue 12.6 us behind a 19 us main loop (tools/gemm_trace.py --addend --bn 1 --cold).
     constexpr bool CAN_ADD = A_RMAJOR;      // backward-data (residual gradient) and forward (residual stream, nsid_linear_fwd_res)
-    constexpr int PPH = RB / ROWS_PER_PASS, NPASS = (WM / RB) * PPH;
-    static_assert(RB % ROWS_PER_PASS == 0 && WM % RB == 0, "a transpose batch is whole store passes");
-    f32x4 pre_a[CAN_ADD ? NPASS : 1], pre_r[CAN_BNRED ? NPASS : 1];
+    f32x4 pre_a[CAN_ADD ? NPASS : 1];
     if constexpr (CAN_ADD) {
       if (p.addend) {
 #pragma unroll
@@ -677,16 +721,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
         }
       }
     }
-    if constexpr (CAN_BNRED) {
-      if (bnred) {
-#pragma unroll
-        for (int q = 0; q < NPASS; ++q) {
-          const int ib = i0 + wm0 + RB * (q / PPH) + (q % PPH) * ROWS_PER_PASS;
-          const bool ok = (FULL || ib + orow < p.I) && jqok;
-          pre_r[q] = *reinterpret_cast<const f32x4*>(reinterpret_cast<const char*>(p.bn_r) +
-                                                     (ok ? ((long)ib * p.bn_ldr + g * p.c_goff + (j0 + wn0)) * 2 + lo_r : 0));
-        }
-      }
+    if constexpr (CAN_BNRED && !EARLY_R) {
+      if (bnred) fetch_r();
     }
 #pragma unroll
     for (int h = 0; h < WM / RB; ++h) {
@@ -816,7 +852,9 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, cons
 
 template <int BM, int BN, bool A_RMAJOR, bool B_RMAJOR, bool H, bool ST, bool AAFF, bool WB = false, bool FULL = false,
           bool ARELU = false, int KS = 1, int PADX = 0, bool ABN = false>
-__global__ __launch_bounds__(NT, KS > 1 ? 1 : ((FULL && WB && BM == 128 && BN == 128 && !AAFF && !ABN) ? 3 : 2))   // waves per SIMD
+// waves per SIMD the register allocation must leave room for. The deep forms ask for 2: two workgroups share a CU (2 x <= 80 KB of
+// LDS), and a form that needs more than 256 registers would own its CU and shut the other view's kernels out.
+__global__ __launch_bounds__(NT, KS > 1 ? 2 : ((FULL && WB && BM == 128 && !AAFF && (BN == 128) != ABN) ? 3 : 2))
 void gemm_kernel(const GemmArgs p) {
   int bid = p.split_major ? blockIdx.y : blockIdx.x;
   const int split = p.split_major ? blockIdx.x : blockIdx.y;
@@ -916,7 +954,11 @@ int launch(GemmArgs p, int groups, hipStream_t s, int act_dtype, bool w_bf16 = f
   // Measured on MI355X with cold operands (tools/gemm_bench.py --cold, round 2), 256-512 workgroups per launch:
   //   forward        : 26.4 -> 20.4 us (16384x256x1024), 44.5 -> 32.1 us (8192x512x2048), 15.7 -> 13.1 us (16384x256x512);
   //   weight gradient: 16.4 -> 12.9 us (16384x256x256), 20.8 -> 18.7 us;
-  //   backward-data  : no deep form wins (the epilogue with addend / BatchNorm sums dominates): round-1 loop kept.
+  //   backward-data  : 32-deep loop kept (gemm_deep_kinds bit 1 off). Re-measured with the peeled tail and with the deep form at two
+  //     workgroups per CU (238 registers; it had needed 265 and owned its CU): alone and cold it wins only where a launch is one
+  //     workgroup per CU -- 256 tiles: 20.7 -> 20.4 us (16384x1024x256), 33.2 -> 32.5 us (8192x2048x512), with addend + BatchNorm sums
+  //     28.0 -> 24.1 and 42.7 -> 37.7 us; 1024 tiles: 21.8 -> 24.1 us (16384x256x1024), 30.4 -> 32.9 us (8192x512x2048) -- and in the
+  //     two-stream step it loses: 6.99 / 7.00 / 7.00 ms with kinds = 5 against 7.03 / 7.62 / 7.03 ms with kinds = 7 (docs/experiments.md).
   // In the TWO-STREAM training step the isolated gains mostly vanish: what the step rewards is little resource-time per tile,
   // not latency. One-box A/B of the whole step (two repetitions each): round-1 loops 8.52 / 8.52 ms, KS = 2 for forward +
   // weight gradient 8.41 / 8.43 ms -> the default. (Three LDS stage buffers with an early commit, and four register sets, were

@@ -17,7 +17,11 @@ ap.add_argument("--aff", action="store_true", help="fwd / bwd_weight: the input 
 ap.add_argument("--bn", type=int, default=-1, help="bwd_data: also emit the BatchNorm-backward sums (activation code 0/1/2)")
 ap.add_argument("--addend", action="store_true", help="bwd_data: add a residual gradient in the epilogue")
 ap.add_argument("--cold", action="store_true", help="flush caches with a 1 GiB write before the traced launch")
+ap.add_argument("--tune", action="append", default=[], metavar="KEY=VALUE", help="tuning key of the kernel library (as tools/gemm_bench.py)")
 args = ap.parse_args()
+for kv in args.tune:
+    k_, v_ = kv.split("=")
+    ops.set_tuning(k_, int(v_))
 M, N, K = (int(v) for v in args.shape.split("x"))
 ops.set_gemm_precision("bf16")
 dev = "cuda"
