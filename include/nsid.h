@@ -362,6 +362,32 @@ int nsid_cqt(const float* wave, long in_stride, int B, long L, int hop, int widt
              const float* taps, long taps_len, const float* scale, float* out, long out_clip_stride, long out_bin_stride,
              void* stream);
 
+/* ---- waveform augmentations of the contrastive pair (modules/transformations.py:39-46, GPUTransformSampleID(cpu=True) for arch
+ * 'grafp': audiomentations Gain on the sample stems, then OneOf(PitchShift, TimeStretch) on the mix, librosa's phase vocoder) for a
+ * BATCH of clips, one launch per stage (csrc/augment.hip; the definition is DESIGN.md "Waveform augmentations"). n_fft 2048, hop
+ * 512, periodic Hann `window` (2048 floats, 16-byte aligned), `twiddle`: 2048 (cos, sin) pairs of -2 pi j / 2048 evaluated in fp64,
+ * 8-byte aligned. T_in = 1 + L/512 frames of 1025 bins; spectra are (B, T, 1025) complex64 with the bin index fastest.
+ * rate (B floats, device) is clamped per clip into the host-side bounds [rate_lo, rate_hi] (a NaN becomes rate_lo); every extent comes
+ * from the bounds alone: T_out_max >= ceil(T_in / rate_lo) frames per clip, wave_stride >= rint(L / rate_lo) samples per clip.
+ * Index arithmetic is fp64 on (double)rate, values are fp32. No atomics: clip b of a batch is bit-equal to the clip alone.
+ *   stft:    spec[b][t][k] = STFT(gain[b] * x_j[b] + x_i[b]), center=True with zero padding
+ *   vocoder: out[b][t][k], t < T_out = ceil(T_in / r): |.| interpolated between columns floor(t r) and floor(t r) + 1, phase advanced
+ *            by the wrapped column-to-column increment; columns t >= T_out are not written
+ *   istft:   wave[b][j], j < n_s = rint(L / r): inverse FFT, window, overlap-add, / sum w^2 (where > FLT_MIN), n_fft/2 samples dropped
+ *   finish:  mode[b] == 1 (pitch shift): out[b][m] = c sum_j h(|m/r - j| c) wave[b][j], m < min(L, ceil(n_s r)), c = min(1, r), h =
+ *            `table` (64 * 512 + 1 floats: a Kaiser-windowed sinc at 512 points per zero crossing, linearly interpolated);
+ *            any other mode (time stretch): out[b][m] = wave[b][m], m < min(L, n_s); zero up to L in both
+ * NSID_EINVAL before any launch: null pointers, B < 1, L < 1 or L >= 2^30, strides shorter than rows, misaligned tables, rate_lo <= 0
+ * or rate_lo > rate_hi, T_out_max or wave_stride below the extents above. */
+int nsid_aug_stft(const float* x_i, long stride_i, const float* x_j, long stride_j, int B, long L, const float* gain,
+                  const float* window, const float* twiddle, float* spec, void* stream);
+int nsid_aug_vocoder(const float* spec, int B, long L, const float* rate, float rate_lo, float rate_hi, float* out,
+                     long T_out_max, void* stream);
+int nsid_aug_istft(const float* spec, long T_out_max, int B, long L, const float* rate, float rate_lo, float rate_hi,
+                   const float* window, const float* twiddle, float* wave, long wave_stride, void* stream);
+int nsid_aug_finish(const float* wave, long wave_stride, int B, long L, const int* mode, const float* rate, float rate_lo,
+                    float rate_hi, const float* table, float* out, long out_stride, void* stream);
+
 /* bf16 shadow of fp32 weights: dst[i] = bf16_rne(src[i]), n % 8 == 0, both 16-byte aligned (operand `w` of
  * nsid_linear_fwd / nsid_linear_bwd_data with w_dtype = NSID_BF16). */
 int nsid_f32_to_bf16(const float* src, void* dst, long n, void* stream);

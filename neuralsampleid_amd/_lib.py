@@ -64,6 +64,10 @@ SIGNATURES = {
     "nsid_unfold_segments": "piiiiips",
     "nsid_logmel_fft": "pliliippppiplls",
     "nsid_cqt": "pliliiipiplpplls",
+    "nsid_aug_stft": "plplilpppps",
+    "nsid_aug_vocoder": "pilpffpls",
+    "nsid_aug_istft": "plilpffpppls",
+    "nsid_aug_finish": "plilppffppls",
     "nsid_bcn_to_rows": "piiipiis",
     "nsid_rows_to_bcn": "piiiipis",
     "nsid_batched_index_select_fwd": "ppiiiiips",

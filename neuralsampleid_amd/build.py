@@ -13,7 +13,8 @@ CSRC = os.path.join(PKG, "csrc")
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libnsid_hip.so")
 OBJ_DIR = os.path.join(PKG, "csrc", "_obj")
-SOURCES = ["tuning.hip", "gemm.hip", "gemm256.hip", "wsgemm.hip", "ffn_fused.hip", "ffn256_fused.hip", "mrconv_fused.hip", "wgrad.hip", "wgrad256.hip", "bn.hip", "knn.hip", "mr.hip", "ntxent.hip", "misc.hip", "frontend.hip", "cqt.hip", "search.hip", "rerank.hip", "clf_train.hip", "dsact.hip", "resnet.hip"]
+SOURCES = ["tuning.hip", "gemm.hip", "gemm256.hip", "wsgemm.hip", "ffn_fused.hip", "ffn256_fused.hip", "mrconv_fused.hip", "wgrad.hip", "wgrad256.hip", "bn.hip", "knn.hip", "mr.hip", "ntxent.hip", "misc.hip", "frontend.hip", "augment.hip", "cqt.hip", "search.hip", "rerank.hip", "clf_train.hip", "dsact.hip", "resnet.hip"]
+HEADERS = ["nsid_common.h", "fft512.h"]          # internal headers: a change in one rebuilds every source
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",
          "-fno-gpu-rdc", "-I", os.path.join(ROOT, "include")]
@@ -24,7 +25,7 @@ def _newer(a, b):
 
 
 def _deps():
-    hdrs = [os.path.join(CSRC, "nsid_common.h"), os.path.join(ROOT, "include", "nsid.h")]
+    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(ROOT, "include", "nsid.h")]
     return max(os.path.getmtime(h) for h in hdrs)
 
 
@@ -40,8 +41,7 @@ def _source_hash() -> str:
     _check_flags()
     # every flag that shapes the code (the include path is the tree itself) and the compiler command
     h = hashlib.sha256((HIPCC + " " + " ".join(f for f in FLAGS if f != os.path.join(ROOT, "include"))).encode())
-    for f in [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "nsid_common.h"),
-                                                         os.path.join(ROOT, "include", "nsid.h")]:
+    for f in [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.join(ROOT, "include", "nsid.h")]:
         h.update(open(f, "rb").read())
     return h.hexdigest()
 

@@ -239,6 +239,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(clf_mine) X(clf_attn_fwd) X(clf_head_fwd) X(clf_head_bwd) X(clf_attn_bwd) X(clf_seg_reduce)   /* clf_train.hip: classifier training */ \
   X(logmel_fft)           /* frontend.hip: batched log-mel front end in one launch */ \
   X(cqt)                  /* cqt.hip: batched constant-Q front end in one launch */ \
+  X(aug_stft) X(aug_vocoder) X(aug_istft) X(aug_finish)   /* augment.hip: waveform augmentations, one launch per stage */ \
   X(conv2d_3x3) X(conv2d_1x1) X(ibn_relu) X(stem7_pool) X(gem_pool)   /* resnet.hip: the ResNet-IBN baseline's eval-mode forward */
 
 enum NsidCounterKey {

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI (include/nsid.h): torch supplies device memory and the stream, nothing else.
 
 Every function enqueues HIP kernels from libnsid_hip.so on torch's current stream; none falls back to ATen."""
+import math
 import os
 from typing import Optional, Tuple
 
@@ -1238,6 +1239,103 @@ def cqt(waves: torch.Tensor, hop: int, width: int, groups, taps: torch.Tensor, s
     out = torch.empty((B, n_bins, T), device=waves.device, dtype=torch.float32)
     call("nsid_cqt", _p(waves), waves.stride(0) if B > 1 else L, B, L, hop, width, n_bins, groups.ctypes.data, groups.shape[0],
          _p(taps), taps.numel(), _p(scale), _p(out), n_bins * T, T, _stream())
+    return out
+
+
+# ---- waveform augmentations (csrc/augment.hip, include/nsid.h nsid_aug_*): one wrapper per stage; modules/transformations.
+# GPUWaveAugment owns the tables and the workspaces and chains the four. The extents follow the host-side rate bounds alone.
+AUG_N_FFT, AUG_HOP, AUG_BINS = 2048, 512, 1025
+
+
+def aug_frames_in(L: int) -> int:
+    return 1 + L // AUG_HOP
+
+
+def aug_frames_out_max(L: int, rate_lo) -> int:
+    """ceil(T_in / rate_lo) in fp64 on float32(rate_lo): the frames a clip can have after the vocoder"""
+    return int(math.ceil(aug_frames_in(L) / float(np.float32(rate_lo))))
+
+
+def aug_stretched_max(L: int, rate_lo) -> int:
+    """rint(L / rate_lo), ties to even: the samples a clip can have after the inverse STFT"""
+    return int(np.rint(float(L) / float(np.float32(rate_lo))))
+
+
+def _aug_waves(name, *ws):
+    for w in ws:
+        if w.dim() != 2 or not w.is_cuda or w.dtype != torch.float32 or w.stride(1) != 1:
+            raise RuntimeError(f"{name} takes (B, L) float32 waveforms on the MI355X device with a contiguous last dimension")
+
+
+def aug_stft(x_i: torch.Tensor, x_j: torch.Tensor, gain: torch.Tensor, window: torch.Tensor, twiddle: torch.Tensor,
+             spec: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """STFT of gain[b] * x_j[b] + x_i[b] (n_fft 2048, hop 512, center / zero padding) -> (B, 1 + L // 512, 1025, 2) fp32 = complex64
+    with the bin index fastest; the mix is applied on the staging load, no mixed copy is written"""
+    _aug_waves("aug_stft", x_i, x_j)
+    _chk(gain, window, twiddle, spec)
+    B, L = x_i.shape
+    if x_j.shape != x_i.shape or gain.numel() != B:
+        raise RuntimeError("aug_stft: x_i, x_j of one shape (B, L) and gain of B entries")
+    T = aug_frames_in(L)
+    if spec is None:
+        spec = torch.empty((B, T, AUG_BINS, 2), device=x_i.device, dtype=torch.float32)
+    elif spec.numel() < B * T * AUG_BINS * 2:
+        raise RuntimeError("aug_stft: the spectrum workspace is too small")
+    call("nsid_aug_stft", _p(x_i), x_i.stride(0) if B > 1 else L, _p(x_j), x_j.stride(0) if B > 1 else L, B, L, _p(gain),
+         _p(window), _p(twiddle), _p(spec), _stream())
+    return spec
+
+
+def aug_vocoder(spec: torch.Tensor, B: int, L: int, rate: torch.Tensor, rate_lo, rate_hi, out: Optional[torch.Tensor] = None):
+    """phase vocoder by rate[b] (clamped into [rate_lo, rate_hi]) on (B, T_in, 1025) spectra -> (B, T_out_max, 1025, 2); clip b's
+    columns t >= ceil(T_in / rate) are not written"""
+    _chk(spec, rate, out)
+    T_max = aug_frames_out_max(L, rate_lo)
+    if spec.numel() < B * aug_frames_in(L) * AUG_BINS * 2 or rate.numel() != B:
+        raise RuntimeError("aug_vocoder: spec must hold (B, 1 + L // 512, 1025) complex values and rate B entries")
+    if out is None:
+        out = torch.empty((B, T_max, AUG_BINS, 2), device=spec.device, dtype=torch.float32)
+    elif out.numel() < B * T_max * AUG_BINS * 2:
+        raise RuntimeError("aug_vocoder: the output workspace is too small")
+    call("nsid_aug_vocoder", _p(spec), B, L, _p(rate), float(rate_lo), float(rate_hi), _p(out), T_max, _stream())
+    return out
+
+
+def aug_istft(spec: torch.Tensor, B: int, L: int, rate: torch.Tensor, rate_lo, rate_hi, window: torch.Tensor, twiddle: torch.Tensor,
+              wave: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """inverse STFT of the vocoder's (B, T_out_max, 1025) spectra -> (B, S_max) stretched waveforms, S_max = rint(L / rate_lo); clip
+    b holds rint(L / rate) samples, the rest of its row is not written"""
+    _chk(spec, rate, window, twiddle, wave)
+    T_max, S_max = aug_frames_out_max(L, rate_lo), aug_stretched_max(L, rate_lo)
+    if spec.numel() < B * T_max * AUG_BINS * 2 or rate.numel() != B:
+        raise RuntimeError("aug_istft: spec must hold (B, T_out_max, 1025) complex values and rate B entries")
+    if wave is None:
+        wave = torch.empty((B, S_max), device=spec.device, dtype=torch.float32)
+    elif wave.numel() < B * S_max:
+        raise RuntimeError("aug_istft: the waveform workspace is too small")
+    call("nsid_aug_istft", _p(spec), T_max, B, L, _p(rate), float(rate_lo), float(rate_hi), _p(window), _p(twiddle), _p(wave),
+         S_max, _stream())
+    return wave
+
+
+def aug_finish(wave: torch.Tensor, B: int, L: int, mode: torch.Tensor, rate: torch.Tensor, rate_lo, rate_hi, table: torch.Tensor,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(B, S_max) stretched waveforms -> (B, L): mode 1 resamples by rate through the tabulated filter, any other mode copies;
+    both cut or zero-fill to L"""
+    _chk(wave, rate, table)
+    S_max = aug_stretched_max(L, rate_lo)
+    if not mode.is_cuda or mode.dtype != torch.int32 or not mode.is_contiguous() or mode.numel() != B or rate.numel() != B:
+        raise RuntimeError("aug_finish: mode must be B contiguous int32 entries on the device, rate B entries")
+    if wave.numel() < B * S_max:
+        raise RuntimeError("aug_finish: wave must hold (B, rint(L / rate_lo)) samples")
+    if out is None:
+        out = torch.empty((B, L), device=wave.device, dtype=torch.float32)
+    else:
+        _aug_waves("aug_finish", out)
+        if out.shape != (B, L):
+            raise RuntimeError("aug_finish: out must be (B, L)")
+    call("nsid_aug_finish", _p(wave), S_max, B, L, _p(mode), _p(rate), float(rate_lo), float(rate_hi), _p(table), _p(out),
+         out.stride(0) if B > 1 else L, _stream())
     return out
 
 

@@ -5,6 +5,7 @@ its audio pipeline (audio decoding / augmentation are outside this path). Shows 
     python tools/train_synthetic.py --steps 50                       # reference-style loop: torch.optim.Adam + clip_grad_norm_
     python tools/train_synthetic.py --steps 50 --fused --bf16        # FusedClipAdam, bf16 activation storage, two-stream views
     python tools/train_synthetic.py --steps 50 --fused --graph --from-wave   # train.py:58 too: waveforms -> log-mel on the GPU
+    python tools/train_synthetic.py --steps 50 --fused --from-wave --augment # and the waveform augmentations in front of it
 """
 import argparse
 import os
@@ -32,6 +33,7 @@ def batches(n, batch, device):
 
 
 FCFG = {"fs": 16000, "n_fft": 1024, "win_len": 1024, "hop_len": 512, "overlap": 0.875, "arch": "grafp"}
+ACFG = {"gain": 10, "pitch_shift": 3, "min_rate": 0.7, "max_rate": 1.5}      # grafp.yaml:45-50, the ranges of --augment
 N_SAMPLES = 65280                                     # 4.08 s at 16 kHz (grafp.yaml): 128 frames
 
 
@@ -57,13 +59,21 @@ def main():
     ap.add_argument("--bf16", action="store_true", help="bf16 activation storage + bf16 MFMA operands (BASELINE config 2)")
     ap.add_argument("--from-wave", action="store_true",
                     help="start every step from waveforms: GPUTransformSampleID(train=True) as train.py:58 `augment`")
+    ap.add_argument("--augment", action="store_true",
+                    help="with --from-wave: Gain + TimeStretch / PitchShift of the pair on the GPU (GPUWaveAugment), eagerly in "
+                         "front of the step, the reference's GPUTransformSampleID(cpu=True) on its DataLoader workers")
     args = ap.parse_args()
+    if args.augment and not args.from_wave:
+        ap.error("--augment works on waveforms: add --from-wave")
     device = torch.device("cuda")
-    source, augment = batches, None
+    source, augment, wave_aug = batches, None, None
     if args.from_wave:
         from neuralsampleid_amd.modules.transformations import GPUTransformSampleID   # (reference: modules.transformations)
         augment = GPUTransformSampleID(cfg={**CFG, **FCFG}, train=True).to(device)    # train.py:100
         source = wave_batches
+    if args.augment:
+        from neuralsampleid_amd.modules.transformations import GPUWaveAugment
+        wave_aug = GPUWaveAugment(cfg={**CFG, **FCFG, **ACFG}).to(device)
     if args.bf16:
         ops.set_gemm_precision("bf16")
         F_.set_activation_dtype("bf16")
@@ -82,6 +92,8 @@ def main():
         torch.cuda.synchronize()
         t0 = time.time()
         for idx, (x_i, x_j) in enumerate(data):
+            if wave_aug is not None:
+                x_i, x_j = wave_aug(x_i, x_j)                                             # eager, in front of the captured step
             loss = step(x_i, x_j)
             if idx % 10 == 0:
                 print(f"Step [{idx}/{args.steps}]\t Loss: {loss.item():.4f}")
@@ -91,6 +103,8 @@ def main():
     t0 = time.time()
     for idx, (x_i, x_j) in enumerate(source(args.steps, args.batch, device)):            # train.py:53
         optimizer.zero_grad()                                                             # :58
+        if wave_aug is not None:
+            x_i, x_j = wave_aug(x_i, x_j)                                                 # the dataset's transform, on the device
         if augment is not None:
             with torch.no_grad():
                 x_i, x_j = augment(x_i, x_j)                                              # :58-59
