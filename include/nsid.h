@@ -77,6 +77,8 @@ int nsid_row_tiles(int M);
  * "ibn_relu", "stem7_pool", "gem_pool")
  * except: "bn_stat" (rows x cols layer: the [2][nsid_row_tiles(rows)][cols] fp32 partial sums between a GEMM's statistics
  * epilogue / nsid_bn_bwd_reduce and the finalize kernels), "ntxent" (rows = pairs of the global batch: nsid_ntxent_ws_floats),
+ * "baseline_loss" (rows = M, cols = D: nsid_baseline_loss_ws_floats),
+ * "gem_pool_bwd" (rows = clips, cols = channels: one dp partial per 64 channels of a clip),
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
  * per-split top-64 lists of its first phase). */
 long nsid_workspace_bytes(const char* op, long rows, long cols);
@@ -402,6 +404,34 @@ size_t nsid_ntxent_ws_floats(int Bg);
 int nsid_ntxent_fwd_bwd(const float* z_i, const float* z_j, int Bg, int d, float tau, int p0, int np, float* ws,
                         float* loss_out, float* dz_i, float* dz_j, void* stream);
 
+/* ---- training objective of the ResNet-IBN baseline (simclr/triplet.py:6-61, baseline/train.py:64-77) ------------------
+ * Limits of all three: D % 16 == 0, 16 <= D <= 2048, at most 2048 rows (M, or 2 * B), 16-byte aligned pointers. Similarities are
+ * exact fp32 (v_mfma_f32_16x16x4_f32); no floating-point atomics: the outputs are bitwise equal from run to run. Everything,
+ * the count of valid anchors and the case without one included, stays on the device. dz / de == NULL: forward only.
+ * ws: nsid_baseline_loss_ws_floats(M, D) floats (M = 2 * B for the pair forms). With Mp = M rounded up to 64, the call leaves in
+ * ws: [0, Mp) log-sum-exp per row; then as int32 [Mp, 2 Mp) the positive p* per anchor (-1: none), [2 Mp, 3 Mp) the semi-hard
+ * negative n* (-1: anchor not valid), [3 Mp, 4 Mp) flags (bit 0: valid, bit 1: hinge active); the rest is scratch.
+ * Decisions (p*, n*, valid) are taken on the fp32 similarities with the threshold pos - (float)margin in fp32, as the reference
+ * takes them; the values that enter the means (row log-sum-exp, pos and neg of the chosen pairs, margin, beta, gamma) are formed
+ * in double and rounded once.
+ *
+ * pair_ce (classifier_loss): z = cat(z_i, z_j) (M = 2 B rows), S = z z^T with the diagonal at -inf, target of row i = (i + B) mod M;
+ *   out[0] = mean cross-entropy; dz = (G + G^T) z, G = (softmax_row(S) - onehot) / M.
+ * triplet (triplet_loss): S = e e^T; per anchor a the hardest positive pos = max S_ab over b != a with labels[b] == labels[a] (-inf
+ *   if none) and the smallest semi-hard negative neg = min S_ab over labels[b] != labels[a] with S_ab > pos - margin (first index
+ *   on exact ties in both); a is valid iff such a negative exists. out[0] = mean over valid a of relu(pos - neg + margin) (0 without
+ *   a valid anchor, with zero gradient), out[1] = number of valid anchors.
+ * baseline_objective (the step of train.py:66-77): out[1] = pair_ce(z_i, z_j), out[2] = triplet(normalize(cat(z_i, z_j)),
+ *   cat(arange(B), arange(B)), margin) with F.normalize's eps = 1e-12, out[0] = beta out[1] + gamma out[2], out[3] = number of valid
+ *   anchors; dz_i / dz_j = d out[0] / d z, the backward of the normalisation included. */
+size_t nsid_baseline_loss_ws_floats(int M, int D);
+int nsid_pair_ce_fwd_bwd(const float* z_i, const float* z_j, int B, int D, float* ws, float* out, float* dz_i, float* dz_j,
+                         void* stream);
+int nsid_triplet_fwd_bwd(const float* e, const int64_t* labels, int M, int D, double margin, float* ws, float* out, float* de,
+                         void* stream);
+int nsid_baseline_objective_fwd_bwd(const float* z_i, const float* z_j, int B, int D, double margin, double beta, double gamma,
+                                    float* ws, float* out, float* dz_i, float* dz_j, void* stream);
+
 /* ---- optimiser (train.py:73-75: clip_grad_norm_(1.0) + Adam) -------------------------------------------
  * sumsq: partial[blocks] sums of squares of g (blocks = nsid_sumsq_blocks(n)).
  * adam:  norm = sqrt(sum partial); coef = min(1, max_norm/(norm+1e-6)); torch.optim.Adam update with g*coef.
@@ -535,6 +565,11 @@ int nsid_ibn_relu_fwd(const void* x, int B, int HW, int C, const float* in_gamma
 int nsid_stem7_pool_fwd(const float* x, int B, int H, int W, const float* w, const float* bias, void* out, int out_dtype,
                         void* stream);
 int nsid_gem_pool_fwd(const void* x, int B, int HW, int C, const float* p, float eps, float* out, int x_dtype, void* stream);
+/* gem_pool_bwd: with xh = max(x, eps), m = mean_hw xh^p, y = m^(1/p): dx[(b hw), c] = dy[b][c] y^(1-p) xh^(p-1) / HW where x > eps,
+ * else 0 (fp32, whatever x_dtype); dp[0] = sum_{b,c} dy y (sum_hw xh^p ln xh / (p HW m) - ln m / p^2), reduced in two stages through
+ * dp_part (B * C / 64 floats of scratch, nsid_workspace_bytes("gem_pool_bwd", B, C)): no atomics. p[0] is read on the device. */
+int nsid_gem_pool_bwd(const void* x, const float* dy, int B, int HW, int C, const float* p, float eps, float* dx, float* dp_part,
+                      float* dp, int x_dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # loaded, nothing inside the library reads the environment; bench.py records an override in its JSON line (config.lib).
 LIB_PATH = os.environ.get("NSID_LIB") or os.path.join(_PKG, "libnsid_hip.so")
 
-# signature letters: p = device pointer, i = int, l = long, z = size_t, f = float, s = stream (void*)
+# signature letters: p = device pointer, i = int, l = long, z = size_t, f = float, d = double, s = stream (void*)
 SIGNATURES = {
     "nsid_set_gemm_precision": "i",
     "nsid_linear_fwd": "pipippiiiiippiipiis",
@@ -56,6 +56,9 @@ SIGNATURES = {
     "nsid_l2norm_fwd": "piifpps",
     "nsid_l2norm_bwd": "pppiifps",
     "nsid_ntxent_fwd_bwd": "ppiifiipppps",
+    "nsid_pair_ce_fwd_bwd": "ppiipppps",
+    "nsid_triplet_fwd_bwd": "ppiidppps",
+    "nsid_baseline_objective_fwd_bwd": "ppiidddpppps",
     "nsid_sumsq_partial": "plps",
     "nsid_adam_step": "pppplpppips",
     "nsid_f32_to_bf16": "ppls",
@@ -95,6 +98,7 @@ SIGNATURES = {
     "nsid_ibn_relu_fwd": "piiippfpppis",
     "nsid_stem7_pool_fwd": "piiipppis",
     "nsid_gem_pool_fwd": "piiipfpis",
+    "nsid_gem_pool_bwd": "ppiiipfpppis",
 }
 
 class WgradProblem(ctypes.Structure):
@@ -105,7 +109,7 @@ class WgradProblem(ctypes.Structure):
                 ("ds_out_nodes", ctypes.c_int)]
 
 
-_CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "s": ctypes.c_void_p,
+_CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "d": ctypes.c_double, "s": ctypes.c_void_p,
        "z": ctypes.c_size_t}
 
 
@@ -167,11 +171,13 @@ def _load():
     lib.nsid_sumsq_blocks.restype = ctypes.c_int
     lib.nsid_ntxent_ws_floats.argtypes = [ctypes.c_int]
     lib.nsid_ntxent_ws_floats.restype = ctypes.c_size_t
+    lib.nsid_baseline_loss_ws_floats.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.nsid_baseline_loss_ws_floats.restype = ctypes.c_size_t
     return lib
 
 
 lib = _load()
-EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_workspace_bytes"]
+EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_baseline_loss_ws_floats", "nsid_workspace_bytes"]
 
 _ERR = {-1: "NSID_EINVAL (unsupported shape, misaligned pointer or bad argument)",
         -2: "NSID_ELAUNCH (HIP runtime refused the launch)"}

@@ -22,6 +22,7 @@
 //                        lanes of a wave, the 49 weights of a channel in registers, the input patch broadcast from LDS) and pooled
 //                        from there; a conv pixel outside the conv map is -inf for the pool.
 //   gem_pool_kernel    : (mean over HW of max(x, eps)^p)^(1/p) per (clip, channel); p is read from device memory.
+//   gem_pool_bwd_kernel: its backward (dx fp32, one dp partial per workgroup; gem_dp_sum_kernel adds them: no atomics).
 #include "nsid_common.h"
 
 namespace {
@@ -410,6 +411,58 @@ __global__ __launch_bounds__(256) void gem_pool_kernel(const T* __restrict__ x, 
   }
 }
 
+// Backward of gem_pool_kernel for the same (64 channels, clip) tile. With xh = max(x, eps), m = mean_hw xh^p, y = m^(1/p):
+//   dx = dy y^(1-p) xh^(p-1) / HW where x > eps, else 0
+//   dp = sum_{b,c} dy y ( sum_hw xh^p ln xh / (p HW m) - ln m / p^2 ): one partial per workgroup, summed by gem_dp_sum_kernel
+template <typename T>
+__global__ __launch_bounds__(256) void gem_pool_bwd_kernel(const T* __restrict__ x, const float* __restrict__ dy, int HW, int C,
+                                                           const float* __restrict__ p_dev, float eps, float* __restrict__ dx,
+                                                           float* __restrict__ dp_part) {
+  __shared__ double red[2][4][64];
+  __shared__ float coef[64];
+  const int tid = threadIdx.x, c = tid & 63, g = tid >> 6;
+  const int c0 = blockIdx.x * 64, b = blockIdx.y;
+  const float p = p_dev[0];
+  const T* xb = x + (long)b * HW * C + c0 + c;
+  double s = 0.0, sl = 0.0;          // dp is a difference of two nearly equal means: sums and the per-channel factors in double
+  for (int r = g; r < HW; r += 4) {
+    const float xh = fmaxf((float)xb[(long)r * C], eps);
+    const float xp = powf(xh, p);
+    s += (double)xp;
+    sl += (double)xp * (double)logf(xh);
+  }
+  red[0][g][c] = s;
+  red[1][g][c] = sl;
+  __syncthreads();
+  if (tid < 64) {
+    const double t = ((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid];
+    const double tl = ((red[1][0][tid] + red[1][1][tid]) + red[1][2][tid]) + red[1][3][tid];
+    const double pd = (double)p, m = t / (double)HW;
+    const double y = pow(m, 1.0 / pd);
+    const double g_y = (double)dy[(long)b * C + c0 + tid];
+    coef[tid] = (float)(g_y * pow(y, 1.0 - pd) / (double)HW);
+    const double part = wave_sum_d(g_y * y * (tl / (pd * (double)HW * m) - log(m) / (pd * pd)));
+    if (tid == 0) dp_part[(long)b * gridDim.x + blockIdx.x] = (float)part;
+  }
+  __syncthreads();
+  const float k = coef[c];
+  float* db = dx + (long)b * HW * C + c0 + c;
+  for (int r = g; r < HW; r += 4) {
+    const float xv = (float)xb[(long)r * C];
+    db[(long)r * C] = xv > eps ? k * powf(xv, p - 1.f) : 0.f;
+  }
+}
+
+__global__ __launch_bounds__(256) void gem_dp_sum_kernel(const float* __restrict__ part, int n, float* __restrict__ dp) {
+  __shared__ double red[4];
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += blockDim.x) s += (double)part[i];
+  s = wave_sum_d(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) dp[0] = (float)((red[0] + red[1]) + (red[2] + red[3]));
+}
+
 }  // namespace
 
 extern "C" int nsid_conv2d_fwd(const void* x, int B, int H, int W, int C, const void* w, int w_dtype, const float* bias,
@@ -474,5 +527,17 @@ extern "C" int nsid_gem_pool_fwd(const void* x, int B, int HW, int C, const floa
   nsid_count(NSID_C_gem_pool);
   NSID_DISPATCH_DTYPE(x_dtype, T, NSID_LAUNCH(gem_pool_kernel<T>, dim3(C / 64, B), dim3(256), 0, static_cast<hipStream_t>(stream),
                                               static_cast<const T*>(x), HW, C, p, eps, out));
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_gem_pool_bwd(const void* x, const float* dy, int B, int HW, int C, const float* p, float eps, float* dx,
+                                 float* dp_part, float* dp, int x_dtype, void* stream) {
+  NSID_REQUIRE(x && dy && p && dx && dp_part && dp && B > 0 && B <= 65535 && HW > 0 && C > 0 && C % 64 == 0 && eps > 0.f);
+  NSID_REQUIRE(NSID_DTYPE_OK(x_dtype) && (long)B * (C / 64) < (1L << 31));
+  nsid_count(NSID_C_gem_pool_bwd);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  NSID_DISPATCH_DTYPE(x_dtype, T, NSID_LAUNCH(gem_pool_bwd_kernel<T>, dim3(C / 64, B), dim3(256), 0, s, static_cast<const T*>(x), dy,
+                                              HW, C, p, eps, dx, dp_part));
+  NSID_LAUNCH(gem_dp_sum_kernel, dim3(1), dim3(256), 0, s, dp_part, B * (C / 64), dp);
   return nsid_launch_status();
 }

@@ -70,6 +70,7 @@ extern "C" const char* nsid_tuning_key(int i) { return (i >= 0 && i < NSID_T_COU
 extern "C" int nsid_row_tiles(int M);
 extern "C" int nsid_sumsq_blocks(long n);
 extern "C" size_t nsid_ntxent_ws_floats(int Bg);
+extern "C" size_t nsid_baseline_loss_ws_floats(int M, int D);
 extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
   if (op == nullptr || rows < 0 || cols < 0) return -1;
   static const char* const kNone[] = {"knn_graph", "mr_aggregate", "linear", "linear_bwd_data", "linear_bwd_weight", "downsample3",
@@ -81,6 +82,10 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
     return 2L * nsid_row_tiles((int)rows) * cols * (long)sizeof(float);
   if (strcmp(op, "ntxent") == 0)             // rows = pairs of the GLOBAL batch
     return (long)(nsid_ntxent_ws_floats((int)rows) * sizeof(float));
+  if (strcmp(op, "baseline_loss") == 0)      // rows = M (2 B for the pair forms), cols = D
+    return (long)(nsid_baseline_loss_ws_floats((int)rows, (int)cols) * sizeof(float));
+  if (strcmp(op, "gem_pool_bwd") == 0)       // rows = clips, cols = channels
+    return rows * ((cols + 63) / 64) * (long)sizeof(float);
   if (strcmp(op, "sumsq") == 0)              // rows = elements of the flat gradient
     return (long)nsid_sumsq_blocks(rows) * (long)sizeof(float);
   if (strcmp(op, "flat_l2_topk") == 0)       // rows = query rows, cols = database rows; for k = 64

@@ -10,7 +10,9 @@ ResidualIBN block:
     conv2 3x3 stride s, bn2 folded (no activation)                          nsid_conv2d_fwd
     relu(conv3 1x1 with bn3 folded + identity)                              nsid_conv2d_fwd (1x1 form: addend + ReLU epilogue)
 Packed / folded weights and their bf16 shadows are cached by ops.folded_conv_bn (parameter versions and state epochs in the key), so
-a load_state_dict is seen by the next forward. Training mode and CPU tensors raise: the backward of these kernels does not exist."""
+a load_state_dict is seen by the next forward. Training mode and CPU tensors raise: the backward of the convolution and norm kernels does
+not exist. What does exist is everything behind the last convolution: ResNetIBN.head_train (GeM pooling and embedding head, forward
+and backward) and the losses of simclr/triplet.py."""
 import torch
 import torch.nn as nn
 
@@ -132,6 +134,34 @@ class GeMPooling(nn.Module):
         return self.pool_rows(rows, B, H * W).view(B, C, 1, 1)
 
 
+class _HeadTrainFn(torch.autograd.Function):
+    """GeM pooling -> embedding head on rows (B*HW, 1024), with its backward (nsid_gem_pool_bwd and the row-GEMM backward kernels)"""
+
+    @staticmethod
+    def forward(ctx, rows, p, weight, bias, B, HW, eps):
+        C, E = weight.shape[1], weight.shape[0]
+        pooled = ops.gem_pool_fwd(rows, B, HW, C, p, eps)
+        # B rows against a 1024-deep reduction: split it, as the projection head of the GNN path does in training
+        # (functional.proj_mean_forward): 4 x the workgroups and 4 x shorter fp32 summation chains; the partial sums meet in atomics
+        h, _ = ops.linear_fwd(pooled, weight, bias, B, E, C, ksplit=4 if (C >= 512 and B <= 512) else 1)
+        ctx.save_for_backward(rows, p, weight, pooled)
+        ctx.dims = (B, HW, C, E, eps)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        rows, p, weight, pooled = ctx.saved_tensors
+        B, HW, C, E, eps = ctx.dims
+        dh = dh.contiguous()
+        dw = ops.zeros((E, C), dh.device)
+        db = ops.zeros((E,), dh.device)
+        ops.linear_bwd_weight(dh, pooled, dw, B, E, C)
+        ops.colsum_acc(dh, db)
+        dpooled = ops.linear_bwd_data(dh, weight, B, E, C)
+        drows, dp = ops.gem_pool_bwd(rows, dpooled, B, HW, C, p, eps)
+        return drows, dp, dw, db, None, None, None
+
+
 def rows_to_bchw(rows, B, H, W):
     """channels-last rows (B*H*W, C) -> the reference's (B, C, H, W) fp32 tensor (module boundary / tests: off the hot path)"""
     return rows.float().view(B, H, W, rows.shape[1]).permute(0, 3, 1, 2).contiguous()
@@ -176,6 +206,17 @@ class ResNetIBN(nn.Module):
         head = self.embedding_head
         h, _ = ops.linear_fwd(pooled, head.weight, head.bias, B, head.out_features, head.in_features)
         return h
+
+    def head_train(self, rows, B, HW):
+        """layer-4 rows (B*HW, 1024), fp32 or bf16 -> h (B, 2048), differentiable: backward fills the gradients of rows (fp32),
+        global_pool.p, embedding_head.weight and embedding_head.bias (autograd rounds the gradient of bf16 rows to bf16; ops.gem_pool_bwd
+        returns it in fp32). What lies in front of the rows has no backward yet."""
+        if not rows.is_cuda:
+            raise NotImplementedError("ResNetIBN.head_train: there is no CPU path; move the model and its input to the GPU")
+        head = self.embedding_head
+        if rows.dim() != 2 or tuple(rows.shape) != (B * HW, head.in_features):
+            raise ValueError(f"head_train: expected rows ({B * HW}, {head.in_features}), got {tuple(rows.shape)}")
+        return _HeadTrainFn.apply(rows, self.global_pool.p, head.weight, head.bias, B, HW, self.global_pool.eps)
 
     def forward(self, x):
         return self.forward_rows(x)

@@ -1178,6 +1178,91 @@ def ntxent_fwd_bwd(z_i, z_j, tau, p0=0, npairs=None, want_grad=True):
     return loss, dzi, dzj
 
 
+# ------------------------------------------------------------------------------------------------ baseline objective (csrc/baseline_loss.hip)
+BL_MAX = 2048        # rows (M, or 2 B) and features of the baseline's losses
+
+
+def _bl_check(name, M, d):
+    if d % 16 != 0 or not 16 <= d <= BL_MAX or not 1 <= M <= BL_MAX:
+        raise ValueError(f"{name}: D % 16 == 0, 16 <= D <= {BL_MAX} and at most {BL_MAX} rows are supported, got {M} rows of {d}")
+
+
+def _bl_ws(M, d, device):
+    return torch.empty((lib.nsid_baseline_loss_ws_floats(M, d),), device=device, dtype=torch.float32)
+
+
+def _bl_mining(ws, M):
+    """the per-anchor decisions a call leaves at the head of its workspace (include/nsid.h): p*, n* (int32, -1: none), valid, active"""
+    Mp = (M + 63) // 64 * 64
+    ints = ws[Mp:4 * Mp].view(torch.int32)
+    flags = ints[2 * Mp:2 * Mp + M]
+    return {"pidx": ints[:M], "nidx": ints[Mp:Mp + M], "valid": (flags & 1).bool(), "active": (flags & 2).bool()}
+
+
+def pair_ce_fwd_bwd(z_i, z_j, want_grad=True):
+    """classifier_loss of simclr/triplet.py:44-61 on z = cat(z_i, z_j): (loss (1,), dz_i, dz_j); gradients None when not wanted"""
+    _chk(z_i, z_j)
+    B, d = z_i.shape
+    if z_j.shape != z_i.shape:
+        raise ValueError(f"pair_ce_fwd_bwd: z_i {tuple(z_i.shape)} and z_j {tuple(z_j.shape)} differ")
+    _bl_check("pair_ce_fwd_bwd", 2 * B, d)
+    ws = _bl_ws(2 * B, d, z_i.device)
+    out = torch.empty((1,), device=z_i.device, dtype=torch.float32)
+    dzi = torch.empty_like(z_i) if want_grad else None
+    dzj = torch.empty_like(z_j) if want_grad else None
+    M = 2 * B
+    _timed("baseline_loss_kernels<ce>", 2.0 * M * M * d * (2 if want_grad else 1), 4.0 * d * M * (2 if want_grad else 1), lambda: call(
+        "nsid_pair_ce_fwd_bwd", _p(z_i), _p(z_j), B, d, _p(ws), _p(out), _p(dzi), _p(dzj), _stream()), (M, M, d, 1))
+    return out, dzi, dzj
+
+
+def triplet_fwd_bwd(e, labels, margin=0.2, want_grad=True, mining=False):
+    """triplet_loss of simclr/triplet.py:6-40: (out (2,) = [loss, n_valid], de); mining=True appends the per-anchor decisions"""
+    _chk(e)
+    if not (labels.is_cuda and labels.dtype == torch.int64 and labels.is_contiguous()):
+        raise RuntimeError("triplet_fwd_bwd: labels must be a contiguous int64 tensor on the GPU")
+    M, d = e.shape
+    if labels.numel() != M:
+        raise ValueError(f"triplet_fwd_bwd: {M} embeddings and {labels.numel()} labels")
+    _bl_check("triplet_fwd_bwd", M, d)
+    ws = _bl_ws(M, d, e.device)
+    out = torch.empty((2,), device=e.device, dtype=torch.float32)
+    de = torch.empty_like(e) if want_grad else None
+    _timed("baseline_loss_kernels<triplet>", 2.0 * M * M * d, 4.0 * d * M * (2 if want_grad else 1), lambda: call(
+        "nsid_triplet_fwd_bwd", _p(e), _p(labels), M, d, float(margin), _p(ws), _p(out), _p(de), _stream()), (M, M, d, 1))
+    return (out, de, _bl_mining(ws, M)) if mining else (out, de)
+
+
+def baseline_objective_fwd_bwd(z_i, z_j, margin=0.2, beta=1.0, gamma=1.0, want_grad=True, mining=False, ws=None, out=None, dz=None):
+    """the step objective of baseline/train.py:66-77: (out (4,) = [loss, cls, trip, n_valid], dz_i, dz_j). ws / out / dz = (dz_i, dz_j):
+    caller-owned buffers (a captured step allocates nothing)"""
+    _chk(z_i, z_j)
+    B, d = z_i.shape
+    if z_j.shape != z_i.shape:
+        raise ValueError(f"baseline_objective_fwd_bwd: z_i {tuple(z_i.shape)} and z_j {tuple(z_j.shape)} differ")
+    M = 2 * B
+    _bl_check("baseline_objective_fwd_bwd", M, d)
+    if ws is None:
+        ws = _bl_ws(M, d, z_i.device)
+    if out is None:
+        out = torch.empty((4,), device=z_i.device, dtype=torch.float32)
+    _chk(ws, out)
+    if ws.numel() < lib.nsid_baseline_loss_ws_floats(M, d) or out.numel() < 4:
+        raise ValueError("baseline_objective_fwd_bwd: workspace or result buffer too small")
+    if dz is not None:
+        dzi, dzj = dz
+        _chk(dzi, dzj)
+        if dzi.shape != z_i.shape or dzj.shape != z_i.shape:
+            raise ValueError("baseline_objective_fwd_bwd: gradient buffers do not match the inputs")
+    else:
+        dzi = torch.empty_like(z_i) if want_grad else None
+        dzj = torch.empty_like(z_j) if want_grad else None
+    _timed("baseline_loss_kernels<objective>", 2.0 * M * M * d * (3 if dzi is not None else 2), 4.0 * d * M * 4, lambda: call(
+        "nsid_baseline_objective_fwd_bwd", _p(z_i), _p(z_j), B, d, float(margin), float(beta), float(gamma), _p(ws), _p(out),
+        _p(dzi), _p(dzj), _stream()), (M, M, d, 1))
+    return (out, dzi, dzj, _bl_mining(ws, M)) if mining else (out, dzi, dzj)
+
+
 # ------------------------------------------------------------------------------------------------ step plumbing
 def fill_zero(t: torch.Tensor) -> torch.Tensor:
     """t[...] = 0 with our own streaming kernel (zero_grad: the captured step holds no ATen kernel)"""
@@ -1809,3 +1894,17 @@ def gem_pool_fwd(x, B, HW, C, p, eps=GEM_EPS) -> torch.Tensor:
     _tk("gem_pool_kernel", float(x.element_size()) * x.numel(), lambda: call(
         "nsid_gem_pool_fwd", _p(x), B, HW, C, _p(p), eps, _p(out), dt, _stream()), (B * HW, C, 0, 1))
     return out
+
+
+def gem_pool_bwd(x, dy, B, HW, C, p, eps=GEM_EPS):
+    """backward of gem_pool_fwd: rows x (B*HW, C) fp32 or bf16, dy (B, C) fp32 -> (dx (B*HW, C) fp32, dp (1,))"""
+    _chk(p, dy)
+    dt = _act(x)
+    if tuple(x.shape) != (B * HW, C) or tuple(dy.shape) != (B, C) or p.numel() != 1:
+        raise ValueError("gem_pool_bwd: shapes do not match")
+    dx = torch.empty((B * HW, C), device=x.device, dtype=torch.float32)
+    part = torch.empty((B * ((C + 63) // 64),), device=x.device, dtype=torch.float32)
+    dp = torch.empty((1,), device=x.device, dtype=torch.float32)
+    _tk("gem_pool_bwd_kernel", float(2 * x.element_size() + 4) * x.numel(), lambda: call(
+        "nsid_gem_pool_bwd", _p(x), _p(dy), B, HW, C, _p(p), eps, _p(dx), _p(part), _p(dp), dt, _stream()), (B * HW, C, 0, 1))
+    return dx, dp
