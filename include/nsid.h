@@ -79,6 +79,9 @@ int nsid_row_tiles(int M);
  * epilogue / nsid_bn_bwd_reduce and the finalize kernels), "ntxent" (rows = pairs of the global batch: nsid_ntxent_ws_floats),
  * "baseline_loss" (rows = M, cols = D: nsid_baseline_loss_ws_floats),
  * "gem_pool_bwd" (rows = clips, cols = channels: one dp partial per 64 channels of a clip),
+ * "conv2d_bwd_weight" (rows = output rows B*Ho*Wo, cols = weight elements Cout*k*k*C: one fp32 dw per row split,
+ * nsid_conv2d_wgrad_splits; 0 when one split covers the rows), "ibn_relu_bwd" (rows = clips, cols = channels: the per-clip sums),
+ * and 0 for "conv2d_bwd_data", "col_stat", "bn_add_relu", "relu_bwd";
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
  * per-split top-64 lists of its first phase). */
 long nsid_workspace_bytes(const char* op, long rows, long cols);
@@ -570,6 +573,41 @@ int nsid_gem_pool_fwd(const void* x, int B, int HW, int C, const float* p, float
  * dp_part (B * C / 64 floats of scratch, nsid_workspace_bytes("gem_pool_bwd", B, C)): no atomics. p[0] is read on the device. */
 int nsid_gem_pool_bwd(const void* x, const float* dy, int B, int HW, int C, const float* p, float eps, float* dx, float* dp_part,
                       float* dp, int x_dtype, void* stream);
+
+/* ---- ResNet-IBN baseline, training-mode residual blocks (csrc/resnet.hip): the backward of conv2d_fwd and ibn_relu_fwd, the batch
+ * statistics of a conv2d output and the block tail. Shapes follow conv2d_fwd's rules (ksize 1 / 3, stride 1 / 2, C % 32 == 0 (bf16) /
+ * % 16 == 0 (fp32), Cout % 128 == 0; NSID_EINVAL otherwise); x / dx are the conv's input rows (B*H*W, C), dy its output rows
+ * (B*Ho*Wo, Cout). No atomics anywhere: a second call gives the same bits.
+ * conv2d_bwd_data: dx[(b*H + hi)*W + wi][c] = addend + sum_{kh,kw,o} dy[b][ho][wo][o] * w[o][kh][kw][c] over the (ho, wo) with
+ *   ho*stride - pad + kh == hi (wo alike): a gather, an implicit GEMM over the input rows through the forward's loop. wt: the
+ *   weight packed (C, ksize*ksize*Cout), wt[c][(kh*ksize + kw)*Cout + o] (tap-major, Cout fastest), of the activations' type. An
+ *   input pixel no output pixel reads is exactly 0 (+ addend). addend (dx's storage and layout) may be NULL. dx must not alias dy.
+ * conv2d_bwd_weight: dw[o][(kh*ksize + kw)*C + c] += sum_m dy[m][o] * x[gather(m, kh, kw)][c] in conv2d_fwd's packed layout, fp32.
+ *   The rows are split nsid_conv2d_wgrad_splits(B*Ho*Wo, Cout*ksize*ksize*C) ways through ws
+ *   (nsid_workspace_bytes("conv2d_bwd_weight", rows, weight elements) bytes; may be NULL when that is 0) and added in split order.
+ * col_stat: per-channel sum and sum of squares of rows x (M, C) with row pitch ldx (elements), per NSID_ROW_TILE rows, into
+ *   stat[2][nsid_row_tiles(M)][C] as nsid_bn_finalize reads it. C % 64 == 0. One launch of its own behind the conv2d.
+ * ibn_relu_bwd: backward of y = relu(IBN(r)) given dy, with batch statistics in the BatchNorm half (bn_scale = gamma * invstd,
+ *   bn_shift = beta - mean * bn_scale, bn_mean, bn_invstd: C/2 each, as nsid_bn_finalize leaves them). With g = dy * [y > 0]
+ *   (the mask recomputed from r with the forward's arithmetic) and xh = (r - mean) * invstd:
+ *   dr = gamma * invstd * (g - mean g - xh * mean(g xh)), the means over the clip's HW rows (channels [0, C/2), statistics
+ *   recomputed as in the forward; HW == 1 gives 0) or over all B*HW rows (channels [C/2, C)); d_in_gamma / d_bn_gamma += sum g xh,
+ *   d_in_beta / d_bn_beta += sum g, per-clip partial sums added in clip order. ws: nsid_workspace_bytes("ibn_relu_bwd", B, C) bytes.
+ *   dr may alias dy. Three launches.
+ * bn_add_relu_fwd: out = relu(scale3 * r3 + shift3 + identity), identity = scale_d * identity + shift_d when scale_d is given.
+ * relu_bwd: g = dy where y > 0, else 0 (n elements). */
+int nsid_conv2d_bwd_data(const void* dy, int B, int H, int W, int C, const void* wt, int w_dtype, const void* addend, void* dx,
+                         int Cout, int ksize, int stride, int act_dtype, void* stream);
+int nsid_conv2d_wgrad_splits(long M, long welems);
+int nsid_conv2d_bwd_weight(const void* dy, const void* x, int B, int H, int W, int C, float* dw, float* ws, int Cout, int ksize,
+                           int stride, int act_dtype, void* stream);
+int nsid_col_stat(const void* x, int ldx, int M, int C, float* stat, int dtype, void* stream);
+int nsid_ibn_relu_bwd(const void* dy, const void* r, int B, int HW, int C, const float* in_gamma, const float* in_beta, float eps,
+                      const float* bn_scale, const float* bn_shift, const float* bn_mean, const float* bn_invstd, void* dr, float* ws,
+                      float* d_in_gamma, float* d_in_beta, float* d_bn_gamma, float* d_bn_beta, int dtype, void* stream);
+int nsid_bn_add_relu_fwd(const void* r3, const float* scale3, const float* shift3, const void* identity, const float* scale_d,
+                         const float* shift_d, void* out, int M, int C, int dtype, void* stream);
+int nsid_relu_bwd(const void* dy, const void* y, void* g, long n, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

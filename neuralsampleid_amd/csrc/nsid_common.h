@@ -242,7 +242,8 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(aug_stft) X(aug_vocoder) X(aug_istft) X(aug_finish)   /* augment.hip: waveform augmentations, one launch per stage */ \
   X(conv2d_3x3) X(conv2d_1x1) X(ibn_relu) X(stem7_pool) X(gem_pool)   /* resnet.hip: the ResNet-IBN baseline's eval-mode forward */ \
   X(pair_ce) X(triplet) X(baseline_objective)   /* baseline_loss.hip: the baseline's training objective, one count per call */ \
-  X(gem_pool_bwd)         /* resnet.hip: backward of the GeM pooling */
+  X(gem_pool_bwd)         /* resnet.hip: backward of the GeM pooling */ \
+  X(conv2d_bwd_data) X(conv2d_bwd_weight) X(col_stat) X(ibn_relu_bwd) X(bn_add_relu) X(relu_bwd)   /* resnet.hip: training-mode residual blocks */
 
 enum NsidCounterKey {
 #define NSID_CNT_ENUM(name) NSID_C_##name,

@@ -1,7 +1,9 @@
-// Eval-mode forward of the ResNet-IBN baseline (encoder/resnet_ibn.py of the reference): the first 2-D convolutional network of
-// this library. Activations are channels-last rows (B*H*W, C), fp32 or bf16 storage, fp32 accumulation.
+// The ResNet-IBN baseline (encoder/resnet_ibn.py of the reference), the first 2-D convolutional network of this library: its eval-mode
+// forward, and the backward of its residual blocks (training mode: conv2d_kernel<T, true>, conv2d_wgrad_kernel, col_stat_kernel,
+// ibn_relu_bwd_kernel and the block tail, each described where it stands). Activations are channels-last rows (B*H*W, C), fp32 or
+// bf16 storage, fp32 accumulation.
 //
-//   conv2d_fwd_kernel  : Conv2d 3x3 (pad 1) / 1x1 (pad 0), stride 1 / 2, as an IMPLICIT GEMM on MFMA: out[m][o] = bias[o] +
+//   conv2d_kernel      : Conv2d 3x3 (pad 1) / 1x1 (pad 0), stride 1 / 2, as an IMPLICIT GEMM on MFMA: out[m][o] = bias[o] +
 //                        sum_{kh, kw, c} x[b][ho*s - pad + kh][wo*s - pad + kw][c] * wp[o][(kh*KW + kw)*C + c] (+ addend) (ReLU).
 //                        The im2col matrix is never formed: a thread keeps the (clip, row, column) of its two operand rows and
 //                        steps through (tap, channel chunk); a tap outside the image is staged as zeros (top, bottom, left and
@@ -37,8 +39,14 @@ struct ConvArgs {
   int B, H, W, C, Ho, Wo, Co, KW, taps, stride, pad, relu, M, tiles_n;
 };
 
-template <typename T>
-__global__ __launch_bounds__(256) void conv2d_fwd_kernel(const ConvArgs a) {
+// BWD = false: the forward above. BWD = true: the backward-data GATHER of the same convolution through the same loop. The roles are
+// swapped by the host: a.x = dy (B, a.H, a.W, a.C) is the conv's OUTPUT map, a.w the (Cin, taps * Cout) packing of pack_conv_bwd, the
+// rows written are the conv's INPUT pixels (a.Ho, a.Wo) with a.Co = Cin columns. Input pixel (hi, wi) meets tap (kh, kw) at output
+// pixel ((hi + pad - kh) / s, (wi + pad - kw) / s) where both divide and the pixel lies inside the map; every other tap is staged as
+// zeros, so a pixel no output pixel reads (three of four under a 1x1 stride-2 conv) comes out as exactly 0.0 (+ addend). a.Co need
+// not fill the last column tile: weight rows past it are staged as zeros and not stored.
+template <typename T, bool BWD>
+__global__ __launch_bounds__(256) void conv2d_kernel(const ConvArgs a) {
   constexpr bool BF = sizeof(T) == 2;
   constexpr int EPC = 16 / (int)sizeof(T);            // elements of a 16-byte chunk
   constexpr int BKE = CV_ROWB / (int)sizeof(T);       // reduction elements of a stage
@@ -59,6 +67,9 @@ __global__ __launch_bounds__(256) void conv2d_fwd_kernel(const ConvArgs a) {
   int hi0[2], wi0[2];
   bool aok[2];
   const T* wrow[2];
+  [[maybe_unused]] int clip[2];
+  [[maybe_unused]] bool wok[2];
+  [[maybe_unused]] const int sh = a.stride - 1;      // stride 1 or 2: the division is a shift
 #pragma unroll
   for (int q = 0; q < 2; ++q) {
     const int row = (tid >> 2) + 64 * q, m = m0 + row;
@@ -70,10 +81,19 @@ __global__ __launch_bounds__(256) void conv2d_fwd_kernel(const ConvArgs a) {
       ho = r / a.Wo;
       wo = r - ho * a.Wo;
     }
-    hi0[q] = ho * a.stride - a.pad;
-    wi0[q] = wo * a.stride - a.pad;
-    abase[q] = (((long)b * a.H + hi0[q]) * a.W + wi0[q]) * C + ch * EPC;
-    wrow[q] = w + (long)(n0 + row) * K + ch * EPC;
+    if constexpr (BWD) {
+      hi0[q] = ho + a.pad;
+      wi0[q] = wo + a.pad;
+      clip[q] = b;
+      abase[q] = ch * EPC;
+      wok[q] = n0 + row < a.Co;
+      wrow[q] = w + (long)min(n0 + row, a.Co - 1) * K + ch * EPC;
+    } else {
+      hi0[q] = ho * a.stride - a.pad;
+      wi0[q] = wo * a.stride - a.pad;
+      abase[q] = (((long)b * a.H + hi0[q]) * a.W + wi0[q]) * C + ch * EPC;
+      wrow[q] = w + (long)(n0 + row) * K + ch * EPC;
+    }
   }
 
   // Global loads go to registers one (bf16) or two (fp32) stages ahead of the MFMA block that uses them. Past the last stage the
@@ -84,11 +104,20 @@ __global__ __launch_bounds__(256) void conv2d_fwd_kernel(const ConvArgs a) {
   auto issue = [&](f32x4 (&sa)[2], f32x4 (&sb)[2]) {
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      const int hi = hi0[q] + ld_kh, wi = wi0[q] + ld_kw;
-      const bool ok = aok[q] && hi >= 0 && hi < a.H && wi >= 0 && wi < a.W;      // the conv's zero padding, in both dimensions
       sa[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (ok) sa[q] = *reinterpret_cast<const f32x4*>(x + abase[q] + ((long)ld_kh * a.W + ld_kw) * C + ld_c0);
-      sb[q] = *reinterpret_cast<const f32x4*>(wrow[q] + ld_k0);
+      if constexpr (BWD) {
+        const int th = hi0[q] - ld_kh, tw = wi0[q] - ld_kw;
+        const int hi = th >> sh, wi = tw >> sh;
+        const bool ok = aok[q] && th >= 0 && tw >= 0 && ((th | tw) & sh) == 0 && hi < a.H && wi < a.W;
+        if (ok) sa[q] = *reinterpret_cast<const f32x4*>(x + (((long)clip[q] * a.H + hi) * a.W + wi) * C + abase[q] + ld_c0);
+        sb[q] = *reinterpret_cast<const f32x4*>(wrow[q] + ld_k0);
+        if (!wok[q]) sb[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      } else {
+        const int hi = hi0[q] + ld_kh, wi = wi0[q] + ld_kw;
+        const bool ok = aok[q] && hi >= 0 && hi < a.H && wi >= 0 && wi < a.W;      // the conv's zero padding, in both dimensions
+        if (ok) sa[q] = *reinterpret_cast<const f32x4*>(x + abase[q] + ((long)ld_kh * a.W + ld_kw) * C + ld_c0);
+        sb[q] = *reinterpret_cast<const f32x4*>(wrow[q] + ld_k0);
+      }
     }
     if (++ld_st < nstage) {
       ld_k0 += BKE;
@@ -199,6 +228,9 @@ __global__ __launch_bounds__(256) void conv2d_fwd_kernel(const ConvArgs a) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
     const int n = n0 + wn0 + 16 * j + 4 * rq;
+    if constexpr (BWD) {
+      if (n >= a.Co) continue;
+    }
     f32x4 bj = {0.f, 0.f, 0.f, 0.f};
     if (a.bias != nullptr) bj = *reinterpret_cast<const f32x4*>(a.bias + n);
 #pragma unroll
@@ -255,6 +287,58 @@ __device__ __forceinline__ void load_rows(const T* x, int r, int HW, int C, floa
   }
 }
 
+// Instance-norm statistics of a workgroup's 64 channels over its clip's HW rows: the mean, then the biased variance around it (two
+// passes over the stored values, fixed summation order). Shared by the forward and the backward: the backward's ReLU mask is then
+// the forward's bit for bit. x points at (clip row 0, this thread's chunk column).
+template <typename T, int RL>
+__device__ __forceinline__ void ibn_in_stats(const T* x, int HW, int C, float eps, int tid, int rl, int cc, float (*red)[IBN_CW],
+                                             float (*stat)[IBN_CW], float (&mu)[Chunk<T>::N], float (&istd)[Chunk<T>::N]) {
+  constexpr int N = Chunk<T>::N;
+  float s[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) s[e] = 0.f;
+  for (int r = rl; r < HW; r += IBN_U * RL) {
+    float v[IBN_U][N];
+    load_rows<T, RL>(x, r, HW, C, v);
+#pragma unroll
+    for (int u = 0; u < IBN_U; ++u)
+#pragma unroll
+      for (int e = 0; e < N; ++e) s[e] += v[u][e];           // rows past the end were loaded as zeros
+  }
+#pragma unroll
+  for (int e = 0; e < N; ++e) red[rl][cc + e] = s[e];
+  __syncthreads();
+  if (tid < IBN_CW) {
+    float t = 0.f;
+    for (int g = 0; g < RL; ++g) t += red[g][tid];
+    stat[0][tid] = t / (float)HW;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < N; ++e) { mu[e] = stat[0][cc + e]; s[e] = 0.f; }
+  for (int r = rl; r < HW; r += IBN_U * RL) {
+    float v[IBN_U][N];
+    load_rows<T, RL>(x, r, HW, C, v);
+#pragma unroll
+    for (int u = 0; u < IBN_U; ++u) {
+      if (r + u * RL >= HW) break;
+#pragma unroll
+      for (int e = 0; e < N; ++e) { const float d = v[u][e] - mu[e]; s[e] = fmaf(d, d, s[e]); }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < N; ++e) red[rl][cc + e] = s[e];
+  __syncthreads();
+  if (tid < IBN_CW) {
+    float t = 0.f;
+    for (int g = 0; g < RL; ++g) t += red[g][tid];
+    stat[1][tid] = 1.f / sqrtf(t / (float)HW + eps);
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < N; ++e) istd[e] = stat[1][cc + e];
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void ibn_relu_kernel(const IbnArgs a) {
   constexpr int N = Chunk<T>::N;
@@ -269,50 +353,11 @@ __global__ __launch_bounds__(256) void ibn_relu_kernel(const IbnArgs a) {
   T* out = static_cast<T*>(a.out) + base;
   float mu[N], scale[N], shift[N];
   if (c0 < half) {                           // (uniform) instance norm: statistics of this clip's HW rows, two passes
-    float s[N];
-#pragma unroll
-    for (int e = 0; e < N; ++e) s[e] = 0.f;
-    for (int r = rl; r < a.HW; r += IBN_U * RL) {
-      float v[IBN_U][N];
-      load_rows<T, RL>(x, r, a.HW, a.C, v);
-#pragma unroll
-      for (int u = 0; u < IBN_U; ++u)
-#pragma unroll
-        for (int e = 0; e < N; ++e) s[e] += v[u][e];           // rows past the end were loaded as zeros
-    }
-#pragma unroll
-    for (int e = 0; e < N; ++e) red[rl][cc + e] = s[e];
-    __syncthreads();
-    if (tid < IBN_CW) {
-      float t = 0.f;
-      for (int g = 0; g < RL; ++g) t += red[g][tid];
-      stat[0][tid] = t / (float)a.HW;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < N; ++e) { mu[e] = stat[0][cc + e]; s[e] = 0.f; }
-    for (int r = rl; r < a.HW; r += IBN_U * RL) {
-      float v[IBN_U][N];
-      load_rows<T, RL>(x, r, a.HW, a.C, v);
-#pragma unroll
-      for (int u = 0; u < IBN_U; ++u) {
-        if (r + u * RL >= a.HW) break;
-#pragma unroll
-        for (int e = 0; e < N; ++e) { const float d = v[u][e] - mu[e]; s[e] = fmaf(d, d, s[e]); }
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < N; ++e) red[rl][cc + e] = s[e];
-    __syncthreads();
-    if (tid < IBN_CW) {
-      float t = 0.f;
-      for (int g = 0; g < RL; ++g) t += red[g][tid];
-      stat[1][tid] = 1.f / sqrtf(t / (float)a.HW + a.eps);
-    }
-    __syncthreads();
+    float istd[N];
+    ibn_in_stats<T, RL>(x, a.HW, a.C, a.eps, tid, rl, cc, red, stat, mu, istd);
 #pragma unroll
     for (int e = 0; e < N; ++e) {
-      scale[e] = a.gamma[c0 + cc + e] * stat[1][cc + e];
+      scale[e] = a.gamma[c0 + cc + e] * istd[e];
       shift[e] = a.beta[c0 + cc + e];
     }
   } else {                                   // eval-mode BatchNorm half: the given affine
@@ -463,6 +508,456 @@ __global__ __launch_bounds__(256) void gem_dp_sum_kernel(const float* __restrict
   if (threadIdx.x == 0) dp[0] = (float)((red[0] + red[1]) + (red[2] + red[3]));
 }
 
+// ---------------------------------------------------------------------------------------------------------------- conv weight gradient
+// dw[o][(kh*KW + kw)*C + c] += sum_m dy[m][o] * x[gather(m, kh, kw)][c]: the forward's packed layout. One workgroup per (row split,
+// 128 output channels, tap, 128 input channels); the reduction runs over the rows m, the strided dimension of both operands, so a
+// stage is KB rows x 128 columns of each operand as they lie in memory and the MFMA fragments come from transposing LDS reads
+// (bf16: ds_read_b64_tr_b16 with the row layout of gemm.hip's i/j-major tiles; fp32: one 4-byte read per MFMA operand, the row pitch
+// 16 banks past a multiple of 64 so that the four reduction rows of a read do not collide). A tap outside the image and the rows
+// past M are staged as zeros. Split over the rows: split sp writes its 128 x 128 tile into part[sp] (the whole dw layout per split),
+// conv2d_wgrad_sum_kernel adds the splits in order into dw: no atomics, two calls give the same bits. One split: straight into dw.
+struct ConvWgArgs {
+  const void* dy; const void* x; float* out;
+  int H, W, C, Ho, Wo, Co, KW, taps, stride, pad, M, tiles_c, splits, stages_per;
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void conv2d_wgrad_kernel(const ConvWgArgs a) {
+  constexpr bool BF = sizeof(T) == 2;
+  constexpr int KB = BF ? 32 : 16;                    // reduction rows of a stage
+  constexpr int EPC = 16 / (int)sizeof(T);
+  constexpr int CPR = 128 / EPC;                      // 16-byte chunks of a 128-column row: 16 (bf16) / 32 (fp32)
+  constexpr int RPP = 256 / CPR;                      // rows the 256 threads cover in one pass: 16 / 8 (two passes per stage)
+  constexpr int LD = BF ? 288 : 576;                  // LDS row pitch in bytes
+  constexpr int OPB = BF ? KB * LD + (KB / 8) * 128 : KB * LD;      // one operand of one stage
+  static_assert(KB == 2 * RPP, "a stage is two passes");
+  __shared__ __attribute__((aligned(16))) char lds[4 * OPB];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int lr = lane & 15, rq = lane >> 4;
+  const int wm0 = (wave >> 1) * 64, wn0 = (wave & 1) * 64;
+  const int sp = blockIdx.x;
+  int t = blockIdx.y;
+  const int tc = t % a.tiles_c;
+  t /= a.tiles_c;
+  const int tap = t % a.taps, to = t / a.taps;
+  const int kh = tap / a.KW, kw = tap - kh * a.KW;
+  const int o0 = to * 128, c0 = tc * 128;
+  const int cch = (tid % CPR) * EPC, rr = tid / CPR;
+  const bool cok = c0 + cch < a.C;
+  const T* dy = static_cast<const T*>(a.dy);
+  const T* x = static_cast<const T*>(a.x);
+  const int nst_all = (a.M + KB - 1) / KB;
+  const int st0 = sp * a.stages_per, st1 = min(st0 + a.stages_per, nst_all);
+  const unsigned HoWo = (unsigned)(a.Ho * a.Wo);
+
+  auto rowoff = [](int k) { return BF ? k * LD + (k >> 3) * 128 : k * LD; };
+  f32x4 ra[2], rb[2];
+  auto issue = [&](int st) {
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int m = st * KB + rr + RPP * q;
+      ra[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      rb[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (m < a.M) {
+        const unsigned b = (unsigned)m / HoWo, r = (unsigned)m - b * HoWo;
+        const int ho = (int)(r / (unsigned)a.Wo), wo = (int)r - ho * a.Wo;
+        const int hi = ho * a.stride - a.pad + kh, wi = wo * a.stride - a.pad + kw;
+        ra[q] = *reinterpret_cast<const f32x4*>(dy + (long)m * a.Co + o0 + cch);
+        if (cok && hi >= 0 && hi < a.H && wi >= 0 && wi < a.W)
+          rb[q] = *reinterpret_cast<const f32x4*>(x + (((long)b * a.H + hi) * a.W + wi) * a.C + c0 + cch);
+      }
+    }
+  };
+  auto commit = [&](int buf) {
+    char* dst = lds + buf * 2 * OPB;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int off = rowoff(rr + RPP * q) + cch * (int)sizeof(T);
+      *reinterpret_cast<f32x4*>(dst + off) = ra[q];
+      *reinterpret_cast<f32x4*>(dst + OPB + off) = rb[q];
+    }
+  };
+
+  f32x4 acc[4][4], tot[BF ? 1 : 4][BF ? 1 : 4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (!BF) tot[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+
+  auto compute = [&](int it) {
+    const char* la = lds + (it & 1) * 2 * OPB;
+    const char* lb = la + OPB;
+    if constexpr (BF) {
+      typedef bf16x4 __attribute__((address_space(3))) * lds_bf16x4_ptr;
+      // lane 4q + p of a 16-lane group addresses reduction row 8 rq + q (then + 4), columns 4p .. 4p + 3 of the fragment's 16; the
+      // hardware hands lane lr column lr of those rows (all 64 lanes are active here: the loop is uniform)
+      const int fo = (8 * rq + (lr >> 2)) * LD + rq * 128 + 8 * (lr & 3);
+      bf16x8 fa[4], fb[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const char* p = la + fo + 2 * (wm0 + 16 * i);
+        const bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(p));
+        const bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(p + 4 * LD));
+        fa[i] = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const char* p = lb + fo + 2 * (wn0 + 16 * j);
+        const bf16x4 t0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(p));
+        const bf16x4 t1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((lds_bf16x4_ptr)(p + 4 * LD));
+        fb[j] = __builtin_shufflevector(t0, t1, 0, 1, 2, 3, 4, 5, 6, 7);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fb[j], fa[i], acc[i][j], 0, 0, 0);
+    } else {
+#pragma unroll
+      for (int s = 0; s < 4; ++s) {
+        float fa[4], fb[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) fa[i] = *reinterpret_cast<const float*>(la + (4 * s + rq) * LD + 4 * (wm0 + 16 * i + lr));
+#pragma unroll
+        for (int j = 0; j < 4; ++j) fb[j] = *reinterpret_cast<const float*>(lb + (4 * s + rq) * LD + 4 * (wn0 + 16 * j + lr));
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(fb[j], fa[i], acc[i][j], 0, 0, 0);
+      }
+      if ((it % CV_FLUSH) == CV_FLUSH - 1) {           // uniform: as in the forward, every 256 reduction rows
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            tot[i][j] += acc[i][j];
+            acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+      }
+    }
+  };
+
+  if (st0 < st1) {                                      // uniform
+    issue(st0);
+    commit(0);
+    __syncthreads();
+    for (int st = st0; st < st1; ++st) {
+      const bool more = st + 1 < st1;
+      if (more) issue(st + 1);                          // lands under the MFMA block below
+      compute(st - st0);
+      if (more) commit((st + 1 - st0) & 1);
+      __syncthreads();
+    }
+  }
+
+  // lane (lr, rq), register r of acc[i][j]: output channel o = 16 i + lr, input channel c = 16 j + 4 rq + r (operands swapped as in
+  // the forward: 16 contiguous bytes per lane)
+  const long K = (long)a.taps * a.C;
+  float* out = a.out + (a.splits > 1 ? (long)sp * a.Co * K : 0L);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int c = c0 + wn0 + 16 * j + 4 * rq;
+    if (c >= a.C) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int o = o0 + wm0 + 16 * i + lr;
+      f32x4 v = acc[i][j];
+      if constexpr (!BF) v += tot[i][j];
+      f32x4* p = reinterpret_cast<f32x4*>(out + (long)o * K + (long)tap * a.C + c);
+      if (a.splits > 1) *p = v; else *p += v;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void conv2d_wgrad_sum_kernel(const float* __restrict__ part, int splits, long n4, float* __restrict__ dw) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n4) return;
+  const f32x4* p = reinterpret_cast<const f32x4*>(part) + i;
+  f32x4 s = p[0];
+  for (int sp = 1; sp < splits; ++sp) s += p[(long)sp * n4];      // fixed order
+  reinterpret_cast<f32x4*>(dw)[i] += s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- column statistics
+// Per-channel sum and sum of squares of the stored rows (M, C) with row pitch ld, one workgroup per (64 channels, 128-row tile), into
+// the [2][row tiles][C] layout bn_finalize_kernel reads: the batch statistics of a conv2d output (bn2, the stride-2 downsample) and of
+// the BatchNorm half of the IBN (a column slice of conv1's output).
+template <typename T>
+__global__ __launch_bounds__(256) void col_stat_kernel(const T* __restrict__ x, long ld, int M, int C, float* __restrict__ stat, int tiles) {
+  __shared__ float red[2][4][64];
+  const int tid = threadIdx.x, c = tid & 63, g = tid >> 6;
+  const int c0 = blockIdx.x * 64, tile = blockIdx.y;
+  const int r1 = min(M, (tile + 1) * NSID_ROW_TILE);
+  float s = 0.f, q = 0.f;
+  for (int r = tile * NSID_ROW_TILE + g; r < r1; r += 4) {
+    const float v = (float)x[(long)r * ld + c0 + c];
+    s += v;
+    q = fmaf(v, v, q);
+  }
+  red[0][g][c] = s;
+  red[1][g][c] = q;
+  __syncthreads();
+  if (tid < 64) {
+    stat[(long)tile * C + c0 + tid] = ((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid];
+    stat[((long)tiles + tile) * C + c0 + tid] = ((red[1][0][tid] + red[1][1][tid]) + red[1][2][tid]) + red[1][3][tid];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- IBN + ReLU backward
+// y = relu(IBN(r)). With g = dy * [y > 0] and xh = (r - mean) * invstd, over the rows the statistics were taken over (the clip's HW
+// rows for the instance-norm half, all B * HW rows for the BatchNorm half):
+//   dr = gamma * invstd * (g - mean(g) - xh * mean(g * xh)),   dgamma = sum g * xh,   dbeta = sum g
+// ibn_relu_bwd_kernel, one workgroup per (clip, 64 channels) as in the forward: the instance-norm half recomputes its statistics
+// with the forward's code, reduces and writes dr; both halves leave their per-clip (sum g, sum g xh) in part[2][B][C].
+// ibn_bwd_finalize_kernel adds the clips in order (fp64) into the four parameter gradients and leaves the BatchNorm half's two means;
+// ibn_bwd_bn_apply_kernel writes the BatchNorm half's dr. The mask is fmaf(r - mu, scale, shift) > 0 exactly as the forward evaluates it.
+struct IbnBwdArgs {
+  const void* dy; const void* r; void* dr;
+  const float* gamma; const float* beta; const float* sc; const float* sh; const float* mean; const float* invstd;
+  float* part; float* coef;
+  int B, HW, C;
+  float eps;
+};
+
+template <typename T, int RL>
+__device__ __forceinline__ void ibn_col_sums(const float (&s0)[Chunk<T>::N], const float (&s1)[Chunk<T>::N], int tid, int rl, int cc,
+                                             float (*red)[IBN_CW], float (*stat)[IBN_CW]) {
+  constexpr int N = Chunk<T>::N;
+#pragma unroll
+  for (int e = 0; e < N; ++e) red[rl][cc + e] = s0[e];
+  __syncthreads();
+  if (tid < IBN_CW) {
+    float t = 0.f;
+    for (int g = 0; g < RL; ++g) t += red[g][tid];
+    stat[0][tid] = t;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int e = 0; e < N; ++e) red[rl][cc + e] = s1[e];
+  __syncthreads();
+  if (tid < IBN_CW) {
+    float t = 0.f;
+    for (int g = 0; g < RL; ++g) t += red[g][tid];
+    stat[1][tid] = t;
+  }
+  __syncthreads();
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ibn_relu_bwd_kernel(const IbnBwdArgs a) {
+  constexpr int N = Chunk<T>::N;
+  constexpr int CPR = IBN_CW / N;
+  constexpr int RL = 256 / CPR;
+  __shared__ float red[RL][IBN_CW];
+  __shared__ float stat[2][IBN_CW];
+  const int tid = threadIdx.x, cc = (tid % CPR) * N, rl = tid / CPR;
+  const int c0 = blockIdx.x * IBN_CW, half = a.C / 2, b = blockIdx.y;
+  const long base = (long)b * a.HW * a.C + c0 + cc;
+  const T* x = static_cast<const T*>(a.r) + base;
+  const T* dy = static_cast<const T*>(a.dy) + base;
+  T* dr = static_cast<T*>(a.dr) + base;
+  const bool in_half = c0 < half;            // uniform
+  float mu[N], istd[N], scale[N], shift[N], mmu[N];       // mmu: what the forward subtracts before its fmaf (the mask's arithmetic)
+  if (in_half) {
+    ibn_in_stats<T, RL>(x, a.HW, a.C, a.eps, tid, rl, cc, red, stat, mu, istd);
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      scale[e] = a.gamma[c0 + cc + e] * istd[e];
+      shift[e] = a.beta[c0 + cc + e];
+      mmu[e] = mu[e];
+    }
+  } else {
+#pragma unroll
+    for (int e = 0; e < N; ++e) {
+      const int c = c0 - half + cc + e;
+      mu[e] = a.mean[c];
+      istd[e] = a.invstd[c];
+      scale[e] = a.sc[c];
+      shift[e] = a.sh[c];
+      mmu[e] = 0.f;
+    }
+  }
+  float s0[N], s1[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) s0[e] = s1[e] = 0.f;
+  for (int r = rl; r < a.HW; r += IBN_U * RL) {
+    float v[IBN_U][N], d[IBN_U][N];
+    load_rows<T, RL>(x, r, a.HW, a.C, v);
+    load_rows<T, RL>(dy, r, a.HW, a.C, d);              // rows past the end: d = 0, so they add nothing
+#pragma unroll
+    for (int u = 0; u < IBN_U; ++u)
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const float g = fmaf(v[u][e] - mmu[e], scale[e], shift[e]) > 0.f ? d[u][e] : 0.f;
+        s0[e] += g;
+        s1[e] = fmaf(g, (v[u][e] - mu[e]) * istd[e], s1[e]);
+      }
+  }
+  ibn_col_sums<T, RL>(s0, s1, tid, rl, cc, red, stat);
+  if (tid < IBN_CW) {
+    a.part[(long)b * a.C + c0 + tid] = stat[0][tid];
+    a.part[((long)a.B + b) * a.C + c0 + tid] = stat[1][tid];
+  }
+  if (!in_half) return;                       // uniform
+  float mg[N], mgx[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    mg[e] = stat[0][cc + e] / (float)a.HW;
+    mgx[e] = stat[1][cc + e] / (float)a.HW;
+  }
+  for (int r = rl; r < a.HW; r += IBN_U * RL) {
+    float v[IBN_U][N], d[IBN_U][N];
+    load_rows<T, RL>(x, r, a.HW, a.C, v);
+    load_rows<T, RL>(dy, r, a.HW, a.C, d);
+#pragma unroll
+    for (int u = 0; u < IBN_U; ++u) {
+      if (r + u * RL >= a.HW) break;
+      float o[N];
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const float g = fmaf(v[u][e] - mmu[e], scale[e], shift[e]) > 0.f ? d[u][e] : 0.f;
+        o[e] = scale[e] * (g - mg[e] - (v[u][e] - mu[e]) * istd[e] * mgx[e]);
+      }
+      Chunk<T>::store(dr + (long)(r + u * RL) * a.C, o);
+    }
+  }
+}
+
+// one thread per channel: the clips' partial sums in clip order, fp64
+__global__ __launch_bounds__(128) void ibn_bwd_finalize_kernel(const float* __restrict__ part, int B, int HW, int C, float* dg_in,
+                                                               float* db_in, float* dg_bn, float* db_bn, float* __restrict__ coef) {
+  const int c = blockIdx.x * 128 + threadIdx.x;
+  if (c >= C) return;
+  const float* p0 = part + c;
+  const float* p1 = part + (long)B * C + c;
+  double sg = 0.0, sgx = 0.0;
+  constexpr int UB = 8;                       // loads of a batch issue before the first add; the order of the adds is the clip order
+  int b = 0;
+  for (; b + UB <= B; b += UB) {
+    float va[UB], vb[UB];
+#pragma unroll
+    for (int u = 0; u < UB; ++u) { va[u] = p0[(long)(b + u) * C]; vb[u] = p1[(long)(b + u) * C]; }
+#pragma unroll
+    for (int u = 0; u < UB; ++u) { sg += (double)va[u]; sgx += (double)vb[u]; }
+  }
+  for (; b < B; ++b) { sg += (double)p0[(long)b * C]; sgx += (double)p1[(long)b * C]; }
+  const int half = C / 2;
+  if (c < half) {
+    dg_in[c] += (float)sgx;
+    db_in[c] += (float)sg;
+  } else {
+    dg_bn[c - half] += (float)sgx;
+    db_bn[c - half] += (float)sg;
+    const double M = (double)B * (double)HW;
+    coef[c - half] = (float)(sg / M);
+    coef[half + c - half] = (float)(sgx / M);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void ibn_bwd_bn_apply_kernel(const IbnBwdArgs a) {
+  constexpr int N = Chunk<T>::N;
+  constexpr int CPR = IBN_CW / N;
+  constexpr int RL = 256 / CPR;
+  const int tid = threadIdx.x, cc = (tid % CPR) * N, rl = tid / CPR;
+  const int half = a.C / 2, ch0 = blockIdx.x * IBN_CW + cc;          // channel of the BatchNorm half
+  const long base = (long)blockIdx.y * a.HW * a.C + half + ch0;
+  const T* x = static_cast<const T*>(a.r) + base;
+  const T* dy = static_cast<const T*>(a.dy) + base;
+  T* dr = static_cast<T*>(a.dr) + base;
+  float mu[N], istd[N], scale[N], shift[N], mg[N], mgx[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    mu[e] = a.mean[ch0 + e];
+    istd[e] = a.invstd[ch0 + e];
+    scale[e] = a.sc[ch0 + e];
+    shift[e] = a.sh[ch0 + e];
+    mg[e] = a.coef[ch0 + e];
+    mgx[e] = a.coef[half + ch0 + e];
+  }
+  for (int r = rl; r < a.HW; r += IBN_U * RL) {
+    float v[IBN_U][N], d[IBN_U][N];
+    load_rows<T, RL>(x, r, a.HW, a.C, v);
+    load_rows<T, RL>(dy, r, a.HW, a.C, d);
+#pragma unroll
+    for (int u = 0; u < IBN_U; ++u) {
+      if (r + u * RL >= a.HW) break;
+      float o[N];
+#pragma unroll
+      for (int e = 0; e < N; ++e) {
+        const float g = fmaf(v[u][e] - 0.f, scale[e], shift[e]) > 0.f ? d[u][e] : 0.f;
+        o[e] = scale[e] * (g - mg[e] - (v[u][e] - mu[e]) * istd[e] * mgx[e]);
+      }
+      Chunk<T>::store(dr + (long)(r + u * RL) * a.C, o);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- block tail
+// out = relu(sc3 * r3 + sh3 + identity), identity = scd * rd + shd (the downsample's BatchNorm) or the block's input as it is
+// (scd == nullptr): the tail of a training-mode block, where bn3's affine comes from batch statistics and cannot be folded.
+// Every thread keeps ONE column chunk for the whole kernel (the launch makes the thread count a multiple of the chunks per row, as
+// nsid_bn_bwd_apply does), so the four per-channel vectors are loaded once and U rows are in flight per iteration.
+template <typename T, int U>
+__global__ __launch_bounds__(256) void bn_add_relu_kernel(const T* __restrict__ r3, const float* __restrict__ sc3,
+                                                          const float* __restrict__ sh3, const T* __restrict__ idn,
+                                                          const float* __restrict__ scd, const float* __restrict__ shd,
+                                                          T* __restrict__ out, long rows, int CV) {
+  constexpr int N = Chunk<T>::N;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x, total = (long)gridDim.x * 256;
+  const int cq = (int)(t % CV), c = cq * N;
+  const long rstep = total / CV;                  // total % CV == 0 (host)
+  const bool ds = scd != nullptr;                 // uniform
+  float a3[N], b3[N], ad[N], bd[N];
+#pragma unroll
+  for (int e = 0; e < N; ++e) {
+    a3[e] = sc3[c + e];
+    b3[e] = sh3[c + e];
+    ad[e] = ds ? scd[c + e] : 1.f;
+    bd[e] = ds ? shd[c + e] : 0.f;
+  }
+  for (long row = t / CV; row < rows; row += U * rstep) {
+    float v[U][N], w[U][N];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long rr = row + u * rstep;
+      if (rr < rows) {
+        Chunk<T>::load(r3 + (rr * CV + cq) * N, v[u]);
+        Chunk<T>::load(idn + (rr * CV + cq) * N, w[u]);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long rr = row + u * rstep;
+      if (rr < rows) {
+        float o[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+          const float id = ds ? fmaf(ad[e], w[u][e], bd[e]) : w[u][e];
+          o[e] = nsid_act(fmaf(a3[e], v[u][e], b3[e]) + id, NSID_ACT_RELU);
+        }
+        Chunk<T>::store(out + (rr * CV + cq) * N, o);
+      }
+    }
+  }
+}
+
+// g = dy where the stored output y is positive, else 0: the gradient behind that ReLU, shared by the main branch and the shortcut
+template <typename T>
+__global__ __launch_bounds__(256) void relu_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ y, T* __restrict__ g, long nchunks) {
+  constexpr int N = Chunk<T>::N;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nchunks; i += (long)gridDim.x * 256) {
+    float d[N], v[N];
+    Chunk<T>::load(dy + i * N, d);
+    Chunk<T>::load(y + i * N, v);
+#pragma unroll
+    for (int e = 0; e < N; ++e) d[e] = v[e] > 0.f ? d[e] : 0.f;
+    Chunk<T>::store(g + i * N, d);
+  }
+}
+
 }  // namespace
 
 extern "C" int nsid_conv2d_fwd(const void* x, int B, int H, int W, int C, const void* w, int w_dtype, const float* bias,
@@ -489,7 +984,7 @@ extern "C" int nsid_conv2d_fwd(const void* x, int B, int H, int W, int C, const 
   NSID_REQUIRE(wgs < (1L << 31) - 1);
   nsid_count(ksize == 3 ? NSID_C_conv2d_3x3 : NSID_C_conv2d_1x1);
   NSID_DISPATCH_DTYPE(act_dtype, T,
-                      NSID_LAUNCH(conv2d_fwd_kernel<T>, dim3((unsigned)wgs), dim3(256), 0, static_cast<hipStream_t>(stream), a));
+                      NSID_LAUNCH((conv2d_kernel<T, false>), dim3((unsigned)wgs), dim3(256), 0, static_cast<hipStream_t>(stream), a));
   return nsid_launch_status();
 }
 
@@ -539,5 +1034,151 @@ extern "C" int nsid_gem_pool_bwd(const void* x, const float* dy, int B, int HW, 
   NSID_DISPATCH_DTYPE(x_dtype, T, NSID_LAUNCH(gem_pool_bwd_kernel<T>, dim3(C / 64, B), dim3(256), 0, s, static_cast<const T*>(x), dy,
                                               HW, C, p, eps, dx, dp_part));
   NSID_LAUNCH(gem_dp_sum_kernel, dim3(1), dim3(256), 0, s, dp_part, B * (C / 64), dp);
+  return nsid_launch_status();
+}
+
+// ---- training: backward of the convolution and of IBN + ReLU, the batch statistics of a conv2d output, the block tail
+extern "C" int nsid_conv2d_bwd_data(const void* dy, int B, int H, int W, int C, const void* wt, int w_dtype, const void* addend,
+                                    void* dx, int Cout, int ksize, int stride, int act_dtype, void* stream) {
+  NSID_REQUIRE(dy && wt && dx && B > 0 && H > 0 && W > 0 && C > 0 && Cout > 0 && NSID_DTYPE_OK(act_dtype));
+  NSID_REQUIRE(w_dtype == act_dtype);
+  NSID_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2));
+  NSID_REQUIRE(C % (act_dtype == NSID_BF16 ? 32 : 16) == 0 && Cout % CV_BN == 0);
+  NSID_REQUIRE(nsid_aligned16(dy) && nsid_aligned16(wt) && nsid_aligned16(dx) && nsid_aligned16(addend));
+  const int pad = ksize / 2;
+  ConvArgs a{};                                  // the roles of the two maps are swapped: see conv2d_kernel<T, true>
+  a.x = dy; a.w = wt; a.bias = nullptr; a.addend = addend; a.out = dx;
+  a.B = B;
+  a.H = (H + 2 * pad - ksize) / stride + 1;      // the map that is gathered from: the conv's output
+  a.W = (W + 2 * pad - ksize) / stride + 1;
+  a.C = Cout;                                    // the reduction runs over (tap, output channel)
+  a.Ho = H; a.Wo = W; a.Co = C;                  // the rows that are written: the conv's input
+  a.KW = ksize; a.taps = ksize * ksize; a.stride = stride; a.pad = pad;
+  a.relu = 0;
+  const long M = (long)B * H * W;
+  NSID_REQUIRE(M < (1L << 31) / 2);
+  a.M = (int)M;
+  a.tiles_n = (C + CV_BN - 1) / CV_BN;
+  const long wgs = ((M + CV_BM - 1) / CV_BM) * a.tiles_n;
+  NSID_REQUIRE(wgs < (1L << 31) - 1);
+  nsid_count(NSID_C_conv2d_bwd_data);
+  NSID_DISPATCH_DTYPE(act_dtype, T,
+                      NSID_LAUNCH((conv2d_kernel<T, true>), dim3((unsigned)wgs), dim3(256), 0, static_cast<hipStream_t>(stream), a));
+  return nsid_launch_status();
+}
+
+// row splits of nsid_conv2d_bwd_weight: enough workgroups for two per CU, at least 256 rows each; a function of the output rows and
+// the weight elements alone, so that nsid_workspace_bytes can answer from those two
+extern "C" int nsid_conv2d_wgrad_splits(long M, long welems) {
+  const long tiles = welems / (128 * 128) > 0 ? welems / (128 * 128) : 1;
+  long s = (512 + tiles - 1) / tiles;
+  const long cap = (M + 255) / 256;
+  if (s > cap) s = cap;
+  if (s > 64) s = 64;
+  return (int)(s < 1 ? 1 : s);
+}
+
+extern "C" int nsid_conv2d_bwd_weight(const void* dy, const void* x, int B, int H, int W, int C, float* dw, float* ws, int Cout,
+                                      int ksize, int stride, int act_dtype, void* stream) {
+  NSID_REQUIRE(dy && x && dw && B > 0 && H > 0 && W > 0 && C > 0 && Cout > 0 && NSID_DTYPE_OK(act_dtype));
+  NSID_REQUIRE((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2));
+  NSID_REQUIRE(C % (act_dtype == NSID_BF16 ? 32 : 16) == 0 && Cout % CV_BN == 0);
+  NSID_REQUIRE(nsid_aligned16(dy) && nsid_aligned16(x) && nsid_aligned16(dw) && nsid_aligned16(ws));
+  ConvWgArgs a{};
+  a.dy = dy; a.x = x;
+  a.H = H; a.W = W; a.C = C; a.Co = Cout;
+  a.KW = ksize; a.taps = ksize * ksize; a.stride = stride; a.pad = ksize / 2;
+  a.Ho = (H + 2 * a.pad - ksize) / stride + 1;
+  a.Wo = (W + 2 * a.pad - ksize) / stride + 1;
+  const long M = (long)B * a.Ho * a.Wo;
+  NSID_REQUIRE(M < (1L << 31) / 2 && (long)B * H * W < (1L << 31) / 2);
+  a.M = (int)M;
+  a.tiles_c = (C + 127) / 128;
+  const long welems = (long)Cout * a.taps * C;
+  a.splits = nsid_conv2d_wgrad_splits(M, welems);
+  NSID_REQUIRE(a.splits == 1 || ws != nullptr);
+  const int KB = act_dtype == NSID_BF16 ? 32 : 16;
+  const int nst = (int)((M + KB - 1) / KB);
+  a.stages_per = (nst + a.splits - 1) / a.splits;
+  a.out = a.splits > 1 ? ws : dw;
+  const long tiles = (long)(Cout / 128) * a.taps * a.tiles_c;
+  NSID_REQUIRE(tiles <= 65535);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  nsid_count(NSID_C_conv2d_bwd_weight);
+  NSID_DISPATCH_DTYPE(act_dtype, T, NSID_LAUNCH(conv2d_wgrad_kernel<T>, dim3(a.splits, (unsigned)tiles), dim3(256), 0, s, a));
+  if (a.splits > 1) {
+    const long n4 = welems / 4;
+    NSID_LAUNCH(conv2d_wgrad_sum_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, ws, a.splits, n4, dw);
+  }
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_col_stat(const void* x, int ldx, int M, int C, float* stat, int dtype, void* stream) {
+  NSID_REQUIRE(x && stat && M > 0 && C > 0 && C % 64 == 0 && ldx >= C && NSID_DTYPE_OK(dtype));
+  const int tiles = (M + NSID_ROW_TILE - 1) / NSID_ROW_TILE;
+  NSID_REQUIRE(tiles <= 65535);
+  nsid_count(NSID_C_col_stat);
+  NSID_DISPATCH_DTYPE(dtype, T, NSID_LAUNCH(col_stat_kernel<T>, dim3(C / 64, tiles), dim3(256), 0, static_cast<hipStream_t>(stream),
+                                            static_cast<const T*>(x), (long)ldx, M, C, stat, tiles));
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_ibn_relu_bwd(const void* dy, const void* r, int B, int HW, int C, const float* in_gamma, const float* in_beta,
+                                 float eps, const float* bn_scale, const float* bn_shift, const float* bn_mean,
+                                 const float* bn_invstd, void* dr, float* ws, float* d_in_gamma, float* d_in_beta, float* d_bn_gamma,
+                                 float* d_bn_beta, int dtype, void* stream) {
+  NSID_REQUIRE(dy && r && dr && ws && in_gamma && in_beta && bn_scale && bn_shift && bn_mean && bn_invstd);
+  NSID_REQUIRE(d_in_gamma && d_in_beta && d_bn_gamma && d_bn_beta && B > 0 && B <= 65535 && HW > 0 && C > 0);
+  NSID_REQUIRE(NSID_DTYPE_OK(dtype) && C % (2 * IBN_CW) == 0 && eps >= 0.f);
+  NSID_REQUIRE(nsid_aligned16(dy) && nsid_aligned16(r) && nsid_aligned16(dr));
+  IbnBwdArgs a{};
+  a.dy = dy; a.r = r; a.dr = dr; a.gamma = in_gamma; a.beta = in_beta; a.sc = bn_scale; a.sh = bn_shift; a.mean = bn_mean;
+  a.invstd = bn_invstd; a.part = ws; a.coef = ws + 2L * B * C;
+  a.B = B; a.HW = HW; a.C = C; a.eps = eps;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  nsid_count(NSID_C_ibn_relu_bwd);
+  NSID_DISPATCH_DTYPE(dtype, T, NSID_LAUNCH(ibn_relu_bwd_kernel<T>, dim3(C / IBN_CW, B), dim3(256), 0, s, a));
+  NSID_LAUNCH(ibn_bwd_finalize_kernel, dim3((C + 127) / 128), dim3(128), 0, s, a.part, B, HW, C, d_in_gamma, d_in_beta, d_bn_gamma,
+              d_bn_beta, a.coef);
+  NSID_DISPATCH_DTYPE(dtype, T, NSID_LAUNCH(ibn_bwd_bn_apply_kernel<T>, dim3(C / 2 / IBN_CW, B), dim3(256), 0, s, a));
+  return nsid_launch_status();
+}
+
+static inline unsigned rn_stream_grid(long nchunks) {
+  const long b = (nchunks + 255) / 256;
+  return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b));         // capped, grid-stride
+}
+
+extern "C" int nsid_bn_add_relu_fwd(const void* r3, const float* scale3, const float* shift3, const void* identity,
+                                    const float* scale_d, const float* shift_d, void* out, int M, int C, int dtype, void* stream) {
+  NSID_REQUIRE(r3 && scale3 && shift3 && identity && out && M > 0 && C > 0 && NSID_DTYPE_OK(dtype));
+  NSID_REQUIRE((scale_d == nullptr) == (shift_d == nullptr) && C % (dtype == NSID_BF16 ? 8 : 4) == 0);
+  NSID_REQUIRE(nsid_aligned16(r3) && nsid_aligned16(identity) && nsid_aligned16(out));
+  nsid_count(NSID_C_bn_add_relu);
+  NSID_DISPATCH_DTYPE(dtype, T, {
+    constexpr int U = 4;
+    const int CV = C / Chunk<T>::N;
+    const long nchunks = (long)M * CV;
+    int g0 = CV, d256 = 256;                        // thread count: a multiple of the chunks per row
+    while (d256 % 2 == 0 && g0 % 2 == 0) { d256 /= 2; g0 /= 2; }          // g0 = CV / gcd(CV, 256)
+    long want = (nchunks + 256L * U - 1) / (256L * U);
+    if (want > 2048) want = 2048;                   // this pass runs alone on its stream: it may take every wave slot
+    const long grid = (want + g0 - 1) / g0 * g0;
+    NSID_LAUNCH((bn_add_relu_kernel<T, U>), dim3((unsigned)grid), dim3(256), 0, static_cast<hipStream_t>(stream),
+                static_cast<const T*>(r3), scale3, shift3, static_cast<const T*>(identity), scale_d, shift_d, static_cast<T*>(out),
+                (long)M, CV);
+  });
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_relu_bwd(const void* dy, const void* y, void* g, long n, int dtype, void* stream) {
+  NSID_REQUIRE(dy && y && g && n > 0 && NSID_DTYPE_OK(dtype) && n % (dtype == NSID_BF16 ? 8 : 4) == 0);
+  NSID_REQUIRE(nsid_aligned16(dy) && nsid_aligned16(y) && nsid_aligned16(g));
+  nsid_count(NSID_C_relu_bwd);
+  NSID_DISPATCH_DTYPE(dtype, T, {
+    const long nchunks = n / Chunk<T>::N;
+    NSID_LAUNCH(relu_bwd_kernel<T>, dim3(rn_stream_grid(nchunks)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                static_cast<const T*>(dy), static_cast<const T*>(y), static_cast<T*>(g), nchunks);
+  });
   return nsid_launch_status();
 }

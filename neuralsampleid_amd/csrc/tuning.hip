@@ -71,11 +71,13 @@ extern "C" int nsid_row_tiles(int M);
 extern "C" int nsid_sumsq_blocks(long n);
 extern "C" size_t nsid_ntxent_ws_floats(int Bg);
 extern "C" size_t nsid_baseline_loss_ws_floats(int M, int D);
+extern "C" int nsid_conv2d_wgrad_splits(long M, long welems);
 extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
   if (op == nullptr || rows < 0 || cols < 0) return -1;
   static const char* const kNone[] = {"knn_graph", "mr_aggregate", "linear", "linear_bwd_data", "linear_bwd_weight", "downsample3",
                                       "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused",
-                                      "conv2d", "ibn_relu", "stem7_pool", "gem_pool"};
+                                      "conv2d", "ibn_relu", "stem7_pool", "gem_pool", "conv2d_bwd_data", "col_stat", "bn_add_relu",
+                                      "relu_bwd"};
   for (const char* n : kNone)
     if (strcmp(op, n) == 0) return 0;
   if (strcmp(op, "bn_stat") == 0)            // [2][row tiles][cols] fp32 partial sums of a rows x cols layer (forward and backward)
@@ -86,6 +88,12 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
     return (long)(nsid_baseline_loss_ws_floats((int)rows, (int)cols) * sizeof(float));
   if (strcmp(op, "gem_pool_bwd") == 0)       // rows = clips, cols = channels
     return rows * ((cols + 63) / 64) * (long)sizeof(float);
+  if (strcmp(op, "conv2d_bwd_weight") == 0) {    // rows = output rows B*Ho*Wo, cols = weight elements Cout*k*k*C: one dw per row split
+    const long splits = nsid_conv2d_wgrad_splits(rows, cols);
+    return splits > 1 ? splits * cols * (long)sizeof(float) : 0;
+  }
+  if (strcmp(op, "ibn_relu_bwd") == 0)       // rows = clips, cols = channels: [2][clips][C] partial sums + the BatchNorm half's two means
+    return (2L * rows * cols + cols) * (long)sizeof(float);
   if (strcmp(op, "sumsq") == 0)              // rows = elements of the flat gradient
     return (long)nsid_sumsq_blocks(rows) * (long)sizeof(float);
   if (strcmp(op, "flat_l2_topk") == 0)       // rows = query rows, cols = database rows; for k = 64

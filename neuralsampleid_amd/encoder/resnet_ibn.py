@@ -10,9 +10,21 @@ ResidualIBN block:
     conv2 3x3 stride s, bn2 folded (no activation)                          nsid_conv2d_fwd
     relu(conv3 1x1 with bn3 folded + identity)                              nsid_conv2d_fwd (1x1 form: addend + ReLU epilogue)
 Packed / folded weights and their bf16 shadows are cached by ops.folded_conv_bn (parameter versions and state epochs in the key), so
-a load_state_dict is seen by the next forward. Training mode and CPU tensors raise: the backward of the convolution and norm kernels does
-not exist. What does exist is everything behind the last convolution: ResNetIBN.head_train (GeM pooling and embedding head, forward
-and backward) and the losses of simclr/triplet.py."""
+a load_state_dict is seen by the next forward. The module forward raises in training mode and on CPU tensors.
+
+Training exists from the stem's output rows on: ResidualIBN.train_rows (one autograd.Function per block: batch statistics in all
+four BatchNorms, running statistics updated as nn.BatchNorm2d does, nothing folded) and ResNetIBN.trunk_train (the eight blocks and
+head_train). Per block, forward / backward:
+    conv1 1x1 (raw r1)                     nsid_linear_fwd                      / nsid_linear_bwd_weight, nsid_linear_bwd_data
+    BN-half statistics of r1               nsid_col_stat, nsid_bn_finalize
+    IBN + ReLU -> y1                       nsid_ibn_relu_fwd                    / nsid_ibn_relu_bwd (y1 is recomputed from r1)
+    conv2 3x3 stride s (raw r2)            nsid_conv2d_fwd                      / nsid_conv2d_bwd_weight, nsid_conv2d_bwd_data
+    bn2 statistics                         nsid_col_stat, nsid_bn_finalize      / nsid_bn_bwd_*
+    conv3 1x1 on bn2(r2) (applied on load) nsid_linear_fwd (statistics epilogue), nsid_bn_finalize / the row-GEMM backward kernels
+    downsample 1x1 stride s (raw rd)       nsid_linear_fwd (s = 1) / nsid_conv2d_fwd + nsid_col_stat (s = 2), nsid_bn_finalize
+    relu(bn3(r3) + bn_d(rd) or x)          nsid_bn_add_relu_fwd                 / nsid_relu_bwd, nsid_bn_bwd_*
+Saved for backward per block: the input rows x (the previous block's output), the raw conv outputs r1, r2, r3, rd, the output rows
+(the next block's x) and the per-channel affines. What has no backward yet is the stem (7x7 conv, bn1, max-pool)."""
 import torch
 import torch.nn as nn
 
@@ -110,6 +122,27 @@ class ResidualIBN(_Bottleneck):
         super().__init__()
         self._build(in_channels, out_channels, stride, IBN)
 
+    def _train_params(self):
+        ps = [self.conv1.weight, self.bn1.IN.weight, self.bn1.IN.bias, self.bn1.BN.weight, self.bn1.BN.bias, self.conv2.weight,
+              self.bn2.weight, self.bn2.bias, self.conv3.weight, self.bn3.weight, self.bn3.bias]
+        if self.downsample is not None:
+            ps += [self.downsample[0].weight, self.downsample[1].weight, self.downsample[1].bias]
+        return ps
+
+    def train_rows(self, x, B, H, W):
+        """training-mode forward on rows x (B*H*W, Cin), fp32 or bf16 -> (rows (B*Ho*Wo, Cout), Ho, Wo), differentiable: batch
+        statistics in the four BatchNorms (the running statistics and num_batches_tracked move as in nn.BatchNorm2d), backward fills
+        the gradients of x and of every parameter of the block"""
+        if not x.is_cuda:
+            raise NotImplementedError("ResidualIBN.train_rows: there is no CPU path; move the model and its input to the GPU")
+        Cin, s = self.conv1.in_channels, self.conv2.stride[0]
+        if x.dim() != 2 or tuple(x.shape) != (B * H * W, Cin):
+            raise ValueError(f"train_rows: expected rows ({B * H * W}, {Cin}), got {tuple(x.shape)}")
+        if self.bn1.IN.num_features != self.conv1.out_channels // 2 or self.bn1.IN.track_running_stats:
+            raise NotImplementedError("IBN on the MI355X path: InstanceNorm2d over the first C/2 channels, without running statistics")
+        out = _BlockTrainFn.apply(x, self, B, H, W, *self._train_params())
+        return out, ops.conv_out_size(H, 3, s), ops.conv_out_size(W, 3, s)
+
 
 class ResidualBlock(_Bottleneck):
     def __init__(self, in_channels, out_channels, stride=1):
@@ -162,6 +195,104 @@ class _HeadTrainFn(torch.autograd.Function):
         return drows, dp, dw, db, None, None, None
 
 
+def _bn_train(stat, M, bn):
+    """batch statistics -> BNAffine; running_mean / running_var / num_batches_tracked move as in nn.BatchNorm2d.train()"""
+    if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+        raise NotImplementedError("training-mode BatchNorm on the MI355X path: affine, running statistics, a fixed momentum")
+    return ops.bn_finalize(stat, M, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps)
+
+
+class _BlockTrainFn(torch.autograd.Function):
+    """one ResidualIBN block in training mode on rows; parameters in the order of _Bottleneck._train_params"""
+
+    @staticmethod
+    def forward(ctx, x, blk, B, H, W, *params):
+        Cin, Cout, s = blk.conv1.in_channels, blk.conv1.out_channels, blk.conv2.stride[0]
+        M = B * H * W
+        Ho, Wo = ops.conv_out_size(H, 3, s), ops.conv_out_size(W, 3, s)
+        Mo = B * Ho * Wo
+        ibn = blk.bn1
+        half = Cout // 2
+        x = x.contiguous()
+        # main branch
+        r1, _ = ops.linear_fwd(x, ops.w2d(blk.conv1.weight), None, M, Cout, Cin)
+        aff1 = _bn_train(ops.col_stat(r1[:, half:], M, Cout - half), M, ibn.BN)
+        y1 = ops.ibn_relu_fwd(r1, B, H * W, Cout, ibn.IN.weight, ibn.IN.bias, aff1, ibn.IN.eps)
+        r2 = ops.conv2d_fwd(y1, B, H, W, Cout, ops.packed_conv(blk.conv2.weight), None, Cout, 3, s)
+        del y1                                # recomputed from r1 in backward
+        aff2 = _bn_train(ops.col_stat(r2, Mo, Cout), Mo, blk.bn2)
+        r3, stat3 = ops.linear_fwd(r2, ops.w2d(blk.conv3.weight), None, Mo, Cout, Cout, want_stat=True, in_aff=aff2)
+        aff3 = _bn_train(stat3, Mo, blk.bn3)
+        # shortcut
+        rd, affd = None, None
+        if blk.downsample is not None:
+            dconv, dbn = blk.downsample[0], blk.downsample[1]
+            if s == 1:
+                rd, statd = ops.linear_fwd(x, ops.w2d(dconv.weight), None, M, Cout, Cin, want_stat=True)
+            else:
+                rd = ops.conv2d_fwd(x, B, H, W, Cin, ops.packed_conv(dconv.weight), None, Cout, 1, s)
+                statd = ops.col_stat(rd, Mo, Cout)
+            affd = _bn_train(statd, Mo, dbn)
+        out = ops.bn_add_relu_fwd(r3, aff3, x if rd is None else rd, affd)
+        ctx.save_for_backward(x, r1, r2, r3, rd, out)
+        ctx.blk, ctx.dims, ctx.affs = blk, (B, H, W, Ho, Wo), (aff1, aff2, aff3, affd)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, r1, r2, r3, rd, out = ctx.saved_tensors
+        blk = ctx.blk
+        B, H, W, Ho, Wo = ctx.dims
+        aff1, aff2, aff3, affd = ctx.affs
+        Cin, Cout, s = blk.conv1.in_channels, blk.conv1.out_channels, blk.conv2.stride[0]
+        M, Mo, half = B * H * W, B * Ho * Wo, Cout // 2
+        ibn = blk.bn1
+        dev = x.device
+        z = lambda *shape: ops.zeros(shape, dev)
+        g = ops.relu_bwd(dout.to(out.dtype).contiguous(), out)
+        # conv3 + bn3
+        dg3, db3 = z(Cout), z(Cout)
+        d3 = ops.bn_backward(g, r3, aff3, ops.ACT_NONE, dg3, db3)
+        dw3 = z(Cout, Cout)
+        ops.linear_bwd_weight(d3, r2, dw3, Mo, Cout, Cout, in_scale=aff2.scale, in_shift=aff2.shift)
+        dz2 = ops.linear_bwd_data(d3, ops.w2d(blk.conv3.weight), Mo, Cout, Cout)
+        # conv2 + bn2
+        dg2, db2 = z(Cout), z(Cout)
+        d2 = ops.bn_backward(dz2, r2, aff2, ops.ACT_NONE, dg2, db2, inplace=True)
+        y1 = ops.ibn_relu_fwd(r1, B, H * W, Cout, ibn.IN.weight, ibn.IN.bias, aff1, ibn.IN.eps)
+        dw2p = z(Cout, 9 * Cout)
+        ops.conv2d_bwd_weight(d2, y1, dw2p, B, H, W, Cout, Cout, 3, s)
+        dy1 = ops.conv2d_bwd_data(d2, B, H, W, Cout, ops.packed_conv_bwd(blk.conv2.weight), Cout, 3, s)
+        del y1
+        # IBN + conv1
+        dgi, dbi, dgb, dbb = z(half), z(half), z(Cout - half), z(Cout - half)
+        dr1 = ops.ibn_relu_bwd(dy1, r1, B, H * W, Cout, ibn.IN.weight, ibn.IN.bias, aff1, dgi, dbi, dgb, dbb, ibn.IN.eps, out=dy1)
+        dw1 = z(Cout, Cin)
+        ops.linear_bwd_weight(dr1, x, dw1, M, Cout, Cin)
+        w1 = ops.w2d(blk.conv1.weight)
+        grads = [dw1.view_as(blk.conv1.weight), dgi, dbi, dgb, dbb, ops.unpack_conv_wgrad(dw2p, Cout, 3), dg2, db2,
+                 dw3.view_as(blk.conv3.weight), dg3, db3]
+        # shortcut: the block's input receives both gradients in one pass (the addend of the last backward-data launch)
+        if rd is None:
+            dx = ops.linear_bwd_data(dr1, w1, M, Cout, Cin, addend=g)
+        else:
+            dconv = blk.downsample[0]
+            dgd, dbd = z(Cout), z(Cout)
+            dd = ops.bn_backward(g, rd, affd, ops.ACT_NONE, dgd, dbd, inplace=True)
+            if s == 1:
+                dwd = z(Cout, Cin)
+                ops.linear_bwd_weight(dd, x, dwd, M, Cout, Cin)
+                dxs = ops.linear_bwd_data(dd, ops.w2d(dconv.weight), M, Cout, Cin)
+                dx = ops.linear_bwd_data(dr1, w1, M, Cout, Cin, addend=dxs)
+            else:
+                dwd = z(Cout, Cin)
+                ops.conv2d_bwd_weight(dd, x, dwd, B, H, W, Cin, Cout, 1, s)
+                dxm = ops.linear_bwd_data(dr1, w1, M, Cout, Cin)
+                dx = ops.conv2d_bwd_data(dd, B, H, W, Cin, ops.packed_conv_bwd(dconv.weight), Cout, 1, s, addend=dxm)
+            grads += [dwd.view_as(dconv.weight), dgd, dbd]
+        return (dx, None, None, None, None) + tuple(grads)
+
+
 def rows_to_bchw(rows, B, H, W):
     """channels-last rows (B*H*W, C) -> the reference's (B, C, H, W) fp32 tensor (module boundary / tests: off the hot path)"""
     return rows.float().view(B, H, W, rows.shape[1]).permute(0, 3, 1, 2).contiguous()
@@ -210,13 +341,21 @@ class ResNetIBN(nn.Module):
     def head_train(self, rows, B, HW):
         """layer-4 rows (B*HW, 1024), fp32 or bf16 -> h (B, 2048), differentiable: backward fills the gradients of rows (fp32),
         global_pool.p, embedding_head.weight and embedding_head.bias (autograd rounds the gradient of bf16 rows to bf16; ops.gem_pool_bwd
-        returns it in fp32). What lies in front of the rows has no backward yet."""
+        returns it in fp32). trunk_train puts the eight residual blocks in front of it."""
         if not rows.is_cuda:
             raise NotImplementedError("ResNetIBN.head_train: there is no CPU path; move the model and its input to the GPU")
         head = self.embedding_head
         if rows.dim() != 2 or tuple(rows.shape) != (B * HW, head.in_features):
             raise ValueError(f"head_train: expected rows ({B * HW}, {head.in_features}), got {tuple(rows.shape)}")
         return _HeadTrainFn.apply(rows, self.global_pool.p, head.weight, head.bias, B, HW, self.global_pool.eps)
+
+    def trunk_train(self, rows, B, H, W):
+        """the stem's output rows (B*H*W, 64), fp32 or bf16 -> h (B, 2048), differentiable, in training mode: the eight residual
+        blocks (ResidualIBN.train_rows) and head_train. Backward fills the gradient of every parameter behind the stem and of rows."""
+        for name in ("layer1", "layer2", "layer3", "layer4"):
+            for blk in getattr(self, name):
+                rows, H, W = blk.train_rows(rows, B, H, W)
+        return self.head_train(rows, B, H * W)
 
     def forward(self, x):
         return self.forward_rows(x)

@@ -645,12 +645,18 @@ def folded_conv_bn(w2d, bias, gamma, beta, running_mean, running_var, eps=BN_EPS
         if w_fold.numel() % 8 == 0:
             SHADOWS.register(w_fold, f32_to_bf16(w_fold), owner=w_fold, fresh=True)
     if cacheable:
-        torch.cuda.current_stream().synchronize()       # once per layer: the constants are then valid on every stream
-        if len(_FOLDED) > 4096:
-            for k in [k for k, v in _FOLDED.items() if v[0]() is None]:
-                del _FOLDED[k]
-        _FOLDED[id(gamma)] = (weakref.ref(gamma), versions, w_fold, b_fold)
+        _cache_constants(_FOLDED, id(gamma), (weakref.ref(gamma), versions, w_fold, b_fold))
     return w_fold, b_fold
+
+
+def _cache_constants(cache, key, entry) -> None:
+    """keep constants derived from a parameter (entry[0]: a weakref to it) in one of the version-keyed caches: synchronise once, so
+    that they are valid on every stream, and drop the entries of dead models when the cache has grown"""
+    torch.cuda.current_stream().synchronize()
+    if len(cache) > 4096:
+        for k in [k for k, v in cache.items() if v[0]() is None]:
+            del cache[k]
+    cache[key] = entry
 
 
 def bn_finalize(stat, M, gamma, beta, running_mean, running_var, num_batches_tracked,
@@ -1908,3 +1914,142 @@ def gem_pool_bwd(x, dy, B, HW, C, p, eps=GEM_EPS):
     _tk("gem_pool_bwd_kernel", float(2 * x.element_size() + 4) * x.numel(), lambda: call(
         "nsid_gem_pool_bwd", _p(x), _p(dy), B, HW, C, _p(p), eps, _p(dx), _p(part), _p(dp), dt, _stream()), (B * HW, C, 0, 1))
     return dx, dp
+
+
+# ------------------------------------------------------------------------------------------------ ResNet-IBN baseline, training
+# Packed conv weights WITHOUT a BatchNorm folded in (training mode normalises with batch statistics): the forward packing of
+# pack_conv_bn and the backward-data packing, cached per weight tensor until its version or the weight epoch moves.
+_PACKED = {}      # (id(conv_w), kind) -> (weakref(conv_w), (data_ptr, version, WEIGHT_EPOCH), packed)
+
+
+def pack_conv_bwd(w) -> torch.Tensor:
+    """Host routine: conv weight (Cout, C, KH, KW) -> the (C, KH*KW*Cout) matrix nsid_conv2d_bwd_data reads (tap-major, Cout fastest)"""
+    with torch.no_grad():
+        return w.detach().permute(1, 2, 3, 0).reshape(w.shape[1], -1).contiguous()
+
+
+def unpack_conv_wgrad(dwp, C, ksize) -> torch.Tensor:
+    """Host routine: the packed gradient (Cout, KH*KW*C) of nsid_conv2d_bwd_weight -> conv.weight's (Cout, C, KH, KW)"""
+    return dwp.view(dwp.shape[0], ksize, ksize, C).permute(0, 3, 1, 2).contiguous()
+
+
+def _packed(conv_w, kind):
+    import weakref
+    key = (id(conv_w), kind)
+    versions = (conv_w.data_ptr(), conv_w._version, WEIGHT_EPOCH)
+    e = _PACKED.get(key)
+    if e is not None and e[0]() is conv_w and e[1] == versions:
+        return e[2]
+    wp = pack_conv_bn(conv_w)[0] if kind == "fwd" else pack_conv_bwd(conv_w)
+    if wp.numel() % 8 == 0:
+        SHADOWS.register(wp, f32_to_bf16(wp), owner=wp, fresh=True)
+    if not torch.cuda.is_current_stream_capturing():    # as folded_conv_bn: nothing is inserted under capture, an earlier entry is used
+        _cache_constants(_PACKED, key, (weakref.ref(conv_w), versions, wp))
+    return wp
+
+
+def packed_conv(conv_w) -> torch.Tensor:
+    """pack_conv_bn(conv_w) without a BatchNorm, cached (bf16 shadow included)"""
+    return _packed(conv_w, "fwd")
+
+
+def packed_conv_bwd(conv_w) -> torch.Tensor:
+    """pack_conv_bwd(conv_w), cached (bf16 shadow included)"""
+    return _packed(conv_w, "bwd")
+
+
+def conv2d_bwd_data(dy, B, H, W, C, wt, Cout, ksize, stride=1, addend=None) -> torch.Tensor:
+    """gradient of conv2d_fwd's input: dy (B*Ho*Wo, Cout) rows -> dx (B*H*W, C) rows (+ addend); wt (C, ksize*ksize*Cout) fp32 from
+    pack_conv_bwd: its bf16 shadow is the operand under bf16 storage"""
+    _chk(wt)
+    dt = _act(dy, addend)
+    Ho, Wo = conv_out_size(H, ksize, stride), conv_out_size(W, ksize, stride)
+    M, K = B * H * W, ksize * ksize * Cout
+    if tuple(dy.shape) != (B * Ho * Wo, Cout) or tuple(wt.shape) != (C, K) or (addend is not None and tuple(addend.shape) != (M, C)):
+        raise ValueError(f"conv2d_bwd_data: dy {tuple(dy.shape)} / wt {tuple(wt.shape)} do not match B={B} H={H} W={W} C={C} "
+                         f"Cout={Cout} k={ksize} s={stride}")
+    dx = torch.empty((M, C), device=dy.device, dtype=dy.dtype)
+    wop = SHADOWS.operand(wt) if dt == BF16 else wt
+    esz = dy.element_size()
+    _timed("conv2d_bwd_data_kernel<%dx%d,s%d>" % (ksize, ksize, stride), 2.0 * M * C * K,
+           esz * (B * Ho * Wo * Cout + M * C * (2 if addend is not None else 1)) + float(wop.element_size()) * C * K,
+           lambda: call("nsid_conv2d_bwd_data", _p(dy), B, H, W, C, _p(wop), dt, _p(addend), _p(dx), Cout, ksize, stride, dt,
+                        _stream()), (M, C, K, 1))
+    return dx
+
+
+def conv2d_bwd_weight(dy, x, dwp, B, H, W, C, Cout, ksize, stride=1) -> None:
+    """dwp += the packed weight gradient (Cout, ksize*ksize*C) fp32 of conv2d_fwd (unpack_conv_wgrad turns it into conv.weight's layout)"""
+    _chk(dwp)
+    dt = _act(dy, x)
+    Ho, Wo = conv_out_size(H, ksize, stride), conv_out_size(W, ksize, stride)
+    M, K = B * Ho * Wo, ksize * ksize * C
+    if tuple(dy.shape) != (M, Cout) or tuple(x.shape) != (B * H * W, C) or tuple(dwp.shape) != (Cout, K):
+        raise ValueError(f"conv2d_bwd_weight: dy {tuple(dy.shape)} / x {tuple(x.shape)} / dw {tuple(dwp.shape)} do not match B={B} "
+                         f"H={H} W={W} C={C} Cout={Cout} k={ksize} s={stride}")
+    nws = lib.nsid_workspace_bytes(b"conv2d_bwd_weight", M, Cout * K)
+    ws = torch.empty((nws // 4,), device=dy.device, dtype=torch.float32) if nws > 0 else None
+    esz = dy.element_size()
+    _timed("conv2d_wgrad_kernel<%dx%d,s%d>" % (ksize, ksize, stride), 2.0 * M * Cout * K,
+           esz * (M * Cout + B * H * W * C) + 8.0 * Cout * K + 2.0 * nws,
+           lambda: call("nsid_conv2d_bwd_weight", _p(dy), _p(x), B, H, W, C, _p(dwp), _p(ws), Cout, ksize, stride, dt, _stream()),
+           (M, Cout, K, 1))
+
+
+def col_stat(x, M, C) -> torch.Tensor:
+    """per-channel sum and sum of squares of rows x (M, C) (a column slice of a wider matrix is fine) per 128-row tile:
+    the (2, row_tiles(M), C) fp32 buffer bn_finalize reads. One launch."""
+    if not x.is_cuda:
+        raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if x.dtype not in (torch.float32, torch.bfloat16) or x.dim() != 2 or x.stride(1) != 1 or tuple(x.shape) != (M, C):
+        raise RuntimeError(f"col_stat: expected float32/bfloat16 rows ({M}, {C}) with unit column stride, got {x.dtype} {tuple(x.shape)}")
+    dt = BF16 if x.dtype == torch.bfloat16 else F32
+    stat = torch.empty((2, row_tiles(M), C), device=x.device, dtype=torch.float32)
+    _tk("col_stat_kernel", float(x.element_size()) * M * C, lambda: call(
+        "nsid_col_stat", _p(x), x.stride(0), M, C, _p(stat), dt, _stream()), (M, C, 0, 1))
+    return stat
+
+
+def ibn_relu_bwd(dy, r, B, HW, C, in_gamma, in_beta, bn_aff: "BNAffine", d_in_gamma, d_in_beta, d_bn_gamma, d_bn_beta,
+                 eps=IN_EPS, out=None) -> torch.Tensor:
+    """backward of ibn_relu_fwd with batch statistics in the BatchNorm half (bn_aff from bn_finalize: scale, shift, mean, invstd):
+    returns dr; the four parameter gradients are accumulated"""
+    _chk(in_gamma, in_beta, bn_aff.scale, bn_aff.shift, bn_aff.mean, bn_aff.invstd, d_in_gamma, d_in_beta, d_bn_gamma, d_bn_beta)
+    dt = _act(dy, r, out)
+    half = C // 2
+    if (tuple(dy.shape) != (B * HW, C) or tuple(r.shape) != (B * HW, C) or in_gamma.numel() != half or bn_aff.scale.numel() != C - half
+            or d_in_gamma.numel() != half or d_in_beta.numel() != half or d_bn_gamma.numel() != C - half or d_bn_beta.numel() != C - half):
+        raise ValueError("ibn_relu_bwd: shapes do not match")
+    if out is None:
+        out = torch.empty_like(dy)
+    ws = torch.empty((lib.nsid_workspace_bytes(b"ibn_relu_bwd", B, C) // 4,), device=dy.device, dtype=torch.float32)
+    _tk("ibn_relu_bwd_kernel", 7.0 * dy.element_size() * dy.numel(), lambda: call(
+        "nsid_ibn_relu_bwd", _p(dy), _p(r), B, HW, C, _p(in_gamma), _p(in_beta), eps, _p(bn_aff.scale), _p(bn_aff.shift),
+        _p(bn_aff.mean), _p(bn_aff.invstd), _p(out), _p(ws), _p(d_in_gamma), _p(d_in_beta), _p(d_bn_gamma), _p(d_bn_beta), dt,
+        _stream()), (B * HW, C, 0, 1))
+    return out
+
+
+def bn_add_relu_fwd(r3, aff3: "BNAffine", identity, aff_d: Optional["BNAffine"] = None) -> torch.Tensor:
+    """relu(BN3(r3) + identity), identity = BN_d(identity) when aff_d is given: the tail of a training-mode residual block"""
+    dt = _act(r3, identity)
+    M, C = r3.shape
+    if tuple(identity.shape) != (M, C):
+        raise ValueError("bn_add_relu_fwd: shapes do not match")
+    _chk(aff3.scale, aff3.shift, None if aff_d is None else aff_d.scale, None if aff_d is None else aff_d.shift)
+    out = torch.empty_like(r3)
+    _tk("bn_add_relu_kernel", 3.0 * r3.element_size() * M * C, lambda: call(
+        "nsid_bn_add_relu_fwd", _p(r3), _p(aff3.scale), _p(aff3.shift), _p(identity), None if aff_d is None else _p(aff_d.scale),
+        None if aff_d is None else _p(aff_d.shift), _p(out), M, C, dt, _stream()), (M, C, 0, 1))
+    return out
+
+
+def relu_bwd(dy, y) -> torch.Tensor:
+    """dy where the stored ReLU output y is positive, else 0"""
+    dt = _act(dy, y)
+    if dy.shape != y.shape:
+        raise ValueError("relu_bwd: shapes do not match")
+    g = torch.empty_like(dy)
+    _tk("relu_bwd_kernel", 3.0 * dy.element_size() * dy.numel(), lambda: call(
+        "nsid_relu_bwd", _p(dy), _p(y), _p(g), dy.numel(), dt, _stream()), tuple(dy.shape) + (0, 1))
+    return g

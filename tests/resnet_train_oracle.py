@@ -1,0 +1,173 @@
+"""The training-mode ResidualIBN block of the ResNet-IBN baseline (encoder/resnet_ibn.py of the reference) restated in plain torch for
+any dtype on (B, C, H, W) tensors, gradients by autograd, and the closed-form backward of IBN + ReLU. Not a test module.
+
+    identity = BN_d(conv_d(x)) or x;  r1 = conv1(x);  y1 = relu(cat(IN(r1[:, :C/2]), BN(r1[:, C/2:])));  r2 = conv2(y1);
+    r3 = conv3(bn2(r2));  out = relu(bn3(r3) + identity)
+
+All BatchNorms use batch statistics (biased variance) and return the updated running statistics (momentum 0.1, unbiased variance).
+Options:
+  bf16    emulate bf16 storage: every tensor the kernels store (r1, y1, r2, r3, rd, the block output, and the gradients that flow back
+          through those places) is rounded to bf16, and every 4-D conv weight is rounded as an operand (its gradient goes to the
+          unrounded weight)
+  masks   {"relu1": bool tensor, "relu2": bool tensor}: use these ReLU masks instead of the sign of the pre-activations
+The state of a block is a dict with the reference's names (conv1.weight, bn1.IN.weight, bn1.BN.running_mean, downsample.0.weight, ...).
+
+Closed form of y = relu(IBN(r)), g = dy * mask, xh = (r - mean) * invstd over the rows the statistics run over:
+    dr = gamma * invstd * (g - mean g - xh * mean(g xh)),  dgamma = sum g xh,  dbeta = sum g"""
+import torch
+
+F = torch.nn.functional
+IN_EPS = 1e-5
+BN_EPS = 1e-5
+MOMENTUM = 0.1
+PARAMS = ("conv1.weight", "bn1.IN.weight", "bn1.IN.bias", "bn1.BN.weight", "bn1.BN.bias", "conv2.weight", "bn2.weight", "bn2.bias",
+          "conv3.weight", "bn3.weight", "bn3.bias", "downsample.0.weight", "downsample.1.weight", "downsample.1.bias")
+BNS = ("bn1.BN", "bn2", "bn3", "downsample.1")
+
+
+class _Store(torch.autograd.Function):
+    """a tensor passing through bf16 storage: the value is rounded on the way forward, its gradient on the way back"""
+
+    @staticmethod
+    def forward(ctx, t):
+        return t.to(torch.bfloat16).to(t.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).to(g.dtype)
+
+
+class _StoreGrad(torch.autograd.Function):
+    """a place where only the gradient passes through bf16 storage (bn2's output: the forward applies bn2 on conv3's operand load,
+    the backward stores the gradient conv3's backward-data GEMM writes)"""
+
+    @staticmethod
+    def forward(ctx, t):
+        return t.view_as(t)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g.to(torch.bfloat16).to(g.dtype)
+
+
+def _operand(w):
+    """a weight rounded to bf16 as an operand; the gradient goes to the unrounded weight"""
+    return w + (w.to(torch.bfloat16).to(w.dtype) - w).detach()
+
+
+def batch_norm_train(r, gamma, beta, running_mean, running_var, eps=BN_EPS, momentum=MOMENTUM):
+    """-> (normalised tensor, new running mean, new running variance)"""
+    n = r.numel() // r.shape[1]
+    mean = r.mean(dim=(0, 2, 3))
+    var = ((r - mean.view(1, -1, 1, 1)) ** 2).mean(dim=(0, 2, 3))
+    y = (r - mean.view(1, -1, 1, 1)) * (var + eps).rsqrt().view(1, -1, 1, 1) * gamma.view(1, -1, 1, 1) + beta.view(1, -1, 1, 1)
+    uvar = var * (n / max(n - 1, 1))
+    return y, ((1 - momentum) * running_mean + momentum * mean).detach(), ((1 - momentum) * running_var + momentum * uvar).detach()
+
+
+def instance_norm(r, gamma, beta, eps=IN_EPS):
+    mean = r.mean(dim=(2, 3), keepdim=True)
+    var = ((r - mean) ** 2).mean(dim=(2, 3), keepdim=True)
+    return (r - mean) * (var + eps).rsqrt() * gamma.view(1, -1, 1, 1) + beta.view(1, -1, 1, 1)
+
+
+def _relu(pre, mask):
+    return torch.relu(pre) if mask is None else pre * mask.to(pre.dtype)
+
+
+def block_forward(x, sd, stride, bf16=False, masks=None):
+    """x (B, Cin, H, W) and the block's state sd in one dtype -> dict(out, pre1, pre2, running: {name: tensor})"""
+    st = _Store.apply if bf16 else (lambda t: t)
+    stg = _StoreGrad.apply if bf16 else (lambda t: t)
+    wop = _operand if bf16 else (lambda w: w)
+    masks = masks or {}
+    running = {}
+    C = sd["conv1.weight"].shape[0]
+    half = C // 2
+
+    def bn(name, r):
+        y, rm, rv = batch_norm_train(r, sd[name + ".weight"], sd[name + ".bias"], sd[name + ".running_mean"], sd[name + ".running_var"])
+        running[name + ".running_mean"], running[name + ".running_var"] = rm, rv
+        return y
+
+    identity = x
+    if "downsample.0.weight" in sd:
+        identity = bn("downsample.1", st(F.conv2d(x, wop(sd["downsample.0.weight"]), stride=stride)))
+    r1 = st(F.conv2d(x, wop(sd["conv1.weight"])))
+    pre1 = torch.cat([instance_norm(r1[:, :half], sd["bn1.IN.weight"], sd["bn1.IN.bias"]), bn("bn1.BN", r1[:, half:])], dim=1)
+    y1 = st(_relu(pre1, masks.get("relu1")))
+    r2 = st(F.conv2d(y1, wop(sd["conv2.weight"]), stride=stride, padding=1))
+    r3 = st(F.conv2d(stg(bn("bn2", r2)), wop(sd["conv3.weight"])))
+    pre2 = bn("bn3", r3) + identity
+    out = st(_relu(pre2, masks.get("relu2")))
+    return dict(out=out, pre1=pre1, pre2=pre2, running=running)
+
+
+def block_reference(x, sd, stride, dout, dtype, bf16=False, masks=None):
+    """forward and autograd backward in dtype: dict(out, dx, grads: {parameter name: gradient}, running, pre1, pre2); with bf16 the
+    input and the upstream gradient are the bf16-rounded ones"""
+    rnd = (lambda t: t.to(torch.bfloat16).to(dtype)) if bf16 else (lambda t: t.to(dtype))
+    xs = rnd(x).clone().requires_grad_(True)
+    s = {k: v.to(dtype).clone() for k, v in sd.items() if v.is_floating_point()}
+    names = [k for k in PARAMS if k in s]
+    for k in names:
+        s[k].requires_grad_(True)
+    res = block_forward(xs, s, stride, bf16=bf16, masks=masks)
+    grads = torch.autograd.grad(res["out"], [xs] + [s[k] for k in names], rnd(dout))
+    return dict(out=res["out"].detach(), dx=rnd(grads[0]), grads=dict(zip(names, grads[1:])), running=res["running"],
+                pre1=res["pre1"].detach(), pre2=res["pre2"].detach())
+
+
+def ibn_relu_bwd_closed_form(r, dy, mask, gamma_in, gamma_bn, eps_in=IN_EPS, eps_bn=BN_EPS):
+    """r, dy, mask (B, C, H, W) -> (dr, dgamma_in, dbeta_in, dgamma_bn, dbeta_bn) by the closed form of the module docstring, in r's dtype"""
+    half = r.shape[1] // 2
+    g = dy * mask.to(dy.dtype)
+
+    def part(r, g, gamma, dims, eps):
+        mean = r.mean(dim=dims, keepdim=True)
+        var = ((r - mean) ** 2).mean(dim=dims, keepdim=True)
+        istd = (var + eps).rsqrt()
+        xh = (r - mean) * istd
+        dr = gamma.view(1, -1, 1, 1) * istd * (g - g.mean(dim=dims, keepdim=True) - xh * (g * xh).mean(dim=dims, keepdim=True))
+        return dr, (g * xh).sum(dim=(0, 2, 3)), g.sum(dim=(0, 2, 3))
+
+    dr_in, dg_in, db_in = part(r[:, :half], g[:, :half], gamma_in, (2, 3), eps_in)
+    dr_bn, dg_bn, db_bn = part(r[:, half:], g[:, half:], gamma_bn, (0, 2, 3), eps_bn)
+    return torch.cat([dr_in, dr_bn], dim=1), dg_in, db_in, dg_bn, db_bn
+
+
+def ibn_relu_forward(r, gamma_in, beta_in, gamma_bn, beta_bn):
+    """pre-activation of relu(IBN(r)) with batch statistics in the BatchNorm half"""
+    half = r.shape[1] // 2
+    z = torch.zeros_like(gamma_bn)
+    return torch.cat([instance_norm(r[:, :half], gamma_in, beta_in),
+                      batch_norm_train(r[:, half:], gamma_bn, beta_bn, z, z)[0]], dim=1)
+
+
+def sub_state(sd, prefix):
+    """the entries of a model state under `prefix` with the prefix removed"""
+    return {k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}
+
+
+LAYERS = (("layer1.0.", 1), ("layer1.1.", 1), ("layer2.0.", 1), ("layer2.1.", 1), ("layer3.0.", 2), ("layer3.1.", 1),
+          ("layer4.0.", 2), ("layer4.1.", 1))
+
+
+def trunk_reference(x, sd, dh, dtype, bf16=False, gem_eps=1e-6):
+    """the eight blocks and the pooling head on the stem's output x (B, 64, H, W): dict(h, dx, grads: {state name: gradient}, running)"""
+    rnd = (lambda t: t.to(torch.bfloat16).to(dtype)) if bf16 else (lambda t: t.to(dtype))
+    xs = rnd(x).clone().requires_grad_(True)
+    s = {k: v.to(dtype).clone() for k, v in sd.items() if v.is_floating_point()}
+    names = [k for k in s if not k.endswith(("running_mean", "running_var")) and not k.startswith(("conv1.", "bn1."))]
+    for k in names:
+        s[k].requires_grad_(True)
+    t, running = xs, {}
+    for prefix, stride in LAYERS:
+        res = block_forward(t, sub_state(s, prefix), stride, bf16=bf16)
+        t = res["out"]
+        running.update({prefix + k: v for k, v in res["running"].items()})
+    p = s["global_pool.p"]
+    pooled = t.clamp(min=gem_eps).pow(p).mean(dim=(2, 3)).pow(1.0 / p)
+    h = F.linear(pooled, s["embedding_head.weight"], s["embedding_head.bias"])
+    grads = torch.autograd.grad(h, [xs] + [s[k] for k in names], dh.to(dtype))
+    return dict(h=h.detach(), dx=grads[0], grads=dict(zip(names, grads[1:])), running=running)

@@ -216,7 +216,7 @@ def profile(args):
         for row in csv.DictReader(open(f)):
             rows.append((int(row["Start_Timestamp"]), int(row["End_Timestamp"]), row["Kernel_Name"]))
     rows.sort()
-    convs = [r for r in rows if "conv2d_fwd_kernel" in r[2]]
+    convs = [r for r in rows if "conv2d_kernel" in r[2]]          # the forward instantiation conv2d_kernel<T, false>: nothing else runs here
     plan = conv_launches(PROFILE_BATCH, args.frames)
     n = len(plan)
     if len(convs) != n * (PROFILE_WARMUP + PROFILE_STEPS):
@@ -227,7 +227,7 @@ def profile(args):
     sel = rows[stems[PROFILE_WARMUP]:]
     acc = {}
     for s, e, name in sel:
-        m = re.match(r"_ZN\d+_GLOBAL__N_1\d+([a-z0-9_]+_kernel)I(DF16b|f)E", name)        # a mangled anonymous-namespace template
+        m = re.match(r"_ZN\d+_GLOBAL__N_1\d+([a-z0-9_]+_kernel)I(DF16b|f)(?:Lb[01]E)?E", name)        # a mangled anonymous-namespace template
         if m:
             name = f"{m.group(1)}<{'bf16' if m.group(2) == 'DF16b' else 'float'}>"
         name = re.sub(r"\(anonymous namespace\)::|^void ", "", name)
