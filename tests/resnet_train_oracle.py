@@ -153,21 +153,48 @@ LAYERS = (("layer1.0.", 1), ("layer1.1.", 1), ("layer2.0.", 1), ("layer2.1.", 1)
           ("layer4.0.", 2), ("layer4.1.", 1))
 
 
-def trunk_reference(x, sd, dh, dtype, bf16=False, gem_eps=1e-6):
-    """the eight blocks and the pooling head on the stem's output x (B, 64, H, W): dict(h, dx, grads: {state name: gradient}, running)"""
+BAND = {torch.float32: (1e-4, 1e-3), torch.bfloat16: (2.0 ** -5, 5e-2)}
+TRUNK_MAPS = ((6, 7), (11, 13))
+TRUNK_B = 3
+
+
+def band_share(pre, thr):
+    """(share of the elements of a pre-activation within thr x its rms of zero, the mask of the elements outside that band)"""
+    clear = pre.abs() > thr * pre.pow(2).mean().sqrt()
+    return 1.0 - float(clear.double().mean()), clear
+
+
+def trunk_case(H, W, p=2.5):
+    """(state, x (B, 64, H, W), dh (B, 2048)) of the trunk tests: synthesized weights, an input like the stem's output (behind a ReLU
+    and a max-pool: non-negative) and an upstream gradient"""
+    from synth import synth_randn, synth_state
+    from neuralsampleid_amd.encoder.resnet_ibn import ResNetIBN
+    sd = synth_state(ResNetIBN().state_dict())
+    sd["global_pool.p"] = torch.full((1,), p)
+    tag = "trunk_train" if (H, W) == (6, 7) else f"trunk_train_{H}x{W}"
+    return sd, synth_randn(tag, TRUNK_B, 64, H, W).abs(), synth_randn(tag + "_dh", TRUNK_B, 2048) / 32
+
+
+def trunk_reference(x, sd, dh, dtype, bf16=False, gem_eps=1e-6, masks=None):
+    """the eight blocks and the pooling head on the stem's output x (B, 64, H, W): dict(h, dx, grads: {state name: gradient}, running,
+    blocks: {block prefix: dict(pre1, pre2, out)}). masks: {block prefix: {"relu1": ..., "relu2": ...}} for the prefixes of LAYERS,
+    each handed to block_forward; without it every ReLU follows the sign of its own pre-activation"""
     rnd = (lambda t: t.to(torch.bfloat16).to(dtype)) if bf16 else (lambda t: t.to(dtype))
     xs = rnd(x).clone().requires_grad_(True)
     s = {k: v.to(dtype).clone() for k, v in sd.items() if v.is_floating_point()}
     names = [k for k in s if not k.endswith(("running_mean", "running_var")) and not k.startswith(("conv1.", "bn1."))]
     for k in names:
         s[k].requires_grad_(True)
-    t, running = xs, {}
+    if masks is not None and set(masks) != {prefix for prefix, _ in LAYERS}:
+        raise ValueError(f"trunk_reference: masks for {sorted(masks)}, expected the eight prefixes of LAYERS")
+    t, running, blocks = xs, {}, {}
     for prefix, stride in LAYERS:
-        res = block_forward(t, sub_state(s, prefix), stride, bf16=bf16)
+        res = block_forward(t, sub_state(s, prefix), stride, bf16=bf16, masks=None if masks is None else masks[prefix])
         t = res["out"]
         running.update({prefix + k: v for k, v in res["running"].items()})
+        blocks[prefix] = dict(pre1=res["pre1"].detach(), pre2=res["pre2"].detach(), out=t.detach())
     p = s["global_pool.p"]
     pooled = t.clamp(min=gem_eps).pow(p).mean(dim=(2, 3)).pow(1.0 / p)
     h = F.linear(pooled, s["embedding_head.weight"], s["embedding_head.bias"])
     grads = torch.autograd.grad(h, [xs] + [s[k] for k in names], dh.to(dtype))
-    return dict(h=h.detach(), dx=grads[0], grads=dict(zip(names, grads[1:])), running=running)
+    return dict(h=h.detach(), dx=grads[0], grads=dict(zip(names, grads[1:])), running=running, blocks=blocks)

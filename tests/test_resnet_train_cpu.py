@@ -80,6 +80,47 @@ def test_forced_masks_and_bf16_emulation():
     assert 1e-4 < e < 3e-2, e                                                           # bf16 storage noise, nothing larger
 
 
+def test_trunk_forced_masks_of_its_own_free_run_change_nothing():
+    """trunk_reference with the signs of its own free fp64 run forced on all sixteen ReLUs is the free run bit for bit"""
+    sd, x, dh = O.trunk_case(6, 7)
+    free = O.trunk_reference(x, sd, dh, torch.float64)
+    assert set(free["blocks"]) == {p for p, _ in O.LAYERS}
+    masks = {p: {"relu1": b["pre1"] > 0, "relu2": b["pre2"] > 0} for p, b in free["blocks"].items()}
+    forced = O.trunk_reference(x, sd, dh, torch.float64, masks=masks)
+    assert torch.equal(forced["h"], free["h"]) and torch.equal(forced["dx"], free["dx"])
+    assert set(forced["grads"]) == set(free["grads"]) and set(forced["running"]) == set(free["running"])
+    for k, g in free["grads"].items():
+        assert torch.equal(forced["grads"][k], g), k
+    for k, v in free["running"].items():
+        assert torch.equal(forced["running"][k], v), k
+    for p, b in free["blocks"].items():
+        for k in ("pre1", "pre2", "out"):
+            assert torch.equal(forced["blocks"][p][k], b[k]), (p, k)
+    with pytest.raises(ValueError, match="eight prefixes"):
+        O.trunk_reference(x, sd, dh, torch.float64, masks={"layer1.0.": masks["layer1.0."]})
+
+
+@pytest.mark.parametrize("hw", O.TRUNK_MAPS, ids=lambda s: "%dx%d" % s)
+def test_trunk_inputs_keep_the_relu_band_thin(hw):
+    """the inputs of the GPU trunk tests: in the fp64 run, each of the sixteen pre-activations has at most the cap's share of its
+    elements within the band around zero in which a kernel's mask bit may differ (BAND: fp32 1e-4 of the rms, cap 1e-3; bf16 2^-5 of
+    the rms, cap 5e-2). A share above its cap is answered by another input seed, never by another cap."""
+    sd, x, dh = O.trunk_case(*hw)
+    with torch.no_grad():
+        s = {k: v.double() for k, v in sd.items() if v.is_floating_point()}
+        t, pres = x.double(), []
+        for prefix, stride in O.LAYERS:
+            res = O.block_forward(t, O.sub_state(s, prefix), stride)
+            t = res["out"]
+            pres += [(prefix + "relu1", res["pre1"]), (prefix + "relu2", res["pre2"])]
+    assert len(pres) == 16
+    for dt, (thr, cap) in O.BAND.items():
+        shares = {name: O.band_share(pre, thr)[0] for name, pre in pres}
+        worst = max(shares, key=shares.get)
+        print(f"  {hw[0]}x{hw[1]} {dt}: worst share within the band {shares[worst]:.2e} ({worst}), cap {cap:g}")
+        assert shares[worst] <= cap, (dt, worst, shares[worst])
+
+
 @pytest.mark.parametrize("shape", [(128, 64, 3), (256, 128, 1)], ids=lambda s: "Co%dC%dk%d" % s)
 def test_backward_weight_packing(lib, shape):
     from neuralsampleid_amd import ops
