@@ -74,7 +74,7 @@ int nsid_row_tiles(int M);
  * query per op"; the reference has no counterpart — its ops allocate through torch). No entry point allocates; the kernels keep
  * their working sets in LDS and registers, so every op answers 0 ("knn_graph", "mr_aggregate", "linear", "linear_bwd_data",
  * "linear_bwd_weight", "downsample3", "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused", "conv2d",
- * "ibn_relu", "stem7_pool", "gem_pool")
+ * "ibn_relu", "stem7_pool", "stem7_pool_train", "gem_pool")
  * except: "bn_stat" (rows x cols layer: the [2][nsid_row_tiles(rows)][cols] fp32 partial sums between a GEMM's statistics
  * epilogue / nsid_bn_bwd_reduce and the finalize kernels), "ntxent" (rows = pairs of the global batch: nsid_ntxent_ws_floats),
  * "baseline_loss" (rows = M, cols = D: nsid_baseline_loss_ws_floats),
@@ -82,6 +82,8 @@ int nsid_row_tiles(int M);
  * "conv2d_bwd_weight" (rows = output rows B*Ho*Wo, cols = weight elements Cout*k*k*C: one fp32 dw per row split,
  * nsid_conv2d_wgrad_splits; 0 when one split covers the rows), "ibn_relu_bwd" (rows = clips, cols = channels: the per-clip sums),
  * and 0 for "conv2d_bwd_data", "col_stat", "bn_add_relu", "relu_bwd";
+ * "stem7_stat" and "stem7_bwd" (rows = clips * pooled rows B*Hp, cols = pooled columns Wp: the [2][nsid_stem7_partials(rows, cols, 0)][64]
+ * statistics sums / nsid_stem7_partials(rows, cols, 1) sets of the backward's partial sums, one per workgroup);
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
  * per-split top-64 lists of its first phase). */
 long nsid_workspace_bytes(const char* op, long rows, long cols);
@@ -183,7 +185,10 @@ int nsid_colsum_acc(const void* x, int ldx, int M, int C, float* out, int dtype,
 /* ---- BatchNorm2d, training mode, split around the GEMMs ------------------------------------------------
  * Replaces nn.BatchNorm2d at encoder/graph_encoder.py:45,75,77,152, torch_vertex.py:154,161, torch_nn.py:32.
  * finalize: reduces the GEMM's partial statistics (fp64), writes scale = gamma*invstd, shift = beta-mean*scale,
- * mean, invstd, and updates running_mean / running_var (unbiased) / num_batches_tracked (momentum 0.1). */
+ * mean, invstd, and updates running_mean / running_var (unbiased) / num_batches_tracked (momentum 0.1). stat is [2][tiles][C]
+ * partial sums over the M rows in all: tiles = nsid_row_tiles(M) behind a GEMM epilogue or nsid_col_stat, or the count
+ * nsid_stem7_partials(..., 0) (at most 1024) behind nsid_stem7_stat, for which the caller answers: the kernel reads 2 * tiles * C
+ * floats. Any other count is NSID_EINVAL. */
 int nsid_bn_finalize(const float* stat, int tiles, int C, int M, const float* gamma, const float* beta,
                      float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum,
                      float eps, float* scale, float* shift, float* mean, float* invstd, void* stream);
@@ -608,6 +613,29 @@ int nsid_ibn_relu_bwd(const void* dy, const void* r, int B, int HW, int C, const
 int nsid_bn_add_relu_fwd(const void* r3, const float* scale3, const float* shift3, const void* identity, const float* scale_d,
                          const float* shift_d, void* out, int M, int C, int dtype, void* stream);
 int nsid_relu_bwd(const void* dy, const void* y, void* g, long n, int dtype, void* stream);
+
+/* ---- ResNet-IBN baseline, training-mode stem (csrc/resnet.hip): Conv2d(1, 64, 7, stride 2, pad 3) -> BatchNorm2d(64) with BATCH
+ * statistics -> ReLU -> MaxPool2d(3, 2, 1). x (B, H, W) fp32, w (64, 49) the RAW conv weight. The conv output (N = B*Hc*Wc pixels,
+ * Hc = (H - 1) / 2 + 1) is never stored: the statistics, the forward and the backward each compute it from x with one summation
+ * order, so the backward's ReLU mask and window winner are the forward's bit for bit. No atomics: a second call gives the same bits.
+ * stem7_partials: partial sets the statistics (which = 0) / the backward (which = 1) leave for rows = B*Hp, cols = Wp.
+ * stem7_bwd_set_floats: floats of one set of the backward (A[49][64], X[49][64], a[64], b[64], S[49] padded to 64).
+ * stem7_stat: per-channel sum and sum of squares of the raw conv output, summed from the conv values themselves, into
+ *   stat[2][nsid_stem7_partials(B*Hp, Wp, 0)][64]: nsid_bn_finalize(stat, that count, 64, N, ...) gives the affine.
+ * stem7_pool_train_fwd: wf (64, 49 scratch) = w * scale per channel on the device, then stem7_pool_fwd's kernel on (wf, shift).
+ * stem7_bwd: dpool (B*Hp*Wp, 64) rows of dpool_dtype; scale / shift / mean / invstd as nsid_bn_finalize left them, gamma = the
+ *   BatchNorm weight. With g = dpool where the window's winning value (first maximum in scan order) is > 0, xh = (r - mean) * invstd at
+ *   the winner and patch_t the input under tap t: dbeta = a = sum g, dgamma = b = sum g xh,
+ *   dw[c][t] = gamma * invstd * (sum g patch_t - (a / N) sum_pixels patch_t - (b / N) sum_pixels xh patch_t). The outputs are
+ *   written, not accumulated. ws: nsid_workspace_bytes("stem7_bwd", B*Hp, Wp) bytes; the sets are added in order in fp64. Two launches. */
+long nsid_stem7_partials(long rows, long cols, int which);
+long nsid_stem7_bwd_set_floats(void);
+int nsid_stem7_stat(const float* x, int B, int H, int W, const float* w, float* stat, void* stream);
+int nsid_stem7_pool_train_fwd(const float* x, int B, int H, int W, const float* w, const float* scale, const float* shift, float* wf,
+                              void* out, int out_dtype, void* stream);
+int nsid_stem7_bwd(const void* dpool, int dpool_dtype, const float* x, int B, int H, int W, const float* w, const float* scale,
+                   const float* shift, const float* mean, const float* invstd, const float* gamma, float* ws, float* dw,
+                   float* dgamma, float* dbeta, void* stream);
 
 #ifdef __cplusplus
 }

@@ -105,6 +105,9 @@ SIGNATURES = {
     "nsid_ibn_relu_bwd": "ppiiippfppppppppppis",
     "nsid_bn_add_relu_fwd": "pppppppiiis",
     "nsid_relu_bwd": "ppplis",
+    "nsid_stem7_stat": "piiipps",
+    "nsid_stem7_pool_train_fwd": "piiipppppis",
+    "nsid_stem7_bwd": "pipiiipppppppppps",
 }
 
 class WgradProblem(ctypes.Structure):
@@ -181,11 +184,15 @@ def _load():
     lib.nsid_baseline_loss_ws_floats.restype = ctypes.c_size_t
     lib.nsid_conv2d_wgrad_splits.argtypes = [ctypes.c_long, ctypes.c_long]
     lib.nsid_conv2d_wgrad_splits.restype = ctypes.c_int
+    lib.nsid_stem7_partials.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_int]
+    lib.nsid_stem7_partials.restype = ctypes.c_long
+    lib.nsid_stem7_bwd_set_floats.argtypes = []
+    lib.nsid_stem7_bwd_set_floats.restype = ctypes.c_long
     return lib
 
 
 lib = _load()
-EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_baseline_loss_ws_floats", "nsid_conv2d_wgrad_splits", "nsid_workspace_bytes"]
+EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_baseline_loss_ws_floats", "nsid_conv2d_wgrad_splits", "nsid_stem7_partials", "nsid_stem7_bwd_set_floats", "nsid_workspace_bytes"]
 
 _ERR = {-1: "NSID_EINVAL (unsupported shape, misaligned pointer or bad argument)",
         -2: "NSID_ELAUNCH (HIP runtime refused the launch)"}

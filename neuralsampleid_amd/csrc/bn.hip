@@ -354,7 +354,9 @@ extern "C" int nsid_bn_finalize(const float* stat, int tiles, int C, int M, cons
                                 float* running_mean, float* running_var, int64_t* nbt, float momentum, float eps,
                                 float* scale, float* shift, float* mean, float* invstd, void* stream) {
   NSID_REQUIRE(stat && gamma && beta && scale && shift && mean && invstd && C > 0 && M > 0);
-  NSID_REQUIRE(tiles == nsid_row_tiles(M));
+  // the kernel reads 2 * tiles * C floats: nsid_row_tiles(M) behind a GEMM epilogue or nsid_col_stat, or the count nsid_stem7_stat
+  // left (nsid_stem7_partials(..., 0) <= NSID_STEM7_STAT_MAX; the caller answers for it)
+  NSID_REQUIRE(tiles == nsid_row_tiles(M) || (tiles > 0 && tiles <= NSID_STEM7_STAT_MAX));
   NSID_REQUIRE((running_mean == nullptr) == (running_var == nullptr));
   NSID_FIN_LAUNCH(bn_finalize_kernel, tiles, C, stream, stat, tiles, C, M, gamma, beta, running_mean, running_var, nbt,
               momentum, eps, scale, shift, mean, invstd, static_cast<float*>(nullptr));

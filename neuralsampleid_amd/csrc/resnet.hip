@@ -390,6 +390,30 @@ constexpr int ST_PW = 16;                    // pooled columns per workgroup
 constexpr int ST_CW = 2 * ST_PW + 1;         // conv columns under them
 constexpr int ST_PR = 11, ST_PC = 2 * (ST_CW - 1) + 7;     // input patch: 11 rows x 71 columns
 
+// conv pixel (i, j) of a workgroup's patch against the 49 weights of one channel: THE summation order of the stem. The training
+// forward (folded weights), its statistics and its backward all go through it, so the backward's ReLU mask and window winner are the
+// forward's bit for bit.
+__device__ __forceinline__ float stem7_conv(const float (&patch)[ST_PR][ST_PC + 1], int i, int j, const float (&wk)[49]) {
+  float s = 0.f;
+#pragma unroll
+  for (int kh = 0; kh < 7; ++kh)
+#pragma unroll
+    for (int kw = 0; kw < 7; ++kw) s = fmaf(patch[2 * i + kh][2 * j + kw], wk[kh * 7 + kw], s);
+  return s;
+}
+
+// the input patch under the 3 x 33 conv pixels of tile (b, hp, wp0 .. wp0 + 15); outside the image: the conv's zero padding
+__device__ __forceinline__ void stem7_load_patch(float (&patch)[ST_PR][ST_PC + 1], const float* __restrict__ x, int H, int W, int b,
+                                                 int hp, int wp0, int tid) {
+  const int r0 = 4 * hp - 5, q0 = 4 * wp0 - 5;
+  const float* xb = x + (long)b * H * W;
+  for (int idx = tid; idx < ST_PR * ST_PC; idx += 256) {
+    const int pr = idx / ST_PC, pc = idx - pr * ST_PC;
+    const int r = r0 + pr, q = q0 + pc;
+    patch[pr][pc] = (r >= 0 && r < H && q >= 0 && q < W) ? xb[(long)r * W + q] : 0.f;
+  }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void stem7_pool_kernel(const StemArgs a) {
   __shared__ float patch[ST_PR][ST_PC + 1];
@@ -414,12 +438,7 @@ __global__ __launch_bounds__(256) void stem7_pool_kernel(const StemArgs a) {
     const int hc = 2 * hp - 1 + i, wc = 2 * wp0 - 1 + j;
     float v = -INFINITY;                                    // the pool's padding
     if (hc >= 0 && hc < a.Hc && wc >= 0 && wc < a.Wc) {
-      float s = 0.f;
-#pragma unroll
-      for (int kh = 0; kh < 7; ++kh)
-#pragma unroll
-        for (int kw = 0; kw < 7; ++kw) s = fmaf(patch[2 * i + kh][2 * j + kw], wk[kh * 7 + kw], s);
-      v = nsid_act(s + bias, NSID_ACT_RELU);
+      v = nsid_act(stem7_conv(patch, i, j, wk) + bias, NSID_ACT_RELU);
     }
     cmap[pix][chn] = v;
   }
@@ -434,6 +453,204 @@ __global__ __launch_bounds__(256) void stem7_pool_kernel(const StemArgs a) {
 #pragma unroll
       for (int j = 0; j < 3; ++j) m = fmaxf(m, cmap[i * ST_CW + 2 * pw + j][chn]);
     out[(((long)b * a.Hp + hp) * a.Wp + wp) * 64 + chn] = (T)m;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- stem, training
+// Training mode: bn1 normalises with batch statistics. stem7_stat_kernel leaves the per-channel sum / sum of squares of the RAW conv
+// output r (each conv pixel is computed once and summed directly: no Gram matrix of the input); nsid_bn_finalize turns them into
+// the affine; stem7_fold_kernel folds it into the weights on the device (wf = w * scale, bias = shift) and stem7_pool_kernel runs as
+// in eval mode. Nothing of the conv plane is stored: stem7_bwd_kernel recomputes it from x.
+//
+// Backward (input: dpool on the pooled rows; the network's input is data, so there is no dx). With q(P, c) the conv pixel that wins
+// pooled pixel P's window in channel c (first maximum in scan order), g = dpool[P, c] where the winning value is > 0 (else 0),
+// xh = (r - mean) * invstd, N = B * Hc * Wc and patch_t(q) the input under tap t of conv pixel q:
+//   dbeta_c = a_c = sum_P g            dgamma_c = b_c = sum_P g * xh_c(q)
+//   A_ct = sum_P g * patch_t(q)        S_t = sum_{all q} patch_t(q)         X_ct = sum_{all q} xh_c(q) * patch_t(q)
+//   dW_ct = gamma_c * invstd_c * (A_ct - (a_c / N) * S_t - (b_c / N) * X_ct)
+// Every g-dependent term is a sum over POOLED pixels, so the g map of the conv plane is never formed and workgroups exchange nothing.
+// ONE pass over the input: a workgroup walks tiles of the forward's shape (clip, pooled row, 16 pooled columns), recomputes the
+// 3 x 33 conv pixels with the folded weights through stem7_conv (mask and winner are the forward's) and with the raw ones (r - mean,
+// which X is accumulated from: centred per pixel, no difference of two large sums), adds the conv pixels it OWNS (rows 2 hp, 2 hp + 1,
+// columns 2 wp0 .. 2 wp0 + 31: every conv pixel belongs to exactly one tile) into X and S, and its pooled pixels into a, b, A.
+// Channel = lane; A and X are 2 x 49 registers per thread. A workgroup leaves ONE partial set; stem7_bwd_finalize_kernel adds the
+// sets in workgroup order in fp64 and applies the closed form. No atomics: the result is bitwise reproducible.
+constexpr int STB_MAX_WG = 256;                   // partial sets of the backward (its registers allow one workgroup per CU)
+constexpr int STS_MAX_WG = NSID_STEM7_STAT_MAX;    // statistics tiles of stem7_stat_kernel (nsid_bn_finalize accepts up to this count)
+constexpr int STB_PART = 2 * 49 * 64 + 3 * 64;    // floats per set: A[49][64], X[49][64], a[64], b[64], S[49] (padded to 64)
+
+struct StemTrainArgs {
+  const float* x; const float* w; const float* scale; const float* shift; const float* mean; const float* invstd;
+  const void* dpool; float* part;
+  int H, W, Hc, Wc, Hp, Wp, tiles_w, ntiles;
+};
+
+__global__ __launch_bounds__(256) void stem7_fold_kernel(const float* __restrict__ w, const float* __restrict__ scale,
+                                                         float* __restrict__ wf) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < 64 * 49) wf[i] = w[i] * scale[i / 49];
+}
+
+__global__ __launch_bounds__(256) void stem7_stat_kernel(const StemTrainArgs a) {
+  __shared__ float patch[ST_PR][ST_PC + 1];
+  __shared__ float red[2][4][64];
+  const int tid = threadIdx.x, chn = tid & 63, g = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float wk[49];
+#pragma unroll
+  for (int t = 0; t < 49; ++t) wk[t] = a.w[chn * 49 + t];
+  float s = 0.f, q = 0.f;
+  for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const int tw = tile % a.tiles_w, rest = tile / a.tiles_w;
+    const int hp = rest % a.Hp, b = rest / a.Hp, wp0 = tw * ST_PW;
+    __syncthreads();                                        // the previous tile's patch has been read
+    stem7_load_patch(patch, a.x, a.H, a.W, b, hp, wp0, tid);
+    __syncthreads();
+    for (int pix = g; pix < 2 * 2 * ST_PW; pix += 4) {      // the owned conv pixels: i = 1, 2, j = 1 .. 32
+      const int i = 1 + pix / (2 * ST_PW), j = 1 + pix % (2 * ST_PW);
+      if (2 * hp - 1 + i < a.Hc && 2 * wp0 - 1 + j < a.Wc) {
+        const float r = stem7_conv(patch, i, j, wk);
+        s += r;
+        q = fmaf(r, r, q);
+      }
+    }
+  }
+  red[0][g][chn] = s;
+  red[1][g][chn] = q;
+  __syncthreads();
+  if (tid < 64) {
+    a.part[(long)blockIdx.x * 64 + tid] = ((red[0][0][tid] + red[0][1][tid]) + red[0][2][tid]) + red[0][3][tid];
+    a.part[((long)gridDim.x + blockIdx.x) * 64 + tid] = ((red[1][0][tid] + red[1][1][tid]) + red[1][2][tid]) + red[1][3][tid];
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void stem7_bwd_kernel(const StemTrainArgs a) {
+  constexpr int NPIX = 3 * ST_CW;
+  __shared__ float patch[ST_PR][ST_PC + 1];
+  __shared__ float lds[2 * NPIX * 64];                      // cmap | rmap; the four waves' accumulators at the end
+  float (*cmap)[64] = reinterpret_cast<float (*)[64]>(lds);                 // relu(bn(r)) as the forward computes it (-inf: pool padding)
+  float (*rmap)[64] = reinterpret_cast<float (*)[64]>(lds + NPIX * 64);     // r - mean
+  const int tid = threadIdx.x, chn = tid & 63, g = __builtin_amdgcn_readfirstlane(tid >> 6);
+  float wr[49], wf[49];
+  {
+    const float sc = a.scale[chn];
+#pragma unroll
+    for (int t = 0; t < 49; ++t) {
+      wr[t] = a.w[chn * 49 + t];
+      wf[t] = wr[t] * sc;                                   // stem7_fold_kernel's product
+    }
+  }
+  const float shift = a.shift[chn], mean = a.mean[chn], invstd = a.invstd[chn];
+  const int kh_l = (chn < 49 ? chn : 0) / 7, kw_l = (chn < 49 ? chn : 0) % 7;      // lane t < 49 sums S_t
+  float A[49], X[49];
+#pragma unroll
+  for (int t = 0; t < 49; ++t) A[t] = X[t] = 0.f;
+  float sa = 0.f, sb = 0.f, S = 0.f;
+  const T* dpool = static_cast<const T*>(a.dpool);
+  for (int tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
+    const int tw = tile % a.tiles_w, rest = tile / a.tiles_w;
+    const int hp = rest % a.Hp, b = rest / a.Hp, wp0 = tw * ST_PW;
+    __syncthreads();                                        // the previous tile's maps and patch have been read
+    stem7_load_patch(patch, a.x, a.H, a.W, b, hp, wp0, tid);
+    __syncthreads();
+    for (int pix = g; pix < NPIX; pix += 4) {               // uniform per wave: the patch reads are broadcasts
+      const int i = pix / ST_CW, j = pix - i * ST_CW;
+      const int hc = 2 * hp - 1 + i, wc = 2 * wp0 - 1 + j;
+      float v = -INFINITY, rc = 0.f;
+      if (hc >= 0 && hc < a.Hc && wc >= 0 && wc < a.Wc) {
+        v = nsid_act(stem7_conv(patch, i, j, wf) + shift, NSID_ACT_RELU);
+        rc = stem7_conv(patch, i, j, wr) - mean;
+        if (i >= 1 && j >= 1 && j <= 2 * ST_PW) {           // owned by this tile
+#pragma unroll
+          for (int kh = 0; kh < 7; ++kh)
+#pragma unroll
+            for (int kw = 0; kw < 7; ++kw) X[kh * 7 + kw] = fmaf(rc, patch[2 * i + kh][2 * j + kw], X[kh * 7 + kw]);
+          if (chn < 49) S += patch[2 * i + kh_l][2 * j + kw_l];
+        }
+      }
+      cmap[pix][chn] = v;
+      rmap[pix][chn] = rc;
+    }
+    __syncthreads();
+    for (int pw = g; pw < ST_PW; pw += 4) {
+      const int wp = wp0 + pw;
+      if (wp >= a.Wp) break;
+      float m = -INFINITY;
+      int win = ST_CW + 2 * pw + 1;                         // the window's centre is always inside the conv map
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          const int p = i * ST_CW + 2 * pw + j;
+          const float v = cmap[p][chn];
+          if (v > m) { m = v; win = p; }                    // strict: the first maximum in scan order
+        }
+      const float gv = m > 0.f ? (float)dpool[(((long)b * a.Hp + hp) * a.Wp + wp) * 64 + chn] : 0.f;
+      const int wi = win / ST_CW, wj = win - wi * ST_CW;
+      sa += gv;
+      sb = fmaf(gv, rmap[win][chn] * invstd, sb);
+#pragma unroll
+      for (int kh = 0; kh < 7; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 7; ++kw) A[kh * 7 + kw] = fmaf(gv, patch[2 * wi + kh][2 * wj + kw], A[kh * 7 + kw]);
+    }
+  }
+  // the four waves' sums in wave order; set layout: A[t][c], X[t][c], a[c], b[c], S[t]
+  float* part = a.part + (long)blockIdx.x * STB_PART;
+  float (*acc)[49][64] = reinterpret_cast<float (*)[49][64]>(lds);
+  for (int which = 0; which < 2; ++which) {
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 49; ++t) acc[g][t][chn] = which == 0 ? A[t] : X[t];
+    __syncthreads();
+    for (int t = g; t < 49; t += 4)
+      part[which * 49 * 64 + t * 64 + chn] = ((acc[0][t][chn] + acc[1][t][chn]) + acc[2][t][chn]) + acc[3][t][chn];
+  }
+  __syncthreads();
+  acc[g][0][chn] = sa;
+  acc[g][1][chn] = sb;
+  acc[g][2][chn] = S;
+  __syncthreads();
+  if (g < 3) part[2 * 49 * 64 + g * 64 + chn] = ((acc[0][g][chn] + acc[1][g][chn]) + acc[2][g][chn]) + acc[3][g][chn];
+}
+
+// one workgroup per tap t, 4 x 64 threads = (quarter of the partial sets) x channel: the sets in order, fp64, then the closed form
+__global__ __launch_bounds__(256) void stem7_bwd_finalize_kernel(const float* __restrict__ part, int nset, double N,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ invstd,
+                                                                 float* __restrict__ dw, float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta) {
+  __shared__ double red[5][4][64];
+  const int t = blockIdx.x, c = threadIdx.x & 63, g = threadIdx.x >> 6;
+  const int per = (nset + 3) / 4, s0 = g * per, s1 = min(nset, s0 + per);
+  double v[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+  const int off[5] = {t * 64 + c, 49 * 64 + t * 64 + c, 2 * 49 * 64 + c, 2 * 49 * 64 + 64 + c, 2 * 49 * 64 + 128 + t};
+  constexpr int UB = 4;                         // loads of a batch issue before the first add; the order of the adds is the set order
+  int s = s0;
+  for (; s + UB <= s1; s += UB) {
+    float l[UB][5];
+#pragma unroll
+    for (int u = 0; u < UB; ++u)
+#pragma unroll
+      for (int k = 0; k < 5; ++k) l[u][k] = part[(long)(s + u) * STB_PART + off[k]];
+#pragma unroll
+    for (int u = 0; u < UB; ++u)
+#pragma unroll
+      for (int k = 0; k < 5; ++k) v[k] += (double)l[u][k];
+  }
+  for (; s < s1; ++s)
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] += (double)part[(long)s * STB_PART + off[k]];
+#pragma unroll
+  for (int k = 0; k < 5; ++k) red[k][g][c] = v[k];
+  __syncthreads();
+  if (g != 0) return;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) v[k] = ((red[k][0][c] + red[k][1][c]) + red[k][2][c]) + red[k][3][c];
+  const double A = v[0], X = v[1] * (double)invstd[c], sa = v[2], sb = v[3], S = v[4];
+  dw[c * 49 + t] = (float)((double)gamma[c] * (double)invstd[c] * (A - sa / N * S - sb / N * X));
+  if (t == 0) {
+    dgamma[c] = (float)sb;
+    dbeta[c] = (float)sa;
   }
 }
 
@@ -1013,6 +1230,71 @@ extern "C" int nsid_stem7_pool_fwd(const float* x, int B, int H, int W, const fl
   nsid_count(NSID_C_stem7_pool);
   const dim3 grid((a.Wp + ST_PW - 1) / ST_PW, a.Hp, B);
   NSID_DISPATCH_DTYPE(out_dtype, T, NSID_LAUNCH(stem7_pool_kernel<T>, grid, dim3(256), 0, static_cast<hipStream_t>(stream), a));
+  return nsid_launch_status();
+}
+
+static inline void stem_train_dims(StemTrainArgs& a, int H, int W) {
+  a.H = H; a.W = W;
+  a.Hc = (H - 1) / 2 + 1; a.Wc = (W - 1) / 2 + 1;
+  a.Hp = (a.Hc - 1) / 2 + 1; a.Wp = (a.Wc - 1) / 2 + 1;
+  a.tiles_w = (a.Wp + ST_PW - 1) / ST_PW;
+}
+
+// tiles of the training-mode stem kernels (clip, pooled row, 16 pooled columns) for rows = B * Hp and cols = Wp, and the number of
+// partial sets the statistics (which = 0) / the backward (which = 1) leave
+extern "C" long nsid_stem7_partials(long rows, long cols, int which) {
+  const long tiles = rows * ((cols + ST_PW - 1) / ST_PW);
+  const long cap = which == 0 ? STS_MAX_WG : STB_MAX_WG;
+  return tiles < cap ? tiles : cap;
+}
+extern "C" long nsid_stem7_bwd_set_floats(void) { return STB_PART; }
+
+extern "C" int nsid_stem7_stat(const float* x, int B, int H, int W, const float* w, float* stat, void* stream) {
+  NSID_REQUIRE(x && w && stat && B > 0 && B <= 65535 && H > 0 && W > 0);
+  StemTrainArgs a{};
+  a.x = x; a.w = w; a.part = stat;
+  stem_train_dims(a, H, W);
+  NSID_REQUIRE(a.Hp <= 65535 && (long)B * a.Hp * a.Wp < (1L << 31) / 64);
+  a.ntiles = B * a.Hp * a.tiles_w;
+  nsid_count(NSID_C_stem7_stat);
+  NSID_LAUNCH(stem7_stat_kernel, dim3((unsigned)nsid_stem7_partials((long)B * a.Hp, a.Wp, 0)), dim3(256), 0,
+              static_cast<hipStream_t>(stream), a);
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_stem7_pool_train_fwd(const float* x, int B, int H, int W, const float* w, const float* scale, const float* shift,
+                                         float* wf, void* out, int out_dtype, void* stream) {
+  NSID_REQUIRE(x && w && scale && shift && wf && out && B > 0 && B <= 65535 && H > 0 && W > 0 && NSID_DTYPE_OK(out_dtype));
+  StemArgs a{};
+  a.x = x; a.w = wf; a.bias = shift; a.out = out;
+  a.H = H; a.W = W;
+  a.Hc = (H - 1) / 2 + 1; a.Wc = (W - 1) / 2 + 1;
+  a.Hp = (a.Hc - 1) / 2 + 1; a.Wp = (a.Wc - 1) / 2 + 1;
+  NSID_REQUIRE(a.Hp <= 65535 && (long)B * a.Hp * a.Wp < (1L << 31) / 64);
+  nsid_count(NSID_C_stem7_pool_train);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  NSID_LAUNCH(stem7_fold_kernel, dim3((64 * 49 + 255) / 256), dim3(256), 0, s, w, scale, wf);
+  const dim3 grid((a.Wp + ST_PW - 1) / ST_PW, a.Hp, B);
+  NSID_DISPATCH_DTYPE(out_dtype, T, NSID_LAUNCH(stem7_pool_kernel<T>, grid, dim3(256), 0, s, a));
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_stem7_bwd(const void* dpool, int dpool_dtype, const float* x, int B, int H, int W, const float* w,
+                              const float* scale, const float* shift, const float* mean, const float* invstd, const float* gamma,
+                              float* ws, float* dw, float* dgamma, float* dbeta, void* stream) {
+  NSID_REQUIRE(dpool && x && w && scale && shift && mean && invstd && gamma && ws && dw && dgamma && dbeta);
+  NSID_REQUIRE(B > 0 && B <= 65535 && H > 0 && W > 0 && NSID_DTYPE_OK(dpool_dtype));
+  StemTrainArgs a{};
+  a.x = x; a.w = w; a.scale = scale; a.shift = shift; a.mean = mean; a.invstd = invstd; a.dpool = dpool; a.part = ws;
+  stem_train_dims(a, H, W);
+  NSID_REQUIRE(a.Hp <= 65535 && (long)B * a.Hp * a.Wp < (1L << 31) / 64);
+  a.ntiles = B * a.Hp * a.tiles_w;
+  const int nset = (int)nsid_stem7_partials((long)B * a.Hp, a.Wp, 1);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  nsid_count(NSID_C_stem7_bwd);
+  NSID_DISPATCH_DTYPE(dpool_dtype, T, NSID_LAUNCH(stem7_bwd_kernel<T>, dim3((unsigned)nset), dim3(256), 0, s, a));
+  NSID_LAUNCH(stem7_bwd_finalize_kernel, dim3(49), dim3(256), 0, s, ws, nset, (double)B * a.Hc * a.Wc, gamma, invstd, dw, dgamma,
+              dbeta);
   return nsid_launch_status();
 }
 

@@ -72,11 +72,13 @@ extern "C" int nsid_sumsq_blocks(long n);
 extern "C" size_t nsid_ntxent_ws_floats(int Bg);
 extern "C" size_t nsid_baseline_loss_ws_floats(int M, int D);
 extern "C" int nsid_conv2d_wgrad_splits(long M, long welems);
+extern "C" long nsid_stem7_partials(long rows, long cols, int which);
+extern "C" long nsid_stem7_bwd_set_floats(void);
 extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
   if (op == nullptr || rows < 0 || cols < 0) return -1;
   static const char* const kNone[] = {"knn_graph", "mr_aggregate", "linear", "linear_bwd_data", "linear_bwd_weight", "downsample3",
                                       "peak_patchify", "bn_apply", "node_mean", "l2norm", "adam", "ffn_fused", "mrconv_fused",
-                                      "conv2d", "ibn_relu", "stem7_pool", "gem_pool", "conv2d_bwd_data", "col_stat", "bn_add_relu",
+                                      "conv2d", "ibn_relu", "stem7_pool", "stem7_pool_train", "gem_pool", "conv2d_bwd_data", "col_stat", "bn_add_relu",
                                       "relu_bwd"};
   for (const char* n : kNone)
     if (strcmp(op, n) == 0) return 0;
@@ -94,6 +96,10 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
   }
   if (strcmp(op, "ibn_relu_bwd") == 0)       // rows = clips, cols = channels: [2][clips][C] partial sums + the BatchNorm half's two means
     return (2L * rows * cols + cols) * (long)sizeof(float);
+  if (strcmp(op, "stem7_stat") == 0)         // rows = clips * pooled rows, cols = pooled columns: [2][partial sets][64]
+    return 2L * nsid_stem7_partials(rows, cols, 0) * 64 * (long)sizeof(float);
+  if (strcmp(op, "stem7_bwd") == 0)          // the same rows / cols: one set of (A, X, a, b, S) partial sums per workgroup
+    return nsid_stem7_partials(rows, cols, 1) * nsid_stem7_bwd_set_floats() * (long)sizeof(float);
   if (strcmp(op, "sumsq") == 0)              // rows = elements of the flat gradient
     return (long)nsid_sumsq_blocks(rows) * (long)sizeof(float);
   if (strcmp(op, "flat_l2_topk") == 0)       // rows = query rows, cols = database rows; for k = 64

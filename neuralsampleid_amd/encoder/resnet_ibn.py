@@ -10,7 +10,8 @@ ResidualIBN block:
     conv2 3x3 stride s, bn2 folded (no activation)                          nsid_conv2d_fwd
     relu(conv3 1x1 with bn3 folded + identity)                              nsid_conv2d_fwd (1x1 form: addend + ReLU epilogue)
 Packed / folded weights and their bf16 shadows are cached by ops.folded_conv_bn (parameter versions and state epochs in the key), so
-a load_state_dict is seen by the next forward. The module forward raises in training mode and on CPU tensors.
+a load_state_dict is seen by the next forward. The module forward raises on CPU tensors; in training mode ResNetIBN.forward is the
+training path below (the block and pooling modules on their own still refuse it).
 
 Training exists from the stem's output rows on: ResidualIBN.train_rows (one autograd.Function per block: batch statistics in all
 four BatchNorms, running statistics updated as nn.BatchNorm2d does, nothing folded) and ResNetIBN.trunk_train (the eight blocks and
@@ -24,7 +25,12 @@ head_train). Per block, forward / backward:
     downsample 1x1 stride s (raw rd)       nsid_linear_fwd (s = 1) / nsid_conv2d_fwd + nsid_col_stat (s = 2), nsid_bn_finalize
     relu(bn3(r3) + bn_d(rd) or x)          nsid_bn_add_relu_fwd                 / nsid_relu_bwd, nsid_bn_bwd_*
 Saved for backward per block: the input rows x (the previous block's output), the raw conv outputs r1, r2, r3, rd, the output rows
-(the next block's x) and the per-channel affines. What has no backward yet is the stem (7x7 conv, bn1, max-pool)."""
+(the next block's x) and the per-channel affines.
+
+The stem trains too (ResNetIBN.stem_train, _StemTrainFn): nsid_stem7_stat -> nsid_bn_finalize (bn1's running statistics move) ->
+nsid_stem7_pool_train_fwd (the batch affine folded into conv1's weight on the device) / nsid_stem7_bwd, which recomputes the conv
+from the input: saved are only the input and the affine. ResNetIBN.forward in training mode is stem_train + trunk_train, so
+model.train()(x) is differentiable in every parameter; IBN.forward, ResidualBlock and GeMPooling.forward keep their refusals."""
 import torch
 import torch.nn as nn
 
@@ -293,6 +299,28 @@ class _BlockTrainFn(torch.autograd.Function):
         return (dx, None, None, None, None) + tuple(grads)
 
 
+class _StemTrainFn(torch.autograd.Function):
+    """conv1 7x7 s2 -> bn1 (batch statistics) -> ReLU -> max-pool 3x3 s2 on x (B, H, W) -> rows (B*Hp*Wp, 64). Saved: x and the
+    affine; the input is data and gets no gradient"""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, bn, dtype):
+        w49 = ops.w2d(w)
+        stat, tiles, N = ops.stem7_stat(x, w49)
+        aff = ops.bn_finalize(stat, N, gamma, beta, bn.running_mean, bn.running_var, bn.num_batches_tracked, bn.momentum, bn.eps,
+                              tiles=tiles)
+        rows, _, _ = ops.stem7_pool_train_fwd(x, w49, aff, dtype)
+        ctx.save_for_backward(x, w, gamma)
+        ctx.aff = aff
+        return rows
+
+    @staticmethod
+    def backward(ctx, drows):
+        x, w, gamma = ctx.saved_tensors
+        dw, dg, db = ops.stem7_bwd(drows.contiguous(), x, ops.w2d(w), ctx.aff, gamma)
+        return None, dw.view_as(w), dg, db, None, None
+
+
 def rows_to_bchw(rows, B, H, W):
     """channels-last rows (B*H*W, C) -> the reference's (B, C, H, W) fp32 tensor (module boundary / tests: off the hot path)"""
     return rows.float().view(B, H, W, rows.shape[1]).permute(0, 3, 1, 2).contiguous()
@@ -357,5 +385,24 @@ class ResNetIBN(nn.Module):
                 rows, H, W = blk.train_rows(rows, B, H, W)
         return self.head_train(rows, B, H * W)
 
+    def stem_train(self, x):
+        """x (B, 84, T) fp32 on the GPU -> (rows (B*Hp*Wp, 64) in ACT_DTYPE, Hp, Wp), differentiable, in training mode: bn1 normalises
+        with the statistics of this batch and its running statistics and num_batches_tracked move as in nn.BatchNorm2d. Backward
+        fills the gradients of conv1.weight, bn1.weight and bn1.bias."""
+        if not x.is_cuda:
+            raise NotImplementedError("ResNetIBN.stem_train: like the eval-mode forward, the training-mode forward has no CPU path; "
+                                      "move the model and its input to the GPU")
+        if x.dim() != 3:
+            raise ValueError(f"ResNetIBN takes (B, bins, frames) segments, got {tuple(x.shape)}")
+        bn = self.bn1
+        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+            raise NotImplementedError("training-mode BatchNorm on the MI355X path: affine, running statistics, a fixed momentum")
+        H, W = x.shape[1], x.shape[2]
+        rows = _StemTrainFn.apply(x.float().contiguous(), self.conv1.weight, bn.weight, bn.bias, bn, F_.ACT_DTYPE)
+        return rows, ops.conv_out_size(ops.conv_out_size(H, 7, 2), 3, 2), ops.conv_out_size(ops.conv_out_size(W, 7, 2), 3, 2)
+
     def forward(self, x):
+        if self.training:
+            rows, H, W = self.stem_train(x)
+            return self.trunk_train(rows, x.shape[0], H, W)
         return self.forward_rows(x)

@@ -660,13 +660,16 @@ def _cache_constants(cache, key, entry) -> None:
 
 
 def bn_finalize(stat, M, gamma, beta, running_mean, running_var, num_batches_tracked,
-                momentum=BN_MOMENTUM, eps=BN_EPS) -> BNAffine:
+                momentum=BN_MOMENTUM, eps=BN_EPS, tiles=None) -> BNAffine:
+    """tiles: the number of partial sums per channel in stat (2, tiles, C); None: row_tiles(M), the layout of the GEMM epilogues and
+    of col_stat (stem7_stat leaves another count)"""
     C = gamma.numel()
+    tiles = row_tiles(M) if tiles is None else int(tiles)
     buf = torch.empty((4, C), device=gamma.device, dtype=torch.float32)
     if running_mean is not None:
         bump_state_epoch(weights=False)
-    _tk("bn_finalize_kernel", 8.0 * row_tiles(M) * C + 16.0 * C, lambda: call(
-        "nsid_bn_finalize", _p(stat), row_tiles(M), C, M, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+    _tk("bn_finalize_kernel", 8.0 * tiles * C + 16.0 * C, lambda: call(
+        "nsid_bn_finalize", _p(stat), tiles, C, M, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
         _p(num_batches_tracked), momentum, eps, _p(buf[0]), _p(buf[1]), _p(buf[2]), _p(buf[3]), _stream()), (M, C, 0, 1))
     return BNAffine(buf[0], buf[1], buf[2], buf[3])
 
@@ -2008,6 +2011,64 @@ def col_stat(x, M, C) -> torch.Tensor:
     _tk("col_stat_kernel", float(x.element_size()) * M * C, lambda: call(
         "nsid_col_stat", _p(x), x.stride(0), M, C, _p(stat), dt, _stream()), (M, C, 0, 1))
     return stat
+
+
+def _stem_dims(x, w):
+    if not x.is_cuda:
+        raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if x.dim() != 3 or tuple(w.shape) != (64, 49):
+        raise ValueError("the stem is Conv2d(1, 64, 7) on (B, H, W) segments: w (64, 49)")
+    B, H, W = x.shape
+    Hc, Wc = conv_out_size(H, 7, 2), conv_out_size(W, 7, 2)
+    return B, H, W, Hc, Wc, conv_out_size(Hc, 3, 2), conv_out_size(Wc, 3, 2)
+
+
+def stem7_stat(x, w49):
+    """x (B, H, W) fp32, w49 (64, 49) the RAW conv1 weight -> (stat, tiles, N): per-channel sum and sum of squares of the raw 7x7
+    stride-2 conv output over its N = B*Hc*Wc pixels as (2, tiles, 64) partial sums: bn_finalize(stat, N, ..., tiles=tiles). The conv
+    output is not stored. One launch."""
+    _chk(x, w49)
+    B, H, W, Hc, Wc, Hp, Wp = _stem_dims(x, w49)
+    tiles = int(lib.nsid_stem7_partials(B * Hp, Wp, 0))
+    stat = torch.empty((2, tiles, 64), device=x.device, dtype=torch.float32)
+    _timed("stem7_stat_kernel", 2.0 * 49 * 64 * B * Hc * Wc, 4.0 * x.numel() + 4.0 * stat.numel(), lambda: call(
+        "nsid_stem7_stat", _p(x), B, H, W, _p(w49), _p(stat), _stream()), (B * Hc * Wc, 64, 49, 1))
+    return stat, tiles, B * Hc * Wc
+
+
+def stem7_pool_train_fwd(x, w49, aff: "BNAffine", out_dtype=torch.float32):
+    """training-mode stem forward: x (B, H, W) fp32 -> (rows (B*Hp*Wp, 64), Hp, Wp) with the BATCH affine aff (bn_finalize of
+    stem7_stat) folded into the raw weight w49 on the device (no host read), then stem7_pool_fwd's kernel"""
+    _chk(x, w49, aff.scale, aff.shift)
+    B, H, W, Hc, Wc, Hp, Wp = _stem_dims(x, w49)
+    if aff.scale.numel() != 64:
+        raise ValueError("stem7_pool_train_fwd: the stem is Conv2d(1, 64, 7)")
+    out = torch.empty((B * Hp * Wp, 64), device=x.device, dtype=out_dtype)
+    wf = torch.empty((64, 49), device=x.device, dtype=torch.float32)
+    _timed("stem7_pool_kernel<train>", 2.0 * 49 * 64 * B * Hc * Wc, 4.0 * x.numel() + float(out.element_size()) * out.numel(),
+           lambda: call("nsid_stem7_pool_train_fwd", _p(x), B, H, W, _p(w49), _p(aff.scale), _p(aff.shift), _p(wf), _p(out),
+                        _act(out), _stream()), (B * Hp * Wp, 64, 49, 1))
+    return out, Hp, Wp
+
+
+def stem7_bwd(dpool, x, w49, aff: "BNAffine", gamma):
+    """backward of the training-mode stem: dpool (B*Hp*Wp, 64) rows fp32 or bf16, x (B, H, W), the raw weight w49, the batch affine
+    of the forward and bn1.weight -> (dW (64, 49), dgamma (64,), dbeta (64,)) fp32. The conv output is recomputed from x (nothing
+    of it was stored); ReLU mask and window winner are the forward's bit for bit; no atomics (bitwise reproducible)."""
+    _chk(x, w49, aff.scale, aff.shift, aff.mean, aff.invstd, gamma)
+    dt = _act(dpool)
+    B, H, W, Hc, Wc, Hp, Wp = _stem_dims(x, w49)
+    if tuple(dpool.shape) != (B * Hp * Wp, 64) or gamma.numel() != 64 or aff.scale.numel() != 64:
+        raise ValueError(f"stem7_bwd: dpool {tuple(dpool.shape)} does not match x {tuple(x.shape)}")
+    nws = lib.nsid_workspace_bytes(b"stem7_bwd", B * Hp, Wp)
+    ws = torch.empty((nws // 4,), device=x.device, dtype=torch.float32)
+    out = torch.empty((64 * 49 + 128,), device=x.device, dtype=torch.float32)
+    dw, dg, db = out[:64 * 49].view(64, 49), out[64 * 49:64 * 49 + 64], out[64 * 49 + 64:]
+    _timed("stem7_bwd_kernel", 2.0 * 64 * 49 * (1.5 * 3 * B * Hc * Wc + B * Hp * Wp),
+           4.0 * x.numel() + float(dpool.element_size()) * dpool.numel() + 2.0 * nws,
+           lambda: call("nsid_stem7_bwd", _p(dpool), dt, _p(x), B, H, W, _p(w49), _p(aff.scale), _p(aff.shift), _p(aff.mean),
+                        _p(aff.invstd), _p(gamma), _p(ws), _p(dw), _p(dg), _p(db), _stream()), (B * Hc * Wc, 64, 49, 1))
+    return dw, dg, db
 
 
 def ibn_relu_bwd(dy, r, B, HW, C, in_gamma, in_beta, bn_aff: "BNAffine", d_in_gamma, d_in_beta, d_bn_gamma, d_bn_beta,

@@ -12,7 +12,7 @@ from . import ops
 
 class FusedClipAdam:
     def __init__(self, params: Iterable[torch.nn.Parameter], lr: float = 8e-5, betas=(0.9, 0.999), eps: float = 1e-8,
-                 max_norm: float = 1.0, direct_grads: bool = True):
+                 max_norm: float = 1.0, direct_grads: bool = True, ds_prep: bool = True):
         self.params: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
         if not self.params:
             raise ValueError("no trainable parameters")
@@ -40,9 +40,11 @@ class FusedClipAdam:
         for p, off in zip(self.params, self.offsets):
             if p.numel() % 8 == 0:
                 ops.SHADOWS.register(p.data, self.flat_p16[off:off + p.numel()], owner=self.flat_p)
-        # Downsample conv weights (Cout, Cin, 3, 3): packed forms + shared packed gradient prepared once per step (ops.DsPrep)
+        # Downsample conv weights (Cout, Cin, 3, 3): packed forms + shared packed gradient prepared once per step (ops.DsPrep).
+        # ds_prep=False: a model whose 3x3 weights are not the GNN's Downsample convolutions (the ResNet-IBN baseline's eight conv2
+        # would take the eight slots of that preparation)
         for p in self.params:            # (register purges the entries of weights that are gone or were re-flattened)
-            if p.dim() == 4 and tuple(p.shape[2:]) == (3, 3):
+            if ds_prep and p.dim() == 4 and tuple(p.shape[2:]) == (3, 3):
                 ops.DS_PREP.register(p)
         self.hyper = torch.tensor([lr, betas[0], betas[1], eps, max_norm if max_norm else 0.0], device=dev)
         self.step_count = torch.zeros((), dtype=torch.int64, device=dev)

@@ -1,7 +1,8 @@
 """Mirror of simclr/triplet.py (reference :6-83): BaselineModel.forward(x_i, x_j) -> (h_i, h_j, z_i, z_j) with
 z = F.normalize(h, p=2, eps=1e-10) and an identity projector, and the two losses of the baseline's training step with the reference's
 signatures, each one fused call of csrc/baseline_loss.hip, forward and backward. baseline_objective is the whole objective of
-baseline/train.py:66-77 in one call. There is no host path: CPU tensors raise."""
+baseline/train.py:66-77 in one call. BaselineModel.train()(x_i, x_j) is the differentiable training forward (tools/
+baseline_train_synthetic.py runs the reference's whole step with it). There is no host path: CPU tensors raise."""
 import torch
 import torch.nn as nn
 
@@ -87,7 +88,27 @@ def baseline_objective(z_i, z_j, margin=0.2, beta=1.0, gamma=1.0):
     return _ObjectiveFn.apply(zi, zj, float(margin), float(beta), float(gamma), torch.is_grad_enabled())
 
 
+class _L2NormFn(torch.autograd.Function):
+    """z = h / max(|h|, eps) per row (nsid_l2norm_fwd / nsid_l2norm_bwd)"""
+
+    @staticmethod
+    def forward(ctx, h, eps):
+        z, norm = ops.l2norm_fwd(h, eps)
+        ctx.save_for_backward(z, norm)
+        ctx.eps = eps
+        return z
+
+    @staticmethod
+    def backward(ctx, dz):
+        z, norm = ctx.saved_tensors
+        return ops.l2norm_bwd(dz.contiguous().float(), z, norm, ctx.eps), None
+
+
 class BaselineModel(nn.Module):
+    """forward(x_i, x_j) -> (h_i, h_j, z_i, z_j). In training mode (ResNetIBN encoder) the call is differentiable; as in the reference
+    each view is an encoder pass of its own: batch statistics per view, and every BatchNorm's running statistics and counter move
+    twice per call."""
+
     def __init__(self, cfg, encoder):
         super().__init__()
         self.encoder = encoder
@@ -96,6 +117,8 @@ class BaselineModel(nn.Module):
 
     def _embed(self, x):
         h = self.encoder(x)
+        if self.training:
+            return h, _L2NormFn.apply(self.projector(h).contiguous(), NORM_EPS)
         z, _ = ops.l2norm_fwd(self.projector(h), NORM_EPS)
         return h, z
 
