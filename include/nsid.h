@@ -398,6 +398,30 @@ int nsid_aug_istft(const float* spec, long T_out_max, int B, long L, const float
 int nsid_aug_finish(const float* wave, long wave_stride, int B, long L, const int* mode, const float* rate, float rate_lo,
                     float rate_hi, const float* table, float* out, long out_stride, void* stream);
 
+/* The baseline's waveform effects (csrc/augment_fx.hip): what the reference's fx_util chain adds for arch 'resnet-ibn' -- Compressor
+ * and BandEQ on the sample stems (T1), FrameLevelCorruption on the mix (T2) -- one launch each for a batch of B clips of L float32
+ * samples (row strides in elements). A clip whose mode selects another transform is neither read nor written. All arithmetic is
+ * unfused (no fused multiply-adds). No atomics: clip b of a batch is bit-equal to the clip alone.
+ *   compress: clips with mode1[b] == 1. cmp[b] = {threshold, ratio, attack, release} (fp64, device), clamped per clip to threshold >= 0,
+ *             ratio >= 1, attack and release in [0, 1] (a NaN becomes the lower end). g = 1; per sample, a = |x[n]| in fp64:
+ *             if a > threshold { t = threshold + (a - threshold) / ratio; g = g > t ? attack * g + (1 - attack) * t
+ *             : release * g + (1 - release) * t }; out[n] = float(double(x[n]) * g). Every operation is one rounded fp64 operation.
+ *   biquad:   clips with mode1[b] == 0. sos[b][s] = {b0, b1, b2, a1, a2, post}, s < S (1 <= S <= 64, fp64, device); n_sec[b] is clamped
+ *             into [0, S]. Sections s < n_sec[b] in order, transposed direct form II in fp64: y = b0 u + z1; z1 = (b1 u - a1 y) + z2;
+ *             z2 = b2 u - a2 y; the section hands on y * post. out[n] = float(output of the last section); n_sec 0: out = x.
+ *   frames:   clips with 2 <= mode2[b] <= 4. frame_size[b] is clamped into [ceil(L / F), L] (1 <= F <= 256); the clip is cut into
+ *             consecutive frames (the last may be short); frame f with frame_ops[b][f] bit 2 is dropped, else with bit 1 it appears
+ *             twice; with bit 4 it is zeros. out[b] = the first L samples of the concatenation, zeros past its end, where a sample
+ *             taken from position p is float(float(gain[b] * t1[b][p]) + x_i[b][p]).
+ * NSID_EINVAL before any launch: null pointers, B < 1, L < 1 or L >= 2^30, strides shorter than rows, S or F outside their ranges,
+ * cmp / sos not 8-byte aligned. */
+int nsid_aug_compress(const float* x, long stride_x, int B, long L, const int* mode1, const double* cmp, float* out, long stride_o,
+                      void* stream);
+int nsid_aug_biquad(const float* x, long stride_x, int B, long L, const int* mode1, const double* sos, int S, const int* n_sec,
+                    float* out, long stride_o, void* stream);
+int nsid_aug_frames(const float* x_i, long stride_i, const float* t1, long stride_t, const float* gain, int B, long L,
+                    const int* mode2, const int* frame_size, const int* frame_ops, int F, float* out, long stride_o, void* stream);
+
 /* bf16 shadow of fp32 weights: dst[i] = bf16_rne(src[i]), n % 8 == 0, both 16-byte aligned (operand `w` of
  * nsid_linear_fwd / nsid_linear_bwd_data with w_dtype = NSID_BF16). */
 int nsid_f32_to_bf16(const float* src, void* dst, long n, void* stream);

@@ -71,6 +71,9 @@ SIGNATURES = {
     "nsid_aug_vocoder": "pilpffpls",
     "nsid_aug_istft": "plilpffpppls",
     "nsid_aug_finish": "plilppffppls",
+    "nsid_aug_compress": "plilpppls",
+    "nsid_aug_biquad": "plilppippls",
+    "nsid_aug_frames": "plplpilpppipls",
     "nsid_bcn_to_rows": "piiipiis",
     "nsid_rows_to_bcn": "piiiipis",
     "nsid_batched_index_select_fwd": "ppiiiiips",

@@ -240,6 +240,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(logmel_fft)           /* frontend.hip: batched log-mel front end in one launch */ \
   X(cqt)                  /* cqt.hip: batched constant-Q front end in one launch */ \
   X(aug_stft) X(aug_vocoder) X(aug_istft) X(aug_finish)   /* augment.hip: waveform augmentations, one launch per stage */ \
+  X(aug_compress) X(aug_biquad) X(aug_frames)   /* augment_fx.hip: the baseline's compressor, band EQ and frame edits */ \
   X(conv2d_3x3) X(conv2d_1x1) X(ibn_relu) X(stem7_pool) X(gem_pool)   /* resnet.hip: the ResNet-IBN baseline's eval-mode forward */ \
   X(pair_ce) X(triplet) X(baseline_objective)   /* baseline_loss.hip: the baseline's training objective, one count per call */ \
   X(gem_pool_bwd)         /* resnet.hip: backward of the GeM pooling */ \

@@ -1433,6 +1433,73 @@ def aug_finish(wave: torch.Tensor, B: int, L: int, mode: torch.Tensor, rate: tor
     return out
 
 
+# ---- the baseline's waveform effects (csrc/augment_fx.hip, include/nsid.h nsid_aug_compress / _biquad / _frames); modules/
+# transformations.GPUBaselineWaveAugment chains them with the four stages above
+AUG_FX_MAX_SECTIONS, AUG_FX_MAX_FRAMES = 64, 256
+
+
+def _aug_table(name, t, dtype, shape):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+        raise RuntimeError(f"{name} must be a contiguous {dtype} tensor of shape {shape} on the MI355X device")
+
+
+def _aug_out(name, x, out):
+    if out is None:
+        return torch.empty(x.shape, device=x.device, dtype=torch.float32)
+    _aug_waves(name, out)
+    if out.shape != x.shape:
+        raise RuntimeError(f"{name}: out must have the input's shape (B, L)")
+    return out
+
+
+def aug_compress(x: torch.Tensor, mode1: torch.Tensor, cmp: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """the reference's Compressor on the rows with mode1 == 1: cmp (B, 4) fp64 = threshold, ratio, attack, release; the other rows
+    of `out` are not written"""
+    _aug_waves("aug_compress", x)
+    B, L = x.shape
+    _aug_table("aug_compress: mode1", mode1, torch.int32, (B,))
+    _aug_table("aug_compress: cmp", cmp, torch.float64, (B, 4))
+    out = _aug_out("aug_compress", x, out)
+    call("nsid_aug_compress", _p(x), x.stride(0) if B > 1 else L, B, L, _p(mode1), _p(cmp), _p(out),
+         out.stride(0) if B > 1 else L, _stream())
+    return out
+
+
+def aug_biquad(x: torch.Tensor, mode1: torch.Tensor, sos: torch.Tensor, n_sec: torch.Tensor,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a cascade of n_sec[b] second-order sections on the rows with mode1 == 0: sos (B, S, 6) fp64 = b0, b1, b2, a1, a2 and the
+    factor applied to the section's output; the other rows of `out` are not written"""
+    _aug_waves("aug_biquad", x)
+    B, L = x.shape
+    if sos.dim() != 3 or not 1 <= sos.shape[1] <= AUG_FX_MAX_SECTIONS:
+        raise RuntimeError(f"aug_biquad: sos must be (B, S, 6) with 1 <= S <= {AUG_FX_MAX_SECTIONS}")
+    _aug_table("aug_biquad: mode1", mode1, torch.int32, (B,))
+    _aug_table("aug_biquad: sos", sos, torch.float64, (B, sos.shape[1], 6))
+    _aug_table("aug_biquad: n_sec", n_sec, torch.int32, (B,))
+    out = _aug_out("aug_biquad", x, out)
+    call("nsid_aug_biquad", _p(x), x.stride(0) if B > 1 else L, B, L, _p(mode1), _p(sos), sos.shape[1], _p(n_sec), _p(out),
+         out.stride(0) if B > 1 else L, _stream())
+    return out
+
+
+def aug_frames(x_i: torch.Tensor, t1: torch.Tensor, gain: torch.Tensor, mode2: torch.Tensor, frame_size: torch.Tensor,
+               frame_ops: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """frame edits of the mix gain * t1 + x_i on the rows with 2 <= mode2 <= 4: frame_ops (B, F) int32 bit masks (1 duplicate, 2
+    remove, 4 silence); the other rows of `out` are not written"""
+    _aug_waves("aug_frames", x_i, t1)
+    B, L = x_i.shape
+    if t1.shape != x_i.shape or frame_ops.dim() != 2 or not 1 <= frame_ops.shape[1] <= AUG_FX_MAX_FRAMES:
+        raise RuntimeError(f"aug_frames: x_i, t1 of one shape (B, L) and frame_ops (B, F) with 1 <= F <= {AUG_FX_MAX_FRAMES}")
+    _aug_table("aug_frames: gain", gain, torch.float32, (B,))
+    _aug_table("aug_frames: mode2", mode2, torch.int32, (B,))
+    _aug_table("aug_frames: frame_size", frame_size, torch.int32, (B,))
+    _aug_table("aug_frames: frame_ops", frame_ops, torch.int32, (B, frame_ops.shape[1]))
+    out = _aug_out("aug_frames", x_i, out)
+    call("nsid_aug_frames", _p(x_i), x_i.stride(0) if B > 1 else L, _p(t1), t1.stride(0) if B > 1 else L, _p(gain), B, L,
+         _p(mode2), _p(frame_size), _p(frame_ops), frame_ops.shape[1], _p(out), out.stride(0) if B > 1 else L, _stream())
+    return out
+
+
 def batched_index_select_fwd(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """x (B, C, N) fp32, idx (B, Nq, k) int32 -> (B, C, Nq, k) — the reference's batched_index_select (torch_nn.py:79-98)"""
     _chk(x)

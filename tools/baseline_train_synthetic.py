@@ -2,7 +2,11 @@
 GPU: model.train()(x_i, x_j), baseline_objective, backward, FusedClipAdam(max_norm=1.0); next to a torch-eager restatement of the same
 step written here from the state_dict (as tools/resnet_train_bench.py does for the trunk), on the same GPU in the same call.
 
-    python tools/baseline_train_synthetic.py [--batch 256] [--steps 10] [--bf16] [--reps 5] [--only-ours] [--no-table]
+    python tools/baseline_train_synthetic.py [--batch 256] [--steps 10] [--bf16] [--reps 5] [--only-ours] [--no-table] [--augment]
+
+--augment runs the loop of baseline/train.py from raw stems instead: synthetic (B, 110 250) stem pairs on the GPU, a fresh draw of
+GPUBaselineWaveAugment per step (the only host work: random numbers and the EQ filter design), GPUTransformCQT(train=True), the step;
+it prints the loss parts and the milliseconds of augmentation, front end and step, and stops there (no interleaved timing).
 
 Prints the loss parts of --steps training steps (fp32 activation storage, or bf16 with --bf16) and their ms per step; then times
   hip_fp32 / hip_bf16         the whole step, fp32 / bf16 activation storage
@@ -151,7 +155,41 @@ def stem_table(model, opt, x_i, x_j, label):
         print(f"  {name[:60]:60s} x{v['launches']:4d} {1e3 * v['ms']:10.1f} us {100.0 * v['ms'] / total:5.1f} %")
 
 
+def run_from_stems(args):
+    """baseline/train.py's loop from waveforms: augment -> CQT -> step, nothing of the signal path on the host"""
+    from baseline_augment_bench import CFG, L, synth_stems
+    from neuralsampleid_amd.modules.transformations import GPUBaselineWaveAugment, GPUTransformCQT
+    B = args.batch
+    F_.set_activation_dtype(torch.bfloat16 if args.bf16 else torch.float32)
+    model = build_model()
+    opt = FusedClipAdam(model.parameters(), lr=args.lr, max_norm=1.0, direct_grads=False, ds_prep=False)
+    gen = torch.Generator().manual_seed(11)
+    augment, front = GPUBaselineWaveAugment(CFG, generator=gen), GPUTransformCQT(CFG, train=True)
+    x_i, x_j = synth_stems(B)
+    for step in range(args.steps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        params = augment.draw(B, generator=gen, device="cuda", L=L)
+        t1 = time.perf_counter()
+        a_i, a_j = augment(x_i, x_j, params)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        X_i, X_j = front(a_i, a_j)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        loss, cls, trip = hip_step(model, opt, X_i, X_j)
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        assert X_i.shape == (B, 84, 216) and bool(torch.isfinite(X_i).all())
+        print(f"step {step:3d} | loss {float(loss):.4f} | cls {float(cls):.4f} | triplet {float(trip):.4f} | grad norm "
+              f"{float(opt.grad_norm):.3f} | draw (host) {1e3 * (t1 - t0):7.2f} ms | augment {1e3 * (t2 - t1):7.2f} ms | CQT "
+              f"{1e3 * (t3 - t2):6.2f} ms | step {1e3 * (t4 - t3):7.2f} ms", flush=True)
+    F_.set_activation_dtype(torch.float32)
+
+
 def run(args):
+    if args.augment:
+        return run_from_stems(args)
     B = args.batch
     x_i, x_j = synth_pairs(B)
     # the training loop itself
@@ -228,6 +266,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only-ours", action="store_true")
     ap.add_argument("--no-table", action="store_true")
+    ap.add_argument("--augment", action="store_true", help="run the loop from raw stems: GPUBaselineWaveAugment, GPUTransformCQT, the step")
     run(ap.parse_args())
 
 
