@@ -422,6 +422,36 @@ int nsid_aug_biquad(const float* x, long stride_x, int B, long L, const int* mod
 int nsid_aug_frames(const float* x_i, long stride_i, const float* t1, long stride_t, const float* gain, int B, long L,
                     const int* mode2, const int* frame_size, const int* frame_ops, int F, float* out, long stride_o, void* stream);
 
+/* Stem pairs from a device-resident bank of resampled tracks (csrc/stems.hip): the DSP of the reference's NeuralSampleIDDataset.
+ * __getitem__ behind the decoder (modules/data.py:45-150). DESIGN.md "Stem pairs" is the definition.
+ *   resample_sinc: torchaudio's Resample(orig, new) with its defaults on the mono downmix of x (C <= 8 rows of T samples, stride_x
+ *             apart): orig, nw are the rates divided by their gcd, width = ceil(6 orig / (0.99 min(orig, nw))). `table` holds, for
+ *             each phase p < nw, the ntap taps k[p][first[p] .. first[p] + ntap) of the (nw, 2 width + orig) filter table in a row of
+ *             ts >= ntap floats; y[q nw + p] = sum_i table[p][i] * xpad[q orig + first[p] + i] (fp32, fused multiply-adds, i
+ *             ascending), xpad = `width` zeros, then (x[0][j] + ... + x[C-1][j]) / C, then zeros. T_out = ceil(nw T / orig).
+ *             NSID_EINVAL: C outside [1, 8], T outside [1, 2^31), a table of more than 64 KiB ((nw ts + nw) * 4 bytes), another T_out.
+ *   The bank: `bank` holds bank_elems floats; track t has three rows (bass + other, vocals, drums) of length[t] samples each from
+ *   element base[t] (int64) on. A clip c of N: track[c] (clamped into [0, n_tracks)), start[c] (clamped into [0, length - W]), W = L + O,
+ *   off_i[c], off_j[c] (clamped into [0, O)), key[c][3].
+ *   gate:     per stem s of the window: tot = (s0 + s1) + s2, sig = tot - s_s, d = sig - s_s (one fp32 operation each); P_sig, P_n =
+ *             the fp64 sums of the (exact) squares; snr[c][s] = float(10 log10((P_sig / W) / (P_n / W + 1e-8))), -inf at P_sig = 0;
+ *             the stem is valid iff P_sig >= 0.1 (P_n + 1e-8 W). Fewer than two valid stems: status 1. Else the valid stems are
+ *             ordered by key ascending (ties: lower index): x_i = the last one from off_i on, x_j = the fp32 sum of the others from
+ *             off_j on, L samples each; status 2 iff max |x_i| < silence or max |x_j| < silence; else 0. status 3: the track's table
+ *             entry is outside the bank or shorter than W (snr = NaN). plan[c] carries the split to the build launch.
+ *   build:    packed == 0: row c of x_i / x_j (N rows) = the clip's crops, zeros where status[c] != 0. packed == 1: the accepted
+ *             clips in order in rows 0 .. n_ok - 1 of B_out rows, n_ok = min(accepted, B_out), zeros from row n_ok on, *n_ok written.
+ * No atomics: every result is bit-equal run to run and independent of the other clips. NSID_EINVAL before any launch: null
+ * pointers, N or B_out outside [1, 65535], L < 1, O < 1, L + O >= 2^30, strides shorter than L. */
+int nsid_resample_sinc(const float* x, long stride_x, int C, long T, int orig, int nw, int width, const float* table,
+                       const int* first, int ntap, int ts, float* y, long T_out, void* stream);
+int nsid_stem_pairs_gate(const float* bank, long bank_elems, const long* base, const int* length, int n_tracks, const int* track,
+                         const int* start, const float* key, const int* off_i, const int* off_j, int N, long L, long O, float silence,
+                         int* status, float* snr, int* plan, void* stream);
+int nsid_stem_pairs_build(const float* bank, long bank_elems, const long* base, const int* length, int n_tracks, const int* track,
+                          const int* start, const int* off_i, const int* off_j, const int* status, const int* plan, int N, long L,
+                          long O, int packed, int B_out, float* x_i, long stride_i, float* x_j, long stride_j, int* n_ok, void* stream);
+
 /* bf16 shadow of fp32 weights: dst[i] = bf16_rne(src[i]), n % 8 == 0, both 16-byte aligned (operand `w` of
  * nsid_linear_fwd / nsid_linear_bwd_data with w_dtype = NSID_BF16). */
 int nsid_f32_to_bf16(const float* src, void* dst, long n, void* stream);

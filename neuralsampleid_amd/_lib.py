@@ -74,6 +74,9 @@ SIGNATURES = {
     "nsid_aug_compress": "plilpppls",
     "nsid_aug_biquad": "plilppippls",
     "nsid_aug_frames": "plplpilpppipls",
+    "nsid_resample_sinc": "pliliiippiipls",
+    "nsid_stem_pairs_gate": "plppipppppillfppps",
+    "nsid_stem_pairs_build": "plppippppppilliiplplps",
     "nsid_bcn_to_rows": "piiipiis",
     "nsid_rows_to_bcn": "piiiipis",
     "nsid_batched_index_select_fwd": "ppiiiiips",

@@ -245,7 +245,8 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(pair_ce) X(triplet) X(baseline_objective)   /* baseline_loss.hip: the baseline's training objective, one count per call */ \
   X(gem_pool_bwd)         /* resnet.hip: backward of the GeM pooling */ \
   X(conv2d_bwd_data) X(conv2d_bwd_weight) X(col_stat) X(ibn_relu_bwd) X(bn_add_relu) X(relu_bwd)   /* resnet.hip: training-mode residual blocks */ \
-  X(stem7_stat) X(stem7_pool_train) X(stem7_bwd)   /* resnet.hip: training-mode stem */
+  X(stem7_stat) X(stem7_pool_train) X(stem7_bwd)   /* resnet.hip: training-mode stem */ \
+  X(resample_sinc) X(stem_pairs_gate) X(stem_pairs_build)   /* stems.hip: sinc resampler, stem-pair sampler */
 
 // nsid_stem7_stat leaves at most this many partial sums per channel (resnet.hip); nsid_bn_finalize accepts such a count next to
 // nsid_row_tiles(M)

@@ -1500,6 +1500,172 @@ def aug_frames(x_i: torch.Tensor, t1: torch.Tensor, gain: torch.Tensor, mode2: t
     return out
 
 
+# ---- stem pairs (csrc/stems.hip, include/nsid.h nsid_resample_sinc / nsid_stem_pairs_*); modules/data.py owns the bank and the draws
+RESAMPLE_WIDTH, RESAMPLE_ROLLOFF = 6, 0.99           # torchaudio's lowpass_filter_width and rolloff defaults
+RESAMPLE_MAX_C, RESAMPLE_LDS_BYTES = 8, 64 * 1024
+_RESAMPLE_TABLES = {}                                # (orig, new, device) -> the compact table on the device
+
+
+def _resample_ratio(orig: int, new: int):
+    """(orig, new) divided by their gcd, width, base"""
+    orig, new = int(orig), int(new)
+    if orig < 1 or new < 1:
+        raise ValueError("resampling rates must be positive integers")
+    g = math.gcd(orig, new)
+    orig, new = orig // g, new // g
+    base = min(orig, new) * RESAMPLE_ROLLOFF
+    return orig, new, int(math.ceil(RESAMPLE_WIDTH * orig / base)), base
+
+
+def _resample_k(p, j, orig, new, width, base):
+    """(t before the clamp, the fp64 filter value) at phases p and taps j (integer arrays that broadcast), in torchaudio's
+    operation order"""
+    t = ((-p).astype(np.float64) / new + (j - width).astype(np.float64) / orig) * base
+    tc = np.clip(t, -RESAMPLE_WIDTH, RESAMPLE_WIDTH)
+    window = np.cos(tc * math.pi / RESAMPLE_WIDTH / 2) ** 2
+    tp = tc * math.pi
+    with np.errstate(invalid="ignore", divide="ignore"):
+        k = np.where(tp == 0, 1.0, np.sin(tp) / tp)
+    return t, k * window * (base / orig)
+
+
+def resample_table(orig: int, new: int) -> np.ndarray:
+    """k[p][j], p < new, j < 2 width + orig (rates divided by their gcd): the polyphase filter of torchaudio's Resample(orig, new)
+    with its defaults, evaluated in fp64 and rounded to fp32 once. The rounded table is part of the resampler's definition."""
+    orig, new, width, base = _resample_ratio(orig, new)
+    if new * (2 * width + orig) > 1 << 26:
+        raise ValueError(f"the full filter table of {orig} -> {new} has {new} x {2 * width + orig} entries: too large to tabulate")
+    _, k = _resample_k(np.arange(new)[:, None], np.arange(2 * width + orig)[None, :], orig, new, width, base)
+    return k.astype(np.float32)
+
+
+def resample_compact(orig: int, new: int, max_bytes: Optional[int] = None):
+    """the live taps of resample_table, computed without the full table: (rows (new, ts) fp32, first (new,) int32, live (new,) int32,
+    ntap, width, orig, new). A tap is live where the clamp did not fire (|t| < 6); phase p's live taps are
+    k[p][first[p] : first[p] + live[p]], its row is zero behind them, ntap = max live, and ts = ntap | 1 is the row stride the kernel
+    keeps in LDS. max_bytes: raise before tabulating when new * (ts + 1) * 4 cannot stay below it."""
+    o, n, width, base = _resample_ratio(orig, new)
+    half = RESAMPLE_WIDTH * o / base                         # |j - width - p o / n| < half
+    if max_bytes is not None and n * int(2 * half) * 4 > max_bytes:          # ts + 1 >= int(2 half): cannot fit
+        raise RuntimeError(f"resample_sinc: the compact filter table of {orig} -> {new} ({n} phases x about {int(2 * half)} taps) "
+                           f"exceeds the {max_bytes} bytes of LDS the kernel keeps it in")
+    p = np.arange(n, dtype=np.int64)[:, None]
+    lo = np.floor(width + p * o / n - half).astype(np.int64) - 2
+    j = lo + np.arange(int(2 * half) + 6, dtype=np.int64)[None, :]
+    t, k = _resample_k(p, j, o, n, width, base)
+    alive = (np.abs(t) < RESAMPLE_WIDTH) & (j >= 0) & (j < 2 * width + o)
+    a0 = alive.argmax(1)
+    live = alive.sum(1).astype(np.int32)
+    first = j[np.arange(n), a0].astype(np.int32)
+    ntap = int(live.max())
+    ts = ntap | 1
+    assert live.min() >= 1 and not alive[:, 0].any() and not alive[:, -1].any()          # the window held every live tap
+    rows = np.zeros((n, ts), dtype=np.float32)
+    k32 = k.astype(np.float32)
+    for q in range(n):
+        assert alive[q, a0[q]:a0[q] + live[q]].all()                                     # one run per phase
+        rows[q, :live[q]] = k32[q, a0[q]:a0[q] + live[q]]
+    if max_bytes is not None and (rows.size + n) * 4 > max_bytes:
+        raise RuntimeError(f"resample_sinc: the compact filter table of {orig} -> {new} ({n} phases x {ntap} taps) exceeds the "
+                           f"{max_bytes} bytes of LDS the kernel keeps it in")
+    return rows, first, live, ntap, width, o, n
+
+
+def resample_out_len(T: int, orig: int, new: int) -> int:
+    g = math.gcd(int(orig), int(new))
+    return -((-(new // g) * T) // (orig // g))
+
+
+def _resample_tables(orig, new, device):
+    key = (int(orig), int(new), torch.device(device))
+    e = _RESAMPLE_TABLES.get(key)
+    if e is None:
+        if orig == new:                              # the downmix alone: one phase, one tap of weight 1
+            rows, first, ntap, width, o, n = np.ones((1, 1), np.float32), np.zeros(1, np.int32), 1, 0, 1, 1
+        else:
+            rows, first, _, ntap, width, o, n = resample_compact(orig, new, RESAMPLE_LDS_BYTES)
+        e = (torch.from_numpy(rows).to(device), torch.from_numpy(first).to(device), ntap, rows.shape[1], width, o, n)
+        _RESAMPLE_TABLES[key] = e
+    return e
+
+
+def resample_sinc(x: torch.Tensor, orig: int, new: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """torchaudio.transforms.Resample(orig, new) (defaults) of the mono downmix of x: (T,) or (C, T) fp32 on the device, C <= 8 ->
+    (ceil(new T / orig),). orig == new returns the input ((T,)) or its downmix ((C, T))."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or x.dim() not in (1, 2) or x.stride(-1) != 1:
+        raise RuntimeError("resample_sinc takes (T,) or (C, T) float32 audio on the MI355X device with a contiguous last dimension; "
+                           "there is no host path")
+    C, T = (1, x.shape[0]) if x.dim() == 1 else x.shape
+    if not 1 <= C <= RESAMPLE_MAX_C or not 1 <= T < 2 ** 31:
+        raise RuntimeError(f"resample_sinc: 1 <= C <= {RESAMPLE_MAX_C} channels of 1 <= T < 2^31 samples, got C = {C}, T = {T}")
+    if orig == new and x.dim() == 1:
+        return x
+    rows, first, ntap, ts, width, o, n = _resample_tables(orig, new, x.device)
+    T_out = resample_out_len(T, orig, new)
+    if T_out >= 2 ** 31:
+        raise RuntimeError("resample_sinc: the output must have fewer than 2^31 samples")
+    if out is None:
+        out = torch.empty((T_out,), device=x.device, dtype=torch.float32)
+    elif not out.is_cuda or out.dtype != torch.float32 or out.shape != (T_out,) or not out.is_contiguous():
+        raise RuntimeError(f"resample_sinc: out must be ({T_out},) contiguous float32 on the device")
+    stride = x.stride(0) if x.dim() == 2 and C > 1 else T
+    _tk("resample_sinc", 4 * (C * T + T_out), lambda: call(
+        "nsid_resample_sinc", _p(x), stride, C, T, o, n, width, _p(rows), _p(first), ntap, ts, _p(out), T_out, _stream()), (C, T))
+    return out
+
+
+def _sp_table(name, t, dtype, shape):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or tuple(t.shape) != shape:
+        raise RuntimeError(f"stem_pairs: {name} must be a contiguous {dtype} tensor of shape {shape} on the MI355X device")
+
+
+def stem_pairs(bank: torch.Tensor, base: torch.Tensor, length: torch.Tensor, track: torch.Tensor, start: torch.Tensor,
+               key: torch.Tensor, off_i: torch.Tensor, off_j: torch.Tensor, L: int, O: int, silence: float,
+               pack: Optional[int] = None):
+    """N candidate clips from the bank (flat fp32 buffer; track t = three rows of length[t] from element base[t]): SNR gate, split,
+    crops and silence test (include/nsid.h nsid_stem_pairs_gate / _build), two launches, no host synchronisation.
+    pack None -> (x_i (N, L), x_j (N, L), status (N,) i32, snr (N, 3) f32), rejected rows zero;
+    pack = B  -> (x_i (B, L), x_j (B, L), n_ok () i32, status, snr): the accepted clips in order, zeros from row n_ok on."""
+    if not isinstance(bank, torch.Tensor) or not bank.is_cuda or bank.dtype != torch.float32 or bank.dim() != 1 or \
+            not bank.is_contiguous() or bank.numel() < 1:
+        raise RuntimeError("stem_pairs: the bank is a flat contiguous float32 buffer on the MI355X device; there is no host path")
+    n_tracks, N = base.numel(), track.numel()
+    L, O = int(L), int(O)
+    if n_tracks < 1 or not 1 <= N <= 65535 or L < 1 or O < 1 or L + O >= 2 ** 30:
+        raise RuntimeError("stem_pairs: need at least one track, 1 <= N <= 65535 clips, L >= 1, O >= 1 and L + O < 2^30")
+    _sp_table("base", base, torch.int64, (n_tracks,))
+    _sp_table("length", length, torch.int32, (n_tracks,))
+    _sp_table("track", track, torch.int32, (N,))
+    _sp_table("start", start, torch.int32, (N,))
+    _sp_table("key", key, torch.float32, (N, 3))
+    _sp_table("off_i", off_i, torch.int32, (N,))
+    _sp_table("off_j", off_j, torch.int32, (N,))
+    dev = bank.device
+    status = torch.empty((N,), device=dev, dtype=torch.int32)
+    plan = torch.empty((N,), device=dev, dtype=torch.int32)
+    snr = torch.empty((N, 3), device=dev, dtype=torch.float32)
+    W = L + O
+    _tk("stem_pairs_gate", 4 * N * (3 * W + 3 * L), lambda: call(
+        "nsid_stem_pairs_gate", _p(bank), bank.numel(), _p(base), _p(length), n_tracks, _p(track), _p(start), _p(key), _p(off_i),
+        _p(off_j), N, L, O, float(silence), _p(status), _p(snr), _p(plan), _stream()), (N, W))
+    if pack is None:
+        rows, n_ok = N, None
+    else:
+        rows = int(pack)
+        if not 1 <= rows <= 65535:
+            raise RuntimeError("stem_pairs: 1 <= pack <= 65535 output rows")
+        n_ok = torch.empty((), device=dev, dtype=torch.int32)
+    x_i = torch.empty((rows, L), device=dev, dtype=torch.float32)
+    x_j = torch.empty((rows, L), device=dev, dtype=torch.float32)
+    _tk("stem_pairs_build", 4 * rows * 5 * L, lambda: call(
+        "nsid_stem_pairs_build", _p(bank), bank.numel(), _p(base), _p(length), n_tracks, _p(track), _p(start), _p(off_i), _p(off_j),
+        _p(status), _p(plan), N, L, O, 0 if pack is None else 1, rows if pack is not None else 0, _p(x_i), L, _p(x_j), L, _p(n_ok),
+        _stream()), (rows, L))
+    if pack is None:
+        return x_i, x_j, status, snr
+    return x_i, x_j, n_ok, status, snr
+
+
 def batched_index_select_fwd(x: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
     """x (B, C, N) fp32, idx (B, Nq, k) int32 -> (B, C, Nq, k) — the reference's batched_index_select (torch_nn.py:79-98)"""
     _chk(x)

@@ -2,7 +2,7 @@
 GPU: model.train()(x_i, x_j), baseline_objective, backward, FusedClipAdam(max_norm=1.0); next to a torch-eager restatement of the same
 step written here from the state_dict (as tools/resnet_train_bench.py does for the trunk), on the same GPU in the same call.
 
-    python tools/baseline_train_synthetic.py [--batch 256] [--steps 10] [--bf16] [--reps 5] [--only-ours] [--no-table] [--augment]
+    python tools/baseline_train_synthetic.py [--batch 256] [--steps 10] [--bf16] [--reps 5] [--only-ours] [--no-table] [--augment [--from-bank]]
 
 --augment runs the loop of baseline/train.py from raw stems instead: synthetic (B, 110 250) stem pairs on the GPU, a fresh draw of
 GPUBaselineWaveAugment per step (the only host work: random numbers and the EQ filter design), GPUTransformCQT(train=True), the step;
@@ -165,10 +165,19 @@ def run_from_stems(args):
     opt = FusedClipAdam(model.parameters(), lr=args.lr, max_norm=1.0, direct_grads=False, ds_prep=False)
     gen = torch.Generator().manual_seed(11)
     augment, front = GPUBaselineWaveAugment(CFG, generator=gen), GPUTransformCQT(CFG, train=True)
-    x_i, x_j = synth_stems(B)
+    sampler = None
+    if args.from_bank:
+        from stem_pairs_bench import BASELINE_CFG, synth_bank
+        from neuralsampleid_amd.modules.data import GPUStemPairSampler
+        sampler = GPUStemPairSampler(BASELINE_CFG, synth_bank(BASELINE_CFG, tracks=4, seconds=30.0))      # built once
+        assert sampler.L == L
+    else:
+        x_i, x_j = synth_stems(B)
     for step in range(args.steps):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if sampler is not None:                       # the dataset's __getitem__ for the batch: stems -> (x_i, x_j), on the device
+            x_i, x_j, n_ok = sampler.batch(B, generator=gen)
         params = augment.draw(B, generator=gen, device="cuda", L=L)
         t1 = time.perf_counter()
         a_i, a_j = augment(x_i, x_j, params)
@@ -182,7 +191,7 @@ def run_from_stems(args):
         t4 = time.perf_counter()
         assert X_i.shape == (B, 84, 216) and bool(torch.isfinite(X_i).all())
         print(f"step {step:3d} | loss {float(loss):.4f} | cls {float(cls):.4f} | triplet {float(trip):.4f} | grad norm "
-              f"{float(opt.grad_norm):.3f} | draw (host) {1e3 * (t1 - t0):7.2f} ms | augment {1e3 * (t2 - t1):7.2f} ms | CQT "
+              f"{float(opt.grad_norm):.3f} | {'sampler.batch + ' if sampler is not None else ''}draw (host) {1e3 * (t1 - t0):7.2f} ms | augment {1e3 * (t2 - t1):7.2f} ms | CQT "
               f"{1e3 * (t3 - t2):6.2f} ms | step {1e3 * (t4 - t3):7.2f} ms", flush=True)
     F_.set_activation_dtype(torch.float32)
 
@@ -267,7 +276,12 @@ def main():
     ap.add_argument("--only-ours", action="store_true")
     ap.add_argument("--no-table", action="store_true")
     ap.add_argument("--augment", action="store_true", help="run the loop from raw stems: GPUBaselineWaveAugment, GPUTransformCQT, the step")
-    run(ap.parse_args())
+    ap.add_argument("--from-bank", action="store_true",
+                    help="with --augment: cut every batch from a synthetic StemBank with GPUStemPairSampler.batch instead of fixed stems")
+    args = ap.parse_args()
+    if args.from_bank and not args.augment:
+        ap.error("--from-bank feeds the augmenter: add --augment")
+    run(args)
 
 
 if __name__ == "__main__":

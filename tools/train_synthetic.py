@@ -62,9 +62,14 @@ def main():
     ap.add_argument("--augment", action="store_true",
                     help="with --from-wave: Gain + TimeStretch / PitchShift of the pair on the GPU (GPUWaveAugment), eagerly in "
                          "front of the step, the reference's GPUTransformSampleID(cpu=True) on its DataLoader workers")
+    ap.add_argument("--from-bank", action="store_true",
+                    help="with --from-wave --augment: cut every batch from a synthetic StemBank with GPUStemPairSampler.batch "
+                         "(the dataset's __getitem__ on the device) instead of ready-made waveform pairs")
     args = ap.parse_args()
     if args.augment and not args.from_wave:
         ap.error("--augment works on waveforms: add --from-wave")
+    if args.from_bank and not args.augment:
+        ap.error("--from-bank feeds the augmenter: add --from-wave --augment")
     device = torch.device("cuda")
     source, augment, wave_aug = batches, None, None
     if args.from_wave:
@@ -74,6 +79,17 @@ def main():
     if args.augment:
         from neuralsampleid_amd.modules.transformations import GPUWaveAugment
         wave_aug = GPUWaveAugment(cfg={**CFG, **FCFG, **ACFG}).to(device)
+    if args.from_bank:
+        sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+        from stem_pairs_bench import ENCODER_CFG, synth_bank
+        from neuralsampleid_amd.modules.data import GPUStemPairSampler
+        sampler = GPUStemPairSampler(ENCODER_CFG, synth_bank(ENCODER_CFG, tracks=4, seconds=30.0))        # built once
+        assert sampler.L == N_SAMPLES
+        draws = torch.Generator().manual_seed(5)
+
+        def source(n, batch, device):                 # every batch is cut from the bank; n_ok stays on the device
+            for _ in range(n):
+                yield sampler.batch(batch, generator=draws)[:2]
     if args.bf16:
         ops.set_gemm_precision("bf16")
         F_.set_activation_dtype("bf16")
