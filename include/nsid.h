@@ -494,6 +494,19 @@ int nsid_triplet_fwd_bwd(const float* e, const int64_t* labels, int M, int D, do
 int nsid_baseline_objective_fwd_bwd(const float* z_i, const float* z_j, int B, int D, double margin, double beta, double gamma,
                                     float* ws, float* out, float* dz_i, float* dz_j, void* stream);
 
+/* baseline_objective for one rank of a data-parallel step. z_i_all / z_j_all: the gathered (Bg, D) embeddings of the GLOBAL batch,
+ * rank-major. Limits: M = 2 * Bg <= 4096, D % 16 == 0, 16 <= D <= 2048, 0 <= p0, 1 <= npairs, p0 + npairs <= Bg.
+ * The forward runs over all M rows on every rank: out[0..3] = [loss, cls, trip, n_valid] of the global batch, bitwise equal on every
+ * rank (no all-reduce), and the head of ws holds the decisions of all M anchors as above. dz_i / dz_j (npairs, D): the gradient of
+ * out[0] with respect to rows [p0, p0 + npairs) of each view; both NULL: forward only. Every output row sums over all M columns and
+ * anchors in ascending order, so the rows do not depend on how the batch is cut: with p0 = 0, npairs = Bg <= 1024 the call equals
+ * nsid_baseline_objective_fwd_bwd bit for bit, and the rows of any shard equal the same rows of that call.
+ * ws: nsid_baseline_loss_rows_ws_floats(M, D) floats (both similarity matrices are kept whole: 2 x 64 MB at M = 4096). */
+size_t nsid_baseline_loss_rows_ws_floats(int M, int D);
+int nsid_baseline_objective_rows_fwd_bwd(const float* z_i_all, const float* z_j_all, int Bg, int D, int p0, int npairs,
+                                         double margin, double beta, double gamma, float* ws, float* out, float* dz_i, float* dz_j,
+                                         void* stream);
+
 /* ---- optimiser (train.py:73-75: clip_grad_norm_(1.0) + Adam) -------------------------------------------
  * sumsq: partial[blocks] sums of squares of g (blocks = nsid_sumsq_blocks(n)).
  * adam:  norm = sqrt(sum partial); coef = min(1, max_norm/(norm+1e-6)); torch.optim.Adam update with g*coef.

@@ -59,6 +59,7 @@ SIGNATURES = {
     "nsid_pair_ce_fwd_bwd": "ppiipppps",
     "nsid_triplet_fwd_bwd": "ppiidppps",
     "nsid_baseline_objective_fwd_bwd": "ppiidddpppps",
+    "nsid_baseline_objective_rows_fwd_bwd": "ppiiiidddpppps",
     "nsid_sumsq_partial": "plps",
     "nsid_adam_step": "pppplpppips",
     "nsid_f32_to_bf16": "ppls",
@@ -188,6 +189,8 @@ def _load():
     lib.nsid_ntxent_ws_floats.restype = ctypes.c_size_t
     lib.nsid_baseline_loss_ws_floats.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.nsid_baseline_loss_ws_floats.restype = ctypes.c_size_t
+    lib.nsid_baseline_loss_rows_ws_floats.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.nsid_baseline_loss_rows_ws_floats.restype = ctypes.c_size_t
     lib.nsid_conv2d_wgrad_splits.argtypes = [ctypes.c_long, ctypes.c_long]
     lib.nsid_conv2d_wgrad_splits.restype = ctypes.c_int
     lib.nsid_stem7_partials.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_int]
@@ -198,7 +201,7 @@ def _load():
 
 
 lib = _load()
-EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_baseline_loss_ws_floats", "nsid_conv2d_wgrad_splits", "nsid_stem7_partials", "nsid_stem7_bwd_set_floats", "nsid_workspace_bytes"]
+EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_baseline_loss_ws_floats", "nsid_baseline_loss_rows_ws_floats", "nsid_conv2d_wgrad_splits", "nsid_stem7_partials", "nsid_stem7_bwd_set_floats", "nsid_workspace_bytes"]
 
 _ERR = {-1: "NSID_EINVAL (unsupported shape, misaligned pointer or bad argument)",
         -2: "NSID_ELAUNCH (HIP runtime refused the launch)"}

@@ -1,5 +1,7 @@
 // Training objective of the ResNet-IBN baseline (simclr/triplet.py:6-61, baseline/train.py:64-77): pair cross-entropy and the
-// semi-hard triplet loss, forward and backward, for embeddings of up to 2048 features and up to 2048 rows.
+// semi-hard triplet loss, forward and backward, for embeddings of up to 2048 features and up to 2048 rows; and the step objective of a
+// data-parallel rank (nsid_baseline_objective_rows_fwd_bwd): the forward over the gathered global batch of up to 4096 rows, the
+// backward for the pairs the rank owns.
 //
 //   bl_normalize_kernel : zn = z / max(|z|, 1e-12) per row (the step's second F.normalize), |z| kept for its backward
 //   bl_sim_kernel       : S = E E^T in exact fp32 on v_mfma_f32_16x16x4_f32, 64 x 64 tiles, K loop over D; S is MATERIALISED
@@ -14,6 +16,8 @@
 //   bl_trip_bwd_kernel  : the sparse backward without floating-point atomics: output row i adds its own anchor's term, then the
 //                         terms of the anchors that chose it, found by a scan of the two index arrays and visited in ascending order
 //                         (bitwise reproducible); with `norm` it also applies the backward of the normalisation
+// Both backward kernels write the output rows an `Owned` names. Every output row sums over ALL M columns / anchors in ascending
+// order whatever the owned range is, so a row's gradient does not depend on how the batch is sharded, bit for bit.
 #include "nsid_common.h"
 
 namespace {
@@ -21,6 +25,7 @@ namespace {
 constexpr int TB = 64;          // tile edge of both MFMA products
 constexpr int LDT = TB + 4;     // LDS row stride (floats): 16-byte aligned rows, rows 4 apart land on different banks
 constexpr int BL_MAX = 2048;    // rows and features
+constexpr int BL_ROWS_MAX = 4096;   // rows of the gathered batch of the sharded objective
 
 // rows [0, split) of the row matrix live at a, the rest at b (the two views); a single matrix has split = M
 struct RowSet {
@@ -34,6 +39,14 @@ __device__ __forceinline__ const float* row_of(const RowSet& R, int r, int D) {
 __device__ __forceinline__ float* row_of(float* a, float* b, int split, int r, int D) {
   return r < split ? a + (long)r * D : b + (long)(r - split) * D;
 }
+
+// The output rows of a backward launch: o in [0, rows) is row (o < n ? p0 + o : B + p0 + o - n) of the row matrix, i.e. pairs
+// [p0, p0 + n) of both views, and is written to row o of (d_a | d_b) split at n. The unsharded entries own every row: p0 = 0,
+// n = the split of their row matrix, rows = M.
+struct Owned {
+  int p0, n, B, rows;
+};
+__device__ __forceinline__ int owned_row(const Owned& O, int o) { return o < O.n ? O.p0 + o : O.B + O.p0 + (o - O.n); }
 
 // deterministic sum over the 256 threads of a workgroup (red: 4 floats of LDS); every thread receives it
 __device__ __forceinline__ float block_sum(float v, float* red) {
@@ -267,30 +280,36 @@ __global__ __launch_bounds__(256) void bl_finish_kernel(const double* __restrict
   }
 }
 
-// dz[i][c] = scale * sum_j Q_ij z[j][c] for the tile of 64 rows i (blockIdx.y) and 64 features c (blockIdx.x)
+// dz[o][c] = scale * sum_j Q_ij z[j][c], i = owned_row(o), for the tile of 64 owned rows o (blockIdx.y) and 64 features c
+// (blockIdx.x); the tile may straddle the two owned ranges or end short of 64 rows. The sum over j runs on two levels: the 64
+// columns of a tile in the fp32 MFMA accumulator, the tiles in double. One fp32 accumulator over all M columns sits at M times the
+// result's magnitude for M / 4 roundings: at M = 4096 that alone is 6 x the distance of the reference's own fp32 run from fp64.
 __global__ __launch_bounds__(256) void bl_ce_bwd_kernel(RowSet R, const float* __restrict__ S, const float* __restrict__ lse, int M,
-                                                        int Mp, int D, int B, float scale, float* __restrict__ dz_a,
+                                                        int Mp, int D, int B, Owned O, double scale, float* __restrict__ dz_a,
                                                         float* __restrict__ dz_b) {
   __shared__ __attribute__((aligned(16))) float Qs[TB * LDT];
   __shared__ __attribute__((aligned(16))) float Zs[TB * LDT];
   const int i0 = blockIdx.y * TB, c0 = blockIdx.x * TB;
   const int cw = min(TB, D - c0);              // a multiple of 16
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, lr = lane & 15, rq = lane >> 4;
-  f32x4 acc[4];
+  double tot[4][4];
 #pragma unroll
-  for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int u = 0; u < 4; ++u)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) tot[u][e] = 0.0;
   float lse_i[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
-    const int i = i0 + (((int)threadIdx.x + 256 * u) >> 4);
-    lse_i[u] = i < M ? lse[i] : 0.f;
+    const int o = i0 + (((int)threadIdx.x + 256 * u) >> 4);
+    lse_i[u] = o < O.rows ? lse[owned_row(O, o)] : 0.f;
   }
   for (int j0 = 0; j0 < M; j0 += TB) {
     f32x4 vq[4], vz[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int q = threadIdx.x + 256 * u, rr = q >> 4, c = (q & 15) * 4;
-      const int i = i0 + rr;
+      const bool own = i0 + rr < O.rows;
+      const int i = own ? owned_row(O, i0 + rr) : 0;           // (a tile row past the owned ones reads row 0 and contributes zeros)
       const f32x4 s = ld4(S + (long)i * Mp + j0 + c);          // inside Mp x Mp
       const f32x4 lj = ld4(lse + j0 + c);                      // inside lse[Mp]; entries past M are not used
       const int tgt = i + B < M ? i + B : i + B - M;
@@ -298,7 +317,7 @@ __global__ __launch_bounds__(256) void bl_ce_bwd_kernel(RowSet R, const float* _
       for (int e = 0; e < 4; ++e) {
         const int j = j0 + c + e;
         float v = 0.f;
-        if (i < M && j < M && j != i) v = expf(s[e] - lse_i[u]) + expf(s[e] - lj[e]) - (j == tgt ? 2.f : 0.f);
+        if (own && j < M && j != i) v = expf(s[e] - lse_i[u]) + expf(s[e] - lj[e]) - (j == tgt ? 2.f : 0.f);
         vq[u][e] = v;
       }
       vz[u] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -315,6 +334,9 @@ __global__ __launch_bounds__(256) void bl_ce_bwd_kernel(RowSet R, const float* _
     // A = Q (row i = 16 * wave + lr, reduction (rq, e) <-> j = jj + 4 * rq + e), B = z[j][16 * u + lr]
     const float* pa = Qs + (16 * wave + lr) * LDT + 4 * rq;
     const float* pb = Zs + 4 * rq * LDT + lr;
+    f32x4 acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int jj = 0; jj < TB; jj += 16) {
       const f32x4 fa = ld4(pa + jj);
@@ -324,30 +346,34 @@ __global__ __launch_bounds__(256) void bl_ce_bwd_kernel(RowSet R, const float* _
         for (int u = 0; u < 4; ++u)
           acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[e], pb[(jj + e) * LDT + 16 * u], acc[u], 0, 0, 0);
     }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) tot[u][e] += (double)acc[u][e];
   }
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
-    const int i = i0 + 16 * wave + 4 * rq + e;
-    if (i >= M) continue;
-    float* dst = row_of(dz_a, dz_b, B, i, D) + c0;
+    const int o = i0 + 16 * wave + 4 * rq + e;
+    if (o >= O.rows) continue;
+    float* dst = row_of(dz_a, dz_b, O.n, o, D) + c0;
 #pragma unroll
     for (int u = 0; u < 4; ++u)
-      if (16 * u + lr < cw) dst[16 * u + lr] = acc[u][e] * scale;
+      if (16 * u + lr < cw) dst[16 * u + lr] = (float)(tot[u][e] * scale);
   }
 }
 
-// Output row i of the triplet backward: g = w [ (E[p_i] - E[n_i]) [i active] + sum_{a active, p_a = i} E[a] - sum_{a active, n_a = i} E[a] ].
+// Output row o of the triplet backward, i = owned_row(o): g = w [ (E[p_i] - E[n_i]) [i active] + sum_{a active, p_a = i} E[a] - sum_{a active, n_a = i} E[a] ].
 // norm != nullptr: E = zn and the result is taken through the normalisation: (g - zn_i (zn_i . g)) / norm_i.
 // accumulate: added to what the cross-entropy backward left in the row (one owner per row: no atomics).
 __global__ __launch_bounds__(256) void bl_trip_bwd_kernel(RowSet E, int M, int D, const int* __restrict__ pidx,
                                                           const int* __restrict__ nidx, const int* __restrict__ flags,
                                                           const float* __restrict__ res, const float* __restrict__ norm,
-                                                          int accumulate, int out_split, float* __restrict__ d_a,
+                                                          int accumulate, Owned O, float* __restrict__ d_a,
                                                           float* __restrict__ d_b) {
-  __shared__ unsigned hit_p[BL_MAX / 32], hit_n[BL_MAX / 32];
+  __shared__ unsigned hit_p[BL_ROWS_MAX / 32], hit_n[BL_ROWS_MAX / 32];
   __shared__ float red[4];
-  const int i = blockIdx.x;
-  if (threadIdx.x < BL_MAX / 32) { hit_p[threadIdx.x] = 0u; hit_n[threadIdx.x] = 0u; }
+  const int i = owned_row(O, blockIdx.x);
+  if (threadIdx.x < BL_ROWS_MAX / 32) { hit_p[threadIdx.x] = 0u; hit_n[threadIdx.x] = 0u; }
   __syncthreads();
   for (int a = threadIdx.x; a < M; a += blockDim.x) {
     if (flags[a] & F_ACTIVE) {                   // integer OR: the bitmaps do not depend on the order of arrival
@@ -401,7 +427,7 @@ __global__ __launch_bounds__(256) void bl_trip_bwd_kernel(RowSet E, int M, int D
 #pragma unroll
       for (int e = 0; e < 4; ++e) g[u][e] = (g[u][e] - z[u][e] * dot) / n;
   }
-  float* dst = row_of(d_a, d_b, out_split, i, D);
+  float* dst = row_of(d_a, d_b, O.n, (int)blockIdx.x, D);
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     if (c[u] >= D) continue;
@@ -438,10 +464,11 @@ inline Workspace carve(float* ws, int M) {
   return w;
 }
 
-// cls: rows (z_a | z_b) of the cross-entropy; trip: rows of the triplet loss (renorm: the normalised cls rows, made here)
+// cls: rows (z_a | z_b) of the cross-entropy; trip: rows of the triplet loss (renorm: the normalised cls rows, made here);
+// own: the rows whose gradient goes to (d_a | d_b). The forward always covers all M rows.
 int run(const float* z_a, const float* z_b, int split, const long long* labels, int M, int D, int B, double margin, double beta,
         double gamma, bool do_cls, bool do_trip, bool renorm, float* ws, float* o_loss, float* o_cls, float* o_trip, float* o_nv,
-        float* d_a, float* d_b, hipStream_t s) {
+        float* d_a, float* d_b, Owned own, hipStream_t s) {
   const Workspace w = carve(ws, M);
   const int Mp = w.Mp, tiles = Mp / TB;
   const RowSet raw{z_a, z_b, split};
@@ -459,11 +486,11 @@ int run(const float* z_a, const float* z_b, int split, const long long* labels, 
               w.res, o_loss, o_cls, o_trip, o_nv);
   if (d_a != nullptr) {
     if (do_cls)
-      NSID_LAUNCH(bl_ce_bwd_kernel, dim3((D + TB - 1) / TB, tiles), dim3(256), 0, s, raw, w.S0, w.lse, M, Mp, D, B, (float)(beta / M),
-                  d_a, d_b);
+      NSID_LAUNCH(bl_ce_bwd_kernel, dim3((D + TB - 1) / TB, (own.rows + TB - 1) / TB), dim3(256), 0, s, raw, w.S0, w.lse, M, Mp, D, B,
+                  own, beta / M, d_a, d_b);
     if (do_trip)
-      NSID_LAUNCH(bl_trip_bwd_kernel, dim3(M), dim3(256), 0, s, trip, M, D, w.pidx, w.nidx, w.flags, w.res,
-                  renorm ? w.norm : nullptr, (int)do_cls, split, d_a, d_b);
+      NSID_LAUNCH(bl_trip_bwd_kernel, dim3(own.rows), dim3(256), 0, s, trip, M, D, w.pidx, w.nidx, w.flags, w.res,
+                  renorm ? w.norm : nullptr, (int)do_cls, own, d_a, d_b);
   }
   return nsid_launch_status();
 }
@@ -485,7 +512,7 @@ extern "C" int nsid_pair_ce_fwd_bwd(const float* z_i, const float* z_j, int B, i
   NSID_REQUIRE((dz_i == nullptr) == (dz_j == nullptr));
   nsid_count(NSID_C_pair_ce);
   return run(z_i, z_j, B, nullptr, 2 * B, D, B, 0.0, 1.0, 0.0, true, false, false, ws, out, nullptr, nullptr, nullptr, dz_i, dz_j,
-             static_cast<hipStream_t>(stream));
+             Owned{0, B, B, 2 * B}, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int nsid_triplet_fwd_bwd(const float* e, const int64_t* labels, int M, int D, double margin, float* ws, float* out,
@@ -494,7 +521,7 @@ extern "C" int nsid_triplet_fwd_bwd(const float* e, const int64_t* labels, int M
   NSID_REQUIRE(nsid_aligned16(e) && nsid_aligned16(ws) && nsid_aligned16(de));
   nsid_count(NSID_C_triplet);
   return run(e, e, M, reinterpret_cast<const long long*>(labels), M, D, M, margin, 0.0, 1.0, false, true, false, ws, out, nullptr,
-             nullptr, out + 1, de, de, static_cast<hipStream_t>(stream));
+             nullptr, out + 1, de, de, Owned{0, M, M, M}, static_cast<hipStream_t>(stream));
 }
 
 extern "C" int nsid_baseline_objective_fwd_bwd(const float* z_i, const float* z_j, int B, int D, double margin, double beta,
@@ -504,5 +531,21 @@ extern "C" int nsid_baseline_objective_fwd_bwd(const float* z_i, const float* z_
   NSID_REQUIRE((dz_i == nullptr) == (dz_j == nullptr));
   nsid_count(NSID_C_baseline_objective);
   return run(z_i, z_j, B, nullptr, 2 * B, D, B, margin, beta, gamma, true, true, true, ws, out, out + 1, out + 2, out + 3, dz_i,
-             dz_j, static_cast<hipStream_t>(stream));
+             dz_j, Owned{0, B, B, 2 * B}, static_cast<hipStream_t>(stream));
+}
+
+// The sharded form keeps both similarity matrices whole (the forward needs every row of both): the layout of the unsharded workspace.
+extern "C" size_t nsid_baseline_loss_rows_ws_floats(int M, int D) { return nsid_baseline_loss_ws_floats(M, D); }
+
+extern "C" int nsid_baseline_objective_rows_fwd_bwd(const float* z_i_all, const float* z_j_all, int Bg, int D, int p0, int npairs,
+                                                    double margin, double beta, double gamma, float* ws, float* out, float* dz_i,
+                                                    float* dz_j, void* stream) {
+  NSID_REQUIRE(z_i_all && z_j_all && ws && out && Bg >= 1 && Bg <= BL_ROWS_MAX / 2 && D % 16 == 0 && D >= 16 && D <= BL_MAX);
+  NSID_REQUIRE(p0 >= 0 && npairs >= 1 && npairs <= Bg && p0 <= Bg - npairs);
+  NSID_REQUIRE(nsid_aligned16(z_i_all) && nsid_aligned16(z_j_all) && nsid_aligned16(ws) && nsid_aligned16(dz_i) &&
+               nsid_aligned16(dz_j));
+  NSID_REQUIRE((dz_i == nullptr) == (dz_j == nullptr));
+  nsid_count(NSID_C_baseline_objective_rows);
+  return run(z_i_all, z_j_all, Bg, nullptr, 2 * Bg, D, Bg, margin, beta, gamma, true, true, true, ws, out, out + 1, out + 2, out + 3,
+             dz_i, dz_j, Owned{p0, npairs, Bg, 2 * npairs}, static_cast<hipStream_t>(stream));
 }

@@ -242,7 +242,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(aug_stft) X(aug_vocoder) X(aug_istft) X(aug_finish)   /* augment.hip: waveform augmentations, one launch per stage */ \
   X(aug_compress) X(aug_biquad) X(aug_frames)   /* augment_fx.hip: the baseline's compressor, band EQ and frame edits */ \
   X(conv2d_3x3) X(conv2d_1x1) X(ibn_relu) X(stem7_pool) X(gem_pool)   /* resnet.hip: the ResNet-IBN baseline's eval-mode forward */ \
-  X(pair_ce) X(triplet) X(baseline_objective)   /* baseline_loss.hip: the baseline's training objective, one count per call */ \
+  X(pair_ce) X(triplet) X(baseline_objective) X(baseline_objective_rows)   /* baseline_loss.hip: the baseline's training objective, one count per call */ \
   X(gem_pool_bwd)         /* resnet.hip: backward of the GeM pooling */ \
   X(conv2d_bwd_data) X(conv2d_bwd_weight) X(col_stat) X(ibn_relu_bwd) X(bn_add_relu) X(relu_bwd)   /* resnet.hip: training-mode residual blocks */ \
   X(stem7_stat) X(stem7_pool_train) X(stem7_bwd)   /* resnet.hip: training-mode stem */ \

@@ -1272,6 +1272,50 @@ def baseline_objective_fwd_bwd(z_i, z_j, margin=0.2, beta=1.0, gamma=1.0, want_g
     return (out, dzi, dzj, _bl_mining(ws, M)) if mining else (out, dzi, dzj)
 
 
+BL_ROWS_MAX = 4096   # rows (2 Bg) of the gathered batch of baseline_objective_rows_fwd_bwd
+
+
+def baseline_objective_rows_fwd_bwd(z_i_all, z_j_all, p0=0, npairs=None, margin=0.2, beta=1.0, gamma=1.0, want_grad=True, mining=False,
+                                    ws=None, out=None, dz=None):
+    """the step objective for one data-parallel rank: z_*_all are the gathered (Bg, d) embeddings of the global batch (rank-major, as
+    parallel.gather_pair returns them), 2 Bg <= 4096. (out (4,) = [loss, cls, trip, n_valid] of the GLOBAL batch, dz_i, dz_j), the
+    gradients (npairs, d) of out[0] with respect to pairs [p0, p0 + npairs); npairs=None: every pair from p0. The forward covers all rows
+    on every rank, so out is bitwise equal on all of them, and a gradient row does not depend on the cut. ws / out / dz and mining (the
+    decisions of all 2 Bg anchors) as in baseline_objective_fwd_bwd."""
+    name = "baseline_objective_rows_fwd_bwd"
+    _chk(z_i_all, z_j_all)
+    Bg, d = z_i_all.shape
+    if z_j_all.shape != z_i_all.shape:
+        raise ValueError(f"{name}: z_i_all {tuple(z_i_all.shape)} and z_j_all {tuple(z_j_all.shape)} differ")
+    M = 2 * Bg
+    if d % 16 != 0 or not 16 <= d <= BL_MAX or not 1 <= Bg or M > BL_ROWS_MAX:
+        raise ValueError(f"{name}: D % 16 == 0, 16 <= D <= {BL_MAX} and at most {BL_ROWS_MAX} rows are supported, got {M} rows of {d}")
+    if npairs is None:
+        npairs = Bg - p0
+    if p0 < 0 or npairs < 1 or p0 + npairs > Bg:
+        raise ValueError(f"{name}: pairs [{p0}, {p0} + {npairs}) are not a range of the {Bg} gathered pairs")
+    if ws is None:
+        ws = torch.empty((lib.nsid_baseline_loss_rows_ws_floats(M, d),), device=z_i_all.device, dtype=torch.float32)
+    if out is None:
+        out = torch.empty((4,), device=z_i_all.device, dtype=torch.float32)
+    _chk(ws, out)
+    if ws.numel() < lib.nsid_baseline_loss_rows_ws_floats(M, d) or out.numel() < 4:
+        raise ValueError(f"{name}: workspace or result buffer too small")
+    if dz is not None:
+        dzi, dzj = dz
+        _chk(dzi, dzj)
+        if dzi.shape != (npairs, d) or dzj.shape != (npairs, d):
+            raise ValueError(f"{name}: gradient buffers do not match the owned pairs")
+    else:
+        dzi = torch.empty((npairs, d), device=z_i_all.device, dtype=torch.float32) if want_grad else None
+        dzj = torch.empty((npairs, d), device=z_i_all.device, dtype=torch.float32) if want_grad else None
+    flops = 2.0 * M * d * (2 * M + (2 * npairs if dzi is not None else 0))
+    _timed("baseline_loss_kernels<objective rows>", flops, 4.0 * d * (3 * M + 2 * npairs), lambda: call(
+        "nsid_baseline_objective_rows_fwd_bwd", _p(z_i_all), _p(z_j_all), Bg, d, p0, npairs, float(margin), float(beta), float(gamma),
+        _p(ws), _p(out), _p(dzi), _p(dzj), _stream()), (2 * npairs, M, d, 1))
+    return (out, dzi, dzj, _bl_mining(ws, M)) if mining else (out, dzi, dzj)
+
+
 # ------------------------------------------------------------------------------------------------ step plumbing
 def fill_zero(t: torch.Tensor) -> torch.Tensor:
     """t[...] = 0 with our own streaming kernel (zero_grad: the captured step holds no ATen kernel)"""

@@ -10,6 +10,9 @@ The MI355X-native equivalent keeps those semantics with two collectives and no p
   2. SUM all-reduce of the flat gradient buffer (73.5 MB fp32) — the per-rank gradients are already gradients of the
      global mean loss through that rank's clips, so they add (no 1/world averaging);
   BatchNorm statistics are per rank (no SyncBN), as under DataParallel.
+The ResNet-IBN baseline (baseline/train.py:154-158) takes the same two collectives: `dist_baseline_objective` evaluates the objective
+of the global batch on every rank from the one all-gather (no loss all-reduce), and its gradients reach the flat buffer through
+autograd, so `GradReducer.install_param_hooks()` listens to autograd's accumulation hooks.
 
 Two transports behind the same three calls (all-gather, all-reduce, bucketed async all-reduce):
   * `rccl.RcclComm` (GPU, the product path): direct RCCL on one dedicated HIP stream — capturable in the step's hipGraph,
@@ -137,6 +140,49 @@ def dist_ntxent_loss(z_i: torch.Tensor, z_j: torch.Tensor, cfg: dict, group=None
     return _DistNtxent.apply(z_i, z_j, float(cfg["tau"]), rows_fn or _hip_rows, group)
 
 
+class _DistBaselineObjective(torch.autograd.Function):
+    """(loss, cls, trip) of the GLOBAL batch, evaluated redundantly on every rank from one all-gather (bitwise equal everywhere: no
+    all-reduce of the loss); backward hands back d loss / d z_local from the rows kernel (no collective)."""
+
+    @staticmethod
+    def forward(ctx, z_i, z_j, margin, beta, gamma, rows_fn, group):
+        rank, world = _rank_world(group)
+        zi_all, zj_all = gather_pair(z_i.detach(), z_j.detach(), group)
+        p0, n = shard_range(zi_all.shape[0], rank, world)
+        out, dzi, dzj = rows_fn(zi_all.contiguous(), zj_all.contiguous(), p0, n, margin, beta, gamma)
+        ctx.save_for_backward(dzi, dzj)
+        loss, cls, trip = out[0].reshape(()), out[1].reshape(()), out[2].reshape(())
+        ctx.mark_non_differentiable(cls, trip)          # the parts are for logging: the gradient is that of the sum
+        return loss, cls, trip
+
+    @staticmethod
+    def backward(ctx, g, _g_cls, _g_trip):
+        dzi, dzj = ctx.saved_tensors
+        if dzi.is_cuda:
+            from . import ops
+            g = g.contiguous().float()
+            return ops.scale_f32(dzi, g), ops.scale_f32(dzj, g), None, None, None, None, None
+        return dzi * g, dzj * g, None, None, None, None, None
+
+
+def _hip_objective_rows(zi_all, zj_all, p0, n, margin, beta, gamma):
+    from . import ops
+    return ops.baseline_objective_rows_fwd_bwd(zi_all, zj_all, p0, n, margin, beta, gamma, want_grad=True)
+
+
+def dist_baseline_objective(z_i: torch.Tensor, z_j: torch.Tensor, margin: float = 0.2, beta: float = 1.0, gamma: float = 1.0,
+                            group=None, rows_fn: Optional[Callable] = None):
+    """Drop-in for simclr.triplet.baseline_objective under data parallelism -> (loss, loss_cls, loss_trip) of the GLOBAL batch: the
+    cross-entropy's columns, the triplet loss's positives and negatives and both means range over every rank's pairs.
+    rows_fn(zi_all, zj_all, p0, n, margin, beta, gamma) -> (out (>= 3,), dz_i, dz_j) of pairs [p0, p0 + n); default: the HIP rows kernel."""
+    if not _distributed(group) and rows_fn is None:
+        from .simclr.triplet import baseline_objective
+        return baseline_objective(z_i, z_j, margin, beta, gamma)
+    if rows_fn is None:
+        z_i, z_j = z_i.contiguous().float(), z_j.contiguous().float()
+    return _DistBaselineObjective.apply(z_i, z_j, float(margin), float(beta), float(gamma), rows_fn or _hip_objective_rows, group)
+
+
 def allreduce_gradients(flat_grad: torch.Tensor, group=None, bucket_bytes: int = 0, async_op: bool = False):
     """SUM the flat gradient buffer over ranks. bucket_bytes > 0 splits it into contiguous buckets (each its own
     collective, so early buckets can overlap the rest of backward when launched from a side stream)."""
@@ -188,11 +234,13 @@ class GradReducer:
     def __init__(self, params, flat_grad: torch.Tensor, offsets, group=None, bucket_bytes: int = 16 << 20,
                  uses_per_step: int = 2):
         self.flat, self.group, self.uses = flat_grad, group, uses_per_step
+        self.params = list(params)
+        self._param_hooks = []
         self.bucket_of, self.bounds, self.need = {}, [], []
         esz = flat_grad.element_size()
         end = flat_grad.numel()
         cur_start, count = end, 0
-        for p, off in zip(reversed(list(params)), reversed(list(offsets))):
+        for p, off in zip(reversed(self.params), reversed(list(offsets))):
             cur_start = off
             count += 1
             self.bucket_of[id(p)] = len(self.bounds)
@@ -257,6 +305,23 @@ class GradReducer:
             # all-reduce of a piece's buckets overlaps the launches of the next one
             functional.DEFER_CHUNKS = 3
         return self
+
+    def install_param_hooks(self):
+        """for a model whose gradients reach p.grad through autograd (the ResNet-IBN baseline: FusedClipAdam(direct_grads=False)):
+        every parameter reports itself when autograd has accumulated its gradient into the flat buffer. The accumulation runs ONCE
+        per parameter and backward pass, however often the forward used the parameter (the two views' contributions are summed
+        before it), so the reducer must have been built with uses_per_step=1: with 2 no bucket would fire before finish()."""
+        if self._param_hooks:
+            raise RuntimeError("GradReducer: the parameter hooks are already installed")
+        for p in self.params:
+            if p.requires_grad:
+                self._param_hooks.append(p.register_post_accumulate_grad_hook(lambda q: self.block_done([q])))
+        return self
+
+    def remove_param_hooks(self):
+        for h in self._param_hooks:
+            h.remove()
+        self._param_hooks = []
 
 
 # Host-side deadlines. The direct RCCL path has no ProcessGroupNCCL watchdog (by design, rccl.py), so the host waits are

@@ -2,6 +2,11 @@
 next to a torch-eager restatement of baseline/train.py:66-77 plus loss.backward(), in the same process on the same inputs.
 
     python tools/baseline_loss_bench.py [--shapes 512x2048,256x2048] [--reps 20] [--inner 10]
+    python tools/baseline_loss_bench.py --rows 2048,0,256 [--rows 1024,0,1024] [--rows-d 2048]
+
+--rows Bg,p0,n times the objective of one data-parallel rank instead (ops.baseline_objective_rows_fwd_bwd on caller-owned buffers: the
+forward over the Bg gathered pairs, the backward for pairs [p0, p0 + n)), forward plus backward and forward alone, at --rows-d
+features; where the unsharded op takes the shape (Bg <= 1024) its time on the same inputs stands next to it.
 
 Inputs are clustered unit-norm pairs (centres, per-clip noise scales), so that a real share of the anchors is valid. Both paths are
 warmed up, then timed alternately: each sample is a device-event window around --inner forward-plus-backward calls, the median over
@@ -92,13 +97,52 @@ def launches(fn):
         return {"kernels": f"not counted ({type(exc).__name__})"}
 
 
+def rows_bench(args):
+    from neuralsampleid_amd import ops
+    from neuralsampleid_amd._lib import lib
+    recs = []
+    for spec in args.rows:
+        Bg, p0, n = (int(v) for v in spec.split(","))
+        D = args.rows_d
+        z_i, z_j = (t.detach() for t in inputs(Bg, D, max(2, Bg // 12)))
+        ws = torch.empty(lib.nsid_baseline_loss_rows_ws_floats(2 * Bg, D), device="cuda")
+        out, dz = torch.empty(4, device="cuda"), (torch.empty(n, D, device="cuda"), torch.empty(n, D, device="cuda"))
+        fns = {"rows_fwd_bwd_ms": lambda: ops.baseline_objective_rows_fwd_bwd(z_i, z_j, p0, n, MARGIN, BETA, GAMMA, ws=ws, out=out, dz=dz),
+               "rows_fwd_ms": lambda: ops.baseline_objective_rows_fwd_bwd(z_i, z_j, p0, n, MARGIN, BETA, GAMMA, want_grad=False, ws=ws,
+                                                                          out=out)}
+        if 2 * Bg <= ops.BL_MAX:
+            full = (torch.empty(Bg, D, device="cuda"), torch.empty(Bg, D, device="cuda"))
+            fns["unsharded_fwd_bwd_ms"] = lambda: ops.baseline_objective_fwd_bwd(z_i, z_j, MARGIN, BETA, GAMMA, ws=ws, out=out, dz=full)
+        for fn in fns.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        ms = {k: [] for k in fns}
+        for _ in range(args.reps):
+            for k, fn in fns.items():
+                ms[k].append(window_ms(fn, args.inner))
+        rec = {"Bg": Bg, "rows": 2 * Bg, "D": D, "p0": p0, "npairs": n, "workspace_mb": round(ws.numel() * 4 / 2 ** 20, 1)}
+        for k, v in ms.items():
+            rec[k] = round(float(np.median(v)), 4)
+            rec[k + "_min_max"] = [round(min(v), 4), round(max(v), 4)]
+        fns["rows_fwd_bwd_ms"]()
+        rec["out"] = [float(v) for v in out.cpu()]
+        recs.append(rec)
+    print(json.dumps({"bench": "baseline_objective_rows fwd+bwd", "reps": args.reps, "inner": args.inner, "shapes": recs}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="512x2048,256x2048")
+    ap.add_argument("--rows", action="append", default=[], metavar="Bg,p0,n",
+                    help="time the rows form (one data-parallel rank's objective) at this cut instead; may be repeated")
+    ap.add_argument("--rows-d", type=int, default=2048)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--inner", type=int, default=10)
     args = ap.parse_args()
     assert torch.cuda.is_available(), "baseline_loss_bench needs an MI355X"
+    if args.rows:
+        return rows_bench(args)
     fused_fn = lambda a, b: baseline_objective(a, b, MARGIN, BETA, GAMMA)      # noqa: E731
     rows = []
     for shape in args.shapes.split(","):

@@ -3,6 +3,15 @@ GPU: model.train()(x_i, x_j), baseline_objective, backward, FusedClipAdam(max_no
 step written here from the state_dict (as tools/resnet_train_bench.py does for the trunk), on the same GPU in the same call.
 
     python tools/baseline_train_synthetic.py [--batch 256] [--steps 10] [--bf16] [--reps 5] [--only-ours] [--no-table] [--augment [--from-bank]]
+    python tools/baseline_train_synthetic.py --dp [--gpus N] [--batch 256] [--steps 10] [--bf16]
+
+--dp runs the data-parallel step instead, one process per GPU, --batch pairs per rank: parallel.dist_baseline_objective (one all-gather
+of the embeddings, the objective of the global batch on every rank, the backward for the rank's own pairs) and a GradReducer on
+autograd's accumulation hooks (bucketed SUM all-reduce under backward). It runs under the torchrun environment contract
+(parallel.init_from_env("rccl")); with --gpus N and no launcher in the environment it starts the N ranks itself as fresh child
+processes (at most 16; this process makes no GPU call). NSID_FORCE_COLLECTIVES=1 with one rank is the single-GPU rehearsal of the
+collective path. Rank 0 prints one JSON line (ms per step, pairs per second, world, the loss parts, the SHA-256 of the flat parameter
+buffer after the last step); every other rank prints its digest on stderr: equal digests mean the replicas stayed in step.
 
 --augment runs the loop of baseline/train.py from raw stems instead: synthetic (B, 110 250) stem pairs on the GPU, a fresh draw of
 GPUBaselineWaveAugment per step (the only host work: random numbers and the EQ filter design), GPUTransformCQT(train=True), the step;
@@ -127,8 +136,8 @@ def hip_stem_step(model, x, drows):
     rows.backward(drows)
 
 
-def synth_pairs(B, H=84, W=216):
-    g = torch.Generator(device="cuda").manual_seed(3)
+def synth_pairs(B, H=84, W=216, seed=3):
+    g = torch.Generator(device="cuda").manual_seed(seed)
     x_i = torch.randn(B, H, W, device="cuda", generator=g).abs() * 2 + 0.5
     x_j = (x_i + 0.3 * torch.randn(B, H, W, device="cuda", generator=g)).abs()
     return x_i, x_j
@@ -196,7 +205,97 @@ def run_from_stems(args):
     F_.set_activation_dtype(torch.float32)
 
 
+# ------------------------------------------------------------------------------------------ the data-parallel step
+MAX_RANKS = 16
+
+
+def spawn_dp_ranks(n):
+    """--dp --gpus N without a launcher: N fresh child ranks through torch.distributed.run (this process has made no GPU call); rank
+    0's JSON line is relayed; non-zero if a rank fails or the job overruns NSID_BENCH_TIMEOUT_S"""
+    import signal
+    import socket
+    import subprocess
+    with socket.socket() as sk:
+        sk.bind(("127.0.0.1", 0))
+        port = sk.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+    deadline = float(os.environ.get("NSID_BENCH_TIMEOUT_S", "900"))
+    print(f"[nsid] no launcher in the environment: spawning {n} ranks through torch.distributed.run", file=sys.stderr, flush=True)
+    proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, text=True, start_new_session=True)
+    try:
+        out, _ = proc.communicate(timeout=deadline)
+    except subprocess.TimeoutExpired:
+        print(f"[nsid] the {n}-rank job did not finish within {deadline:.0f} s: terminating its process group", file=sys.stderr, flush=True)
+        os.killpg(proc.pid, signal.SIGTERM)
+        try:
+            proc.wait(timeout=20)
+        except subprocess.TimeoutExpired:
+            os.killpg(proc.pid, signal.SIGKILL)
+            proc.wait()
+        return 124
+    lines = [ln for ln in out.splitlines() if ln.startswith("{")]
+    if proc.returncode == 0 and len(lines) == 1:
+        print(lines[0], flush=True)
+        return 0
+    sys.stderr.write(out)
+    print(f"[nsid] launcher exit code {proc.returncode}, {len(lines)} JSON lines", file=sys.stderr, flush=True)
+    return proc.returncode or 1
+
+
+def dp_step(model, opt, red, x_i, x_j):
+    from neuralsampleid_amd import parallel
+    opt.zero_grad()
+    red.start_step()
+    _, _, z_i, z_j = model(x_i, x_j)
+    loss, cls, trip = parallel.dist_baseline_objective(z_i, z_j, margin=MARGIN)
+    loss.backward()                 # every bucket's all-reduce is launched from the accumulation hooks, under the rest of backward
+    early = len(red.fired)
+    red.finish()                    # the compute stream waits for the communicator's
+    opt.step()
+    return loss, cls, trip, early
+
+
+def run_dp(args):
+    import hashlib
+    from neuralsampleid_amd import parallel
+    rank, local, world = parallel.init_from_env("rccl")
+    B = args.batch                                          # pairs per rank
+    x_i, x_j = synth_pairs(B, seed=3 + rank)                # every rank owns its own clips
+    F_.set_activation_dtype(torch.bfloat16 if args.bf16 else torch.float32)
+    model = build_model()                                   # the same seed on every rank: identical replicas, no parameter broadcast
+    opt = FusedClipAdam(model.parameters(), lr=args.lr, max_norm=1.0, direct_grads=False, ds_prep=False)
+    red = parallel.GradReducer(opt.params, opt.flat_g, opt.offsets, bucket_bytes=16 << 20, uses_per_step=1).install_param_hooks()
+    ms, loss = [], None
+    for step in range(args.steps):
+        parallel.sync_with_deadline(what=f"the work before step {step}")
+        t0 = time.perf_counter()
+        loss, cls, trip, early = dp_step(model, opt, red, x_i, x_j)
+        parallel.sync_with_deadline(what=f"step {step}")
+        ms.append(1e3 * (time.perf_counter() - t0))
+        loss = loss.detach()
+        print(f"[nsid] rank {rank} step {step:3d} | loss {float(loss):.4f} | cls {float(cls):.4f} | triplet {float(trip):.4f} | grad norm "
+              f"{float(opt.grad_norm):.3f} | {ms[-1]:8.2f} ms", file=sys.stderr, flush=True)
+    red.remove_param_hooks()
+    digest = hashlib.sha256(opt.flat_p.cpu().numpy().tobytes()).hexdigest()
+    timed = ms[1:] if len(ms) > 1 else ms                   # the first step pays for code objects, the allocator and RCCL's setup
+    per_step = float(np.median(timed))
+    if rank == 0:
+        print(json.dumps({"bench": "baseline data-parallel step", "world": world, "batch_per_rank": B, "segment": [84, 216],
+                          "storage": "bf16" if args.bf16 else "fp32", "steps": args.steps, "ms_per_step": round(per_step, 3),
+                          "pairs_per_s": round(world * B / (per_step * 1e-3), 1), "ms_all": [round(v, 3) for v in ms],
+                          "loss": float(loss), "loss_cls": float(cls), "loss_trip": float(trip), "buckets": len(red.bounds),
+                          "buckets_fired_in_backward": early,
+                          "collectives": parallel.COMM is not None, "param_sha256": digest}), flush=True)
+    else:
+        print(f"[nsid] rank {rank} param_sha256 {digest}", file=sys.stderr, flush=True)
+    F_.set_activation_dtype(torch.float32)
+    parallel.shutdown()
+
+
 def run(args):
+    if args.dp:
+        return run_dp(args)
     if args.augment:
         return run_from_stems(args)
     B = args.batch
@@ -278,9 +377,19 @@ def main():
     ap.add_argument("--augment", action="store_true", help="run the loop from raw stems: GPUBaselineWaveAugment, GPUTransformCQT, the step")
     ap.add_argument("--from-bank", action="store_true",
                     help="with --augment: cut every batch from a synthetic StemBank with GPUStemPairSampler.batch instead of fixed stems")
+    ap.add_argument("--dp", action="store_true", help="the data-parallel step: dist_baseline_objective and a GradReducer on autograd's hooks")
+    ap.add_argument("--gpus", type=int, default=1, help="with --dp and no launcher in the environment: start this many ranks")
     args = ap.parse_args()
     if args.from_bank and not args.augment:
         ap.error("--from-bank feeds the augmenter: add --augment")
+    if args.dp and args.augment:
+        ap.error("--dp runs the step on synthetic CQT segments: drop --augment")
+    if args.gpus != 1 and not args.dp:
+        ap.error("--gpus starts data-parallel ranks: add --dp")
+    if not 1 <= args.gpus <= MAX_RANKS:
+        ap.error(f"--gpus: 1 to {MAX_RANKS} ranks")
+    if args.dp and args.gpus > 1 and "RANK" not in os.environ:
+        sys.exit(spawn_dp_ranks(args.gpus))
     run(args)
 
 
