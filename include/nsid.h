@@ -372,6 +372,31 @@ int nsid_cqt(const float* wave, long in_stride, int B, long L, int hop, int widt
              const float* taps, long taps_len, const float* scale, float* out, long out_clip_stride, long out_bin_stride,
              void* stream);
 
+/* ---- both front ends over a PACK of songs of different lengths in ONE launch (csrc/frontend.hip, csrc/cqt.hip; the database
+ * build of test_fp.py:92-216 without a launch per file). pack: the mono fp32 waveforms of n_songs songs back to back in one
+ * buffer, at any sample offsets (no alignment asked). songs: DEVICE table of n_songs x 4 longs {first sample in the pack, samples
+ * L_i, first output column col_i, work items of the songs before it}; a work item is a run of 8 frames (log-mel) or a tile of 32
+ * frames (CQT) of ONE song, so song i has ceil(T_i / 8) or ceil(T_i / 32) of them, T_i = 1 + L_i / hop. out is ONE matrix
+ * (n_mels or n_bins, ld): song i's frames are the columns [col_i, col_i + T_i) of every row, frame index fastest, the layout the
+ * batched entries write for one clip with a row stride of ld. Reflection uses the song's own L_i; no workspace, no atomics: song
+ * i's columns are bit-equal to nsid_logmel_fft / nsid_cqt on that song alone (B = 1), wherever it sits in the pack and whatever
+ * else the pack holds. max_len: the longest L_i; total_runs / total_tiles: the work items of the pack (the grid); total_cols: the
+ * columns the songs occupy. NSID_EINVAL before any launch: null pointers, n_songs < 1, the n_fft / hop / width / groups the
+ * batched entries refuse, max_len outside their range for L, ld < total_cols, a work-item total >= 2^31. The entries cannot read
+ * the device table: its validity (offsets and lengths inside the pack, every L_i above the reflect minimum, columns inside ld,
+ * prefixes that match the lengths) is the caller's duty (packs.plan_pack checks all of it on the host). */
+int nsid_logmel_fft_ragged(const float* pack, const long* songs, int n_songs, long max_len, long total_runs, long total_cols,
+                           int n_fft, int hop, const float* window, const float* twiddle, const float* fb, const int* band,
+                           int n_mels, float* out, long ld, void* stream);
+int nsid_cqt_ragged(const float* pack, const long* songs, int n_songs, long max_len, long total_tiles, long total_cols, int hop,
+                    int width, int n_bins, const int* groups, int n_groups, const float* taps, long taps_len, const float* scale,
+                    float* out, long ld, void* stream);
+/* segments out of such a matrix: out[s][m][f] = spec[m*ld + seg_col[s0 + s] + f], s < nseg, m < n_rows, f < n_frames. seg_col:
+ * DEVICE table with the first column of every segment of the pack (song column base + k*step); out: nseg rows of a caller-owned
+ * micro-batch buffer, rows from nseg on are not touched. The caller guarantees seg_col[s] + n_frames <= ld for the entries read. */
+int nsid_unfold_segments_ragged(const float* spec, long ld, int n_rows, int n_frames, const long* seg_col, long s0, int nseg,
+                                float* out, void* stream);
+
 /* ---- waveform augmentations of the contrastive pair (modules/transformations.py:39-46, GPUTransformSampleID(cpu=True) for arch
  * 'grafp': audiomentations Gain on the sample stems, then OneOf(PitchShift, TimeStretch) on the mix, librosa's phase vocoder) for a
  * BATCH of clips, one launch per stage (csrc/augment.hip; the definition is DESIGN.md "Waveform augmentations"). n_fft 2048, hop

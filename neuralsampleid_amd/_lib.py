@@ -68,6 +68,9 @@ SIGNATURES = {
     "nsid_unfold_segments": "piiiiips",
     "nsid_logmel_fft": "pliliippppiplls",
     "nsid_cqt": "pliliiipiplpplls",
+    "nsid_logmel_fft_ragged": "ppillliippppipls",
+    "nsid_cqt_ragged": "ppillliiipiplppls",
+    "nsid_unfold_segments_ragged": "pliiplips",
     "nsid_aug_stft": "plplilpppps",
     "nsid_aug_vocoder": "pilpffpls",
     "nsid_aug_istft": "plilpffpppls",

@@ -60,21 +60,18 @@ __device__ __forceinline__ int cq_reflect(int j, const int L) {
   return j < 0 ? 0 : (j >= L ? L - 1 : j);
 }
 
-__global__ __launch_bounds__(CQ_WAVES* NSID_WAVE) void cqt_kernel(
-    const float* __restrict__ wave, const long in_stride, const int L, const int hop, const int hopP, const int half, const int T,
-    const int tiles, const int B, const CqArgs ga, const float* __restrict__ taps, const float* __restrict__ scale,
-    float* __restrict__ out, const long out_clip_stride, const long out_bin_stride) {
+// one tile: the frames t0 .. t0 + CQ_F - 1 of the clip x (L samples, T frames) for the bins of group g ->
+// o[(g.bin0 + b) * out_bin_stride + t0 + f], t0 + f < T (o: the clip's first output column). The whole workgroup calls it with the
+// same arguments (it holds workgroup-wide barriers); both work maps below end in it.
+__device__ __forceinline__ void cq_tile(const float* __restrict__ x, const int L, const int hop, const int hopP, const int half,
+                                        const int T, const int t0, const CqGroup g, const float* __restrict__ taps,
+                                        const float* __restrict__ scale, float* __restrict__ o, const long out_bin_stride) {
   extern __shared__ __attribute__((aligned(16))) float cq_lds[];
   float* const red = cq_lds;                              // [CQ_WAVES][CQ_F][CQ_COLS]
   float* const stage = cq_lds + CQ_RED;                   // [CQ_F + Q - 1][CQ_PITCH]
   const int tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
-  const int per_group = B * tiles;
-  const int gi = blockIdx.x / per_group, rest = blockIdx.x % per_group;
-  const int clip = rest / tiles, t0 = (rest % tiles) * CQ_F;
-  const CqGroup g = ga.g[gi];
   const int Q = (g.extent - 1) / hop + 1;
   const int rows = CQ_F + Q - 1;
-  const float* x = wave + (long)clip * in_stride;
   const float* tbl = taps + g.table;
   const int i = lane & 15, kq = lane >> 4;
   const int base = t0 * hop + g.tap0 - half;              // sample of row 0, r = 0 (may be negative)
@@ -154,25 +151,46 @@ __global__ __launch_bounds__(CQ_WAVES* NSID_WAVE) void cqt_kernel(
       const float s = scale[g.bin0 + b];
       re = re * s;
       im = -im * s;
-      out[(long)clip * out_clip_stride + (long)(g.bin0 + b) * out_bin_stride + t0 + f] = sqrtf(re * re + im * im);
+      o[(long)(g.bin0 + b) * out_bin_stride + t0 + f] = sqrtf(re * re + im * im);
     }
   }
 }
 
-extern "C" int nsid_cqt(const float* wave, long in_stride, int B, long L, int hop, int width, int n_bins, const int* groups,
-                        int n_groups, const float* taps, long taps_len, const float* scale, float* out, long out_clip_stride,
-                        long out_bin_stride, void* stream) {
-  static_assert(CQ_RC == CQ_WAVES * NSID_WAVE && CQ_F * 8 == CQ_WAVES * NSID_WAVE, "one staged column and one output per thread");
-  NSID_REQUIRE(wave && groups && taps && scale && out);
-  NSID_REQUIRE(B >= 1 && hop >= 1 && n_bins >= 1 && width >= 2 && (width & 1) == 0);
-  NSID_REQUIRE(L > width / 2 && L < (1L << 28) && hop < (1 << 24));        // torch's reflect pad raises for L <= width/2
-  NSID_REQUIRE(in_stride >= L);
-  NSID_REQUIRE(nsid_aligned16(taps));                                      // 16-byte table fragments
+__global__ __launch_bounds__(CQ_WAVES* NSID_WAVE) void cqt_kernel(
+    const float* __restrict__ wave, const long in_stride, const int L, const int hop, const int hopP, const int half, const int T,
+    const int tiles, const int B, const CqArgs ga, const float* __restrict__ taps, const float* __restrict__ scale,
+    float* __restrict__ out, const long out_clip_stride, const long out_bin_stride) {
+  const int per_group = B * tiles;
+  const int gi = blockIdx.x / per_group, rest = blockIdx.x % per_group;
+  const int clip = rest / tiles, t0 = (rest % tiles) * CQ_F;
+  cq_tile(wave + (long)clip * in_stride, L, hop, hopP, half, T, t0, ga.g[gi], taps, scale, out + (long)clip * out_clip_stride,
+          out_bin_stride);
+}
+
+// The same over a PACK of songs of different lengths (include/nsid.h nsid_cqt_ragged). The grid stays group-major with the longest
+// group first; within a group, item b of the pack's `tiles` tiles belongs to the song i with prefix_i <= b < prefix_(i+1)
+// (nsid_pack_song: a bisection that depends on blockIdx alone, so the workgroup's barriers stay uniform). A tile stays inside its
+// song: the reflection is by that song's length, and a song's columns are bit-equal to the song in a launch of its own.
+__global__ __launch_bounds__(CQ_WAVES* NSID_WAVE) void cqt_ragged_kernel(
+    const float* __restrict__ pack, const long* __restrict__ songs, const int n_songs, const int tiles, const int hop,
+    const int hopP, const int half, const CqArgs ga, const float* __restrict__ taps, const float* __restrict__ scale,
+    float* __restrict__ out, const long ld) {
+  const int gi = blockIdx.x / tiles;
+  const long b = blockIdx.x % tiles;
+  const int i = nsid_pack_song(songs, n_songs, b);
+  const long* sg = songs + (long)NSID_PACK_COLS * i;
+  const int L = (int)sg[1], t0 = (int)(b - sg[3]) * CQ_F;
+  cq_tile(pack + sg[0], L, hop, hopP, half, 1 + L / hop, t0, ga.g[gi], taps, scale, out + sg[2], ld);
+}
+
+// the host array of group descriptors -> the kernel argument, checked against the table; qmax: the most hops a group's extent spans
+static int cq_read_groups(const int* groups, const int n_groups, const int n_bins, const int hop, const int width,
+                          const long taps_len, CqArgs& ga, int& qmax) {
   NSID_REQUIRE(n_groups >= 1 && n_groups <= CQ_MAXG);
   const long hopP = ((long)hop + CQ_RC - 1) / CQ_RC * CQ_RC;
-  CqArgs ga;
   ga.n = n_groups;
-  int next_bin = 0, qmax = 1;
+  int next_bin = 0;
+  qmax = 1;
   for (int k = 0; k < n_groups; ++k) {
     CqGroup& g = ga.g[k];
     g.bin0 = groups[5 * k]; g.nbins = groups[5 * k + 1]; g.tap0 = groups[5 * k + 2]; g.extent = groups[5 * k + 3];
@@ -187,6 +205,22 @@ extern "C" int nsid_cqt(const float* wave, long in_stride, int B, long L, int ho
   }
   NSID_REQUIRE(next_bin == n_bins);
   for (int k = n_groups; k < CQ_MAXG; ++k) ga.g[k] = CqGroup{0, 0, 0, 0, 0};
+  return NSID_OK;
+}
+
+extern "C" int nsid_cqt(const float* wave, long in_stride, int B, long L, int hop, int width, int n_bins, const int* groups,
+                        int n_groups, const float* taps, long taps_len, const float* scale, float* out, long out_clip_stride,
+                        long out_bin_stride, void* stream) {
+  static_assert(CQ_RC == CQ_WAVES * NSID_WAVE && CQ_F * 8 == CQ_WAVES * NSID_WAVE, "one staged column and one output per thread");
+  NSID_REQUIRE(wave && groups && taps && scale && out);
+  NSID_REQUIRE(B >= 1 && hop >= 1 && n_bins >= 1 && width >= 2 && (width & 1) == 0);
+  NSID_REQUIRE(L > width / 2 && L < (1L << 28) && hop < (1 << 24));        // torch's reflect pad raises for L <= width/2
+  NSID_REQUIRE(in_stride >= L);
+  NSID_REQUIRE(nsid_aligned16(taps));                                      // 16-byte table fragments
+  const long hopP = ((long)hop + CQ_RC - 1) / CQ_RC * CQ_RC;
+  CqArgs ga;
+  int qmax;
+  NSID_REQUIRE(cq_read_groups(groups, n_groups, n_bins, hop, width, taps_len, ga, qmax) == NSID_OK);
   const long T = 1 + L / hop;
   NSID_REQUIRE(out_bin_stride >= T && out_clip_stride >= (long)(n_bins - 1) * out_bin_stride + T);
   const long tiles = (T + CQ_F - 1) / CQ_F;
@@ -198,5 +232,29 @@ extern "C" int nsid_cqt(const float* wave, long in_stride, int B, long L, int ho
   NSID_LAUNCH(cqt_kernel, dim3((unsigned)(tiles * B * n_groups)), dim3(CQ_WAVES * NSID_WAVE), lds,
               static_cast<hipStream_t>(stream), wave, in_stride, (int)L, hop, (int)hopP, width / 2, (int)T, (int)tiles, B, ga, taps,
               scale, out, out_clip_stride, out_bin_stride);
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_cqt_ragged(const float* pack, const long* songs, int n_songs, long max_len, long total_tiles, long total_cols,
+                               int hop, int width, int n_bins, const int* groups, int n_groups, const float* taps, long taps_len,
+                               const float* scale, float* out, long ld, void* stream) {
+  NSID_REQUIRE(pack && songs && groups && taps && scale && out);
+  NSID_REQUIRE(n_songs >= 1 && hop >= 1 && n_bins >= 1 && width >= 2 && (width & 1) == 0);
+  NSID_REQUIRE(max_len > width / 2 && max_len < (1L << 28) && hop < (1 << 24));     // the longest song of the pack
+  NSID_REQUIRE(nsid_aligned16(taps));
+  const long hopP = ((long)hop + CQ_RC - 1) / CQ_RC * CQ_RC;
+  CqArgs ga;
+  int qmax;
+  NSID_REQUIRE(cq_read_groups(groups, n_groups, n_bins, hop, width, taps_len, ga, qmax) == NSID_OK);
+  NSID_REQUIRE(total_cols >= 1 && ld >= total_cols);
+  NSID_REQUIRE(total_tiles >= n_songs && total_tiles < (1L << 31) && total_tiles * n_groups < (1L << 31));
+  const long tiles_max = (1 + max_len / hop + CQ_F - 1) / CQ_F;
+  NSID_REQUIRE((tiles_max * CQ_F + qmax) * (long)hop + width < (1L << 31));  // staged sample indices stay in int range
+  const size_t lds = sizeof(float) * (CQ_RED + (size_t)(CQ_F + qmax - 1) * CQ_PITCH);
+  NSID_REQUIRE(lds <= 64 * 1024);
+  nsid_count(NSID_C_cqt_ragged);
+  NSID_LAUNCH(cqt_ragged_kernel, dim3((unsigned)(total_tiles * n_groups)), dim3(CQ_WAVES * NSID_WAVE), lds,
+              static_cast<hipStream_t>(stream), pack, songs, n_songs, (int)total_tiles, hop, (int)hopP, width / 2, ga, taps, scale,
+              out, ld);
   return nsid_launch_status();
 }

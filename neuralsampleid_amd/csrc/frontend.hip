@@ -109,18 +109,18 @@ FE_HD int fe_reflect(int j, const int L) {
   return j < 0 ? 0 : (j >= L ? L - 1 : j);
 }
 
-__global__ __launch_bounds__(FE_WAVES* NSID_WAVE) void logmel_fft_kernel(
-    const float* __restrict__ wave, const long in_stride, const int L, const int hop, const int T, const int runs,
-    const float* __restrict__ win, const f32x2* __restrict__ tw, const float* __restrict__ fb, const int* __restrict__ band,
-    const int n_mels, float* __restrict__ out, const long out_clip_stride, const long out_mel_stride) {
+// one run: the frames t0 .. t0 + FE_RUN - 1 of the clip x (L samples, T frames) -> o[m * out_mel_stride + f], f < min(FE_RUN, T - t0).
+// The whole workgroup calls it with the same arguments (it holds workgroup-wide barriers); both work maps below end in it.
+__device__ __forceinline__ void fe_run(const float* __restrict__ x, const int L, const int hop, const int T, const int t0,
+                                       const float* __restrict__ win, const f32x2* __restrict__ tw, const float* __restrict__ fb,
+                                       const int* __restrict__ band, const int n_mels, float* __restrict__ o,
+                                       const long out_mel_stride) {
   extern __shared__ __attribute__((aligned(16))) float fe_lds[];
   const int span = (FE_RUN - 1) * hop + FE_N;
   f32x2* const bufs = reinterpret_cast<f32x2*>(fe_lds);                   // [FE_WAVES][FE_BUF]
   float* const res = fe_lds + 2 * FE_WAVES * FE_BUF;                      // [FE_RUN][n_mels]
   float* const stage = res + FE_RUN * n_mels;                             // [span]
   const int tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
-  const int clip = blockIdx.x / runs, t0 = (blockIdx.x % runs) * FE_RUN;
-  const float* x = wave + (long)clip * in_stride;
   const int first = t0 * hop - FE_N / 2;                                   // t0 * hop <= L: no overflow
   for (int i = tid; i < span; i += FE_WAVES * NSID_WAVE) stage[i] = x[fe_reflect(first + i, L)];
   FeTw t;
@@ -151,11 +151,35 @@ __global__ __launch_bounds__(FE_WAVES* NSID_WAVE) void logmel_fft_kernel(
     __syncthreads();
   }
   const int nf = min(FE_RUN, T - t0);
-  float* o = out + (long)clip * out_clip_stride + t0;
   for (int i = tid; i < n_mels * FE_RUN; i += FE_WAVES * NSID_WAVE) {
     const int m = i / FE_RUN, f = i % FE_RUN;
     if (f < nf) o[(long)m * out_mel_stride + f] = res[f * n_mels + m];
   }
+}
+
+__global__ __launch_bounds__(FE_WAVES* NSID_WAVE) void logmel_fft_kernel(
+    const float* __restrict__ wave, const long in_stride, const int L, const int hop, const int T, const int runs,
+    const float* __restrict__ win, const f32x2* __restrict__ tw, const float* __restrict__ fb, const int* __restrict__ band,
+    const int n_mels, float* __restrict__ out, const long out_clip_stride, const long out_mel_stride) {
+  const int clip = blockIdx.x / runs, t0 = (blockIdx.x % runs) * FE_RUN;
+  fe_run(wave + (long)clip * in_stride, L, hop, T, t0, win, tw, fb, band, n_mels, out + (long)clip * out_clip_stride + t0,
+         out_mel_stride);
+}
+
+// The same over a PACK of songs of different lengths (include/nsid.h nsid_logmel_fft_ragged): workgroup b takes run b - prefix_i of
+// the song i with prefix_i <= b < prefix_(i+1), found by a bisection every lane of the workgroup makes alike (it depends on
+// blockIdx alone). songs: NSID_PACK_COLS longs per song {first sample, samples, first output column, runs before the song}. A run
+// stays inside its song: the reflection is by that song's length, and a song's columns are bit-equal to the song in a launch of
+// its own.
+__global__ __launch_bounds__(FE_WAVES* NSID_WAVE) void logmel_fft_ragged_kernel(
+    const float* __restrict__ pack, const long* __restrict__ songs, const int n_songs, const int hop,
+    const float* __restrict__ win, const f32x2* __restrict__ tw, const float* __restrict__ fb, const int* __restrict__ band,
+    const int n_mels, float* __restrict__ out, const long ld) {
+  const long b = blockIdx.x;
+  const int i = nsid_pack_song(songs, n_songs, b);
+  const long* sg = songs + (long)NSID_PACK_COLS * i;
+  const int L = (int)sg[1], t0 = (int)(b - sg[3]) * FE_RUN;
+  fe_run(pack + sg[0], L, hop, 1 + L / hop, t0, win, tw, fb, band, n_mels, out + sg[2] + t0, ld);
 }
 
 #ifndef FE_HOST_TEST
@@ -178,6 +202,25 @@ extern "C" int nsid_logmel_fft(const float* wave, long in_stride, int B, long L,
   NSID_LAUNCH(logmel_fft_kernel, dim3((unsigned)(runs * B)), dim3(FE_WAVES * NSID_WAVE), lds, static_cast<hipStream_t>(stream),
               wave, in_stride, (int)L, hop, (int)T, (int)runs, window, reinterpret_cast<const f32x2*>(twiddle), fb, band, n_mels,
               out, out_clip_stride, out_mel_stride);
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_logmel_fft_ragged(const float* pack, const long* songs, int n_songs, long max_len, long total_runs,
+                                      long total_cols, int n_fft, int hop, const float* window, const float* twiddle,
+                                      const float* fb, const int* band, int n_mels, float* out, long ld, void* stream) {
+  NSID_REQUIRE(pack && songs && window && twiddle && fb && band && out);
+  NSID_REQUIRE(n_fft == FE_N);
+  NSID_REQUIRE(hop >= 1 && hop <= n_fft && n_songs >= 1 && n_mels >= 1 && n_mels <= 1024);
+  NSID_REQUIRE(max_len > n_fft / 2 && max_len < (1L << 30));
+  NSID_REQUIRE((reinterpret_cast<uintptr_t>(twiddle) & 7u) == 0);
+  NSID_REQUIRE(total_cols >= 1 && ld >= total_cols);
+  NSID_REQUIRE(total_runs >= n_songs && total_runs < (1L << 31));
+  const size_t lds = sizeof(float) * (2 * FE_WAVES * FE_BUF + (size_t)FE_RUN * n_mels + (FE_RUN - 1) * hop + FE_N);
+  NSID_REQUIRE(lds <= 64 * 1024);
+  nsid_count(NSID_C_logmel_fft_ragged);
+  NSID_LAUNCH(logmel_fft_ragged_kernel, dim3((unsigned)total_runs), dim3(FE_WAVES * NSID_WAVE), lds,
+              static_cast<hipStream_t>(stream), pack, songs, n_songs, hop, window, reinterpret_cast<const f32x2*>(twiddle), fb, band,
+              n_mels, out, ld);
   return nsid_launch_status();
 }
 #endif

@@ -866,6 +866,27 @@ __global__ void unfold_segments_kernel(const float* __restrict__ lm, int n_mels,
   }
 }
 
+// the same out of a PACK of songs (n_rows, ld) with the songs side by side in the columns: segments s0 .. s0 + nseg - 1 of the
+// pack's segment list, segment s starting at column seg_col[s] -> out (nseg, n_rows, n_frames)
+__global__ void unfold_segments_ragged_kernel(const float* __restrict__ spec, long ld, int n_rows, int n_frames,
+                                              const long* __restrict__ seg_col, long s0, int nseg, float* __restrict__ out) {
+  const long n = (long)nseg * n_rows * n_frames;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+    const int f = (int)(i % n_frames), m = (int)((i / n_frames) % n_rows);
+    const long s = i / ((long)n_frames * n_rows);
+    out[i] = spec[(long)m * ld + seg_col[s0 + s] + f];
+  }
+}
+
+extern "C" int nsid_unfold_segments_ragged(const float* spec, long ld, int n_rows, int n_frames, const long* seg_col, long s0,
+                                           int nseg, float* out, void* stream) {
+  NSID_REQUIRE(spec && seg_col && out && n_rows > 0 && n_frames > 0 && ld >= n_frames && s0 >= 0 && nseg > 0);
+  nsid_count(NSID_C_unfold_segments_ragged);
+  NSID_LAUNCH(unfold_segments_ragged_kernel, dim3(grid_for((long)nseg * n_rows * n_frames)), dim3(256), 0,
+              static_cast<hipStream_t>(stream), spec, ld, n_rows, n_frames, seg_col, s0, nseg, out);
+  return nsid_launch_status();
+}
+
 extern "C" int nsid_reflect_pad(const float* x, long L, int pad, float* out, void* stream) {
   NSID_REQUIRE(x && out && L > 1 && pad >= 0 && pad < L);
   NSID_LAUNCH(reflect_pad_kernel, dim3(grid_for(L + 2L * pad)), dim3(256), 0, static_cast<hipStream_t>(stream), x, L, pad,

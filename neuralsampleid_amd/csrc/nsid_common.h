@@ -246,7 +246,8 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(gem_pool_bwd)         /* resnet.hip: backward of the GeM pooling */ \
   X(conv2d_bwd_data) X(conv2d_bwd_weight) X(col_stat) X(ibn_relu_bwd) X(bn_add_relu) X(relu_bwd)   /* resnet.hip: training-mode residual blocks */ \
   X(stem7_stat) X(stem7_pool_train) X(stem7_bwd)   /* resnet.hip: training-mode stem */ \
-  X(resample_sinc) X(stem_pairs_gate) X(stem_pairs_build)   /* stems.hip: sinc resampler, stem-pair sampler */
+  X(resample_sinc) X(stem_pairs_gate) X(stem_pairs_build)   /* stems.hip: sinc resampler, stem-pair sampler */ \
+  X(logmel_fft_ragged) X(cqt_ragged) X(unfold_segments_ragged)   /* frontend.hip, cqt.hip, misc.hip: a pack of songs of different lengths in one launch, and its segment gather */
 
 // nsid_stem7_stat leaves at most this many partial sums per channel (resnet.hip); nsid_bn_finalize accepts such a count next to
 // nsid_row_tiles(M)
@@ -260,6 +261,20 @@ enum NsidCounterKey {
 };
 extern long g_nsid_counter[NSID_C_COUNT];
 static inline void nsid_count(NsidCounterKey k) { ++g_nsid_counter[k]; }
+
+// ---- packs of songs (include/nsid.h nsid_logmel_fft_ragged / nsid_cqt_ragged): the device table has NSID_PACK_COLS longs per song,
+// {first sample in the pack, samples, first output column, work items (runs / tiles) of the songs before it}. The song of work item
+// b is the last one whose prefix is <= b (prefix[0] = 0, strictly increasing: every song has at least one item). The result
+// depends on b alone, so with b = blockIdx.x it is uniform over the workgroup.
+constexpr int NSID_PACK_COLS = 4;
+__device__ __forceinline__ int nsid_pack_song(const long* __restrict__ songs, const int n_songs, const long b) {
+  int lo = 0, hi = n_songs - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (songs[(long)NSID_PACK_COLS * mid + 3] <= b) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
 
 // ---- grouped weight gradients (gemm.hip wgrad_grouped_kernel, wgrad.hip wgrad3_grouped_kernel): the table of problems one launch
 // serves, carried in the kernel arguments

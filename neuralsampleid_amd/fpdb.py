@@ -111,6 +111,115 @@ def build_fp_db(model, songs: Iterable[Tuple[str, "object"]], output_root_dir: s
     return n, d
 
 
+class FpDbAppender:
+    """the same three files written a block of rows at a time: `{fname}.mm` is a raw float32 array, so appending rows keeps
+    the format; the shape and lookup files are written by close(). Byte-identical to write_fp_db on the same rows."""
+
+    def __init__(self, output_root_dir: str, fname: str, d: int):
+        os.makedirs(output_root_dir, exist_ok=True)
+        self.dir, self.fname, self.d, self.n = output_root_dir, fname, int(d), 0
+        self.lookup: List[str] = []
+        self._f = open(os.path.join(output_root_dir, f"{fname}.mm"), "wb")
+
+    def append(self, rows, names: Sequence[str]) -> None:
+        rows = _to_numpy(rows)
+        if rows.ndim != 2 or rows.shape[1] != self.d:
+            raise ValueError(f"fingerprints must be (rows, {self.d})")
+        if len(names) != rows.shape[0]:
+            raise ValueError(f"{len(names)} lookup entries for {rows.shape[0]} fingerprints")
+        rows.tofile(self._f)
+        self.lookup.extend(names)
+        self.n += int(rows.shape[0])
+
+    def close(self) -> Tuple[int, int]:
+        self._f.close()
+        np.save(os.path.join(self.dir, f"{self.fname}_shape.npy"), (self.n, self.d))
+        with open(os.path.join(self.dir, f"{self.fname}_lookup.json"), "w") as f:
+            json.dump(self.lookup, f)
+        return self.n, self.d
+
+
+def build_fp_db_from_waves(model, front, songs: Iterable[Tuple[str, "object"]], output_root_dir: str, fname: str = "ref_db",
+                           query_style: bool = False, batch: int = 1024, pack_samples: int = 1 << 26,
+                           extract=None) -> Tuple[int, int, dict]:
+    """The database of test_fp.py:92-216 (create_ref_db / create_query_db / create_dummy_db) straight from waveforms, without a
+    launch, an unfolded tensor and a host copy per audio file (packs.py).
+
+    songs: any iterable of (name, wave) with wave a mono fp32 1-D tensor on the CPU or the GPU, already at the front end's sample
+    rate; it is consumed once, a pack at a time. front: a LogMelFrontEnd (SimCLR models) or a CQTFrontEnd (the ResNet-IBN
+    baseline). Consecutive songs are grouped into packs of at most `pack_samples` samples (a longer song is a pack of its own); per
+    pack there is one upload, one front-end launch, micro-batches of `batch` segments gathered into one reused buffer and handed
+    to `extract`, and ONE device-to-host copy of the pack's fingerprints, whose rows are appended to `{fname}.mm`. Micro-batches do
+    not cross packs. extract: `extract(specs, out)` -> fingerprints of specs written into out, e.g. a GraphedFingerprinter; by
+    default extract_fingerprints on `model`.
+
+    Songs at or below the front end's reflect-pad minimum, or shorter than one segment, are skipped (the reference's unfold raises
+    and create_dummy_db skips the file). Lookup strings are `name`, or f"{name}_{idx}" with query_style, idx being the song's
+    position in `songs`, skipped songs included (test_fp.py:110-115).
+
+    The packed front end always uses the fused-FFT arithmetic (`front.batch`), whatever `stft` a LogMelFrontEnd was built with:
+    a database and its queries must come from the same form.
+
+    Returns (n, d, report): report["skipped"] = [(idx, name, reason)], report["packs"] = [{"songs": (first idx, last idx + 1),
+    "rows": (first row, last row + 1)}] in file order."""
+    import torch
+    from .fingerprint import embedding_dim, extract_fingerprints
+    from .packs import PackArena, WavePack, check_wave, plan_pack
+    batch, pack_samples = int(batch), int(pack_samples)
+    if batch < 1 or pack_samples < 1:
+        raise ValueError("batch and pack_samples must be positive")
+    d = embedding_dim(model)
+    dev = next(model.parameters()).device
+    if extract is None:
+        def extract(specs, out):
+            return extract_fingerprints(model, specs, batch, out)
+    writer = FpDbAppender(output_root_dir, fname, d)
+    report = {"skipped": [], "packs": []}
+    arena = PackArena(dev)
+    bufs = {}
+
+    def flush(group, first_idx, end_idx):
+        plan = plan_pack([w.numel() for _, _, w in group], front)
+        for j, reason in plan.skipped:
+            report["skipped"].append((group[j][0], group[j][1], reason))
+        row0 = writer.n
+        if plan.n_songs:
+            pack = WavePack(plan, [group[j][2] for j in plan.index], dev, arena)
+            n = plan.total_segs
+            if "x" not in bufs:
+                bufs["x"] = torch.empty((batch, plan.n_rows, plan.n_frames), device=dev, dtype=torch.float32)
+            if "z" not in bufs or bufs["z"].shape[0] < n:
+                bufs["z"] = torch.empty((n, d), device=dev, dtype=torch.float32)
+            z = bufs["z"][:n]
+            with torch.no_grad():
+                for s0 in range(0, n, batch):
+                    k = min(batch, n - s0)
+                    extract(pack.segments(s0, k, bufs["x"]), z[s0:s0 + k])
+            names = []
+            for j, c in zip(plan.index, plan.segs):
+                idx, nm, _ = group[j]
+                names.extend([f"{nm}_{idx}" if query_style else nm] * int(c))
+            writer.append(z.cpu().numpy(), names)                          # the pack's one device-to-host copy (blocking)
+        report["packs"].append({"songs": (first_idx, end_idx), "rows": (row0, writer.n)})
+
+    group, held, first = [], 0, 0
+    idx = -1
+    try:
+        for idx, (nm, wave) in enumerate(songs):
+            check_wave(wave)
+            L = wave.numel()
+            if group and held + L > pack_samples:
+                flush(group, first, idx)
+                group, held, first = [], 0, idx
+            group.append((idx, nm, wave))
+            held += L
+        if group:
+            flush(group, first, idx + 1)
+    finally:
+        n, d = writer.close()
+    return n, d, report
+
+
 def _to_numpy(x) -> np.ndarray:
     if hasattr(x, "detach"):
         x = x.detach().cpu().numpy()

@@ -1380,6 +1380,61 @@ def cqt(waves: torch.Tensor, hop: int, width: int, groups, taps: torch.Tensor, s
     return out
 
 
+# ---- packs of songs (packs.py): the kernels cannot check their device tables, so the wrappers take them from a packs.WavePack only
+# (built from a PackPlan that packs.plan_pack derived and validated on the host), never as loose tensors.
+def _pack_of(pack, kind: Optional[str], spec: torch.Tensor):
+    from .packs import WavePack
+    if not isinstance(pack, WavePack) or (kind is not None and pack.plan.kind != kind):
+        raise TypeError(f"expected a packs.WavePack{'' if kind is None else ' of kind ' + kind}")
+    plan = pack.plan
+    if not spec.is_cuda or spec.dtype != torch.float32 or spec.dim() != 2 or spec.stride(1) != 1 or spec.stride(0) != plan.ld \
+            or spec.shape[0] != plan.n_rows or spec.shape[1] < plan.total_cols:
+        raise RuntimeError(f"the packed spectrogram must be ({plan.n_rows}, >= {plan.total_cols}) float32 on the MI355X device "
+                           f"with a row stride of {plan.ld}")
+    return plan
+
+
+def logmel_fft_ragged(pack, n_fft: int, window: torch.Tensor, twiddle: torch.Tensor, fb: torch.Tensor, band: torch.Tensor,
+                      spec: torch.Tensor) -> torch.Tensor:
+    """the songs of a packs.WavePack -> log-mel dB in ONE launch (nsid_logmel_fft_ragged, csrc/frontend.hip): song i's frames
+    are the columns [cols[i], cols[i] + frames[i]) of spec (n_mels, ld), bit-equal to logmel_fft on that song alone"""
+    _chk(window, twiddle, fb)
+    plan = _pack_of(pack, "logmel", spec)
+    if fb.shape[0] != plan.n_rows:
+        raise RuntimeError("the filterbank does not match the plan's rows")
+    call("nsid_logmel_fft_ragged", _p(pack.wave), _p(pack._songs), plan.n_songs, plan.max_len, plan.total_items, plan.total_cols,
+         n_fft, plan.hop, _p(window), _p(twiddle), _p(fb), _p(band), plan.n_rows, _p(spec), plan.ld, _stream())
+    return spec
+
+
+def cqt_ragged(pack, width: int, groups, taps: torch.Tensor, scale: torch.Tensor, spec: torch.Tensor) -> torch.Tensor:
+    """the songs of a packs.WavePack -> constant-Q magnitudes in ONE launch (nsid_cqt_ragged, csrc/cqt.hip), in the same packed
+    columns, bit-equal to cqt on each song alone"""
+    _chk(taps, scale)
+    plan = _pack_of(pack, "cqt", spec)
+    if groups.dtype != np.int32 or groups.ndim != 2 or groups.shape[1] != 5 or not groups.flags["C_CONTIGUOUS"]:
+        raise RuntimeError("groups must be a C-contiguous int32 host array of shape (n_groups, 5)")
+    if scale.numel() != plan.n_rows:
+        raise RuntimeError("the bin scales do not match the plan's rows")
+    call("nsid_cqt_ragged", _p(pack.wave), _p(pack._songs), plan.n_songs, plan.max_len, plan.total_items, plan.total_cols, plan.hop,
+         width, plan.n_rows, groups.ctypes.data, groups.shape[0], _p(taps), taps.numel(), _p(scale), _p(spec), plan.ld, _stream())
+    return spec
+
+
+def unfold_segments_ragged(pack, s0: int, nseg: int, out: torch.Tensor) -> torch.Tensor:
+    """segments s0 .. s0 + nseg - 1 of the pack's segment list -> out[:nseg] (nsid_unfold_segments_ragged, csrc/misc.hip); out:
+    (>= nseg, n_rows, n_frames) contiguous fp32, the rows from nseg on are not touched"""
+    plan = _pack_of(pack, None, pack.spec)
+    if s0 < 0 or nseg < 1 or s0 + nseg > plan.total_segs:
+        raise RuntimeError(f"segments [{s0}, {s0 + nseg}) outside the pack's {plan.total_segs}")
+    _chk(out)
+    if out.dim() != 3 or out.shape[0] < nseg or tuple(out.shape[1:]) != (plan.n_rows, plan.n_frames):
+        raise RuntimeError(f"the micro-batch buffer must be (>= {nseg}, {plan.n_rows}, {plan.n_frames})")
+    call("nsid_unfold_segments_ragged", _p(pack.spec), plan.ld, plan.n_rows, plan.n_frames, _p(pack._seg_col), s0, nseg, _p(out),
+         _stream())
+    return out[:nseg]
+
+
 # ---- waveform augmentations (csrc/augment.hip, include/nsid.h nsid_aug_*): one wrapper per stage; modules/transformations.
 # GPUWaveAugment owns the tables and the workspaces and chains the four. The extents follow the host-side rate bounds alone.
 AUG_N_FFT, AUG_HOP, AUG_BINS = 2048, 512, 1025
