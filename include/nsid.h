@@ -603,6 +603,35 @@ int nsid_clf_pair_scores_n(const float* q, int nq_seg, const float* kp, int nc_s
                            const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail,
                            float* out, int64_t out_len, void* stream);
 
+/* ---- song-level vote of a search result (csrc/vote.hip; eval.py:296-367 on sequence scores, eval_hr.py:85-156 on classifier
+ * scores). One workgroup per pair p = (s = starts[p], L = lens[p]) (device int32; the caller guarantees s + L <= the rows of I).
+ * The candidates are cid = I[s + j/k][j%k] for j < L k, walked in that order. A candidate is skipped when cid < 0, cid < n_dummy,
+ * cid >= n_dummy + n_ref, or its song song_of[cid - n_dummy] (device int32 codes, one per ref row) is negative (a row that never
+ * votes) or equals exclude[p] (-1 = none; exclude may be NULL). Every remaining candidate adds its score to its song, a repeated candidate again. Totals are fp64 sums
+ * of the fp32 scores in walk order from 0.0, as the reference's dict of Python floats: bit for bit the host's. Songs rank by
+ * descending total, equal totals in the order of first appearance in the walk (Python's stable sorted(reverse=True)). songs
+ * (npairs x top, int32) = the song codes best first, -1 past the last; totals (npairs x top, fp64) their sums, 0 past the last;
+ * n_songs[p] = the distinct songs that entered (it can exceed top). No atomics; a pair's result depends on nothing but the pair.
+ * Limits: 1 <= k <= 64, 1 <= top <= 32, 1 <= L and L k <= 4096; npairs == 0 launches nothing.
+ * song_vote: the score of walk position j is scores[p lds + j]; lds bounds every pair's L k, and 1 <= lds <= 4096.
+ * song_vote_clf: the score of walk position j is max over i < L of S[s_off[p] + i s_ld[p] + j] in fp32 (device int64 s_off, int32
+ *   s_ld: per pair its score block and its row length; a NaN wins the max, as numpy's); the candidate is skipped unless score >=
+ *   threshold (the reference: 0.5), so a song enters, and gets its first-appearance position, at its first candidate that passes.
+ *   Column j of a block is walk position j: the walk of a shorter L over the same start is a prefix, so one block per test at its
+ *   longest length serves every shorter one.
+ * k, top or lds outside their limits: NSID_EINVAL before any launch. The lengths live on the device: the caller checks them (ops.py
+ * does); a pair with L < 1, L k > 4096 or (song_vote) L k > lds reads and sums nothing and gets n_songs[p] = -1 and an empty row.
+ * vote_candidates: cidx[i] = I[i] - n_dummy for a ref row (n_dummy <= I[i] < n_dummy + n_ref), else 0: the candidate list of
+ *   clf_pair_scores_c / _n for a search result, on the device. The vote skips the other positions from I, so what is scored there is
+ *   never read. */
+int nsid_song_vote(const int64_t* I, int k, const float* scores, int lds, const int* starts, const int* lens, int npairs,
+                   const int* song_of, int n_ref, int n_dummy, const int* exclude, int top, int* songs, double* totals, int* n_songs,
+                   void* stream);
+int nsid_song_vote_clf(const int64_t* I, int k, const float* S, const int64_t* s_off, const int* s_ld, const int* starts,
+                       const int* lens, int npairs, const int* song_of, int n_ref, int n_dummy, const int* exclude, float threshold,
+                       int top, int* songs, double* totals, int* n_songs, void* stream);
+int nsid_vote_candidates(const int64_t* I, long n, int n_dummy, int n_ref, int* cidx, void* stream);
+
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed
  * order and no entry uses atomics: a pair's score and its per-pair gradients depend on nothing but the pair.

@@ -95,6 +95,9 @@ SIGNATURES = {
     "nsid_clf_pair_scores_c": "pipiiipppiipppls",
     "nsid_clf_node_rows_n": "piiipps",
     "nsid_clf_pair_scores_n": "pipiiipppiipppls",
+    "nsid_song_vote": "pipippipiipippps",
+    "nsid_song_vote_clf": "pipppppipiipfippps",
+    "nsid_vote_candidates": "pliips",
     "nsid_clf_mine_hard_negatives": "pipiiips",
     "nsid_clf_attn_fwd": "pipiippippps",
     "nsid_clf_head_fwd": "ppppips",

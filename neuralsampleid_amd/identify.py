@@ -1,0 +1,422 @@
+"""Which songs does this query sample? A resident index on the GPU: search, song-level vote and classifier re-rank without files.
+
+    idx = SampleIndex(model, classifier=clf, front=LogMelFrontEnd(cfg))
+    idx.add_dummy(noise_fp)                               # optional: rows that can be retrieved but never vote
+    for name, specs in songs:
+        idx.add(name, specs=specs)                        # or wave=..., or add_rows(name, fp, nodes) from fpdb files
+    r = idx.identify(wave=query, k_probe=20, top=10)      # r.songs: names, best first; r.totals; r.n_songs
+    r = idx.identify(specs=q_specs, rerank=True)          # the stage-2 classifier decides
+
+Reference: the votes are eval.py:296-367 (sequence scores, search.aggregate_hit_rates's rule) and eval_hr.py:85-156 (classifier
+scores, rerank.vote_hit_rates_clf's rule), on csrc/vote.hip; match_score and rejection_stats are ablation.py:84-97 and :111-139.
+The fingerprints live in a FlatL2Index over dummy ++ ref, the candidates' projected [K | P] classifier rows (4 N (C + 512) bytes
+per reference segment) and the song codes next to it, so an identification is search -> scores -> vote on the device and only
+the `top` results come back. The file-based evaluations (search.eval_hit_rates, rerank.eval_hit_rates_clf) are unchanged and do
+not use this module.
+
+Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs."""
+from typing import List, NamedTuple, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import ops
+from .search import FlatL2Index
+
+PROJ_BLOCK = 4096             # segments per classifier projection call
+CLF_THRESHOLD = 0.5           # eval_hr.py:131
+
+
+class Identification(NamedTuple):
+    songs: List[str]          # names, best first (at most `top`)
+    totals: np.ndarray        # float64, one per name
+    n_songs: int              # the distinct songs that voted (can exceed `top`)
+
+
+class PairVotes:
+    """the votes of many (start, length) pairs: device tensors codes (pairs, top) int32 (-1 past the last song), totals (pairs, top)
+    float64, n_songs (pairs,) int32; with a re-rank also the flat classifier scores and, per pair, the offset and the row length of
+    its block (column j = walk position j)"""
+
+    def __init__(self, names, codes, totals, n_songs, scores=None, s_off=None, s_ld=None):
+        self.names, self.codes, self.totals, self.n_songs = names, codes, totals, n_songs
+        self.scores, self.s_off, self.s_ld = scores, s_off, s_ld
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    def results(self) -> List[Identification]:
+        codes, totals, n = self.codes.cpu().numpy(), self.totals.cpu().numpy(), self.n_songs.cpu().numpy()
+        out = []
+        for p in range(codes.shape[0]):
+            m = int((codes[p] >= 0).sum())
+            out.append(Identification([self.names[c] for c in codes[p, :m].tolist()], totals[p, :m].copy(), int(n[p])))
+        return out
+
+
+def _is_baseline(model) -> bool:
+    from .encoder.resnet_ibn import ResNetIBN
+    return isinstance(model.encoder, ResNetIBN)
+
+
+def _need_tensor(t, what, dim, shape_text):
+    """type, rank and dtype: ValueError / TypeError before the device is looked at"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor on the GPU")
+    if t.dim() != dim:
+        raise ValueError(f"{what}: expected {shape_text}, got {tuple(t.shape)}")
+    if t.dtype != torch.float32:
+        raise ValueError(f"{what}: expected float32, got {t.dtype}")
+
+
+def _need_cuda(t, what):
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: SampleIndex runs on the MI355X (cuda) device; there is no CPU path")
+
+
+class SampleIndex:
+    """A resident sample-identification index. model: SimCLR (graph encoder) or BaselineModel (ResNet-IBN, no re-rank); classifier: a
+    CrossAttentionClassifier for rerank=True and match_score; front: LogMelFrontEnd / CQTFrontEnd, needed only for waveforms.
+    model may be None for an index fed with precomputed rows only (add_rows, identify(fp=...)); then d is taken from the first
+    rows."""
+
+    def __init__(self, model, classifier=None, front=None, device="cuda", micro_batch: int = 1024):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("SampleIndex runs on the MI355X (cuda) device; there is no CPU path")
+        self.model, self.classifier, self.front = model, classifier, front
+        self.micro_batch = int(micro_batch)
+        self.names: List[str] = []
+        self._code = {}
+        self._song_rows = []                  # per song: (first ref row, rows, rows with node matrices)
+        self._index: Optional[FlatL2Index] = None       # made with the first rows: nothing touches the device before
+        self._d = None
+        self.n_dummy = 0
+        self.n_ref = 0
+        self._song_of = None                  # (capacity,) int32 on the device: song code per ref row
+        self._song_of_nodes = None            # the same, -1 for a row without node matrices
+        self._kp = None                       # (capacity N, C + 512): the candidates' [K | P] rows
+        self.N = None                         # nodes per segment of the resident table
+        if model is not None:
+            from .fingerprint import embedding_dim
+            self._d = int(embedding_dim(model))
+
+    # ------------------------------------------------------------------------------------------------ state
+    @property
+    def d(self) -> Optional[int]:
+        return self._d
+
+    @property
+    def C(self) -> Optional[int]:
+        return None if self.classifier is None else int(self.classifier.attn.embed_dim)
+
+    @property
+    def fingerprints(self) -> torch.Tensor:
+        """the reference rows (n_ref, d) on the device, in add order"""
+        return self._index.xb[self.n_dummy:]
+
+    @property
+    def kp_bytes_per_segment(self) -> int:
+        return 0 if self._kp is None else 4 * self.N * self._kp.shape[1]
+
+    def __contains__(self, name) -> bool:
+        return name in self._code
+
+    def code(self, name: str) -> int:
+        if name not in self._code:
+            raise KeyError(f"SampleIndex: no song named {name!r}")
+        return self._code[name]
+
+    def _check_fp(self, fp, what, device=True):
+        _need_tensor(fp, what, 2, "(rows, d) fingerprints")
+        if self._d is not None and fp.shape[1] != self._d:
+            raise ValueError(f"{what}: the index holds d = {self._d} fingerprints, got {tuple(fp.shape)}")
+        if not ops.search_d_ok(fp.shape[1]):
+            raise ValueError(f"{what}: d = {fp.shape[1]} is outside the search kernels' limits ({ops.SEARCH_D_LIMITS})")
+        if device:
+            _need_cuda(fp, what)
+
+    def _store(self):
+        """the device state, made with the first rows"""
+        if self._index is None:
+            self._index = FlatL2Index(self._d, self.device)
+            self._song_of = torch.empty((0,), device=self.device, dtype=torch.int32)
+            self._song_of_nodes = torch.empty((0,), device=self.device, dtype=torch.int32)
+        return self._index
+
+    def _check_nodes(self, nodes, what):
+        if self.classifier is None:
+            raise RuntimeError(f"{what}: node matrices need a classifier (SampleIndex(model, classifier=...))")
+        _need_tensor(nodes, what, 3, f"(S, {self.C}, N) node matrices")
+        if nodes.shape[1] != self.C:
+            raise ValueError(f"{what}: expected (S, {self.C}, N) node matrices for a classifier of in_dim {self.C}, got {tuple(nodes.shape)}")
+        if self.N is not None and nodes.shape[2] != self.N:
+            raise ValueError(f"{what}: the index holds node matrices of N = {self.N} nodes, got {tuple(nodes.shape)}")
+        if not 1 <= nodes.shape[2] <= ops.CLF_MAX_N_EVAL:
+            raise ValueError(f"{what}: N = {nodes.shape[2]} nodes is outside [1, {ops.CLF_MAX_N_EVAL}]")
+        _need_cuda(nodes, what)
+
+    @staticmethod
+    def _grown(t, rows, unit=1):
+        """t with room for `rows` units of `unit` rows: capacity doubles, earlier rows are kept"""
+        if rows * unit <= t.shape[0]:
+            return t
+        cap = max(rows, 2 * (t.shape[0] // unit))
+        new = torch.zeros((cap * unit,) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype)
+        new[: t.shape[0]].copy_(t)
+        return new
+
+    # ------------------------------------------------------------------------------------------------ encoding
+    @torch.no_grad()
+    def _encode(self, specs, want_nodes):
+        """(S, bins, frames) segments -> (fingerprints (S, d), node matrices (S, C, N) or None): one eval pass per micro-batch, both
+        outputs of forward_rows(..., return_nodes=True) as downstream.encode_pairs takes them"""
+        from . import functional
+        from .fingerprint import extract_fingerprints
+        if self.model is None:
+            raise RuntimeError("SampleIndex: specs / wave need a model")
+        _need_tensor(specs, "specs", 3, "(S, bins, frames) segments")
+        _need_cuda(specs, "specs")
+        model = self.model
+        if _is_baseline(model) or not want_nodes:
+            if want_nodes:
+                raise NotImplementedError("the ResNet-IBN baseline has no node matrices: rerank / classifier are not available with it")
+            return extract_fingerprints(model, specs, self.micro_batch), None
+        was_training = model.training
+        model.eval()
+        if functional.ACT_DTYPE == torch.bfloat16:
+            ops.register_weight_shadows(model)
+        try:
+            pe = model.peak_extractor
+            S = specs.shape[0]
+            fp = torch.empty((S, self.d), device=specs.device, dtype=torch.float32)
+            nodes = []
+            for lo in range(0, S, self.micro_batch):
+                x = specs[lo:lo + self.micro_batch].contiguous()
+                B, H, W = x.shape
+                N = (H // pe.patch_bins) * (W // pe.patch_frames)
+                rows, n_last, emb = model.encoder.forward_rows(pe.forward_rows(x), B, N, return_nodes=True)
+                nodes.append(functional.from_rows(rows, B, n_last).float().contiguous())
+                fp[lo:lo + B].copy_(model._project(emb))
+            return fp, (torch.cat(nodes, 0) if len(nodes) > 1 else nodes[0]) if nodes else None
+        finally:
+            model.train(was_training)
+
+    def _segments(self, specs, wave):
+        if (specs is None) == (wave is None):
+            raise ValueError("give exactly one of specs and wave")
+        if wave is not None:
+            if self.front is None:
+                raise RuntimeError("SampleIndex: a waveform needs a front end (SampleIndex(model, front=LogMelFrontEnd(cfg)))")
+            _need_tensor(wave, "wave", 1, "a mono (samples,) waveform")
+            _need_cuda(wave, "wave")
+            specs = self.front(wave)
+        if specs.shape[0] == 0:
+            raise ValueError("no segment: the audio is shorter than one segment")
+        return specs
+
+    @torch.no_grad()
+    def _project(self, fn, nodes):
+        parts = [fn(nodes[a:a + PROJ_BLOCK].contiguous()) for a in range(0, nodes.shape[0], PROJ_BLOCK)]
+        return torch.cat(parts) if len(parts) > 1 else parts[0]
+
+    # ------------------------------------------------------------------------------------------------ filling
+    def add_dummy(self, fp_rows: torch.Tensor) -> None:
+        """rows that can be retrieved but never vote (the reference's dummy_db); before the first add()"""
+        self._check_fp(fp_rows, "add_dummy")
+        if self.n_ref:
+            raise RuntimeError("SampleIndex.add_dummy: dummy rows come before the first song (ids are dummy ++ ref)")
+        self._d = int(fp_rows.shape[1])
+        self._store().add(fp_rows)
+        self.n_dummy += fp_rows.shape[0]
+
+    def add(self, name: str, specs: Optional[torch.Tensor] = None, wave: Optional[torch.Tensor] = None) -> int:
+        """one song from its (S, bins, frames) segments, or from its waveform through `front`; returns its number of segments"""
+        specs = self._segments(specs, wave)
+        fp, nodes = self._encode(specs, self.classifier is not None)
+        self.add_rows(name, fp, nodes)
+        return int(fp.shape[0])
+
+    def add_rows(self, name: str, fp: torch.Tensor, nodes: Optional[torch.Tensor] = None) -> None:
+        """one song from precomputed rows: (S, d) fingerprints and, for the re-rank, (S', C, N) node matrices (fpdb's files). Segments
+        without node matrices (nodes=None, or S' < S: the reference's missing / short ref_nmatrix file) are retrieved and vote on
+        sequence scores, and are skipped by the classifier vote, as eval_hr.py skips them."""
+        self._check_fp(fp, "add_rows", device=False)          # every shape before the device: a refusal names the first thing wrong
+        if nodes is not None:
+            self._check_nodes(nodes, "add_rows")
+        _need_cuda(fp, "add_rows")
+        if not isinstance(name, str) or name in self._code:
+            raise ValueError(f"SampleIndex.add_rows: a song name must be a new string, got {name!r}")
+        S = int(fp.shape[0])
+        if S == 0:
+            raise ValueError("SampleIndex.add_rows: a song needs at least one segment")
+        with_nodes = 0
+        if nodes is not None:
+            with_nodes = min(S, int(nodes.shape[0]))
+        code = len(self.names)
+        lo, hi = self.n_ref, self.n_ref + S
+        kp = None
+        if with_nodes:
+            kp = self._project(self.classifier.project_candidates, nodes[:with_nodes].contiguous())
+        self._d = int(fp.shape[1])
+        self._store().add(fp)
+        self._song_of = self._grown(self._song_of, hi)
+        self._song_of_nodes = self._grown(self._song_of_nodes, hi)
+        self._song_of[lo:hi] = code
+        self._song_of_nodes[lo:hi] = -1
+        self._song_of_nodes[lo:lo + with_nodes] = code
+        if self.classifier is not None and (kp is not None or self._kp is not None):
+            if self._kp is None:
+                self.N = int(nodes.shape[2])
+                self._kp = torch.zeros((0, kp.shape[1]), device=self.device, dtype=torch.float32)
+            self._kp = self._grown(self._kp, hi, self.N)
+            if kp is not None:
+                self._kp[lo * self.N:(lo + with_nodes) * self.N].copy_(kp)
+        self.names.append(name)
+        self._code[name] = code
+        self._song_rows.append((lo, S, with_nodes))
+        self.n_ref = hi
+
+    # ------------------------------------------------------------------------------------------------ asking
+    def _query(self, specs, wave, fp, nodes, rerank):
+        if fp is None:
+            fp, enc_nodes = self._encode(self._segments(specs, wave), rerank)
+            nodes = enc_nodes if nodes is None else nodes
+        elif specs is not None or wave is not None:
+            raise ValueError("give fp (with nodes for a re-rank), or specs, or wave")
+        return fp, nodes
+
+    def identify(self, specs=None, wave=None, fp=None, nodes=None, k_probe: int = 20, top: int = 10, exclude: Optional[str] = None,
+                 rerank: bool = False) -> Identification:
+        """the songs a query samples, best first: all its L segments as one pair (0, L). exclude: a song name that never votes (the
+        reference skips a ref song named like the query id)"""
+        if rerank:
+            self._check_rerank()
+        fp, nodes = self._query(specs, wave, fp, nodes, rerank)
+        self._check_fp(fp, "identify")
+        pv = self.identify_pairs(fp, [0], [fp.shape[0]], k_probe=k_probe, top=top, exclude=None if exclude is None else [exclude],
+                                 rerank=rerank, nodes=nodes)
+        return pv.results()[0]
+
+    def _check_rerank(self):
+        if self.model is not None and _is_baseline(self.model):
+            raise NotImplementedError("the ResNet-IBN baseline has no node matrices: rerank=True is not available with it")
+        if self.classifier is None:
+            raise RuntimeError("SampleIndex: rerank=True needs a classifier (SampleIndex(model, classifier=...))")
+
+    @torch.no_grad()
+    def identify_pairs(self, fp: torch.Tensor, starts: Sequence[int], lens: Sequence[int], k_probe: int = 20, top: int = 10,
+                       exclude: Optional[Sequence[Optional[str]]] = None, rerank: bool = False,
+                       nodes: Optional[torch.Tensor] = None) -> PairVotes:
+        """many (start, length) pairs of one query table at once, the evaluation's form: fp (rows, d); pair p votes over rows
+        [starts[p], starts[p] + lens[p]); exclude: per pair a song name or None; nodes (rows, C, N) for rerank=True. Every row is
+        searched once, and with a re-rank the pairs of one start share one score block at their longest length."""
+        self._check_fp(fp, "identify_pairs")
+        if rerank:
+            self._check_rerank()
+            if nodes is None:
+                raise ValueError("identify_pairs: rerank=True needs the query's node matrices")
+            self._check_nodes(nodes, "identify_pairs")
+            if nodes.shape[0] != fp.shape[0]:
+                raise ValueError(f"identify_pairs: {fp.shape[0]} fingerprints but {nodes.shape[0]} node matrices")
+            if self._kp is None:
+                raise RuntimeError("identify_pairs: rerank=True, but no song of the index has node matrices")
+        k, top = int(k_probe), int(top)
+        if not 1 <= k <= ops.SEARCH_MAX_K:
+            raise ValueError(f"k_probe = {k} is outside [1, {ops.SEARCH_MAX_K}]")
+        if not 1 <= top <= ops.VOTE_MAX_TOP:
+            raise ValueError(f"top = {top} is outside [1, {ops.VOTE_MAX_TOP}]")
+        starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+        lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+        if starts.shape != lens.shape:
+            raise ValueError("identify_pairs: starts and lens differ in length")
+        if starts.size and (starts.min() < 0 or lens.min() < 1 or (starts + lens).max() > fp.shape[0]):
+            raise ValueError("identify_pairs: every pair needs 0 <= start, 1 <= length and start + length <= the rows of fp")
+        if starts.size and int(lens.max()) * k > ops.VOTE_MAX_CAND:
+            raise ValueError(f"identify_pairs: {int(lens.max())} segments x k_probe = {k} is more than {ops.VOTE_MAX_CAND} candidates per "
+                             "vote: lower k_probe or split the query")
+        ex = None
+        if exclude is not None:
+            if len(exclude) != starts.size:
+                raise ValueError("identify_pairs: exclude must hold one song name (or None) per pair")
+            ex = np.asarray([-1 if e is None else self.code(e) for e in exclude], dtype=np.int64)
+        if self.n_ref == 0:
+            raise RuntimeError("SampleIndex: the index holds no song")
+        npairs = starts.size
+        if npairs == 0:
+            return PairVotes(self.names, torch.empty((0, top), device=self.device, dtype=torch.int32),
+                             torch.empty((0, top), device=self.device, dtype=torch.float64),
+                             torch.empty((0,), device=self.device, dtype=torch.int32))
+        fp = fp.contiguous()
+        _, I = self._index.search(fp, k)
+        if not rerank:
+            scores = ops.seq_scores(fp, self._index.xb, I, starts, lens, int(lens.max()) * k)
+            return PairVotes(self.names, *ops.song_vote(I, scores, starts, lens, self._song_of[: self.n_ref], self.n_dummy, ex, top))
+        # one group per distinct start: its rows at the longest length against their own candidates, in walk order
+        ustarts, inv = np.unique(starts, return_inverse=True)
+        longest = np.zeros(ustarts.size, dtype=np.int64)
+        np.maximum.at(longest, inv, lens)
+        rows = np.concatenate([np.arange(s, s + n) for s, n in zip(ustarts.tolist(), longest.tolist())])
+        rows_dev = torch.from_numpy(rows).to(self.device)
+        cidx = ops.vote_candidates(I.index_select(0, rows_dev).contiguous(), self.n_dummy, self.n_ref).reshape(-1)
+        q = self._project(self.classifier.project_queries, nodes)
+        tail = self.classifier.folded()[4]
+        out, off = ops.clf_pair_scores_dev(q, self._kp[: self.n_ref * self.N], self.N, tail, ustarts, longest, longest * k, cidx)
+        s_off, s_ld = np.asarray(off)[inv], (longest * k)[inv]
+        votes = ops.song_vote_clf(I, out, s_off, s_ld, starts, lens, self._song_of_nodes[: self.n_ref], self.n_dummy, ex,
+                                  CLF_THRESHOLD, top)
+        return PairVotes(self.names, *votes, scores=out, s_off=s_off, s_ld=s_ld)
+
+    @torch.no_grad()
+    def match_score(self, nodes_q: torch.Tensor, name: Optional[str] = None, nodes: Optional[torch.Tensor] = None) -> float:
+        """ablation.py:84-97: the mean over the query's segments of the best classifier score over a song's segments. The song is a
+        resident one (name) or explicit (S, C, N) node matrices (the reference's torch.randn_like stand-in for 'no song')."""
+        if self.classifier is None:
+            raise RuntimeError("SampleIndex.match_score needs a classifier (SampleIndex(model, classifier=...))")
+        if (name is None) == (nodes is None):
+            raise ValueError("match_score: give exactly one of name and nodes")
+        self._check_nodes(nodes_q, "match_score")
+        if nodes_q.shape[0] == 0:
+            raise ValueError("match_score: the query has no segment")
+        N = int(nodes_q.shape[2])
+        if name is not None:
+            lo, _, with_nodes = self._song_rows[self.code(name)]
+            if with_nodes == 0:
+                raise ValueError(f"match_score: song {name!r} has no node matrices")
+            if N != self.N:
+                raise ValueError(f"match_score: the index holds node matrices of N = {self.N} nodes, got {N}")
+            kp = self._kp[lo * N:(lo + with_nodes) * N]
+            n_seg = with_nodes
+        else:
+            self._check_nodes(nodes, "match_score")
+            if nodes.shape[2] != N or nodes.shape[0] == 0:
+                raise ValueError("match_score: query and song node counts differ, or the song has no segment")
+            kp = self._project(self.classifier.project_candidates, nodes.contiguous())
+            n_seg = int(nodes.shape[0])
+        q = self._project(self.classifier.project_queries, nodes_q.contiguous())
+        Sq = int(nodes_q.shape[0])
+        out, _ = self.classifier.score_blocks(q, kp, N, [0], [Sq], np.arange(n_seg), [0], [n_seg])
+        return float(out.view(Sq, n_seg).max(dim=1).values.double().mean())
+
+
+def rejection_stats(real_scores, dummy_scores, threshold: float = 0.5):
+    """ablation.py:111-139 without the plot: (auroc, true_rejects, false_accepts). AUROC of real (label 1) against dummy (label 0)
+    scores by ranks with ties averaged (Mann-Whitney U / (n1 n0), what sklearn's roc_auc_score computes); true_rejects = dummies
+    below the threshold, false_accepts = dummies at or above it."""
+    real = np.asarray(real_scores, dtype=np.float64).reshape(-1)
+    dummy = np.asarray(dummy_scores, dtype=np.float64).reshape(-1)
+    if real.size == 0 or dummy.size == 0:
+        raise ValueError("rejection_stats: both score lists must be non-empty")
+    if np.isnan(real).any() or np.isnan(dummy).any():
+        raise ValueError("rejection_stats: a score is NaN")
+    scores = np.concatenate([real, dummy])
+    order = np.argsort(scores, kind="stable")
+    sorted_scores = scores[order]
+    first = np.flatnonzero(np.r_[True, sorted_scores[1:] != sorted_scores[:-1]])
+    count = np.diff(np.r_[first, scores.size])
+    avg_rank = np.repeat(first + (count + 1) / 2.0, count)          # 1-based ranks, ties averaged
+    rank = np.empty(scores.size)
+    rank[order] = avg_rank
+    u = rank[: real.size].sum() - real.size * (real.size + 1) / 2.0
+    auroc = float(u / (real.size * dummy.size))
+    return auroc, int((dummy < threshold).sum()), int((dummy >= threshold).sum())

@@ -1914,6 +1914,135 @@ def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:
     return out
 
 
+# ------------------------------------------------------------------------------------------------ song-level vote (csrc/vote.hip)
+VOTE_MAX_CAND = 4096          # L k of a pair at most
+VOTE_MAX_TOP = 32
+
+
+def _vote_args(name, I, starts, lens, song_of, n_dummy, exclude, top):
+    """the checks the two votes share; returns (k, starts, lens as int64 numpy, exclude as int32 numpy or None, n_ref, n_dummy, top)"""
+    if not I.is_cuda or not song_of.is_cuda:
+        raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if I.dtype != torch.int64 or I.dim() != 2 or not I.is_contiguous():
+        raise RuntimeError(f"{name}: I must be a contiguous (rows, k) int64 tensor on the GPU")
+    if song_of.dtype != torch.int32 or song_of.dim() != 1 or not song_of.is_contiguous():
+        raise RuntimeError(f"{name}: song_of must be a contiguous 1-D int32 tensor (one song code per ref row; negative = never votes) on the GPU")
+    k, top, n_dummy = I.shape[1], int(top), int(n_dummy)
+    if not 1 <= k <= SEARCH_MAX_K:
+        raise ValueError(f"{name}: k = {k} is outside [1, {SEARCH_MAX_K}]")
+    if not 1 <= top <= VOTE_MAX_TOP:
+        raise ValueError(f"{name}: top = {top} is outside [1, {VOTE_MAX_TOP}]")
+    if n_dummy < 0 or n_dummy + song_of.numel() >= 2 ** 31:
+        raise ValueError(f"{name}: n_dummy must be >= 0 and the ids must stay below 2^31")
+    starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+    lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+    if starts.shape != lens.shape:
+        raise ValueError(f"{name}: starts and lens differ in length")
+    if starts.size and (starts.min() < 0 or lens.min() < 1 or (starts + lens).max() > I.shape[0]):
+        raise ValueError(f"{name}: every pair needs 0 <= start, 1 <= length and start + length <= the rows of I")
+    if starts.size and int(lens.max()) * k > VOTE_MAX_CAND:
+        raise ValueError(f"{name}: a pair of {int(lens.max())} rows x k = {k} has more than {VOTE_MAX_CAND} candidates")
+    if exclude is not None:
+        exclude = np.asarray(exclude, dtype=np.int64).reshape(-1)
+        if exclude.shape != starts.shape:
+            raise ValueError(f"{name}: exclude must hold one song code (-1 = none) per pair")
+        exclude = exclude.astype(np.int32)
+    return k, starts, lens, exclude, int(song_of.numel()), n_dummy, top
+
+
+def _vote_out(npairs, top, device):
+    return (torch.empty((npairs, top), device=device, dtype=torch.int32), torch.empty((npairs, top), device=device, dtype=torch.float64),
+            torch.empty((npairs,), device=device, dtype=torch.int32))
+
+
+def _vote_table(device, starts, lens, exclude, *more):
+    """the per-pair int32 columns of a vote in ONE upload (a one-pair vote is latency: every copy counts); returns the device rows
+    (starts, lens, exclude or None, *more)"""
+    cols = [starts, lens, lens if exclude is None else exclude, *more]
+    t = torch.from_numpy(np.stack(cols).astype(np.int32)).to(device)
+    return (t[0], t[1], None if exclude is None else t[2], *(t[3 + i] for i in range(len(more))))
+
+
+def song_vote(I, scores, starts, lens, song_of, n_dummy, exclude=None, top=10):
+    """The song-level vote of eval.py:296-367 for every (start, length) pair at once (search.aggregate_hit_rates's rule).
+
+    I (rows, k) int64 ids over dummy ++ ref; scores (pairs, >= max length * k) fp32: seq_scores' output for the same pairs; song_of
+    (n_ref,) int32 device song codes (a negative code never votes); exclude: one song code per pair that never votes (-1 = none), or None. starts / lens / exclude:
+    host integer sequences, checked here. Returns (songs (pairs, top) int32, best first, -1 past the last; totals (pairs, top) float64,
+    bit for bit the host's sums; n_songs (pairs,) int32 = the distinct songs that voted), all on the device."""
+    k, starts, lens, exclude, n_ref, n_dummy, top = _vote_args("song_vote", I, starts, lens, song_of, n_dummy, exclude, top)
+    if not scores.is_cuda:
+        raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if scores.dtype != torch.float32 or scores.dim() != 2 or scores.stride(1) != 1 and scores.shape[1] > 1:
+        raise RuntimeError("song_vote: scores must be a (pairs, columns) float32 matrix with unit column stride on the GPU")
+    npairs = starts.size
+    if scores.shape[0] != npairs or (npairs and scores.shape[1] < int(lens.max()) * k):
+        raise ValueError(f"song_vote: scores must be ({npairs}, >= {int(lens.max()) * k if npairs else 0}), got {tuple(scores.shape)}")
+    songs, totals, n_songs = _vote_out(npairs, top, I.device)
+    if npairs == 0:
+        return songs, totals, n_songs
+    lds = int(scores.stride(0)) if npairs > 1 else int(scores.shape[1])
+    if not scores.shape[1] <= lds <= VOTE_MAX_CAND:
+        raise ValueError(f"song_vote: the rows of scores must be {VOTE_MAX_CAND} floats apart at most and must not overlap, got {lds}")
+    st, ln, ex = _vote_table(I.device, starts, lens, exclude)
+    ncand = float((lens * k).sum())
+    _tk("song_vote_kernel", 12.0 * ncand + 4.0 * ncand + 16.0 * npairs * top, lambda: call(
+        "nsid_song_vote", _p(I), k, _p(scores), lds, _p(st), _p(ln), npairs, _p(song_of), n_ref, n_dummy, _p(ex), top, _p(songs),
+        _p(totals), _p(n_songs), _stream()), (npairs, int(lens.max()) * k, top, 1))
+    return songs, totals, n_songs
+
+
+def song_vote_clf(I, S, s_off, s_ld, starts, lens, song_of, n_dummy, exclude=None, threshold=0.5, top=10):
+    """The song-level vote of eval_hr.py:85-156 for every (start, length) pair at once (rerank.vote_hit_rates_clf's rule, without
+    its node-matrix file skips: every ref row of the index has node matrices).
+
+    S: flat fp32 classifier scores on the device; pair p's block starts at s_off[p], has rows of s_ld[p] floats, and its column j is
+    walk position j (clf_pair_scores_dev over vote_candidates' list): the score of position j is the max over the pair's first L rows,
+    added to its song when >= threshold. The other arguments and the result are song_vote's."""
+    k, starts, lens, exclude, n_ref, n_dummy, top = _vote_args("song_vote_clf", I, starts, lens, song_of, n_dummy, exclude, top)
+    _chk(S)
+    S = S.reshape(-1)
+    s_off = np.asarray(s_off, dtype=np.int64).reshape(-1)
+    s_ld = np.asarray(s_ld, dtype=np.int64).reshape(-1)
+    npairs = starts.size
+    if s_off.shape != starts.shape or s_ld.shape != starts.shape:
+        raise ValueError("song_vote_clf: s_off and s_ld must hold one entry per pair")
+    if npairs and (s_off.min() < 0 or s_ld.min() < 0 or s_ld.max() >= 2 ** 31
+                   or (s_off + (lens - 1) * s_ld + lens * k).max() > S.numel()):
+        raise ValueError("song_vote_clf: a pair's score block (length rows of s_ld floats, length * k columns) leaves S")
+    threshold = float(threshold)
+    if threshold != threshold:
+        raise ValueError("song_vote_clf: threshold is NaN")
+    songs, totals, n_songs = _vote_out(npairs, top, I.device)
+    if npairs == 0:
+        return songs, totals, n_songs
+    st, ln, ex, sl = _vote_table(I.device, starts, lens, exclude, s_ld)
+    so = torch.from_numpy(np.ascontiguousarray(s_off)).to(I.device)
+    ncand = float((lens * k).sum())
+    _tk("song_vote_kernel<clf>", 12.0 * ncand + 4.0 * float((lens * lens * k).sum()) + 16.0 * npairs * top, lambda: call(
+        "nsid_song_vote_clf", _p(I), k, _p(S), _p(so), _p(sl), _p(st), _p(ln), npairs, _p(song_of), n_ref, n_dummy, _p(ex), threshold,
+        top, _p(songs), _p(totals), _p(n_songs), _stream()), (npairs, int(lens.max()) * k, top, 1))
+    return songs, totals, n_songs
+
+
+def vote_candidates(I, n_dummy, n_ref) -> torch.Tensor:
+    """the device candidate list of a search result: I (any shape) int64 ids over dummy ++ ref -> int32 of the same shape, I - n_dummy
+    for a ref row and 0 elsewhere (the votes skip those positions from I, so what is scored there is never read)"""
+    if not I.is_cuda:
+        raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if I.dtype != torch.int64 or not I.is_contiguous():
+        raise RuntimeError("vote_candidates: I must be a contiguous int64 tensor on the GPU")
+    n_dummy, n_ref = int(n_dummy), int(n_ref)
+    if n_dummy < 0 or n_ref < 0 or n_dummy + n_ref >= 2 ** 31:
+        raise ValueError("vote_candidates: n_dummy and n_ref must be >= 0 and the ids must stay below 2^31")
+    cidx = torch.empty(I.shape, device=I.device, dtype=torch.int32)
+    n = I.numel()
+    if n:
+        _tk("vote_candidates_kernel", 12.0 * n, lambda: call("nsid_vote_candidates", _p(I), n, n_dummy, n_ref, _p(cidx), _stream()),
+            (n, 0, 0, 1))
+    return cidx
+
+
 # ------------------------------------------------------------------------------------------------ classifier re-rank (csrc/rerank.hip)
 CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = 512, 1024, 32, 64
 CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
@@ -2015,6 +2144,60 @@ def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_c
            4.0 * npairs + 4.0 * (C + CLF_PW) * N * float(tile_off[-1]),
            lambda: call("nsid_clf_pair_scores_c", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
                         _p(cit), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
+    return out, out_off[:-1]
+
+
+def clf_pair_scores_dev(q, kp, N, tail, q_start, q_count, cand_count, cidx):
+    """clf_pair_scores with the candidate lists on the device: cidx is a 1-D int32 device tensor (vote_candidates of a search result)
+    that holds the groups' lists one after the other, so group i's list starts at the running sum of cand_count. The host still owns
+    every size (q_start, q_count, cand_count: host integer sequences, checked here); the entries of cidx are not read by the host:
+    the kernels skip, and leave unwritten, a pair whose candidate lies outside [0, nc_seg). Same kernels, same scores and the same
+    result form as clf_pair_scores: (out, out_off)."""
+    _chk(q, kp, tail)
+    N = int(N)
+    if not 1 <= N <= CLF_MAX_N_EVAL:
+        raise ValueError(f"clf_pair_scores_dev: N = {N} is outside [1, {CLF_MAX_N_EVAL}]")
+    if q.dim() != 2 or kp.dim() != 2:
+        raise ValueError(f"clf_pair_scores_dev: expected q (S N, C) and kp (S N, C + {CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
+    C = _clf_width(q.shape[1], "clf_pair_scores_dev")
+    if q.shape[0] % N or kp.shape[1] != C + CLF_PW or kp.shape[0] % N:
+        raise ValueError(f"clf_pair_scores_dev: expected q (S N, {C}) and kp (S N, {C + CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
+    if tail.numel() != 257:
+        raise ValueError("clf_pair_scores_dev: tail must hold g (128), w2 (128) and b2")
+    _clf_idx(cidx, "clf_pair_scores_dev cidx")
+    nq_seg, nc_seg = q.shape[0] // N, kp.shape[0] // N
+    qs, qn, cn = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (q_start, q_count, cand_count))
+    G = qs.size
+    if not qn.size == cn.size == G:
+        raise ValueError("clf_pair_scores_dev: q_start, q_count and cand_count differ in length")
+    if G and (qs.min() < 0 or qn.min() < 0 or (qs + qn).max() > nq_seg or cn.min() < 0 or cn.sum() > cidx.numel()):
+        raise ValueError("clf_pair_scores_dev: a group's query range or candidate list is out of range")
+    co = np.cumsum(cn) - cn
+    sizes = qn * cn
+    out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    tiles = cn * ((qn + CLF_QCHUNK - 1) // CLF_QCHUNK)
+    tile_off = np.concatenate([[0], np.cumsum(tiles)]).astype(np.int64)
+    if tile_off[-1] >= 2 ** 31 or max(nq_seg, nc_seg) * N >= 2 ** 31 or (G and cn.sum() >= 2 ** 31):
+        raise ValueError("clf_pair_scores_dev: too many pairs for one call")
+    out = torch.empty((int(out_off[-1]),), device=q.device, dtype=torch.float32)
+    if G == 0 or tile_off[-1] == 0:
+        return out, out_off[:-1]
+    dev = q.device
+    grp = torch.from_numpy(np.stack([qs, qn, co, cn], 1).astype(np.int32).reshape(-1)).to(dev)
+    oo = torch.from_numpy(out_off[:-1].copy()).to(dev)
+    to = torch.from_numpy(tile_off.astype(np.int32)).to(dev)
+    npairs = float(sizes.sum())
+    if N > CLF_MAX_N:                     # flop and byte counts: as clf_pair_scores
+        nt = (N + 31) // 32
+        _timed("clf_pair_wide_kernel", (2.0 * N * N * C + 12.0 * 4 * N * N + 2.0 * N * CLF_PW + 512.0) * npairs,
+               4.0 * npairs + 4.0 * CLF_PW * N * float(tile_off[-1]) + 4.0 * N * C * (1 + nt) * npairs,
+               lambda: call("nsid_clf_pair_scores_n", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G,
+                            int(tile_off[-1]), _p(cidx), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
+        return out, out_off[:-1]
+    _timed("clf_pair_kernel", (1.2e6 + 2.0 * CLF_MAX_N * CLF_MAX_N * (C - CLF_C)) * npairs,
+           4.0 * npairs + 4.0 * (C + CLF_PW) * N * float(tile_off[-1]),
+           lambda: call("nsid_clf_pair_scores_c", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
+                        _p(cidx), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
     return out, out_off[:-1]
 
 
