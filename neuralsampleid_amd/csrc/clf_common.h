@@ -1,0 +1,139 @@
+// The attention tile of the stage-2 classifier (downstream.py:30-78 CrossAttentionClassifier), shared by its evaluation kernels
+// (rerank.hip) and its training kernels (clf_train.hip): the constants, the 32 x 32 MFMA register map, the masked row softmax, the
+// column sums, the workgroup -> (group, candidate, query chunk) decode, the folded tail and the dispatch over the widths.
+//
+// One tile is S^T[key][query] of 32 keys x 32 queries from v_mfma_f32_32x32x2f32 with A = K rows and B = Q rows: lane (r, hh), r =
+// lane & 31, hh = lane >> 5, holds in register i the score of query r against key acc_row(i, hh). The softmax of a query therefore
+// runs over the 16 registers of a lane and the two lane halves, the mean over the queries over the 32 lanes of a half. Every sum here
+// runs in one fixed order, and the evaluation and training kernels spell it the same way: a trained state scores in evaluation
+// exactly what a training forward with a ones mask gives (tests/test_clf_train_gpu.py).
+#pragma once
+#include "nsid_common.h"
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int CLF_H = 4;                   // heads; node channels C = 4 DH are template parameters of the kernels
+constexpr int CLF_TILE = 32;               // nodes of one 32 x 32 MFMA tile
+constexpr int CLF_HID = 128;               // fc.0 width
+constexpr int CLF_PW = CLF_H * CLF_HID;    // P row of the folded candidate side: one fc.0-wide block per head
+
+// 1 / sqrt(DH), rounded to fp32
+template <int DH> struct clf_scale;
+template <> struct clf_scale<128> { static constexpr float v = 0.08838834764831845f; };
+template <> struct clf_scale<160> { static constexpr float v = 0.07905694150420949f; };
+template <> struct clf_scale<192> { static constexpr float v = 0.07216878364870323f; };
+template <> struct clf_scale<256> { static constexpr float v = 0.0625f; };
+
+static inline bool clf_width_ok(int C) { return C == 512 || C == 640 || C == 768 || C == 1024; }
+// one launch of KERNEL<C, C / 4> for the supported widths
+#define CLF_LAUNCH_C(C, KERNEL, grid, block, st, ...)                                    \
+  switch (C) {                                                                           \
+    case 512: NSID_LAUNCH((KERNEL<512, 128>), grid, block, 0, st, __VA_ARGS__); break;   \
+    case 640: NSID_LAUNCH((KERNEL<640, 160>), grid, block, 0, st, __VA_ARGS__); break;   \
+    case 768: NSID_LAUNCH((KERNEL<768, 192>), grid, block, 0, st, __VA_ARGS__); break;   \
+    default: NSID_LAUNCH((KERNEL<1024, 256>), grid, block, 0, st, __VA_ARGS__); break;   \
+  }
+
+// key row of accumulator register i on lane half hh (the 32x32 C/D map)
+__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
+
+// ---- masked row softmax of a query over its keys. SCALED: the logits are acc * scale (training; the evaluation kernels get the
+// scale folded into the caller's projection and pass acc as it stands). key0 = first key of the tile; keys >= N get no weight.
+// One tile: clf_tile_softmax. Several key tiles of one query row: clf_tile_max over all of them, clf_half_max, clf_tile_exp over all
+// of them in tile order, clf_half_sum, then clf_tile_norm of each. The masked values are computed on every register and then
+// selected, which keeps the tile free of branches.
+template <bool SCALED> __device__ __forceinline__ float clf_logit(float a, float scale) { return SCALED ? a * scale : a; }
+template <bool SCALED>
+__device__ __forceinline__ float clf_tile_max(const f32x16& acc, int key0, int hh, int N, float scale, float mx) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if (key0 + acc_row(i, hh) < N) mx = fmaxf(mx, clf_logit<SCALED>(acc[i], scale));
+  return mx;
+}
+__device__ __forceinline__ float clf_half_max(float mx) { return fmaxf(mx, __shfl_xor(mx, 32)); }
+
+// e = exp(logit - mx), 0 on the keys >= N; returns sum + the 16 weights, added in register order. E: float[16] or f32x16, and e may
+// be acc itself (the kernel with several key tiles keeps the weights in the accumulators)
+template <bool SCALED, class E>
+__device__ __forceinline__ float clf_tile_exp(const f32x16& acc, E& e, int key0, int hh, int N, float scale, float mx, float sum) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float x = expf(clf_logit<SCALED>(acc[i], scale) - mx);       // training: one fma, as acc * scale - mx contracts
+    e[i] = key0 + acc_row(i, hh) < N ? x : 0.f;
+    sum += e[i];
+  }
+  return sum;
+}
+__device__ __forceinline__ float clf_half_sum(float sum) { return sum + __shfl_xor(sum, 32); }
+
+// v = the attention weights of the tile; a query row >= N (rowok false) has none. v may be e itself.
+template <class E>
+__device__ __forceinline__ void clf_tile_norm(const E& e, float (&v)[16], bool rowok, float sum) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const float x = e[i] / sum;
+    v[i] = rowok ? x : 0.f;
+  }
+}
+
+template <bool SCALED>
+__device__ __forceinline__ void clf_tile_softmax(const f32x16& acc, float (&v)[16], int hh, int N, bool rowok, float scale) {
+  const float mx = clf_half_max(clf_tile_max<SCALED>(acc, 0, hh, N, scale, -__builtin_inff()));
+  const float sum = clf_half_sum(clf_tile_exp<SCALED>(acc, v, 0, hh, N, scale, mx, 0.f));
+  clf_tile_norm(v, v, rowok, sum);
+}
+
+// ---- column sums of a tile's weights v over the 32 query lanes of each half: a reduce-scatter that halves the registers at every
+// step (16 .. 2: the lane with bit `off` of r set keeps the upper half and sends the lower), then one add across lanes r ^ 1. Both
+// lanes of a pair return the sum of key clf_lane_key(r, hh); v is used up.
+__device__ __forceinline__ float clf_colsum(float (&v)[16], int r) {
+#pragma unroll
+  for (int c = 16, off = 16; c > 1; c >>= 1, off >>= 1) {
+    const bool up = (r & off) != 0;
+#pragma unroll
+    for (int i = 0; i < c / 2; ++i) {
+      const float got = __shfl_xor(up ? v[i] : v[i + c / 2], off);      // sent first: the kept half is picked under its latency
+      v[i] = (up ? v[i + c / 2] : v[i]) + got;
+    }
+  }
+  return v[0] + __shfl_xor(v[0], 1);
+}
+// the key whose column sum clf_colsum leaves on lane (r, hh): bit 4 of r chose bit 3 of the register, bit 3 bit 2, bit 2 bit 1 and
+// bit 1 bit 0; that register's row on this lane half
+__device__ __forceinline__ int clf_lane_key(int r, int hh) {
+  const int gf = (((r >> 4) & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 1) & 1);
+  return acc_row(gf, hh);
+}
+
+// ---- pair lists of the evaluation kernels. Group g: {first query segment, query segments, offset into cidx, candidates}; its
+// scores are the row-major (q count x c count) block at out + out_off[g]. tile_off: prefix sums of the groups' workgroups (c count x
+// query chunks), ngroups + 1 entries. Workgroup b of the launch takes candidate jpos of group g (segment cand: not range-checked
+// here) and the query chunk qc.
+struct clf_tile { int g, q0, qn, cn, jpos, qc, cand; };
+__device__ __forceinline__ clf_tile clf_tile_decode(const int* grp, const int* tile_off, int ngroups, const int* cidx) {
+  // the last g with tile_off[g] <= blockIdx.x
+  int lo = 0, hi = ngroups - 1;
+  const int b = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (tile_off[mid] <= b) lo = mid; else hi = mid - 1;
+  }
+  const int coff = grp[4 * lo + 2], cn = grp[4 * lo + 3], i = b - tile_off[lo];
+  return clf_tile{lo, grp[4 * lo], grp[4 * lo + 1], cn, i % cn, i / cn, cidx[coff + i % cn]};
+}
+
+// ---- the tail. Sums over the wave are __shfl_xor trees over the offsets 32 .. 1: wave_sum (DPP) adds in another order.
+__device__ __forceinline__ float clf_xor_sum(float z) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off);
+  return z;
+}
+__device__ __forceinline__ float clf_sigmoid(float z) { return 1.0f / (1.0f + expf(-z)); }
+
+// folded tail of a pair: part0 / part1 = hidden[lane] / hidden[64 + lane] without g; tail = {g (128), w2 (128), b2}. Lane 0 stores
+// s = sigmoid(w2 . relu(hidden + g) + b2).
+__device__ __forceinline__ void clf_tail_store(float part0, float part1, const float* tail, int lane, float* dst) {
+  const float h0 = fmaxf(part0 + tail[lane], 0.f), h1 = fmaxf(part1 + tail[64 + lane], 0.f);
+  const float z = clf_xor_sum(fmaf(tail[CLF_HID + 64 + lane], h1, tail[CLF_HID + lane] * h0));
+  if (lane == 0) *dst = clf_sigmoid(z + tail[2 * CLF_HID]);
+}

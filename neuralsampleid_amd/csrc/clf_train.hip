@@ -15,27 +15,16 @@
 //
 // Widths: the attention kernels and the per-segment sums are templates on <C, DH>, C = 4 DH in {512, 640, 768, 1024}; the saved
 // attention layout (P, 4, 16, 64) and abar (P, 4, 32) do not depend on C. Mining and the head (fc.0 width 128) are the same at every C.
-#include "nsid_common.h"
+//
+// Nodes: N <= 32 (CLF_TILE), one 32 x 32 tile per head. The tile arithmetic (register map, masked softmax, column sums) and the
+// width dispatch are clf_common.h's, shared with the evaluation kernels, so a trained state scores there what it scores here.
+#include "clf_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int CT_H = 4;              // heads; node channels C = 4 DH are template parameters
-constexpr int CT_N = 32;             // nodes per segment at most (one 32x32 MFMA tile)
-constexpr int CT_HID = 128;          // fc.0 width
 constexpr int CT_MINE_MAXN = 8192;   // rows of the mining pool (2B) at most: their dots live in LDS
 constexpr int CT_MINE_MAXD = 512;
 constexpr int CT_RED_THREADS = 512;  // nsid_clf_seg_reduce: one workgroup per segment, C / 64 float4 per thread cover N x C
-
-// key row of accumulator register i on lane half hh (the 32x32 C/D map)
-__device__ __forceinline__ int acc_row(int i, int hh) { return (i & 3) + 8 * (i >> 2) + 4 * hh; }
-// 1 / sqrt(DH), rounded to fp32
-template <int DH> struct ct_scale;
-template <> struct ct_scale<128> { static constexpr float v = 0.08838834764831845f; };
-template <> struct ct_scale<160> { static constexpr float v = 0.07905694150420949f; };
-template <> struct ct_scale<192> { static constexpr float v = 0.07216878364870323f; };
-template <> struct ct_scale<256> { static constexpr float v = 0.0625f; };
 
 // ------------------------------------------------------------------------------------------------ hard-negative mining
 // (v, j) precedes (w, k) in the descending order with ties to the smaller index
@@ -95,8 +84,8 @@ __global__ __launch_bounds__(256) void clf_mine_kernel(const float* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ attention forward
-// One wave per pair, 4 pairs per workgroup. S^T[key][query] on the fp32 MFMA as rerank.hip does (A = K rows, B = Q rows, both
-// streamed from global memory as fragments); the softmax runs over the keys of each query lane. A is stored in its register layout,
+// One wave per pair, 4 pairs per workgroup. S^T[key][query] on the fp32 MFMA in clf_common.h's tile layout (A = K rows, B = Q rows,
+// both streamed from global memory as fragments); the softmax runs over the keys of each query lane. A is stored in its register layout,
 // (P, 4, 16, 64): the backward reloads the same registers. abar (P, 4, 32) = a_h; obar (P, C) = concat_h a_h^T V_h, 64 columns of
 // a head at a time (the last block of DH = 160 is half full).
 template <int C, int DH>
@@ -104,27 +93,26 @@ __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restri
                                                            int nc_seg, int N, const int* __restrict__ qi, const int* __restrict__ ci,
                                                            int P, float* __restrict__ obar, float* __restrict__ attn,
                                                            float* __restrict__ abar) {
-  static_assert(C == CT_H * DH && DH % 32 == 0, "4 heads of DH channels");
+  static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels");
   constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;        // [K | V] rows
   constexpr int OB = (DH + 63) / 64;                         // 64-column blocks of a head's output
-  __shared__ float abs_[4][CT_N];
+  __shared__ float abs_[4][CLF_TILE];
   const int lane = lane_id(), w = threadIdx.x >> 6;
   const int r = lane & 31, hh = lane >> 5;
   const int p = blockIdx.x * 4 + w;
   if (p >= P) return;
   const int qs = qi[p], cs = ci[p];
   if (qs < 0 || qs >= nq_seg || cs < 0 || cs >= nc_seg) return;      // the host checks the lists; this only keeps a bad one in bounds
-  const float scale = ct_scale<DH>::v;
+  const float scale = clf_scale<DH>::v;
   const float invN = 1.0f / (float)N;
   const bool rin = r < N;
   const float* qp = q + ((size_t)qs * N + (rin ? r : 0)) * CT_C + 4 * hh;
   const float* kp = kv + ((size_t)cs * N + (rin ? r : 0)) * CT_KV + 4 * hh;
   const float* vb = kv + (size_t)cs * N * CT_KV + CT_C;
-  const int gf = (((r >> 4) & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 1) & 1);
-  const int jf = (gf & 3) + 8 * (gf >> 2) + 4 * hh;
+  const int jf = clf_lane_key(r, hh);
 
 #pragma unroll 1
-  for (int h = 0; h < CT_H; ++h) {
+  for (int h = 0; h < CLF_H; ++h) {
     f32x16 acc = {};
 #pragma unroll
     for (int bb = 0; bb < CT_DH / 8; ++bb) {
@@ -133,39 +121,15 @@ __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restri
 #pragma unroll
       for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[e], qb[e], acc, 0, 0, 0);
     }
-    float mx = -__builtin_inff();
-#pragma unroll
-    for (int i = 0; i < 16; ++i)
-      if (acc_row(i, hh) < N) mx = fmaxf(mx, acc[i] * scale);
-    mx = fmaxf(mx, __shfl_xor(mx, 32));
     float v[16];
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      v[i] = acc_row(i, hh) < N ? expf(acc[i] * scale - mx) : 0.f;
-      sum += v[i];
-    }
-    sum += __shfl_xor(sum, 32);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) v[i] = rin ? v[i] / sum : 0.f;
-    float* ap = attn + ((size_t)p * CT_H + h) * 16 * 64 + lane;
+    clf_tile_softmax<true>(acc, v, hh, N, rin, scale);
+    float* ap = attn + ((size_t)p * CLF_H + h) * 16 * 64 + lane;
 #pragma unroll
     for (int i = 0; i < 16; ++i) ap[i * 64] = v[i];
-    // column sums over the 32 query lanes of each half (rerank.hip's reduce-scatter)
-#pragma unroll
-    for (int c = 16, off = 16; c > 1; c >>= 1, off >>= 1) {
-      const bool up = (r & off) != 0;
-#pragma unroll
-      for (int i = 0; i < c / 2; ++i) {
-        const float keep = up ? v[i + c / 2] : v[i];
-        const float send = up ? v[i] : v[i + c / 2];
-        v[i] = keep + __shfl_xor(send, off);
-      }
-    }
-    v[0] += __shfl_xor(v[0], 1);
+    const float cs = clf_colsum(v, r);
     if ((r & 1) == 0) {
-      abs_[w][jf] = v[0] * invN;
-      abar[((size_t)p * CT_H + h) * CT_N + jf] = v[0] * invN;
+      abs_[w][jf] = cs * invN;
+      abar[((size_t)p * CLF_H + h) * CLF_TILE + jf] = cs * invN;
     }
     __builtin_amdgcn_wave_barrier();
     float o[OB];
@@ -193,12 +157,10 @@ __global__ __launch_bounds__(256) void clf_head_fwd_kernel(const float* __restri
                                                            float* __restrict__ s) {
   const int lane = lane_id(), p = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (p >= P) return;
-  const float* hp = hid + (size_t)p * CT_HID;
-  const float* kp = keep + (size_t)p * CT_HID;
-  float z = fmaf(w2[64 + lane], relu_keep(hp[64 + lane], kp[64 + lane]), w2[lane] * relu_keep(hp[lane], kp[lane]));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off);
-  if (lane == 0) s[p] = 1.0f / (1.0f + expf(-(z + b2[0])));
+  const float* hp = hid + (size_t)p * CLF_HID;
+  const float* kp = keep + (size_t)p * CLF_HID;
+  const float z = clf_xor_sum(fmaf(w2[64 + lane], relu_keep(hp[64 + lane], kp[64 + lane]), w2[lane] * relu_keep(hp[lane], kp[lane])));
+  if (lane == 0) s[p] = clf_sigmoid(z + b2[0]);
 }
 
 // one wave per pair: dz = ds (1 - s) s (torch's sigmoid backward), dH = dz w2 keep where H > 0
@@ -210,7 +172,7 @@ __global__ __launch_bounds__(256) void clf_head_bwd_kernel(const float* __restri
   if (p >= P) return;
   const float sp = s[p];
   const float g = ds[p] * (1.0f - sp) * sp;
-  const size_t o = (size_t)p * CT_HID;
+  const size_t o = (size_t)p * CLF_HID;
 #pragma unroll
   for (int t = 0; t < 2; ++t) {
     const int j = lane + 64 * t;
@@ -222,25 +184,25 @@ __global__ __launch_bounds__(256) void clf_head_bwd_kernel(const float* __restri
 // one workgroup of 8 x 128 threads: dw2[j] = sum_p dz[p] (relu(H[p][j]) keep[p][j]) and db2 = sum_p dz[p]. Row group g sums the
 // pairs p = g (mod 8) in pair order, then the 8 partials are added in group order: a fixed order that does not depend on the GPU.
 constexpr int CT_WG_GROUPS = 8;
-__global__ __launch_bounds__(CT_WG_GROUPS * CT_HID) void clf_head_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ hid,
+__global__ __launch_bounds__(CT_WG_GROUPS * CLF_HID) void clf_head_wgrad_kernel(const float* __restrict__ dz, const float* __restrict__ hid,
                                                                              const float* __restrict__ keep, int P,
                                                                              float* __restrict__ dw2, float* __restrict__ db2) {
-  __shared__ float part[CT_WG_GROUPS][CT_HID + 1];
-  const int j = threadIdx.x % CT_HID, g = threadIdx.x / CT_HID;
+  __shared__ float part[CT_WG_GROUPS][CLF_HID + 1];
+  const int j = threadIdx.x % CLF_HID, g = threadIdx.x / CLF_HID;
   float acc = 0.f, accb = 0.f;
 #pragma unroll 8
   for (int p = g; p < P; p += CT_WG_GROUPS) {
     const float d = dz[p];
-    acc = fmaf(d, relu_keep(hid[(size_t)p * CT_HID + j], keep[(size_t)p * CT_HID + j]), acc);
+    acc = fmaf(d, relu_keep(hid[(size_t)p * CLF_HID + j], keep[(size_t)p * CLF_HID + j]), acc);
     accb += d;
   }
   part[g][j] = acc;
-  if (j == 0) part[g][CT_HID] = accb;
+  if (j == 0) part[g][CLF_HID] = accb;
   __syncthreads();
-  if (threadIdx.x <= CT_HID) {
+  if (threadIdx.x <= CLF_HID) {
     float s = part[0][threadIdx.x];
     for (int i = 1; i < CT_WG_GROUPS; ++i) s += part[i][threadIdx.x];
-    if (threadIdx.x < CT_HID) dw2[threadIdx.x] = s;
+    if (threadIdx.x < CLF_HID) dw2[threadIdx.x] = s;
     else db2[0] = s;
   }
 }
@@ -254,17 +216,17 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
                                                            const float* __restrict__ q, int nq_seg, const float* __restrict__ kv,
                                                            int nc_seg, int N, const int* __restrict__ qi, const int* __restrict__ ci,
                                                            int P, float* __restrict__ dq, float* __restrict__ dk) {
-  static_assert(C == CT_H * DH && DH % 32 == 0, "4 heads of DH channels");
+  static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels");
   constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C, HALF = DH / 2;
-  __shared__ float dsT[4][CT_N][CT_N + 1];
-  __shared__ float das[4][CT_N];
+  __shared__ float dsT[4][CLF_TILE][CLF_TILE + 1];
+  __shared__ float das[4][CLF_TILE];
   const int lane = lane_id(), w = threadIdx.x >> 6;
   const int r = lane & 31, hh = lane >> 5;
   const int p = blockIdx.x * 4 + w;
   if (p >= P) return;
   const int qs = qi[p], cs = ci[p];
   if (qs < 0 || qs >= nq_seg || cs < 0 || cs >= nc_seg) return;
-  const float scale = ct_scale<DH>::v;
+  const float scale = clf_scale<DH>::v;
   const float invN = 1.0f / (float)N;
   const bool rin = r < N;
   const float* qrow = q + (size_t)qs * N * CT_C;              // Q of the query segment (N x C)
@@ -274,7 +236,7 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
   float* dkp = dk + (size_t)p * N * CT_C;
 
 #pragma unroll 1
-  for (int h = 0; h < CT_H; ++h) {
+  for (int h = 0; h < CLF_H; ++h) {
     // da[key r] = V[r][h] . do[h]: half hh of the DH dims on each lane half, halves added in one order on both
     float part = 0.f;
     if (rin) {
@@ -293,7 +255,7 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
     const float da = hh == 0 ? part + other : other + part;
     if (hh == 0) das[w][r] = rin ? da * invN : 0.f;
     __builtin_amdgcn_wave_barrier();
-    const float* ap = attn + ((size_t)p * CT_H + h) * 16 * 64 + lane;
+    const float* ap = attn + ((size_t)p * CLF_H + h) * 16 * 64 + lane;
     float a[16], g[16];
     float t = 0.f;
 #pragma unroll
@@ -358,7 +320,7 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
                                                                         const int* __restrict__ qi, const int* __restrict__ ci, int P,
                                                                         int N, int nq_seg, float* __restrict__ dq_seg,
                                                                         float* __restrict__ dkv_seg) {
-  static_assert(C == CT_H * DH && DH % 4 == 0 && (CT_N * C) % (4 * CT_RED_THREADS) == 0, "4 heads of DH channels");
+  static_assert(C == CLF_H * DH && DH % 4 == 0 && (CLF_TILE * C) % (4 * CT_RED_THREADS) == 0, "4 heads of DH channels");
   constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;
   __shared__ uint64_t masks[CT_RED_THREADS / 64];
   const int tid = threadIdx.x, w = tid >> 6;
@@ -366,7 +328,7 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
   const int seg = isq ? (int)blockIdx.x : (int)blockIdx.x - nq_seg;
   const int* idx = isq ? qi : ci;
   const int nel = N * CT_C;                                  // elements of one segment's gradient (a multiple of 128)
-  constexpr int U = CT_N * CT_C / (4 * CT_RED_THREADS);      // float4 per thread
+  constexpr int U = CLF_TILE * CT_C / (4 * CT_RED_THREADS);      // float4 per thread
   f32x4 acc[U], accv[U];
 #pragma unroll
   for (int u = 0; u < U; ++u) acc[u] = accv[u] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -396,7 +358,7 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
             const int e = 4 * (tid + CT_RED_THREADS * u);
             if (e < nel) {
               const int n = e / CT_C, c = e % CT_C;
-              const float a = abar[((size_t)p * CT_H + c / CT_DH) * CT_N + n];
+              const float a = abar[((size_t)p * CLF_H + c / CT_DH) * CLF_TILE + n];
               const f32x4 d = ld4(dobar + (size_t)p * CT_C + c);
 #pragma unroll
               for (int x = 0; x < 4; ++x) accv[u][x] = fmaf(a, d[x], accv[u][x]);
@@ -434,25 +396,15 @@ extern "C" int nsid_clf_mine_hard_negatives(const float* zq, int nq, const float
   return nsid_launch_status();
 }
 
-// one launch of KERNEL<C, C / 4> for the supported widths
-#define CT_LAUNCH_C(KERNEL, grid, block, st, ...)                                        \
-  switch (C) {                                                                           \
-    case 512: NSID_LAUNCH((KERNEL<512, 128>), grid, block, 0, st, __VA_ARGS__); break;   \
-    case 640: NSID_LAUNCH((KERNEL<640, 160>), grid, block, 0, st, __VA_ARGS__); break;   \
-    case 768: NSID_LAUNCH((KERNEL<768, 192>), grid, block, 0, st, __VA_ARGS__); break;   \
-    default: NSID_LAUNCH((KERNEL<1024, 256>), grid, block, 0, st, __VA_ARGS__); break;   \
-  }
-static inline bool ct_width_ok(int C) { return C == 512 || C == 640 || C == 768 || C == 1024; }
-
 extern "C" int nsid_clf_attn_fwd_c(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
                                    int P, float* obar, float* attn, float* abar, void* stream) {
-  NSID_REQUIRE(ct_width_ok(C));
-  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CT_N && P >= 0 && P <= (1 << 28));
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CLF_TILE && P >= 0 && P <= (1 << 28));
   if (P == 0) return NSID_OK;
   NSID_REQUIRE(q && kv && qi && ci && obar && attn && abar && nsid_aligned16(q) && nsid_aligned16(kv));
   nsid_count(NSID_C_clf_attn_fwd);
-  CT_LAUNCH_C(clf_attn_fwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), q, nq_seg, kv, nc_seg, N, qi, ci,
-              P, obar, attn, abar);
+  CLF_LAUNCH_C(C, clf_attn_fwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), q, nq_seg, kv, nc_seg, N, qi,
+               ci, P, obar, attn, abar);
   return nsid_launch_status();
 }
 
@@ -480,19 +432,19 @@ extern "C" int nsid_clf_head_bwd(const float* ds, const float* s, const float* h
     NSID_LAUNCH(clf_head_bwd_kernel, dim3((P + 3) / 4), dim3(256), 0, st, ds, s, hid, keep, w2, P, dh, dz);
     if (nsid_launch_status() != NSID_OK) return NSID_ELAUNCH;
   }
-  NSID_LAUNCH(clf_head_wgrad_kernel, dim3(1), dim3(CT_WG_GROUPS * CT_HID), 0, st, dz, hid, keep, P, dw2, db2);
+  NSID_LAUNCH(clf_head_wgrad_kernel, dim3(1), dim3(CT_WG_GROUPS * CLF_HID), 0, st, dz, hid, keep, P, dw2, db2);
   return nsid_launch_status();
 }
 
 extern "C" int nsid_clf_attn_bwd_c(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
                                    int C, int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
-  NSID_REQUIRE(ct_width_ok(C));
-  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CT_N && P >= 0 && P <= (1 << 28));
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CLF_TILE && P >= 0 && P <= (1 << 28));
   if (P == 0) return NSID_OK;
   NSID_REQUIRE(dobar && attn && q && kv && qi && ci && dq && dk && nsid_aligned16(dobar) && nsid_aligned16(kv));
   nsid_count(NSID_C_clf_attn_bwd);
-  CT_LAUNCH_C(clf_attn_bwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), dobar, attn, q, nq_seg, kv, nc_seg,
-              N, qi, ci, P, dq, dk);
+  CLF_LAUNCH_C(C, clf_attn_bwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), dobar, attn, q, nq_seg, kv,
+               nc_seg, N, qi, ci, P, dq, dk);
   return nsid_launch_status();
 }
 
@@ -504,14 +456,14 @@ extern "C" int nsid_clf_attn_bwd(const float* dobar, const float* attn, const fl
 extern "C" int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
                                      const int* ci, int P, int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg,
                                      void* stream) {
-  NSID_REQUIRE(ct_width_ok(C));
-  NSID_REQUIRE(P >= 0 && P <= (1 << 28) && N >= 1 && N <= CT_N && nq_seg >= 0 && nc_seg >= 0 && nq_seg + nc_seg <= (1 << 30));
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(P >= 0 && P <= (1 << 28) && N >= 1 && N <= CLF_TILE && nq_seg >= 0 && nc_seg >= 0 && nq_seg + nc_seg <= (1 << 30));
   if (nq_seg + nc_seg == 0) return NSID_OK;
   NSID_REQUIRE((P == 0 || (dq && dk && abar && dobar && qi && ci)) && dq_seg && dkv_seg);
   NSID_REQUIRE(nsid_aligned16(dq) && nsid_aligned16(dk) && nsid_aligned16(dobar) && nsid_aligned16(dq_seg) && nsid_aligned16(dkv_seg));
   nsid_count(NSID_C_clf_seg_reduce);
-  CT_LAUNCH_C(clf_seg_reduce_kernel, dim3(nq_seg + nc_seg), dim3(CT_RED_THREADS), static_cast<hipStream_t>(stream), dq, dk, abar,
-              dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg);
+  CLF_LAUNCH_C(C, clf_seg_reduce_kernel, dim3(nq_seg + nc_seg), dim3(CT_RED_THREADS), static_cast<hipStream_t>(stream), dq, dk, abar,
+               dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg);
   return nsid_launch_status();
 }
 

@@ -21,60 +21,45 @@
 //
 // Nodes: clf_pair_kernel covers N <= 32 (one 32 x 32 tile per head). 33 <= N <= 128 (evaluation only) is clf_pair_wide_kernel below:
 // up to 4 x 4 tiles per head, P staged one head at a time; it has its own entries and leaves the N <= 32 kernels and scores alone.
-#include "nsid_common.h"
+//
+// The tile arithmetic (register map, masked softmax, column sums), the pair-list decode and the folded tail are clf_common.h's,
+// shared with the training kernels; what differs between the kernels here is how K, P and Q are staged.
+#include "clf_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int RR_H = 4;              // heads; node channels C = 4 DH are template parameters
-constexpr int RR_N = 32;             // nodes per segment at most (one 32x32 MFMA tile)
-constexpr int RR_HID = 128;          // fc.0 width
 constexpr int RR_WAVES = 8;
 constexpr int RR_QCH = 64;           // query segments per workgroup
-constexpr int RR_PW = RR_H * RR_HID;  // P row: one fc.0-wide block per head
 constexpr int RR_LDS_MAX = 160 * 1024;
 // K next to P in LDS (rows of C + 4 floats: +16 B so that the 32 rows of a fragment read start in different banks), else P alone
-constexpr bool rr_k_in_lds(int C) { return (RR_N * (C + 4) + RR_N * RR_PW + RR_WAVES * RR_N) * 4 <= RR_LDS_MAX; }
+constexpr bool rr_k_in_lds(int C) { return (CLF_TILE * (C + 4) + CLF_TILE * CLF_PW + RR_WAVES * CLF_TILE) * 4 <= RR_LDS_MAX; }
 
-// group g: {first query segment, query segments, offset into cidx, candidates}; its scores are the row-major (q count x c count)
-// block at out + out_off[g]. tile_off: prefix sums of the groups' workgroups (c count x query chunks), ngroups + 1 entries.
+// grp, out_off, tile_off and cidx: the pair lists, see clf_tile_decode
 template <int C, int DH>
 __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kp,
                                                        int nc_seg, int N, const int* __restrict__ grp,
                                                        const int64_t* __restrict__ out_off, const int* __restrict__ tile_off,
                                                        int ngroups, const int* __restrict__ cidx, const float* __restrict__ tail,
                                                        float* __restrict__ out, int64_t out_len) {
-  static_assert(C == RR_H * DH && DH % 8 == 0, "4 heads of DH channels");
+  static_assert(C == CLF_H * DH && DH % 8 == 0, "4 heads of DH channels");
   constexpr bool KLDS = rr_k_in_lds(C);
   static_assert(KLDS || DH % 64 == 0, "the streamed form loads K and Q eight k-steps at a time");
   constexpr int KLD = C + 4;           // LDS row of K
-  constexpr int LDKP = C + RR_PW;      // the candidates' projected rows: [K | P]
-  __shared__ __attribute__((aligned(16))) float ks[KLDS ? RR_N : 1][KLDS ? KLD : 4];
-  __shared__ __attribute__((aligned(16))) float ps[RR_N][RR_PW];
-  __shared__ float abar[RR_WAVES][RR_N];
+  constexpr int LDKP = C + CLF_PW;      // the candidates' projected rows: [K | P]
+  __shared__ __attribute__((aligned(16))) float ks[KLDS ? CLF_TILE : 1][KLDS ? KLD : 4];
+  __shared__ __attribute__((aligned(16))) float ps[CLF_TILE][CLF_PW];
+  __shared__ float abar[RR_WAVES][CLF_TILE];
 
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
 
-  // the group of this workgroup: the last g with tile_off[g] <= blockIdx.x
-  int lo = 0, hi = ngroups - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tile_off[mid] <= b) lo = mid; else hi = mid - 1;
-  }
-  const int g = lo;
-  const int q0 = grp[4 * g], qn = grp[4 * g + 1], coff = grp[4 * g + 2], cn = grp[4 * g + 3];
-  const int t = b - tile_off[g];
-  const int jpos = t % cn, qc = t / cn;
-  const int cand = cidx[coff + jpos];
-  if (cand < 0 || cand >= nc_seg) return;              // the host checks the lists; this only keeps a bad list in bounds
+  const clf_tile t = clf_tile_decode(grp, tile_off, ngroups, cidx);
+  if (t.cand < 0 || t.cand >= nc_seg) return;          // the host checks the lists; this only keeps a bad list in bounds
 
   // stage K and P of the candidate (rows >= N are zero)
-  const float* kc = kp + (size_t)cand * N * LDKP;
-  if constexpr (KLDS && C == RR_PW) {
-    for (int i = tid; i < RR_N * (C / 4); i += 512) {
+  const float* kc = kp + (size_t)t.cand * N * LDKP;
+  if constexpr (KLDS && C == CLF_PW) {
+    for (int i = tid; i < CLF_TILE * (C / 4); i += 512) {
       const int n = i / (C / 4), c = 4 * (i % (C / 4));
       f32x4 kv = {0.f, 0.f, 0.f, 0.f}, pv = {0.f, 0.f, 0.f, 0.f};
       if (n < N) {
@@ -86,28 +71,26 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
     }
   } else {
     if constexpr (KLDS) {
-      for (int i = tid; i < RR_N * (C / 4); i += 512) {
+      for (int i = tid; i < CLF_TILE * (C / 4); i += 512) {
         const int n = i / (C / 4), c = 4 * (i % (C / 4));
         *reinterpret_cast<f32x4*>(&ks[n][c]) = n < N ? ld4(kc + (size_t)n * LDKP + c) : f32x4{0.f, 0.f, 0.f, 0.f};
       }
     }
-    for (int i = tid; i < RR_N * (RR_PW / 4); i += 512) {
-      const int n = i / (RR_PW / 4), c = 4 * (i % (RR_PW / 4));
+    for (int i = tid; i < CLF_TILE * (CLF_PW / 4); i += 512) {
+      const int n = i / (CLF_PW / 4), c = 4 * (i % (CLF_PW / 4));
       *reinterpret_cast<f32x4*>(&ps[n][c]) = n < N ? ld4(kc + (size_t)n * LDKP + C + c) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
   __syncthreads();
 
   const float invN = 1.0f / (float)N;
-  const int s_end = min(qn, (qc + 1) * RR_QCH);
-  // the register this lane holds after the column reduce-scatter below, and its key
-  const int gf = (((r >> 4) & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 1) & 1);
-  const int jf = (gf & 3) + 8 * (gf >> 2) + 4 * hh;
+  const int s_end = min(t.qn, (t.qc + 1) * RR_QCH);
+  const int jf = clf_lane_key(r, hh);
 
-  for (int s = qc * RR_QCH + w; s < s_end; s += RR_WAVES) {
-    const int qseg = q0 + s;
+  for (int s = t.qc * RR_QCH + w; s < s_end; s += RR_WAVES) {
+    const int qseg = t.q0 + s;
     if (qseg < 0 || qseg >= nq_seg) continue;
-    const int64_t o = out_off[g] + (int64_t)s * cn + jpos;
+    const int64_t o = out_off[t.g] + (int64_t)s * t.cn + t.jpos;
     if (o < 0 || o >= out_len) continue;
     const float* qp = q + ((size_t)qseg * N + (r < N ? r : 0)) * C + 4 * hh;
     float part0 = 0.f, part1 = 0.f;             // hidden[lane], hidden[64 + lane] without g
@@ -120,7 +103,7 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
     }
 
 #pragma unroll
-    for (int h = 0; h < RR_H; ++h) {
+    for (int h = 0; h < CLF_H; ++h) {
       // S^T[key][query]: A = K rows (LDS), B = Q rows; lane (r, hh) supplies dims 8 bb + 4 hh + e of row r at step (bb, e)
       f32x16 acc = {};
       if constexpr (KLDS) {
@@ -128,7 +111,7 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
         for (int bb = 0; bb < DH / 8; ++bb) {
           const f32x4 ka = *reinterpret_cast<const f32x4*>(&ks[r][h * DH + 8 * bb + 4 * hh]);
           const f32x4 qb = qf[bb];
-          if (h + 1 < RR_H) qf[bb] = r < N ? ld4(qp + (h + 1) * DH + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
+          if (h + 1 < CLF_H) qf[bb] = r < N ? ld4(qp + (h + 1) * DH + 8 * bb) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[e], qb[e], acc, 0, 0, 0);
         }
@@ -149,49 +132,21 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
             for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[bb][e], qb[bb][e], acc, 0, 0, 0);
         }
       }
-      // acc[i] of lane (r, hh) = score of query node r against key (i & 3) + 8 (i >> 2) + 4 hh: softmax over the keys of query r
-      float mx = -__builtin_inff();
-#pragma unroll
-      for (int i = 0; i < 16; ++i)
-        if ((i & 3) + 8 * (i >> 2) + 4 * hh < N) mx = fmaxf(mx, acc[i]);
-      mx = fmaxf(mx, __shfl_xor(mx, 32));
+      // softmax over the keys of query r, then the mean over the queries
       float v[16];
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        v[i] = (i & 3) + 8 * (i >> 2) + 4 * hh < N ? expf(acc[i] - mx) : 0.f;
-        sum += v[i];
-      }
-      sum += __shfl_xor(sum, 32);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) v[i] = r < N ? v[i] / sum : 0.f;
-      // column sums over the 32 query lanes of each half: reduce-scatter, halving the registers at every step
-#pragma unroll
-      for (int c = 16, off = 16; c > 1; c >>= 1, off >>= 1) {
-        const bool up = (r & off) != 0;
-#pragma unroll
-        for (int i = 0; i < c / 2; ++i) {
-          const float keep = up ? v[i + c / 2] : v[i];
-          const float send = up ? v[i] : v[i + c / 2];
-          v[i] = keep + __shfl_xor(send, off);
-        }
-      }
-      v[0] += __shfl_xor(v[0], 1);
-      if ((r & 1) == 0) abar[w][jf] = v[0] * invN;
+      clf_tile_softmax<false>(acc, v, hh, N, r < N, 1.0f);
+      const float cs = clf_colsum(v, r);
+      if ((r & 1) == 0) abar[w][jf] = cs * invN;
       __builtin_amdgcn_wave_barrier();
       // hidden += a_h^T P_h
       for (int m = 0; m < N; ++m) {
         const float a = abar[w][m];
-        part0 = fmaf(a, ps[m][h * RR_HID + lane], part0);
-        part1 = fmaf(a, ps[m][h * RR_HID + 64 + lane], part1);
+        part0 = fmaf(a, ps[m][h * CLF_HID + lane], part0);
+        part1 = fmaf(a, ps[m][h * CLF_HID + 64 + lane], part1);
       }
       __builtin_amdgcn_wave_barrier();
     }
-    const float h0 = fmaxf(part0 + tail[lane], 0.f), h1 = fmaxf(part1 + tail[64 + lane], 0.f);
-    float z = fmaf(tail[RR_HID + 64 + lane], h1, tail[RR_HID + lane] * h0);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off);
-    if (lane == 0) out[o] = 1.0f / (1.0f + expf(-(z + tail[2 * RR_HID])));
+    clf_tail_store(part0, part1, tail, lane, out + o);
   }
 }
 
@@ -207,22 +162,6 @@ constexpr int RW_N = 128;            // nodes per segment at most
 constexpr int RW_T = RW_N / 32;      // tiles per side
 constexpr int RW_SLOTS = RR_QCH / RR_WAVES;   // segments of a chunk per wave
 
-// column sums of a 32 (keys, registers x lane half) x 32 (queries, lanes) tile: reduce-scatter over the 32 query lanes of each half,
-// halving the registers at every step; the even lanes return the sum of key jf (clf_pair_kernel's comment) of their half
-__device__ __forceinline__ float rw_colsum(float* v, int r) {
-#pragma unroll
-  for (int c = 16, off = 16; c > 1; c >>= 1, off >>= 1) {
-    const bool up = (r & off) != 0;
-#pragma unroll
-    for (int i = 0; i < c / 2; ++i) {
-      const float keep = up ? v[i + c / 2] : v[i];
-      const float send = up ? v[i] : v[i + c / 2];
-      v[i] = keep + __shfl_xor(send, off);
-    }
-  }
-  return v[0] + __shfl_xor(v[0], 1);
-}
-
 template <int C, int DH>
 __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kp,
                                                             int nc_seg, int N, const int* __restrict__ grp,
@@ -230,52 +169,40 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
                                                             int ngroups, const int* __restrict__ cidx,
                                                             const float* __restrict__ tail, float* __restrict__ out,
                                                             int64_t out_len) {
-  static_assert(C == RR_H * DH && DH % 32 == 0, "4 heads of DH channels; K and Q are loaded four k-steps of 8 at a time");
-  constexpr int LDKP = C + RR_PW;      // the candidates' projected rows: [K | P]
-  __shared__ __attribute__((aligned(16))) float ps[RW_N][RR_HID];          // P_h of the candidate
-  __shared__ float hacc[RR_QCH][RR_HID];                                   // the pairs' hidden vectors between two heads
+  static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels; K and Q are loaded four k-steps of 8 at a time");
+  constexpr int LDKP = C + CLF_PW;      // the candidates' projected rows: [K | P]
+  __shared__ __attribute__((aligned(16))) float ps[RW_N][CLF_HID];          // P_h of the candidate
+  __shared__ float hacc[RR_QCH][CLF_HID];                                   // the pairs' hidden vectors between two heads
   __shared__ float abar[RR_WAVES][RW_N];
 
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
 
-  // the group of this workgroup: the last g with tile_off[g] <= blockIdx.x
-  int lo = 0, hi = ngroups - 1;
-  const int b = blockIdx.x;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (tile_off[mid] <= b) lo = mid; else hi = mid - 1;
-  }
-  const int g = lo;
-  const int q0 = grp[4 * g], qn = grp[4 * g + 1], coff = grp[4 * g + 2], cn = grp[4 * g + 3];
-  const int t = b - tile_off[g];
-  const int jpos = t % cn, qc = t / cn;
-  const int cand = cidx[coff + jpos];
-  if (cand < 0 || cand >= nc_seg) return;              // the host checks the lists; this only keeps a bad list in bounds (uniform)
+  const clf_tile t = clf_tile_decode(grp, tile_off, ngroups, cidx);
+  if (t.cand < 0 || t.cand >= nc_seg) return;          // the host checks the lists; this only keeps a bad list in bounds (uniform)
 
-  const float* kc = kp + (size_t)cand * N * LDKP;
+  const float* kc = kp + (size_t)t.cand * N * LDKP;
   const int nT = (N + 31) >> 5;
   const float invN = 1.0f / (float)N;
-  const int s_end = min(qn, (qc + 1) * RR_QCH);
-  const int gf = (((r >> 4) & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 1) & 1);
-  const int jf = (gf & 3) + 8 * (gf >> 2) + 4 * hh;
+  const int s_end = min(t.qn, (t.qc + 1) * RR_QCH);
+  const int jf = clf_lane_key(r, hh);
 
 #pragma unroll 1
-  for (int h = 0; h < RR_H; ++h) {
+  for (int h = 0; h < CLF_H; ++h) {
     __syncthreads();                                   // every wave is done with the last head's P_h
-    for (int i = tid; i < N * (RR_HID / 4); i += 512) {
-      const int n = i / (RR_HID / 4), c = 4 * (i % (RR_HID / 4));
-      *reinterpret_cast<f32x4*>(&ps[n][c]) = ld4(kc + (size_t)n * LDKP + C + h * RR_HID + c);
+    for (int i = tid; i < N * (CLF_HID / 4); i += 512) {
+      const int n = i / (CLF_HID / 4), c = 4 * (i % (CLF_HID / 4));
+      *reinterpret_cast<f32x4*>(&ps[n][c]) = ld4(kc + (size_t)n * LDKP + C + h * CLF_HID + c);
     }
     __syncthreads();
 
 #pragma unroll 1
     for (int slot = 0; slot < RW_SLOTS; ++slot) {
-      const int s = qc * RR_QCH + w + slot * RR_WAVES;
+      const int s = t.qc * RR_QCH + w + slot * RR_WAVES;
       if (s >= s_end) break;
-      const int qseg = q0 + s;
+      const int qseg = t.q0 + s;
       if (qseg < 0 || qseg >= nq_seg) continue;
-      const int64_t o = out_off[g] + (int64_t)s * cn + jpos;
+      const int64_t o = out_off[t.g] + (int64_t)s * t.cn + t.jpos;
       if (o < 0 || o >= out_len) continue;
       const float* qs = q + (size_t)qseg * N * C + h * DH + 4 * hh;
       const float* kh = kc + h * DH + 4 * hh;
@@ -314,37 +241,23 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
             }
           }
         }
-        // acc[kt][i] of lane (r, hh) = score of query node qrow against key 32 kt + (i & 3) + 8 (i >> 2) + 4 hh: the softmax of
-        // query qrow runs over the registers of all key tiles and the two lane halves
+        // the softmax of query qrow runs over the registers of all key tiles (tile kt: keys from 32 kt) and the two lane halves
         float mx = -__builtin_inff();
 #pragma unroll
-        for (int kt = 0; kt < RW_T; ++kt) {
-          if (kt < nT) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i)
-              if (32 * kt + (i & 3) + 8 * (i >> 2) + 4 * hh < N) mx = fmaxf(mx, acc[kt][i]);
-          }
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        for (int kt = 0; kt < RW_T; ++kt)
+          if (kt < nT) mx = clf_tile_max<false>(acc[kt], 32 * kt, hh, N, 1.0f, mx);
+        mx = clf_half_max(mx);
         float sum = 0.f;
 #pragma unroll
-        for (int kt = 0; kt < RW_T; ++kt) {
-          if (kt < nT) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-              acc[kt][i] = 32 * kt + (i & 3) + 8 * (i >> 2) + 4 * hh < N ? expf(acc[kt][i] - mx) : 0.f;
-              sum += acc[kt][i];
-            }
-          }
-        }
-        sum += __shfl_xor(sum, 32);
+        for (int kt = 0; kt < RW_T; ++kt)
+          if (kt < nT) sum = clf_tile_exp<false>(acc[kt], acc[kt], 32 * kt, hh, N, 1.0f, mx, sum);
+        sum = clf_half_sum(sum);
 #pragma unroll
         for (int kt = 0; kt < RW_T; ++kt) {
           if (kt < nT) {
             float v[16];
-#pragma unroll
-            for (int i = 0; i < 16; ++i) v[i] = qok ? acc[kt][i] / sum : 0.f;
-            cs[kt] += rw_colsum(v, r);
+            clf_tile_norm(acc[kt], v, qok, sum);
+            cs[kt] += clf_colsum(v, r);
           }
         }
       }
@@ -363,16 +276,12 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
         part1 = fmaf(a, ps[m][64 + lane], part1);
       }
       __builtin_amdgcn_wave_barrier();
-      if (h + 1 < RR_H) {
+      if (h + 1 < CLF_H) {
         hacc[pair][lane] = part0;
         hacc[pair][64 + lane] = part1;
         continue;
       }
-      const float h0 = fmaxf(part0 + tail[lane], 0.f), h1 = fmaxf(part1 + tail[64 + lane], 0.f);
-      float z = fmaf(tail[RR_HID + 64 + lane], h1, tail[RR_HID + lane] * h0);
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) z += __shfl_xor(z, off);
-      if (lane == 0) out[o] = 1.0f / (1.0f + expf(-(z + tail[2 * RR_HID])));
+      clf_tail_store(part0, part1, tail, lane, out + o);
     }
   }
 }
@@ -394,69 +303,61 @@ __global__ __launch_bounds__(256) void clf_node_rows_kernel(const float* __restr
   }
 }
 
+// the entries have checked C and N <= NMAX
+template <int NMAX>
+int launch_node_rows(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream, NsidCounterKey key) {
+  if (S == 0) return NSID_OK;
+  NSID_REQUIRE(x && rows);
+  nsid_count(key);
+  NSID_LAUNCH(clf_node_rows_kernel<NMAX>, dim3(S, C / 32), dim3(256), 0, static_cast<hipStream_t>(stream), x, C, N, pos, rows);
+  return nsid_launch_status();
+}
+
+// wide: clf_pair_wide_kernel (N <= 128), else clf_pair_kernel (N <= 32)
+int launch_pair_scores(bool wide, const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
+                       const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail,
+                       float* out, int64_t out_len, void* stream) {
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= (wide ? RW_N : CLF_TILE) && ngroups >= 0 && ntiles >= 0 && out_len >= 0);
+  if (ngroups == 0 || ntiles == 0) return NSID_OK;
+  NSID_REQUIRE(q && kp && groups && out_off && tile_off && cidx && tail && out && nsid_aligned16(q) && nsid_aligned16(kp));
+  nsid_count(wide ? NSID_C_clf_pair_scores_n : NSID_C_clf_pair_scores);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (wide) {
+    CLF_LAUNCH_C(C, clf_pair_wide_kernel, dim3(ntiles), dim3(512), st, q, nq_seg, kp, nc_seg, N, groups, out_off, tile_off, ngroups,
+                 cidx, tail, out, out_len);
+  } else {
+    CLF_LAUNCH_C(C, clf_pair_kernel, dim3(ntiles), dim3(512), st, q, nq_seg, kp, nc_seg, N, groups, out_off, tile_off, ngroups, cidx,
+                 tail, out, out_len);
+  }
+  return nsid_launch_status();
+}
+
 }  // namespace
 
 extern "C" int nsid_clf_node_rows(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream) {
-  NSID_REQUIRE(S >= 0 && C > 0 && C % 32 == 0 && C <= 32 * 65535 && N >= 1 && N <= RR_N);
-  if (S == 0) return NSID_OK;
-  NSID_REQUIRE(x && rows);
-  nsid_count(NSID_C_clf_node_rows);
-  hipLaunchKernelGGL(clf_node_rows_kernel<RR_N>, dim3(S, C / 32), dim3(256), 0, static_cast<hipStream_t>(stream), x, C, N, pos, rows);
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  NSID_REQUIRE(S >= 0 && C > 0 && C % 32 == 0 && C <= 32 * 65535 && N >= 1 && N <= CLF_TILE);
+  return launch_node_rows<CLF_TILE>(x, S, C, N, pos, rows, stream, NSID_C_clf_node_rows);
 }
 
 extern "C" int nsid_clf_node_rows_n(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream) {
-  NSID_REQUIRE(C == 512 || C == 640 || C == 768 || C == 1024);
+  NSID_REQUIRE(clf_width_ok(C));
   NSID_REQUIRE(S >= 0 && N >= 1 && N <= RW_N);
-  if (S == 0) return NSID_OK;
-  NSID_REQUIRE(x && rows);
-  nsid_count(NSID_C_clf_node_rows_n);
-  hipLaunchKernelGGL(clf_node_rows_kernel<RW_N>, dim3(S, C / 32), dim3(256), 0, static_cast<hipStream_t>(stream), x, C, N, pos, rows);
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  return launch_node_rows<RW_N>(x, S, C, N, pos, rows, stream, NSID_C_clf_node_rows_n);
 }
 
 extern "C" int nsid_clf_pair_scores_n(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
                                       const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
                                       const float* tail, float* out, int64_t out_len, void* stream) {
-  NSID_REQUIRE(C == 512 || C == 640 || C == 768 || C == 1024);
-  NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= RW_N && ngroups >= 0 && ntiles >= 0 && out_len >= 0);
-  if (ngroups == 0 || ntiles == 0) return NSID_OK;
-  NSID_REQUIRE(q && kp && groups && out_off && tile_off && cidx && tail && out && nsid_aligned16(q) && nsid_aligned16(kp));
-  nsid_count(NSID_C_clf_pair_scores_n);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-#define RW_LAUNCH(CC)                                                                                                            \
-  hipLaunchKernelGGL((clf_pair_wide_kernel<CC, CC / RR_H>), dim3(ntiles), dim3(512), 0, st, q, nq_seg, kp, nc_seg, N, groups,    \
-                     out_off, tile_off, ngroups, cidx, tail, out, out_len)
-  switch (C) {
-    case 512: RW_LAUNCH(512); break;
-    case 640: RW_LAUNCH(640); break;
-    case 768: RW_LAUNCH(768); break;
-    default: RW_LAUNCH(1024); break;
-  }
-#undef RW_LAUNCH
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  return launch_pair_scores(true, q, nq_seg, kp, nc_seg, C, N, groups, out_off, tile_off, ngroups, ntiles, cidx, tail, out, out_len,
+                            stream);
 }
 
 extern "C" int nsid_clf_pair_scores_c(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,
                                       const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
                                       const float* tail, float* out, int64_t out_len, void* stream) {
-  NSID_REQUIRE(C == 512 || C == 640 || C == 768 || C == 1024);
-  NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= RR_N && ngroups >= 0 && ntiles >= 0 && out_len >= 0);
-  if (ngroups == 0 || ntiles == 0) return NSID_OK;
-  NSID_REQUIRE(q && kp && groups && out_off && tile_off && cidx && tail && out && nsid_aligned16(q) && nsid_aligned16(kp));
-  nsid_count(NSID_C_clf_pair_scores);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-#define RR_LAUNCH(CC)                                                                                                             \
-  hipLaunchKernelGGL((clf_pair_kernel<CC, CC / RR_H>), dim3(ntiles), dim3(512), 0, st, q, nq_seg, kp, nc_seg, N, groups, out_off, \
-                     tile_off, ngroups, cidx, tail, out, out_len)
-  switch (C) {
-    case 512: RR_LAUNCH(512); break;
-    case 640: RR_LAUNCH(640); break;
-    case 768: RR_LAUNCH(768); break;
-    default: RR_LAUNCH(1024); break;
-  }
-#undef RR_LAUNCH
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  return launch_pair_scores(false, q, nq_seg, kp, nc_seg, C, N, groups, out_off, tile_off, ngroups, ntiles, cidx, tail, out, out_len,
+                            stream);
 }
 
 extern "C" int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups,
@@ -465,3 +366,4 @@ extern "C" int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp,
   return nsid_clf_pair_scores_c(q, nq_seg, kp, nc_seg, 512, N, groups, out_off, tile_off, ngroups, ntiles, cidx, tail, out, out_len,
                                 stream);
 }
+

@@ -438,9 +438,8 @@ int launch_split(const float* q, int ldq, int nq, const float* x, int ldx, int n
                  float* wkey, int* wid, hipStream_t st) {
   constexpr int NB = D / 8;
   constexpr int CH = (D <= 128 && NB % 8 == 0) ? 8 : (NB % 4 == 0 ? 4 : 2);
-  hipLaunchKernelGGL((l2_topk_split_kernel<D, CH>), dim3(nqt * S), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk,
-                     wkey, wid);
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  NSID_LAUNCH((l2_topk_split_kernel<D, CH>), dim3(nqt * S), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey, wid);
+  return nsid_launch_status();
 }
 
 template <int... Ds>
@@ -482,9 +481,9 @@ int launch_wide(const float* q, int ldq, int nq, const float* x, int ldx, int nx
     configured = true;
   }
   const int nqb = (nq + L2Wide<WQ>::BQ - 1) / L2Wide<WQ>::BQ;
-  hipLaunchKernelGGL((l2_topk_wide_kernel<WQ>), dim3(nqb * S), dim3(256), L2Wide<WQ>::lds, st, q, ldq, nq, x, ldx, nx, xn, d, k, nqb, S,
-                     chunk, wkey, wid);
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  NSID_LAUNCH((l2_topk_wide_kernel<WQ>), dim3(nqb * S), dim3(256), L2Wide<WQ>::lds, st, q, ldq, nq, x, ldx, nx, xn, d, k, nqb, S, chunk,
+              wkey, wid);
+  return nsid_launch_status();
 }
 
 }  // namespace
@@ -515,8 +514,8 @@ extern "C" int nsid_row_sqnorm(const float* x, int ldx, int n, int d, float* out
   if (n == 0) return NSID_OK;
   NSID_REQUIRE(x && out && ldx >= d && ldx % 4 == 0 && nsid_aligned16(x));
   nsid_count(NSID_C_row_sqnorm);
-  hipLaunchKernelGGL(row_sqnorm_kernel, dim3((n + 15) / 16), dim3(256), 0, static_cast<hipStream_t>(stream), x, ldx, n, d, out);
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  NSID_LAUNCH(row_sqnorm_kernel, dim3((n + 15) / 16), dim3(256), 0, static_cast<hipStream_t>(stream), x, ldx, n, d, out);
+  return nsid_launch_status();
 }
 
 extern "C" int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
@@ -549,8 +548,8 @@ extern "C" int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x
         d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, st);
   }
   if (rc != NSID_OK) return rc;
-  hipLaunchKernelGGL(l2_topk_merge_kernel, dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  NSID_LAUNCH(l2_topk_merge_kernel, dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
+  return nsid_launch_status();
 }
 
 extern "C" int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, int d, const int64_t* I, int k,
@@ -559,7 +558,7 @@ extern "C" int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx,
   if (npairs == 0 || ldo == 0) return NSID_OK;
   NSID_REQUIRE(q && x && I && starts && lens && out && ldq >= d && ldx >= d);
   nsid_count(NSID_C_seq_scores);
-  hipLaunchKernelGGL(seq_scores_kernel, dim3(npairs, (ldo + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), q, ldq, x, ldx,
-                     nx, d, I, k, starts, lens, out, ldo);
-  return hipGetLastError() == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+  NSID_LAUNCH(seq_scores_kernel, dim3(npairs, (ldo + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), q, ldq, x, ldx, nx, d,
+              I, k, starts, lens, out, ldo);
+  return nsid_launch_status();
 }

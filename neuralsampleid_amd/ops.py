@@ -2080,6 +2080,70 @@ def clf_node_rows(x, pos=None) -> torch.Tensor:
     return rows
 
 
+def _clf_pair_plan(name, q, kp, N, tail, q_start, q_count, cand_off, cand_count, ncand):
+    """The checks and the layout that clf_pair_scores and clf_pair_scores_dev (name, for the messages) share: the tensors, N, the
+    width and the tail; the groups against the segments of q and a candidate list of ncand entries (cand_off None: the groups' lists
+    follow one another); the groups' offsets into the scores and into the launch's workgroups. Returns (out, out_off, plan): the
+    unwritten score tensor, the groups' int64 offsets into it and, unless there is nothing to launch, _clf_pair_launch's arguments
+    with the tables on the device."""
+    _chk(q, kp, tail)
+    N = int(N)
+    if not 1 <= N <= CLF_MAX_N_EVAL:
+        raise ValueError(f"{name}: N = {N} is outside [1, {CLF_MAX_N_EVAL}]")
+    if q.dim() != 2 or kp.dim() != 2:
+        raise ValueError(f"{name}: expected q (S N, C) and kp (S N, C + {CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
+    C = _clf_width(q.shape[1], name)
+    if q.shape[0] % N or kp.shape[1] != C + CLF_PW or kp.shape[0] % N:
+        raise ValueError(f"{name}: expected q (S N, {C}) and kp (S N, {C + CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
+    if tail.numel() != 257:
+        raise ValueError(f"{name}: tail must hold g (128), w2 (128) and b2")
+    nq_seg, nc_seg = q.shape[0] // N, kp.shape[0] // N
+    qs, qn, cn = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (q_start, q_count, cand_count))
+    co = np.cumsum(cn) - cn if cand_off is None else np.asarray(cand_off, dtype=np.int64).reshape(-1)
+    G = qs.size
+    if not qn.size == co.size == cn.size == G:
+        raise ValueError(f"{name}: q_start, q_count{' and' if cand_off is None else ', cand_off and'} cand_count differ in length")
+    if G and (qs.min() < 0 or qn.min() < 0 or (qs + qn).max() > nq_seg or co.min() < 0 or cn.min() < 0 or (co + cn).max() > ncand):
+        raise ValueError(f"{name}: a group's query range or candidate list is out of range")
+    sizes = qn * cn
+    out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    tiles = cn * ((qn + CLF_QCHUNK - 1) // CLF_QCHUNK)
+    tile_off = np.concatenate([[0], np.cumsum(tiles)]).astype(np.int64)
+    # grp and tile_off are int32 on the device
+    if tile_off[-1] >= 2 ** 31 or max(nq_seg, nc_seg) * N >= 2 ** 31 or (G and (co + cn).max() >= 2 ** 31):
+        raise ValueError(f"{name}: too many pairs for one call")
+    out = torch.empty((int(out_off[-1]),), device=q.device, dtype=torch.float32)
+    if G == 0 or tile_off[-1] == 0:
+        return out, out_off[:-1], None
+    dev = q.device
+    grp = torch.from_numpy(np.stack([qs, qn, co, cn], 1).astype(np.int32).reshape(-1)).to(dev)
+    oo = torch.from_numpy(out_off[:-1].copy()).to(dev)
+    to = torch.from_numpy(tile_off.astype(np.int32)).to(dev)
+    return out, out_off[:-1], (N, C, nq_seg, nc_seg, grp, oo, to, G, int(tile_off[-1]), float(sizes.sum()))
+
+
+def _clf_pair_launch(q, kp, tail, out, plan, cidx):
+    """one launch of a _clf_pair_plan over the int32 device candidate list cidx: nsid_clf_pair_scores_c for N <= 32, else _n"""
+    N, C, nq_seg, nc_seg, grp, oo, to, G, ntiles, npairs = plan
+    if N > CLF_MAX_N:
+        # 33 <= N <= 128, per pair: Q K^T 2 N^2 C on the matrix pipe, the softmax (about 8 per attention weight) and the column sums
+        # 4 N^2 each, a P 2 N 512, the tail 512. Bytes: the scores; per workgroup the candidate's P once; per pair the Q rows once per
+        # head and the K rows once per query tile (both stream from L2)
+        nt = (N + 31) // 32
+        kernel, entry = "clf_pair_wide_kernel", "nsid_clf_pair_scores_n"
+        flops = (2.0 * N * N * C + 12.0 * 4 * N * N + 2.0 * N * CLF_PW + 512.0) * npairs
+        nbytes = 4.0 * npairs + 4.0 * CLF_PW * N * float(ntiles) + 4.0 * N * C * (1 + nt) * npairs
+    else:
+        # per pair 2 N^2 C (Q K^T on the matrix pipe) + softmax, a P and the folded tail: 1.2 MFLOP at C = 512; bytes: the scores and
+        # K / P staged per workgroup
+        kernel, entry = "clf_pair_kernel", "nsid_clf_pair_scores_c"
+        flops = (1.2e6 + 2.0 * CLF_MAX_N * CLF_MAX_N * (C - CLF_C)) * npairs
+        nbytes = 4.0 * npairs + 4.0 * (C + CLF_PW) * N * float(ntiles)
+    _timed(kernel, flops, nbytes,
+           lambda: call(entry, _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G, ntiles, _p(cidx), _p(tail), _p(out),
+                        out.numel(), _stream()), (G, int(npairs), N, 1))
+
+
 def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_count):
     """Scores of blocked pair lists on the classifier's folded form (csrc/rerank.hip).
 
@@ -2089,62 +2153,14 @@ def clf_pair_scores(q, kp, N, tail, q_start, q_count, cand_idx, cand_off, cand_c
     Group i pairs query segments [q_start[i], q_start[i] + q_count[i]) with the candidate segments cand_idx[cand_off[i] :
     cand_off[i] + cand_count[i]] (repeats allowed). Host integer sequences, checked here. Returns (out, out_off): the flat fp32
     score tensor and, per group, the int64 offset of its row-major (q_count x cand_count) block."""
-    import numpy as np
-    _chk(q, kp, tail)
-    N = int(N)
-    if not 1 <= N <= CLF_MAX_N_EVAL:
-        raise ValueError(f"clf_pair_scores: N = {N} is outside [1, {CLF_MAX_N_EVAL}]")
-    if q.dim() != 2 or kp.dim() != 2:
-        raise ValueError(f"clf_pair_scores: expected q (S N, C) and kp (S N, C + {CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
-    C = _clf_width(q.shape[1], "clf_pair_scores")
-    if q.shape[0] % N or kp.shape[1] != C + CLF_PW or kp.shape[0] % N:
-        raise ValueError(f"clf_pair_scores: expected q (S N, {C}) and kp (S N, {C + CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
-    if tail.numel() != 257:
-        raise ValueError("clf_pair_scores: tail must hold g (128), w2 (128) and b2")
-    nq_seg, nc_seg = q.shape[0] // N, kp.shape[0] // N
-    qs, qn = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (q_start, q_count))
-    co, cn = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (cand_off, cand_count))
     ci = np.asarray(cand_idx, dtype=np.int64).reshape(-1)
-    G = qs.size
-    if not qn.size == co.size == cn.size == G:
-        raise ValueError("clf_pair_scores: q_start, q_count, cand_off and cand_count differ in length")
-    if G and (qs.min() < 0 or qn.min() < 0 or (qs + qn).max() > nq_seg or co.min() < 0 or cn.min() < 0
-              or (co + cn).max() > ci.size):
-        raise ValueError("clf_pair_scores: a group's query range or candidate list is out of range")
+    out, out_off, plan = _clf_pair_plan("clf_pair_scores", q, kp, N, tail, q_start, q_count, cand_off, cand_count, ci.size)
+    nc_seg = kp.shape[0] // int(N)
     if ci.size and (ci.min() < 0 or ci.max() >= nc_seg):
         raise ValueError(f"clf_pair_scores: candidate indices must lie in [0, {nc_seg})")
-    sizes = qn * cn
-    out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    tiles = cn * ((qn + CLF_QCHUNK - 1) // CLF_QCHUNK)
-    tile_off = np.concatenate([[0], np.cumsum(tiles)]).astype(np.int64)
-    if tile_off[-1] >= 2 ** 31 or max(nq_seg, nc_seg) * N >= 2 ** 31:
-        raise ValueError("clf_pair_scores: too many pairs for one call")
-    out = torch.empty((int(out_off[-1]),), device=q.device, dtype=torch.float32)
-    if G == 0 or tile_off[-1] == 0:
-        return out, out_off[:-1]
-    dev = q.device
-    grp = torch.from_numpy(np.stack([qs, qn, co, cn], 1).astype(np.int32).reshape(-1)).to(dev)
-    oo = torch.from_numpy(out_off[:-1].copy()).to(dev)
-    to = torch.from_numpy(tile_off.astype(np.int32)).to(dev)
-    cit = torch.from_numpy((ci if ci.size else np.zeros(1, np.int64)).astype(np.int32)).to(dev)
-    npairs = float(sizes.sum())
-    if N > CLF_MAX_N:
-        # 33 <= N <= 128, per pair: Q K^T 2 N^2 C on the matrix pipe, the softmax (about 8 per attention weight) and the column sums
-        # 4 N^2 each, a P 2 N 512, the tail 512. Bytes: the scores; per workgroup the candidate's P once; per pair the Q rows once per
-        # head and the K rows once per query tile (both stream from L2)
-        nt = (N + 31) // 32
-        _timed("clf_pair_wide_kernel", (2.0 * N * N * C + 12.0 * 4 * N * N + 2.0 * N * CLF_PW + 512.0) * npairs,
-               4.0 * npairs + 4.0 * CLF_PW * N * float(tile_off[-1]) + 4.0 * N * C * (1 + nt) * npairs,
-               lambda: call("nsid_clf_pair_scores_n", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G,
-                            int(tile_off[-1]), _p(cit), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
-        return out, out_off[:-1]
-    # per pair 2 N^2 C (Q K^T on the matrix pipe) + softmax, a P and the folded tail: 1.2 MFLOP at C = 512; bytes: the scores and
-    # K / P staged per workgroup
-    _timed("clf_pair_kernel", (1.2e6 + 2.0 * CLF_MAX_N * CLF_MAX_N * (C - CLF_C)) * npairs,
-           4.0 * npairs + 4.0 * (C + CLF_PW) * N * float(tile_off[-1]),
-           lambda: call("nsid_clf_pair_scores_c", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
-                        _p(cit), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
-    return out, out_off[:-1]
+    if plan is not None:
+        _clf_pair_launch(q, kp, tail, out, plan, torch.from_numpy(ci.astype(np.int32)).to(q.device))
+    return out, out_off
 
 
 def clf_pair_scores_dev(q, kp, N, tail, q_start, q_count, cand_count, cidx):
@@ -2153,52 +2169,12 @@ def clf_pair_scores_dev(q, kp, N, tail, q_start, q_count, cand_count, cidx):
     every size (q_start, q_count, cand_count: host integer sequences, checked here); the entries of cidx are not read by the host:
     the kernels skip, and leave unwritten, a pair whose candidate lies outside [0, nc_seg). Same kernels, same scores and the same
     result form as clf_pair_scores: (out, out_off)."""
-    _chk(q, kp, tail)
-    N = int(N)
-    if not 1 <= N <= CLF_MAX_N_EVAL:
-        raise ValueError(f"clf_pair_scores_dev: N = {N} is outside [1, {CLF_MAX_N_EVAL}]")
-    if q.dim() != 2 or kp.dim() != 2:
-        raise ValueError(f"clf_pair_scores_dev: expected q (S N, C) and kp (S N, C + {CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
-    C = _clf_width(q.shape[1], "clf_pair_scores_dev")
-    if q.shape[0] % N or kp.shape[1] != C + CLF_PW or kp.shape[0] % N:
-        raise ValueError(f"clf_pair_scores_dev: expected q (S N, {C}) and kp (S N, {C + CLF_PW}), got {tuple(q.shape)}, {tuple(kp.shape)}")
-    if tail.numel() != 257:
-        raise ValueError("clf_pair_scores_dev: tail must hold g (128), w2 (128) and b2")
     _clf_idx(cidx, "clf_pair_scores_dev cidx")
-    nq_seg, nc_seg = q.shape[0] // N, kp.shape[0] // N
-    qs, qn, cn = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (q_start, q_count, cand_count))
-    G = qs.size
-    if not qn.size == cn.size == G:
-        raise ValueError("clf_pair_scores_dev: q_start, q_count and cand_count differ in length")
-    if G and (qs.min() < 0 or qn.min() < 0 or (qs + qn).max() > nq_seg or cn.min() < 0 or cn.sum() > cidx.numel()):
-        raise ValueError("clf_pair_scores_dev: a group's query range or candidate list is out of range")
-    co = np.cumsum(cn) - cn
-    sizes = qn * cn
-    out_off = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-    tiles = cn * ((qn + CLF_QCHUNK - 1) // CLF_QCHUNK)
-    tile_off = np.concatenate([[0], np.cumsum(tiles)]).astype(np.int64)
-    if tile_off[-1] >= 2 ** 31 or max(nq_seg, nc_seg) * N >= 2 ** 31 or (G and cn.sum() >= 2 ** 31):
-        raise ValueError("clf_pair_scores_dev: too many pairs for one call")
-    out = torch.empty((int(out_off[-1]),), device=q.device, dtype=torch.float32)
-    if G == 0 or tile_off[-1] == 0:
-        return out, out_off[:-1]
-    dev = q.device
-    grp = torch.from_numpy(np.stack([qs, qn, co, cn], 1).astype(np.int32).reshape(-1)).to(dev)
-    oo = torch.from_numpy(out_off[:-1].copy()).to(dev)
-    to = torch.from_numpy(tile_off.astype(np.int32)).to(dev)
-    npairs = float(sizes.sum())
-    if N > CLF_MAX_N:                     # flop and byte counts: as clf_pair_scores
-        nt = (N + 31) // 32
-        _timed("clf_pair_wide_kernel", (2.0 * N * N * C + 12.0 * 4 * N * N + 2.0 * N * CLF_PW + 512.0) * npairs,
-               4.0 * npairs + 4.0 * CLF_PW * N * float(tile_off[-1]) + 4.0 * N * C * (1 + nt) * npairs,
-               lambda: call("nsid_clf_pair_scores_n", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G,
-                            int(tile_off[-1]), _p(cidx), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
-        return out, out_off[:-1]
-    _timed("clf_pair_kernel", (1.2e6 + 2.0 * CLF_MAX_N * CLF_MAX_N * (C - CLF_C)) * npairs,
-           4.0 * npairs + 4.0 * (C + CLF_PW) * N * float(tile_off[-1]),
-           lambda: call("nsid_clf_pair_scores_c", _p(q), nq_seg, _p(kp), nc_seg, C, N, _p(grp), _p(oo), _p(to), G, int(tile_off[-1]),
-                        _p(cidx), _p(tail), _p(out), out.numel(), _stream()), (G, int(npairs), N, 1))
-    return out, out_off[:-1]
+    # cand_off None: group i's list starts at the running sum of cand_count, so the lists fit when cand_count.sum() <= cidx.numel()
+    out, out_off, plan = _clf_pair_plan("clf_pair_scores_dev", q, kp, N, tail, q_start, q_count, None, cand_count, cidx.numel())
+    if plan is not None:
+        _clf_pair_launch(q, kp, tail, out, plan, cidx)
+    return out, out_off
 
 
 # ------------------------------------------------------------------------------------------------ classifier training (csrc/clf_train.hip)
