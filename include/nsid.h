@@ -307,6 +307,7 @@ int nsid_dsact_part_rows(int B, int N);
  * and view: nsid_ds_prepack writes the packed forward weight (Cout, 3*Cin) and the packed backward weight [W_2 ; W_0] (2*Cout, Cin) of
  * every layer straight to bf16 and zeroes its packed gradient buffers dwp (TWO of them, contiguous: (2, Cout, 3*Cin) fp32, one per view of a
  * contrastive step; dwp or its entries may be NULL). Each view unpacks its own packed gradient with nsid_unpack_ds_wgrad (atomic adds). */
+#define NSID_DS_PREPACK_MAX_LAYERS 8 /* n of nsid_ds_prepack at most */
 int nsid_ds_prepack(int n, const float* const* w, void* const* wp16, void* const* wb16, float* const* dwp, const int* Cout,
                     const int* Cin, void* stream);
 int nsid_unpack_ds_wgrad(const float* dwp, int Cout, int Cin, float* dw /* += */, void* stream);
@@ -368,6 +369,8 @@ int nsid_logmel_fft(const float* wave, long in_stride, int B, long L, int n_fft,
  * bit-equal to the clip alone), stream-ordered. NSID_EINVAL before any launch: null pointers, B < 1, hop < 1, L <= width/2
  * (torch's reflect pad raises there), in_stride < L, groups that do not cover n_bins or leave the table, a misaligned table, and a
  * hop so small that a group's longest bin spans more than 24 hops (the staged rows would not fit 64 KB of LDS). */
+#define NSID_CQT_GROUP_BINS 8 /* bins of a group at most: 16 re / im columns */
+#define NSID_CQT_RC 256       /* hopP: the hop rounded up to a multiple of this */
 int nsid_cqt(const float* wave, long in_stride, int B, long L, int hop, int width, int n_bins, const int* groups, int n_groups,
              const float* taps, long taps_len, const float* scale, float* out, long out_clip_stride, long out_bin_stride,
              void* stream);
@@ -385,6 +388,9 @@ int nsid_cqt(const float* wave, long in_stride, int B, long L, int hop, int widt
  * batched entries refuse, max_len outside their range for L, ld < total_cols, a work-item total >= 2^31. The entries cannot read
  * the device table: its validity (offsets and lengths inside the pack, every L_i above the reflect minimum, columns inside ld,
  * prefixes that match the lengths) is the caller's duty (packs.plan_pack checks all of it on the host). */
+#define NSID_PACK_COLS 4   /* longs per song of the `songs` table */
+#define NSID_LOGMEL_RUN 8  /* frames of a log-mel work item */
+#define NSID_CQT_TILE 32   /* frames of a constant-Q work item */
 int nsid_logmel_fft_ragged(const float* pack, const long* songs, int n_songs, long max_len, long total_runs, long total_cols,
                            int n_fft, int hop, const float* window, const float* twiddle, const float* fb, const int* band,
                            int n_mels, float* out, long ld, void* stream);
@@ -414,6 +420,11 @@ int nsid_unfold_segments_ragged(const float* spec, long ld, int n_rows, int n_fr
  *            any other mode (time stretch): out[b][m] = wave[b][m], m < min(L, n_s); zero up to L in both
  * NSID_EINVAL before any launch: null pointers, B < 1, L < 1 or L >= 2^30, strides shorter than rows, misaligned tables, rate_lo <= 0
  * or rate_lo > rate_hi, T_out_max or wave_stride below the extents above. */
+#define NSID_AUG_N_FFT 2048     /* n_fft of the four stages: the length of `window` and `twiddle` */
+#define NSID_AUG_HOP 512        /* their hop: T_in = 1 + L / NSID_AUG_HOP */
+#define NSID_AUG_BINS 1025      /* bins of a spectrum frame: NSID_AUG_N_FFT / 2 + 1 */
+#define NSID_AUG_ZEROS 64       /* `table` of nsid_aug_finish: zero crossings, */
+#define NSID_AUG_PRECISION 512  /* points per zero crossing */
 int nsid_aug_stft(const float* x_i, long stride_i, const float* x_j, long stride_j, int B, long L, const float* gain,
                   const float* window, const float* twiddle, float* spec, void* stream);
 int nsid_aug_vocoder(const float* spec, int B, long L, const float* rate, float rate_lo, float rate_hi, float* out,
@@ -440,6 +451,8 @@ int nsid_aug_finish(const float* wave, long wave_stride, int B, long L, const in
  *             taken from position p is float(float(gain[b] * t1[b][p]) + x_i[b][p]).
  * NSID_EINVAL before any launch: null pointers, B < 1, L < 1 or L >= 2^30, strides shorter than rows, S or F outside their ranges,
  * cmp / sos not 8-byte aligned. */
+#define NSID_AUG_FX_MAX_SECTIONS 64 /* S of nsid_aug_biquad at most */
+#define NSID_AUG_FX_MAX_FRAMES 256  /* F of nsid_aug_frames at most */
 int nsid_aug_compress(const float* x, long stride_x, int B, long L, const int* mode1, const double* cmp, float* out, long stride_o,
                       void* stream);
 int nsid_aug_biquad(const float* x, long stride_x, int B, long L, const int* mode1, const double* sos, int S, const int* n_sec,
@@ -468,6 +481,8 @@ int nsid_aug_frames(const float* x_i, long stride_i, const float* t1, long strid
  *             clips in order in rows 0 .. n_ok - 1 of B_out rows, n_ok = min(accepted, B_out), zeros from row n_ok on, *n_ok written.
  * No atomics: every result is bit-equal run to run and independent of the other clips. NSID_EINVAL before any launch: null
  * pointers, N or B_out outside [1, 65535], L < 1, O < 1, L + O >= 2^30, strides shorter than L. */
+#define NSID_RESAMPLE_MAX_C 8         /* channels of nsid_resample_sinc at most */
+#define NSID_RESAMPLE_LDS_BYTES 65536 /* its filter table at most: (nw ts + nw) * 4 bytes */
 int nsid_resample_sinc(const float* x, long stride_x, int C, long T, int orig, int nw, int width, const float* table,
                        const int* first, int ntap, int ts, float* y, long T_out, void* stream);
 int nsid_stem_pairs_gate(const float* bank, long bank_elems, const long* base, const int* length, int n_tracks, const int* track,
@@ -511,6 +526,7 @@ int nsid_ntxent_fwd_bwd(const float* z_i, const float* z_j, int Bg, int d, float
  * baseline_objective (the step of train.py:66-77): out[1] = pair_ce(z_i, z_j), out[2] = triplet(normalize(cat(z_i, z_j)),
  *   cat(arange(B), arange(B)), margin) with F.normalize's eps = 1e-12, out[0] = beta out[1] + gamma out[2], out[3] = number of valid
  *   anchors; dz_i / dz_j = d out[0] / d z, the backward of the normalisation included. */
+#define NSID_BL_MAX 2048 /* rows (M, or 2 B) and features D of the three at most */
 size_t nsid_baseline_loss_ws_floats(int M, int D);
 int nsid_pair_ce_fwd_bwd(const float* z_i, const float* z_j, int B, int D, float* ws, float* out, float* dz_i, float* dz_j,
                          void* stream);
@@ -527,6 +543,7 @@ int nsid_baseline_objective_fwd_bwd(const float* z_i, const float* z_j, int B, i
  * anchors in ascending order, so the rows do not depend on how the batch is cut: with p0 = 0, npairs = Bg <= 1024 the call equals
  * nsid_baseline_objective_fwd_bwd bit for bit, and the rows of any shard equal the same rows of that call.
  * ws: nsid_baseline_loss_rows_ws_floats(M, D) floats (both similarity matrices are kept whole: 2 x 64 MB at M = 4096). */
+#define NSID_BL_ROWS_MAX 4096 /* M = 2 * Bg at most */
 size_t nsid_baseline_loss_rows_ws_floats(int M, int D);
 int nsid_baseline_objective_rows_fwd_bwd(const float* z_i_all, const float* z_j_all, int Bg, int D, int p0, int npairs,
                                          double margin, double beta, double gamma, float* ws, float* out, float* dz_i, float* dz_j,
@@ -565,6 +582,7 @@ int nsid_rows_to_bcn(const void* rows, int ld, int B, int C, int N, float* x, in
  * seq_scores: for pair p = (s = starts[p], L = lens[p]) (device int32; the caller guarantees s + L <= the rows of q and of I) and
  *   candidate j < L*k with cid = I[s + j/k][j%k]: out[p*ldo + j] = mean over i < min(L, nx - cid) of q[s+i].x[cid+i] (fp32),
  *   NaN when cid < 0 and for L*k <= j < ldo (eval.py:325-331, the window truncated at the end of the index). ldo <= 262140. */
+#define NSID_SEARCH_MAX_K 64 /* k of flat_l2_topk, seq_scores and the vote at most */
 int nsid_row_sqnorm(const float* x, int ldx, int n, int d, float* out, void* stream);
 int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm, const float* q_sqnorm,
                       int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream);
@@ -591,6 +609,14 @@ int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, in
  *   pair's score bitwise independent of the rest of the call. N = 0, N > 128, another C, a null or (q, kp) misaligned pointer:
  *   NSID_EINVAL before anything is read or launched. Launches count on their own counters (clf_node_rows_n, clf_pair_scores_n); the
  *   entries above keep their bound N <= 32 and their kernels. */
+#define NSID_CLF_C 512          /* the width of the entries without a _c suffix */
+#define NSID_CLF_H 4            /* heads */
+#define NSID_CLF_HID 128        /* fc.0 width */
+#define NSID_CLF_PW 512         /* the folded block P of a candidate row: NSID_CLF_H * NSID_CLF_HID, at every width */
+#define NSID_CLF_KP 1024        /* a [K | P] row at C = NSID_CLF_C: NSID_CLF_C + NSID_CLF_PW */
+#define NSID_CLF_MAX_N 32       /* nodes at most: clf_node_rows, clf_pair_scores[_c] and the training entries */
+#define NSID_CLF_MAX_N_EVAL 128 /* nodes at most: the _n entries */
+#define NSID_CLF_QCHUNK 64      /* query segments per tile of tile_off */
 int nsid_clf_node_rows(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream);
 int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups, const int64_t* out_off,
                          const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail, float* out,
@@ -624,6 +650,8 @@ int nsid_clf_pair_scores_n(const float* q, int nq_seg, const float* kp, int nc_s
  * vote_candidates: cidx[i] = I[i] - n_dummy for a ref row (n_dummy <= I[i] < n_dummy + n_ref), else 0: the candidate list of
  *   clf_pair_scores_c / _n for a search result, on the device. The vote skips the other positions from I, so what is scored there is
  *   never read. */
+#define NSID_VOTE_MAX_CAND 4096 /* L k of a pair, and lds, at most */
+#define NSID_VOTE_MAX_TOP 32    /* top at most */
 int nsid_song_vote(const int64_t* I, int k, const float* scores, int lds, const int* starts, const int* lens, int npairs,
                    const int* song_of, int n_ref, int n_dummy, const int* exclude, int top, int* songs, double* totals, int* n_songs,
                    void* stream);
@@ -652,6 +680,8 @@ int nsid_vote_candidates(const int64_t* I, long n, int n_dummy, int n_ref, int* 
  * clf_attn_bwd: from dobar (P x 512) = dL/dobar: dq, dk (P x N x 512) = the per-pair dL/dQ and dL/dK of the query and candidate rows.
  * clf_seg_reduce: dq_seg (nq_seg N x 512) = sum over the pairs with qi[p] == seg of dq[p]; dkv_seg (nc_seg N x 1024) = [sum dk[p] |
  *   sum abar[p] (x) dobar[p]] over the pairs with ci[p] == seg; both in pair order, zeros for a segment without pairs. */
+#define NSID_CLF_MINE_MAX_ROWS 8192 /* na of clf_mine_hard_negatives at most */
+#define NSID_CLF_MINE_MAX_D 512     /* d at most */
 int nsid_clf_mine_hard_negatives(const float* zq, int nq, const float* za, int na, int d, int k, int64_t* out, void* stream);
 int nsid_clf_attn_fwd(const float* q, int nq_seg, const float* kv, int nc_seg, int N, const int* qi, const int* ci, int P, float* obar,
                       float* attn, float* abar, void* stream);

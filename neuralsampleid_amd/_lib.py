@@ -4,6 +4,7 @@ The product path has no CPU fallback: if the library is missing this module rais
 RuntimeError on a non-zero return code."""
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  -- must come first: torch bundles its own libamdhip64; loading the kernel library before it
 #                              would bind the system HIP runtime and leave two runtimes in one process
@@ -12,116 +13,91 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 # NSID_LIB: path of an alternative BUILD of the same library (one-box kernel A/B, tools/build_variant.sh). It selects which .so is
 # loaded, nothing inside the library reads the environment; bench.py records an override in its JSON line (config.lib).
 LIB_PATH = os.environ.get("NSID_LIB") or os.path.join(_PKG, "libnsid_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "nsid.h")      # the C ABI; build.py compiles against the same file
 
-# signature letters: p = device pointer, i = int, l = long, z = size_t, f = float, d = double, s = stream (void*)
-SIGNATURES = {
-    "nsid_set_gemm_precision": "i",
-    "nsid_linear_fwd": "pipippiiiiippiipiis",
-    "nsid_linear_fwd_res": "pipippipiiiiippiis",
-    "nsid_linear_bwd_data": "pipipipiiiiiis",
-    "nsid_linear_bwd_data_bn": "pipipipiiiiiipppppips",
-    "nsid_linear_bwd_weight": "pipipiiiippiis",
-    "nsid_linear_bwd_weight_grouped": "piiis",
-    "nsid_colsum_acc": "piiipis",
-    "nsid_bn_finalize": "piiipppppffpppps",
-    "nsid_bn_finalize_deferred": "piiippfppppps",
-    "nsid_bn_running_update": "ippppppppfs",
-    "nsid_bn_eval_affine": "ppppfipps",
-    "nsid_bn_apply": "pppippiiis",
-    "nsid_bn_bwd_reduce": "ppiippppipis",
-    "nsid_bn_bwd_finalize": "piiippps",
-    "nsid_bn_bwd_apply": "ppiippppippis",
-    "nsid_bn_bwd_finalize_fused": "piiipppppppps",
-    "nsid_knn_graph": "pippiiiiipis",
-    "nsid_mr_aggregate_fwd": "pipppiiiippis",
-    "nsid_mr_aggregate_bwd": "pppiiiipis",
-    "nsid_im2col3_fwd": "piiipis",
-    "nsid_im2col3_bwd": "piiipis",
-    "nsid_pack_ds_weight": "piips",
-    "nsid_dsact_fwd": "piiippipppipppiis",
-    "nsid_dsact_bwd_weight": "ppppipiiiiis",
-    "nsid_dsact_bwd_data": "pppiiiipppppipis",
-    "nsid_pack_ds_weight_bwd": "piips",
-    "nsid_downsample3_fwd": "piiipippipis",
-    "nsid_downsample3_bwd_weight": "pppiiiiis",
-    "nsid_downsample3_bwd_data": "pppipiiiiis",
-    "nsid_unpack_ds_wgrad": "piips",
-    "nsid_ds_prepack": "ipppppps",
-    "nsid_peak_patchify_fwd": "pppiiiiiipipis",
-    "nsid_peak_patchify_bwd": "ppppiiiiiiippis",
-    "nsid_peak_patchify_bwd_ws": "ppppiiiiiiipppis",
-    "nsid_node_mean_fwd": "piiipis",
-    "nsid_node_mean_bwd": "piiipis",
-    "nsid_elu_bwd": "pplps",
-    "nsid_l2norm_fwd": "piifpps",
-    "nsid_l2norm_bwd": "pppiifps",
-    "nsid_ntxent_fwd_bwd": "ppiifiipppps",
-    "nsid_pair_ce_fwd_bwd": "ppiipppps",
-    "nsid_triplet_fwd_bwd": "ppiidppps",
-    "nsid_baseline_objective_fwd_bwd": "ppiidddpppps",
-    "nsid_baseline_objective_rows_fwd_bwd": "ppiiiidddpppps",
-    "nsid_sumsq_partial": "plps",
-    "nsid_adam_step": "pppplpppips",
-    "nsid_f32_to_bf16": "ppls",
-    "nsid_reflect_pad": "plips",
-    "nsid_power_mel_db": "plippiips",
-    "nsid_unfold_segments": "piiiiips",
-    "nsid_logmel_fft": "pliliippppiplls",
-    "nsid_cqt": "pliliiipiplpplls",
-    "nsid_logmel_fft_ragged": "ppillliippppipls",
-    "nsid_cqt_ragged": "ppillliiipiplppls",
-    "nsid_unfold_segments_ragged": "pliiplips",
-    "nsid_aug_stft": "plplilpppps",
-    "nsid_aug_vocoder": "pilpffpls",
-    "nsid_aug_istft": "plilpffpppls",
-    "nsid_aug_finish": "plilppffppls",
-    "nsid_aug_compress": "plilpppls",
-    "nsid_aug_biquad": "plilppippls",
-    "nsid_aug_frames": "plplpilpppipls",
-    "nsid_resample_sinc": "pliliiippiipls",
-    "nsid_stem_pairs_gate": "plppipppppillfppps",
-    "nsid_stem_pairs_build": "plppippppppilliiplplps",
-    "nsid_bcn_to_rows": "piiipiis",
-    "nsid_rows_to_bcn": "piiiipis",
-    "nsid_batched_index_select_fwd": "ppiiiiips",
-    "nsid_batched_index_select_bwd": "ppiiiiips",
-    "nsid_fill_zero": "pzs",
-    "nsid_scale_f32": "pplps",
-    "nsid_row_sqnorm": "piiips",
-    "nsid_flat_l2_topk": "piipiippiipppzs",
-    "nsid_seq_scores": "pipiiipippipis",
-    "nsid_clf_node_rows": "piiipps",
-    "nsid_clf_pair_scores": "pipiipppiipppls",
-    "nsid_clf_pair_scores_c": "pipiiipppiipppls",
-    "nsid_clf_node_rows_n": "piiipps",
-    "nsid_clf_pair_scores_n": "pipiiipppiipppls",
-    "nsid_song_vote": "pipippipiipippps",
-    "nsid_song_vote_clf": "pipppppipiipfippps",
-    "nsid_vote_candidates": "pliips",
-    "nsid_clf_mine_hard_negatives": "pipiiips",
-    "nsid_clf_attn_fwd": "pipiippippps",
-    "nsid_clf_head_fwd": "ppppips",
-    "nsid_clf_head_bwd": "pppppipppps",
-    "nsid_clf_attn_bwd": "pppipiippipps",
-    "nsid_clf_seg_reduce": "ppppppiiiipps",
-    "nsid_clf_attn_fwd_c": "pipiiippippps",
-    "nsid_clf_attn_bwd_c": "pppipiiippipps",
-    "nsid_clf_seg_reduce_c": "ppppppiiiiipps",
-    "nsid_conv2d_fwd": "piiiipipppiiiiis",
-    "nsid_ibn_relu_fwd": "piiippfpppis",
-    "nsid_stem7_pool_fwd": "piiipppis",
-    "nsid_gem_pool_fwd": "piiipfpis",
-    "nsid_gem_pool_bwd": "ppiiipfpppis",
-    "nsid_conv2d_bwd_data": "piiiipippiiiis",
-    "nsid_conv2d_bwd_weight": "ppiiiippiiiis",
-    "nsid_col_stat": "piiipis",
-    "nsid_ibn_relu_bwd": "ppiiippfppppppppppis",
-    "nsid_bn_add_relu_fwd": "pppppppiiis",
-    "nsid_relu_bwd": "ppplis",
-    "nsid_stem7_stat": "piiipps",
-    "nsid_stem7_pool_train_fwd": "piiipppppis",
-    "nsid_stem7_bwd": "pipiiipppppppppps",
-}
+# type letters: p = pointer, s = the `void* stream` parameter, i = int / int32_t, l = long / int64_t, z = size_t, f = float, d = double,
+# c = const char*. include/nsid.h is the only description of the entry points: nothing below names one.
+_CT = {"p": ctypes.c_void_p, "s": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "z": ctypes.c_size_t, "f": ctypes.c_float,
+       "d": ctypes.c_double, "c": ctypes.c_char_p}
+_SCALARS = {"int": "i", "int32_t": "i", "long": "l", "int64_t": "l", "size_t": "z", "float": "f", "double": "d"}
+_POINTEES = {"void", "char", "float", "double", "int", "long", "int32_t", "int64_t", "uint8_t", "size_t"}
+
+
+def _letter(ctype: str, pointees) -> str:
+    """type letter of a C type without its parameter name; KeyError (parse_header's ImportError) for a type outside the alphabet"""
+    words = ctype.replace("*", " * ").split()
+    base = [w for w in words if w not in ("const", "*")]
+    if len(base) != 1:
+        raise KeyError(ctype)
+    if "*" not in words:
+        return _SCALARS[base[0]]
+    if base[0] not in pointees:
+        raise KeyError(ctype)
+    return "c" if words == ["const", "char", "*"] else "p"
+
+
+def parse_header(text: str):
+    """(prototypes, defines) of a C header in the style of include/nsid.h: prototypes = {name: (return letter, parameter letters)} in
+    header order, defines = {NSID_*: int}. Fails closed: a declaration, a type or an NSID_* define it does not understand raises
+    ImportError naming it; nothing defaults to int."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    scanned = set(re.findall(r"\b(nsid_\w+)\s*\(", text))
+    guards = set(re.findall(r"^[ \t]*#[ \t]*ifndef[ \t]+(\w+)", text, flags=re.M))
+    defines = {}
+    for name, value in re.findall(r"^[ \t]*#[ \t]*define[ \t]+(NSID_\w+)(.*)$", text, flags=re.M):
+        if name in guards and not value.strip():
+            continue
+        m = re.fullmatch(r"\s+(?:\(\s*([+-]?\d+)\s*\)|([+-]?\d+))\s*", value)
+        if not m:
+            raise ImportError(f"#define {name}{value.rstrip()}: not an integer constant")
+        defines[name] = int(m.group(1) or m.group(2))
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{', " ", text)
+    structs = set()
+
+    def skip_struct(m):
+        structs.add(m.group(1))
+        return " "
+    text = re.sub(r"typedef\s+struct\b[^{;]*\{[^{}]*\}\s*(\w+)\s*;", skip_struct, text)
+    *statements, rest = text.split(";")
+    if rest.strip() not in ("", "}"):
+        raise ImportError(f"cannot parse the end of the header: {' '.join(rest.split())[:80]!r}")
+    prototypes = {}
+    for statement in statements:
+        statement = " ".join(statement.split())
+        m = re.fullmatch(r"(.*?)\b(nsid_\w+) ?\((.*)\)", statement)
+        if not m or m.group(2) in prototypes:
+            raise ImportError(f"cannot parse the declaration {statement[:120]!r}")
+        ret, name, params = m.groups()
+        try:
+            letters = _letter(ret, {"char"})
+            if letters not in "ilzc":
+                raise KeyError(ret)
+            for param in ([] if params.strip() == "void" else params.split(",")):
+                pm = re.fullmatch(r"(.*[\s*])(\w+)", param.strip())
+                if not pm:
+                    raise KeyError(param)
+                letter = _letter(pm.group(1), _POINTEES | structs)
+                letters += "s" if pm.group(2) == "stream" and pm.group(1).replace(" ", "") == "void*" else letter
+        except KeyError as e:
+            raise ImportError(f"{name}: unknown type or unsplittable parameter {e.args[0].strip()!r}") from None
+        prototypes[name] = (letters[0], letters[1:])
+    if set(prototypes) != scanned:
+        raise ImportError(f"prototypes parsed and names scanned disagree: {sorted(set(prototypes) ^ scanned)}")
+    return prototypes, defines
+
+
+def load_header():
+    if not os.path.exists(HEADER_PATH):
+        raise ImportError(f"{HEADER_PATH} is missing: the ctypes binding is derived from it")
+    with open(HEADER_PATH) as f:
+        return parse_header(f.read())
+
+
+PROTOTYPES, DEFINES = load_header()
+SIGNATURES = {name: args for name, (_, args) in PROTOTYPES.items()}
+EXPORTS = list(SIGNATURES)
+
 
 class WgradProblem(ctypes.Structure):
     """include/nsid.h nsid_wgrad_problem: one layer's weight gradient over up to two row segments (the two views)"""
@@ -131,86 +107,26 @@ class WgradProblem(ctypes.Structure):
                 ("ds_out_nodes", ctypes.c_int)]
 
 
-_CT = {"p": ctypes.c_void_p, "i": ctypes.c_int, "l": ctypes.c_long, "f": ctypes.c_float, "d": ctypes.c_double, "s": ctypes.c_void_p,
-       "z": ctypes.c_size_t}
-
-
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
             f"{LIB_PATH} is missing: build it with `python -m neuralsampleid_amd.build` "
             "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, sig in SIGNATURES.items():
+    for name, (ret, args) in PROTOTYPES.items():
         fn = getattr(lib, name)
-        fn.argtypes = [_CT[c] for c in sig]
-        fn.restype = ctypes.c_int
-    lib.nsid_version.restype = ctypes.c_int
+        fn.argtypes = [_CT[c] for c in args]
+        fn.restype = _CT[ret]
     if lib.nsid_version() < 0:      # (builds of rounds 3-4 with result-changing timing switches reported a negative version)
         raise ImportError(f"{LIB_PATH} reports a negative version: not a product build of this tree; rebuild with "
                           "`python -m neuralsampleid_amd.build --force`")
-    lib.nsid_debug_gemm_trace.argtypes = [ctypes.c_void_p]
-    lib.nsid_debug_gemm_trace.restype = ctypes.c_int
-    lib.nsid_debug_knn_trace.argtypes = [ctypes.c_void_p]
-    lib.nsid_debug_knn_trace.restype = ctypes.c_int
-    lib.nsid_get_gemm_precision.restype = ctypes.c_int
-    lib.nsid_gemm_g256_launches.argtypes = []
-    lib.nsid_gemm_g256_launches.restype = ctypes.c_long
-    lib.nsid_set_tuning.argtypes = [ctypes.c_char_p, ctypes.c_long]
-    lib.nsid_set_tuning.restype = ctypes.c_int
-    lib.nsid_get_tuning.argtypes = [ctypes.c_char_p, ctypes.POINTER(ctypes.c_long)]
-    lib.nsid_get_tuning.restype = ctypes.c_int
-    lib.nsid_reset_tuning.argtypes = []
-    lib.nsid_reset_tuning.restype = ctypes.c_int
-    lib.nsid_workspace_bytes.argtypes = [ctypes.c_char_p, ctypes.c_long, ctypes.c_long]
-    lib.nsid_workspace_bytes.restype = ctypes.c_long
-    lib.nsid_tuning_count.argtypes = []
-    lib.nsid_tuning_count.restype = ctypes.c_int
-    lib.nsid_tuning_key.argtypes = [ctypes.c_int]
-    lib.nsid_tuning_key.restype = ctypes.c_char_p
-    lib.nsid_debug_counter.argtypes = [ctypes.c_char_p]
-    lib.nsid_debug_counter.restype = ctypes.c_long
-    lib.nsid_debug_counters_reset.argtypes = []
-    lib.nsid_debug_counters_reset.restype = ctypes.c_int
-    lib.nsid_debug_counter_count.argtypes = []
-    lib.nsid_debug_counter_count.restype = ctypes.c_int
-    lib.nsid_debug_counter_key.argtypes = [ctypes.c_int]
-    lib.nsid_debug_counter_key.restype = ctypes.c_char_p
-    # returns 1 (nothing launched) for shapes outside the fused form: bound directly, not through call()
-    lib.nsid_linear_bwd_data_bnapply.argtypes = [_CT[c] for c in "pppippipipiiiiiipppppips"]
-    lib.nsid_linear_bwd_data_bnapply.restype = ctypes.c_int
-    lib.nsid_mr_aggregate_bwd_bn.argtypes = [_CT[c] for c in "pppiiiippippppipis"]     # declines with NSID_EINVAL outside its form: the caller falls back
-    lib.nsid_mr_aggregate_bwd_bn.restype = ctypes.c_int
-    lib.nsid_ffn_fused_fwd.argtypes = [_CT[c] for c in "ppppppiiis"]
-    lib.nsid_ffn_fused_fwd.restype = ctypes.c_int
-    lib.nsid_mrconv_fused_fwd.argtypes = [_CT[c] for c in "ppiiiippps"]
-    lib.nsid_mrconv_fused_fwd.restype = ctypes.c_int
-    lib.nsid_row_tiles.argtypes = [ctypes.c_int]
-    lib.nsid_row_tiles.restype = ctypes.c_int
-    lib.nsid_dsact_part_rows.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.nsid_dsact_part_rows.restype = ctypes.c_int
-    lib.nsid_sumsq_blocks.argtypes = [ctypes.c_long]
-    lib.nsid_sumsq_blocks.restype = ctypes.c_int
-    lib.nsid_ntxent_ws_floats.argtypes = [ctypes.c_int]
-    lib.nsid_ntxent_ws_floats.restype = ctypes.c_size_t
-    lib.nsid_baseline_loss_ws_floats.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.nsid_baseline_loss_ws_floats.restype = ctypes.c_size_t
-    lib.nsid_baseline_loss_rows_ws_floats.argtypes = [ctypes.c_int, ctypes.c_int]
-    lib.nsid_baseline_loss_rows_ws_floats.restype = ctypes.c_size_t
-    lib.nsid_conv2d_wgrad_splits.argtypes = [ctypes.c_long, ctypes.c_long]
-    lib.nsid_conv2d_wgrad_splits.restype = ctypes.c_int
-    lib.nsid_stem7_partials.argtypes = [ctypes.c_long, ctypes.c_long, ctypes.c_int]
-    lib.nsid_stem7_partials.restype = ctypes.c_long
-    lib.nsid_stem7_bwd_set_floats.argtypes = []
-    lib.nsid_stem7_bwd_set_floats.restype = ctypes.c_long
     return lib
 
 
 lib = _load()
-EXPORTS = list(SIGNATURES) + ["nsid_version", "nsid_debug_gemm_trace", "nsid_debug_knn_trace", "nsid_get_gemm_precision", "nsid_gemm_g256_launches", "nsid_linear_bwd_data_bnapply", "nsid_mr_aggregate_bwd_bn", "nsid_ffn_fused_fwd", "nsid_mrconv_fused_fwd", "nsid_debug_counter", "nsid_debug_counters_reset", "nsid_debug_counter_count", "nsid_debug_counter_key", "nsid_set_tuning", "nsid_get_tuning", "nsid_reset_tuning", "nsid_tuning_count", "nsid_tuning_key", "nsid_row_tiles", "nsid_dsact_part_rows", "nsid_sumsq_blocks", "nsid_ntxent_ws_floats", "nsid_baseline_loss_ws_floats", "nsid_baseline_loss_rows_ws_floats", "nsid_conv2d_wgrad_splits", "nsid_stem7_partials", "nsid_stem7_bwd_set_floats", "nsid_workspace_bytes"]
 
-_ERR = {-1: "NSID_EINVAL (unsupported shape, misaligned pointer or bad argument)",
-        -2: "NSID_ELAUNCH (HIP runtime refused the launch)"}
+_ERR = {DEFINES["NSID_EINVAL"]: "NSID_EINVAL (unsupported shape, misaligned pointer or bad argument)",
+        DEFINES["NSID_ELAUNCH"]: "NSID_ELAUNCH (HIP runtime refused the launch)"}
 
 
 def call(name, *args):

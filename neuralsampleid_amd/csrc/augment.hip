@@ -20,15 +20,16 @@
 #include "nsid_common.h"
 #include "fft512.h"
 
-constexpr int AG_N = 2048;                // n_fft
-constexpr int AG_HOP = 512;
+constexpr int AG_N = NSID_AUG_N_FFT;      // n_fft
+constexpr int AG_HOP = NSID_AUG_HOP;
 constexpr int AG_M = AG_N / 2;            // complex points
 constexpr int AG_BINS = AG_M + 1;
+static_assert(AG_BINS == NSID_AUG_BINS, "include/nsid.h states the bins of a spectrum");
 constexpr int AG_RUN = 8;                 // STFT: frames per workgroup
 constexpr int AG_WAVES = 4;               // STFT: waves per workgroup
 constexpr int AG_CH = 8;                  // inverse STFT: hops of output per (one-wave) workgroup
-constexpr int AG_ZC = 64;                 // resampling filter: zero crossings,
-constexpr int AG_TP = 512;                // table points per zero crossing
+constexpr int AG_ZC = NSID_AUG_ZEROS;     // resampling filter: zero crossings,
+constexpr int AG_TP = NSID_AUG_PRECISION; // table points per zero crossing
 constexpr float AG_TWO_PI = 6.28318530717958647692f;
 constexpr float AG_INV_TWO_PI = 0.15915494309189533577f;
 constexpr float AG_HALF_PI = 1.57079632679489661923f;

@@ -22,8 +22,9 @@
 constexpr int FX_BLOCK = 1024;            // samples taken at a time (compressor, biquad): global memory is touched between blocks
                                           // only, so no load or store is outstanding while the serial loops run
 constexpr int FX_PER = FX_BLOCK / NSID_WAVE;
-constexpr int FX_MAX_SEC = NSID_WAVE;     // sections per clip: one lane each
-constexpr int FX_MAX_FRAMES = 256;        // frames per clip: one thread each
+constexpr int FX_MAX_SEC = NSID_AUG_FX_MAX_SECTIONS;    // sections per clip: one lane each
+static_assert(NSID_AUG_FX_MAX_SECTIONS == NSID_WAVE, "one lane per section");
+constexpr int FX_MAX_FRAMES = NSID_AUG_FX_MAX_FRAMES;   // frames per clip: one thread each
 constexpr int FX_FR_THREADS = 256;
 constexpr int FX_FR_PER = 4;              // output samples per thread of the frame gather
 

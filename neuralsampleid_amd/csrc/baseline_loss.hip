@@ -24,8 +24,8 @@ namespace {
 
 constexpr int TB = 64;          // tile edge of both MFMA products
 constexpr int LDT = TB + 4;     // LDS row stride (floats): 16-byte aligned rows, rows 4 apart land on different banks
-constexpr int BL_MAX = 2048;    // rows and features
-constexpr int BL_ROWS_MAX = 4096;   // rows of the gathered batch of the sharded objective
+constexpr int BL_MAX = NSID_BL_MAX;    // rows and features
+constexpr int BL_ROWS_MAX = NSID_BL_ROWS_MAX;   // rows of the gathered batch of the sharded objective
 
 // rows [0, split) of the row matrix live at a, the rest at b (the two views); a single matrix has split = M
 struct RowSet {

@@ -12,10 +12,12 @@
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int CLF_H = 4;                   // heads; node channels C = 4 DH are template parameters of the kernels
+constexpr int CLF_H = NSID_CLF_H;          // heads; node channels C = 4 DH are template parameters of the kernels
 constexpr int CLF_TILE = 32;               // nodes of one 32 x 32 MFMA tile
-constexpr int CLF_HID = 128;               // fc.0 width
+constexpr int CLF_HID = NSID_CLF_HID;      // fc.0 width
 constexpr int CLF_PW = CLF_H * CLF_HID;    // P row of the folded candidate side: one fc.0-wide block per head
+static_assert(CLF_PW == NSID_CLF_PW && NSID_CLF_KP == NSID_CLF_C + NSID_CLF_PW, "include/nsid.h states the row widths");
+static_assert(NSID_CLF_MAX_N == CLF_TILE, "the entries with one tile per side take a tile of nodes at most");
 
 // 1 / sqrt(DH), rounded to fp32
 template <int DH> struct clf_scale;

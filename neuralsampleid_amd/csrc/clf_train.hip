@@ -22,8 +22,8 @@
 
 namespace {
 
-constexpr int CT_MINE_MAXN = 8192;   // rows of the mining pool (2B) at most: their dots live in LDS
-constexpr int CT_MINE_MAXD = 512;
+constexpr int CT_MINE_MAXN = NSID_CLF_MINE_MAX_ROWS;   // rows of the mining pool (2B) at most: their dots live in LDS
+constexpr int CT_MINE_MAXD = NSID_CLF_MINE_MAX_D;
 constexpr int CT_RED_THREADS = 512;  // nsid_clf_seg_reduce: one workgroup per segment, C / 64 float4 per thread cover N x C
 
 // ------------------------------------------------------------------------------------------------ hard-negative mining
@@ -410,7 +410,7 @@ extern "C" int nsid_clf_attn_fwd_c(const float* q, int nq_seg, const float* kv, 
 
 extern "C" int nsid_clf_attn_fwd(const float* q, int nq_seg, const float* kv, int nc_seg, int N, const int* qi, const int* ci, int P,
                                  float* obar, float* attn, float* abar, void* stream) {
-  return nsid_clf_attn_fwd_c(q, nq_seg, kv, nc_seg, 512, N, qi, ci, P, obar, attn, abar, stream);
+  return nsid_clf_attn_fwd_c(q, nq_seg, kv, nc_seg, NSID_CLF_C, N, qi, ci, P, obar, attn, abar, stream);
 }
 
 extern "C" int nsid_clf_head_fwd(const float* hid, const float* keep, const float* w2, const float* b2, int P, float* s, void* stream) {
@@ -450,7 +450,7 @@ extern "C" int nsid_clf_attn_bwd_c(const float* dobar, const float* attn, const 
 
 extern "C" int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int N,
                                  const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
-  return nsid_clf_attn_bwd_c(dobar, attn, q, nq_seg, kv, nc_seg, 512, N, qi, ci, P, dq, dk, stream);
+  return nsid_clf_attn_bwd_c(dobar, attn, q, nq_seg, kv, nc_seg, NSID_CLF_C, N, qi, ci, P, dq, dk, stream);
 }
 
 extern "C" int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
@@ -469,5 +469,5 @@ extern "C" int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const flo
 
 extern "C" int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
                                    const int* ci, int P, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream) {
-  return nsid_clf_seg_reduce_c(dq, dk, abar, dobar, qi, ci, P, 512, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
+  return nsid_clf_seg_reduce_c(dq, dk, abar, dobar, qi, ci, P, NSID_CLF_C, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
 }

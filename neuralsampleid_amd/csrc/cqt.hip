@@ -36,12 +36,13 @@
 // The staging write is one float per lane at consecutive addresses (conflict-free, ds_write_b32).
 #include "nsid_common.h"
 
-constexpr int CQ_F = 32;                  // frames per workgroup (two 16-frame MFMA tiles)
+constexpr int CQ_F = NSID_CQT_TILE;       // frames per workgroup (two 16-frame MFMA tiles)
 constexpr int CQ_FT = CQ_F / 16;
 constexpr int CQ_WAVES = 4;
-constexpr int CQ_RC = 256;                // values of r per staged chunk: 4 kq x 16 mm x 4 e
+constexpr int CQ_RC = NSID_CQT_RC;        // values of r per staged chunk: 4 kq x 16 mm x 4 e
 constexpr int CQ_PITCH = CQ_RC + 4;       // floats per staged row
 constexpr int CQ_COLS = 16;               // re/im columns of a group
+static_assert(CQ_COLS == 2 * NSID_CQT_GROUP_BINS, "two columns per bin of a group");
 constexpr int CQ_MAXG = 32;               // groups per launch (the descriptors travel in the kernel arguments)
 constexpr int CQ_RED = CQ_WAVES * CQ_F * CQ_COLS;      // floats of the partial-sum exchange
 

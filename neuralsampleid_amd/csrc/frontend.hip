@@ -30,7 +30,7 @@
 
 constexpr int FE_N = 1024;                // n_fft of the tuned form
 constexpr int FE_M = FE_N / 2;            // complex points
-constexpr int FE_RUN = 8;                 // frames per workgroup
+constexpr int FE_RUN = NSID_LOGMEL_RUN;   // frames per workgroup
 constexpr int FE_WAVES = 4;
 
 // the per-lane twiddles of the three passes (FeTw): constant over frames, loaded once per wave

@@ -93,7 +93,7 @@ __global__ void unpack_ds_wgrad_kernel(const float* __restrict__ dwp, int Cout, 
 // wp[o][t*Cin + c] = w[o][c][t][1] and the packed backward weight wb = [W_2 ; W_0] straight to bf16 and zeroes the layer's two packed
 // gradient buffers (one per view; each view still unpacks its own right after its weight-gradient GEMM, so a parameter's .grad is
 // complete when backward returns).
-constexpr int DSP_LAYERS = 8;
+constexpr int DSP_LAYERS = NSID_DS_PREPACK_MAX_LAYERS;
 #define NSID_DS_SLOTS 2
 struct DsPrepArgs {
   const float* w[DSP_LAYERS]; __bf16* wp16[DSP_LAYERS]; __bf16* wb16[DSP_LAYERS]; float* dwp[DSP_LAYERS];

@@ -267,7 +267,6 @@ static inline void nsid_count(NsidCounterKey k) { ++g_nsid_counter[k]; }
 // {first sample in the pack, samples, first output column, work items (runs / tiles) of the songs before it}. The song of work item
 // b is the last one whose prefix is <= b (prefix[0] = 0, strictly increasing: every song has at least one item). The result
 // depends on b alone, so with b = blockIdx.x it is uniform over the workgroup.
-constexpr int NSID_PACK_COLS = 4;
 __device__ __forceinline__ int nsid_pack_song(const long* __restrict__ songs, const int n_songs, const long b) {
   int lo = 0, hi = n_songs - 1;
   while (lo < hi) {

@@ -29,7 +29,7 @@
 namespace {
 
 constexpr int RR_WAVES = 8;
-constexpr int RR_QCH = 64;           // query segments per workgroup
+constexpr int RR_QCH = NSID_CLF_QCHUNK;      // query segments per workgroup
 constexpr int RR_LDS_MAX = 160 * 1024;
 // K next to P in LDS (rows of C + 4 floats: +16 B so that the 32 rows of a fragment read start in different banks), else P alone
 constexpr bool rr_k_in_lds(int C) { return (CLF_TILE * (C + 4) + CLF_TILE * CLF_PW + RR_WAVES * CLF_TILE) * 4 <= RR_LDS_MAX; }
@@ -158,7 +158,7 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
 // (4 x 16 accumulator registers), so a row's max and sum are in registers; the column sums of a key tile accumulate over the query
 // tiles in their order. A pair's partial hidden vector waits in LDS between two heads (lane-private slots). Keys >= N get no weight,
 // query rows >= N no share in the column mean, which divides by N; no row >= N of a segment is addressed.
-constexpr int RW_N = 128;            // nodes per segment at most
+constexpr int RW_N = NSID_CLF_MAX_N_EVAL;      // nodes per segment at most
 constexpr int RW_T = RW_N / 32;      // tiles per side
 constexpr int RW_SLOTS = RR_QCH / RR_WAVES;   // segments of a chunk per wave
 
@@ -363,7 +363,7 @@ extern "C" int nsid_clf_pair_scores_c(const float* q, int nq_seg, const float* k
 extern "C" int nsid_clf_pair_scores(const float* q, int nq_seg, const float* kp, int nc_seg, int N, const int* groups,
                                     const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx,
                                     const float* tail, float* out, int64_t out_len, void* stream) {
-  return nsid_clf_pair_scores_c(q, nq_seg, kp, nc_seg, 512, N, groups, out_off, tile_off, ngroups, ntiles, cidx, tail, out, out_len,
+  return nsid_clf_pair_scores_c(q, nq_seg, kp, nc_seg, NSID_CLF_C, N, groups, out_off, tile_off, ngroups, ntiles, cidx, tail, out, out_len,
                                 stream);
 }
 

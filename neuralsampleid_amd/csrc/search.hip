@@ -21,7 +21,7 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int L2_QT = 32;            // query rows per wave (the 32x32 MFMA tile)
-constexpr int L2_LIST = 64;          // list slots per row (k <= 64)
+constexpr int L2_LIST = NSID_SEARCH_MAX_K;   // list slots per row (k <= 64)
 constexpr int L2_Q1 = 32;            // survivor queue per row, phase 1 (one half-wave's candidates at most per append)
 constexpr int L2_Q2 = 64;            // phase 2
 constexpr int L2_UNITS = 2048;       // waves phase 1 aims at: 256 CUs x 8

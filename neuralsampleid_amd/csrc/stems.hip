@@ -22,8 +22,8 @@
 constexpr int RS_THREADS = 256;
 constexpr int RS_PER = 16;                           // outputs per thread: a workgroup stages the table once for 4 096 outputs
 constexpr int RS_TILE = RS_THREADS * RS_PER;
-constexpr int RS_MAX_C = 8;
-constexpr long RS_LDS_BYTES = 64 * 1024;
+constexpr int RS_MAX_C = NSID_RESAMPLE_MAX_C;
+constexpr long RS_LDS_BYTES = NSID_RESAMPLE_LDS_BYTES;
 
 // the mono sample j: the fp32 sum of the channels in channel order, divided by C
 __device__ __forceinline__ float rs_mono(const float* __restrict__ x, const long stride_x, const int C, const float Cf, const long j) {

@@ -15,9 +15,9 @@
 
 namespace {
 
-constexpr int VOTE_MAX_CAND = 4096;   // L k of a pair at most: 48 KB of LDS
-constexpr int VOTE_MAX_K = 64;
-constexpr int VOTE_MAX_TOP = 32;
+constexpr int VOTE_MAX_CAND = NSID_VOTE_MAX_CAND;   // L k of a pair at most: 48 KB of LDS
+constexpr int VOTE_MAX_K = NSID_SEARCH_MAX_K;
+constexpr int VOTE_MAX_TOP = NSID_VOTE_MAX_TOP;
 constexpr int VOTE_THREADS = 256;
 constexpr int VOTE_PER_THREAD = VOTE_MAX_CAND / VOTE_THREADS;
 constexpr int VOTE_CHUNK = 8;         // LDS entries per step of the compare loops

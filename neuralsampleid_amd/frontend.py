@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._lib import call
+from ._lib import DEFINES, call
 
 
 def mel_filterbank(n_freqs: int, f_min: float, f_max: float, n_mels: int, sample_rate: int) -> torch.Tensor:
@@ -132,8 +132,8 @@ class LogMelFrontEnd:
 
 
 CQT_FMIN, CQT_BINS, CQT_BPO = 32.70, 84, 12          # nnAudio CQT defaults (filter_scale 1, norm 1, Hann)
-CQT_GROUP = 8                                        # bins per group of the banded kernel: 16 re/im columns of one MFMA tile
-CQT_RC = 256                                         # csrc/cqt.hip CQ_RC: the table pads the hop to a multiple of it
+CQT_GROUP = DEFINES["NSID_CQT_GROUP_BINS"]           # bins per group of the banded kernel: 16 re/im columns of one MFMA tile
+CQT_RC = DEFINES["NSID_CQT_RC"]                      # the table pads the hop to a multiple of it
 
 
 def cqt_kernels(fs: float):

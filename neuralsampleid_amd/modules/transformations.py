@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .._lib import call
+from .._lib import DEFINES, call
 from ..frontend import CQTFrontEnd, LogMelFrontEnd
 
 
@@ -109,7 +109,7 @@ class GPUTransformCQT(nn.Module):
         return out, None
 
 
-AUG_ZEROS, AUG_PRECISION = 64, 512                   # resampling filter: zero crossings, table points per zero crossing
+AUG_ZEROS, AUG_PRECISION = DEFINES["NSID_AUG_ZEROS"], DEFINES["NSID_AUG_PRECISION"]      # filter table: zero crossings, points each
 AUG_ROLLOFF, AUG_BETA = 0.9475937167399596, 14.769656459379492     # resampy's kaiser_best design
 AUG_CHUNK = 64                                       # clips per pass through the spectrum workspaces
 

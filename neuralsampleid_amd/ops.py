@@ -8,10 +8,11 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
+from ._lib import DEFINES as _H        # the integer #defines of include/nsid.h: every kernel constant below is read from it
 from ._lib import call, get_tuning, launch_counters, lib, reset_tuning, set_tuning  # noqa: F401  (tuning, counters: re-exported)
 
-ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_ELU = 0, 1, 2, 3
-ROW_TILE = 128
+ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_ELU = _H["NSID_ACT_NONE"], _H["NSID_ACT_RELU"], _H["NSID_ACT_LEAKY"], _H["NSID_ACT_ELU"]
+ROW_TILE = _H["NSID_ROW_TILE"]
 BN_MOMENTUM = 0.1
 BN_EPS = 1e-5
 
@@ -119,7 +120,7 @@ def _chk(*ts):
             raise RuntimeError(f"expected contiguous float32, got {t.dtype} contiguous={t.is_contiguous()}")
 
 
-F32, BF16 = 0, 1
+F32, BF16 = _H["NSID_F32"], _H["NSID_BF16"]
 
 
 def _tk(name, nbytes, fn, shape=()):
@@ -145,7 +146,7 @@ def _act(*ts) -> int:
     return code
 
 
-GEMM_FP32, GEMM_BF16 = 0, 1
+GEMM_FP32, GEMM_BF16 = _H["NSID_GEMM_FP32"], _H["NSID_GEMM_BF16"]
 
 
 def set_gemm_precision(mode: str) -> None:
@@ -894,7 +895,7 @@ class DsPrep:
     def __init__(self):
         self.entries = {}           # weight data_ptr -> dict(w, wp16, wb16, dwp, key)
 
-    MAX_LAYERS = 8                  # csrc/misc.hip DSP_LAYERS
+    MAX_LAYERS = _H["NSID_DS_PREPACK_MAX_LAYERS"]
 
     def purge(self) -> None:
         """drop the layers whose weight is gone or has moved (re-flattened by a newer optimiser): the entries of OTHER live optimisers
@@ -1188,7 +1189,7 @@ def ntxent_fwd_bwd(z_i, z_j, tau, p0=0, npairs=None, want_grad=True):
 
 
 # ------------------------------------------------------------------------------------------------ baseline objective (csrc/baseline_loss.hip)
-BL_MAX = 2048        # rows (M, or 2 B) and features of the baseline's losses
+BL_MAX = _H["NSID_BL_MAX"]        # rows (M, or 2 B) and features of the baseline's losses
 
 
 def _bl_check(name, M, d):
@@ -1272,7 +1273,7 @@ def baseline_objective_fwd_bwd(z_i, z_j, margin=0.2, beta=1.0, gamma=1.0, want_g
     return (out, dzi, dzj, _bl_mining(ws, M)) if mining else (out, dzi, dzj)
 
 
-BL_ROWS_MAX = 4096   # rows (2 Bg) of the gathered batch of baseline_objective_rows_fwd_bwd
+BL_ROWS_MAX = _H["NSID_BL_ROWS_MAX"]   # rows (2 Bg) of the gathered batch of baseline_objective_rows_fwd_bwd
 
 
 def baseline_objective_rows_fwd_bwd(z_i_all, z_j_all, p0=0, npairs=None, margin=0.2, beta=1.0, gamma=1.0, want_grad=True, mining=False,
@@ -1437,7 +1438,7 @@ def unfold_segments_ragged(pack, s0: int, nseg: int, out: torch.Tensor) -> torch
 
 # ---- waveform augmentations (csrc/augment.hip, include/nsid.h nsid_aug_*): one wrapper per stage; modules/transformations.
 # GPUWaveAugment owns the tables and the workspaces and chains the four. The extents follow the host-side rate bounds alone.
-AUG_N_FFT, AUG_HOP, AUG_BINS = 2048, 512, 1025
+AUG_N_FFT, AUG_HOP, AUG_BINS = _H["NSID_AUG_N_FFT"], _H["NSID_AUG_HOP"], _H["NSID_AUG_BINS"]
 
 
 def aug_frames_in(L: int) -> int:
@@ -1534,7 +1535,7 @@ def aug_finish(wave: torch.Tensor, B: int, L: int, mode: torch.Tensor, rate: tor
 
 # ---- the baseline's waveform effects (csrc/augment_fx.hip, include/nsid.h nsid_aug_compress / _biquad / _frames); modules/
 # transformations.GPUBaselineWaveAugment chains them with the four stages above
-AUG_FX_MAX_SECTIONS, AUG_FX_MAX_FRAMES = 64, 256
+AUG_FX_MAX_SECTIONS, AUG_FX_MAX_FRAMES = _H["NSID_AUG_FX_MAX_SECTIONS"], _H["NSID_AUG_FX_MAX_FRAMES"]
 
 
 def _aug_table(name, t, dtype, shape):
@@ -1601,7 +1602,7 @@ def aug_frames(x_i: torch.Tensor, t1: torch.Tensor, gain: torch.Tensor, mode2: t
 
 # ---- stem pairs (csrc/stems.hip, include/nsid.h nsid_resample_sinc / nsid_stem_pairs_*); modules/data.py owns the bank and the draws
 RESAMPLE_WIDTH, RESAMPLE_ROLLOFF = 6, 0.99           # torchaudio's lowpass_filter_width and rolloff defaults
-RESAMPLE_MAX_C, RESAMPLE_LDS_BYTES = 8, 64 * 1024
+RESAMPLE_MAX_C, RESAMPLE_LDS_BYTES = _H["NSID_RESAMPLE_MAX_C"], _H["NSID_RESAMPLE_LDS_BYTES"]
 _RESAMPLE_TABLES = {}                                # (orig, new, device) -> the compact table on the device
 
 
@@ -1819,7 +1820,7 @@ def rows_to_bcn(rows, B, N) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ exact flat-L2 search (csrc/search.hip)
-SEARCH_MAX_K = 64
+SEARCH_MAX_K = _H["NSID_SEARCH_MAX_K"]
 SEARCH_D_LIMITS = "d % 16 == 0 and 16 <= d <= 256, or d % 64 == 0 and 256 < d <= 2048"
 
 
@@ -1915,8 +1916,8 @@ def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ song-level vote (csrc/vote.hip)
-VOTE_MAX_CAND = 4096          # L k of a pair at most
-VOTE_MAX_TOP = 32
+VOTE_MAX_CAND = _H["NSID_VOTE_MAX_CAND"]          # L k of a pair at most
+VOTE_MAX_TOP = _H["NSID_VOTE_MAX_TOP"]
 
 
 def _vote_args(name, I, starts, lens, song_of, n_dummy, exclude, top):
@@ -2044,10 +2045,10 @@ def vote_candidates(I, n_dummy, n_ref) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ classifier re-rank (csrc/rerank.hip)
-CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = 512, 1024, 32, 64
+CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = _H["NSID_CLF_C"], _H["NSID_CLF_KP"], _H["NSID_CLF_MAX_N"], _H["NSID_CLF_QCHUNK"]
 CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
-CLF_PW = 512                            # the folded candidate block P: 4 heads x fc.0's 128, at every width
-CLF_MAX_N_EVAL = 128                    # eval-mode scoring (the _n entries: multi-tile attention); training stays at CLF_MAX_N
+CLF_PW = _H["NSID_CLF_PW"]               # the folded candidate block P: 4 heads x fc.0's 128, at every width
+CLF_MAX_N_EVAL = _H["NSID_CLF_MAX_N_EVAL"]     # eval-mode scoring (the _n entries: multi-tile attention); training stays at CLF_MAX_N
 
 
 def _clf_width(C, name) -> int:
@@ -2178,7 +2179,8 @@ def clf_pair_scores_dev(q, kp, N, tail, q_start, q_count, cand_count, cidx):
 
 
 # ------------------------------------------------------------------------------------------------ classifier training (csrc/clf_train.hip)
-CLF_HID, CLF_H, CLF_MINE_MAX_ROWS, CLF_MINE_MAX_D = 128, 4, 8192, 512
+CLF_HID, CLF_H = _H["NSID_CLF_HID"], _H["NSID_CLF_H"]
+CLF_MINE_MAX_ROWS, CLF_MINE_MAX_D = _H["NSID_CLF_MINE_MAX_ROWS"], _H["NSID_CLF_MINE_MAX_D"]
 
 
 def _clf_idx(t, name):

@@ -19,10 +19,12 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ._lib import DEFINES
+
 MAX_PACK_SAMPLES = 1 << 30           # the kernels index a song's samples with ints, the entries refuse more
 MAX_CQT_SONG = 1 << 28               # nsid_cqt's limit for one clip
-LOGMEL_RUN, CQT_TILE = 8, 32         # frames per workgroup: csrc/frontend.hip FE_RUN, csrc/cqt.hip CQ_F
-TABLE_COLS = 4                       # csrc/nsid_common.h NSID_PACK_COLS: {first sample, samples, first column, items before}
+LOGMEL_RUN, CQT_TILE = DEFINES["NSID_LOGMEL_RUN"], DEFINES["NSID_CQT_TILE"]      # frames per work item (include/nsid.h)
+TABLE_COLS = DEFINES["NSID_PACK_COLS"]                 # {first sample, samples, first column, items before}
 
 
 def front_kind(front) -> str:
