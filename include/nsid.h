@@ -679,7 +679,18 @@ int nsid_vote_candidates(const int64_t* I, long n, int n_dummy, int n_ref, int* 
  *   order (written, not accumulated).
  * clf_attn_bwd: from dobar (P x 512) = dL/dobar: dq, dk (P x N x 512) = the per-pair dL/dQ and dL/dK of the query and candidate rows.
  * clf_seg_reduce: dq_seg (nq_seg N x 512) = sum over the pairs with qi[p] == seg of dq[p]; dkv_seg (nc_seg N x 1024) = [sum dk[p] |
- *   sum abar[p] (x) dobar[p]] over the pairs with ci[p] == seg; both in pair order, zeros for a segment without pairs. */
+ *   sum abar[p] (x) dobar[p]] over the pairs with ci[p] == seg; both in pair order, zeros for a segment without pairs.
+ * clf_attn_fwd_n, clf_attn_bwd_n, clf_seg_reduce_n: the three per-pair operations for 1 <= N <= 128 nodes (training on the 256-mel
+ *   configuration's 128-node matrices and at the reference's default num_nodes = 100); arguments as the _c entries, C in {512, 640,
+ *   768, 1024}. A head's attention is nT x nT tiles of 32 x 32, nT = ceil(N / 32). Saved attention: attn (P x 4 x nT x nT x 16 x 64),
+ *   P 4 (32 nT)^2 floats (256 KB per pair at N = 128): for pair p and head h, tile (qt, kt) = queries 32 qt .., keys 32 kt .. in the
+ *   kernel's register layout (element i 64 + lane = query 32 qt + lane % 32 against key 32 kt + (i & 3) + 8 (i >> 2) + 4 (lane / 32)),
+ *   zero on keys >= N and query rows >= N. abar (P x 4 x 128): stride 128 per head, zero past N. dq, dk (P x N x C). Keys >= N get no
+ *   weight, query rows >= N no share in the column mean, which divides by N; no row at or beyond nq_seg N of q or nc_seg N of kv is
+ *   addressed. Same guarantees as above: fixed summation order, no atomics, a pair's outputs bitwise independent of the rest of the
+ *   call, an out-of-range pair skipped. N = 0, N > 128, another C, a null or misaligned pointer: NSID_EINVAL before anything is
+ *   read or launched; P = 0 (clf_seg_reduce_n: no segments) is NSID_OK with nothing launched. Launches count on their own counters
+ *   (clf_attn_fwd_n, clf_attn_bwd_n, clf_seg_reduce_n); the entries above keep their bound N <= 32, their kernels and their layouts. */
 #define NSID_CLF_MINE_MAX_ROWS 8192 /* na of clf_mine_hard_negatives at most */
 #define NSID_CLF_MINE_MAX_D 512     /* d at most */
 int nsid_clf_mine_hard_negatives(const float* zq, int nq, const float* za, int na, int d, int k, int64_t* out, void* stream);
@@ -697,6 +708,12 @@ int nsid_clf_attn_fwd_c(const float* q, int nq_seg, const float* kv, int nc_seg,
 int nsid_clf_attn_bwd_c(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N,
                         const int* qi, const int* ci, int P, float* dq, float* dk, void* stream);
 int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi, const int* ci, int P,
+                          int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream);
+int nsid_clf_attn_fwd_n(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci, int P,
+                        float* obar, float* attn, float* abar, void* stream);
+int nsid_clf_attn_bwd_n(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N,
+                        const int* qi, const int* ci, int P, float* dq, float* dk, void* stream);
+int nsid_clf_seg_reduce_n(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi, const int* ci, int P,
                           int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream);
 
 /* ---- ResNet-IBN baseline, eval-mode forward (encoder/resnet_ibn.py; simclr/triplet.py:65-83 BaselineModel). Activations are

@@ -17,8 +17,8 @@ Supported: in_dim 512, 640, 768 or 1024 (the encoder sizes 't', 's', 'm' and the
 raises before a launch. N <= 32 runs on the single-tile kernel (nsid_clf_pair_scores_c), 33 <= N <= 128 (the 256-mel configuration's
 128-node matrices; num_nodes=128, or the reference's default 100 for N <= 100) on the multi-tile one (nsid_clf_pair_scores_n); the
 dispatch is by N alone, in ops.clf_node_rows / ops.clf_pair_scores. This module's forward stays the eval-mode re-rank path and refuses training mode and grad. Training
-(downstream.py's loop) runs through neuralsampleid_amd.downstream: clf_train_scores is the training-mode forward and backward on
-csrc/clf_train.hip, and train() / train_step() drive it (N <= 32 only); the trained state_dict loads here as it is."""
+(downstream.py's loop) runs through neuralsampleid_amd.downstream: clf_train_scores_n is the training-mode forward and backward on
+csrc/clf_train.hip, and train() / train_step() drive it (N <= 128, the same dispatch by N); the trained state_dict loads here as it is."""
 import math
 
 import numpy as np

@@ -18,6 +18,8 @@
 //
 // Nodes: N <= 32 (CLF_TILE), one 32 x 32 tile per head. The tile arithmetic (register map, masked softmax, column sums) and the
 // width dispatch are clf_common.h's, shared with the evaluation kernels, so a trained state scores there what it scores here.
+// 1 <= N <= 128 (the _n entries): the *_wide_kernel forms below run a head's attention as up to 4 x 4 such tiles with the same
+// tile arithmetic; saved attention (P, 4, nT, nT, 16, 64), nT = ceil(N / 32), abar (P, 4, 128).
 #include "clf_common.h"
 
 namespace {
@@ -25,6 +27,9 @@ namespace {
 constexpr int CT_MINE_MAXN = NSID_CLF_MINE_MAX_ROWS;   // rows of the mining pool (2B) at most: their dots live in LDS
 constexpr int CT_MINE_MAXD = NSID_CLF_MINE_MAX_D;
 constexpr int CT_RED_THREADS = 512;  // nsid_clf_seg_reduce: one workgroup per segment, C / 64 float4 per thread cover N x C
+constexpr int CW_N = NSID_CLF_MAX_N_EVAL;   // nodes at most of the _n entries (the multi-tile kernels)
+constexpr int CW_T = CW_N / CLF_TILE;       // tiles per side at most
+static_assert(CW_T == 4, "one wave of a workgroup per query / key tile");
 
 // ------------------------------------------------------------------------------------------------ hard-negative mining
 // (v, j) precedes (w, k) in the descending order with ties to the smaller index
@@ -146,6 +151,112 @@ __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restri
       if (DH % 64 == 0 || 64 * t + lane < DH) obar[(size_t)p * CT_C + h * CT_DH + 64 * t + lane] = o[t];
     __builtin_amdgcn_wave_barrier();
   }
+}
+
+// ---- 1 <= N <= 128 (nsid_clf_attn_fwd_n): a head's attention is nT x nT tiles of 32 x 32, nT = ceil(N / 32) ----------------------------
+// One workgroup per pair, wave h = head h (the heads write disjoint columns of obar). Per query tile the wave holds S^T against
+// every key tile (4 x 16 accumulators, K and Q fragments streamed from global memory as in rerank.hip's clf_pair_wide_kernel), so
+// a row's max and sum stay in registers; the column sums of a key tile accumulate over the query tiles in tile order. Saved
+// attention: (P, 4, nT, nT, 16, 64), tile (qt, kt) of a head in the register layout above (zero on keys >= N and query rows >= N).
+// abar (P, 4, 128), zero past N. No row >= N of a segment is addressed.
+template <int C, int DH>
+__global__ __launch_bounds__(256) void clf_attn_fwd_wide_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kv,
+                                                                int nc_seg, int N, const int* __restrict__ qi,
+                                                                const int* __restrict__ ci, int P, float* __restrict__ obar,
+                                                                float* __restrict__ attn, float* __restrict__ abar) {
+  static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels; K and Q are loaded four k-steps of 8 at a time");
+  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;        // [K | V] rows
+  constexpr int OB = (DH + 63) / 64;                         // 64-column blocks of a head's output
+  __shared__ float abs_[CLF_H][CW_N];
+  const int lane = lane_id(), h = threadIdx.x >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int p = blockIdx.x;                                  // the grid is P workgroups
+  const int qseg = qi[p], cseg = ci[p];
+  if (qseg < 0 || qseg >= nq_seg || cseg < 0 || cseg >= nc_seg) return;      // uniform over the workgroup
+  const float scale = clf_scale<DH>::v;
+  const float invN = 1.0f / (float)N;
+  const int nT = (N + CLF_TILE - 1) / CLF_TILE;
+  const float* qh = q + (size_t)qseg * N * CT_C + h * CT_DH + 4 * hh;
+  const float* kh = kv + (size_t)cseg * N * CT_KV + h * CT_DH + 4 * hh;
+  const float* vb = kv + (size_t)cseg * N * CT_KV + CT_C + h * CT_DH;
+  float* ap = attn + ((size_t)p * CLF_H + h) * nT * nT * (16 * 64) + lane;
+  const int jf = clf_lane_key(r, hh);
+
+  float cs[CW_T] = {0.f, 0.f, 0.f, 0.f};           // column sums of the key tiles (even lanes: key 32 kt + jf)
+#pragma unroll 1
+  for (int qt = 0; qt < nT; ++qt) {
+    const int qrow = CLF_TILE * qt + r;
+    const bool qok = qrow < N;
+    const float* qp = qh + (size_t)(qok ? qrow : 0) * CT_C;
+    f32x16 acc[CW_T] = {};
+#pragma unroll 1
+    for (int b0 = 0; b0 < CT_DH / 8; b0 += 4) {
+      f32x4 qb[4], ka[CW_T][4];
+#pragma unroll
+      for (int bb = 0; bb < 4; ++bb) qb[bb] = qok ? ld4(qp + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kt = 0; kt < CW_T; ++kt) {
+        if (kt < nT) {
+          const int krow = CLF_TILE * kt + r;
+          const float* kr = kh + (size_t)(krow < N ? krow : 0) * CT_KV;
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb) ka[kt][bb] = krow < N ? ld4(kr + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+#pragma unroll
+      for (int kt = 0; kt < CW_T; ++kt) {
+        if (kt < nT) {
+#pragma unroll
+          for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+              acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kt][bb][e], qb[bb][e], acc[kt], 0, 0, 0);
+        }
+      }
+    }
+    float mx = -__builtin_inff();
+#pragma unroll
+    for (int kt = 0; kt < CW_T; ++kt)
+      if (kt < nT) mx = clf_tile_max<true>(acc[kt], CLF_TILE * kt, hh, N, scale, mx);
+    mx = clf_half_max(mx);
+    float sum = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < CW_T; ++kt)
+      if (kt < nT) sum = clf_tile_exp<true>(acc[kt], acc[kt], CLF_TILE * kt, hh, N, scale, mx, sum);
+    sum = clf_half_sum(sum);
+#pragma unroll
+    for (int kt = 0; kt < CW_T; ++kt) {
+      if (kt < nT) {
+        float v[16];
+        clf_tile_norm(acc[kt], v, qok, sum);
+        float* at = ap + (size_t)(qt * nT + kt) * (16 * 64);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) at[i * 64] = v[i];
+        cs[kt] += clf_colsum(v, r);
+      }
+    }
+  }
+  if ((r & 1) == 0) {
+#pragma unroll
+    for (int kt = 0; kt < CW_T; ++kt) {
+      const float a = kt < nT ? cs[kt] * invN : 0.f;
+      abs_[h][CLF_TILE * kt + jf] = a;
+      abar[((size_t)p * CLF_H + h) * CW_N + CLF_TILE * kt + jf] = a;
+    }
+  }
+  __builtin_amdgcn_wave_barrier();
+  float o[OB];
+#pragma unroll
+  for (int t = 0; t < OB; ++t) o[t] = 0.f;
+  for (int m = 0; m < N; ++m) {
+    const float a = abs_[h][m];
+#pragma unroll
+    for (int t = 0; t < OB; ++t)
+      if (DH % 64 == 0 || 64 * t + lane < DH) o[t] = fmaf(a, vb[(size_t)m * CT_KV + 64 * t + lane], o[t]);
+  }
+#pragma unroll
+  for (int t = 0; t < OB; ++t)
+    if (DH % 64 == 0 || 64 * t + lane < DH) obar[(size_t)p * CT_C + h * CT_DH + 64 * t + lane] = o[t];
 }
 
 // ------------------------------------------------------------------------------------------------ head: relu, dropout, fc.3, sigmoid
@@ -310,16 +421,155 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
   }
 }
 
+// ---- 1 <= N <= 128 (nsid_clf_attn_bwd_n) ---------------------------------------------------------------------------------------------
+// One workgroup of four waves per (pair, head). Wave w first forms da of key tile w into LDS. After a barrier wave qt (< nT) reloads
+// the saved tiles (qt, *), takes t = rowsum(A o da) over all key tiles in tile order, forms dS = A o (da - t) / sqrt(dh) in the
+// forward's register layout, leaves it in the LDS plane dS[query][key] (128 x 129 floats) and writes its dQ rows, dS K over all
+// keys, once. After the second barrier wave kt (< nT) reads its key columns of the plane (key on the lane) and writes the dK rows of
+// key tile kt, the query tiles summed in tile order inside the accumulators. No wave leaves ahead of a barrier: a skipped pair is
+// skipped by the whole workgroup. Rows >= N are neither read nor written.
+template <int C, int DH>
+__global__ __launch_bounds__(256) void clf_attn_bwd_wide_kernel(const float* __restrict__ dobar, const float* __restrict__ attn,
+                                                                const float* __restrict__ q, int nq_seg, const float* __restrict__ kv,
+                                                                int nc_seg, int N, const int* __restrict__ qi,
+                                                                const int* __restrict__ ci, int P, float* __restrict__ dq,
+                                                                float* __restrict__ dk) {
+  static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels");
+  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C, HALF = DH / 2;
+  __shared__ float dsp[CW_N][CW_N + 1];                      // dS[query][key] of the head
+  __shared__ float das[CW_N];
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int r = lane & 31, hh = lane >> 5;
+  const int p = (int)(blockIdx.x >> 2), h = (int)(blockIdx.x & 3);      // the grid is 4 P workgroups
+  const int qseg = qi[p], cseg = ci[p];
+  if (qseg < 0 || qseg >= nq_seg || cseg < 0 || cseg >= nc_seg) return;      // uniform over the workgroup, ahead of every barrier
+  const float scale = clf_scale<DH>::v;
+  const float invN = 1.0f / (float)N;
+  const int nT = (N + CLF_TILE - 1) / CLF_TILE;
+  const float* qrow = q + (size_t)qseg * N * CT_C + h * CT_DH;              // Q_h of the query segment (row stride C)
+  const float* krow = kv + (size_t)cseg * N * CT_KV + h * CT_DH;            // K_h of the candidate (row stride 2 C)
+  const float* dop = dobar + (size_t)p * CT_C + h * CT_DH;
+  float* dqp = dq + (size_t)p * N * CT_C + h * CT_DH;
+  float* dkp = dk + (size_t)p * N * CT_C + h * CT_DH;
+
+  {  // da[key] = V_h[key] . do_h / N for the keys of tile w: half hh of the DH dims on each lane half, halves added in one order
+    const int key = CLF_TILE * w + r;
+    const bool kin = key < N;
+    float part = 0.f;
+    if (kin) {
+      const float* vr = krow + (size_t)key * CT_KV + CT_C + HALF * hh;
+      const float* dr = dop + HALF * hh;
+#pragma unroll 4
+      for (int e = 0; e < HALF; e += 4) {
+        const f32x4 a = ld4(vr + e), b = ld4(dr + e);
+        part = fmaf(a[0], b[0], part);
+        part = fmaf(a[1], b[1], part);
+        part = fmaf(a[2], b[2], part);
+        part = fmaf(a[3], b[3], part);
+      }
+    }
+    const float other = __shfl_xor(part, 32);
+    const float da = hh == 0 ? part + other : other + part;
+    if (hh == 0) das[key] = kin ? da * invN : 0.f;
+  }
+  __syncthreads();
+
+  if (w < nT) {
+    const int qt = w;
+    const float* ap = attn + (((size_t)p * CLF_H + h) * nT + qt) * nT * (16 * 64) + lane;
+    float dS[CW_T][16];
+    float t = 0.f;
+#pragma unroll
+    for (int kt = 0; kt < CW_T; ++kt) {
+      if (kt < nT) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          dS[kt][i] = ap[(size_t)kt * (16 * 64) + i * 64];
+          t = fmaf(dS[kt][i], das[CLF_TILE * kt + acc_row(i, hh)], t);
+        }
+      }
+    }
+    const float to = __shfl_xor(t, 32);
+    const float tr = hh == 0 ? t + to : to + t;          // rowsum over all keys of query 32 qt + r
+#pragma unroll
+    for (int kt = 0; kt < CW_T; ++kt) {
+      if (kt < nT) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int key = CLF_TILE * kt + acc_row(i, hh);
+          dS[kt][i] = dS[kt][i] * (das[key] - tr) * scale;
+          dsp[CLF_TILE * qt + r][key] = dS[kt][i];
+        }
+      }
+    }
+    // dQ[query][d0 + c] = sum_key dS[query][key] K[key][d0 + c]; step (kt, s): k index hh = key 32 kt + acc_row(s, hh)
+#pragma unroll 1
+    for (int d0 = 0; d0 < CT_DH; d0 += 32) {
+      f32x16 acc = {};
+#pragma unroll
+      for (int kt = 0; kt < CW_T; ++kt) {
+        if (kt < nT) {
+#pragma unroll
+          for (int s = 0; s < 16; ++s) {
+            const int key = CLF_TILE * kt + acc_row(s, hh);
+            const float kb = key < N ? krow[(size_t)key * CT_KV + d0 + r] : 0.f;
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dS[kt][s], kb, acc, 0, 0, 0);
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = CLF_TILE * qt + acc_row(i, hh);
+        if (row < N) dqp[(size_t)row * CT_C + d0 + r] = acc[i];
+      }
+    }
+  }
+  __syncthreads();
+
+  if (w < nT) {
+    const int kt = w;
+    // dK[key][d0 + c] = sum_query dS[query][key] Q[query][d0 + c]; step (qt, s): k index hh = query 32 qt + 2 s + hh
+    float dT[CW_T][16];
+#pragma unroll
+    for (int qt = 0; qt < CW_T; ++qt) {
+      if (qt < nT) {
+#pragma unroll
+        for (int s = 0; s < 16; ++s) dT[qt][s] = dsp[CLF_TILE * qt + 2 * s + hh][CLF_TILE * kt + r];
+      }
+    }
+#pragma unroll 1
+    for (int d0 = 0; d0 < CT_DH; d0 += 32) {
+      f32x16 acc = {};
+#pragma unroll
+      for (int qt = 0; qt < CW_T; ++qt) {
+        if (qt < nT) {
+#pragma unroll
+          for (int s = 0; s < 16; ++s) {
+            const int qn = CLF_TILE * qt + 2 * s + hh;
+            const float qb = qn < N ? qrow[(size_t)qn * CT_C + d0 + r] : 0.f;
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(dT[qt][s], qb, acc, 0, 0, 0);
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int row = CLF_TILE * kt + acc_row(i, hh);
+        if (row < N) dkp[(size_t)row * CT_C + d0 + r] = acc[i];
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ per-segment sums
 // One workgroup per segment: blocks [0, nq_seg) sum dQ_p over the pairs with qi[p] == seg, blocks [nq_seg, nq_seg + nc_seg) sum
 // dK_p and dV_p = a_h (x) do_h over the pairs with ci[p] == seg. The pair list is scanned in chunks of 512 (a ballot per wave), the
 // matches are added in pair order; a segment with no pairs gets zeros.
-template <int C, int DH>
-__global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const float* __restrict__ dq, const float* __restrict__ dk,
-                                                                        const float* __restrict__ abar, const float* __restrict__ dobar,
-                                                                        const int* __restrict__ qi, const int* __restrict__ ci, int P,
-                                                                        int N, int nq_seg, float* __restrict__ dq_seg,
-                                                                        float* __restrict__ dkv_seg) {
+// The workgroup sums rows [n0, n0 + rows) of its segment, rows <= 32 (the float4 budget of a thread); abar has ABAR_LD floats per head.
+template <int C, int DH, int ABAR_LD>
+__device__ __forceinline__ void clf_seg_reduce_rows(const float* __restrict__ dq, const float* __restrict__ dk,
+                                                    const float* __restrict__ abar, const float* __restrict__ dobar,
+                                                    const int* __restrict__ qi, const int* __restrict__ ci, int P, int N, int nq_seg,
+                                                    float* __restrict__ dq_seg, float* __restrict__ dkv_seg, int n0, int rows) {
   static_assert(C == CLF_H * DH && DH % 4 == 0 && (CLF_TILE * C) % (4 * CT_RED_THREADS) == 0, "4 heads of DH channels");
   constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;
   __shared__ uint64_t masks[CT_RED_THREADS / 64];
@@ -327,7 +577,7 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
   const bool isq = (int)blockIdx.x < nq_seg;
   const int seg = isq ? (int)blockIdx.x : (int)blockIdx.x - nq_seg;
   const int* idx = isq ? qi : ci;
-  const int nel = N * CT_C;                                  // elements of one segment's gradient (a multiple of 128)
+  const int nel = rows * CT_C;                               // elements of the workgroup's rows (a multiple of 128)
   constexpr int U = CLF_TILE * CT_C / (4 * CT_RED_THREADS);      // float4 per thread
   f32x4 acc[U], accv[U];
 #pragma unroll
@@ -346,7 +596,7 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
         const int b = __builtin_ctzll(mm);
         mm &= mm - 1;
         const int p = base + 64 * ww + b;
-        const float* sp = src + (size_t)p * nel;
+        const float* sp = src + ((size_t)p * N + n0) * CT_C;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int e = 4 * (tid + CT_RED_THREADS * u);
@@ -358,7 +608,7 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
             const int e = 4 * (tid + CT_RED_THREADS * u);
             if (e < nel) {
               const int n = e / CT_C, c = e % CT_C;
-              const float a = abar[((size_t)p * CLF_H + c / CT_DH) * CLF_TILE + n];
+              const float a = abar[((size_t)p * CLF_H + c / CT_DH) * ABAR_LD + n0 + n];
               const f32x4 d = ld4(dobar + (size_t)p * CT_C + c);
 #pragma unroll
               for (int x = 0; x < 4; ++x) accv[u][x] = fmaf(a, d[x], accv[u][x]);
@@ -373,7 +623,7 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
   for (int u = 0; u < U; ++u) {
     const int e = 4 * (tid + CT_RED_THREADS * u);
     if (e >= nel) continue;
-    const int n = e / CT_C, c = e % CT_C;
+    const int n = n0 + e / CT_C, c = e % CT_C;
     if (isq) {
       *reinterpret_cast<f32x4*>(dq_seg + ((size_t)seg * N + n) * CT_C + c) = acc[u];
     } else {
@@ -382,6 +632,26 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const fl
       *reinterpret_cast<f32x4*>(o + CT_C) = accv[u];
     }
   }
+}
+
+template <int C, int DH>
+__global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_kernel(const float* __restrict__ dq, const float* __restrict__ dk,
+                                                                        const float* __restrict__ abar, const float* __restrict__ dobar,
+                                                                        const int* __restrict__ qi, const int* __restrict__ ci, int P,
+                                                                        int N, int nq_seg, float* __restrict__ dq_seg,
+                                                                        float* __restrict__ dkv_seg) {
+  clf_seg_reduce_rows<C, DH, CLF_TILE>(dq, dk, abar, dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg, 0, N);
+}
+
+// nsid_clf_seg_reduce_n: grid (segments, node tiles); workgroup (seg, t) owns rows [32 t, min(N, 32 t + 32)) of its segment
+template <int C, int DH>
+__global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_wide_kernel(const float* __restrict__ dq, const float* __restrict__ dk,
+                                                                             const float* __restrict__ abar,
+                                                                             const float* __restrict__ dobar, const int* __restrict__ qi,
+                                                                             const int* __restrict__ ci, int P, int N, int nq_seg,
+                                                                             float* __restrict__ dq_seg, float* __restrict__ dkv_seg) {
+  const int n0 = CLF_TILE * (int)blockIdx.y;
+  clf_seg_reduce_rows<C, DH, CW_N>(dq, dk, abar, dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg, n0, min(CLF_TILE, N - n0));
 }
 
 }  // namespace
@@ -470,4 +740,43 @@ extern "C" int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const flo
 extern "C" int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
                                    const int* ci, int P, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream) {
   return nsid_clf_seg_reduce_c(dq, dk, abar, dobar, qi, ci, P, NSID_CLF_C, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
+}
+
+// ---- the _n entries: 1 <= N <= 128, the multi-tile kernels; arguments as the _c entries
+extern "C" int nsid_clf_attn_fwd_n(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
+                                   int P, float* obar, float* attn, float* abar, void* stream) {
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CW_N && P >= 0 && P <= (1 << 28));
+  if (P == 0) return NSID_OK;
+  NSID_REQUIRE(q && kv && qi && ci && obar && attn && abar && nsid_aligned16(q) && nsid_aligned16(kv));
+  nsid_count(NSID_C_clf_attn_fwd_n);
+  CLF_LAUNCH_C(C, clf_attn_fwd_wide_kernel, dim3(P), dim3(256), static_cast<hipStream_t>(stream), q, nq_seg, kv, nc_seg, N, qi, ci, P,
+               obar, attn, abar);
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_clf_attn_bwd_n(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
+                                   int C, int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CW_N && P >= 0 && P <= (1 << 28));
+  if (P == 0) return NSID_OK;
+  NSID_REQUIRE(dobar && attn && q && kv && qi && ci && dq && dk && nsid_aligned16(dobar) && nsid_aligned16(kv));
+  nsid_count(NSID_C_clf_attn_bwd_n);
+  CLF_LAUNCH_C(C, clf_attn_bwd_wide_kernel, dim3(4u * (unsigned)P), dim3(256), static_cast<hipStream_t>(stream), dobar, attn, q,
+               nq_seg, kv, nc_seg, N, qi, ci, P, dq, dk);
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_clf_seg_reduce_n(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
+                                     const int* ci, int P, int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg,
+                                     void* stream) {
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(P >= 0 && P <= (1 << 28) && N >= 1 && N <= CW_N && nq_seg >= 0 && nc_seg >= 0 && nq_seg + nc_seg <= (1 << 30));
+  if (nq_seg + nc_seg == 0) return NSID_OK;
+  NSID_REQUIRE((P == 0 || (dq && dk && abar && dobar && qi && ci)) && dq_seg && dkv_seg);
+  NSID_REQUIRE(nsid_aligned16(dq) && nsid_aligned16(dk) && nsid_aligned16(dobar) && nsid_aligned16(dq_seg) && nsid_aligned16(dkv_seg));
+  nsid_count(NSID_C_clf_seg_reduce_n);
+  CLF_LAUNCH_C(C, clf_seg_reduce_wide_kernel, dim3(nq_seg + nc_seg, (N + CLF_TILE - 1) / CLF_TILE), dim3(CT_RED_THREADS),
+               static_cast<hipStream_t>(stream), dq, dk, abar, dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg);
+  return nsid_launch_status();
 }

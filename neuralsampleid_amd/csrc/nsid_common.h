@@ -237,6 +237,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(clf_node_rows) X(clf_pair_scores)           /* rerank.hip: classifier re-rank pair scores */ \
   X(clf_node_rows_n) X(clf_pair_scores_n)       /* rerank.hip: the same at up to 128 nodes (multi-tile attention) */ \
   X(clf_mine) X(clf_attn_fwd) X(clf_head_fwd) X(clf_head_bwd) X(clf_attn_bwd) X(clf_seg_reduce)   /* clf_train.hip: classifier training */ \
+  X(clf_attn_fwd_n) X(clf_attn_bwd_n) X(clf_seg_reduce_n)   /* clf_train.hip: the same at up to 128 nodes (multi-tile attention) */ \
   X(logmel_fft)           /* frontend.hip: batched log-mel front end in one launch */ \
   X(cqt)                  /* cqt.hip: batched constant-Q front end in one launch */ \
   X(aug_stft) X(aug_vocoder) X(aug_istft) X(aug_finish)   /* augment.hip: waveform augmentations, one launch per stage */ \

@@ -10,7 +10,7 @@ the frozen encoder, on the MI355X (csrc/clf_train.hip).
 Per batch, as the reference: the frozen encoder's pre-projection node matrices and normalised projections of both views (one eval
 pass per view: encode_pairs), ranks 1..k of z_i z_all^T as hard negatives (mine_hard_negatives), B positive pairs (x_i[p], x_j[p])
 and kB negative pairs (x_i[p mod B], x_all[hn.view(-1)[p]]) (pair_lists), the classifier's scores in training mode
-(clf_train_scores), BCE(pos) + BCE(neg), backward, and the optimiser / GradScaler step. The classifier's forward and backward run
+(clf_train_scores_n: up to 128 nodes per segment; clf_train_scores is its N <= 32 form), BCE(pos) + BCE(neg), backward, and the optimiser / GradScaler step. The classifier's forward and backward run
 as one autograd op over segments and pair lists: Q is projected once per query segment and [K | V] once per candidate segment, and
 the per-pair attention, the head and their backward are HIP kernels; the projections and the tail's linears are the project's fp32
 GEMMs. Training never goes through classifier(x_i, x_j), which stays the eval-mode re-rank forward (classifier.py)."""
@@ -23,7 +23,8 @@ import torch.nn as nn
 from . import ops
 from .classifier import CrossAttentionClassifier
 
-__all__ = ["encode_pairs", "mine_hard_negatives", "pair_lists", "draw_keep", "clf_train_scores", "train_step", "train"]
+__all__ = ["encode_pairs", "mine_hard_negatives", "pair_lists", "draw_keep", "clf_train_scores", "clf_train_scores_n", "train_step",
+           "train"]
 
 
 # ------------------------------------------------------------------------------------------------ features
@@ -119,12 +120,14 @@ class _TrainScores(torch.autograd.Function):
     def forward(ctx, nodes_q, nodes_c, qi, ci, keep, pos, w_in, b_in, w_o, b_o, w1, b1, w2, b2):
         C = w_o.shape[0]                    # the classifier's in_dim (checked by clf_train_scores)
         N = nodes_q.shape[2]
+        wide = N > ops.CLF_MAX_N            # 33 .. 128 nodes: the multi-tile entries (clf_node_rows dispatches on N itself)
+        attn_fwd = ops.clf_attn_fwd_n if wide else ops.clf_attn_fwd
         with _Fp32Gemm():
             xq = ops.clf_node_rows(nodes_q, pos)
             xc = ops.clf_node_rows(nodes_c, pos)
             q = _linear(xq, w_in[:C], b_in[:C])
             kv = _linear(xc, w_in[C:], b_in[C:])
-            obar, attn, abar = ops.clf_attn_fwd(q, kv, N, qi, ci)
+            obar, attn, abar = attn_fwd(q, kv, N, qi, ci)
             m = _linear(obar, w_o, b_o)
             hid = _linear(m, w1, b1)
             s = ops.clf_head_fwd(hid, keep, w2.reshape(-1), b2)
@@ -138,6 +141,8 @@ class _TrainScores(torch.autograd.Function):
         N, Sq, Sc = ctx.dims
         C = w_o.shape[0]
         P = s.shape[0]
+        wide = N > ops.CLF_MAX_N
+        attn_bwd, seg_reduce = (ops.clf_attn_bwd_n, ops.clf_seg_reduce_n) if wide else (ops.clf_attn_bwd, ops.clf_seg_reduce)
         ds = ds.reshape(-1).float().contiguous()
         with _Fp32Gemm():
             dh, _, dw2, db2 = ops.clf_head_bwd(ds, s, hid, keep, w2.reshape(-1))
@@ -145,20 +150,20 @@ class _TrainScores(torch.autograd.Function):
             dm = ops.linear_bwd_data(dh, w1, P, ops.CLF_HID, C)
             dwo, dbo = _wgrad(dm, obar, C)
             dobar = ops.linear_bwd_data(dm, w_o, P, C, C)
-            dq, dk = ops.clf_attn_bwd(dobar, attn, q, kv, N, qi, ci)
-            dq_seg, dkv_seg = ops.clf_seg_reduce(dq, dk, abar, dobar, qi, ci, N, Sq, Sc)
+            dq, dk = attn_bwd(dobar, attn, q, kv, N, qi, ci)
+            dq_seg, dkv_seg = seg_reduce(dq, dk, abar, dobar, qi, ci, N, Sq, Sc)
             dwq, dbq = _wgrad(dq_seg, xq, C)
             dwkv, dbkv = _wgrad(dkv_seg, xc, 2 * C)
         return (None, None, None, None, None, None, torch.cat([dwq, dwkv], 0), torch.cat([dbq, dbkv], 0), dwo, dbo, dw1, db1,
                 dw2.view(1, -1), db2)
 
 
-def _host_index(a, name):
+def _host_index(a, name, fn="clf_train_scores"):
     if isinstance(a, torch.Tensor):
         a = a.detach().cpu().numpy()
     a = np.asarray(a)
     if a.dtype.kind not in "iu":
-        raise ValueError(f"clf_train_scores: {name} must hold integers, got {a.dtype}")
+        raise ValueError(f"{fn}: {name} must hold integers, got {a.dtype}")
     return a.astype(np.int64).reshape(-1)
 
 
@@ -167,31 +172,46 @@ def clf_train_scores(classifier: CrossAttentionClassifier, nodes_q, nodes_c, q_i
     parameters (attn.in_proj_*, attn.out_proj.*, fc.0.*, fc.3.*). nodes_q (Sq, C, N), nodes_c (Sc, C, N), C = the classifier's in_dim
     (512, 640, 768 or 1024): fp32 contiguous device node matrices that do not require grad (the encoder is frozen). q_idx, c_idx: integer sequences of length P (host or device; they
     are checked on the host). keep (P, 128): the dropout keep mask scaled by 1 / (1 - p) (draw_keep); all ones = no dropout. The
-    classifier's own forward (eval-mode re-rank) is not used."""
+    classifier's own forward (eval-mode re-rank) is not used. N <= 32 (one attention tile per head); clf_train_scores_n is the
+    entry for larger graphs."""
+    return _train_scores("clf_train_scores", ops.CLF_MAX_N, classifier, nodes_q, nodes_c, q_idx, c_idx, keep)
+
+
+def clf_train_scores_n(classifier: CrossAttentionClassifier, nodes_q, nodes_c, q_idx, c_idx, keep) -> torch.Tensor:
+    """clf_train_scores for 1 <= N <= ops.CLF_MAX_N_EVAL (128) nodes, same contract: N <= 32 runs the one-tile kernels (the same
+    launches and bits as clf_train_scores), 33 .. 128 the multi-tile ones (nsid_clf_attn_fwd_n, _bwd_n, nsid_clf_seg_reduce_n), as
+    classifier.pair_scores dispatches in evaluation. The saved attention is 16 (32 ceil(N / 32))^2 bytes per pair (256 KB at
+    N = 128) and the per-pair dQ, dK 8 N C bytes, held until the backward has run."""
+    return _train_scores("clf_train_scores_n", ops.CLF_MAX_N_EVAL, classifier, nodes_q, nodes_c, q_idx, c_idx, keep)
+
+
+def _train_scores(fn, max_n, classifier, nodes_q, nodes_c, q_idx, c_idx, keep):
+    """the checks of clf_train_scores / clf_train_scores_n (fn, for the messages; max_n nodes at most) and the autograd op"""
     classifier._check_module()
     if classifier.attn.dropout != 0.0:
-        raise NotImplementedError("clf_train_scores: attention dropout is not supported (the reference's is 0)")
-    N = classifier._check_nodes(nodes_q, "clf_train_scores nodes_q")
-    if N > ops.CLF_MAX_N:
-        raise ValueError(f"clf_train_scores: N = {N} nodes: eval-mode scoring covers N <= {ops.CLF_MAX_N_EVAL}, training covers "
-                         f"N <= {ops.CLF_MAX_N} only")
-    if classifier._check_nodes(nodes_c, "clf_train_scores nodes_c") != N:
-        raise ValueError(f"clf_train_scores: query and candidate node counts differ ({N} vs {nodes_c.shape[2]})")
+        raise NotImplementedError(f"{fn}: attention dropout is not supported (the reference's is 0)")
+    N = classifier._check_nodes(nodes_q, f"{fn} nodes_q")
+    if N > max_n:
+        raise ValueError(f"{fn}: N = {N} nodes: eval-mode scoring covers N <= {ops.CLF_MAX_N_EVAL}, training covers "
+                         + (f"N <= {ops.CLF_MAX_N} only here; clf_train_scores_n is the entry for graphs of up to {ops.CLF_MAX_N_EVAL}"
+                            if max_n < ops.CLF_MAX_N_EVAL else f"N <= {max_n} only"))
+    if classifier._check_nodes(nodes_c, f"{fn} nodes_c") != N:
+        raise ValueError(f"{fn}: query and candidate node counts differ ({N} vs {nodes_c.shape[2]})")
     if nodes_q.requires_grad or nodes_c.requires_grad:
-        raise ValueError("clf_train_scores: node matrices must not require grad (the encoder is frozen; inputs get no gradient)")
-    qi, ci = _host_index(q_idx, "q_idx"), _host_index(c_idx, "c_idx")
+        raise ValueError(f"{fn}: node matrices must not require grad (the encoder is frozen; inputs get no gradient)")
+    qi, ci = _host_index(q_idx, "q_idx", fn), _host_index(c_idx, "c_idx", fn)
     P = qi.size
     if ci.size != P or P == 0:
-        raise ValueError(f"clf_train_scores: q_idx and c_idx must have the same nonzero length, got {qi.size}, {ci.size}")
+        raise ValueError(f"{fn}: q_idx and c_idx must have the same nonzero length, got {qi.size}, {ci.size}")
     Sq, Sc = nodes_q.shape[0], nodes_c.shape[0]
     if qi.min() < 0 or qi.max() >= Sq or ci.min() < 0 or ci.max() >= Sc:
-        raise ValueError(f"clf_train_scores: indices must lie in [0, {Sq}) (queries) and [0, {Sc}) (candidates)")
+        raise ValueError(f"{fn}: indices must lie in [0, {Sq}) (queries) and [0, {Sc}) (candidates)")
     if P > (1 << 28) or max(Sq, Sc) * N >= (1 << 31):
-        raise ValueError("clf_train_scores: too many pairs or segments for one call")
+        raise ValueError(f"{fn}: too many pairs or segments for one call")
     if not isinstance(keep, torch.Tensor) or keep.dtype != torch.float32 or not keep.is_cuda or not keep.is_contiguous():
-        raise ValueError("clf_train_scores: keep must be a contiguous float32 device tensor")
+        raise ValueError(f"{fn}: keep must be a contiguous float32 device tensor")
     if tuple(keep.shape) != (P, ops.CLF_HID):
-        raise ValueError(f"clf_train_scores: keep must be ({P}, {ops.CLF_HID}), got {tuple(keep.shape)}")
+        raise ValueError(f"{fn}: keep must be ({P}, {ops.CLF_HID}), got {tuple(keep.shape)}")
     dev = nodes_q.device
     qt = torch.from_numpy(qi.astype(np.int32)).to(dev)
     ct = torch.from_numpy(ci.astype(np.int32)).to(dev)
@@ -217,7 +237,7 @@ def train_step(classifier, optimizer, scaler, nodes_i, nodes_j, z_i, z_j, num_ne
     if keep is None:
         keep = draw_keep(P, classifier.fc[2].p, nodes_i.device)
     nodes_all = torch.cat((nodes_i, nodes_j), dim=0)
-    scores = clf_train_scores(classifier, nodes_i, nodes_all, q_idx, c_idx, keep)
+    scores = clf_train_scores_n(classifier, nodes_i, nodes_all, q_idx, c_idx, keep)
     logits_pos, logits_neg = scores[:B], scores[B:]
     pos_labels = torch.ones(logits_pos.shape[0], 1, device=scores.device)
     neg_labels = torch.zeros(logits_neg.shape[0], 1, device=scores.device)

@@ -2048,7 +2048,7 @@ def vote_candidates(I, n_dummy, n_ref) -> torch.Tensor:
 CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = _H["NSID_CLF_C"], _H["NSID_CLF_KP"], _H["NSID_CLF_MAX_N"], _H["NSID_CLF_QCHUNK"]
 CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
 CLF_PW = _H["NSID_CLF_PW"]               # the folded candidate block P: 4 heads x fc.0's 128, at every width
-CLF_MAX_N_EVAL = _H["NSID_CLF_MAX_N_EVAL"]     # eval-mode scoring (the _n entries: multi-tile attention); training stays at CLF_MAX_N
+CLF_MAX_N_EVAL = _H["NSID_CLF_MAX_N_EVAL"]     # the _n entries (multi-tile attention), evaluation and training; the others stay at CLF_MAX_N
 
 
 def _clf_width(C, name) -> int:
@@ -2207,11 +2207,11 @@ def clf_mine_hard_negatives(zq, za, k) -> torch.Tensor:
     return out
 
 
-def _clf_qkv_width(q, kv, N, name) -> int:
+def _clf_qkv_width(q, kv, N, name, max_n=CLF_MAX_N) -> int:
     """C of Q rows (S N, C) and [K | V] rows (S N, 2 C), checked against the supported widths before any launch"""
     N = int(N)
-    if not 1 <= N <= CLF_MAX_N:
-        raise ValueError(f"{name}: N = {N} is outside [1, {CLF_MAX_N}]")
+    if not 1 <= N <= max_n:
+        raise ValueError(f"{name}: N = {N} is outside [1, {max_n}]")
     if q.dim() != 2 or kv.dim() != 2 or kv.shape[1] % 2:
         raise ValueError(f"{name}: expected q (S N, C) and kv (S N, 2 C), got {tuple(q.shape)}, {tuple(kv.shape)}")
     C = _clf_width(kv.shape[1] // 2, name)
@@ -2307,6 +2307,81 @@ def clf_seg_reduce(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
     _tk("clf_seg_reduce_kernel", float(P) * (8.0 * N * C + 4.0 * C) + 4.0 * (nq_seg + nc_seg) * (P + N * C)
         + 4.0 * nc_seg * N * C, lambda: call(
             "nsid_clf_seg_reduce_c", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, C, N, nq_seg, nc_seg, _p(dq_seg),
+            _p(dkv_seg), _stream()), (P, N, nq_seg + nc_seg, 1))
+    return dq_seg, dkv_seg
+
+
+# ---- the same three at 1 <= N <= CLF_MAX_N_EVAL nodes: nT x nT tiles of 32 x 32 per head (the *_wide_kernel forms of clf_train.hip)
+def _clf_tiles(N) -> int:
+    return (int(N) + CLF_MAX_N - 1) // CLF_MAX_N
+
+
+def clf_attn_fwd_n(q, kv, N, qi, ci):
+    """clf_attn_fwd for 1 <= N <= 128: (obar (P, C), attn (P, 4, nT, nT, 16, 64), abar (P, 4, 128)), nT = ceil(N / 32)"""
+    _chk(q, kv)
+    _clf_idx(qi, "clf_attn_fwd_n")
+    _clf_idx(ci, "clf_attn_fwd_n")
+    C = _clf_qkv_width(q, kv, N, "clf_attn_fwd_n", CLF_MAX_N_EVAL)
+    N = int(N)
+    P, nT = qi.numel(), _clf_tiles(N)
+    dev = q.device
+    obar = torch.empty((P, C), device=dev, dtype=torch.float32)
+    attn = torch.empty((P, CLF_H, nT, nT, 16, 64), device=dev, dtype=torch.float32)
+    abar = torch.empty((P, CLF_H, CLF_MAX_N_EVAL), device=dev, dtype=torch.float32)
+    # 2 N^2 C (Q K^T) + 2 N C (a V) per pair; bytes: Q once per head, K once per query tile, V (from L2 mostly), obar, attn, abar
+    _timed("clf_attn_fwd_wide_kernel", float(P) * (2.0 * N * N * C + 2.0 * N * C),
+           float(P) * (4.0 * N * C * (2 + nT) + 4.0 * C + 4.0 * CLF_H * (32 * nT) ** 2 + 4.0 * CLF_H * CLF_MAX_N_EVAL), lambda: call(
+               "nsid_clf_attn_fwd_n", _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P, _p(obar), _p(attn),
+               _p(abar), _stream()), (P, N, C, 1))
+    return obar, attn, abar
+
+
+def clf_attn_bwd_n(dobar, attn, q, kv, N, qi, ci):
+    """clf_attn_bwd for 1 <= N <= 128, from clf_attn_fwd_n's attn: per-pair (dQ (P, N, C), dK (P, N, C))"""
+    _chk(dobar, attn, q, kv)
+    _clf_idx(qi, "clf_attn_bwd_n")
+    _clf_idx(ci, "clf_attn_bwd_n")
+    C = _clf_qkv_width(q, kv, N, "clf_attn_bwd_n", CLF_MAX_N_EVAL)
+    N = int(N)
+    P, nT = qi.numel(), _clf_tiles(N)
+    if tuple(dobar.shape) != (P, C) or attn.numel() != P * CLF_H * (32 * nT) ** 2:
+        raise ValueError(f"clf_attn_bwd_n: expected dobar ({P}, {C}) and attn ({P}, 4, {nT}, {nT}, 16, 64), got "
+                         f"{tuple(dobar.shape)}, {tuple(attn.shape)}")
+    dev = q.device
+    dq = torch.empty((P, N, C), device=dev, dtype=torch.float32)
+    dk = torch.empty((P, N, C), device=dev, dtype=torch.float32)
+    # 2 N C (da) + 2 N^2 C (dQ) + 2 N^2 C (dK) per pair on the matrix side; bytes: V and attn once, K once per query tile, Q once per
+    # key tile, dQ and dK written
+    _timed("clf_attn_bwd_wide_kernel", float(P) * (4.0 * N * N * C + 2.0 * N * C),
+           float(P) * (4.0 * N * C * (1 + 2 * nT) + 4.0 * C + 4.0 * CLF_H * (32 * nT) ** 2 + 8.0 * N * C), lambda: call(
+               "nsid_clf_attn_bwd_n", _p(dobar), _p(attn), _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P,
+               _p(dq), _p(dk), _stream()), (P, N, C, 1))
+    return dq, dk
+
+
+def clf_seg_reduce_n(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
+    """clf_seg_reduce for 1 <= N <= 128, abar (P, 4, 128) from clf_attn_fwd_n: (dQ (nq_seg N, C), [dK | dV] (nc_seg N, 2 C))"""
+    _chk(dq, dk, abar, dobar)
+    _clf_idx(qi, "clf_seg_reduce_n")
+    _clf_idx(ci, "clf_seg_reduce_n")
+    P = qi.numel()
+    N = int(N)
+    if not 1 <= N <= CLF_MAX_N_EVAL:
+        raise ValueError(f"clf_seg_reduce_n: N = {N} is outside [1, {CLF_MAX_N_EVAL}]")
+    if dobar.dim() != 2:
+        raise ValueError(f"clf_seg_reduce_n: expected dobar (P, C), got {tuple(dobar.shape)}")
+    C = _clf_width(dobar.shape[1], "clf_seg_reduce_n")
+    if dobar.shape[0] != P or dq.numel() != P * N * C or dk.numel() != P * N * C or abar.numel() != P * CLF_H * CLF_MAX_N_EVAL:
+        raise ValueError(f"clf_seg_reduce_n: expected dq, dk ({P}, {N}, {C}), abar ({P}, 4, {CLF_MAX_N_EVAL}) and dobar ({P}, {C}), "
+                         f"got {tuple(dq.shape)}, {tuple(dk.shape)}, {tuple(abar.shape)}, {tuple(dobar.shape)}")
+    dev = dq.device
+    dq_seg = torch.empty((nq_seg * N, C), device=dev, dtype=torch.float32)
+    dkv_seg = torch.empty((nc_seg * N, 2 * C), device=dev, dtype=torch.float32)
+    # as clf_seg_reduce; every node tile of a segment scans the pair list and reads dobar again
+    nT = _clf_tiles(N)
+    _tk("clf_seg_reduce_wide_kernel", float(P) * (8.0 * N * C + 4.0 * C * nT) + 4.0 * (nq_seg + nc_seg) * (P * nT + N * C)
+        + 4.0 * nc_seg * N * C, lambda: call(
+            "nsid_clf_seg_reduce_n", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, C, N, nq_seg, nc_seg, _p(dq_seg),
             _p(dkv_seg), _stream()), (P, N, nq_seg + nc_seg, 1))
     return dq_seg, dkv_seg
 

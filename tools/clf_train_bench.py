@@ -2,13 +2,18 @@
 reference's step in torch-eager fp32 on the same GPU with the same pairs and dropout masks, and the encoder forward that supplies the
 features.
 
-    python tools/clf_train_bench.py [--sizes 32,256,1024] [--reps 7] [--only-ours] [--in-dim 512|640|768|1024]
+    python tools/clf_train_bench.py [--sizes 32,256,1024] [--reps 7] [--only-ours] [--in-dim 512|640|768|1024] [--nodes 32] [--kernels]
 
 Per size: ms per step (median of --reps after two warm-up steps, device events around each step), the step's FLOPs from shapes
 (per pair 1.05 MFLOP attention forward + 2.2 MFLOP backward: A is stored, not recomputed, plus the per-segment projections and the tail's linears and their
 backward) and the speed-up. The eager step is downstream.py:119-134: the per-row argsort mining loop, x_all[hn.view(-1)], two
 nn.MultiheadAttention classifier calls with the same keep masks, BCE + BCE, backward, torch.optim.Adam. One JSON line per size.
---only-ours runs just the HIP step (a rocprofv3 --kernel-trace --stats run uses it for the attention kernels' share of the peak)."""
+--only-ours runs just the HIP step (a rocprofv3 --kernel-trace --stats run uses it for the attention kernels' share of the peak).
+--nodes N (1 .. 128, default 32): the nodes per segment of both steps; above 32 the HIP step runs the multi-tile attention kernels
+(downstream.clf_train_scores_n) and the eager module attends over N nodes, with num_nodes = N in both. The HIP and the eager
+repetitions of a size are interleaved in rounds (one warm round first), so a drift of the device reaches both alike. --kernels adds
+one more HIP step per size under ops.KernelProfile and prints its classifier kernels (event pairs behind a plug: per-launch
+microseconds, TFLOP/s and algorithmic GB/s from the shape formulas of ops.py)."""
 import argparse
 import json
 import os
@@ -37,6 +42,37 @@ def step_flops(B, C):
     attn_f = P * (2.0 * N * N * C + 2.0 * N * C)                         # ~1.05 MFLOP per pair
     attn_b = P * (4.0 * N * N * C + 2.0 * N * C + 2.0 * N * C)          # dQ, dK, da, dV
     return 3.0 * (proj + tail) + attn_f + attn_b                         # proj / tail: forward, backward-data, weight gradient
+
+
+def timed_interleaved(fns, reps):
+    """per fn (median ms, all ms): rounds of one call of each fn in turn, the first two rounds warm-up"""
+    for _ in range(2):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    ms = [[] for _ in fns]
+    for _ in range(reps):
+        for i, fn in enumerate(fns):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[i].append(e0.elapsed_time(e1))
+    return [(float(np.median(m)), [round(x, 3) for x in m]) for m in ms]
+
+
+def kernel_rows(step):
+    """one step under ops.KernelProfile: the rows of its classifier kernels"""
+    from neuralsampleid_amd import ops
+    ops.PROFILE = ops.KernelProfile()
+    try:
+        ops.KernelProfile.plug(20.0)
+        step()
+        rows = ops.PROFILE.by_shape()
+    finally:
+        ops.PROFILE = None
+    return [r for r in rows if r["kernel"].startswith("clf_")]
 
 
 def timed(fn, reps):
@@ -112,25 +148,38 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--only-ours", action="store_true")
     ap.add_argument("--in-dim", type=int, default=512, choices=(512, 640, 768, 1024), help="the classifier's width C")
+    ap.add_argument("--nodes", type=int, default=32, help="nodes per segment, 1 .. 128 (above 32: the multi-tile kernels)")
+    ap.add_argument("--kernels", action="store_true", help="one more HIP step per size under ops.KernelProfile: its clf_ kernels")
     args = ap.parse_args()
     C = args.in_dim
+    global N
+    if not 1 <= args.nodes <= 128:
+        ap.error("--nodes must lie in [1, 128]")
+    N = args.nodes
     for B in [int(s) for s in args.sizes.split(",")]:
         torch.manual_seed(0)
         clf = CrossAttentionClassifier(in_dim=C, num_nodes=N).cuda()
         ni, nj, zi, zj = features(B, C)
         keep = downstream.draw_keep((1 + K) * B, 0.3, "cuda")
         opt = torch.optim.Adam(clf.parameters(), lr=1e-4)
-        ours, ours_all = timed(lambda: downstream.train_step(clf, opt, None, ni, nj, zi, zj, num_negatives=K, keep=keep), args.reps)
-        rec = {"in_dim": C, "B": B, "pairs": (1 + K) * B, "step_gflop": round(step_flops(B, C) / 1e9, 2), "hip_ms": round(ours, 3), "hip_all": ours_all,
-               "hip_tflops": round(step_flops(B, C) / ours / 1e9, 2)}
-        if not args.only_ours:
+        hip = lambda: downstream.train_step(clf, opt, None, ni, nj, zi, zj, num_negatives=K, keep=keep)
+        if args.only_ours:
+            (ours, ours_all), = timed_interleaved([hip], args.reps)
+        else:
             torch.manual_seed(0)
             clf_e = CrossAttentionClassifier(in_dim=C, num_nodes=N).cuda().train()
             model = EagerClf(clf_e)
             opt_e = torch.optim.Adam(clf_e.parameters(), lr=1e-4)
-            eager, eager_all = timed(lambda: eager_step(model, opt_e, ni, nj, zi, zj, keep), args.reps)
+            (ours, ours_all), (eager, eager_all) = timed_interleaved([hip, lambda: eager_step(model, opt_e, ni, nj, zi, zj, keep)],
+                                                                     args.reps)
+        rec = {"in_dim": C, "nodes": N, "B": B, "pairs": (1 + K) * B, "step_gflop": round(step_flops(B, C) / 1e9, 2),
+               "hip_ms": round(ours, 3), "hip_all": ours_all, "hip_tflops": round(step_flops(B, C) / ours / 1e9, 2)}
+        if not args.only_ours:
             rec.update({"eager_ms": round(eager, 3), "eager_all": eager_all, "speedup": round(eager / ours, 2)})
         print(json.dumps(rec), flush=True)
+        if args.kernels:
+            for row in kernel_rows(hip):
+                print(json.dumps(row), flush=True)
     if not args.only_ours:
         enc, enc_all = encoder_ms(32, args.reps)
         print(json.dumps({"encoder_forward_B32_ms": round(enc, 3), "all": enc_all}), flush=True)
