@@ -660,6 +660,48 @@ int nsid_song_vote_clf(const int64_t* I, int k, const float* S, const int64_t* s
                        int top, int* songs, double* totals, int* n_songs, void* stream);
 int nsid_vote_candidates(const int64_t* I, long n, int n_dummy, int n_ref, int* cidx, void* stream);
 
+/* ---- locating a sample in time (csrc/align.hip): the score matrices of many (query, song) pairs and their local alignment. The
+ * reference stops at the song (eval.py:250-258 leaves a "histogram-based matching score" to "future implementations"); sample100-ext
+ * annotates where every occurrence lies in both tracks, with a tempo ratio.
+ * The rule, for one pair with query rows 0 .. Lq-1, song rows 0 .. Lr-1, the fp32 score matrix S and the fp32 threshold theta; every
+ * operation is one fp32 operation rounded once, nothing is contracted or reassociated:
+ *     e[i][j] = S[i][j] - theta
+ *     best = 0, from = none
+ *     for (di, dj) in (1,1), (1,2), (2,1), in this order:  a = i - di, b = j - dj;
+ *         if a >= 0 and b >= 0 and H[a][b] > best:  best = H[a][b], from = (a, b)        (strict: the first of equals wins, a zero is never taken)
+ *     v = best + e[i][j]
+ *     if v > 0:  H[i][j] = v, org[i][j] = from ? org[from] : (i, j)        else:  H[i][j] = 0, org[i][j] = none
+ *   Row result: among the cells of row i with e[i][j] > 0 the largest H[i][j], ties to the smallest j: row_h[i], row_j[i] and
+ *   row_org[i] = i0 << 16 | j0 (int32) of that cell's origin; a row without such a cell gets 0, -1, -1. (Only a cell that itself passes
+ *   the threshold can be a row's result: the decaying tail of a finished path does not hide the start of the next occurrence.)
+ *   Occurrences: the rows with row_org != -1 are grouped by row_org; a group's representative is its row of largest row_h, ties to the
+ *   smallest i; the occurrence is (i0, i1 = i, j0, j1 = row_j[i]) with score row_h[i]. Those with score >= min_score are kept and ordered
+ *   by score descending, then i0 ascending, then j0 ascending; n_occ = the number kept (it can exceed top); the first top go to occ
+ *   (npairs x top x 4, int32: i0, i1, j0, j1) and occ_score (npairs x top); unused slots hold -1 and score 0.
+ * pair_sim: S_p[i][j] = q[q_start[p] + i] . x[x_start[p] + j] for i < q_len[p], j < x_len[p], written at S + s_off[p] with row stride
+ *   s_ld[p] >= x_len[p]; nothing else of S is written. The dot is flat_l2_topk's: one k-ordered fp32 fmaf chain on
+ *   v_mfma_f32_32x32x2_f32, the same for every (i, j), so an element's bits depend on its two rows alone. q (nq x d), x (nx x d) as for the
+ *   search (d, ld, alignment). q_start, q_len, x_len, s_ld: device int32; x_start, s_off: device int64, one per pair. tiles: device
+ *   int32 (ntiles x 3) = {pair, i0, j0}, the 32 x 32 tiles that cover every pair (the caller orders them, largest pairs first); one wave
+ *   per tile. s_len = the floats of S. The caller guarantees that the tables are in range; a tile whose pair leaves q, x or S is skipped,
+ *   never written.
+ * local_align: one workgroup per pair runs the rule on S_p = S + s_off[p] (row stride s_ld[p]: pair_sim's output, or a block of
+ *   classifier scores as song_vote_clf takes it). q_len, x_len: device int32 per pair, each at most max_q_len / max_x_len (host values,
+ *   <= 4096 each). The row results of pair p go to row_h / row_j / row_org at row_off[p] (device int64) + i. A pair with q_len == 0 or
+ *   x_len == 0 gets n_occ = 0, an empty occ row and 0, -1, -1 in its rows (if it has any); a pair whose length exceeds the host maxima reads
+ *   nothing and gets n_occ = -1. No atomics; a pair's result depends on nothing but the pair.
+ * d outside the search's widths, max_q_len / max_x_len > 4096, top outside [1, 64], a NaN theta or min_score, a null or misaligned
+ * pointer: NSID_EINVAL before any launch; npairs == 0 launches nothing. */
+#define NSID_ALIGN_MAX_ROWS 4096 /* query rows of a pair at most (also what the 16-bit packing of row_org needs) */
+#define NSID_ALIGN_MAX_COLS 4096 /* song rows of a pair at most */
+#define NSID_ALIGN_MAX_TOP 64    /* occurrences written per pair at most */
+int nsid_pair_sim(const float* q, int ldq, int nq, const float* x, int ldx, long nx, int d, const int* q_start, const int* q_len,
+                  const int64_t* x_start, const int* x_len, const int64_t* s_off, const int* s_ld, int npairs, const int* tiles,
+                  int ntiles, float* S, int64_t s_len, void* stream);
+int nsid_local_align(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len, int npairs,
+                     int max_q_len, int max_x_len, float theta, float min_score, int top, const int64_t* row_off, float* row_h,
+                     int* row_j, int* row_org, int* occ, float* occ_score, int* n_occ, void* stream);
+
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed
  * order and no entry uses atomics: a pair's score and its per-pair gradients depend on nothing but the pair.

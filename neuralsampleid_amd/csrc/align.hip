@@ -1,0 +1,396 @@
+// Time-localised matching: the score matrices of many (query, song) pairs and their local alignment (include/nsid.h nsid_pair_sim /
+// nsid_local_align).
+//
+// The reference stops at "which song" (eval.py:250-258 keeps the reconstructed index "for calculating histogram-based matching score" in
+// "future implementations"; sample100-ext annotates where every occurrence lies in both tracks). This file answers where.
+//
+// pair_sim: one wave per 32x32 tile of one pair's S = q x^T; the tiles of all pairs come from a host-built table (largest pairs first).
+// The dot is the chain of csrc/search.hip: one k-ordered fp32 fmaf chain on v_mfma_f32_32x32x2_f32, the same for every (i, j) whichever
+// tile, lane or pair holds it (up to d = 256 the pairing of l2_topk_split_kernel, above it the pairing of l2_topk_wide_kernel).
+//
+// local_align: one workgroup per pair walks the rows of S_p; threads own columns. The rule (stated in include/nsid.h) needs rows i - 1
+// and i - 2 only, so all columns of a row are independent: three rotating rows of (H, origin) cells in LDS, 8 bytes a cell, one barrier per
+// row (it orders LDS only), S read eight rows at a time with all loads in flight together. A row's result (its best cell that itself
+// passes the threshold) is reduced per wave (DPP), left in LDS, and combined during the next row. After the walk the same workgroup
+// reads the row results back and forms the occurrences with the quadratic compares of csrc/vote.hip. No atomics; a pair's result
+// depends on nothing but the pair.
+#include "nsid_common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+constexpr int AL_MAX_ROWS = NSID_ALIGN_MAX_ROWS;
+constexpr int AL_MAX_COLS = NSID_ALIGN_MAX_COLS;
+constexpr int AL_MAX_TOP = NSID_ALIGN_MAX_TOP;
+constexpr int AL_CPT = 4;             // columns (and, after the walk, rows) per thread at the most
+constexpr int AL_RB = 8;              // rows of S a thread loads at a time during the walk
+constexpr int AL_CHUNK = 8;           // LDS entries per step of the compare loops
+static_assert(AL_MAX_ROWS <= (1 << 15) && AL_MAX_COLS <= (1 << 16), "row_org packs (i0, j0) into 16 bits each of an int32 >= 0");
+static_assert(AL_MAX_ROWS <= 1024 * AL_CPT && AL_MAX_COLS <= 1024 * AL_CPT, "1024 threads own at most AL_CPT columns / rows each");
+
+// ---- pair_sim -------------------------------------------------------------------------------------------------------------------
+// Lane (r, h) = (lane & 31, lane >> 5) holds query row i0 + r as the A operand and song row j0 + r as the B operand; accumulator
+// register g is query row i0 + (g & 3) + 8 (g >> 2) + 4 h against song row j0 + r. WIDE = false: MFMA step (b, e) pairs k = 8 b + e
+// (h = 0) with k = 8 b + 4 + e (h = 1), 16 contiguous bytes per lane and block. WIDE = true: step t pairs k = 2 t with k = 2 t + 1.
+// Rows past a pair's end are read from its last row and never stored.
+template <bool WIDE>
+__global__ __launch_bounds__(64) void pair_sim_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x, int ldx,
+                                                      long nx, int d, const int* __restrict__ q_start, const int* __restrict__ q_len,
+                                                      const int64_t* __restrict__ x_start, const int* __restrict__ x_len,
+                                                      const int64_t* __restrict__ s_off, const int* __restrict__ s_ld, int npairs,
+                                                      const int* __restrict__ tiles, float* __restrict__ S, int64_t s_len) {
+  const int lane = lane_id(), r = lane & 31, h = lane >> 5;
+  const int* t = tiles + 3 * (size_t)blockIdx.x;
+  const int p = t[0], i0 = t[1], j0 = t[2];
+  if (p < 0 || p >= npairs) return;
+  const int Lq = q_len[p], Lr = x_len[p];
+  const long qs = q_start[p], xs = x_start[p], so = s_off[p], ld = s_ld[p];
+  // the caller checks the table; this only keeps a bad entry in bounds (uniform)
+  if (i0 < 0 || j0 < 0 || i0 >= Lq || j0 >= Lr || qs < 0 || xs < 0 || qs + Lq > nq || xs + Lr > nx || ld < Lr || so < 0 ||
+      so + (long)(Lq - 1) * ld + Lr > s_len)
+    return;
+  const float* qp = q + (size_t)(qs + min(i0 + r, Lq - 1)) * ldq;
+  const float* xp = x + (size_t)(xs + min(j0 + r, Lr - 1)) * ldx;
+  f32x16 acc = {};
+  const int nb = d / 8;
+  if (!WIDE) {
+    qp += 4 * h;
+    xp += 4 * h;
+    for (int b = 0; b < nb; b += 2) {                 // d % 16 == 0: two blocks' loads in flight per step
+      const f32x4 a0 = ld4(qp + 8 * b), c0 = ld4(xp + 8 * b), a1 = ld4(qp + 8 * b + 8), c1 = ld4(xp + 8 * b + 8);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], c0[e], acc, 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[e], c1[e], acc, 0, 0, 0);
+    }
+  } else {
+    for (int b = 0; b < nb; ++b) {
+      const f32x4 a0 = ld4(qp + 8 * b), a1 = ld4(qp + 8 * b + 4), c0 = ld4(xp + 8 * b), c1 = ld4(xp + 8 * b + 4);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a0[1] : a0[0], h ? c0[1] : c0[0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a0[3] : a0[2], h ? c0[3] : c0[2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a1[1] : a1[0], h ? c1[1] : c1[0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a1[3] : a1[2], h ? c1[3] : c1[2], acc, 0, 0, 0);
+    }
+  }
+  const int col = j0 + r;
+  float* sp = S + so + col;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int row = i0 + (g & 3) + 8 * (g >> 2) + 4 * h;
+    if (row < Lq && col < Lr) sp[(size_t)row * ld] = acc[g];
+  }
+}
+
+// ---- local_align ----------------------------------------------------------------------------------------------------------------
+// a row's best cell as one key: H's bits (H > 0, so they order as the floats do) above the complement of j (ties: the smaller j wins a max);
+// 0 = the row has no cell that passes the threshold
+__device__ __forceinline__ unsigned long long al_key(float h, int j) {
+  return ((unsigned long long)__builtin_bit_cast(unsigned, h) << 32) | (0xffffffffu - (unsigned)j);
+}
+
+// 64-lane max of the keys with DPP only, the steps of nsid_common.h's wave_sum (0 is the identity of the max, as of the sum there): no
+// LDS permutes on the row's critical path. Every lane receives the result.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ unsigned long long al_key_dpp_max(unsigned long long v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, ROW_MASK, 0xF, true);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, ROW_MASK, 0xF, true);
+  const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+  return o > v ? o : v;
+}
+__device__ __forceinline__ unsigned long long al_wave_key_max(unsigned long long v) {
+  v = al_key_dpp_max<0xB1, 0xF>(v);
+  v = al_key_dpp_max<0x4E, 0xF>(v);
+  v = al_key_dpp_max<0x141, 0xF>(v);
+  v = al_key_dpp_max<0x140, 0xF>(v);
+  v = al_key_dpp_max<0x142, 0xA>(v);
+  v = al_key_dpp_max<0x143, 0xC>(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, 63);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), 63);
+  return ((unsigned long long)hi << 32) | lo;
+}
+
+__device__ __forceinline__ void al_empty(int p, int top, int n, int tid, int* __restrict__ occ, float* __restrict__ occ_score,
+                                         int* __restrict__ n_occ) {
+  if (tid < top) {
+    int* o = occ + ((size_t)p * top + tid) * 4;
+    o[0] = o[1] = o[2] = o[3] = -1;
+    occ_score[(size_t)p * top + tid] = 0.f;
+  }
+  if (tid == 0) n_occ[p] = n;
+}
+
+// cols: cells per LDS row = max_x + 2 (two zero cells in front stand for j - 1, j - 2 < 0). Dynamic LDS: three rows of cells during the
+// walk, then the row results (h, origin) of the pair.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void local_align_kernel(const float* __restrict__ S, const int64_t* __restrict__ s_off,
+                                                              const int* __restrict__ s_ld, const int* __restrict__ q_len,
+                                                              const int* __restrict__ x_len, int max_q, int max_x, int cols, float theta,
+                                                              float min_score, int top, const int64_t* __restrict__ row_off,
+                                                              float* __restrict__ row_h, int* __restrict__ row_j,
+                                                              int* __restrict__ row_org, int* __restrict__ occ,
+                                                              float* __restrict__ occ_score, int* __restrict__ n_occ) {
+  constexpr int NW = THREADS / NSID_WAVE;
+  extern __shared__ __attribute__((aligned(16))) char al_smem[];
+  __shared__ unsigned long long part[2][NW];
+  __shared__ int o_occ[AL_MAX_TOP][4];
+  __shared__ float o_sc[AL_MAX_TOP];
+  __shared__ int wcnt[NW];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
+  const int Lq = q_len[p], Lr = x_len[p];
+  // every return below is uniform over the workgroup and ahead of every barrier
+  if (Lq < 0 || Lr < 0 || Lq > max_q || Lr > max_x) {       // the caller checks the lengths; this only keeps a bad pair in bounds
+    al_empty(p, top, -1, tid, occ, occ_score, n_occ);
+    return;
+  }
+  if (Lq == 0 || Lr == 0) {
+    al_empty(p, top, 0, tid, occ, occ_score, n_occ);
+    for (int i = tid; i < Lq; i += THREADS) {                // rows without a column: no cell, so 0, -1, -1
+      row_h[row_off[p] + i] = 0.f;
+      row_j[row_off[p] + i] = -1;
+      row_org[row_off[p] + i] = -1;
+    }
+    return;
+  }
+  const float* Sp = S + s_off[p];
+  const size_t ld = (size_t)s_ld[p];
+  const int64_t ro = row_off[p];
+
+  int2* cell = reinterpret_cast<int2*>(al_smem);
+  for (int t = tid; t < 3 * cols; t += THREADS) cell[t] = int2{0, -1};        // H = +0.0, no origin
+  if (tid < AL_MAX_TOP) {
+    o_occ[tid][0] = o_occ[tid][1] = o_occ[tid][2] = o_occ[tid][3] = -1;
+    o_sc[tid] = 0.f;
+  }
+  __syncthreads();
+
+  // between the barriers of rows `row` and `row + 1`: the waves' keys of the row -> its result. Every wave does the (broadcast) reads, so
+  // that they are scheduled among the row's own reads and no wave is later at the barrier than the others; thread 0 stores
+  auto combine = [&](int row, const int2* buf) {
+    unsigned long long k = 0;
+#pragma unroll
+    for (int u = 0; u < NW; ++u) {
+      const unsigned long long v = part[row & 1][u];
+      k = v > k ? v : k;
+    }
+    const int j = k ? (int)(0xffffffffu - (unsigned)k) : -1;
+    const int org = buf[max(j, 0) + 2].y;
+    if (tid == 0) {
+      row_h[ro + row] = __builtin_bit_cast(float, (unsigned)(k >> 32));
+      row_j[ro + row] = j;
+      row_org[ro + row] = k ? org : -1;
+    }
+  };
+
+  int2* cur = cell;                  // row i
+  int2* prev1 = cell + 2 * cols;     // row i - 1
+  int2* prev2 = cell + cols;         // row i - 2
+  // AL_RB rows of S per thread at a time, all their loads in flight together: the memory latency is paid once per AL_RB rows, not per row
+  // (columns past the pair's end read its last column and are not used)
+  for (int ib = 0; ib < Lq; ib += AL_RB) {
+    float sv[AL_RB][AL_CPT];
+#pragma unroll
+    for (int r = 0; r < AL_RB; ++r) {
+      const float* rp = Sp + (size_t)min(ib + r, Lq - 1) * ld;
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) sv[r][c] = rp[min(tid + c * THREADS, Lr - 1)];
+    }
+#pragma unroll
+    for (int r = 0; r < AL_RB; ++r) {
+      const int i = ib + r;
+      if (i >= Lq) break;              // uniform
+      if (i > 0) combine(i - 1, prev1);
+      unsigned long long key = 0;
+      // branch-free over the thread's columns (a column past the pair's end reads the last one and writes nothing), so that the LDS
+      // reads of all of them are in flight together
+      int2 d11[AL_CPT], d12[AL_CPT], d21[AL_CPT];
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) {
+        const int jc = min(tid + c * THREADS, Lr - 1);
+        d11[c] = prev1[jc + 1];
+        d12[c] = prev1[jc];
+        d21[c] = prev2[jc + 1];
+      }
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) {
+        const int j = tid + c * THREADS;
+        const float e = sv[r][c] - theta;
+        float best = 0.f;
+        int from = -1;
+        const float h11 = __builtin_bit_cast(float, d11[c].x), h12 = __builtin_bit_cast(float, d12[c].x),
+                    h21 = __builtin_bit_cast(float, d21[c].x);
+        if (h11 > best) {
+          best = h11;
+          from = d11[c].y;
+        }
+        if (h12 > best) {
+          best = h12;
+          from = d12[c].y;
+        }
+        if (h21 > best) {
+          best = h21;
+          from = d21[c].y;
+        }
+        const float v = best + e;
+        const bool pos = v > 0.f;
+        if (j < Lr) cur[j + 2] = int2{pos ? __builtin_bit_cast(int, v) : 0, pos ? (from >= 0 ? from : ((i << 16) | j)) : -1};
+        const unsigned long long k = (j < Lr && e > 0.f) ? al_key(v, j) : 0ull;
+        key = k > key ? k : key;
+      }
+      key = al_wave_key_max(key);
+      if (lane == 0) part[i & 1][w] = key;
+      int2* t = prev2;
+      prev2 = prev1;
+      prev1 = cur;
+      cur = t;
+      // the row's barrier orders LDS only: wave 0's row results, which nobody reads before the walk ends, stay in flight over it
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    }
+  }
+  combine(Lq - 1, prev1);
+  __syncthreads();                   // the row results are in memory for the whole workgroup; the cells are dead
+
+  // ---- occurrences: the rows grouped by origin, a group's best row, the kept ones ranked
+  float* rh = reinterpret_cast<float*>(al_smem);
+  int* rg = reinterpret_cast<int*>(al_smem) + max_q;
+  for (int i = tid; i < Lq; i += THREADS) {
+    rh[i] = row_h[ro + i];
+    rg[i] = row_org[ro + i];
+  }
+  __syncthreads();
+  unsigned keep_mask = 0;
+  int n_keep = 0;
+#pragma unroll
+  for (int c = 0; c < AL_CPT; ++c) {
+    const int i = tid + c * THREADS;
+    if (i >= Lq) continue;
+    const int og = rg[i];
+    const float hi = rh[i];
+    bool rep = og >= 0 && hi >= min_score;
+    for (int i0 = 0; i0 < Lq && rep; i0 += AL_CHUNK) {
+      bool hit = false;
+#pragma unroll
+      for (int u = 0; u < AL_CHUNK; ++u) {
+        const int a = i0 + u, ac = min(a, Lq - 1);
+        const float ha = rh[ac];
+        hit |= (a < Lq) & (rg[ac] == og) & ((ha > hi) | ((ha == hi) & (a < i)));
+      }
+      rep = !hit;
+    }
+    if (rep) {
+      keep_mask |= 1u << c;
+      ++n_keep;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n_keep += __shfl_xor(n_keep, o, NSID_WAVE);
+  if (lane == 0) wcnt[w] = n_keep;
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < AL_CPT; ++c) {
+    const int i = tid + c * THREADS;
+    if (i < Lq && !((keep_mask >> c) & 1u)) rg[i] = -1;         // from here on rg >= 0 marks a kept occurrence
+  }
+  __syncthreads();
+#pragma unroll
+  for (int c = 0; c < AL_CPT; ++c) {
+    const int i = tid + c * THREADS;
+    if (!((keep_mask >> c) & 1u)) continue;
+    const int og = rg[i];
+    const float hi = rh[i];
+    int rank = 0;
+    for (int i0 = 0; i0 < Lq && rank < top; i0 += AL_CHUNK) {
+#pragma unroll
+      for (int u = 0; u < AL_CHUNK; ++u) {
+        const int a = i0 + u, ac = min(a, Lq - 1);
+        const float ha = rh[ac];
+        const int oa = rg[ac];
+        rank += ((a < Lq) & (oa >= 0) & ((ha > hi) | ((ha == hi) & (oa < og)))) ? 1 : 0;
+      }
+    }
+    if (rank < top) {
+      o_occ[rank][0] = og >> 16;
+      o_occ[rank][1] = i;
+      o_occ[rank][2] = og & 0xffff;
+      o_occ[rank][3] = row_j[ro + i];
+      o_sc[rank] = hi;
+    }
+  }
+  __syncthreads();
+  if (tid < top) {
+    int* o = occ + ((size_t)p * top + tid) * 4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) o[u] = o_occ[tid][u];
+    occ_score[(size_t)p * top + tid] = o_sc[tid];
+  }
+  if (tid == 0) {
+    int n = 0;
+    for (int u = 0; u < NW; ++u) n += wcnt[u];
+    n_occ[p] = n;
+  }
+}
+
+size_t align_lds_bytes(int max_q, int max_x) {
+  const size_t walk = 3 * (size_t)(max_x + 2) * sizeof(int2), rows = 2 * (size_t)max_q * sizeof(int);
+  return (std::max(walk, rows) + 15) / 16 * 16;
+}
+
+template <int THREADS>
+int launch_align(size_t lds, hipStream_t st, int npairs, const float* S, const int64_t* s_off, const int* s_ld, const int* q_len,
+                 const int* x_len, int max_q, int max_x, float theta, float min_score, int top, const int64_t* row_off, float* row_h,
+                 int* row_j, int* row_org, int* occ, float* occ_score, int* n_occ) {
+  static size_t configured = 48 * 1024;
+  if (lds > configured) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(local_align_kernel<THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)lds) != hipSuccess)
+      return NSID_ELAUNCH;
+    configured = lds;
+  }
+  NSID_LAUNCH((local_align_kernel<THREADS>), dim3(npairs), dim3(THREADS), lds, st, S, s_off, s_ld, q_len, x_len, max_q, max_x, max_x + 2,
+              theta, min_score, top, row_off, row_h, row_j, row_org, occ, occ_score, n_occ);
+  return nsid_launch_status();
+}
+
+bool sim_d_ok(int d) { return (d % 16 == 0 && d >= 16 && d <= 256) || (d % 64 == 0 && d > 256 && d <= 2048); }
+
+}  // namespace
+
+extern "C" int nsid_pair_sim(const float* q, int ldq, int nq, const float* x, int ldx, long nx, int d, const int* q_start,
+                             const int* q_len, const int64_t* x_start, const int* x_len, const int64_t* s_off, const int* s_ld,
+                             int npairs, const int* tiles, int ntiles, float* S, int64_t s_len, void* stream) {
+  NSID_REQUIRE(sim_d_ok(d) && nq >= 0 && nx >= 0 && npairs >= 0 && ntiles >= 0 && s_len >= 0);
+  if (npairs == 0 || ntiles == 0) return NSID_OK;
+  NSID_REQUIRE(q && x && q_start && q_len && x_start && x_len && s_off && s_ld && tiles && S);
+  NSID_REQUIRE(ldq >= d && ldq % 4 == 0 && ldx >= d && ldx % 4 == 0 && nsid_aligned16(q) && nsid_aligned16(x));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  nsid_count(NSID_C_pair_sim);
+  if (d > 256) {
+    NSID_LAUNCH(pair_sim_kernel<true>, dim3(ntiles), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, d, q_start, q_len, x_start, x_len, s_off,
+                s_ld, npairs, tiles, S, s_len);
+  } else {
+    NSID_LAUNCH(pair_sim_kernel<false>, dim3(ntiles), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, d, q_start, q_len, x_start, x_len, s_off,
+                s_ld, npairs, tiles, S, s_len);
+  }
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_local_align(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len, int npairs,
+                                int max_q_len, int max_x_len, float theta, float min_score, int top, const int64_t* row_off,
+                                float* row_h, int* row_j, int* row_org, int* occ, float* occ_score, int* n_occ, void* stream) {
+  NSID_REQUIRE(npairs >= 0 && max_q_len >= 0 && max_q_len <= AL_MAX_ROWS && max_x_len >= 0 && max_x_len <= AL_MAX_COLS && top >= 1 &&
+               top <= AL_MAX_TOP && theta == theta && min_score == min_score);
+  if (npairs == 0) return NSID_OK;
+  NSID_REQUIRE(s_off && s_ld && q_len && x_len && row_off && occ && occ_score && n_occ);
+  NSID_REQUIRE((max_q_len == 0 || max_x_len == 0) || (S && row_h && row_j && row_org));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t lds = align_lds_bytes(max_q_len, max_x_len);
+  nsid_count(NSID_C_local_align);
+  // 256 threads own every column and every row of a pair up to 1024; above that 1024 threads do (the results do not depend on it)
+  if (std::max(max_q_len, max_x_len) <= 256 * AL_CPT)
+    return launch_align<256>(lds, st, npairs, S, s_off, s_ld, q_len, x_len, max_q_len, max_x_len, theta, min_score, top, row_off, row_h,
+                             row_j, row_org, occ, occ_score, n_occ);
+  return launch_align<1024>(lds, st, npairs, S, s_off, s_ld, q_len, x_len, max_q_len, max_x_len, theta, min_score, top, row_off, row_h,
+                            row_j, row_org, occ, occ_score, n_occ);
+}

@@ -249,7 +249,8 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(stem7_stat) X(stem7_pool_train) X(stem7_bwd)   /* resnet.hip: training-mode stem */ \
   X(resample_sinc) X(stem_pairs_gate) X(stem_pairs_build)   /* stems.hip: sinc resampler, stem-pair sampler */ \
   X(logmel_fft_ragged) X(cqt_ragged) X(unfold_segments_ragged)   /* frontend.hip, cqt.hip, misc.hip: a pack of songs of different lengths in one launch, and its segment gather */ \
-  X(song_vote) X(song_vote_clf) X(vote_candidates)   /* vote.hip: the song-level vote of a search result, and the device candidate list of the re-rank */
+  X(song_vote) X(song_vote_clf) X(vote_candidates)   /* vote.hip: the song-level vote of a search result, and the device candidate list of the re-rank */ \
+  X(pair_sim) X(local_align)   /* align.hip: the score matrices of (query, song) pairs and their local alignment */
 
 // nsid_stem7_stat leaves at most this many partial sums per channel (resnet.hip); nsid_bn_finalize accepts such a count next to
 // nsid_row_tiles(M)

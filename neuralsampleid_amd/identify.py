@@ -14,8 +14,18 @@ per reference segment) and the song codes next to it, so an identification is se
 the `top` results come back. The file-based evaluations (search.eval_hit_rates, rerank.eval_hit_rates_clf) are unchanged and do
 not use this module.
 
-Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs."""
-from typing import List, NamedTuple, Optional, Sequence
+Where in time: align / locate answer "song X, query rows i0..i1, taken from song rows j0..j1, played about `stretch` times as fast"
+with a local alignment of the query's rows against a song's rows (csrc/align.hip; the rule is stated in include/nsid.h). The
+reference has no such step (eval.py:250-258 leaves it to "future implementations"); sample100-ext's per-occurrence annotations are
+what interval_recall is shaped for.
+
+    occs = idx.locate(wave=query, threshold=0.6, min_score=2.0)      # [Occurrence(song, score, q_rows, r_rows, q_time, r_time, stretch)]
+    per_song = idx.align(q_fp, ["song a", "song b"], threshold=0.6)
+
+Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs or queries past 4096 rows
+(refused, not split), gap steps other than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated
+on real audio, parsing sample100-ext's annotation files."""
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -397,6 +407,223 @@ class SampleIndex:
         Sq = int(nodes_q.shape[0])
         out, _ = self.classifier.score_blocks(q, kp, N, [0], [Sq], np.arange(n_seg), [0], [n_seg])
         return float(out.view(Sq, n_seg).max(dim=1).values.double().mean())
+
+
+    # ------------------------------------------------------------------------------------------------ locating
+    def _row_timing(self, row_hop_s, row_len_s):
+        """(row hop, row length) in seconds, from the keywords or the front end; None when neither is known"""
+        if (row_hop_s is None) != (row_len_s is None):
+            raise ValueError("give row_hop_s and row_len_s together")
+        if row_hop_s is not None:
+            hop, length = float(row_hop_s), float(row_len_s)
+            if not (hop > 0 and length > 0):
+                raise ValueError("row_hop_s and row_len_s must be positive")
+            return hop, length
+        if self.front is not None:
+            f = self.front
+            return f.step * f.hop / f.fs, f.n_frames * f.hop / f.fs
+        return None
+
+    def _align_checks(self, what, fp, songs, threshold, top, nodes, rerank):
+        """every refusal of align, before the device is touched for the shapes; returns (song codes, threshold)"""
+        if rerank:
+            self._check_rerank()
+        elif threshold is None:
+            raise ValueError(f"{what}: threshold has no default for fingerprint scores (the reference has no such number and none has "
+                             "been measured on real audio): pass one, or use rerank=True")
+        self._check_fp(fp, what, device=False)
+        if fp.shape[0] > ops.ALIGN_MAX_ROWS:
+            raise ValueError(f"{what}: a query of {fp.shape[0]} rows is past the limit of {ops.ALIGN_MAX_ROWS}; longer inputs are refused, "
+                             "not split")
+        top = int(top)
+        if not 1 <= top <= ops.ALIGN_MAX_TOP:
+            raise ValueError(f"{what}: top = {top} is outside [1, {ops.ALIGN_MAX_TOP}]")
+        if isinstance(songs, str):
+            raise TypeError(f"{what}: songs must be a sequence of names, not one string")
+        codes = [self.code(s) for s in songs]
+        for c in codes:
+            if self._song_rows[c][1] > ops.ALIGN_MAX_COLS:
+                raise ValueError(f"{what}: song {self.names[c]!r} has {self._song_rows[c][1]} rows, past the limit of "
+                                 f"{ops.ALIGN_MAX_COLS}; longer inputs are refused, not split")
+        if rerank:
+            if nodes is None:
+                raise ValueError(f"{what}: rerank=True needs the query's node matrices")
+            self._check_nodes(nodes, what)
+            if nodes.shape[0] != fp.shape[0]:
+                raise ValueError(f"{what}: {fp.shape[0]} fingerprints but {nodes.shape[0]} node matrices")
+            if self._kp is None:
+                raise RuntimeError(f"{what}: rerank=True, but no song of the index has node matrices")
+            threshold = CLF_THRESHOLD if threshold is None else threshold
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError(f"{what}: threshold is NaN")
+        _need_cuda(fp, what)
+        return codes, threshold
+
+    @torch.no_grad()
+    def align(self, fp: torch.Tensor, songs: Sequence[str], threshold: Optional[float] = None, min_score: float = 0.0, top: int = 16,
+              nodes: Optional[torch.Tensor] = None, rerank: bool = False, return_rows: bool = False, row_hop_s=None, row_len_s=None,
+              s_budget_bytes: int = 1 << 30):
+        """Where in the query, and where in each named resident song, does the query sample the song? The local alignment of
+        include/nsid.h ("locating a sample") of the query's rows against each song's rows, one pair per song, all songs in one
+        pair_sim + local_align per chunk; a chunk's score workspace (4 Lq Lr bytes per song) stays under s_budget_bytes.
+
+        threshold: the score a (query row, song row) cell must exceed to extend a path. It has NO default for fingerprint scores: the
+        reference has no such number and none has been measured on real audio. With rerank=True the cells are the classifier's scores
+        of (query row, song row with node matrices) pairs, the song rows without node matrices are not columns, and threshold defaults
+        to CLF_THRESHOLD. Returns a list of Occurrence lists, one per song, best first; with return_rows=True also a dict of the per-row
+        tensors and the S used, per chunk: {"chunks": [(codes, S, s_off, s_ld, x_len, row_h, row_j, row_org, row_off, occ, occ_score,
+        n_occ), ...]}."""
+        timing = self._row_timing(row_hop_s, row_len_s)
+        codes, threshold = self._align_checks("align", fp, songs, threshold, top, nodes, rerank)
+        Lq, top = int(fp.shape[0]), int(top)
+        out: List[List[Occurrence]] = [[] for _ in codes]
+        chunks = []
+        if Lq == 0 or not codes:
+            return (out, {"chunks": chunks}) if return_rows else out
+        fp = fp.contiguous()
+        if rerank:
+            qproj = self._project(self.classifier.project_queries, nodes)
+        x_len_all = [self._song_rows[c][2 if rerank else 1] for c in codes]
+        lo = 0
+        while lo < len(codes):
+            hi, used = lo, 0
+            while hi < len(codes) and (hi == lo or used + 4 * Lq * x_len_all[hi] <= int(s_budget_bytes)):
+                used += 4 * Lq * x_len_all[hi]
+                hi += 1
+            part = codes[lo:hi]
+            x_start = np.asarray([self._song_rows[c][0] for c in part], dtype=np.int64)
+            x_len = np.asarray(x_len_all[lo:hi], dtype=np.int64)
+            q_len = np.full(len(part), Lq, dtype=np.int64)
+            if rerank:
+                cand = np.concatenate([np.arange(s, s + n) for s, n in zip(x_start.tolist(), x_len.tolist())]) if x_len.sum() else \
+                    np.zeros(0, dtype=np.int64)
+                S, s_off = self.classifier.score_blocks(qproj, self._kp[: self.n_ref * self.N], self.N, np.zeros(len(part), np.int64),
+                                                        q_len, cand, np.cumsum(x_len) - x_len, x_len)
+                s_off, s_ld = np.asarray(s_off, dtype=np.int64), x_len
+            else:
+                S, s_off, s_ld = ops.pair_sim(fp, self.fingerprints, np.zeros(len(part), np.int64), q_len, x_start, x_len)
+            res = ops.local_align(S, s_off, s_ld, q_len, x_len, threshold, min_score, top)
+            occ, sc = res[0].cpu().numpy(), res[1].cpu().numpy()
+            for p, c in enumerate(part):
+                for (i0, i1, j0, j1), s in zip(occ[p].tolist(), sc[p].tolist()):
+                    if i0 < 0:
+                        break
+                    out[lo + p].append(_occurrence(self.names[c], s, i0, i1, j0, j1, timing))
+            chunks.append((part, S, s_off, s_ld, x_len) + tuple(res[3:]) + tuple(res[:3]))
+            lo = hi
+        return (out, {"chunks": chunks}) if return_rows else out
+
+    @torch.no_grad()
+    def locate(self, specs=None, wave=None, fp=None, nodes=None, songs: Optional[Sequence[str]] = None, k_probe: int = 20,
+               n_songs: int = 5, exclude: Optional[str] = None, threshold: Optional[float] = None, min_score: float = 0.0,
+               top: int = 16, rerank: bool = False, row_hop_s=None, row_len_s=None) -> List["Occurrence"]:
+        """The occurrences of resident songs in a query, one flat list sorted by score: encodes as identify does, finds the candidate
+        songs (songs=None) and aligns the query against them.
+
+        The candidates: the query is cut into consecutive windows of W = min(Lq, VOTE_MAX_CAND // k_probe) rows (the last one ends at
+        the last row), one identify_pairs call votes in every window, and the songs of any window's top list are ordered by their best
+        window total (descending, then by code); the first n_songs are aligned. This is also what lets a whole track through at
+        k_probe = 20. exclude: a song name that is never a candidate. threshold: see align (no default without rerank)."""
+        if rerank:
+            self._check_rerank()
+        elif threshold is None:
+            raise ValueError("locate: threshold has no default for fingerprint scores (the reference has no such number and none has "
+                             "been measured on real audio): pass one, or use rerank=True")
+        n_songs, k = int(n_songs), int(k_probe)
+        if n_songs < 1:
+            raise ValueError(f"locate: n_songs = {n_songs} must be at least 1")
+        if not 1 <= k <= ops.SEARCH_MAX_K:
+            raise ValueError(f"k_probe = {k} is outside [1, {ops.SEARCH_MAX_K}]")
+        if songs is not None and exclude is not None:
+            raise ValueError("locate: exclude applies to the candidate search; with songs= leave the song out")
+        if exclude is not None:
+            self.code(exclude)
+        fp, nodes = self._query(specs, wave, fp, nodes, rerank)
+        if songs is None:
+            self._check_fp(fp, "locate", device=False)
+            if fp.shape[0] > ops.ALIGN_MAX_ROWS:
+                raise ValueError(f"locate: a query of {fp.shape[0]} rows is past the limit of {ops.ALIGN_MAX_ROWS}; longer inputs are "
+                                 "refused, not split")
+            songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank)
+        per_song = self.align(fp, songs, threshold, min_score, top, nodes, rerank, row_hop_s=row_hop_s, row_len_s=row_len_s)
+        flat = [(o, c, n) for c, occs in enumerate(per_song) for n, o in enumerate(occs)]
+        flat.sort(key=lambda t: (-t[0].score, t[1], t[2]))
+        return [t[0] for t in flat]
+
+    def _candidates(self, fp, nodes, k, n_songs, exclude, rerank) -> List[str]:
+        """the songs of any window's top list, by their best window total (descending, then by code), at most n_songs"""
+        Lq = int(fp.shape[0])
+        if Lq == 0:
+            raise ValueError("locate: the query has no row")
+        W = min(Lq, max(1, ops.VOTE_MAX_CAND // k))
+        starts = list(range(0, Lq - W + 1, W))
+        if starts[-1] + W < Lq:
+            starts.append(Lq - W)
+        pv = self.identify_pairs(fp, starts, [W] * len(starts), k_probe=k, top=min(ops.VOTE_MAX_TOP, max(n_songs, 1)),
+                                 exclude=None if exclude is None else [exclude] * len(starts), rerank=rerank, nodes=nodes)
+        best = {}
+        for r in pv.results():
+            for name, total in zip(r.songs, r.totals.tolist()):
+                c = self._code[name]
+                if c not in best or total > best[c]:
+                    best[c] = total
+        order = sorted(best, key=lambda c: (-best[c], c))
+        return [self.names[c] for c in order[:n_songs]]
+
+
+class Occurrence(NamedTuple):
+    song: str
+    score: float
+    q_rows: Tuple[int, int]                       # (first, last) row, inclusive, of the query
+    r_rows: Tuple[int, int]                       # the same of the song
+    q_time: Optional[Tuple[float, float]]         # seconds, when the row timing is known
+    r_time: Optional[Tuple[float, float]]
+    stretch: float                                # (j1 - j0) / (i1 - i0): song rows per query row; nan for a one-row occurrence
+
+
+def _occurrence(song, score, i0, i1, j0, j1, timing) -> Occurrence:
+    qt = rt = None
+    if timing is not None:
+        hop, length = timing
+        qt, rt = (i0 * hop, i1 * hop + length), (j0 * hop, j1 * hop + length)
+    return Occurrence(song, float(score), (int(i0), int(i1)), (int(j0), int(j1)), qt, rt,
+                      (j1 - j0) / (i1 - i0) if i1 > i0 else float("nan"))
+
+
+def interval_recall(found, truth, min_cover: float = 0.5):
+    """Segment-wise evaluation of located occurrences against annotated ones (the query_time_annotations / target_time_annotations of
+    sample100-ext, as plain lists): found, truth = lists of (start, end) seconds. A truth interval counts as found when the union of the
+    found intervals covers at least min_cover of it (a truth interval of zero length: when a found interval contains it). Returns
+    (recall, covered_seconds, found_seconds_outside_truth): recall = found truth intervals / truth intervals (nan without truth),
+    covered_seconds = the length of union(found) inside union(truth), the last = the length of union(found) outside it."""
+    def union(iv):
+        iv = sorted((float(a), float(b)) for a, b in iv)
+        out = []
+        for a, b in iv:
+            if b < a:
+                raise ValueError(f"interval_recall: an interval ends before it starts: ({a}, {b})")
+            if out and a <= out[-1][1]:
+                out[-1][1] = max(out[-1][1], b)
+            else:
+                out.append([a, b])
+        return out
+
+    def overlap(a, b, iv):
+        return sum(max(0.0, min(b, d) - max(a, c)) for c, d in iv)
+
+    fu, tu = union(found), union(truth)
+    hits = 0
+    for a, b in truth:
+        a, b = float(a), float(b)
+        if b > a:
+            hits += overlap(a, b, fu) >= float(min_cover) * (b - a)
+        else:
+            hits += any(c <= a <= d for c, d in fu)
+    covered = sum(overlap(a, b, fu) for a, b in tu)
+    total_found = sum(b - a for a, b in fu)
+    recall = hits / len(truth) if len(truth) else float("nan")
+    return recall, covered, total_found - covered
 
 
 def rejection_stats(real_scores, dummy_scores, threshold: float = 0.5):

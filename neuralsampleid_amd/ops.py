@@ -2044,6 +2044,137 @@ def vote_candidates(I, n_dummy, n_ref) -> torch.Tensor:
     return cidx
 
 
+# ------------------------------------------------------------------------------------------------ locating a sample (csrc/align.hip)
+ALIGN_MAX_ROWS = _H["NSID_ALIGN_MAX_ROWS"]        # query rows of a pair at most
+ALIGN_MAX_COLS = _H["NSID_ALIGN_MAX_COLS"]        # song rows of a pair at most
+ALIGN_MAX_TOP = _H["NSID_ALIGN_MAX_TOP"]
+ALIGN_TILE = 32                                   # pair_sim's tiles (one wave each)
+
+
+def _align_seq(name, what, v, n=None):
+    v = np.asarray(v, dtype=np.int64).reshape(-1)
+    if n is not None and v.size != n:
+        raise ValueError(f"{name}: {what} must hold one entry per pair ({n}), got {v.size}")
+    return v
+
+
+def pair_sim_tiles(q_len, x_len) -> np.ndarray:
+    """the work list of pair_sim: (ntiles, 3) int32 rows {pair, i0, j0}, the 32 x 32 tiles of every pair, largest pairs first (equal
+    sizes in pair order), a pair's tiles row-major"""
+    q_len, x_len = np.asarray(q_len, dtype=np.int64), np.asarray(x_len, dtype=np.int64)
+    ti, tj = (q_len + ALIGN_TILE - 1) // ALIGN_TILE, (x_len + ALIGN_TILE - 1) // ALIGN_TILE
+    order = np.argsort(-(ti * tj), kind="stable")
+    order = order[(ti * tj)[order] > 0]
+    if order.size == 0:
+        return np.zeros((0, 3), dtype=np.int32)
+    cnt = (ti * tj)[order]
+    pair = np.repeat(order, cnt)
+    local = np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+    w = tj[pair]
+    return np.stack([pair, (local // w) * ALIGN_TILE, (local % w) * ALIGN_TILE], axis=1).astype(np.int32)
+
+
+def pair_sim(q, x, q_start, q_len, x_start, x_len, s_ld=None, out=None):
+    """The score matrices of many (query rows, song rows) pairs in one launch: S_p[i, j] = q[q_start[p] + i] . x[x_start[p] + j], the
+    dot of flat_l2_topk (one k-ordered fp32 fmaf chain; an element's bits depend on its two rows alone).
+
+    q (nq, d), x (nx, d): fp32 rows as the search takes them. q_start / q_len / x_start / x_len: host integer sequences, one entry per
+    pair, checked here and then uploaded; lengths may be 0, and are at most ALIGN_MAX_ROWS / ALIGN_MAX_COLS. s_ld: per pair the row
+    stride of its block (default x_len). out: a flat fp32 device tensor to write into (default: a new one; what lies between x_len
+    and s_ld is not written). Returns (S flat fp32, s_off int64 numpy, s_ld int64 numpy): pair p's block starts at S[s_off[p]]."""
+    q_start = _align_seq("pair_sim", "q_start", q_start)
+    npairs = q_start.size
+    q_len, x_start, x_len = (_align_seq("pair_sim", w, v, npairs) for w, v in (("q_len", q_len), ("x_start", x_start), ("x_len", x_len)))
+    s_ld = x_len.copy() if s_ld is None else _align_seq("pair_sim", "s_ld", s_ld, npairs)
+    if npairs and (q_start.min() < 0 or q_len.min() < 0 or x_start.min() < 0 or x_len.min() < 0):
+        raise ValueError("pair_sim: every pair needs 0 <= start and 0 <= length")
+    if npairs and (q_len.max() > ALIGN_MAX_ROWS or x_len.max() > ALIGN_MAX_COLS):
+        raise ValueError(f"pair_sim: a pair of {int(q_len.max())} x {int(x_len.max())} rows is outside the limits "
+                         f"({ALIGN_MAX_ROWS} query rows, {ALIGN_MAX_COLS} song rows); longer inputs are refused, not split")
+    ldq, ldx = _search_rows(q, "pair_sim q"), _search_rows(x, "pair_sim x")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"pair_sim: query d = {q.shape[1]} != song d = {x.shape[1]}")
+    if npairs and ((q_start + q_len).max() > q.shape[0] or (x_start + x_len).max() > x.shape[0]):
+        raise ValueError("pair_sim: every pair needs start + length <= the rows of q / x")
+    if npairs and ((s_ld < x_len).any() or s_ld.max() >= 2 ** 31):
+        raise ValueError("pair_sim: s_ld must be >= x_len for every pair")
+    if q.shape[0] >= 2 ** 31:
+        raise ValueError("pair_sim: q must have fewer than 2^31 rows")
+    size = q_len * s_ld
+    s_off = np.cumsum(size) - size
+    total = int(size.sum())
+    if out is None:
+        out = torch.empty((total,), device=q.device, dtype=torch.float32)
+    else:
+        _chk(out)
+        if out.dim() != 1 or out.numel() < total:
+            raise ValueError(f"pair_sim: out must be a flat tensor of at least {total} floats")
+    tiles = pair_sim_tiles(q_len, x_len)
+    if tiles.shape[0] == 0:
+        return out, s_off, s_ld
+    dev = q.device
+    t32 = torch.from_numpy(np.stack([q_start, q_len, x_len, s_ld]).astype(np.int32)).to(dev)
+    t64 = torch.from_numpy(np.stack([x_start, s_off])).to(dev)
+    tl = torch.from_numpy(np.ascontiguousarray(tiles)).to(dev)
+    d = q.shape[1]
+    cells = float((q_len * x_len).sum())
+    _timed("pair_sim_kernel", 2.0 * cells * d, 4.0 * cells + 4.0 * d * 2 * ALIGN_TILE * tiles.shape[0], lambda: call(
+        "nsid_pair_sim", _p(q), ldq, q.shape[0], _p(x), ldx, x.shape[0], d, _p(t32[0]), _p(t32[1]), _p(t64[0]), _p(t32[2]), _p(t64[1]),
+        _p(t32[3]), npairs, _p(tl), tiles.shape[0], _p(out), out.numel(), _stream()), (npairs, tiles.shape[0], d, 1))
+    return out, s_off, s_ld
+
+
+def local_align(S, s_off, s_ld, q_len, x_len, theta, min_score=0.0, top=16):
+    """The local alignment of include/nsid.h ("locating a sample") for many pairs in one launch, one workgroup per pair.
+
+    S: flat fp32 scores on the device; pair p's matrix starts at s_off[p], has q_len[p] rows of s_ld[p] floats and x_len[p] columns
+    (pair_sim's output, or classifier scores). s_off / s_ld / q_len / x_len: host integer sequences, checked here, then uploaded.
+    Returns (occ (pairs, top, 4) int32 = (i0, i1, j0, j1), -1 in unused slots; occ_score (pairs, top) fp32, 0 in unused slots; n_occ
+    (pairs,) int32, it can exceed top; row_h, row_j, row_org: the per-row results of all pairs, pair p's at row_off[p] + i; row_off int64
+    numpy). A pair with a zero length has n_occ = 0 (and 0, -1, -1 in its rows, if it has any)."""
+    if not isinstance(S, torch.Tensor):
+        raise TypeError("local_align: S must be a torch tensor on the GPU")
+    _chk(S)
+    S = S.reshape(-1)
+    s_off = _align_seq("local_align", "s_off", s_off)
+    npairs = s_off.size
+    s_ld, q_len, x_len = (_align_seq("local_align", w, v, npairs) for w, v in (("s_ld", s_ld), ("q_len", q_len), ("x_len", x_len)))
+    top = int(top)
+    if not 1 <= top <= ALIGN_MAX_TOP:
+        raise ValueError(f"local_align: top = {top} is outside [1, {ALIGN_MAX_TOP}]")
+    theta, min_score = float(theta), float(min_score)
+    if theta != theta or min_score != min_score:
+        raise ValueError("local_align: theta or min_score is NaN")
+    if npairs and (q_len.min() < 0 or x_len.min() < 0):
+        raise ValueError("local_align: a length is negative")
+    if npairs and (q_len.max() > ALIGN_MAX_ROWS or x_len.max() > ALIGN_MAX_COLS):
+        raise ValueError(f"local_align: a pair of {int(q_len.max())} x {int(x_len.max())} rows is outside the limits "
+                         f"({ALIGN_MAX_ROWS} query rows, {ALIGN_MAX_COLS} song rows); longer inputs are refused, not split")
+    full = (q_len > 0) & (x_len > 0)
+    if npairs and full.any() and (s_off[full].min() < 0 or (s_ld[full] < x_len[full]).any() or s_ld.max() >= 2 ** 31
+                                  or (s_off + (q_len - 1) * s_ld + x_len)[full].max() > S.numel()):
+        raise ValueError("local_align: a pair's score block (q_len rows of s_ld >= x_len floats) leaves S")
+    dev = S.device
+    row_off = np.cumsum(q_len) - q_len
+    rows = int(q_len.sum())
+    occ = torch.empty((npairs, top, 4), device=dev, dtype=torch.int32)
+    occ_score = torch.empty((npairs, top), device=dev, dtype=torch.float32)
+    n_occ = torch.empty((npairs,), device=dev, dtype=torch.int32)
+    row_h = torch.empty((rows,), device=dev, dtype=torch.float32)
+    row_j = torch.empty((rows,), device=dev, dtype=torch.int32)
+    row_org = torch.empty((rows,), device=dev, dtype=torch.int32)
+    if npairs == 0:
+        return occ, occ_score, n_occ, row_h, row_j, row_org, row_off
+    t32 = torch.from_numpy(np.stack([s_ld, q_len, x_len]).astype(np.int32)).to(dev)
+    t64 = torch.from_numpy(np.stack([np.where(full, s_off, 0), row_off])).to(dev)
+    cells = float((q_len * x_len).sum())
+    _tk("local_align_kernel", 4.0 * cells + 24.0 * rows, lambda: call(
+        "nsid_local_align", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), npairs, int(q_len.max()), int(x_len.max()), theta,
+        min_score, top, _p(t64[1]), _p(row_h), _p(row_j), _p(row_org), _p(occ), _p(occ_score), _p(n_occ), _stream()),
+        (npairs, int(q_len.max()), int(x_len.max()), top))
+    return occ, occ_score, n_occ, row_h, row_j, row_org, row_off
+
+
 # ------------------------------------------------------------------------------------------------ classifier re-rank (csrc/rerank.hip)
 CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = _H["NSID_CLF_C"], _H["NSID_CLF_KP"], _H["NSID_CLF_MAX_N"], _H["NSID_CLF_QCHUNK"]
 CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
