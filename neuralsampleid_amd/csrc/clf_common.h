@@ -1,6 +1,9 @@
 // The attention tile of the stage-2 classifier (downstream.py:30-78 CrossAttentionClassifier), shared by its evaluation kernels
 // (rerank.hip) and its training kernels (clf_train.hip): the constants, the 32 x 32 MFMA register map, the masked row softmax, the
-// column sums, the workgroup -> (group, candidate, query chunk) decode, the folded tail and the dispatch over the widths.
+// column sums, the workgroup -> (group, candidate, query chunk) decode, the folded tail and the dispatch over the widths. The head
+// of up to 4 x 4 such tiles (33 .. 128 nodes) is here as well, clf_wide_logits / _softmax / _colsums: clf_attn_fwd_wide_kernel runs
+// these three per query tile, and clf_pair_wide_kernel spells the same statements out (rerank.hip says why). So are the two small
+// pieces that the training kernels of both node ranges share, clf_av_head and clf_da.
 //
 // One tile is S^T[key][query] of 32 keys x 32 queries from v_mfma_f32_32x32x2f32 with A = K rows and B = Q rows: lane (r, hh), r =
 // lane & 31, hh = lane >> 5, holds in register i the score of query r against key acc_row(i, hh). The softmax of a query therefore
@@ -18,6 +21,9 @@ constexpr int CLF_HID = NSID_CLF_HID;      // fc.0 width
 constexpr int CLF_PW = CLF_H * CLF_HID;    // P row of the folded candidate side: one fc.0-wide block per head
 static_assert(CLF_PW == NSID_CLF_PW && NSID_CLF_KP == NSID_CLF_C + NSID_CLF_PW, "include/nsid.h states the row widths");
 static_assert(NSID_CLF_MAX_N == CLF_TILE, "the entries with one tile per side take a tile of nodes at most");
+constexpr int CLF_MAX_NODES = NSID_CLF_MAX_N_EVAL;         // nodes at most of the _n entries (the multi-tile kernels)
+constexpr int CLF_MAX_TILES = CLF_MAX_NODES / CLF_TILE;    // tiles per side at most
+static_assert(CLF_MAX_TILES == 4, "one wave of a workgroup per query / key tile; 4 x 16 accumulators per lane");
 
 // 1 / sqrt(DH), rounded to fp32
 template <int DH> struct clf_scale;
@@ -105,6 +111,123 @@ __device__ __forceinline__ float clf_colsum(float (&v)[16], int r) {
 __device__ __forceinline__ int clf_lane_key(int r, int hh) {
   const int gf = (((r >> 4) & 1) << 3) | (((r >> 3) & 1) << 2) | (((r >> 2) & 1) << 1) | ((r >> 1) & 1);
   return acc_row(gf, hh);
+}
+
+// ---- the head of several tiles (N <= CLF_MAX_NODES, nT = ceil(N / 32) tiles per side): one query tile at a time against every key
+// tile, so a row's max and sum stay in registers. K rows have LDK floats, Q rows LDQ; kh / qh = row 0 of the head's K / Q + 4 hh.
+// Keys >= N get no weight, query rows >= N no share in the column sums; row 0 is addressed in place of a row >= N. The kt loops
+// are unrolled over CLF_MAX_TILES with `kt < nT` inside, which keeps acc[] in registers.
+
+// acc[kt] = S^T[key][query] of query tile qt against key tile kt < nT: A = K rows, B = Q rows, lane (r, hh) supplies dims
+// 8 bb + 4 hh + e of its row at step (bb, e). Both fragments stream from global memory (L2) four k-steps of 8 at a time, which
+// bounds the registers in flight.
+template <int DH, int LDK, int LDQ>
+__device__ __forceinline__ void clf_wide_logits(const float* kh, const float* qh, int qt, int r, int N, int nT,
+                                                f32x16 (&acc)[CLF_MAX_TILES]) {
+  static_assert(DH % 32 == 0, "K and Q are loaded four k-steps of 8 at a time");
+  const int qrow = CLF_TILE * qt + r;
+  const bool qok = qrow < N;
+  const float* qp = qh + (size_t)(qok ? qrow : 0) * LDQ;
+#pragma unroll 1
+  for (int b0 = 0; b0 < DH / 8; b0 += 4) {
+    f32x4 qb[4], ka[CLF_MAX_TILES][4];
+#pragma unroll
+    for (int bb = 0; bb < 4; ++bb) qb[bb] = qok ? ld4(qp + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
+      if (kt < nT) {
+        const int krow = CLF_TILE * kt + r;
+        const float* kr = kh + (size_t)(krow < N ? krow : 0) * LDK;
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb) ka[kt][bb] = krow < N ? ld4(kr + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+#pragma unroll
+    for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
+      if (kt < nT) {
+#pragma unroll
+        for (int bb = 0; bb < 4; ++bb)
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kt][bb][e], qb[bb][e], acc[kt], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// the softmax of a query row over the registers of all key tiles (tile kt: keys from 32 kt) and the two lane halves: the weights
+// before the division replace the logits in acc, their sum is returned
+template <bool SCALED>
+__device__ __forceinline__ float clf_wide_softmax(f32x16 (&acc)[CLF_MAX_TILES], int hh, int N, int nT, float scale) {
+  float mx = -__builtin_inff();
+#pragma unroll
+  for (int kt = 0; kt < CLF_MAX_TILES; ++kt)
+    if (kt < nT) mx = clf_tile_max<SCALED>(acc[kt], CLF_TILE * kt, hh, N, scale, mx);
+  mx = clf_half_max(mx);
+  float sum = 0.f;
+#pragma unroll
+  for (int kt = 0; kt < CLF_MAX_TILES; ++kt)
+    if (kt < nT) sum = clf_tile_exp<SCALED>(acc[kt], acc[kt], CLF_TILE * kt, hh, N, scale, mx, sum);
+  return clf_half_sum(sum);
+}
+
+// per key tile: v = the attention weights of tile (qt, kt), handed to sink(kt, v), then added to the tile's column sums cs[kt]
+// (even lanes: key 32 kt + clf_lane_key). The sums accumulate over the query tiles in the order of the calls. Training's sink saves
+// the tile.
+template <class Sink>
+__device__ __forceinline__ void clf_wide_colsums(const f32x16 (&acc)[CLF_MAX_TILES], bool rowok, float sum, int r, int nT,
+                                                 float (&cs)[CLF_MAX_TILES], Sink&& sink) {
+#pragma unroll
+  for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
+    if (kt < nT) {
+      float v[16];
+      clf_tile_norm(acc[kt], v, rowok, sum);
+      sink(kt, v);
+      cs[kt] += clf_colsum(v, r);
+    }
+  }
+}
+
+// ---- training, both node ranges. obar_h = a_h^T V_h: ah = the head's N column means (LDS), vh = V_h of the candidate's row 0 (rows
+// of LDV floats), oh = the head's DH columns of the pair's obar. One wave, 64 columns at a time (the last block of DH = 160 is half
+// full).
+template <int DH, int LDV>
+__device__ __forceinline__ void clf_av_head(const float* ah, const float* vh, int N, int lane, float* oh) {
+  constexpr int OB = (DH + 63) / 64;
+  float o[OB];
+#pragma unroll
+  for (int t = 0; t < OB; ++t) o[t] = 0.f;
+  for (int m = 0; m < N; ++m) {
+    const float a = ah[m];
+#pragma unroll
+    for (int t = 0; t < OB; ++t)
+      if (DH % 64 == 0 || 64 * t + lane < DH) o[t] = fmaf(a, vh[(size_t)m * LDV + 64 * t + lane], o[t]);
+  }
+#pragma unroll
+  for (int t = 0; t < OB; ++t)
+    if (DH % 64 == 0 || 64 * t + lane < DH) oh[64 * t + lane] = o[t];
+}
+
+// V_h[key] . do_h on both lane halves of the key's lane: half hh of the DH dims on each, the halves added in one order on both. vh as
+// above; a key >= N is not read and gives 0
+template <int DH, int LDV>
+__device__ __forceinline__ float clf_da(const float* vh, const float* doh, int key, int N, int hh) {
+  constexpr int HALF = DH / 2;
+  float part = 0.f;
+  if (key < N) {
+    const float* vr = vh + (size_t)key * LDV + HALF * hh;
+    const float* dr = doh + HALF * hh;
+#pragma unroll 4
+    for (int e = 0; e < HALF; e += 4) {
+      const f32x4 a = ld4(vr + e), b = ld4(dr + e);
+      part = fmaf(a[0], b[0], part);
+      part = fmaf(a[1], b[1], part);
+      part = fmaf(a[2], b[2], part);
+      part = fmaf(a[3], b[3], part);
+    }
+  }
+  const float other = __shfl_xor(part, 32);
+  return hh == 0 ? part + other : other + part;
 }
 
 // ---- pair lists of the evaluation kernels. Group g: {first query segment, query segments, offset into cidx, candidates}; its

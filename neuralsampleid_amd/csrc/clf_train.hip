@@ -18,8 +18,10 @@
 //
 // Nodes: N <= 32 (CLF_TILE), one 32 x 32 tile per head. The tile arithmetic (register map, masked softmax, column sums) and the
 // width dispatch are clf_common.h's, shared with the evaluation kernels, so a trained state scores there what it scores here.
-// 1 <= N <= 128 (the _n entries): the *_wide_kernel forms below run a head's attention as up to 4 x 4 such tiles with the same
-// tile arithmetic; saved attention (P, 4, nT, nT, 16, 64), nT = ceil(N / 32), abar (P, 4, 128).
+// 1 <= N <= 128 (the _n entries): the *_wide_kernel forms below run a head's attention as up to 4 x 4 such tiles; the forward's head
+// is clf_common.h's clf_wide_logits / _softmax / _colsums, statement for statement the evaluation kernel's for these node counts.
+// Saved attention (P, 4, nT, nT, 16, 64), nT = ceil(N / 32), abar (P, 4, 128). Both node ranges share clf_av_head (obar) and clf_da
+// (the backward's da) from there; each operation has one host function, launch_*(wide, ...), behind its _c, _n and C = 512 entries.
 #include "clf_common.h"
 
 namespace {
@@ -27,9 +29,6 @@ namespace {
 constexpr int CT_MINE_MAXN = NSID_CLF_MINE_MAX_ROWS;   // rows of the mining pool (2B) at most: their dots live in LDS
 constexpr int CT_MINE_MAXD = NSID_CLF_MINE_MAX_D;
 constexpr int CT_RED_THREADS = 512;  // nsid_clf_seg_reduce: one workgroup per segment, C / 64 float4 per thread cover N x C
-constexpr int CW_N = NSID_CLF_MAX_N_EVAL;   // nodes at most of the _n entries (the multi-tile kernels)
-constexpr int CW_T = CW_N / CLF_TILE;       // tiles per side at most
-static_assert(CW_T == 4, "one wave of a workgroup per query / key tile");
 
 // ------------------------------------------------------------------------------------------------ hard-negative mining
 // (v, j) precedes (w, k) in the descending order with ties to the smaller index
@@ -100,7 +99,6 @@ __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restri
                                                            float* __restrict__ abar) {
   static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels");
   constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;        // [K | V] rows
-  constexpr int OB = (DH + 63) / 64;                         // 64-column blocks of a head's output
   __shared__ float abs_[4][CLF_TILE];
   const int lane = lane_id(), w = threadIdx.x >> 6;
   const int r = lane & 31, hh = lane >> 5;
@@ -137,126 +135,59 @@ __global__ __launch_bounds__(256) void clf_attn_fwd_kernel(const float* __restri
       abar[((size_t)p * CLF_H + h) * CLF_TILE + jf] = cs * invN;
     }
     __builtin_amdgcn_wave_barrier();
-    float o[OB];
-#pragma unroll
-    for (int t = 0; t < OB; ++t) o[t] = 0.f;
-    for (int m = 0; m < N; ++m) {
-      const float a = abs_[w][m];
-#pragma unroll
-      for (int t = 0; t < OB; ++t)
-        if (DH % 64 == 0 || 64 * t + lane < DH) o[t] = fmaf(a, vb[(size_t)m * CT_KV + h * CT_DH + 64 * t + lane], o[t]);
-    }
-#pragma unroll
-    for (int t = 0; t < OB; ++t)
-      if (DH % 64 == 0 || 64 * t + lane < DH) obar[(size_t)p * CT_C + h * CT_DH + 64 * t + lane] = o[t];
+    clf_av_head<DH, CT_KV>(abs_[w], vb + h * CT_DH, N, lane, obar + (size_t)p * CT_C + h * CT_DH);
     __builtin_amdgcn_wave_barrier();
   }
 }
 
 // ---- 1 <= N <= 128 (nsid_clf_attn_fwd_n): a head's attention is nT x nT tiles of 32 x 32, nT = ceil(N / 32) ----------------------------
-// One workgroup per pair, wave h = head h (the heads write disjoint columns of obar). Per query tile the wave holds S^T against
-// every key tile (4 x 16 accumulators, K and Q fragments streamed from global memory as in rerank.hip's clf_pair_wide_kernel), so
-// a row's max and sum stay in registers; the column sums of a key tile accumulate over the query tiles in tile order. Saved
-// attention: (P, 4, nT, nT, 16, 64), tile (qt, kt) of a head in the register layout above (zero on keys >= N and query rows >= N).
+// One workgroup per pair, wave h = head h (the heads write disjoint columns of obar). The head's logits, softmax and column sums
+// are clf_common.h's clf_wide_logits / _softmax / _colsums, statement for statement what clf_pair_wide_kernel scores with; the sink saves each tile here. Saved attention:
+// (P, 4, nT, nT, 16, 64), tile (qt, kt) of a head in the register layout above (zero on keys >= N and query rows >= N).
 // abar (P, 4, 128), zero past N. No row >= N of a segment is addressed.
 template <int C, int DH>
 __global__ __launch_bounds__(256) void clf_attn_fwd_wide_kernel(const float* __restrict__ q, int nq_seg, const float* __restrict__ kv,
                                                                 int nc_seg, int N, const int* __restrict__ qi,
                                                                 const int* __restrict__ ci, int P, float* __restrict__ obar,
                                                                 float* __restrict__ attn, float* __restrict__ abar) {
-  static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels; K and Q are loaded four k-steps of 8 at a time");
+  static_assert(C == CLF_H * DH, "4 heads of DH channels");
   constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;        // [K | V] rows
-  constexpr int OB = (DH + 63) / 64;                         // 64-column blocks of a head's output
-  __shared__ float abs_[CLF_H][CW_N];
+  __shared__ float abs_[CLF_H][CLF_MAX_NODES];
   const int lane = lane_id(), h = threadIdx.x >> 6;
   const int r = lane & 31, hh = lane >> 5;
   const int p = blockIdx.x;                                  // the grid is P workgroups
   const int qseg = qi[p], cseg = ci[p];
   if (qseg < 0 || qseg >= nq_seg || cseg < 0 || cseg >= nc_seg) return;      // uniform over the workgroup
-  const float scale = clf_scale<DH>::v;
   const float invN = 1.0f / (float)N;
   const int nT = (N + CLF_TILE - 1) / CLF_TILE;
   const float* qh = q + (size_t)qseg * N * CT_C + h * CT_DH + 4 * hh;
   const float* kh = kv + (size_t)cseg * N * CT_KV + h * CT_DH + 4 * hh;
-  const float* vb = kv + (size_t)cseg * N * CT_KV + CT_C + h * CT_DH;
+  const float* vh = kv + (size_t)cseg * N * CT_KV + CT_C + h * CT_DH;
   float* ap = attn + ((size_t)p * CLF_H + h) * nT * nT * (16 * 64) + lane;
   const int jf = clf_lane_key(r, hh);
 
-  float cs[CW_T] = {0.f, 0.f, 0.f, 0.f};           // column sums of the key tiles (even lanes: key 32 kt + jf)
+  float cs[CLF_MAX_TILES] = {0.f, 0.f, 0.f, 0.f};  // column sums of the key tiles (even lanes: key 32 kt + jf)
 #pragma unroll 1
   for (int qt = 0; qt < nT; ++qt) {
-    const int qrow = CLF_TILE * qt + r;
-    const bool qok = qrow < N;
-    const float* qp = qh + (size_t)(qok ? qrow : 0) * CT_C;
-    f32x16 acc[CW_T] = {};
-#pragma unroll 1
-    for (int b0 = 0; b0 < CT_DH / 8; b0 += 4) {
-      f32x4 qb[4], ka[CW_T][4];
+    f32x16 acc[CLF_MAX_TILES] = {};
+    clf_wide_logits<DH, CT_KV, CT_C>(kh, qh, qt, r, N, nT, acc);
+    const float sum = clf_wide_softmax<true>(acc, hh, N, nT, clf_scale<DH>::v);
+    clf_wide_colsums(acc, CLF_TILE * qt + r < N, sum, r, nT, cs, [&](int kt, const float (&v)[16]) {
+      float* at = ap + (size_t)(qt * nT + kt) * (16 * 64);      // the saved tile (qt, kt)
 #pragma unroll
-      for (int bb = 0; bb < 4; ++bb) qb[bb] = qok ? ld4(qp + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int kt = 0; kt < CW_T; ++kt) {
-        if (kt < nT) {
-          const int krow = CLF_TILE * kt + r;
-          const float* kr = kh + (size_t)(krow < N ? krow : 0) * CT_KV;
-#pragma unroll
-          for (int bb = 0; bb < 4; ++bb) ka[kt][bb] = krow < N ? ld4(kr + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-      }
-#pragma unroll
-      for (int kt = 0; kt < CW_T; ++kt) {
-        if (kt < nT) {
-#pragma unroll
-          for (int bb = 0; bb < 4; ++bb)
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-              acc[kt] = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[kt][bb][e], qb[bb][e], acc[kt], 0, 0, 0);
-        }
-      }
-    }
-    float mx = -__builtin_inff();
-#pragma unroll
-    for (int kt = 0; kt < CW_T; ++kt)
-      if (kt < nT) mx = clf_tile_max<true>(acc[kt], CLF_TILE * kt, hh, N, scale, mx);
-    mx = clf_half_max(mx);
-    float sum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < CW_T; ++kt)
-      if (kt < nT) sum = clf_tile_exp<true>(acc[kt], acc[kt], CLF_TILE * kt, hh, N, scale, mx, sum);
-    sum = clf_half_sum(sum);
-#pragma unroll
-    for (int kt = 0; kt < CW_T; ++kt) {
-      if (kt < nT) {
-        float v[16];
-        clf_tile_norm(acc[kt], v, qok, sum);
-        float* at = ap + (size_t)(qt * nT + kt) * (16 * 64);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) at[i * 64] = v[i];
-        cs[kt] += clf_colsum(v, r);
-      }
-    }
+      for (int i = 0; i < 16; ++i) at[i * 64] = v[i];
+    });
   }
   if ((r & 1) == 0) {
 #pragma unroll
-    for (int kt = 0; kt < CW_T; ++kt) {
+    for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
       const float a = kt < nT ? cs[kt] * invN : 0.f;
       abs_[h][CLF_TILE * kt + jf] = a;
-      abar[((size_t)p * CLF_H + h) * CW_N + CLF_TILE * kt + jf] = a;
+      abar[((size_t)p * CLF_H + h) * CLF_MAX_NODES + CLF_TILE * kt + jf] = a;
     }
   }
   __builtin_amdgcn_wave_barrier();
-  float o[OB];
-#pragma unroll
-  for (int t = 0; t < OB; ++t) o[t] = 0.f;
-  for (int m = 0; m < N; ++m) {
-    const float a = abs_[h][m];
-#pragma unroll
-    for (int t = 0; t < OB; ++t)
-      if (DH % 64 == 0 || 64 * t + lane < DH) o[t] = fmaf(a, vb[(size_t)m * CT_KV + 64 * t + lane], o[t]);
-  }
-#pragma unroll
-  for (int t = 0; t < OB; ++t)
-    if (DH % 64 == 0 || 64 * t + lane < DH) obar[(size_t)p * CT_C + h * CT_DH + 64 * t + lane] = o[t];
+  clf_av_head<DH, CT_KV>(abs_[h], vh, N, lane, obar + (size_t)p * CT_C + h * CT_DH);
 }
 
 // ------------------------------------------------------------------------------------------------ head: relu, dropout, fc.3, sigmoid
@@ -328,7 +259,7 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
                                                            int nc_seg, int N, const int* __restrict__ qi, const int* __restrict__ ci,
                                                            int P, float* __restrict__ dq, float* __restrict__ dk) {
   static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels");
-  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C, HALF = DH / 2;
+  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;
   __shared__ float dsT[4][CLF_TILE][CLF_TILE + 1];
   __shared__ float das[4][CLF_TILE];
   const int lane = lane_id(), w = threadIdx.x >> 6;
@@ -348,22 +279,8 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_kernel(const float* __restri
 
 #pragma unroll 1
   for (int h = 0; h < CLF_H; ++h) {
-    // da[key r] = V[r][h] . do[h]: half hh of the DH dims on each lane half, halves added in one order on both
-    float part = 0.f;
-    if (rin) {
-      const float* vr = krow + (size_t)r * CT_KV + CT_C + h * CT_DH + HALF * hh;
-      const float* dr = dop + h * CT_DH + HALF * hh;
-#pragma unroll 4
-      for (int e = 0; e < HALF; e += 4) {
-        const f32x4 a = ld4(vr + e), b = ld4(dr + e);
-        part = fmaf(a[0], b[0], part);
-        part = fmaf(a[1], b[1], part);
-        part = fmaf(a[2], b[2], part);
-        part = fmaf(a[3], b[3], part);
-      }
-    }
-    const float other = __shfl_xor(part, 32);
-    const float da = hh == 0 ? part + other : other + part;
+    // da[key r] = V[r][h] . do[h] / N
+    const float da = clf_da<DH, CT_KV>(krow + CT_C + h * CT_DH, dop + h * CT_DH, r, N, hh);
     if (hh == 0) das[w][r] = rin ? da * invN : 0.f;
     __builtin_amdgcn_wave_barrier();
     const float* ap = attn + ((size_t)p * CLF_H + h) * 16 * 64 + lane;
@@ -435,9 +352,9 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_wide_kernel(const float* __r
                                                                 const int* __restrict__ ci, int P, float* __restrict__ dq,
                                                                 float* __restrict__ dk) {
   static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels");
-  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C, HALF = DH / 2;
-  __shared__ float dsp[CW_N][CW_N + 1];                      // dS[query][key] of the head
-  __shared__ float das[CW_N];
+  constexpr int CT_C = C, CT_DH = DH, CT_KV = 2 * C;
+  __shared__ float dsp[CLF_MAX_NODES][CLF_MAX_NODES + 1];                      // dS[query][key] of the head
+  __shared__ float das[CLF_MAX_NODES];
   const int lane = lane_id(), w = threadIdx.x >> 6;
   const int r = lane & 31, hh = lane >> 5;
   const int p = (int)(blockIdx.x >> 2), h = (int)(blockIdx.x & 3);      // the grid is 4 P workgroups
@@ -452,35 +369,20 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_wide_kernel(const float* __r
   float* dqp = dq + (size_t)p * N * CT_C + h * CT_DH;
   float* dkp = dk + (size_t)p * N * CT_C + h * CT_DH;
 
-  {  // da[key] = V_h[key] . do_h / N for the keys of tile w: half hh of the DH dims on each lane half, halves added in one order
+  {  // da[key] = V_h[key] . do_h / N for the keys of tile w
     const int key = CLF_TILE * w + r;
-    const bool kin = key < N;
-    float part = 0.f;
-    if (kin) {
-      const float* vr = krow + (size_t)key * CT_KV + CT_C + HALF * hh;
-      const float* dr = dop + HALF * hh;
-#pragma unroll 4
-      for (int e = 0; e < HALF; e += 4) {
-        const f32x4 a = ld4(vr + e), b = ld4(dr + e);
-        part = fmaf(a[0], b[0], part);
-        part = fmaf(a[1], b[1], part);
-        part = fmaf(a[2], b[2], part);
-        part = fmaf(a[3], b[3], part);
-      }
-    }
-    const float other = __shfl_xor(part, 32);
-    const float da = hh == 0 ? part + other : other + part;
-    if (hh == 0) das[key] = kin ? da * invN : 0.f;
+    const float da = clf_da<DH, CT_KV>(krow + CT_C, dop, key, N, hh);
+    if (hh == 0) das[key] = key < N ? da * invN : 0.f;
   }
   __syncthreads();
 
   if (w < nT) {
     const int qt = w;
     const float* ap = attn + (((size_t)p * CLF_H + h) * nT + qt) * nT * (16 * 64) + lane;
-    float dS[CW_T][16];
+    float dS[CLF_MAX_TILES][16];
     float t = 0.f;
 #pragma unroll
-    for (int kt = 0; kt < CW_T; ++kt) {
+    for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
       if (kt < nT) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -492,7 +394,7 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_wide_kernel(const float* __r
     const float to = __shfl_xor(t, 32);
     const float tr = hh == 0 ? t + to : to + t;          // rowsum over all keys of query 32 qt + r
 #pragma unroll
-    for (int kt = 0; kt < CW_T; ++kt) {
+    for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
       if (kt < nT) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -507,7 +409,7 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_wide_kernel(const float* __r
     for (int d0 = 0; d0 < CT_DH; d0 += 32) {
       f32x16 acc = {};
 #pragma unroll
-      for (int kt = 0; kt < CW_T; ++kt) {
+      for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
         if (kt < nT) {
 #pragma unroll
           for (int s = 0; s < 16; ++s) {
@@ -529,9 +431,9 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_wide_kernel(const float* __r
   if (w < nT) {
     const int kt = w;
     // dK[key][d0 + c] = sum_query dS[query][key] Q[query][d0 + c]; step (qt, s): k index hh = query 32 qt + 2 s + hh
-    float dT[CW_T][16];
+    float dT[CLF_MAX_TILES][16];
 #pragma unroll
-    for (int qt = 0; qt < CW_T; ++qt) {
+    for (int qt = 0; qt < CLF_MAX_TILES; ++qt) {
       if (qt < nT) {
 #pragma unroll
         for (int s = 0; s < 16; ++s) dT[qt][s] = dsp[CLF_TILE * qt + 2 * s + hh][CLF_TILE * kt + r];
@@ -541,7 +443,7 @@ __global__ __launch_bounds__(256) void clf_attn_bwd_wide_kernel(const float* __r
     for (int d0 = 0; d0 < CT_DH; d0 += 32) {
       f32x16 acc = {};
 #pragma unroll
-      for (int qt = 0; qt < CW_T; ++qt) {
+      for (int qt = 0; qt < CLF_MAX_TILES; ++qt) {
         if (qt < nT) {
 #pragma unroll
           for (int s = 0; s < 16; ++s) {
@@ -651,7 +553,61 @@ __global__ __launch_bounds__(CT_RED_THREADS) void clf_seg_reduce_wide_kernel(con
                                                                              const int* __restrict__ ci, int P, int N, int nq_seg,
                                                                              float* __restrict__ dq_seg, float* __restrict__ dkv_seg) {
   const int n0 = CLF_TILE * (int)blockIdx.y;
-  clf_seg_reduce_rows<C, DH, CW_N>(dq, dk, abar, dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg, n0, min(CLF_TILE, N - n0));
+  clf_seg_reduce_rows<C, DH, CLF_MAX_NODES>(dq, dk, abar, dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg, n0, min(CLF_TILE, N - n0));
+}
+
+// ---- one host function per operation. wide: the _n entry (N <= 128, the *_wide_kernel and its grid), else the _c entry (N <= 32)
+int launch_attn_fwd(bool wide, const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
+                    int P, float* obar, float* attn, float* abar, void* stream) {
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= (wide ? CLF_MAX_NODES : CLF_TILE) && P >= 0 && P <= (1 << 28));
+  if (P == 0) return NSID_OK;
+  NSID_REQUIRE(q && kv && qi && ci && obar && attn && abar && nsid_aligned16(q) && nsid_aligned16(kv));
+  nsid_count(wide ? NSID_C_clf_attn_fwd_n : NSID_C_clf_attn_fwd);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (wide) {      // a workgroup per pair
+    CLF_LAUNCH_C(C, clf_attn_fwd_wide_kernel, dim3(P), dim3(256), st, q, nq_seg, kv, nc_seg, N, qi, ci, P, obar, attn, abar);
+  } else {         // a wave per pair
+    CLF_LAUNCH_C(C, clf_attn_fwd_kernel, dim3((P + 3) / 4), dim3(256), st, q, nq_seg, kv, nc_seg, N, qi, ci, P, obar, attn, abar);
+  }
+  return nsid_launch_status();
+}
+
+int launch_attn_bwd(bool wide, const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int C,
+                    int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= (wide ? CLF_MAX_NODES : CLF_TILE) && P >= 0 && P <= (1 << 28));
+  if (P == 0) return NSID_OK;
+  NSID_REQUIRE(dobar && attn && q && kv && qi && ci && dq && dk && nsid_aligned16(dobar) && nsid_aligned16(kv));
+  nsid_count(wide ? NSID_C_clf_attn_bwd_n : NSID_C_clf_attn_bwd);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (wide) {      // a workgroup per (pair, head)
+    CLF_LAUNCH_C(C, clf_attn_bwd_wide_kernel, dim3(4u * (unsigned)P), dim3(256), st, dobar, attn, q, nq_seg, kv, nc_seg, N, qi, ci, P,
+                 dq, dk);
+  } else {         // a wave per pair
+    CLF_LAUNCH_C(C, clf_attn_bwd_kernel, dim3((P + 3) / 4), dim3(256), st, dobar, attn, q, nq_seg, kv, nc_seg, N, qi, ci, P, dq, dk);
+  }
+  return nsid_launch_status();
+}
+
+int launch_seg_reduce(bool wide, const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi, const int* ci,
+                      int P, int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream) {
+  NSID_REQUIRE(clf_width_ok(C));
+  NSID_REQUIRE(P >= 0 && P <= (1 << 28) && N >= 1 && N <= (wide ? CLF_MAX_NODES : CLF_TILE) && nq_seg >= 0 && nc_seg >= 0 &&
+               nq_seg + nc_seg <= (1 << 30));
+  if (nq_seg + nc_seg == 0) return NSID_OK;
+  NSID_REQUIRE((P == 0 || (dq && dk && abar && dobar && qi && ci)) && dq_seg && dkv_seg);
+  NSID_REQUIRE(nsid_aligned16(dq) && nsid_aligned16(dk) && nsid_aligned16(dobar) && nsid_aligned16(dq_seg) && nsid_aligned16(dkv_seg));
+  nsid_count(wide ? NSID_C_clf_seg_reduce_n : NSID_C_clf_seg_reduce);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (wide) {      // a workgroup per (segment, node tile)
+    CLF_LAUNCH_C(C, clf_seg_reduce_wide_kernel, dim3(nq_seg + nc_seg, (N + CLF_TILE - 1) / CLF_TILE), dim3(CT_RED_THREADS), st, dq, dk,
+                 abar, dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg);
+  } else {         // a workgroup per segment
+    CLF_LAUNCH_C(C, clf_seg_reduce_kernel, dim3(nq_seg + nc_seg), dim3(CT_RED_THREADS), st, dq, dk, abar, dobar, qi, ci, P, N, nq_seg,
+                 dq_seg, dkv_seg);
+  }
+  return nsid_launch_status();
 }
 
 }  // namespace
@@ -664,23 +620,6 @@ extern "C" int nsid_clf_mine_hard_negatives(const float* zq, int nq, const float
   nsid_count(NSID_C_clf_mine);
   NSID_LAUNCH(clf_mine_kernel, dim3(nq), dim3(256), 0, static_cast<hipStream_t>(stream), zq, za, na, d, k, out);
   return nsid_launch_status();
-}
-
-extern "C" int nsid_clf_attn_fwd_c(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
-                                   int P, float* obar, float* attn, float* abar, void* stream) {
-  NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CLF_TILE && P >= 0 && P <= (1 << 28));
-  if (P == 0) return NSID_OK;
-  NSID_REQUIRE(q && kv && qi && ci && obar && attn && abar && nsid_aligned16(q) && nsid_aligned16(kv));
-  nsid_count(NSID_C_clf_attn_fwd);
-  CLF_LAUNCH_C(C, clf_attn_fwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), q, nq_seg, kv, nc_seg, N, qi,
-               ci, P, obar, attn, abar);
-  return nsid_launch_status();
-}
-
-extern "C" int nsid_clf_attn_fwd(const float* q, int nq_seg, const float* kv, int nc_seg, int N, const int* qi, const int* ci, int P,
-                                 float* obar, float* attn, float* abar, void* stream) {
-  return nsid_clf_attn_fwd_c(q, nq_seg, kv, nc_seg, NSID_CLF_C, N, qi, ci, P, obar, attn, abar, stream);
 }
 
 extern "C" int nsid_clf_head_fwd(const float* hid, const float* keep, const float* w2, const float* b2, int P, float* s, void* stream) {
@@ -706,77 +645,51 @@ extern "C" int nsid_clf_head_bwd(const float* ds, const float* s, const float* h
   return nsid_launch_status();
 }
 
-extern "C" int nsid_clf_attn_bwd_c(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
-                                   int C, int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
-  NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CLF_TILE && P >= 0 && P <= (1 << 28));
-  if (P == 0) return NSID_OK;
-  NSID_REQUIRE(dobar && attn && q && kv && qi && ci && dq && dk && nsid_aligned16(dobar) && nsid_aligned16(kv));
-  nsid_count(NSID_C_clf_attn_bwd);
-  CLF_LAUNCH_C(C, clf_attn_bwd_kernel, dim3((P + 3) / 4), dim3(256), static_cast<hipStream_t>(stream), dobar, attn, q, nq_seg, kv,
-               nc_seg, N, qi, ci, P, dq, dk);
-  return nsid_launch_status();
+// ---- the attention and the per-segment sums: _c at N <= 32, _n at 1 <= N <= 128 (the multi-tile kernels), the plain names at C = 512
+extern "C" int nsid_clf_attn_fwd_c(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
+                                   int P, float* obar, float* attn, float* abar, void* stream) {
+  return launch_attn_fwd(false, q, nq_seg, kv, nc_seg, C, N, qi, ci, P, obar, attn, abar, stream);
 }
 
-extern "C" int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg, int N,
-                                 const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
-  return nsid_clf_attn_bwd_c(dobar, attn, q, nq_seg, kv, nc_seg, NSID_CLF_C, N, qi, ci, P, dq, dk, stream);
+extern "C" int nsid_clf_attn_fwd_n(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
+                                   int P, float* obar, float* attn, float* abar, void* stream) {
+  return launch_attn_fwd(true, q, nq_seg, kv, nc_seg, C, N, qi, ci, P, obar, attn, abar, stream);
+}
+
+extern "C" int nsid_clf_attn_fwd(const float* q, int nq_seg, const float* kv, int nc_seg, int N, const int* qi, const int* ci,
+                                 int P, float* obar, float* attn, float* abar, void* stream) {
+  return launch_attn_fwd(false, q, nq_seg, kv, nc_seg, NSID_CLF_C, N, qi, ci, P, obar, attn, abar, stream);
+}
+
+extern "C" int nsid_clf_attn_bwd_c(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
+                                   int C, int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+  return launch_attn_bwd(false, dobar, attn, q, nq_seg, kv, nc_seg, C, N, qi, ci, P, dq, dk, stream);
+}
+
+extern "C" int nsid_clf_attn_bwd_n(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
+                                   int C, int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+  return launch_attn_bwd(true, dobar, attn, q, nq_seg, kv, nc_seg, C, N, qi, ci, P, dq, dk, stream);
+}
+
+extern "C" int nsid_clf_attn_bwd(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
+                                 int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
+  return launch_attn_bwd(false, dobar, attn, q, nq_seg, kv, nc_seg, NSID_CLF_C, N, qi, ci, P, dq, dk, stream);
 }
 
 extern "C" int nsid_clf_seg_reduce_c(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
                                      const int* ci, int P, int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg,
                                      void* stream) {
-  NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(P >= 0 && P <= (1 << 28) && N >= 1 && N <= CLF_TILE && nq_seg >= 0 && nc_seg >= 0 && nq_seg + nc_seg <= (1 << 30));
-  if (nq_seg + nc_seg == 0) return NSID_OK;
-  NSID_REQUIRE((P == 0 || (dq && dk && abar && dobar && qi && ci)) && dq_seg && dkv_seg);
-  NSID_REQUIRE(nsid_aligned16(dq) && nsid_aligned16(dk) && nsid_aligned16(dobar) && nsid_aligned16(dq_seg) && nsid_aligned16(dkv_seg));
-  nsid_count(NSID_C_clf_seg_reduce);
-  CLF_LAUNCH_C(C, clf_seg_reduce_kernel, dim3(nq_seg + nc_seg), dim3(CT_RED_THREADS), static_cast<hipStream_t>(stream), dq, dk, abar,
-               dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg);
-  return nsid_launch_status();
-}
-
-extern "C" int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
-                                   const int* ci, int P, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg, void* stream) {
-  return nsid_clf_seg_reduce_c(dq, dk, abar, dobar, qi, ci, P, NSID_CLF_C, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
-}
-
-// ---- the _n entries: 1 <= N <= 128, the multi-tile kernels; arguments as the _c entries
-extern "C" int nsid_clf_attn_fwd_n(const float* q, int nq_seg, const float* kv, int nc_seg, int C, int N, const int* qi, const int* ci,
-                                   int P, float* obar, float* attn, float* abar, void* stream) {
-  NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CW_N && P >= 0 && P <= (1 << 28));
-  if (P == 0) return NSID_OK;
-  NSID_REQUIRE(q && kv && qi && ci && obar && attn && abar && nsid_aligned16(q) && nsid_aligned16(kv));
-  nsid_count(NSID_C_clf_attn_fwd_n);
-  CLF_LAUNCH_C(C, clf_attn_fwd_wide_kernel, dim3(P), dim3(256), static_cast<hipStream_t>(stream), q, nq_seg, kv, nc_seg, N, qi, ci, P,
-               obar, attn, abar);
-  return nsid_launch_status();
-}
-
-extern "C" int nsid_clf_attn_bwd_n(const float* dobar, const float* attn, const float* q, int nq_seg, const float* kv, int nc_seg,
-                                   int C, int N, const int* qi, const int* ci, int P, float* dq, float* dk, void* stream) {
-  NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(nq_seg >= 1 && nc_seg >= 1 && N >= 1 && N <= CW_N && P >= 0 && P <= (1 << 28));
-  if (P == 0) return NSID_OK;
-  NSID_REQUIRE(dobar && attn && q && kv && qi && ci && dq && dk && nsid_aligned16(dobar) && nsid_aligned16(kv));
-  nsid_count(NSID_C_clf_attn_bwd_n);
-  CLF_LAUNCH_C(C, clf_attn_bwd_wide_kernel, dim3(4u * (unsigned)P), dim3(256), static_cast<hipStream_t>(stream), dobar, attn, q,
-               nq_seg, kv, nc_seg, N, qi, ci, P, dq, dk);
-  return nsid_launch_status();
+  return launch_seg_reduce(false, dq, dk, abar, dobar, qi, ci, P, C, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
 }
 
 extern "C" int nsid_clf_seg_reduce_n(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
                                      const int* ci, int P, int C, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg,
                                      void* stream) {
-  NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(P >= 0 && P <= (1 << 28) && N >= 1 && N <= CW_N && nq_seg >= 0 && nc_seg >= 0 && nq_seg + nc_seg <= (1 << 30));
-  if (nq_seg + nc_seg == 0) return NSID_OK;
-  NSID_REQUIRE((P == 0 || (dq && dk && abar && dobar && qi && ci)) && dq_seg && dkv_seg);
-  NSID_REQUIRE(nsid_aligned16(dq) && nsid_aligned16(dk) && nsid_aligned16(dobar) && nsid_aligned16(dq_seg) && nsid_aligned16(dkv_seg));
-  nsid_count(NSID_C_clf_seg_reduce_n);
-  CLF_LAUNCH_C(C, clf_seg_reduce_wide_kernel, dim3(nq_seg + nc_seg, (N + CLF_TILE - 1) / CLF_TILE), dim3(CT_RED_THREADS),
-               static_cast<hipStream_t>(stream), dq, dk, abar, dobar, qi, ci, P, N, nq_seg, dq_seg, dkv_seg);
-  return nsid_launch_status();
+  return launch_seg_reduce(true, dq, dk, abar, dobar, qi, ci, P, C, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
+}
+
+extern "C" int nsid_clf_seg_reduce(const float* dq, const float* dk, const float* abar, const float* dobar, const int* qi,
+                                   const int* ci, int P, int N, int nq_seg, int nc_seg, float* dq_seg, float* dkv_seg,
+                                   void* stream) {
+  return launch_seg_reduce(false, dq, dk, abar, dobar, qi, ci, P, NSID_CLF_C, N, nq_seg, nc_seg, dq_seg, dkv_seg, stream);
 }

@@ -158,8 +158,9 @@ __global__ __launch_bounds__(512) void clf_pair_kernel(const float* __restrict__
 // (4 x 16 accumulator registers), so a row's max and sum are in registers; the column sums of a key tile accumulate over the query
 // tiles in their order. A pair's partial hidden vector waits in LDS between two heads (lane-private slots). Keys >= N get no weight,
 // query rows >= N no share in the column mean, which divides by N; no row >= N of a segment is addressed.
-constexpr int RW_N = NSID_CLF_MAX_N_EVAL;      // nodes per segment at most
-constexpr int RW_T = RW_N / 32;      // tiles per side
+// The query-tile loop below is, statement for statement, clf_common.h's clf_wide_logits / _softmax / _colsums with SCALED = false
+// and an empty sink, which the training forward calls. It is written out here because the helper form measured 0.2 % slower on the
+// hit-rate-like block at 128 nodes (docs/experiments.md, "One multi-tile head"); a change to either goes into both.
 constexpr int RW_SLOTS = RR_QCH / RR_WAVES;   // segments of a chunk per wave
 
 template <int C, int DH>
@@ -171,9 +172,9 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
                                                             int64_t out_len) {
   static_assert(C == CLF_H * DH && DH % 32 == 0, "4 heads of DH channels; K and Q are loaded four k-steps of 8 at a time");
   constexpr int LDKP = C + CLF_PW;      // the candidates' projected rows: [K | P]
-  __shared__ __attribute__((aligned(16))) float ps[RW_N][CLF_HID];          // P_h of the candidate
+  __shared__ __attribute__((aligned(16))) float ps[CLF_MAX_NODES][CLF_HID];          // P_h of the candidate
   __shared__ float hacc[RR_QCH][CLF_HID];                                   // the pairs' hidden vectors between two heads
-  __shared__ float abar[RR_WAVES][RW_N];
+  __shared__ float abar[RR_WAVES][CLF_MAX_NODES];
 
   const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
   const int r = lane & 31, hh = lane >> 5;
@@ -207,7 +208,7 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
       const float* qs = q + (size_t)qseg * N * C + h * DH + 4 * hh;
       const float* kh = kc + h * DH + 4 * hh;
 
-      float cs[RW_T] = {0.f, 0.f, 0.f, 0.f};           // column sums of the key tiles (even lanes: key 32 kt + jf)
+      float cs[CLF_MAX_TILES] = {0.f, 0.f, 0.f, 0.f};  // column sums of the key tiles (even lanes: key 32 kt + jf)
 #pragma unroll 1
       for (int qt = 0; qt < nT; ++qt) {
         // S^T[key][query] of query tile qt against every key tile: A = K rows, B = Q rows; lane (r, hh) supplies dims
@@ -215,14 +216,14 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
         const int qrow = 32 * qt + r;
         const bool qok = qrow < N;
         const float* qp = qs + (size_t)(qok ? qrow : 0) * C;
-        f32x16 acc[RW_T] = {};
+        f32x16 acc[CLF_MAX_TILES] = {};
 #pragma unroll 1
         for (int b0 = 0; b0 < DH / 8; b0 += 4) {
-          f32x4 qb[4], ka[RW_T][4];
+          f32x4 qb[4], ka[CLF_MAX_TILES][4];
 #pragma unroll
           for (int bb = 0; bb < 4; ++bb) qb[bb] = qok ? ld4(qp + 8 * (b0 + bb)) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int kt = 0; kt < RW_T; ++kt) {
+          for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
             if (kt < nT) {
               const int krow = 32 * kt + r;
               const float* kr = kh + (size_t)(krow < N ? krow : 0) * LDKP;
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
             }
           }
 #pragma unroll
-          for (int kt = 0; kt < RW_T; ++kt) {
+          for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
             if (kt < nT) {
 #pragma unroll
               for (int bb = 0; bb < 4; ++bb)
@@ -244,16 +245,16 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
         // the softmax of query qrow runs over the registers of all key tiles (tile kt: keys from 32 kt) and the two lane halves
         float mx = -__builtin_inff();
 #pragma unroll
-        for (int kt = 0; kt < RW_T; ++kt)
+        for (int kt = 0; kt < CLF_MAX_TILES; ++kt)
           if (kt < nT) mx = clf_tile_max<false>(acc[kt], 32 * kt, hh, N, 1.0f, mx);
         mx = clf_half_max(mx);
         float sum = 0.f;
 #pragma unroll
-        for (int kt = 0; kt < RW_T; ++kt)
+        for (int kt = 0; kt < CLF_MAX_TILES; ++kt)
           if (kt < nT) sum = clf_tile_exp<false>(acc[kt], acc[kt], 32 * kt, hh, N, 1.0f, mx, sum);
         sum = clf_half_sum(sum);
 #pragma unroll
-        for (int kt = 0; kt < RW_T; ++kt) {
+        for (int kt = 0; kt < CLF_MAX_TILES; ++kt) {
           if (kt < nT) {
             float v[16];
             clf_tile_norm(acc[kt], v, qok, sum);
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(512) void clf_pair_wide_kernel(const float* __restr
       }
       if ((r & 1) == 0) {
 #pragma unroll
-        for (int kt = 0; kt < RW_T; ++kt)
+        for (int kt = 0; kt < CLF_MAX_TILES; ++kt)
           if (kt < nT) abar[w][32 * kt + jf] = cs[kt] * invN;
       }
       __builtin_amdgcn_wave_barrier();
@@ -318,7 +319,8 @@ int launch_pair_scores(bool wide, const float* q, int nq_seg, const float* kp, i
                        const int64_t* out_off, const int* tile_off, int ngroups, int ntiles, const int* cidx, const float* tail,
                        float* out, int64_t out_len, void* stream) {
   NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= (wide ? RW_N : CLF_TILE) && ngroups >= 0 && ntiles >= 0 && out_len >= 0);
+  NSID_REQUIRE(nq_seg >= 0 && nc_seg >= 0 && N >= 1 && N <= (wide ? CLF_MAX_NODES : CLF_TILE) && ngroups >= 0 && ntiles >= 0 &&
+               out_len >= 0);
   if (ngroups == 0 || ntiles == 0) return NSID_OK;
   NSID_REQUIRE(q && kp && groups && out_off && tile_off && cidx && tail && out && nsid_aligned16(q) && nsid_aligned16(kp));
   nsid_count(wide ? NSID_C_clf_pair_scores_n : NSID_C_clf_pair_scores);
@@ -342,8 +344,8 @@ extern "C" int nsid_clf_node_rows(const float* x, int S, int C, int N, const flo
 
 extern "C" int nsid_clf_node_rows_n(const float* x, int S, int C, int N, const float* pos, float* rows, void* stream) {
   NSID_REQUIRE(clf_width_ok(C));
-  NSID_REQUIRE(S >= 0 && N >= 1 && N <= RW_N);
-  return launch_node_rows<RW_N>(x, S, C, N, pos, rows, stream, NSID_C_clf_node_rows_n);
+  NSID_REQUIRE(S >= 0 && N >= 1 && N <= CLF_MAX_NODES);
+  return launch_node_rows<CLF_MAX_NODES>(x, S, C, N, pos, rows, stream, NSID_C_clf_node_rows_n);
 }
 
 extern "C" int nsid_clf_pair_scores_n(const float* q, int nq_seg, const float* kp, int nc_seg, int C, int N, const int* groups,

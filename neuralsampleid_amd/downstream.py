@@ -10,7 +10,8 @@ the frozen encoder, on the MI355X (csrc/clf_train.hip).
 Per batch, as the reference: the frozen encoder's pre-projection node matrices and normalised projections of both views (one eval
 pass per view: encode_pairs), ranks 1..k of z_i z_all^T as hard negatives (mine_hard_negatives), B positive pairs (x_i[p], x_j[p])
 and kB negative pairs (x_i[p mod B], x_all[hn.view(-1)[p]]) (pair_lists), the classifier's scores in training mode
-(clf_train_scores_n: up to 128 nodes per segment; clf_train_scores is its N <= 32 form), BCE(pos) + BCE(neg), backward, and the optimiser / GradScaler step. The classifier's forward and backward run
+(clf_train_scores_n), BCE(pos) + BCE(neg), backward, and the optimiser / GradScaler step. clf_train_scores_n takes up to 128 nodes
+per segment; clf_train_scores is its N <= 32 form. The classifier's forward and backward run
 as one autograd op over segments and pair lists: Q is projected once per query segment and [K | V] once per candidate segment, and
 the per-pair attention, the head and their backward are HIP kernels; the projections and the tail's linears are the project's fp32
 GEMMs. Training never goes through classifier(x_i, x_j), which stays the eval-mode re-rank forward (classifier.py)."""

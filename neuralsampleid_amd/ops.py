@@ -2351,24 +2351,121 @@ def _clf_qkv_width(q, kv, N, name, max_n=CLF_MAX_N) -> int:
     return C
 
 
+def _clf_tiles(N) -> int:
+    return (int(N) + CLF_MAX_N - 1) // CLF_MAX_N
+
+
+# The attention and the per-segment sums have two forms each: N <= CLF_MAX_N nodes (one 32 x 32 tile per head; the _c entries) and
+# 1 <= N <= CLF_MAX_N_EVAL (nT x nT tiles, the *_wide_kernel forms of clf_train.hip; the _n entries, public names with _n). One body
+# per operation holds the checks and the allocations; name is the public function (messages), wide its form.
+def _clf_attn_fwd(name, wide, q, kv, N, qi, ci):
+    _chk(q, kv)
+    _clf_idx(qi, name)
+    _clf_idx(ci, name)
+    C = _clf_qkv_width(q, kv, N, name, CLF_MAX_N_EVAL if wide else CLF_MAX_N)
+    N = int(N)
+    P, nT = qi.numel(), _clf_tiles(N)
+    dev = q.device
+    obar = torch.empty((P, C), device=dev, dtype=torch.float32)
+    attn = torch.empty((P, CLF_H, nT, nT, 16, 64) if wide else (P, CLF_H, 16, 64), device=dev, dtype=torch.float32)
+    abar = torch.empty((P, CLF_H, CLF_MAX_N_EVAL if wide else CLF_MAX_N), device=dev, dtype=torch.float32)
+    # 2 N^2 C (Q K^T) + 2 N C (a V) per pair. Bytes: obar, attn, abar written; read per pair (from L2 mostly) Q, K, V rows once, wide:
+    # Q once per head, K once per query tile, V
+    if wide:
+        kernel, entry = "clf_attn_fwd_wide_kernel", "nsid_clf_attn_fwd_n"
+        nbytes = float(P) * (4.0 * N * C * (2 + nT) + 4.0 * C + 4.0 * CLF_H * (32 * nT) ** 2 + 4.0 * CLF_H * CLF_MAX_N_EVAL)
+    else:
+        kernel, entry = "clf_attn_fwd_kernel", "nsid_clf_attn_fwd_c"
+        nbytes = float(P) * (12.0 * N * C + 4.0 * C + 4.0 * CLF_H * 16 * 64 + 4.0 * CLF_H * CLF_MAX_N)
+    _timed(kernel, float(P) * (2.0 * N * N * C + 2.0 * N * C), nbytes, lambda: call(
+        entry, _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P, _p(obar), _p(attn), _p(abar), _stream()),
+        (P, N, C, 1))
+    return obar, attn, abar
+
+
+def _clf_attn_bwd(name, wide, dobar, attn, q, kv, N, qi, ci):
+    _chk(dobar, attn, q, kv)
+    _clf_idx(qi, name)
+    _clf_idx(ci, name)
+    C = _clf_qkv_width(q, kv, N, name, CLF_MAX_N_EVAL if wide else CLF_MAX_N)
+    N = int(N)
+    P, nT = qi.numel(), _clf_tiles(N)
+    if tuple(dobar.shape) != (P, C) or attn.numel() != P * CLF_H * (32 * nT) ** 2:
+        raise ValueError(f"{name}: expected dobar ({P}, {C}) and attn ({P}, 4, {f'{nT}, {nT}, ' if wide else ''}16, 64), got "
+                         f"{tuple(dobar.shape)}, {tuple(attn.shape)}")
+    dev = q.device
+    dq = torch.empty((P, N, C), device=dev, dtype=torch.float32)
+    dk = torch.empty((P, N, C), device=dev, dtype=torch.float32)
+    # 2 N C (da) + 2 N^2 C (dQ) + 2 N^2 C (dK) per pair on the matrix side. Bytes: dQ, dK written; Q, K, V, attn read, wide: V and attn
+    # once, K once per query tile, Q once per key tile
+    if wide:
+        kernel, entry = "clf_attn_bwd_wide_kernel", "nsid_clf_attn_bwd_n"
+        nbytes = float(P) * (4.0 * N * C * (1 + 2 * nT) + 4.0 * C + 4.0 * CLF_H * (32 * nT) ** 2 + 8.0 * N * C)
+    else:
+        kernel, entry = "clf_attn_bwd_kernel", "nsid_clf_attn_bwd_c"
+        nbytes = float(P) * (12.0 * N * C + 4.0 * C + 4.0 * CLF_H * 16 * 64 + 8.0 * N * C)
+    _timed(kernel, float(P) * (4.0 * N * N * C + 2.0 * N * C), nbytes, lambda: call(
+        entry, _p(dobar), _p(attn), _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P, _p(dq), _p(dk),
+        _stream()), (P, N, C, 1))
+    return dq, dk
+
+
+def _clf_seg_reduce(name, wide, dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
+    _chk(dq, dk, abar, dobar)
+    _clf_idx(qi, name)
+    _clf_idx(ci, name)
+    P = qi.numel()
+    N = int(N)
+    max_n = CLF_MAX_N_EVAL if wide else CLF_MAX_N          # also abar's row: (P, 4, max_n)
+    if not 1 <= N <= max_n:
+        raise ValueError(f"{name}: N = {N} is outside [1, {max_n}]")
+    if dobar.dim() != 2:
+        raise ValueError(f"{name}: expected dobar (P, C), got {tuple(dobar.shape)}")
+    C = _clf_width(dobar.shape[1], name)
+    if dobar.shape[0] != P or dq.numel() != P * N * C or dk.numel() != P * N * C or abar.numel() != P * CLF_H * max_n:
+        raise ValueError(f"{name}: expected dq, dk ({P}, {N}, {C}), abar ({P}, 4, {max_n}) and dobar ({P}, {C}), got "
+                         f"{tuple(dq.shape)}, {tuple(dk.shape)}, {tuple(abar.shape)}, {tuple(dobar.shape)}")
+    dev = dq.device
+    dq_seg = torch.empty((nq_seg * N, C), device=dev, dtype=torch.float32)
+    dkv_seg = torch.empty((nc_seg * N, 2 * C), device=dev, dtype=torch.float32)
+    # wide: every node tile of a segment scans the pair list and reads dobar again
+    nT = _clf_tiles(N) if wide else 1
+    kernel, entry = ("clf_seg_reduce_wide_kernel", "nsid_clf_seg_reduce_n") if wide else ("clf_seg_reduce_kernel", "nsid_clf_seg_reduce_c")
+    _tk(kernel, float(P) * (8.0 * N * C + 4.0 * C * nT) + 4.0 * (nq_seg + nc_seg) * (P * nT + N * C) + 4.0 * nc_seg * N * C,
+        lambda: call(entry, _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, C, N, nq_seg, nc_seg, _p(dq_seg), _p(dkv_seg),
+                     _stream()), (P, N, nq_seg + nc_seg, 1))
+    return dq_seg, dkv_seg
+
+
 def clf_attn_fwd(q, kv, N, qi, ci):
     """per pair (qi[p], ci[p]): (obar (P, C), attn (P, 4, 16, 64), abar (P, 4, 32)); q (Sq N, C) Q rows, kv (Sc N, 2 C) [K | V]
     rows, C one of CLF_WIDTHS; qi, ci int32 device lists, in range (checked by the caller)"""
-    _chk(q, kv)
-    _clf_idx(qi, "clf_attn_fwd")
-    _clf_idx(ci, "clf_attn_fwd")
-    C = _clf_qkv_width(q, kv, N, "clf_attn_fwd")
-    P = qi.numel()
-    dev = q.device
-    obar = torch.empty((P, C), device=dev, dtype=torch.float32)
-    attn = torch.empty((P, CLF_H, 16, 64), device=dev, dtype=torch.float32)
-    abar = torch.empty((P, CLF_H, CLF_MAX_N), device=dev, dtype=torch.float32)
-    # 2 N^2 C (Q K^T) + 2 N C (a V) per pair; bytes: Q, K, V rows read per pair (from L2 mostly), obar, attn, abar written
-    _timed("clf_attn_fwd_kernel", float(P) * (2.0 * N * N * C + 2.0 * N * C),
-           float(P) * (12.0 * N * C + 4.0 * C + 4.0 * CLF_H * 16 * 64 + 4.0 * CLF_H * CLF_MAX_N), lambda: call(
-               "nsid_clf_attn_fwd_c", _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P, _p(obar), _p(attn),
-               _p(abar), _stream()), (P, N, C, 1))
-    return obar, attn, abar
+    return _clf_attn_fwd("clf_attn_fwd", False, q, kv, N, qi, ci)
+
+
+def clf_attn_fwd_n(q, kv, N, qi, ci):
+    """clf_attn_fwd for 1 <= N <= 128: (obar (P, C), attn (P, 4, nT, nT, 16, 64), abar (P, 4, 128)), nT = ceil(N / 32)"""
+    return _clf_attn_fwd("clf_attn_fwd_n", True, q, kv, N, qi, ci)
+
+
+def clf_attn_bwd(dobar, attn, q, kv, N, qi, ci):
+    """per-pair (dQ (P, N, C), dK (P, N, C)) from dobar (P, C) = dL/dobar and the forward's attn"""
+    return _clf_attn_bwd("clf_attn_bwd", False, dobar, attn, q, kv, N, qi, ci)
+
+
+def clf_attn_bwd_n(dobar, attn, q, kv, N, qi, ci):
+    """clf_attn_bwd for 1 <= N <= 128, from clf_attn_fwd_n's attn: per-pair (dQ (P, N, C), dK (P, N, C))"""
+    return _clf_attn_bwd("clf_attn_bwd_n", True, dobar, attn, q, kv, N, qi, ci)
+
+
+def clf_seg_reduce(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
+    """per-segment sums in pair order: (dQ (nq_seg N, C), [dK | dV] (nc_seg N, 2 C)); C is dobar's width (P, C)"""
+    return _clf_seg_reduce("clf_seg_reduce", False, dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg)
+
+
+def clf_seg_reduce_n(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
+    """clf_seg_reduce for 1 <= N <= 128, abar (P, 4, 128) from clf_attn_fwd_n: (dQ (nq_seg N, C), [dK | dV] (nc_seg N, 2 C))"""
+    return _clf_seg_reduce("clf_seg_reduce_n", True, dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg)
 
 
 def clf_head_fwd(hid, keep, w2, b2) -> torch.Tensor:
@@ -2394,127 +2491,6 @@ def clf_head_bwd(ds, s, hid, keep, w2):
         "nsid_clf_head_bwd", _p(ds), _p(s), _p(hid), _p(keep), _p(w2), P, _p(dh), _p(dz), _p(dw2), _p(db2), _stream()),
         (P, CLF_HID, 1, 1))
     return dh, dz, dw2, db2
-
-
-def clf_attn_bwd(dobar, attn, q, kv, N, qi, ci):
-    """per-pair (dQ (P, N, C), dK (P, N, C)) from dobar (P, C) = dL/dobar and the forward's attn"""
-    _chk(dobar, attn, q, kv)
-    _clf_idx(qi, "clf_attn_bwd")
-    _clf_idx(ci, "clf_attn_bwd")
-    C = _clf_qkv_width(q, kv, N, "clf_attn_bwd")
-    P = qi.numel()
-    if tuple(dobar.shape) != (P, C) or attn.numel() != P * CLF_H * 16 * 64:
-        raise ValueError(f"clf_attn_bwd: expected dobar ({P}, {C}) and attn ({P}, 4, 16, 64), got {tuple(dobar.shape)}, "
-                         f"{tuple(attn.shape)}")
-    dev = q.device
-    dq = torch.empty((P, N, C), device=dev, dtype=torch.float32)
-    dk = torch.empty((P, N, C), device=dev, dtype=torch.float32)
-    # 2 N C (da) + 2 N^2 C (dQ) + 2 N^2 C (dK) per pair on the matrix side; bytes: Q, K, V, attn read, dQ, dK written
-    _timed("clf_attn_bwd_kernel", float(P) * (4.0 * N * N * C + 2.0 * N * C),
-           float(P) * (12.0 * N * C + 4.0 * C + 4.0 * CLF_H * 16 * 64 + 8.0 * N * C), lambda: call(
-               "nsid_clf_attn_bwd_c", _p(dobar), _p(attn), _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P,
-               _p(dq), _p(dk), _stream()), (P, N, C, 1))
-    return dq, dk
-
-
-def clf_seg_reduce(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
-    """per-segment sums in pair order: (dQ (nq_seg N, C), [dK | dV] (nc_seg N, 2 C)); C is dobar's width (P, C)"""
-    _chk(dq, dk, abar, dobar)
-    _clf_idx(qi, "clf_seg_reduce")
-    _clf_idx(ci, "clf_seg_reduce")
-    P = qi.numel()
-    N = int(N)
-    if not 1 <= N <= CLF_MAX_N:
-        raise ValueError(f"clf_seg_reduce: N = {N} is outside [1, {CLF_MAX_N}]")
-    if dobar.dim() != 2:
-        raise ValueError(f"clf_seg_reduce: expected dobar (P, C), got {tuple(dobar.shape)}")
-    C = _clf_width(dobar.shape[1], "clf_seg_reduce")
-    if dobar.shape[0] != P or dq.numel() != P * N * C or dk.numel() != P * N * C or abar.numel() != P * CLF_H * CLF_MAX_N:
-        raise ValueError(f"clf_seg_reduce: expected dq, dk ({P}, {N}, {C}), abar ({P}, 4, 32) and dobar ({P}, {C}), got "
-                         f"{tuple(dq.shape)}, {tuple(dk.shape)}, {tuple(abar.shape)}, {tuple(dobar.shape)}")
-    dev = dq.device
-    dq_seg = torch.empty((nq_seg * N, C), device=dev, dtype=torch.float32)
-    dkv_seg = torch.empty((nc_seg * N, 2 * C), device=dev, dtype=torch.float32)
-    _tk("clf_seg_reduce_kernel", float(P) * (8.0 * N * C + 4.0 * C) + 4.0 * (nq_seg + nc_seg) * (P + N * C)
-        + 4.0 * nc_seg * N * C, lambda: call(
-            "nsid_clf_seg_reduce_c", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, C, N, nq_seg, nc_seg, _p(dq_seg),
-            _p(dkv_seg), _stream()), (P, N, nq_seg + nc_seg, 1))
-    return dq_seg, dkv_seg
-
-
-# ---- the same three at 1 <= N <= CLF_MAX_N_EVAL nodes: nT x nT tiles of 32 x 32 per head (the *_wide_kernel forms of clf_train.hip)
-def _clf_tiles(N) -> int:
-    return (int(N) + CLF_MAX_N - 1) // CLF_MAX_N
-
-
-def clf_attn_fwd_n(q, kv, N, qi, ci):
-    """clf_attn_fwd for 1 <= N <= 128: (obar (P, C), attn (P, 4, nT, nT, 16, 64), abar (P, 4, 128)), nT = ceil(N / 32)"""
-    _chk(q, kv)
-    _clf_idx(qi, "clf_attn_fwd_n")
-    _clf_idx(ci, "clf_attn_fwd_n")
-    C = _clf_qkv_width(q, kv, N, "clf_attn_fwd_n", CLF_MAX_N_EVAL)
-    N = int(N)
-    P, nT = qi.numel(), _clf_tiles(N)
-    dev = q.device
-    obar = torch.empty((P, C), device=dev, dtype=torch.float32)
-    attn = torch.empty((P, CLF_H, nT, nT, 16, 64), device=dev, dtype=torch.float32)
-    abar = torch.empty((P, CLF_H, CLF_MAX_N_EVAL), device=dev, dtype=torch.float32)
-    # 2 N^2 C (Q K^T) + 2 N C (a V) per pair; bytes: Q once per head, K once per query tile, V (from L2 mostly), obar, attn, abar
-    _timed("clf_attn_fwd_wide_kernel", float(P) * (2.0 * N * N * C + 2.0 * N * C),
-           float(P) * (4.0 * N * C * (2 + nT) + 4.0 * C + 4.0 * CLF_H * (32 * nT) ** 2 + 4.0 * CLF_H * CLF_MAX_N_EVAL), lambda: call(
-               "nsid_clf_attn_fwd_n", _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P, _p(obar), _p(attn),
-               _p(abar), _stream()), (P, N, C, 1))
-    return obar, attn, abar
-
-
-def clf_attn_bwd_n(dobar, attn, q, kv, N, qi, ci):
-    """clf_attn_bwd for 1 <= N <= 128, from clf_attn_fwd_n's attn: per-pair (dQ (P, N, C), dK (P, N, C))"""
-    _chk(dobar, attn, q, kv)
-    _clf_idx(qi, "clf_attn_bwd_n")
-    _clf_idx(ci, "clf_attn_bwd_n")
-    C = _clf_qkv_width(q, kv, N, "clf_attn_bwd_n", CLF_MAX_N_EVAL)
-    N = int(N)
-    P, nT = qi.numel(), _clf_tiles(N)
-    if tuple(dobar.shape) != (P, C) or attn.numel() != P * CLF_H * (32 * nT) ** 2:
-        raise ValueError(f"clf_attn_bwd_n: expected dobar ({P}, {C}) and attn ({P}, 4, {nT}, {nT}, 16, 64), got "
-                         f"{tuple(dobar.shape)}, {tuple(attn.shape)}")
-    dev = q.device
-    dq = torch.empty((P, N, C), device=dev, dtype=torch.float32)
-    dk = torch.empty((P, N, C), device=dev, dtype=torch.float32)
-    # 2 N C (da) + 2 N^2 C (dQ) + 2 N^2 C (dK) per pair on the matrix side; bytes: V and attn once, K once per query tile, Q once per
-    # key tile, dQ and dK written
-    _timed("clf_attn_bwd_wide_kernel", float(P) * (4.0 * N * N * C + 2.0 * N * C),
-           float(P) * (4.0 * N * C * (1 + 2 * nT) + 4.0 * C + 4.0 * CLF_H * (32 * nT) ** 2 + 8.0 * N * C), lambda: call(
-               "nsid_clf_attn_bwd_n", _p(dobar), _p(attn), _p(q), q.shape[0] // N, _p(kv), kv.shape[0] // N, C, N, _p(qi), _p(ci), P,
-               _p(dq), _p(dk), _stream()), (P, N, C, 1))
-    return dq, dk
-
-
-def clf_seg_reduce_n(dq, dk, abar, dobar, qi, ci, N, nq_seg, nc_seg):
-    """clf_seg_reduce for 1 <= N <= 128, abar (P, 4, 128) from clf_attn_fwd_n: (dQ (nq_seg N, C), [dK | dV] (nc_seg N, 2 C))"""
-    _chk(dq, dk, abar, dobar)
-    _clf_idx(qi, "clf_seg_reduce_n")
-    _clf_idx(ci, "clf_seg_reduce_n")
-    P = qi.numel()
-    N = int(N)
-    if not 1 <= N <= CLF_MAX_N_EVAL:
-        raise ValueError(f"clf_seg_reduce_n: N = {N} is outside [1, {CLF_MAX_N_EVAL}]")
-    if dobar.dim() != 2:
-        raise ValueError(f"clf_seg_reduce_n: expected dobar (P, C), got {tuple(dobar.shape)}")
-    C = _clf_width(dobar.shape[1], "clf_seg_reduce_n")
-    if dobar.shape[0] != P or dq.numel() != P * N * C or dk.numel() != P * N * C or abar.numel() != P * CLF_H * CLF_MAX_N_EVAL:
-        raise ValueError(f"clf_seg_reduce_n: expected dq, dk ({P}, {N}, {C}), abar ({P}, 4, {CLF_MAX_N_EVAL}) and dobar ({P}, {C}), "
-                         f"got {tuple(dq.shape)}, {tuple(dk.shape)}, {tuple(abar.shape)}, {tuple(dobar.shape)}")
-    dev = dq.device
-    dq_seg = torch.empty((nq_seg * N, C), device=dev, dtype=torch.float32)
-    dkv_seg = torch.empty((nc_seg * N, 2 * C), device=dev, dtype=torch.float32)
-    # as clf_seg_reduce; every node tile of a segment scans the pair list and reads dobar again
-    nT = _clf_tiles(N)
-    _tk("clf_seg_reduce_wide_kernel", float(P) * (8.0 * N * C + 4.0 * C * nT) + 4.0 * (nq_seg + nc_seg) * (P * nT + N * C)
-        + 4.0 * nc_seg * N * C, lambda: call(
-            "nsid_clf_seg_reduce_n", _p(dq), _p(dk), _p(abar), _p(dobar), _p(qi), _p(ci), P, C, N, nq_seg, nc_seg, _p(dq_seg),
-            _p(dkv_seg), _stream()), (P, N, nq_seg + nc_seg, 1))
-    return dq_seg, dkv_seg
 
 
 # ------------------------------------------------------------------------------------------------ ResNet-IBN baseline (csrc/resnet.hip)
