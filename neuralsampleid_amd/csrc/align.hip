@@ -341,15 +341,8 @@ template <int THREADS>
 int launch_align(size_t lds, hipStream_t st, int npairs, const float* S, const int64_t* s_off, const int* s_ld, const int* q_len,
                  const int* x_len, int max_q, int max_x, float theta, float min_score, int top, const int64_t* row_off, float* row_h,
                  int* row_j, int* row_org, int* occ, float* occ_score, int* n_occ) {
-  static size_t configured = 48 * 1024;
-  if (lds > configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(local_align_kernel<THREADS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = lds;
-  }
-  NSID_LAUNCH((local_align_kernel<THREADS>), dim3(npairs), dim3(THREADS), lds, st, S, s_off, s_ld, q_len, x_len, max_q, max_x, max_x + 2,
-              theta, min_score, top, row_off, row_h, row_j, row_org, occ, occ_score, n_occ);
+  NSID_LAUNCH_LDS((local_align_kernel<THREADS>), dim3(npairs), dim3(THREADS), lds, st, S, s_off, s_ld, q_len, x_len, max_q, max_x,
+                  max_x + 2, theta, min_score, top, row_off, row_h, row_j, row_org, occ, occ_score, n_occ);
   return nsid_launch_status();
 }
 

@@ -170,15 +170,8 @@ template <int C, int NW>
 int ffn_launch(const FfnArgs& p, hipStream_t s) {
   constexpr size_t bytes = (size_t)FF_TM * (C * 2 + 32) + (size_t)FF_HC * (C * 2 + 32) + (size_t)C * (FF_HC * 2 + 32) +
                            (size_t)FF_TM * FF_HC * 2;
-  static_assert(bytes <= 160 * 1024 && FF_TM * (C * 2 + 16) <= FF_HC * (C * 2 + 32), "LDS budget");
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(ffn_fused_kernel<C, NW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
-  NSID_LAUNCH((ffn_fused_kernel<C, NW>), dim3(p.M / FF_TM), dim3(64 * NW), bytes, s, p);
+  static_assert(bytes <= NSID_LDS_MAX && FF_TM * (C * 2 + 16) <= FF_HC * (C * 2 + 32), "LDS budget");
+  NSID_LAUNCH_LDS((ffn_fused_kernel<C, NW>), dim3(p.M / FF_TM), dim3(64 * NW), bytes, s, p);
   return nsid_launch_status();
 }
 

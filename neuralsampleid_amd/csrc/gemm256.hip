@@ -50,7 +50,7 @@ constexpr int RING = 4 * SLOT;
 constexpr int TROW = 144;           // bytes per row of a wave's bf16 transpose buffer: 64 columns + 16 B (rows stay 16-byte aligned)
 constexpr int TBUF = 16 * TROW;     // one 16-row batch per wave
 constexpr int EPI = 8 * TBUF + 2 * 2 * 256 * 4;      // transpose buffers + parked statistics [2 sums][2 wave-rows][256 columns]
-static_assert(RING + EPI <= 160 * 1024, "one workgroup per CU: the ring and the epilogue region together fit the 160 KB of LDS");
+static_assert(RING + EPI <= NSID_LDS_MAX, "one workgroup per CU: the ring and the epilogue region together fit the 160 KB of LDS");
 
 // (wait_vm / wait_lgkm0 and the LDS-DMA of the main loop: nsid_common.h)
 enum { G256_PLAIN = 0, G256_RELU = 1, G256_STAT = 2, G256_ADD = 3 };     // epilogue variants

@@ -1214,16 +1214,9 @@ int launch_knn_sel(const void* r, int ldr, const float* scale, const float* shif
                    int dilation, int32_t* idx, hipStream_t s) {
   const size_t bytes = (size_t)2 * N * C * 2 + (size_t)N * sizeof(float) +
                        (size_t)KNN2_WAVES * 4 * (16 * TILES + 2 * KSEL_CH) * sizeof(unsigned long long);
-  if (bytes > 160 * 1024 || N != 16 * TILES) return 1;
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(knn_sel_kernel<T, TILES>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
-  NSID_LAUNCH((knn_sel_kernel<T, TILES>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
-              shift, N, C, k, dilation, idx);
+  if (bytes > NSID_LDS_MAX || N != 16 * TILES) return 1;
+  NSID_LAUNCH_LDS((knn_sel_kernel<T, TILES>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
+                  shift, N, C, k, dilation, idx);
   return nsid_launch_status();
 }
 
@@ -1231,15 +1224,8 @@ template <typename T, int NT>
 int launch_knn_rank_nt(const void* r, int ldr, const float* scale, const float* shift, int B, int N, int C, int k,
                        int dilation, int32_t* idx, hipStream_t s) {
   const size_t bytes = (size_t)2 * N * C * 2 + ((size_t)N + (size_t)KNN2_WAVES * 16 * (N + 4)) * sizeof(float);
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(knn_rank_kernel<T, NT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
-  NSID_LAUNCH((knn_rank_kernel<T, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
-              shift, N, C, k, dilation, idx);
+  NSID_LAUNCH_LDS((knn_rank_kernel<T, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
+                  shift, N, C, k, dilation, idx);
   return nsid_launch_status();
 }
 template <typename T>
@@ -1258,13 +1244,6 @@ template <typename T, int KD, int NT>
 int launch_knn2_nt(const void* r, int ldr, const float* scale, const float* shift, int B, int N, int C, int k,
                    int dilation, int32_t* idx, hipStream_t s) {
   const size_t bytes = (size_t)2 * N * C * 2 + ((size_t)N + 2 * 4 * 16 * KD) * sizeof(float);      // two fp16 images + |y|^2 + hand-over lists
-  static bool configured = false;      // raise the dynamic-LDS cap once per instantiation (not a per-call sync)
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(knn2_kernel<T, KD, NT>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
   const int pair_min = nsid_tune(NSID_T_knn_pair_min);      // clips from which two workgroups share a CU (0 = never)
   if constexpr (std::is_same<T, __bf16>::value) {
     // stored bf16 features without an affine (eval mode, BatchNorm folded) and a launch of many clips: one bf16 MFMA pass on the raw
@@ -1273,39 +1252,23 @@ int launch_knn2_nt(const void* r, int ldr, const float* scale, const float* shif
       const size_t rbytes = (size_t)N * C * 2 + ((size_t)2 * N + 2 * 4 * 16 * KD) * sizeof(float);
       nsid_count(NSID_C_knn2_raw);
       const long wpe = nsid_tune(NSID_T_knn_raw_wpe);
-#define NSID_KNN_RAW_GO(W_)                                                                                                     \
-      do {                                                                                                                      \
-        static bool configured3 = false;                                                                                        \
-        if (!configured3) {                                                                                                     \
-          if (hipFuncSetAttribute(reinterpret_cast<const void*>(knn2_raw_kernel<KD, NT, W_>),                                   \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)                        \
-            return NSID_ELAUNCH;                                                                                                \
-          configured3 = true;                                                                                                   \
-        }                                                                                                                       \
-        NSID_LAUNCH((knn2_raw_kernel<KD, NT, W_>), dim3(B), dim3(KNN2_THREADS), rbytes, s, static_cast<const __bf16*>(r), (long)ldr, N, \
-                    C, k, dilation, idx);                                                                                       \
-      } while (0)
+#define NSID_KNN_RAW_GO(W_)                                                                                                         \
+      NSID_LAUNCH_LDS((knn2_raw_kernel<KD, NT, W_>), dim3(B), dim3(KNN2_THREADS), rbytes, s, static_cast<const __bf16*>(r), (long)ldr, N, \
+                      C, k, dilation, idx)
       if (wpe >= 6) NSID_KNN_RAW_GO(6);       // (8 waves per SIMD = 64 registers spills 20-48 bytes per lane at N >= 128 and measured the same)
       else NSID_KNN_RAW_GO(4);
 #undef NSID_KNN_RAW_GO
       return nsid_launch_status();
     }
   }
-  if (pair_min > 0 && B >= pair_min && 2 * bytes <= 160 * 1024) {
-    static bool configured2 = false;
-    if (!configured2) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(knn2_pair_kernel<T, KD, NT>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return NSID_ELAUNCH;
-      configured2 = true;
-    }
+  if (pair_min > 0 && B >= pair_min && 2 * bytes <= NSID_LDS_MAX) {
     nsid_count(NSID_C_knn2_pair);
-    NSID_LAUNCH((knn2_pair_kernel<T, KD, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr,
-                scale, shift, N, C, k, dilation, idx);
+    NSID_LAUNCH_LDS((knn2_pair_kernel<T, KD, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr,
+                    scale, shift, N, C, k, dilation, idx);
     return nsid_launch_status();
   }
-  NSID_LAUNCH((knn2_kernel<T, KD, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
-              shift, N, C, k, dilation, idx);
+  NSID_LAUNCH_LDS((knn2_kernel<T, KD, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
+                  shift, N, C, k, dilation, idx);
   return nsid_launch_status();
 }
 template <typename T, int KD>
@@ -1334,20 +1297,11 @@ static int knn_graph_impl(const void* r, int ldr, const float* scale, const floa
   // 16 384 in every timed configuration, up to 32 768 at the encoder sizes 'm' / default): one workgroup per 16-row strip
   if (N > 256 || (long)N * C > 32768) {
     const size_t bytes = ((size_t)16 * (C + 4) + 3 * (size_t)N + (size_t)16 * (N + 4)) * sizeof(float);
-    NSID_REQUIRE(bytes <= 160 * 1024 && B <= 65535);
+    NSID_REQUIRE(bytes <= NSID_LDS_MAX && B <= 65535);
     nsid_count(NSID_C_knn_big);
-    static bool configured = false;
-    if (!configured) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(knn_big_kernel<float>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(knn_big_kernel<__bf16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return NSID_ELAUNCH;
-      configured = true;
-    }
     NSID_DISPATCH_DTYPE(dtype, T, {
-      NSID_LAUNCH((knn_big_kernel<T>), dim3(N / 16, B), dim3(256), bytes, static_cast<hipStream_t>(stream),
-                  static_cast<const T*>(r), (long)ldr, scale, shift, N, C, k, dilation, idx);
+      NSID_LAUNCH_LDS((knn_big_kernel<T>), dim3(N / 16, B), dim3(256), bytes, static_cast<hipStream_t>(stream),
+                      static_cast<const T*>(r), (long)ldr, scale, shift, N, C, k, dilation, idx);
     });
     return nsid_launch_status();
   }
@@ -1361,8 +1315,7 @@ static int knn_graph_impl(const void* r, int ldr, const float* scale, const floa
     int rc = 1;
 #define NSID_KSEL_CASE(TL)                                                                                            \
     case 16 * TL:                                                                                                    \
-      rc = dtype == NSID_BF16 ? launch_knn_sel<__bf16, TL>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s)       \
-                              : launch_knn_sel<float, TL>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);       \
+      NSID_DISPATCH_DTYPE(dtype, T, rc = launch_knn_sel<T, TL>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s)); \
       break;
     switch (N) { NSID_KSEL_CASE(16) NSID_KSEL_CASE(8) NSID_KSEL_CASE(4) NSID_KSEL_CASE(2) default: break; }
 #undef NSID_KSEL_CASE
@@ -1371,39 +1324,26 @@ static int knn_graph_impl(const void* r, int ldr, const float* scale, const floa
   if (use_fast && pow2 && kd > 8 && N <= 128) {              // small graphs: rank counting
     nsid_count(NSID_C_knn_rank);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    return dtype == NSID_BF16 ? launch_knn_rank<__bf16>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s)
-                              : launch_knn_rank<float>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
+    NSID_DISPATCH_DTYPE(dtype, T, return launch_knn_rank<T>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s));
   }
   if (use_fast && kd <= 8 && pow2) {
     nsid_count(NSID_C_knn2);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (dtype == NSID_BF16) {
-      if (kd <= 3) return launch_knn2<__bf16, 3>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
-      if (kd <= 5) return launch_knn2<__bf16, 5>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
-      return launch_knn2<__bf16, 8>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
-    }
-    if (kd <= 3) return launch_knn2<float, 3>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
-    if (kd <= 5) return launch_knn2<float, 5>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
-    return launch_knn2<float, 8>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
+    NSID_DISPATCH_DTYPE(dtype, T, {
+      if (kd <= 3) return launch_knn2<T, 3>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
+      if (kd <= 5) return launch_knn2<T, 5>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
+      return launch_knn2<T, 8>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s);
+    });
   }
   int waves = KNN_WAVES;
   auto lds_bytes = [&](int w) { return ((size_t)N * (C + 4) + N + (size_t)w * 16 * (N + 4)) * sizeof(float); };
-  while (waves > 1 && lds_bytes(waves) > 160 * 1024) waves >>= 1;
+  while (waves > 1 && lds_bytes(waves) > NSID_LDS_MAX) waves >>= 1;
   const size_t bytes = lds_bytes(waves);
-  NSID_REQUIRE(bytes <= 160 * 1024);
+  NSID_REQUIRE(bytes <= NSID_LDS_MAX);
   nsid_count(NSID_C_knn_strips);
-  static size_t configured = 0;       // raise the dynamic-LDS cap once per size step (not a per-call sync)
-  if (bytes > configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(knn_kernel<float>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(knn_kernel<__bf16>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = 160 * 1024;
-  }
   NSID_DISPATCH_DTYPE(dtype, T, {
-    NSID_LAUNCH((knn_kernel<T>), dim3(B), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream),
-                static_cast<const T*>(r), (long)ldr, scale, shift, N, C, k, dilation, idx);
+    NSID_LAUNCH_LDS((knn_kernel<T>), dim3(B), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream),
+                    static_cast<const T*>(r), (long)ldr, scale, shift, N, C, k, dilation, idx);
   });
   return nsid_launch_status();
 }

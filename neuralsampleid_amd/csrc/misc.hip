@@ -698,30 +698,19 @@ extern "C" int nsid_peak_patchify_fwd(const float* spec, const float* w, const f
   NSID_REQUIRE(H % pb == 0 && W % pf == 0 && ldo >= F && NSID_DTYPE_OK(out_dtype));
   const size_t bytes = ((size_t)F * 3 * pb * pf + 8 + (size_t)H * (W + 8)) * sizeof(float);
   // the clip is staged whole (its min / max come first): 35 KB for grafp.yaml's 64 x 128, 139 KB for a 256-mel input
-  NSID_REQUIRE(bytes <= 160 * 1024 && W % 4 == 0 && (F * 3 * pb * pf) % 4 == 0 && nsid_aligned16(spec) && pb * pf <= 64);
-  bool attr_ok = true;
-  auto big_lds = [&](const void* fn) {          // beyond the default 64 KB of dynamic LDS: raise the kernel's cap (idempotent)
-    if (bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) attr_ok = false;
-  };
+  NSID_REQUIRE(bytes <= NSID_LDS_MAX && W % 4 == 0 && (F * 3 * pb * pf) % 4 == 0 && nsid_aligned16(spec) && pb * pf <= 64);
   NSID_DISPATCH_DTYPE(out_dtype, T, {
     if (pb == 4 && pf == 8) {
-      big_lds(reinterpret_cast<const void*>(patchify_fwd_kernel<T, 32, 4, 8>));
-      if (attr_ok)
-        NSID_LAUNCH((patchify_fwd_kernel<T, 32, 4, 8>), dim3(B), dim3(256), bytes, static_cast<hipStream_t>(stream), spec, w,
-                    bias, H, W, pb, pf, F, static_cast<T*>(out), ldo, minmax);
+      NSID_LAUNCH_LDS((patchify_fwd_kernel<T, 32, 4, 8>), dim3(B), dim3(256), bytes, static_cast<hipStream_t>(stream), spec, w,
+                      bias, H, W, pb, pf, F, static_cast<T*>(out), ldo, minmax);
     } else if (pb * pf == 32) {
-      big_lds(reinterpret_cast<const void*>(patchify_fwd_kernel<T, 32>));
-      if (attr_ok)
-        NSID_LAUNCH((patchify_fwd_kernel<T, 32>), dim3(B), dim3(256), bytes, static_cast<hipStream_t>(stream), spec, w,
-                    bias, H, W, pb, pf, F, static_cast<T*>(out), ldo, minmax);
+      NSID_LAUNCH_LDS((patchify_fwd_kernel<T, 32>), dim3(B), dim3(256), bytes, static_cast<hipStream_t>(stream), spec, w,
+                      bias, H, W, pb, pf, F, static_cast<T*>(out), ldo, minmax);
     } else {
-      big_lds(reinterpret_cast<const void*>(patchify_fwd_kernel<T, 64>));
-      if (attr_ok)
-        NSID_LAUNCH((patchify_fwd_kernel<T, 64>), dim3(B), dim3(256), bytes, static_cast<hipStream_t>(stream), spec, w,
-                    bias, H, W, pb, pf, F, static_cast<T*>(out), ldo, minmax);
+      NSID_LAUNCH_LDS((patchify_fwd_kernel<T, 64>), dim3(B), dim3(256), bytes, static_cast<hipStream_t>(stream), spec, w,
+                      bias, H, W, pb, pf, F, static_cast<T*>(out), ldo, minmax);
     }
   });
-  if (!attr_ok) return NSID_ELAUNCH;
   return nsid_launch_status();
 }
 extern "C" int nsid_peak_patchify_bwd(const float* spec, const float* minmax, const void* out, const void* dout,

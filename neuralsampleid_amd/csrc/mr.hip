@@ -685,17 +685,6 @@ extern "C" int nsid_mr_aggregate_fwd(const void* r, int ldr, const float* scale,
   const bool use_lds = nsid_tune(NSID_T_mr_grid_stride) == 0;
   const size_t clip_bytes = (size_t)N * C * (dtype == NSID_BF16 ? 2 : 4);
   if (use_lds && clip_bytes <= 64 * 1024 && (size_t)N * k * 4 <= 64 * 1024) {
-    static bool configured = false;
-    if (!configured) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(mr_fwd_key_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(mr_fwd_lds_kernel<float>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(mr_fwd_lds_kernel<__bf16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-        return NSID_ELAUNCH;
-      configured = true;
-    }
     const int force_split = (int)nsid_tune(NSID_T_mr_split);
     nsid_count(NSID_C_mr_fwd_lds);
     int split = force_split > 0 ? force_split : (B <= 256 ? 2 : 1);
@@ -704,13 +693,13 @@ extern "C" int nsid_mr_aggregate_fwd(const void* r, int ldr, const float* scale,
     const long key_min = nsid_tune(NSID_T_mr_key_min_k);
     if (dtype == NSID_BF16 && key_min > 0 && k >= key_min) {
       nsid_count(NSID_C_mr_fwd_key);
-      NSID_LAUNCH(mr_fwd_key_kernel, dim3(B * split), dim3(MRF_THREADS), clip_bytes / split + (size_t)N * k * 4, static_cast<hipStream_t>(stream),
-                  static_cast<const __bf16*>(r), (long)ldr, scale, shift, idx, N, C, k, static_cast<__bf16*>(u), argmax, split);
+      NSID_LAUNCH_LDS(mr_fwd_key_kernel, dim3(B * split), dim3(MRF_THREADS), clip_bytes / split + (size_t)N * k * 4, static_cast<hipStream_t>(stream),
+                      static_cast<const __bf16*>(r), (long)ldr, scale, shift, idx, N, C, k, static_cast<__bf16*>(u), argmax, split);
       return nsid_launch_status();
     }
     NSID_DISPATCH_DTYPE(dtype, T, {
-      NSID_LAUNCH((mr_fwd_lds_kernel<T>), dim3(B * split), dim3(MRF_THREADS), clip_bytes / split + (size_t)N * k * 4, static_cast<hipStream_t>(stream),
-                  static_cast<const T*>(r), (long)ldr, scale, shift, idx, N, C, k, static_cast<T*>(u), argmax, split);
+      NSID_LAUNCH_LDS((mr_fwd_lds_kernel<T>), dim3(B * split), dim3(MRF_THREADS), clip_bytes / split + (size_t)N * k * 4, static_cast<hipStream_t>(stream),
+                      static_cast<const T*>(r), (long)ldr, scale, shift, idx, N, C, k, static_cast<T*>(u), argmax, split);
     });
     return nsid_launch_status();
   }
@@ -731,26 +720,17 @@ static int mrs_launch(const void* du, const int32_t* idx, const uint8_t* argmax,
   const long sorted_min = nsid_tune(NSID_T_mr_bwd_sorted_min_k);
   const size_t sbytes = (size_t)3 * 16384 + ((size_t)5 * N + 1 + (size_t)N * k) * sizeof(int) + 16;
   if (!(dtype == NSID_BF16 && sorted_min > 0 && k >= sorted_min && (long)N * C == 16384 && (C & (C - 1)) == 0 && C >= 64 && C <= 512 &&
-        sbytes <= 160 * 1024))
+        sbytes <= NSID_LDS_MAX))
     return 1;
-  static bool sconfigured = false;
-  if (!sconfigured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mr_bwd_sorted_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(mr_bwd_sorted_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    sconfigured = true;
-  }
   int cshift = 0;
   while ((1 << cshift) < C) ++cshift;
   nsid_count(NSID_C_mr_bwd_sorted);
   if (bn != nullptr)
-    NSID_LAUNCH(mr_bwd_sorted_kernel<true>, dim3(B), dim3(MRS_THREADS), sbytes, static_cast<hipStream_t>(stream),
-                static_cast<const __bf16*>(du), idx, argmax, N, C, cshift, k, static_cast<__bf16*>(dy), *bn);
+    NSID_LAUNCH_LDS(mr_bwd_sorted_kernel<true>, dim3(B), dim3(MRS_THREADS), sbytes, static_cast<hipStream_t>(stream),
+                    static_cast<const __bf16*>(du), idx, argmax, N, C, cshift, k, static_cast<__bf16*>(dy), *bn);
   else
-    NSID_LAUNCH(mr_bwd_sorted_kernel<false>, dim3(B), dim3(MRS_THREADS), sbytes, static_cast<hipStream_t>(stream),
-                static_cast<const __bf16*>(du), idx, argmax, N, C, cshift, k, static_cast<__bf16*>(dy), MrsBn{});
+    NSID_LAUNCH_LDS(mr_bwd_sorted_kernel<false>, dim3(B), dim3(MRS_THREADS), sbytes, static_cast<hipStream_t>(stream),
+                    static_cast<const __bf16*>(du), idx, argmax, N, C, cshift, k, static_cast<__bf16*>(dy), MrsBn{});
   return nsid_launch_status();
 }
 
@@ -855,7 +835,7 @@ extern "C" int nsid_mr_aggregate_bwd(const void* du, const int32_t* idx, const u
   NSID_REQUIRE(C % (dtype == NSID_BF16 ? 8 : 4) == 0 && nsid_aligned16(du) && nsid_aligned16(dy));
   const size_t esz = dtype == NSID_BF16 ? 2 : 4;
   const size_t bytes = (size_t)N * C * (esz + 1) + ((size_t)2 * N + 1 + (size_t)N * k) * sizeof(int) + 16;
-  if (bytes > 160 * 1024 && dtype == NSID_F32) {
+  if (bytes > NSID_LDS_MAX && dtype == NSID_F32) {
     const long total = (long)B * N * C;
     const int grid = (int)std::min<long>((total + 255) / 256, 4096);
     NSID_LAUNCH(mr_bwd_own_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(du), total,
@@ -864,37 +844,21 @@ extern "C" int nsid_mr_aggregate_bwd(const void* du, const int32_t* idx, const u
                 argmax, N, C, k, total, static_cast<float*>(dy));
     return nsid_launch_status();
   }
-  if (bytes > 160 * 1024) {                  // bf16 storage, a clip beyond the LDS: the edge list alone stays there
+  if (bytes > NSID_LDS_MAX) {                // bf16 storage, a clip beyond the LDS: the edge list alone stays there
     const size_t gbytes = ((size_t)2 * N + 1 + (size_t)N * k) * sizeof(int);
-    NSID_REQUIRE(gbytes <= 160 * 1024 && C % 8 == 0 && N < (1 << 23));
-    static bool big_configured = false;
-    if (!big_configured) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(mr_bwd_big_kernel<__bf16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-        return NSID_ELAUNCH;
-      big_configured = true;
-    }
-    NSID_LAUNCH((mr_bwd_big_kernel<__bf16>), dim3(B), dim3(MRB_THREADS), gbytes, static_cast<hipStream_t>(stream),
-                static_cast<const __bf16*>(du), idx, argmax, N, C, k, static_cast<__bf16*>(dy));
+    NSID_REQUIRE(gbytes <= NSID_LDS_MAX && C % 8 == 0 && N < (1 << 23));
+    NSID_LAUNCH_LDS((mr_bwd_big_kernel<__bf16>), dim3(B), dim3(MRB_THREADS), gbytes, static_cast<hipStream_t>(stream),
+                    static_cast<const __bf16*>(du), idx, argmax, N, C, k, static_cast<__bf16*>(dy));
     return nsid_launch_status();
   }
   NSID_REQUIRE(C % 4 == 0 && ((size_t)N * C * (esz + 1)) % 4 == 0);
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mr_bwd_kernel<float>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute(reinterpret_cast<const void*>(mr_bwd_kernel<__bf16>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
   {
     const int rc = mrs_launch(du, idx, argmax, B, N, C, k, dy, dtype, nullptr, stream);
     if (rc != 1) return rc;
   }
   NSID_DISPATCH_DTYPE(dtype, T, {
-    NSID_LAUNCH((mr_bwd_kernel<T>), dim3(B), dim3(MRB_THREADS), bytes, static_cast<hipStream_t>(stream),
-                static_cast<const T*>(du), idx, argmax, N, C, k, static_cast<T*>(dy));
+    NSID_LAUNCH_LDS((mr_bwd_kernel<T>), dim3(B), dim3(MRB_THREADS), bytes, static_cast<hipStream_t>(stream),
+                    static_cast<const T*>(du), idx, argmax, N, C, k, static_cast<T*>(dy));
   });
   return nsid_launch_status();
 }

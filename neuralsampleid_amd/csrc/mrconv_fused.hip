@@ -316,19 +316,12 @@ int mrc_launch_pg(const MrcArgs& p, int B, hipStream_t s) {
   constexpr int N = 16384 / C, K = C / 2, CS = C / 4;
   if (p.k > 8) return 1;
   const size_t bytes = (size_t)K * (K * 2 + 32) + (size_t)N * (CS * 2 + 16) + (size_t)N * p.k * 4;
-  if (bytes > 160 * 1024) return 1;
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mrconv_pg_kernel<C, NW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
+  if (bytes > NSID_LDS_MAX) return 1;
   const long target = std::max<long>(1, nsid_tune(NSID_T_mrconv_pg_wgs) / 4);       // clip ranges
   const int per = (int)std::max<long>(1, (B + target - 1) / target);
   const int ranges = (B + per - 1) / per;
   MrcPgArgs q{p.y, p.idx, p.w, p.bias, p.out, p.k, B, per};
-  NSID_LAUNCH((mrconv_pg_kernel<C, NW>), dim3(4 * ranges), dim3(64 * NW), bytes, s, q);
+  NSID_LAUNCH_LDS((mrconv_pg_kernel<C, NW>), dim3(4 * ranges), dim3(64 * NW), bytes, s, q);
   return nsid_launch_status();
 }
 
@@ -336,15 +329,8 @@ template <int C, int NW, bool DIRECT>
 int mrc_launch_v(const MrcArgs& p, int B, hipStream_t s) {
   constexpr int N = 16384 / C, K = C / 2;
   const size_t bytes = (size_t)N * (C * 2 + 16) + (size_t)K * (K * 2 + 32) + (DIRECT ? 0 : (size_t)N * (K * 2 + 16)) + (size_t)N * p.k * 4;
-  if (bytes > 160 * 1024) return 1;
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(mrconv_fused_kernel<C, NW, DIRECT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
-  NSID_LAUNCH((mrconv_fused_kernel<C, NW, DIRECT>), dim3(B), dim3(64 * NW), bytes, s, p);
+  if (bytes > NSID_LDS_MAX) return 1;
+  NSID_LAUNCH_LDS((mrconv_fused_kernel<C, NW, DIRECT>), dim3(B), dim3(64 * NW), bytes, s, p);
   return nsid_launch_status();
 }
 

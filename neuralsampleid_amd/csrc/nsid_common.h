@@ -136,19 +136,56 @@ __device__ __forceinline__ void glds16(const char* sbase, unsigned voff, unsigne
                : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
 }
 
+// ---- the launch layer: every kernel of the library is enqueued by NSID_LAUNCH or NSID_LAUNCH_LDS, and every entry that passed
+// one of them ends in nsid_launch_status() ("The launch layer").
+// The first runtime error since the last nsid_launch_status(). One host variable: the library is single-threaded per process, as
+// its counters and its tuning table assume.
+inline hipError_t g_nsid_launch_error = hipSuccess;
+static inline void nsid_note_launch(hipError_t e) {
+  if (g_nsid_launch_error == hipSuccess) g_nsid_launch_error = e;
+}
+// NSID_OK, or NSID_ELAUNCH when the runtime refused any launch (or LDS cap) of the entry: the first refusal is the one printed.
+// Reading clears it, so that the next entry starts clean.
+static inline int nsid_launch_status() {
+  const hipError_t e = g_nsid_launch_error;
+  g_nsid_launch_error = hipSuccess;
+  if (e != hipSuccess) fprintf(stderr, "[nsid] kernel launch failed: %s\n", hipGetErrorString(e));
+  return e == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+}
+
 // hipGetLastError() reports the last error of ANY earlier runtime call on this thread (torch's own included), so the
-// error state is cleared right before a launch and read right after it.
+// error state is cleared right before a launch and read right after it; nsid_note_launch keeps the first error of an entry that
+// launches several kernels. A refused launch skips nothing: the launches after it are enqueued as they would have been.
 #define NSID_LAUNCH(kernel, grid, block, shmem, stream, ...)                \
   do {                                                                      \
     (void)hipGetLastError();                                                \
     hipLaunchKernelGGL(kernel, grid, block, shmem, stream, __VA_ARGS__);    \
+    nsid_note_launch(hipGetLastError());                                    \
   } while (0)
 
-static inline int nsid_launch_status() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) fprintf(stderr, "[nsid] kernel launch failed: %s\n", hipGetErrorString(e));
-  return e == hipSuccess ? NSID_OK : NSID_ELAUNCH;
+// The LDS a workgroup may use on gfx950. A kernel's dynamic LDS beyond the runtime's default needs its cap raised: nsid_big_lds
+// raises the cap of Kernel to all of NSID_LDS_MAX (a ceiling, not an allocation; less the kernel's static LDS, with which the
+// runtime refuses the full figure) the first time Kernel is about to be launched in the process and remembers the outcome. One
+// process drives one device (parallel.py starts a process per GPU), so once is enough.
+constexpr int NSID_LDS_MAX = 160 * 1024;
+inline hipError_t nsid_set_lds_cap(const void* kernel) {
+  hipFuncAttributes a;
+  const hipError_t e = hipFuncGetAttributes(&a, kernel);
+  if (e != hipSuccess) return e;
+  return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, NSID_LDS_MAX - (int)a.sharedSizeBytes);
 }
+template <auto Kernel>
+inline hipError_t nsid_big_lds() {
+  static const hipError_t e = nsid_set_lds_cap(reinterpret_cast<const void*>(Kernel));
+  return e;
+}
+// NSID_LAUNCH for a kernel whose dynamic LDS can exceed the default: the only way to launch one. A refused cap is reported by
+// nsid_launch_status() like a refused launch.
+#define NSID_LAUNCH_LDS(kernel, grid, block, bytes, stream, ...)            \
+  do {                                                                      \
+    nsid_note_launch(nsid_big_lds<kernel>());                               \
+    NSID_LAUNCH(kernel, grid, block, bytes, stream, __VA_ARGS__);           \
+  } while (0)
 static inline bool nsid_aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 #define NSID_REQUIRE(cond) \

@@ -306,13 +306,6 @@ __global__ __launch_bounds__(256) void ntxent_loss_kernel(const float* __restric
   if (threadIdx.x == 0) loss_out[0] = (float)((red[0] + red[1] + red[2] + red[3]) / (double)M);
 }
 
-template <typename K>
-int raise_lds(K kernel, size_t bytes) {
-  if (bytes <= 64 * 1024) return NSID_OK;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)bytes) == hipSuccess ? NSID_OK : NSID_ELAUNCH;
-}
-
 }  // namespace
 
 constexpr int LSE_MAX_GROUPS = 16;
@@ -328,7 +321,6 @@ extern "C" int nsid_ntxent_fwd_bwd(const float* z_i, const float* z_j, int Bg, i
   float* rowloss = ws + M;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const size_t bytes = ((size_t)(RB + CBK) * (d + 4) + 4 * 3 * 16) * sizeof(float);
-  if (raise_lds(ntxent_lse_kernel, bytes) != NSID_OK) return NSID_ELAUNCH;
   {
     const int row_tiles = (M + RB - 1) / RB, nblocks = (M + CBK - 1) / CBK;
     int cg = row_tiles >= 512 ? 1 : (512 + row_tiles - 1) / row_tiles;        // ~512 workgroups
@@ -337,8 +329,8 @@ extern "C" int nsid_ntxent_fwd_bwd(const float* z_i, const float* z_j, int Bg, i
     const int cols_per_group = (nblocks + cg - 1) / cg * CBK;
     cg = (M + cols_per_group - 1) / cols_per_group;
     float* part = ws + 2 * M + 8;
-    NSID_LAUNCH(ntxent_lse_kernel, dim3(row_tiles, cg), dim3(256), bytes, s, z_i, z_j, M, d, tau, cols_per_group, lse,
-                rowloss, part);
+    NSID_LAUNCH_LDS(ntxent_lse_kernel, dim3(row_tiles, cg), dim3(256), bytes, s, z_i, z_j, M, d, tau, cols_per_group, lse,
+                    rowloss, part);
     if (cg > 1) NSID_LAUNCH(ntxent_lse_merge_kernel, dim3((M + 255) / 256), dim3(256), 0, s, part, cg, M, lse, rowloss);
   }
   NSID_LAUNCH(ntxent_loss_kernel, dim3(1), dim3(256), 0, s, rowloss, 2 * p0, 2 * np, M, loss_out);
@@ -351,19 +343,22 @@ extern "C" int nsid_ntxent_fwd_bwd(const float* z_i, const float* z_j, int Bg, i
     cg = (M + cols_per_group - 1) / cols_per_group;
     if (cg > 1) {          // partial rows are accumulated atomically: zero the outputs first (a memset node when captured)
       if (hipMemsetAsync(dz_i, 0, (size_t)np * d * sizeof(float), s) != hipSuccess ||
-          hipMemsetAsync(dz_j, 0, (size_t)np * d * sizeof(float), s) != hipSuccess)
+          hipMemsetAsync(dz_j, 0, (size_t)np * d * sizeof(float), s) != hipSuccess) {
+        (void)nsid_launch_status();          // the launches above are read here: nothing stays pending for the next entry
         return NSID_ELAUNCH;
+      }
     }
     dim3 grid(row_tiles, cg);
 #define NSID_NTX_CASE(DTV)                                                                                   \
   case DTV:                                                                                                  \
-    if (raise_lds(ntxent_grad_kernel<DTV>, bytes) != NSID_OK) return NSID_ELAUNCH;                           \
-    NSID_LAUNCH((ntxent_grad_kernel<DTV>), grid, dim3(256), bytes, s, z_i, z_j, M, d, tau, lse, row0, \
-                       nrows, cols_per_group, dz_i, dz_j);                                                                   \
+    NSID_LAUNCH_LDS((ntxent_grad_kernel<DTV>), grid, dim3(256), bytes, s, z_i, z_j, M, d, tau, lse, row0,    \
+                    nrows, cols_per_group, dz_i, dz_j);                                                      \
     break;
     switch (d / 16) {
       NSID_NTX_CASE(1) NSID_NTX_CASE(2) NSID_NTX_CASE(4) NSID_NTX_CASE(8) NSID_NTX_CASE(16)
-      default: return NSID_EINVAL;
+      default:
+        (void)nsid_launch_status();
+        return NSID_EINVAL;
     }
 #undef NSID_NTX_CASE
   }

@@ -30,9 +30,8 @@ namespace {
 
 constexpr int RR_WAVES = 8;
 constexpr int RR_QCH = NSID_CLF_QCHUNK;      // query segments per workgroup
-constexpr int RR_LDS_MAX = 160 * 1024;
 // K next to P in LDS (rows of C + 4 floats: +16 B so that the 32 rows of a fragment read start in different banks), else P alone
-constexpr bool rr_k_in_lds(int C) { return (CLF_TILE * (C + 4) + CLF_TILE * CLF_PW + RR_WAVES * CLF_TILE) * 4 <= RR_LDS_MAX; }
+constexpr bool rr_k_in_lds(int C) { return (CLF_TILE * (C + 4) + CLF_TILE * CLF_PW + RR_WAVES * CLF_TILE) * 4 <= NSID_LDS_MAX; }
 
 // grp, out_off, tile_off and cidx: the pair lists, see clf_tile_decode
 template <int C, int DH>

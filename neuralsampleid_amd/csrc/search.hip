@@ -473,16 +473,9 @@ void l2_plan_wide(long nq, long nx, int* splits, int* chunk, int* slots) {
 template <int WQ>
 int launch_wide(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int d, int k, int S, int chunk,
                 float* wkey, int* wid, hipStream_t st) {
-  static bool configured = false;
-  if (!configured) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(l2_topk_wide_kernel<WQ>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)L2Wide<WQ>::lds) != hipSuccess)
-      return NSID_ELAUNCH;
-    configured = true;
-  }
   const int nqb = (nq + L2Wide<WQ>::BQ - 1) / L2Wide<WQ>::BQ;
-  NSID_LAUNCH((l2_topk_wide_kernel<WQ>), dim3(nqb * S), dim3(256), L2Wide<WQ>::lds, st, q, ldq, nq, x, ldx, nx, xn, d, k, nqb, S, chunk,
-              wkey, wid);
+  NSID_LAUNCH_LDS((l2_topk_wide_kernel<WQ>), dim3(nqb * S), dim3(256), L2Wide<WQ>::lds, st, q, ldq, nq, x, ldx, nx, xn, d, k, nqb, S,
+                  chunk, wkey, wid);
   return nsid_launch_status();
 }
 

@@ -27,7 +27,7 @@ constexpr int W4_ROW = W4_T * 2;                 // bytes of one operand row in 
 constexpr int W4_OP = W4_BK * W4_ROW;            // 16 KB: one operand of one stage
 constexpr int W4_SLOT = 2 * W4_OP;               // dY then X
 constexpr int W4_RING = 4 * W4_SLOT;             // 128 KB
-static_assert(W4_RING <= 160 * 1024, "one workgroup per CU");
+static_assert(W4_RING <= NSID_LDS_MAX, "one workgroup per CU");
 
 typedef __attribute__((address_space(3))) void* w4_lds_ptr;
 
