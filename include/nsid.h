@@ -579,6 +579,14 @@ int nsid_rows_to_bcn(const void* rows, int ld, int B, int C, int N, float* x, in
  *   FAISS reports it), I (nq x k, int64) the row ids; k > nx: the tail is I = -1, D = +inf. A row's result is bitwise independent of
  *   the other rows of the call and of how the database is split; no atomics. ws: nsid_workspace_bytes("flat_l2_topk", nq, nx)
  *   bytes (enough for any supported d and any k <= 64).
+ * flat_l2_topk_excl: flat_l2_topk with one range of database rows per query row that does not compete (leave-one-out search: the
+ *   query is a song of the database). ex_lo, ex_hi: device int32 arrays of nq entries; database rows ex_lo[i] <= j < ex_hi[i] do not
+ *   exist for query row i; ex_lo[i] >= ex_hi[i] is an empty range. Any pair of ints is memory-safe: the values are only compared with
+ *   row ids, never used as an index. Row i's (D, I) are bitwise flat_l2_topk's result over the database with rows [lo, hi) removed,
+ *   ids >= lo mapped back by + (hi - lo): equal keys smaller id first, and where fewer than k rows remain the tail is I = -1,
+ *   D = +inf. Everything else is flat_l2_topk's contract: the d and k limits, the workspace (nsid_workspace_bytes("flat_l2_topk",
+ *   nq, nx)), NSID_EINVAL before any launch (also for a null ex_lo / ex_hi with nq > 0), batch and split independence, no atomics.
+ *   Launch counters "flat_l2_topk_excl" and, at d > 256, "flat_l2_topk_wide_excl"; the plain entry's counters do not move.
  * seq_scores: for pair p = (s = starts[p], L = lens[p]) (device int32; the caller guarantees s + L <= the rows of q and of I) and
  *   candidate j < L*k with cid = I[s + j/k][j%k]: out[p*ldo + j] = mean over i < min(L, nx - cid) of q[s+i].x[cid+i] (fp32),
  *   NaN when cid < 0 and for L*k <= j < ldo (eval.py:325-331, the window truncated at the end of the index). ldo <= 262140. */
@@ -586,6 +594,9 @@ int nsid_rows_to_bcn(const void* rows, int ld, int B, int C, int N, float* x, in
 int nsid_row_sqnorm(const float* x, int ldx, int n, int d, float* out, void* stream);
 int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm, const float* q_sqnorm,
                       int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream);
+int nsid_flat_l2_topk_excl(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
+                           const float* q_sqnorm, const int* ex_lo, const int* ex_hi, int d, int k, float* D, int64_t* I, void* ws,
+                           size_t ws_bytes, void* stream);
 int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, int d, const int64_t* I, int k, const int* starts,
                     const int* lens, int npairs, float* out, int ldo, void* stream);
 

@@ -287,7 +287,8 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(resample_sinc) X(stem_pairs_gate) X(stem_pairs_build)   /* stems.hip: sinc resampler, stem-pair sampler */ \
   X(logmel_fft_ragged) X(cqt_ragged) X(unfold_segments_ragged)   /* frontend.hip, cqt.hip, misc.hip: a pack of songs of different lengths in one launch, and its segment gather */ \
   X(song_vote) X(song_vote_clf) X(vote_candidates)   /* vote.hip: the song-level vote of a search result, and the device candidate list of the re-rank */ \
-  X(pair_sim) X(local_align)   /* align.hip: the score matrices of (query, song) pairs and their local alignment */
+  X(pair_sim) X(local_align)   /* align.hip: the score matrices of (query, song) pairs and their local alignment */ \
+  X(flat_l2_topk_excl) X(flat_l2_topk_wide_excl)   /* search.hip: nsid_flat_l2_topk_excl (_wide: its d > 256 kernel) */
 
 // nsid_stem7_stat leaves at most this many partial sums per channel (resnet.hip); nsid_bn_finalize accepts such a count next to
 // nsid_row_tiles(M)

@@ -13,6 +13,10 @@
 //  2. one workgroup per query row merges the splits' lists the same way and writes D = max(0, ||q||^2 + key) and int64 ids.
 // Above d = 256 (the ResNet-IBN baseline's 2048-d fingerprints) phase 1 is l2_topk_wide_kernel, which stages both operands through
 // LDS per K chunk; lists, queues, phase 2 and every invariant are the same.
+// nsid_flat_l2_topk_excl is the same search with one range of database rows per query row that does not compete (a catalogue song
+// as the query: its own rows would otherwise take every slot). Phase 1 runs its EX instantiations: an excluded (row, column) is a
+// column that does not exist for that row, decided ahead of the threshold compare, so the lists hold exactly what the plain search
+// holds over the database without those rows, under the same total order. The plain entry launches the EX = false instantiations.
 // No atomics anywhere on the ranking path.
 #include "nsid_common.h"
 
@@ -66,14 +70,24 @@ __device__ __forceinline__ void merge_queue(KI* list, const KI* queue, int cnt, 
 // one wave, one finished 32x32 tile: accumulator register g of lane (r, h) = (lane & 31, lane >> 5) is query row
 // (g & 3) + 8 (g >> 2) + 4 h of the tile against database row `col` (cv: the row exists, xv its squared norm). Scores that pass
 // their row's threshold (the k-th list entry) go to the row's queue, which is merged into the list when it would overflow.
+// EX: exr[row] = the row's excluded range {lo, hi}; exh (wave-uniform): this column tile meets the hull of the tile's ranges. A
+// half-wave's register g is one query row, so the range is one broadcast LDS read, and only on tiles inside the hull.
+template <bool EX>
 __device__ __forceinline__ void offer_tile(KI (*list)[L2_LIST], KI (*queue)[L2_Q1], int* cnt, const f32x16& acc, int col, bool cv,
-                                           float xv, int k, int lane) {
+                                           float xv, int k, int lane, const int2* exr = nullptr, bool exh = false) {
   const int h = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
     const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
     const KI c{xv - (acc[g] + acc[g]), col};
-    const bool pass = cv && ki_before(c, list[row][k - 1]);
+    bool keep = cv;
+    if constexpr (EX) {
+      if (exh) {
+        const int2 e = exr[row];
+        keep = cv && !(col >= e.x && col < e.y);
+      }
+    }
+    const bool pass = keep && ki_before(c, list[row][k - 1]);
     const unsigned long long m = __builtin_amdgcn_ballot_w64(pass);
     if (m == 0) continue;
     const int n0 = __builtin_popcountll(m & 0xffffffffull), n1 = __builtin_popcountll(m >> 32);
@@ -96,6 +110,28 @@ __device__ __forceinline__ void offer_tile(KI (*list)[L2_LIST], KI (*queue)[L2_Q
   }
 }
 
+// EX: the ranges of the wave's 32 query rows q0.. go to LDS once (a row past nq or with lo >= hi: a range no column is in); hlo / hhi
+// = their hull [min lo, max hi), wave-uniform. The values are only ever compared with column ids. The caller's wave barrier follows.
+constexpr int L2_EX_NONE_LO = 0x7fffffff, L2_EX_NONE_HI = (-0x7fffffff - 1);
+__device__ __forceinline__ void stage_ranges(int2* exr, const int* __restrict__ exlo, const int* __restrict__ exhi, int q0, int nq,
+                                             int lane, int& hlo, int& hhi) {
+  int lo = L2_EX_NONE_LO, hi = L2_EX_NONE_HI;
+  if (lane < L2_QT && q0 + lane < nq) {
+    const int a = exlo[q0 + lane], b = exhi[q0 + lane];
+    if (a < b) lo = a, hi = b;
+  }
+  if (lane < L2_QT) exr[lane] = int2{lo, hi};
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    lo = min(lo, __shfl_xor(lo, o, 64));
+    hi = max(hi, __shfl_xor(hi, o, 64));
+  }
+  hlo = __builtin_amdgcn_readfirstlane(lo);
+  hhi = __builtin_amdgcn_readfirstlane(hi);
+}
+// does the column tile [c0, c0 + 32) meet the hull?
+__device__ __forceinline__ bool in_hull(int c0, int hlo, int hhi) { return c0 < hhi && (long)c0 + 31 >= (long)hlo; }
+
 // the wave's lists of query rows q0.. go to workspace slot `slot` of `nslot` per row
 __device__ __forceinline__ void flush_lists(KI (*list)[L2_LIST], KI (*queue)[L2_Q1], const int* cnt, int q0, int nq, int nslot, int slot,
                                             int k, int lane, float* __restrict__ wkey, int* __restrict__ wid) {
@@ -115,15 +151,17 @@ __device__ __forceinline__ void flush_lists(KI (*list)[L2_LIST], KI (*queue)[L2_
 // Lane (r, h) = (lane & 31, lane >> 5). MFMA step (b, e) pairs k = 8b + e (h = 0) with k = 8b + 4 + e (h = 1), so a lane reads
 // 16 contiguous bytes of its row per block and the two halves read the adjacent 32 bytes. Accumulator register g of lane (r, h)
 // is query row (g & 3) + 8 (g >> 2) + 4 h of the tile against database row j0 + r.
-template <int D, int CH>
+template <int D, int CH, bool EX>
 __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x,
                                                            int ldx, int nx, const float* __restrict__ xn, int k, int nqt, int S,
-                                                           int chunk, float* __restrict__ wkey, int* __restrict__ wid) {
+                                                           int chunk, float* __restrict__ wkey, int* __restrict__ wid,
+                                                           const int* __restrict__ exlo, const int* __restrict__ exhi) {
   constexpr int NB = D / 8;          // 8-float blocks per row
   constexpr int NC = NB / CH;        // chunks per tile
   __shared__ KI list[L2_QT][L2_LIST];
   __shared__ KI queue[L2_QT][L2_Q1];
   __shared__ int cnt[L2_QT];
+  __shared__ int2 exr[EX ? L2_QT : 1];            // never referenced, so not allocated, without EX
 
   const int lane = lane_id();
   const int r = lane & 31, h = lane >> 5;
@@ -135,6 +173,8 @@ __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restri
   if (lane < L2_QT) cnt[lane] = 0;
   // rows past nq get a threshold nothing passes
   if (lane < L2_QT && q0 + lane >= nq) list[lane][k - 1] = KI{-__builtin_inff(), 0};
+  int hlo = 0, hhi = 0;
+  if constexpr (EX) stage_ranges(exr, exlo, exhi, q0, nq, lane, hlo, hhi);
   __builtin_amdgcn_wave_barrier();
 
   f32x4 a[NB];
@@ -171,7 +211,10 @@ __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restri
 
     const int col = lo + tile * 32 + r;
     const bool cv = col < hi;
-    offer_tile(list, queue, cnt, acc, col, cv, cv ? xn[col] : 0.f, k, lane);
+    if constexpr (EX)
+      offer_tile<true>(list, queue, cnt, acc, col, cv, cv ? xn[col] : 0.f, k, lane, exr, in_hull(lo + tile * 32, hlo, hhi));
+    else
+      offer_tile<false>(list, queue, cnt, acc, col, cv, cv ? xn[col] : 0.f, k, lane);
   }
 
   flush_lists(list, queue, cnt, q0, nq, S, s, k, lane, wkey, wid);
@@ -191,7 +234,8 @@ __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restri
 // reads 32 consecutive floats of one k (32 banks; a row-major [row][32] stage would put them all on one). The +1 pad serves the
 // transposing store: a thread holds 4 consecutive k of one row, 8 threads share a row, and with a stride = 1 mod 32 the 32 lanes of
 // a half-wave (4 rows x 8 k-quads) write 32 different banks. One stage per operand, the next two chunks prefetched in registers.
-// LDS: the lists, queues and counters of the narrow kernel per wave (4 x 24.1 KB) + 2 x 16.1 KB (WQ = 4) or 4.1 + 32.1 KB of stages.
+// LDS: the lists, queues and counters of the narrow kernel per wave (4 x 24.1 KB) + 2 x 16.1 KB (WQ = 4) or 4.1 + 32.1 KB of stages;
+// EX adds the waves' ranges behind them (4 x 256 B).
 constexpr int L2W_KC = 32;           // floats of K per stage
 constexpr int L2W_UNITS = 512;       // workgroups phase 1 aims at: one per CU fits (LDS), two rounds of 256
 template <int WQ>
@@ -200,12 +244,15 @@ struct L2Wide {
   static constexpr int BQ = 32 * WQ, BC = 32 * WC * NACC;
   static constexpr int QS = BQ + 1, XS = BC + 1;
   static constexpr size_t lds = 4 * (sizeof(KI) * L2_QT * (L2_LIST + L2_Q1) + sizeof(int) * L2_QT) + sizeof(float) * L2W_KC * (QS + XS);
+  static constexpr size_t lds_ex = lds + 4 * sizeof(int2) * L2_QT;
+  static_assert(lds % alignof(int2) == 0, "the ranges follow the stages");
 };
 
-template <int WQ>
+template <int WQ, bool EX>
 __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x,
                                                            int ldx, int nx, const float* __restrict__ xn, int d, int k, int nqb, int S,
-                                                           int chunk, float* __restrict__ wkey, int* __restrict__ wid) {
+                                                           int chunk, float* __restrict__ wkey, int* __restrict__ wid,
+                                                           const int* __restrict__ exlo, const int* __restrict__ exhi) {
   using C = L2Wide<WQ>;
   constexpr int WC = C::WC, NACC = C::NACC, BQ = C::BQ, BC = C::BC, QS = C::QS, XS = C::XS;
   constexpr int QL = BQ / 32, XL = BC / 32;      // f32x4 per thread and chunk
@@ -216,6 +263,7 @@ __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restri
   int* cnt = reinterpret_cast<int*>(l2w_smem + 4 * sizeof(KI) * L2_QT * (L2_LIST + L2_Q1)) + w * L2_QT;
   float* qs = reinterpret_cast<float*>(l2w_smem + 4 * (sizeof(KI) * L2_QT * (L2_LIST + L2_Q1) + sizeof(int) * L2_QT));
   float* xs = qs + L2W_KC * QS;
+  [[maybe_unused]] int2* exr = reinterpret_cast<int2*>(l2w_smem + C::lds) + w * L2_QT;       // EX only: the launch sizes LDS by lds_ex
 
   const int r = lane & 31, h = lane >> 5;
   const int wq = w % WQ, wc = w / WQ;
@@ -227,6 +275,8 @@ __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restri
   for (int t = lane; t < L2_QT * L2_LIST; t += 64) list[t / L2_LIST][t % L2_LIST] = ki_pad();
   if (lane < L2_QT) cnt[lane] = 0;
   if (lane < L2_QT && wq0 + lane >= nq) list[lane][k - 1] = KI{-__builtin_inff(), 0};
+  int hlo = 0, hhi = 0;
+  if constexpr (EX) stage_ranges(exr, exlo, exhi, wq0, nq, lane, hlo, hhi);
   __builtin_amdgcn_wave_barrier();
 
   const int nblk = hi > lo ? (hi - lo + BC - 1) / BC : 0;
@@ -310,7 +360,10 @@ __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restri
       auto offer_n = [&](const f32x16& tile, int n) {
         const int col = lo + blk * BC + 32 * (NACC * wc + n) + r;
         const bool cv = col < hi;
-        offer_tile(list, queue, cnt, tile, col, cv, cv ? xn[col] : 0.f, k, lane);
+        if constexpr (EX)
+          offer_tile<true>(list, queue, cnt, tile, col, cv, cv ? xn[col] : 0.f, k, lane, exr, in_hull(__builtin_amdgcn_readfirstlane(col - r), hlo, hhi));
+        else
+          offer_tile<false>(list, queue, cnt, tile, col, cv, cv ? xn[col] : 0.f, k, lane);
       };
       offer_n(acc[0], 0);                        // spelled out: a loop the compiler declines to unroll would index acc through scratch
       offer_n(acc[1], 1);
@@ -433,20 +486,21 @@ __global__ __launch_bounds__(256) void seq_scores_kernel(const float* __restrict
 bool l2_wide(int d) { return d > 256; }
 bool l2_shape_ok(int d) { return (d % 16 == 0 && d >= 16 && d <= 256) || (d % 64 == 0 && l2_wide(d) && d <= 2048); }
 
-template <int D>
+template <int D, bool EX>
 int launch_split(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int k, int nqt, int S, int chunk,
-                 float* wkey, int* wid, hipStream_t st) {
+                 float* wkey, int* wid, const int* exlo, const int* exhi, hipStream_t st) {
   constexpr int NB = D / 8;
   constexpr int CH = (D <= 128 && NB % 8 == 0) ? 8 : (NB % 4 == 0 ? 4 : 2);
-  NSID_LAUNCH((l2_topk_split_kernel<D, CH>), dim3(nqt * S), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey, wid);
+  NSID_LAUNCH((l2_topk_split_kernel<D, CH, EX>), dim3(nqt * S), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey,
+              wid, exlo, exhi);
   return nsid_launch_status();
 }
 
-template <int... Ds>
+template <bool EX, int... Ds>
 int dispatch_split(int d, const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int k, int nqt, int S,
-                   int chunk, float* wkey, int* wid, hipStream_t st) {
+                   int chunk, float* wkey, int* wid, const int* exlo, const int* exhi, hipStream_t st) {
   int rc = NSID_EINVAL;
-  ((d == Ds ? (rc = launch_split<Ds>(q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey, wid, st), 0) : 0), ...);
+  ((d == Ds ? (rc = launch_split<Ds, EX>(q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey, wid, exlo, exhi, st), 0) : 0), ...);
   return rc;
 }
 
@@ -470,12 +524,12 @@ void l2_plan_wide(long nq, long nx, int* splits, int* chunk, int* slots) {
   *slots = (int)(S * (one ? L2Wide<1>::WC : L2Wide<4>::WC));
 }
 
-template <int WQ>
+template <int WQ, bool EX>
 int launch_wide(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int d, int k, int S, int chunk,
-                float* wkey, int* wid, hipStream_t st) {
+                float* wkey, int* wid, const int* exlo, const int* exhi, hipStream_t st) {
   const int nqb = (nq + L2Wide<WQ>::BQ - 1) / L2Wide<WQ>::BQ;
-  NSID_LAUNCH_LDS((l2_topk_wide_kernel<WQ>), dim3(nqb * S), dim3(256), L2Wide<WQ>::lds, st, q, ldq, nq, x, ldx, nx, xn, d, k, nqb, S,
-                  chunk, wkey, wid);
+  NSID_LAUNCH_LDS((l2_topk_wide_kernel<WQ, EX>), dim3(nqb * S), dim3(256), EX ? L2Wide<WQ>::lds_ex : L2Wide<WQ>::lds, st, q, ldq, nq, x,
+                  ldx, nx, xn, d, k, nqb, S, chunk, wkey, wid, exlo, exhi);
   return nsid_launch_status();
 }
 
@@ -511,12 +565,16 @@ extern "C" int nsid_row_sqnorm(const float* x, int ldx, int n, int d, float* out
   return nsid_launch_status();
 }
 
-extern "C" int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
-                                 const float* q_sqnorm, int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream) {
+namespace {
+// the body of both search entries; EX: with the per-row ranges exlo / exhi
+template <bool EX>
+int l2_topk_entry(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm, const float* q_sqnorm,
+                  const int* exlo, const int* exhi, int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream) {
   NSID_REQUIRE(nq >= 0 && nx >= 0 && l2_shape_ok(d) && k >= 1 && k <= L2_LIST);
   if (nq == 0) return NSID_OK;
   NSID_REQUIRE(q && q_sqnorm && D && I && ws && ldq >= d && ldq % 4 == 0 && nsid_aligned16(q) && nsid_aligned16(ws));
   NSID_REQUIRE(nx == 0 || (x && x_sqnorm && ldx >= d && ldx % 4 == 0 && nsid_aligned16(x)));
+  NSID_REQUIRE(!EX || (exlo && exhi));
   int S, chunk, slots;
   if (l2_wide(d)) {
     l2_plan_wide(nq, nx, &S, &chunk, &slots);
@@ -530,19 +588,31 @@ extern "C" int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x
   int* wid = reinterpret_cast<int*>(wkey + per);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nqt = (nq + L2_QT - 1) / L2_QT;
-  nsid_count(NSID_C_flat_l2_topk);
+  nsid_count(EX ? NSID_C_flat_l2_topk_excl : NSID_C_flat_l2_topk);
   int rc;
   if (l2_wide(d)) {
-    nsid_count(NSID_C_flat_l2_topk_wide);
-    rc = l2_wide_one(nq, nx) ? launch_wide<1>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, st)
-                     : launch_wide<4>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, st);
+    nsid_count(EX ? NSID_C_flat_l2_topk_wide_excl : NSID_C_flat_l2_topk_wide);
+    rc = l2_wide_one(nq, nx) ? launch_wide<1, EX>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, exlo, exhi, st)
+                             : launch_wide<4, EX>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, exlo, exhi, st);
   } else {
-    rc = dispatch_split<16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
-        d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, st);
+    rc = dispatch_split<EX, 16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
+        d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, exlo, exhi, st);
   }
   if (rc != NSID_OK) return rc;
   NSID_LAUNCH(l2_topk_merge_kernel, dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
   return nsid_launch_status();
+}
+}  // namespace
+
+extern "C" int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
+                                 const float* q_sqnorm, int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream) {
+  return l2_topk_entry<false>(q, ldq, nq, x, ldx, nx, x_sqnorm, q_sqnorm, nullptr, nullptr, d, k, D, I, ws, ws_bytes, stream);
+}
+
+extern "C" int nsid_flat_l2_topk_excl(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
+                                      const float* q_sqnorm, const int* ex_lo, const int* ex_hi, int d, int k, float* D, int64_t* I,
+                                      void* ws, size_t ws_bytes, void* stream) {
+  return l2_topk_entry<true>(q, ldq, nq, x, ldx, nx, x_sqnorm, q_sqnorm, ex_lo, ex_hi, d, k, D, I, ws, ws_bytes, stream);
 }
 
 extern "C" int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, int d, const int64_t* I, int k,

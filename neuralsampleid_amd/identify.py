@@ -22,6 +22,12 @@ what interval_recall is shaped for.
     occs = idx.locate(wave=query, threshold=0.6, min_score=2.0)      # [Occurrence(song, score, q_rows, r_rows, q_time, r_time, stretch)]
     per_song = idx.align(q_fp, ["song a", "song b"], threshold=0.6)
 
+A query that is already in the index: leave_out= keeps the named song's rows out of the search itself (exclude= only keeps it out of
+the vote, after its rows took the k_probe slots), and links runs every song against all the others that way, batched.
+
+    occs = idx.locate(fp=idx.fingerprints[lo:lo + n], leave_out="song a", threshold=0.6, min_score=2.0)
+    res = idx.links(threshold=0.6, min_score=2.0)                    # res.occurrences[name], res.skipped
+
 Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs or queries past 4096 rows
 (refused, not split), gap steps other than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated
 on real audio, parsing sample100-ext's annotation files."""
@@ -297,15 +303,19 @@ class SampleIndex:
         return fp, nodes
 
     def identify(self, specs=None, wave=None, fp=None, nodes=None, k_probe: int = 20, top: int = 10, exclude: Optional[str] = None,
-                 rerank: bool = False) -> Identification:
+                 rerank: bool = False, leave_out: Optional[str] = None) -> Identification:
         """the songs a query samples, best first: all its L segments as one pair (0, L). exclude: a song name that never votes (the
-        reference skips a ref song named like the query id)"""
+        reference skips a ref song named like the query id); its rows still take their k_probe slots of the search. leave_out: a song
+        name whose rows do not compete in the search at all (the query is that resident song: its own overlapping rows would fill
+        every slot); it never votes and the slots go to the other songs."""
         if rerank:
             self._check_rerank()
+        if leave_out is not None:
+            self.code(leave_out)
         fp, nodes = self._query(specs, wave, fp, nodes, rerank)
         self._check_fp(fp, "identify")
         pv = self.identify_pairs(fp, [0], [fp.shape[0]], k_probe=k_probe, top=top, exclude=None if exclude is None else [exclude],
-                                 rerank=rerank, nodes=nodes)
+                                 rerank=rerank, nodes=nodes, leave_out=None if leave_out is None else [leave_out])
         return pv.results()[0]
 
     def _check_rerank(self):
@@ -317,10 +327,12 @@ class SampleIndex:
     @torch.no_grad()
     def identify_pairs(self, fp: torch.Tensor, starts: Sequence[int], lens: Sequence[int], k_probe: int = 20, top: int = 10,
                        exclude: Optional[Sequence[Optional[str]]] = None, rerank: bool = False,
-                       nodes: Optional[torch.Tensor] = None) -> PairVotes:
+                       nodes: Optional[torch.Tensor] = None, leave_out: Optional[Sequence[Optional[str]]] = None) -> PairVotes:
         """many (start, length) pairs of one query table at once, the evaluation's form: fp (rows, d); pair p votes over rows
         [starts[p], starts[p] + lens[p]); exclude: per pair a song name or None; nodes (rows, C, N) for rerank=True. Every row is
-        searched once, and with a re-rank the pairs of one start share one score block at their longest length."""
+        searched once, and with a re-rank the pairs of one start share one score block at their longest length. leave_out: per pair a
+        song name or None; the named song's rows do not compete in the search of the pair's rows (FlatL2Index.search's exclude). A row
+        is still searched once, so the pairs that share a row must name the same song (or all None): ValueError otherwise."""
         self._check_fp(fp, "identify_pairs")
         if rerank:
             self._check_rerank()
@@ -350,6 +362,7 @@ class SampleIndex:
             if len(exclude) != starts.size:
                 raise ValueError("identify_pairs: exclude must hold one song name (or None) per pair")
             ex = np.asarray([-1 if e is None else self.code(e) for e in exclude], dtype=np.int64)
+        left = None if leave_out is None else self._leave_out_ranges(leave_out, starts, lens, int(fp.shape[0]))
         if self.n_ref == 0:
             raise RuntimeError("SampleIndex: the index holds no song")
         npairs = starts.size
@@ -358,7 +371,7 @@ class SampleIndex:
                              torch.empty((0, top), device=self.device, dtype=torch.float64),
                              torch.empty((0,), device=self.device, dtype=torch.int32))
         fp = fp.contiguous()
-        _, I = self._index.search(fp, k)
+        _, I = self._index.search(fp, k, exclude=left)
         if not rerank:
             scores = ops.seq_scores(fp, self._index.xb, I, starts, lens, int(lens.max()) * k)
             return PairVotes(self.names, *ops.song_vote(I, scores, starts, lens, self._song_of[: self.n_ref], self.n_dummy, ex, top))
@@ -376,6 +389,28 @@ class SampleIndex:
         votes = ops.song_vote_clf(I, out, s_off, s_ld, starts, lens, self._song_of_nodes[: self.n_ref], self.n_dummy, ex,
                                   CLF_THRESHOLD, top)
         return PairVotes(self.names, *votes, scores=out, s_off=s_off, s_ld=s_ld)
+
+    def _leave_out_ranges(self, leave_out, starts, lens, rows):
+        """identify_pairs' leave_out as FlatL2Index.search's exclude: per row of the query table the index rows (dummy ++ ref ids) of
+        the song its pairs leave out, (0, 0) for a row no pair names a song for; None when no pair names one. Host only."""
+        if len(leave_out) != starts.size:
+            raise ValueError("identify_pairs: leave_out must hold one song name (or None) per pair")
+        code = np.asarray([-1 if e is None else self.code(e) for e in leave_out], dtype=np.int64)
+        if not (code >= 0).any():
+            return None
+        pair = np.repeat(np.arange(starts.size), lens)
+        row = np.arange(int(lens.sum())) - np.repeat(np.cumsum(lens) - lens, lens) + starts[pair]
+        least = np.full(rows, len(self.names), dtype=np.int64)    # the smallest and the largest claim of every row
+        most = np.full(rows, -2, dtype=np.int64)                  # -2: no pair claims the row
+        np.minimum.at(least, row, code[pair])
+        np.maximum.at(most, row, code[pair])
+        bad = np.flatnonzero((most > -2) & (least != most))
+        if bad.size:
+            raise ValueError(f"identify_pairs: row {int(bad[0])} is claimed by pairs with different leave_out: a row is searched once")
+        song = np.asarray([(lo, n) for lo, n, _ in self._song_rows], dtype=np.int64).reshape(-1, 2)
+        has = most >= 0
+        lo = np.where(has, self.n_dummy + song[np.maximum(most, 0), 0], 0)
+        return lo, np.where(has, lo + song[np.maximum(most, 0), 1], 0)
 
     @torch.no_grad()
     def match_score(self, nodes_q: torch.Tensor, name: Optional[str] = None, nodes: Optional[torch.Tensor] = None) -> float:
@@ -517,14 +552,17 @@ class SampleIndex:
     @torch.no_grad()
     def locate(self, specs=None, wave=None, fp=None, nodes=None, songs: Optional[Sequence[str]] = None, k_probe: int = 20,
                n_songs: int = 5, exclude: Optional[str] = None, threshold: Optional[float] = None, min_score: float = 0.0,
-               top: int = 16, rerank: bool = False, row_hop_s=None, row_len_s=None) -> List["Occurrence"]:
+               top: int = 16, rerank: bool = False, row_hop_s=None, row_len_s=None,
+               leave_out: Optional[str] = None) -> List["Occurrence"]:
         """The occurrences of resident songs in a query, one flat list sorted by score: encodes as identify does, finds the candidate
         songs (songs=None) and aligns the query against them.
 
         The candidates: the query is cut into consecutive windows of W = min(Lq, VOTE_MAX_CAND // k_probe) rows (the last one ends at
         the last row), one identify_pairs call votes in every window, and the songs of any window's top list are ordered by their best
         window total (descending, then by code); the first n_songs are aligned. This is also what lets a whole track through at
-        k_probe = 20. exclude: a song name that is never a candidate. threshold: see align (no default without rerank)."""
+        k_probe = 20. exclude: a song name that is never a candidate. leave_out: a song name whose rows do not compete in the search
+        (identify's leave_out: the query is that resident song), so it is never a candidate either and the other songs get its slots;
+        refused with songs=, as exclude is. threshold: see align (no default without rerank)."""
         if rerank:
             self._check_rerank()
         elif threshold is None:
@@ -537,39 +575,171 @@ class SampleIndex:
             raise ValueError(f"k_probe = {k} is outside [1, {ops.SEARCH_MAX_K}]")
         if songs is not None and exclude is not None:
             raise ValueError("locate: exclude applies to the candidate search; with songs= leave the song out")
+        if songs is not None and leave_out is not None:
+            raise ValueError("locate: leave_out applies to the candidate search; with songs= leave the song out")
         if exclude is not None:
             self.code(exclude)
+        if leave_out is not None:
+            self.code(leave_out)
         fp, nodes = self._query(specs, wave, fp, nodes, rerank)
         if songs is None:
             self._check_fp(fp, "locate", device=False)
             if fp.shape[0] > ops.ALIGN_MAX_ROWS:
                 raise ValueError(f"locate: a query of {fp.shape[0]} rows is past the limit of {ops.ALIGN_MAX_ROWS}; longer inputs are "
                                  "refused, not split")
-            songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank)
+            songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank, leave_out)
         per_song = self.align(fp, songs, threshold, min_score, top, nodes, rerank, row_hop_s=row_hop_s, row_len_s=row_len_s)
         flat = [(o, c, n) for c, occs in enumerate(per_song) for n, o in enumerate(occs)]
         flat.sort(key=lambda t: (-t[0].score, t[1], t[2]))
         return [t[0] for t in flat]
 
-    def _candidates(self, fp, nodes, k, n_songs, exclude, rerank) -> List[str]:
-        """the songs of any window's top list, by their best window total (descending, then by code), at most n_songs"""
-        Lq = int(fp.shape[0])
-        if Lq == 0:
-            raise ValueError("locate: the query has no row")
+    @staticmethod
+    def _windows(Lq, k):
+        """the vote windows of a query of Lq rows: (starts, W)"""
         W = min(Lq, max(1, ops.VOTE_MAX_CAND // k))
         starts = list(range(0, Lq - W + 1, W))
         if starts[-1] + W < Lq:
             starts.append(Lq - W)
-        pv = self.identify_pairs(fp, starts, [W] * len(starts), k_probe=k, top=min(ops.VOTE_MAX_TOP, max(n_songs, 1)),
-                                 exclude=None if exclude is None else [exclude] * len(starts), rerank=rerank, nodes=nodes)
+        return starts, W
+
+    @staticmethod
+    def _best_songs(codes, totals):
+        """song codes of some windows' top lists (-1 = none), by their best window total (descending, then by code)"""
         best = {}
-        for r in pv.results():
-            for name, total in zip(r.songs, r.totals.tolist()):
-                c = self._code[name]
-                if c not in best or total > best[c]:
-                    best[c] = total
-        order = sorted(best, key=lambda c: (-best[c], c))
+        for c, total in zip(codes, totals):
+            if c >= 0 and (c not in best or total > best[c]):
+                best[c] = total
+        return sorted(best, key=lambda c: (-best[c], c))
+
+    def _candidates(self, fp, nodes, k, n_songs, exclude, rerank, leave_out=None) -> List[str]:
+        """the songs of any window's top list, by their best window total (descending, then by code), at most n_songs"""
+        Lq = int(fp.shape[0])
+        if Lq == 0:
+            raise ValueError("locate: the query has no row")
+        starts, W = self._windows(Lq, k)
+        pv = self.identify_pairs(fp, starts, [W] * len(starts), k_probe=k, top=min(ops.VOTE_MAX_TOP, max(n_songs, 1)),
+                                 exclude=None if exclude is None else [exclude] * len(starts), rerank=rerank, nodes=nodes,
+                                 leave_out=None if leave_out is None else [leave_out] * len(starts))
+        order = self._best_songs(pv.codes.cpu().numpy().reshape(-1).tolist(), pv.totals.cpu().numpy().reshape(-1).tolist())
         return [self.names[c] for c in order[:n_songs]]
+
+    # ------------------------------------------------------------------------------------------------ the catalogue against itself
+    @torch.no_grad()
+    def links(self, names: Optional[Sequence[str]] = None, k_probe: int = 20, n_songs: int = 5, threshold: Optional[float] = None,
+              min_score: float = 0.0, top: int = 16, block_rows: int = 1 << 16, s_budget_bytes: int = 1 << 30, row_hop_s=None,
+              row_len_s=None) -> "CatalogueLinks":
+        """Which resident songs share material with which others? The self-join of the catalogue: for every named song (default: all,
+        in add order) the query is the song's own resident fingerprint rows (nothing is encoded again or copied to the host), and
+        occurrences[name] is what locate(fp=those rows, leave_out=name, k_probe=..., n_songs=..., threshold=..., min_score=..., top=...)
+        returns, the same tuples and score bits. Both directions are reported (when A samples B, B also shares those rows with A);
+        nothing is deduplicated.
+
+        The work is batched: the songs go in blocks of at most block_rows rows (a longer song is a block of its own); a block is one
+        leave-one-out search over all its rows, each row with its own song's range, one seq_scores and one song_vote over the windows
+        of all its songs (locate's windows, per song), one round to the host for the candidate lists, and then every (song, candidate)
+        pair through pair_sim and local_align over the resident rows in chunks whose score workspace stays under s_budget_bytes. The
+        launches of a block do not grow with its number of songs.
+
+        skipped: the songs of more than ALIGN_MAX_ROWS rows, which are not queried, and those of more than ALIGN_MAX_COLS rows, which
+        are no candidates either (they are dropped from a song's candidate list before it is cut to n_songs, where locate would refuse
+        the call); both limits stay. threshold has no default, as in locate. There is no rerank here: the index keeps the candidates'
+        [K | P] rows, not the queries' projection, so a song's rows cannot be the classifier's query side."""
+        if threshold is None:
+            raise ValueError("links: threshold has no default for fingerprint scores (the reference has no such number and none has "
+                             "been measured on real audio): pass one")
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("links: threshold is NaN")
+        n_songs, k, top, block_rows = int(n_songs), int(k_probe), int(top), int(block_rows)
+        if n_songs < 1:
+            raise ValueError(f"links: n_songs = {n_songs} must be at least 1")
+        if not 1 <= k <= ops.SEARCH_MAX_K:
+            raise ValueError(f"k_probe = {k} is outside [1, {ops.SEARCH_MAX_K}]")
+        if not 1 <= top <= ops.ALIGN_MAX_TOP:
+            raise ValueError(f"links: top = {top} is outside [1, {ops.ALIGN_MAX_TOP}]")
+        if block_rows < 1:
+            raise ValueError(f"links: block_rows = {block_rows} must be at least 1")
+        if isinstance(names, str):
+            raise TypeError("links: names must be a sequence of names, not one string")
+        timing = self._row_timing(row_hop_s, row_len_s)
+        codes = list(range(len(self.names))) if names is None else [self.code(n) for n in names]
+        if len(set(codes)) != len(codes):
+            raise ValueError("links: a song is named twice")
+        if self.n_ref == 0:
+            raise RuntimeError("SampleIndex: the index holds no song")
+        rows_of = [n for _, n, _ in self._song_rows]
+        too_long = {c for c, n in enumerate(rows_of) if n > ops.ALIGN_MAX_COLS}
+        skipped = [self.names[c] for c in codes if rows_of[c] > ops.ALIGN_MAX_ROWS or c in too_long]
+        query = [c for c in codes if rows_of[c] <= ops.ALIGN_MAX_ROWS and c not in too_long]
+        out = {self.names[c]: [] for c in query}
+        vote_top = min(ops.VOTE_MAX_TOP, max(n_songs, 1))
+        lo = 0
+        while lo < len(query):
+            hi, used = lo, 0
+            while hi < len(query) and (hi == lo or used + rows_of[query[hi]] <= block_rows):
+                used += rows_of[query[hi]]
+                hi += 1
+            self._links_block(query[lo:hi], k, n_songs, vote_top, too_long, threshold, min_score, top, int(s_budget_bytes), timing, out)
+            lo = hi
+        return CatalogueLinks(out, skipped)
+
+    def _links_block(self, block, k, n_songs, vote_top, too_long, threshold, min_score, top, budget, timing, out):
+        """one block of links: the songs `block` (codes) as queries; fills out[name]"""
+        first = np.asarray([self._song_rows[c][0] for c in block], dtype=np.int64)
+        count = np.asarray([self._song_rows[c][1] for c in block], dtype=np.int64)
+        base = np.cumsum(count) - count                           # a song's first row in the block's query table
+        ref = self.fingerprints
+        if (first[1:] == first[:-1] + count[:-1]).all():           # neighbours in add order: the resident rows themselves
+            fp = ref[int(first[0]): int(first[-1] + count[-1])]
+        else:
+            rows = np.repeat(first - base, count) + np.arange(int(count.sum()))
+            fp = ref.index_select(0, torch.from_numpy(rows).to(self.device))
+        starts, lens, owner = [], [], []
+        for b, c in enumerate(block):
+            s, W = self._windows(int(count[b]), k)
+            starts += [int(base[b]) + v for v in s]
+            lens += [W] * len(s)
+            owner += [b] * len(s)
+        pv = self.identify_pairs(fp, starts, lens, k_probe=k, top=vote_top, leave_out=[self.names[block[b]] for b in owner])
+        codes, totals = pv.codes.cpu().numpy(), pv.totals.cpu().numpy()
+        owner = np.asarray(owner)
+        pairs = []                                                # (song of the block, candidate code), a song's candidates in order
+        for b in range(len(block)):
+            mine = owner == b
+            order = self._best_songs(codes[mine].reshape(-1).tolist(), totals[mine].reshape(-1).tolist())
+            pairs += [(b, c) for c in [c for c in order if c not in too_long][:n_songs]]
+        found = {b: [] for b in range(len(block))}
+        lo = 0
+        while lo < len(pairs):
+            hi, used = lo, 0
+            while hi < len(pairs):
+                cells = 4 * int(count[pairs[hi][0]]) * self._song_rows[pairs[hi][1]][1]
+                if hi > lo and used + cells > budget:
+                    break
+                used += cells
+                hi += 1
+            part = pairs[lo:hi]
+            q_start = np.asarray([first[b] for b, _ in part], dtype=np.int64)
+            q_len = np.asarray([count[b] for b, _ in part], dtype=np.int64)
+            x_start = np.asarray([self._song_rows[c][0] for _, c in part], dtype=np.int64)
+            x_len = np.asarray([self._song_rows[c][1] for _, c in part], dtype=np.int64)
+            S, s_off, s_ld = ops.pair_sim(ref, ref, q_start, q_len, x_start, x_len)
+            res = ops.local_align(S, s_off, s_ld, q_len, x_len, threshold, min_score, top)
+            occ, sc = res[0].cpu().numpy(), res[1].cpu().numpy()
+            for p, (b, c) in enumerate(part):
+                for n, ((i0, i1, j0, j1), s) in enumerate(zip(occ[p].tolist(), sc[p].tolist())):
+                    if i0 < 0:
+                        break
+                    found[b].append((_occurrence(self.names[c], s, i0, i1, j0, j1, timing), lo + p, n))
+            lo = hi
+        for b, c in enumerate(block):                             # locate's order: by score, then candidate rank, then occurrence rank
+            found[b].sort(key=lambda t: (-t[0].score, t[1], t[2]))
+            out[self.names[c]] = [t[0] for t in found[b]]
+
+
+class CatalogueLinks(NamedTuple):
+    occurrences: dict                             # {song name: [Occurrence], as locate(fp=its rows, leave_out=name) returns them}
+    skipped: List[str]                            # songs past ALIGN_MAX_ROWS / ALIGN_MAX_COLS rows: not queried, no candidates
 
 
 class Occurrence(NamedTuple):

@@ -1851,20 +1851,23 @@ def row_sqnorm(x) -> torch.Tensor:
     return out
 
 
-def flat_l2_topk(q, x, x_sqnorm, k, q_sqnorm=None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """exhaustive squared-L2 top-k of every row of q (nq, d) over the rows of x (nx, d) with their norms x_sqnorm (row_sqnorm):
-    D (nq, k) fp32 ascending, I (nq, k) int64, equal distances smaller id first, k > nx padded with I = -1, D = +inf"""
+def _flat_l2_topk(name, q, x, x_sqnorm, k, q_sqnorm, ex):
+    """the two search entries: ex = None (nsid_flat_l2_topk) or the (ex_lo, ex_hi) device tensors of nsid_flat_l2_topk_excl"""
     k = int(k)
     if not 1 <= k <= SEARCH_MAX_K:
-        raise ValueError(f"flat_l2_topk: k = {k} is outside [1, {SEARCH_MAX_K}]")
-    ldq, ldx = _search_rows(q, "flat_l2_topk q"), _search_rows(x, "flat_l2_topk x")
+        raise ValueError(f"{name}: k = {k} is outside [1, {SEARCH_MAX_K}]")
+    ldq, ldx = _search_rows(q, f"{name} q"), _search_rows(x, f"{name} x")
     if q.shape[1] != x.shape[1]:
-        raise ValueError(f"flat_l2_topk: query d = {q.shape[1]} != database d = {x.shape[1]}")
+        raise ValueError(f"{name}: query d = {q.shape[1]} != database d = {x.shape[1]}")
     _chk(x_sqnorm)
     nq, d = q.shape
     nx = x.shape[0]
     if x_sqnorm.numel() != nx:
-        raise ValueError("flat_l2_topk: x_sqnorm must hold one norm per database row")
+        raise ValueError(f"{name}: x_sqnorm must hold one norm per database row")
+    for t in ex or ():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() \
+                or t.numel() != nq:
+            raise ValueError(f"{name}: ex_lo and ex_hi must be contiguous int32 tensors of {nq} entries on the GPU")
     if q_sqnorm is None:
         q_sqnorm = row_sqnorm(q)
     D = torch.empty((nq, k), device=q.device, dtype=torch.float32)
@@ -1873,11 +1876,29 @@ def flat_l2_topk(q, x, x_sqnorm, k, q_sqnorm=None) -> Tuple[torch.Tensor, torch.
         return D, I
     wsb = int(lib.nsid_workspace_bytes(b"flat_l2_topk", nq, nx))
     ws = torch.empty((max(wsb, 16),), device=q.device, dtype=torch.uint8)
+    xp, xnp = (_p(x), _p(x_sqnorm)) if nx else (None, None)
+    tail = (d, k, _p(D), _p(I), _p(ws), ws.numel(), _stream())
     # phase 1 streams the database once per query block (32 rows; 128 at d > 256) and runs 2 nq nx d flop on the fp32 matrix pipe
-    _timed("flat_l2_topk", 2.0 * nq * nx * d, 4.0 * nx * d + 4.0 * nq * d + 12.0 * nq * k, lambda: call(
-        "nsid_flat_l2_topk", _p(q), ldq, nq, _p(x) if nx else None, ldx, nx, _p(x_sqnorm) if nx else None, _p(q_sqnorm), d, k,
-        _p(D), _p(I), _p(ws), ws.numel(), _stream()), (nq, nx, d, k))
+    if ex is None:
+        fn = lambda: call("nsid_flat_l2_topk", _p(q), ldq, nq, xp, ldx, nx, xnp, _p(q_sqnorm), *tail)
+    else:
+        fn = lambda: call("nsid_flat_l2_topk_excl", _p(q), ldq, nq, xp, ldx, nx, xnp, _p(q_sqnorm), _p(ex[0]), _p(ex[1]), *tail)
+    _timed(name, 2.0 * nq * nx * d, 4.0 * nx * d + 4.0 * nq * d + 12.0 * nq * k, fn, (nq, nx, d, k))
     return D, I
+
+
+def flat_l2_topk(q, x, x_sqnorm, k, q_sqnorm=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """exhaustive squared-L2 top-k of every row of q (nq, d) over the rows of x (nx, d) with their norms x_sqnorm (row_sqnorm):
+    D (nq, k) fp32 ascending, I (nq, k) int64, equal distances smaller id first, k > nx padded with I = -1, D = +inf"""
+    return _flat_l2_topk("flat_l2_topk", q, x, x_sqnorm, k, q_sqnorm, None)
+
+
+def flat_l2_topk_excl(q, x, x_sqnorm, k, ex_lo, ex_hi, q_sqnorm=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """flat_l2_topk in which the database rows ex_lo[i] <= j < ex_hi[i] do not compete for query row i (leave-one-out search; ex_lo[i]
+    >= ex_hi[i]: nothing is left out). ex_lo, ex_hi: int32 device tensors of nq entries, any values (they are only compared with row
+    ids); nothing here reads them on the host. Row i's result is bitwise flat_l2_topk's over x without those rows, the ids mapped
+    back; a row with fewer than k rows left is padded with I = -1, D = +inf."""
+    return _flat_l2_topk("flat_l2_topk_excl", q, x, x_sqnorm, k, q_sqnorm, (ex_lo, ex_hi))
 
 
 def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:

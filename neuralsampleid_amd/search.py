@@ -78,15 +78,18 @@ class FlatL2Index:
             self._norm[self._n: self._n + n] = ops.row_sqnorm(self._x[self._n: self._n + n])
         self._n += n
 
-    def search(self, q, k: int):
+    def search(self, q, k: int, exclude=None):
         """(nq, d) queries -> (D, I): (nq, k) squared L2 distances ascending and row ids; ties smaller id first; k > ntotal pads
-        with I = -1, D = +inf"""
+        with I = -1, D = +inf. exclude = (lo, hi): two array-likes of nq row ids; the stored rows lo[i] <= j < hi[i] do not compete
+        for query row i (leave-one-out search: the query is a run of stored rows), and its result is bitwise the search over the
+        index without them. Checked on the host (0 <= lo <= hi <= ntotal) before the device is touched."""
         as_numpy = not isinstance(q, torch.Tensor)
         k = int(k)
         if not 1 <= k <= ops.SEARCH_MAX_K:
             raise ValueError(f"FlatL2Index.search: k = {k} is outside [1, {ops.SEARCH_MAX_K}]")
         if q.ndim != 2 or q.shape[1] != self.d:
             raise ValueError(f"FlatL2Index.search: expected (nq, {self.d}) queries, got {tuple(q.shape)}")
+        ex = None if exclude is None else exclude_ranges(exclude, int(q.shape[0]), self._n)
         if as_numpy:
             qt = torch.from_numpy(np.ascontiguousarray(q, dtype=np.float32)).to(self.device)
         else:
@@ -94,12 +97,34 @@ class FlatL2Index:
         nq = qt.shape[0]
         D = torch.empty((nq, k), device=self.device, dtype=torch.float32)
         I = torch.empty((nq, k), device=self.device, dtype=torch.int64)
+        if ex is not None:
+            ex = torch.from_numpy(ex).to(self.device)           # one upload: rows 0 / 1 = lo / hi
         for a in range(0, nq, QUERY_BLOCK):
             b = min(nq, a + QUERY_BLOCK)
-            D[a:b], I[a:b] = ops.flat_l2_topk(qt[a:b], self.xb, self._norm[: self._n], k)
+            if ex is None:
+                D[a:b], I[a:b] = ops.flat_l2_topk(qt[a:b], self.xb, self._norm[: self._n], k)
+            else:
+                D[a:b], I[a:b] = ops.flat_l2_topk_excl(qt[a:b], self.xb, self._norm[: self._n], k, ex[0, a:b], ex[1, a:b])
         if as_numpy:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
+
+
+def exclude_ranges(exclude, nq: int, ntotal: int) -> np.ndarray:
+    """FlatL2Index.search's exclude = (lo, hi) checked on the host: a (2, nq) int32 array, or ValueError"""
+    try:
+        lo, hi = exclude
+    except (TypeError, ValueError):
+        raise ValueError("FlatL2Index.search: exclude must be a pair (lo, hi) of row-id sequences") from None
+    lo, hi = (np.asarray(v.cpu() if isinstance(v, torch.Tensor) else v) for v in (lo, hi))
+    if lo.ndim != 1 or hi.ndim != 1 or lo.size != nq or hi.size != nq:
+        raise ValueError(f"FlatL2Index.search: exclude must hold one (lo, hi) per query row ({nq}), got {lo.shape} and {hi.shape}")
+    if nq and not (np.issubdtype(lo.dtype, np.integer) and np.issubdtype(hi.dtype, np.integer)):
+        raise ValueError("FlatL2Index.search: exclude must hold integer row ids")
+    lo, hi = lo.astype(np.int64), hi.astype(np.int64)
+    if nq and (lo.min() < 0 or (lo > hi).any() or hi.max() > ntotal):
+        raise ValueError(f"FlatL2Index.search: every excluded range needs 0 <= lo <= hi <= ntotal = {ntotal}")
+    return np.stack([lo, hi]).astype(np.int32)
 
 
 # ------------------------------------------------------------------------------------------------ evaluation
