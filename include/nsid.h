@@ -85,7 +85,7 @@ int nsid_row_tiles(int M);
  * "stem7_stat" and "stem7_bwd" (rows = clips * pooled rows B*Hp, cols = pooled columns Wp: the [2][nsid_stem7_partials(rows, cols, 0)][64]
  * statistics sums / nsid_stem7_partials(rows, cols, 1) sets of the backward's partial sums, one per workgroup);
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
- * per-split top-64 lists of its first phase). */
+ * per-split top-64 lists of its first phase), "flat_l2_topk_coarse" (the same rows / cols: the pre-filter's per-split lists). */
 long nsid_workspace_bytes(const char* op, long rows, long cols);
 
 /* ---- 1x1 convolution / Linear as a row GEMM on MFMA (fp32 accumulate) ------------------------------------
@@ -599,6 +599,40 @@ int nsid_flat_l2_topk_excl(const float* q, int ldq, int nq, const float* x, int 
                            size_t ws_bytes, void* stream);
 int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, int d, const int64_t* I, int k, const int* starts,
                     const int* lens, int npairs, float* out, int ldo, void* stream);
+
+/* ---- certified bf16 pre-filter of flat_l2_topk (opt-in; derivation: DESIGN.md section 7). d % 16 == 0 and 16 <= d <= 256 for the
+ * coarse pass and the re-score (a wider d is NSID_EINVAL: the caller runs the plain search); M = NSID_SEARCH_MAX_K candidates per row.
+ * The rule, per query row q with RNE bf16 image q~ (x_j, x~_j likewise):
+ *   key_j  = x_sqnorm[j] - 2 dot(q, x_j)             exactly as flat_l2_topk computes it (stored fp32 norm, k-ordered fp32 chain);
+ *   ckey_j = x_sqnorm[j] - 2 dot_bf16(q~, x~_j)      the dot on v_mfma_f32_32x32x16_bf16, fp32 accumulate;
+ *   E = 2 (||q - q~|| Xmax + Nq EXmax) + 2^-24 (16 d Nq Xmax + 8 Xmax^2) + 2^-100 (1 + Nq + Xmax), evaluated in fp64 and rounded up,
+ *     with Xmax >= max_j max(||x_j||, ||x~_j||), EXmax >= max_j ||x_j - x~_j||, Nq >= max(||q||, ||q~||): |key_j - ckey_j| <= E for
+ *     every j. The second term covers the fp32 roundings of both chains (also if the bf16 MFMA truncates its internal additions) and
+ *     of the final subtractions, the third a flush of subnormal operands, products or sums to zero.
+ *   1. coarse: the M smallest (ckey, id) over the competing rows (excluded ranges as in flat_l2_topk_excl), pads (+inf, INT_MAX) last;
+ *      thr = the M-th coarse key.
+ *   2. re-score: the candidates' exact keys, sorted by (key, id); the first k are (D, I), D = max(0, ||q||^2 + key), pads I = -1,
+ *      D = +inf: for every candidate the bits of the plain search.
+ *   3. cert[i] = 1 iff Nq, Xmax, EXmax, ||q - q~|| < 2^60 (so nothing is NaN or overflows) and E is finite, and either slot M - 1 is
+ *      a pad (every competing row is a candidate) or thr - E > key_k (fp64, rounded against the certificate, strict; thr and key_k
+ *      finite). Then no row outside the candidates has an exact key <= key_k, and (D, I) of row i are flat_l2_topk's bit for bit.
+ *   4. cert[i] = 0: (D, I) of row i are NOT the search result; the caller runs flat_l2_topk(_excl) on those rows.
+ * bf16_rows: xb (n x d bf16, ldb % 8 == 0, 16-byte aligned) = the RNE bf16 image of x; err[i] >= ||x_i - x~_i||, nrm[i] >=
+ *   max(||x_i||, ||x~_i||), fp64 sums rounded upwards (a NaN row gives NaN, an overflow of the rounding +inf). d as row_sqnorm.
+ * flat_l2_topk_coarse: qb / xb = bf16 rows (ld % 8 == 0); ex_lo / ex_hi both NULL (no excluded ranges) or both device arrays as in
+ *   flat_l2_topk_excl. ckey (nq x M fp32), cid (nq x M int32) = step 1, bitwise independent of the other rows of the call and of the
+ *   database split. ws: nsid_workspace_bytes("flat_l2_topk_coarse", nq, nx). 128 query rows per workgroup, database tiles through LDS.
+ * flat_l2_rescore: steps 2 and 3 from ckey / cid, the fp32 rows, q_sqnorm / x_sqnorm (row_sqnorm), q_err / q_nrm (bf16_rows of q)
+ *   and xmax / exmax (device floats: no host read). Writes D, I (nq x k), E (nq) and cert (nq, uint8). cid entries that are no row id
+ *   count as pads. 1 <= k <= M.
+ * All three: no atomics, no scratch, NSID_EINVAL before any launch for a bad d, k, ld, alignment or null pointer; nq = 0 (n = 0) is
+ * NSID_OK. Launch counters "bf16_rows", "flat_l2_topk_coarse", "flat_l2_rescore". */
+int nsid_bf16_rows(const float* x, int ldx, int n, int d, void* xb, int ldb, float* err, float* nrm, void* stream);
+int nsid_flat_l2_topk_coarse(const void* qb, int ldq, int nq, const void* xb, int ldx, int nx, const float* x_sqnorm, const int* ex_lo,
+                             const int* ex_hi, int d, float* ckey, int* cid, void* ws, size_t ws_bytes, void* stream);
+int nsid_flat_l2_rescore(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm, const float* q_sqnorm,
+                         const float* q_err, const float* q_nrm, const float* xmax, const float* exmax, const float* ckey,
+                         const int* cid, int d, int k, float* D, int64_t* I, float* E, uint8_t* cert, void* stream);
 
 /* ---- classifier re-rank (downstream.py:30-78 CrossAttentionClassifier in eval mode, as eval_hr.py::eval_faiss_clf and
  * eval_map.py::eval_faiss_map_clf call it). fp32; C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing

@@ -288,6 +288,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(logmel_fft_ragged) X(cqt_ragged) X(unfold_segments_ragged)   /* frontend.hip, cqt.hip, misc.hip: a pack of songs of different lengths in one launch, and its segment gather */ \
   X(song_vote) X(song_vote_clf) X(vote_candidates)   /* vote.hip: the song-level vote of a search result, and the device candidate list of the re-rank */ \
   X(pair_sim) X(local_align)   /* align.hip: the score matrices of (query, song) pairs and their local alignment */ \
+  X(bf16_rows) X(flat_l2_topk_coarse) X(flat_l2_rescore)   /* search.hip: the certified bf16 pre-filter of the exact search */ \
   X(flat_l2_topk_excl) X(flat_l2_topk_wide_excl)   /* search.hip: nsid_flat_l2_topk_excl (_wide: its d > 256 kernel) */
 
 // nsid_stem7_stat leaves at most this many partial sums per channel (resnet.hip); nsid_bn_finalize accepts such a count next to
@@ -397,4 +398,5 @@ int nsid_ffn256_fused_launch(const void* x, const void* w1, const float* b1, con
 // search.hip: the database split of nsid_flat_l2_topk's first phase, and its workspace for k entries per (row, split)
 void nsid_l2_plan(long nq, long nx, int* splits, int* chunk);
 long nsid_l2_ws_bytes(long nq, long nx, int k);
+long nsid_l2_coarse_ws_bytes(long nq, long nx);      // the same for nsid_flat_l2_topk_coarse's lists of NSID_SEARCH_MAX_K entries
 extern void* g_gemm_trace_host;        // gemm.hip: the buffer installed by nsid_debug_gemm_trace (nullptr = none)

@@ -395,8 +395,10 @@ __device__ __forceinline__ void offer(KI* list, KI* queue, int& cnt, int k, int 
   __builtin_amdgcn_wave_barrier();
 }
 
+// RAW (the pre-filter's coarse lists, IdT = int): D / I get the merged keys and ids as they are, pads included; qn is not read
+template <typename IdT, bool RAW>
 __global__ __launch_bounds__(256) void l2_topk_merge_kernel(const float* __restrict__ wkey, const int* __restrict__ wid, int S, int k,
-                                                            const float* __restrict__ qn, float* __restrict__ D, int64_t* __restrict__ I) {
+                                                            const float* __restrict__ qn, float* __restrict__ D, IdT* __restrict__ I) {
   __shared__ KI list[4][L2_LIST];
   __shared__ KI queue[4][L2_Q2];
   const int lane = lane_id(), w = threadIdx.x >> 6;
@@ -426,9 +428,14 @@ __global__ __launch_bounds__(256) void l2_topk_merge_kernel(const float* __restr
   if (cnt > 0) merge_queue(list[0], queue[0], cnt, k, lane);
   if (lane < k) {
     const KI e = list[0][lane];
-    const bool real = e.i != L2_PAD_ID;
-    D[(size_t)row * k + lane] = real ? fmaxf(0.f, qn[row] + e.k) : __builtin_inff();
-    I[(size_t)row * k + lane] = real ? (int64_t)e.i : (int64_t)-1;
+    if constexpr (RAW) {
+      D[(size_t)row * k + lane] = e.k;
+      I[(size_t)row * k + lane] = e.i;
+    } else {
+      const bool real = e.i != L2_PAD_ID;
+      D[(size_t)row * k + lane] = real ? fmaxf(0.f, qn[row] + e.k) : __builtin_inff();
+      I[(size_t)row * k + lane] = real ? (int64_t)e.i : (int64_t)-1;
+    }
   }
 }
 
@@ -599,7 +606,7 @@ int l2_topk_entry(const float* q, int ldq, int nq, const float* x, int ldx, int 
         d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, exlo, exhi, st);
   }
   if (rc != NSID_OK) return rc;
-  NSID_LAUNCH(l2_topk_merge_kernel, dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
+  NSID_LAUNCH((l2_topk_merge_kernel<int64_t, false>), dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
   return nsid_launch_status();
 }
 }  // namespace
@@ -623,5 +630,399 @@ extern "C" int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx,
   nsid_count(NSID_C_seq_scores);
   NSID_LAUNCH(seq_scores_kernel, dim3(npairs, (ldo + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), q, ldq, x, ldx, nx, d,
               I, k, starts, lens, out, ldo);
+  return nsid_launch_status();
+}
+
+// ---- the certified bf16 pre-filter (include/nsid.h nsid_bf16_rows / nsid_flat_l2_topk_coarse / nsid_flat_l2_rescore; the rule and
+// the derivation of its error bound: DESIGN.md section 7) ---------------------------------------------------------------------------
+// A bf16 pass proposes L2_LIST candidates per query row under the coarse key ||x_j||^2 - 2 dot_bf16(q~, x~_j); the candidates are
+// re-scored with the exact chain of l2_topk_split_kernel, and a row is certified when no database row outside the candidates can have
+// an exact key among its k smallest. The bf16 data never reaches a result: (D, I) of a certified row are the plain search's bits, and
+// an uncertified row is the caller's to search with the plain entry.
+namespace {
+
+// a non-negative double as a float that is not below it (NaN stays NaN); below the normal range: the smallest normal float
+__device__ __forceinline__ float f32_up(double v) {
+  float f = (float)v;
+  if ((double)f < v) f = __uint_as_float(__float_as_uint(f) + 1u);
+  if (v > 0.0 && f < 0x1p-126f) f = 0x1p-126f;
+  return f;
+}
+
+// 16 lanes per row: RNE bf16 image, ||x - x~|| and max(||x||, ||x~||) from fp64 sums (every term exact in fp64), rounded upwards
+__global__ __launch_bounds__(256) void bf16_rows_kernel(const float* __restrict__ x, int ldx, int n, int d, __bf16* __restrict__ xb,
+                                                        int ldb, float* __restrict__ err, float* __restrict__ nrm) {
+  const int row = blockIdx.x * 16 + (threadIdx.x >> 4);
+  const int l = threadIdx.x & 15;
+  double se = 0.0, sx = 0.0, sb = 0.0;
+  if (row < n) {
+    const float* p = x + (size_t)row * ldx;
+    __bf16* o = xb + (size_t)row * ldb;
+    for (int c = l; c < d / 8; c += 16) {
+      const f32x4 v0 = ld4(p + 8 * c), v1 = ld4(p + 8 * c + 4);
+      bf16x8 w;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float v = e < 4 ? v0[e & 3] : v1[e & 3];
+        w[e] = (__bf16)v;                                  // RNE (v_cvt_pk_bf16_f32)
+        const double t = (double)v, u = (double)(float)w[e], dlt = t - u;
+        se += dlt * dlt;
+        sx += t * t;
+        sb += u * u;
+      }
+      *reinterpret_cast<bf16x8*>(o + 8 * c) = w;
+    }
+  }
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) {
+    se += __shfl_xor(se, o, 16);
+    sx += __shfl_xor(sx, o, 16);
+    sb += __shfl_xor(sb, o, 16);
+  }
+  if (row < n && l == 0) {
+    double m = sx >= sb ? sx : sb;
+    if (sx != sx) m = sx;                                  // NaN in, NaN out
+    err[row] = f32_up(sqrt(se) * (1.0 + 0x1p-40));         // the factor covers the fp64 roundings of the sums and of the root
+    nrm[row] = f32_up(sqrt(m) * (1.0 + 0x1p-40));
+  }
+}
+
+// ---- coarse phase 1: a workgroup of 4 waves owns 128 query rows (wave w rows 32 w.., as bf16 A fragments in registers) and walks
+// its database split in blocks of 64 rows staged through LDS, so a staged block serves four waves. Lane (r, h) holds
+// A[row r][k = 16 s + 8 h + j] of k-step s in element j; the B fragment of database row r is the 16 bytes at 32 s + 16 h of its staged
+// row. Staged rows are 2 D + 16 bytes apart: 16 lanes then read 16 different 16-byte bank groups. The next block travels in
+// registers while this one is multiplied. Lists, queues and counters per wave as in l2_topk_split_kernel, at k = L2_LIST.
+constexpr int L2C_BQ = 128;          // query rows per workgroup
+constexpr int L2C_BC = 64;           // database rows per stage
+constexpr int L2C_UNITS = 256;       // workgroups aimed at: LDS holds one per CU
+template <int D>
+struct L2Coarse {
+  static constexpr int STR = 2 * D + 16;
+  static constexpr size_t wave = sizeof(KI) * L2_QT * (L2_LIST + L2_Q1) + sizeof(int) * L2_QT;
+  static constexpr size_t lds = 4 * wave + (size_t)L2C_BC * STR;
+  static constexpr size_t lds_ex = lds + 4 * sizeof(int2) * L2_QT;
+  static_assert((4 * wave) % 16 == 0 && lds % alignof(int2) == 0, "the stage is read in 16-byte chunks; the ranges follow it");
+};
+
+// offer_tile with the rows' thresholds (the L2_LIST-th list entries) in registers: tk / ti [g] belong to accumulator register g of
+// this lane. A tile none of whose 16 x 64 scores reaches its row's threshold key costs the compares and one ballot. Otherwise the
+// scores are compared on the exact order (key, id), the queues the tile would overflow are merged (which refreshes those rows'
+// thresholds), and the per-register append of offer_tile runs.
+template <bool EX>
+__device__ __forceinline__ void offer_tile_thr(KI (*list)[L2_LIST], KI (*queue)[L2_Q1], int* cnt, float (&tk)[16], int (&ti)[16],
+                                               const f32x16& acc, int col, bool cv, float xv, int lane, const int2* exr, bool exh) {
+  constexpr int k = L2_LIST;
+  const int h = lane >> 5;
+  bool any = false;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) any |= (xv - (acc[g] + acc[g])) <= tk[g];
+  if (__builtin_amdgcn_ballot_w64(cv && any) == 0) return;
+  // the exact compares: m[g] = the lanes whose score of register g goes to its row's queue
+  unsigned long long m[16], anym = 0;
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
+    const KI c{xv - (acc[g] + acc[g]), col};
+    bool keep = cv;
+    if constexpr (EX) {
+      if (exh) {
+        const int2 e = exr[row];
+        keep = cv && !(col >= e.x && col < e.y);
+      }
+    }
+    m[g] = __builtin_amdgcn_ballot_w64(keep && ki_before(c, KI{tk[g], ti[g]}));
+    anym |= m[g];
+  }
+  if (anym == 0) return;
+  // lane l < 32 looks after row l (register gs of half hs): a queue this tile would overflow is merged first, one merge_queue in
+  // the code instead of one per register and half; its row's threshold is refreshed in the registers that hold the row
+  {
+    const int gs = (lane & 3) + 4 * ((lane & 31) >> 3), hs = (lane >> 2) & 1;
+    int mine = 0;
+#pragma unroll
+    for (int g = 0; g < 16; ++g)
+      if (g == gs) mine = __builtin_popcount(hs ? (unsigned)(m[g] >> 32) : (unsigned)m[g]);
+    const int have = lane < L2_QT ? cnt[lane] : 0;
+    unsigned long long need = __builtin_amdgcn_ballot_w64(lane < L2_QT && mine > 0 && have + mine > L2_Q1);
+    while (need) {
+      const int rr = __builtin_ctzll(need);
+      need &= need - 1;
+      merge_queue(list[rr], queue[rr], __builtin_amdgcn_readfirstlane(cnt[rr]), k, lane);
+      if (lane == 0) cnt[rr] = 0;
+      __builtin_amdgcn_wave_barrier();
+      const KI t = list[rr][k - 1];
+#pragma unroll
+      for (int g = 0; g < 16; ++g)
+        if ((g & 3) + 8 * (g >> 2) + 4 * h == rr) tk[g] = t.k, ti[g] = t.i;
+    }
+  }
+  // the per-register append of offer_tile; every queue now has room
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    if (m[g] == 0) continue;
+    const bool pass = (m[g] >> lane) & 1;
+    const KI c{xv - (acc[g] + acc[g]), col};
+    const int n0 = __builtin_popcountll(m[g] & 0xffffffffull), n1 = __builtin_popcountll(m[g] >> 32);
+    const int pos = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m[g] >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m[g], 0u)) - (h ? n0 : 0);
+#pragma unroll
+    for (int hh = 0; hh < 2; ++hh) {
+      const int n = hh ? n1 : n0;
+      if (n == 0) continue;
+      const int rr = (g & 3) + 8 * (g >> 2) + 4 * hh;
+      const int c0 = __builtin_amdgcn_readfirstlane(cnt[rr]);
+      if (pass && h == hh) queue[rr][c0 + pos] = c;
+      __builtin_amdgcn_wave_barrier();
+      if (lane == 0) cnt[rr] = c0 + n;
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
+}
+
+template <int D, bool EX>
+__global__ __launch_bounds__(256) void l2_coarse_kernel(const __bf16* __restrict__ q, int ldq, int nq, const __bf16* __restrict__ x,
+                                                        int ldx, int nx, const float* __restrict__ xn, int nqb, int S, int chunk,
+                                                        float* __restrict__ wkey, int* __restrict__ wid,
+                                                        const int* __restrict__ exlo, const int* __restrict__ exhi) {
+  using C = L2Coarse<D>;
+  constexpr int NS = D / 16, STR = C::STR, RC = D / 8, NCH = L2C_BC * RC, PT = (NCH + 255) / 256;
+  extern __shared__ __attribute__((aligned(16))) char l2c_smem[];
+  const int tid = threadIdx.x, lane = lane_id(), w = tid >> 6;
+  KI(*list)[L2_LIST] = reinterpret_cast<KI(*)[L2_LIST]>(l2c_smem) + w * L2_QT;
+  KI(*queue)[L2_Q1] = reinterpret_cast<KI(*)[L2_Q1]>(l2c_smem + 4 * sizeof(KI) * L2_QT * L2_LIST) + w * L2_QT;
+  int* cnt = reinterpret_cast<int*>(l2c_smem + 4 * sizeof(KI) * L2_QT * (L2_LIST + L2_Q1)) + w * L2_QT;
+  char* stage = l2c_smem + 4 * C::wave;
+  [[maybe_unused]] int2* exr = reinterpret_cast<int2*>(l2c_smem + C::lds) + w * L2_QT;       // EX only: the launch sizes LDS by lds_ex
+
+  const int r = lane & 31, h = lane >> 5;
+  const int qb = blockIdx.x % nqb, s = blockIdx.x / nqb;
+  const int wq0 = qb * L2C_BQ + 32 * w;
+  const int lo = s * chunk, hi = min(nx, lo + chunk);
+  const bool active = wq0 < nq;                  // a wave whose rows all lie past nq only helps staging
+
+  for (int t = lane; t < L2_QT * L2_LIST; t += 64) list[t / L2_LIST][t % L2_LIST] = ki_pad();
+  if (lane < L2_QT) cnt[lane] = 0;
+  if (lane < L2_QT && wq0 + lane >= nq) list[lane][L2_LIST - 1] = KI{-__builtin_inff(), 0};   // a threshold nothing passes
+  int hlo = 0, hhi = 0;
+  if constexpr (EX) stage_ranges(exr, exlo, exhi, wq0, nq, lane, hlo, hhi);
+  __builtin_amdgcn_wave_barrier();
+
+  float tk[16];
+  int ti[16];
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const bool ok = wq0 + (g & 3) + 8 * (g >> 2) + 4 * h < nq;
+    tk[g] = ok ? __builtin_inff() : -__builtin_inff();
+    ti[g] = ok ? L2_PAD_ID : 0;
+  }
+
+  bf16x8 a[NS];
+  {
+    const bool ok = wq0 + r < nq;
+    const __bf16* qp = q + (size_t)(ok ? wq0 + r : 0) * ldq + 8 * h;
+#pragma unroll
+    for (int i = 0; i < NS; ++i) a[i] = ok ? *reinterpret_cast<const bf16x8*>(qp + 16 * i) : bf16x8{};
+  }
+
+  const int nblk = hi > lo ? (hi - lo + L2C_BC - 1) / L2C_BC : 0;
+  u32x4 gx[PT];
+  float xv0 = 0.f, xv1 = 0.f, nv0 = 0.f, nv1 = 0.f;     // the squared norms of this lane's two columns: this block's, the next one's
+  auto gload = [&](int blk) {
+#pragma unroll
+    for (int i = 0; i < PT; ++i) {
+      const int idx = tid + 256 * i;
+      if (NCH % 256 == 0 || idx < NCH) {
+        const int j = min(lo + blk * L2C_BC + idx / RC, hi - 1);
+        gx[i] = *reinterpret_cast<const u32x4*>(x + (size_t)j * ldx + 8 * (idx % RC));
+      }
+    }
+    const int c = lo + blk * L2C_BC + r;
+    nv0 = c < hi ? xn[c] : 0.f;
+    nv1 = c + 32 < hi ? xn[c + 32] : 0.f;
+  };
+  if (nblk > 0) gload(0);
+
+  const char* bp = stage + r * STR + 16 * h;
+  for (int blk = 0; blk < nblk; ++blk) {
+    __syncthreads();                             // every wave has read the previous block
+#pragma unroll
+    for (int i = 0; i < PT; ++i) {
+      const int idx = tid + 256 * i;
+      if (NCH % 256 == 0 || idx < NCH) *reinterpret_cast<u32x4*>(stage + (idx / RC) * STR + 16 * (idx % RC)) = gx[i];
+    }
+    xv0 = nv0, xv1 = nv1;
+    __syncthreads();
+    if (blk + 1 < nblk) gload(blk + 1);
+    if (!active) continue;
+    f32x16 acc0 = {}, acc1 = {};
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+      const bf16x8 b0 = *reinterpret_cast<const bf16x8*>(bp + 32 * i);
+      const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(bp + 32 * STR + 32 * i);
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b0, acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b1, acc1, 0, 0, 0);
+    }
+    const int c0 = lo + blk * L2C_BC;            // uniform
+    const int col = c0 + r;
+    offer_tile_thr<EX>(list, queue, cnt, tk, ti, acc0, col, col < hi, xv0, lane, exr, EX && in_hull(c0, hlo, hhi));
+    offer_tile_thr<EX>(list, queue, cnt, tk, ti, acc1, col + 32, col + 32 < hi, xv1, lane, exr, EX && in_hull(c0 + 32, hlo, hhi));
+  }
+
+  if (active) flush_lists(list, queue, cnt, wq0, nq, S, s, L2_LIST, lane, wkey, wid);
+}
+
+void l2_plan_coarse(long nq, long nx, int* splits, int* chunk) {
+  const long nqb = (nq + L2C_BQ - 1) / L2C_BQ;
+  long S = nqb > 0 ? (L2C_UNITS + nqb - 1) / nqb : 1;
+  S = std::min(S, std::max(1L, nx / L2_MIN_SPLIT));
+  long c = (nx + S - 1) / S;
+  c = (c + L2C_BC - 1) / L2C_BC * L2C_BC;
+  if (c == 0) c = L2C_BC;
+  S = std::max(1L, (nx + c - 1) / c);
+  *splits = (int)S;
+  *chunk = (int)c;
+}
+
+template <int D, bool EX>
+int launch_coarse(const __bf16* q, int ldq, int nq, const __bf16* x, int ldx, int nx, const float* xn, int S, int chunk, float* wkey,
+                  int* wid, const int* exlo, const int* exhi, hipStream_t st) {
+  const int nqb = (nq + L2C_BQ - 1) / L2C_BQ;
+  NSID_LAUNCH_LDS((l2_coarse_kernel<D, EX>), dim3(nqb * S), dim3(256), EX ? L2Coarse<D>::lds_ex : L2Coarse<D>::lds, st, q, ldq, nq, x,
+                  ldx, nx, xn, nqb, S, chunk, wkey, wid, exlo, exhi);
+  return nsid_launch_status();
+}
+
+template <bool EX, int... Ds>
+int dispatch_coarse(int d, const __bf16* q, int ldq, int nq, const __bf16* x, int ldx, int nx, const float* xn, int S, int chunk,
+                    float* wkey, int* wid, const int* exlo, const int* exhi, hipStream_t st) {
+  int rc = NSID_EINVAL;
+  ((d == Ds ? (rc = launch_coarse<Ds, EX>(q, ldq, nq, x, ldx, nx, xn, S, chunk, wkey, wid, exlo, exhi, st), 0) : 0), ...);
+  return rc;
+}
+
+// ---- re-score: one wave per query row. The row is the A operand of every tile row, its L2_LIST candidates are the columns of two
+// tiles, and the MFMA steps run in l2_topk_split_kernel's order (step (b, e): k = 8 b + e and 8 b + 4 + e), so the key of a
+// candidate has the bits the plain search gives that (query row, database row) pair. Sorted by (key, id, slot) like a merge; the
+// first k are the result. The certificate is evaluated in fp64 with every rounding against it.
+__global__ __launch_bounds__(256) void l2_rescore_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x,
+                                                         int ldx, int nx, const float* __restrict__ xn, const float* __restrict__ qn,
+                                                         const float* __restrict__ qerr, const float* __restrict__ qnrm,
+                                                         const float* __restrict__ xmax, const float* __restrict__ exmax,
+                                                         const float* __restrict__ ckey, const int* __restrict__ cid, int d, int k,
+                                                         float* __restrict__ D, int64_t* __restrict__ I, float* __restrict__ E,
+                                                         uint8_t* __restrict__ cert) {
+  __shared__ KI cand[4][L2_LIST];
+  __shared__ KI srt[4][L2_LIST];
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + w;
+  if (row >= nq) return;                         // uniform over the wave; no workgroup barrier below
+  const int r = lane & 31, h = lane >> 5;
+  const int id0 = cid[(size_t)row * L2_LIST + r], id1 = cid[(size_t)row * L2_LIST + 32 + r];
+  const bool real0 = id0 >= 0 && id0 < nx, real1 = id1 >= 0 && id1 < nx;      // a pad (or anything that is no row id) is read nowhere
+  const float* qp = q + (size_t)row * ldq + 4 * h;
+  const float* x0 = x + (size_t)(real0 ? id0 : 0) * ldx + 4 * h;
+  const float* x1 = x + (size_t)(real1 ? id1 : 0) * ldx + 4 * h;
+  f32x16 acc0 = {}, acc1 = {};
+  for (int b = 0; b < d / 8; ++b) {
+    const f32x4 a = ld4(qp + 8 * b);
+    const f32x4 b0 = real0 ? ld4(x0 + 8 * b) : f32x4{0.f, 0.f, 0.f, 0.f};
+    const f32x4 b1 = real1 ? ld4(x1 + 8 * b) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b0[e], acc0, 0, 0, 0);
+      acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b1[e], acc1, 0, 0, 0);
+    }
+  }
+  // every tile row is the same query row: register 0 of lane (r, h) is the pair (row, column r) in both halves
+  const KI c0 = real0 ? KI{xn[id0] - (acc0[0] + acc0[0]), id0} : ki_pad();
+  const KI c1 = real1 ? KI{xn[id1] - (acc1[0] + acc1[0]), id1} : ki_pad();
+  cand[w][lane] = h ? c1 : c0;
+  __builtin_amdgcn_wave_barrier();
+  const KI e = cand[w][lane];
+  int rank = 0;
+  for (int f = 0; f < L2_LIST; ++f) rank += ki_less(cand[w][f], f, e, lane) ? 1 : 0;
+  srt[w][rank] = e;                              // distinct ranks unless a key is NaN, and then the row is not certified
+  __builtin_amdgcn_wave_barrier();
+  if (lane < k) {
+    const KI o = srt[w][lane];
+    const bool real = o.i != L2_PAD_ID;
+    D[(size_t)row * k + lane] = real ? fmaxf(0.f, qn[row] + o.k) : __builtin_inff();
+    I[(size_t)row * k + lane] = real ? (int64_t)o.i : (int64_t)-1;
+  }
+  if (lane != 0) return;
+  const double Nq = (double)qnrm[row], eq = (double)qerr[row], X = (double)*xmax, EX = (double)*exmax;
+  // E = 2 (||q - q~|| Xmax + Nq EXmax) + slack; the last factor covers the fp64 roundings of this line
+  const double Ed = (2.0 * (eq * X + Nq * EX) + 0x1p-24 * (16.0 * d * Nq * X + 8.0 * X * X) + 0x1p-100 * (1.0 + Nq + X)) * (1.0 + 0x1p-40);
+  const float Ef = f32_up(Ed);
+  const float thr = ckey[(size_t)row * L2_LIST + L2_LIST - 1];
+  const bool thr_pad = cid[(size_t)row * L2_LIST + L2_LIST - 1] == L2_PAD_ID;
+  const float kk = srt[w][k - 1].k;
+  // no certificate where a norm is NaN, infinite or so large that a dot or a squared norm could overflow
+  bool ok = Nq < 0x1p60 && X < 0x1p60 && EX < 0x1p60 && eq < 0x1p60 && Ef < __builtin_inff();
+  if (ok && !thr_pad) {
+    double lhs = (double)thr - (double)Ef;
+    lhs -= fabs(lhs) * 0x1p-50;                  // the fp64 subtraction rounds: only ever towards "not certified"
+    ok = fabsf(thr) < __builtin_inff() && fabsf(kk) < __builtin_inff() && lhs > (double)kk;
+  }
+  E[row] = Ef;
+  cert[row] = ok ? 1 : 0;
+}
+
+}  // namespace
+
+long nsid_l2_coarse_ws_bytes(long nq, long nx) {
+  int S, c;
+  l2_plan_coarse(nq, nx, &S, &c);
+  return (long)S * nq * L2_LIST * (long)(sizeof(float) + sizeof(int));
+}
+
+extern "C" int nsid_bf16_rows(const float* x, int ldx, int n, int d, void* xb, int ldb, float* err, float* nrm, void* stream) {
+  NSID_REQUIRE(n >= 0 && l2_shape_ok(d));
+  if (n == 0) return NSID_OK;
+  NSID_REQUIRE(x && xb && err && nrm && ldx >= d && ldx % 4 == 0 && nsid_aligned16(x) && ldb >= d && ldb % 8 == 0 && nsid_aligned16(xb));
+  nsid_count(NSID_C_bf16_rows);
+  NSID_LAUNCH(bf16_rows_kernel, dim3((n + 15) / 16), dim3(256), 0, static_cast<hipStream_t>(stream), x, ldx, n, d,
+              static_cast<__bf16*>(xb), ldb, err, nrm);
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_flat_l2_topk_coarse(const void* qb, int ldq, int nq, const void* xb, int ldx, int nx, const float* x_sqnorm,
+                                        const int* ex_lo, const int* ex_hi, int d, float* ckey, int* cid, void* ws, size_t ws_bytes,
+                                        void* stream) {
+  NSID_REQUIRE(nq >= 0 && nx >= 0 && d % 16 == 0 && d >= 16 && d <= 256);
+  if (nq == 0) return NSID_OK;
+  NSID_REQUIRE(qb && ckey && cid && ws && ldq >= d && ldq % 8 == 0 && nsid_aligned16(qb) && nsid_aligned16(ws));
+  NSID_REQUIRE(nx == 0 || (xb && x_sqnorm && ldx >= d && ldx % 8 == 0 && nsid_aligned16(xb)));
+  NSID_REQUIRE((ex_lo == nullptr) == (ex_hi == nullptr));
+  int S, chunk;
+  l2_plan_coarse(nq, nx, &S, &chunk);
+  const size_t per = (size_t)S * nq * L2_LIST;
+  NSID_REQUIRE(ws_bytes >= per * (sizeof(float) + sizeof(int)));
+  float* wkey = static_cast<float*>(ws);
+  int* wid = reinterpret_cast<int*>(wkey + per);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const __bf16* q = static_cast<const __bf16*>(qb);
+  const __bf16* x = static_cast<const __bf16*>(xb);
+  nsid_count(NSID_C_flat_l2_topk_coarse);
+  const int rc = ex_lo ? dispatch_coarse<true, 16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
+                             d, q, ldq, nq, x, ldx, nx, x_sqnorm, S, chunk, wkey, wid, ex_lo, ex_hi, st)
+                       : dispatch_coarse<false, 16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
+                             d, q, ldq, nq, x, ldx, nx, x_sqnorm, S, chunk, wkey, wid, nullptr, nullptr, st);
+  if (rc != NSID_OK) return rc;
+  NSID_LAUNCH((l2_topk_merge_kernel<int, true>), dim3(nq), dim3(256), 0, st, wkey, wid, S, L2_LIST, nullptr, ckey, cid);
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_flat_l2_rescore(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
+                                    const float* q_sqnorm, const float* q_err, const float* q_nrm, const float* xmax,
+                                    const float* exmax, const float* ckey, const int* cid, int d, int k, float* D, int64_t* I, float* E,
+                                    uint8_t* cert, void* stream) {
+  NSID_REQUIRE(nq >= 0 && nx >= 0 && d % 16 == 0 && d >= 16 && d <= 256 && k >= 1 && k <= L2_LIST);
+  if (nq == 0) return NSID_OK;
+  NSID_REQUIRE(q && q_sqnorm && q_err && q_nrm && xmax && exmax && ckey && cid && D && I && E && cert && ldq >= d && ldq % 4 == 0 &&
+               nsid_aligned16(q));
+  NSID_REQUIRE(nx == 0 || (x && x_sqnorm && ldx >= d && ldx % 4 == 0 && nsid_aligned16(x)));
+  nsid_count(NSID_C_flat_l2_rescore);
+  NSID_LAUNCH(l2_rescore_kernel, dim3((nq + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), q, ldq, nq, x, ldx, nx, x_sqnorm,
+              q_sqnorm, q_err, q_nrm, xmax, exmax, ckey, cid, d, k, D, I, E, cert);
   return nsid_launch_status();
 }

@@ -104,5 +104,7 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
     return (long)nsid_sumsq_blocks(rows) * (long)sizeof(float);
   if (strcmp(op, "flat_l2_topk") == 0)       // rows = query rows, cols = database rows; for k = 64
     return nsid_l2_ws_bytes(rows, cols, 64);
+  if (strcmp(op, "flat_l2_topk_coarse") == 0)   // the same rows / cols: the pre-filter's candidate lists per (row, split)
+    return nsid_l2_coarse_ws_bytes(rows, cols);
   return -1;
 }

@@ -94,14 +94,16 @@ class SampleIndex:
     """A resident sample-identification index. model: SimCLR (graph encoder) or BaselineModel (ResNet-IBN, no re-rank); classifier: a
     CrossAttentionClassifier for rerank=True and match_score; front: LogMelFrontEnd / CQTFrontEnd, needed only for waveforms.
     model may be None for an index fed with precomputed rows only (add_rows, identify(fp=...)); then d is taken from the first
-    rows."""
+    rows. prefilter: the index's searches (identify, identify_pairs, locate, links) run through FlatL2Index's certified bf16
+    pre-filter; the results are the same bits."""
 
-    def __init__(self, model, classifier=None, front=None, device="cuda", micro_batch: int = 1024):
+    def __init__(self, model, classifier=None, front=None, device="cuda", micro_batch: int = 1024, prefilter: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SampleIndex runs on the MI355X (cuda) device; there is no CPU path")
         self.model, self.classifier, self.front = model, classifier, front
         self.micro_batch = int(micro_batch)
+        self.prefilter = bool(prefilter)
         self.names: List[str] = []
         self._code = {}
         self._song_rows = []                  # per song: (first ref row, rows, rows with node matrices)
@@ -155,7 +157,7 @@ class SampleIndex:
     def _store(self):
         """the device state, made with the first rows"""
         if self._index is None:
-            self._index = FlatL2Index(self._d, self.device)
+            self._index = FlatL2Index(self._d, self.device, prefilter=self.prefilter)
             self._song_of = torch.empty((0,), device=self.device, dtype=torch.int32)
             self._song_of_nodes = torch.empty((0,), device=self.device, dtype=torch.int32)
         return self._index

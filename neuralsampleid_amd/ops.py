@@ -1901,6 +1901,116 @@ def flat_l2_topk_excl(q, x, x_sqnorm, k, ex_lo, ex_hi, q_sqnorm=None) -> Tuple[t
     return _flat_l2_topk("flat_l2_topk_excl", q, x, x_sqnorm, k, q_sqnorm, (ex_lo, ex_hi))
 
 
+# ---- the certified bf16 pre-filter (include/nsid.h)
+PREFILTER_M = SEARCH_MAX_K          # candidates per query row
+PREFILTER_MAX_D = 256               # the coarse kernel's widest row; above it the plain search runs
+
+
+def prefilter_d_ok(d) -> bool:
+    return d % 16 == 0 and 16 <= d <= PREFILTER_MAX_D
+
+
+def _bf16_rows_t(t, name):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.bfloat16 or t.dim() != 2 or t.stride(1) != 1 \
+            or t.stride(0) % 8 or t.data_ptr() % 16:
+        raise RuntimeError(f"{name}: expected a (rows, d) bfloat16 matrix on the GPU with unit column stride and 16-byte aligned rows")
+    return max(t.stride(0), t.shape[1])
+
+
+def bf16_rows(x) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """(n, d) fp32 -> (xb, err, nrm): the round-to-nearest-even bf16 rows, err[i] >= ||x_i - xb_i|| and nrm[i] >= max(||x_i||,
+    ||xb_i||) as fp32 rounded upwards (fp64 sums on the device)"""
+    ldx = _search_rows(x, "bf16_rows")
+    n, d = x.shape
+    xb = torch.empty((n, d), device=x.device, dtype=torch.bfloat16)
+    err = torch.empty((n,), device=x.device, dtype=torch.float32)
+    nrm = torch.empty((n,), device=x.device, dtype=torch.float32)
+    _tk("bf16_rows_kernel", 6.0 * n * d + 8.0 * n, lambda: call("nsid_bf16_rows", _p(x), ldx, n, d, _p(xb), d, _p(err), _p(nrm), _stream()),
+        (n, d, 0, 1))
+    return xb, err, nrm
+
+
+def _ex_pair(name, ex, nq):
+    for t in ex or ():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() \
+                or t.numel() != nq:
+            raise ValueError(f"{name}: ex_lo and ex_hi must be contiguous int32 tensors of {nq} entries on the GPU")
+
+
+def flat_l2_topk_coarse(qb, xb, x_sqnorm, ex=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """the pre-filter's coarse pass: per row of qb (nq, d) bf16 the PREFILTER_M smallest coarse keys x_sqnorm[j] - 2 qb.xb_j (bf16
+    MFMA, fp32 accumulate) over the rows of xb, ties smaller id first; ex = (ex_lo, ex_hi) as in flat_l2_topk_excl. Returns ckey
+    (nq, M) fp32 and cid (nq, M) int32, pads (+inf, INT_MAX) last."""
+    name = "flat_l2_topk_coarse"
+    ldq, ldx = _bf16_rows_t(qb, f"{name} qb"), _bf16_rows_t(xb, f"{name} xb")
+    nq, d = qb.shape
+    nx = xb.shape[0]
+    if xb.shape[1] != d:
+        raise ValueError(f"{name}: query d = {d} != database d = {xb.shape[1]}")
+    if not prefilter_d_ok(d):
+        raise ValueError(f"{name}: d = {d} is outside d % 16 == 0 and 16 <= d <= {PREFILTER_MAX_D}")
+    _chk(x_sqnorm)
+    if x_sqnorm.numel() != nx:
+        raise ValueError(f"{name}: x_sqnorm must hold one norm per database row")
+    _ex_pair(name, ex, nq)
+    M = PREFILTER_M
+    ckey = torch.empty((nq, M), device=qb.device, dtype=torch.float32)
+    cid = torch.empty((nq, M), device=qb.device, dtype=torch.int32)
+    if nq == 0:
+        return ckey, cid
+    wsb = int(lib.nsid_workspace_bytes(b"flat_l2_topk_coarse", nq, nx))
+    ws = torch.empty((max(wsb, 16),), device=qb.device, dtype=torch.uint8)
+    xp, xnp = (_p(xb), _p(x_sqnorm)) if nx else (None, None)
+    lo, hi = (_p(ex[0]), _p(ex[1])) if ex is not None else (None, None)
+    _timed(name, 2.0 * nq * nx * d, 2.0 * nx * d + 2.0 * nq * d + 8.0 * nq * M, lambda: call(
+        "nsid_flat_l2_topk_coarse", _p(qb), ldq, nq, xp, ldx, nx, xnp, lo, hi, d, _p(ckey), _p(cid), _p(ws), ws.numel(), _stream()),
+        (nq, nx, d, M))
+    return ckey, cid
+
+
+def flat_l2_rescore(q, x, x_sqnorm, q_sqnorm, q_err, q_nrm, xmax, exmax, ckey, cid, k):
+    """the pre-filter's exact pass: the candidates cid (nq, M) of every query row re-scored with flat_l2_topk's fp32 chain and sorted by
+    (key, id). Returns (D, I, E, cert): (nq, k) results, the per-row error bound and the uint8 certificate; D / I of a row with
+    cert = 0 are not the search result. xmax / exmax: device floats (1 element) >= max ||x_j|| / max ||x_j - bf16(x_j)||."""
+    name = "flat_l2_rescore"
+    k = int(k)
+    if not 1 <= k <= SEARCH_MAX_K:
+        raise ValueError(f"{name}: k = {k} is outside [1, {SEARCH_MAX_K}]")
+    ldq, ldx = _search_rows(q, f"{name} q"), _search_rows(x, f"{name} x")
+    nq, d = q.shape
+    nx = x.shape[0]
+    if x.shape[1] != d or not prefilter_d_ok(d):
+        raise ValueError(f"{name}: d = {d} / {x.shape[1]} must agree and lie in d % 16 == 0, 16 <= d <= {PREFILTER_MAX_D}")
+    _chk(x_sqnorm, q_sqnorm, q_err, q_nrm, xmax, exmax, ckey)
+    if x_sqnorm.numel() != nx or q_sqnorm.numel() != nq or q_err.numel() != nq or q_nrm.numel() != nq or xmax.numel() != 1 \
+            or exmax.numel() != 1:
+        raise ValueError(f"{name}: one norm per row and one-element xmax / exmax are expected")
+    M = PREFILTER_M
+    if tuple(ckey.shape) != (nq, M) or tuple(cid.shape) != (nq, M) or cid.dtype != torch.int32 or not cid.is_cuda or not cid.is_contiguous():
+        raise ValueError(f"{name}: ckey / cid must be ({nq}, {M}) fp32 / int32 tensors on the GPU")
+    D = torch.empty((nq, k), device=q.device, dtype=torch.float32)
+    I = torch.empty((nq, k), device=q.device, dtype=torch.int64)
+    E = torch.empty((nq,), device=q.device, dtype=torch.float32)
+    cert = torch.empty((nq,), device=q.device, dtype=torch.uint8)
+    if nq == 0:
+        return D, I, E, cert
+    xp, xnp = (_p(x), _p(x_sqnorm)) if nx else (None, None)
+    _timed(name, 128.0 * nq * M * d, 4.0 * nq * M * d + 4.0 * nq * d + 12.0 * nq * k, lambda: call(
+        "nsid_flat_l2_rescore", _p(q), ldq, nq, xp, ldx, nx, xnp, _p(q_sqnorm), _p(q_err), _p(q_nrm), _p(xmax), _p(exmax), _p(ckey),
+        _p(cid), d, k, _p(D), _p(I), _p(E), _p(cert), _stream()), (nq, M, d, k))
+    return D, I, E, cert
+
+
+def flat_l2_topk_pre(q, x, xb16, x_sqnorm, xmax, exmax, k, ex=None):
+    """flat_l2_topk (ex = None) or flat_l2_topk_excl (ex = (ex_lo, ex_hi)) through the certified bf16 pre-filter: bf16_rows of the
+    queries, the coarse pass over xb16 (bf16_rows of x), the exact re-score. Returns (D, I, cert); rows with cert = 1 hold the plain
+    entry's result bit for bit, rows with cert = 0 do NOT: there is no fallback here (search.FlatL2Index.search runs it)."""
+    qb, q_err, q_nrm = bf16_rows(q)
+    ckey, cid = flat_l2_topk_coarse(qb, xb16, x_sqnorm, ex)
+    D, I, _, cert = flat_l2_rescore(q, x, x_sqnorm, row_sqnorm(q), q_err, q_nrm, xmax, exmax, ckey, cid, k)
+    return D, I, cert
+
+
 def seq_scores(q, x, I, starts, lens, ldo) -> torch.Tensor:
     """eval.py:325-331 for every (start, length) pair at once: out[p, j] = mean over i < min(L, nx - cid) of q[s+i].x[cid+i] with
     cid = I[s + j // k, j % k] (j < L k), NaN for cid < 0 and for j >= L k. starts / lens: host integer sequences (checked here

@@ -7,6 +7,7 @@ behaviour. One deliberate difference: the reference extends dummy_db.mm in place
 eval.py:263-267); here the database lives in GPU memory and every input file is left as it was.
 
     python -m neuralsampleid_amd.search --emb-dir DIR --gt gt_dict.json [--dummy-dir DIR] [--k-probe 20] [--test-seq-len "1 3 5"]
+        [--prefilter]
 """
 import argparse
 import json
@@ -21,13 +22,16 @@ from . import fpdb, ops
 
 SLAB_BYTES = 256 << 20          # host -> device copies of a memmap in slabs of at most this size
 QUERY_BLOCK = 65536             # query rows per flat_l2_topk launch (bounds the workspace)
+PREFILTER_CUT_K = ops.PREFILTER_M // 2   # the pre-filter serves k up to here; larger k runs the plain search
 
 
 class FlatL2Index:
     """faiss.IndexFlatL2 on the MI355X: exhaustive squared-L2 search, ids in add() order. search() of a numpy array returns
     numpy (float32 D, int64 I, as FAISS does); of a torch tensor, tensors on the index's device."""
 
-    def __init__(self, d: int, device="cuda"):
+    def __init__(self, d: int, device="cuda", prefilter: bool = False):
+        """prefilter: search() runs the certified bf16 pre-filter (results are the plain search's bit for bit).
+        The index then also keeps a bf16 copy of its rows (2 d more bytes per row) and two running maxima as device scalars."""
         d = int(d)
         if not ops.search_d_ok(d):
             raise ValueError(f"FlatL2Index: d = {d} is outside the search kernels' limits ({ops.SEARCH_D_LIMITS})")
@@ -38,10 +42,46 @@ class FlatL2Index:
         self._x = torch.empty((0, d), device=self.device, dtype=torch.float32)
         self._norm = torch.empty((0,), device=self.device, dtype=torch.float32)
         self._n = 0
+        self._prefilter = bool(prefilter)
+        self._xb16 = None               # the bf16 rows, built by _sync_bf16 for the first _nb16 rows
+        self._xmax = self._exmax = None  # device scalars >= max ||x_j|| (and of its bf16 image), >= max ||x_j - bf16(x_j)||
+        self._nb16 = 0
+        self.prefilter_stats = {"rows": 0, "certified": 0, "fell_back": 0, "bypassed": 0}
 
     @property
     def ntotal(self) -> int:
         return self._n
+
+    @property
+    def prefilter(self) -> bool:
+        return self._prefilter
+
+    def enable_prefilter(self) -> None:
+        """switch the pre-filter on for later searches; the bf16 copy of the rows stored so far is built now"""
+        self._prefilter = True
+        self._sync_bf16()
+
+    def _sync_bf16(self) -> None:
+        """bring the bf16 copy and the running maxima up to the stored rows (nothing at a d the coarse kernel does not take)"""
+        if not ops.prefilter_d_ok(self.d) or (self._xb16 is not None and self._nb16 == self._n):
+            return
+        if self._xb16 is None:
+            self._xb16 = torch.empty((self._x.shape[0], self.d), device=self.device, dtype=torch.bfloat16)
+            self._xmax = torch.zeros((1,), device=self.device, dtype=torch.float32)
+            self._exmax = torch.zeros((1,), device=self.device, dtype=torch.float32)
+            self._nb16 = 0
+        if self._xb16.shape[0] < self._x.shape[0]:
+            xb = torch.empty((self._x.shape[0], self.d), device=self.device, dtype=torch.bfloat16)
+            xb[: self._nb16].copy_(self._xb16[: self._nb16])
+            self._xb16 = xb
+        step = max(1, SLAB_BYTES // (4 * self.d))
+        for a in range(self._nb16, self._n, step):
+            b = min(self._n, a + step)
+            xb, err, nrm = ops.bf16_rows(self._x[a:b])
+            self._xb16[a:b].copy_(xb)
+            self._xmax = torch.maximum(self._xmax, nrm.max().reshape(1))       # NaN propagates: then no row is ever certified
+            self._exmax = torch.maximum(self._exmax, err.max().reshape(1))
+        self._nb16 = self._n
 
     @property
     def xb(self) -> torch.Tensor:
@@ -77,12 +117,17 @@ class FlatL2Index:
         if n:
             self._norm[self._n: self._n + n] = ops.row_sqnorm(self._x[self._n: self._n + n])
         self._n += n
+        if self._prefilter:
+            self._sync_bf16()
 
-    def search(self, q, k: int, exclude=None):
+    def search(self, q, k: int, exclude=None, prefilter: Optional[bool] = None):
         """(nq, d) queries -> (D, I): (nq, k) squared L2 distances ascending and row ids; ties smaller id first; k > ntotal pads
         with I = -1, D = +inf. exclude = (lo, hi): two array-likes of nq row ids; the stored rows lo[i] <= j < hi[i] do not compete
         for query row i (leave-one-out search: the query is a run of stored rows), and its result is bitwise the search over the
-        index without them. Checked on the host (0 <= lo <= hi <= ntotal) before the device is touched."""
+        index without them. Checked on the host (0 <= lo <= hi <= ntotal) before the device is touched.
+        prefilter (None: the index's setting): per QUERY_BLOCK the certified bf16 pre-filter (ops.flat_l2_topk_pre) runs first; the
+        rows it does not certify are counted (one device-to-host read) and searched with the plain entry, so the result is the same
+        bits either way. d > 256 and k > PREFILTER_M / 2 go straight to the plain entry. prefilter_stats counts the rows."""
         as_numpy = not isinstance(q, torch.Tensor)
         k = int(k)
         if not 1 <= k <= ops.SEARCH_MAX_K:
@@ -99,12 +144,38 @@ class FlatL2Index:
         I = torch.empty((nq, k), device=self.device, dtype=torch.int64)
         if ex is not None:
             ex = torch.from_numpy(ex).to(self.device)           # one upload: rows 0 / 1 = lo / hi
+        use = getattr(self, "_prefilter", False) if prefilter is None else bool(prefilter)     # (no setting: an index put together by hand)
+        # k > M / 2 leaves fewer than M / 2 coarse keys between the k-th candidate and the threshold: the plain entry at once
+        # (PREFILTER_CUT_K: a starting point, not yet moved by a measurement; docs/experiments.md)
+        pre = use and ops.prefilter_d_ok(self.d) and k <= PREFILTER_CUT_K
+        if pre:
+            self._sync_bf16()
+        norm = self._norm[: self._n]
         for a in range(0, nq, QUERY_BLOCK):
             b = min(nq, a + QUERY_BLOCK)
-            if ex is None:
-                D[a:b], I[a:b] = ops.flat_l2_topk(qt[a:b], self.xb, self._norm[: self._n], k)
+            exb = None if ex is None else (ex[0, a:b], ex[1, a:b])
+            if pre:
+                Db, Ib, cert = ops.flat_l2_topk_pre(qt[a:b], self.xb, self._xb16[: self._n], norm, self._xmax, self._exmax, k, exb)
+                rest = torch.nonzero(cert == 0).flatten()                 # the one device-to-host read: how many rows remain
+                if rest.numel():
+                    qr = qt[a:b].index_select(0, rest)
+                    if exb is None:
+                        Dr, Ir = ops.flat_l2_topk(qr, self.xb, norm, k)
+                    else:
+                        Dr, Ir = ops.flat_l2_topk_excl(qr, self.xb, norm, k, exb[0].index_select(0, rest), exb[1].index_select(0, rest))
+                    Db[rest], Ib[rest] = Dr, Ir
+                D[a:b], I[a:b] = Db, Ib
+                self.prefilter_stats["rows"] += b - a
+                self.prefilter_stats["fell_back"] += int(rest.numel())
+                self.prefilter_stats["certified"] += b - a - int(rest.numel())
+                continue
+            if use:
+                self.prefilter_stats["rows"] += b - a
+                self.prefilter_stats["bypassed"] += b - a
+            if exb is None:
+                D[a:b], I[a:b] = ops.flat_l2_topk(qt[a:b], self.xb, norm, k)
             else:
-                D[a:b], I[a:b] = ops.flat_l2_topk_excl(qt[a:b], self.xb, self._norm[: self._n], k, ex[0, a:b], ex[1, a:b])
+                D[a:b], I[a:b] = ops.flat_l2_topk_excl(qt[a:b], self.xb, norm, k, exb[0], exb[1])
         if as_numpy:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
@@ -251,7 +322,7 @@ def _slabs(mm, d):
         yield s
 
 
-def _load_db(emb_dir, emb_dummy_dir, query_name, device):
+def _load_db(emb_dir, emb_dummy_dir, query_name, device, prefilter=False):
     """the databases of one evaluation: (FlatL2Index over dummy ++ ref, the query rows on its device, query lookup, ref lookup,
     rows of dummy_db). Shared by eval_hit_rates, rerank.py and baseline_eval.py."""
     query = _open_rows(emb_dir, query_name)
@@ -264,7 +335,7 @@ def _load_db(emb_dir, emb_dummy_dir, query_name, device):
     ref_lookup = fpdb.load_lookup(emb_dir, "ref_db")
     if len(query_lookup) != query.shape[0] or len(ref_lookup) != ref.shape[0]:
         raise ValueError("a lookup table does not have one entry per database row")
-    index = FlatL2Index(d, device)
+    index = FlatL2Index(d, device, prefilter=prefilter)
     for s in _slabs(dummy, d):                                        # index.add(dummy_db); index.add(db): eval.py:243-244
         index.add(s)
     for s in _slabs(ref, d):
@@ -278,20 +349,21 @@ def _load_db(emb_dir, emb_dummy_dir, query_name, device):
 
 
 def eval_hit_rates(emb_dir: str, gt: Union[str, Dict[str, Sequence[str]]], emb_dummy_dir: Optional[str] = None,
-                   test_seq_len='1 3 5 9 11 19', k_probe: int = 20, save: bool = True, device="cuda"):
+                   test_seq_len='1 3 5 9 11 19', k_probe: int = 20, save: bool = True, device="cuda",
+                   prefilter: bool = False):
     """eval.py eval_faiss(emb_dir, emb_dummy_dir, index_type='l2', test_seq_len=..., k_probe=...) on the GPU.
 
     Reads {query,ref}_db from emb_dir and dummy_db from emb_dummy_dir (default emb_dir) in fpdb's format; gt: {ref song:
     [query ids]} or its JSON path (the reference reads data/gt_dict.json). Returns hit_rates (3, len(test_seq_len)): top-1/3/10
     in percent per query length; with save, writes hit_rates.npy, raw_score.npy and test_ids.npy into emb_dir as the reference
-    does. Input files are never modified."""
+    does. Input files are never modified. prefilter: the search runs through the certified bf16 pre-filter (same results)."""
     gt = _load_gt(gt)
     sl = parse_seq_len(test_seq_len)
     k_probe = int(k_probe)
     if not 1 <= k_probe <= ops.SEARCH_MAX_K:
         raise ValueError(f"k_probe = {k_probe} is outside [1, {ops.SEARCH_MAX_K}]")
     emb_dummy_dir = emb_dir if emb_dummy_dir is None else emb_dummy_dir
-    index, qt, query_lookup, ref_lookup, n_dummy = _load_db(emb_dir, emb_dummy_dir, "query_db", device)
+    index, qt, query_lookup, ref_lookup, n_dummy = _load_db(emb_dir, emb_dummy_dir, "query_db", device, prefilter)
 
     # every query row is searched once: a (test, length) pair uses rows [start, start + length) of the one result
     _, I = index.search(qt, k_probe)
@@ -323,8 +395,9 @@ def main(argv=None) -> None:
     ap.add_argument("--k-probe", type=int, default=20)
     ap.add_argument("--test-seq-len", default="1 3 5 9 11 19")
     ap.add_argument("--no-save", action="store_true", help="do not write hit_rates.npy / raw_score.npy / test_ids.npy")
+    ap.add_argument("--prefilter", action="store_true", help="search through the certified bf16 pre-filter (same results)")
     a = ap.parse_args(argv)
-    hr = eval_hit_rates(a.emb_dir, a.gt, a.dummy_dir, a.test_seq_len, a.k_probe, save=not a.no_save)
+    hr = eval_hit_rates(a.emb_dir, a.gt, a.dummy_dir, a.test_seq_len, a.k_probe, save=not a.no_save, prefilter=a.prefilter)
     print(format_hit_rates(hr, a.test_seq_len))
 
 
