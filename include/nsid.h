@@ -9,7 +9,8 @@
  *  - features are node-major rows: a (B, C, N, 1) reference tensor is the matrix X[B*N][C] (row = b*N + n);
  *  - `stream` is a hipStream_t; calls only enqueue work: no allocation, no synchronisation, no retained
  *    pointers, safe under hipGraph stream capture;
- *  - return value: NSID_OK, or a negative NSID_E* code (the Python host raises RuntimeError on it);
+ *  - return value: NSID_OK, or a negative NSID_E* code (the Python host raises RuntimeError on it); the four entries that try a
+ *    fused form may also answer NSID_DECLINED (below);
  *  - buffers documented "+=" are accumulated into (zero them first for a fresh gradient).
  */
 #ifndef NSID_H
@@ -24,6 +25,10 @@ extern "C" {
 #define NSID_OK 0
 #define NSID_EINVAL (-1)   /* unsupported shape / misaligned pointer / bad argument */
 #define NSID_ELAUNCH (-2)  /* the HIP runtime refused the launch */
+/* not an error: the entry's fused or fast form does not serve this call. Nothing was launched or written, and the caller runs the
+ * unfused sequence named at the entry. Only nsid_ffn_fused_fwd, nsid_mrconv_fused_fwd, nsid_linear_bwd_data_bnapply and
+ * nsid_mr_aggregate_bwd_bn return it; null pointers and bad arguments stay NSID_EINVAL there too. */
+#define NSID_DECLINED 1
 
 #define NSID_ACT_NONE 0
 #define NSID_ACT_RELU 1
@@ -66,6 +71,15 @@ long nsid_debug_counter(const char* key);
 int nsid_debug_counters_reset(void);
 int nsid_debug_counter_count(void);
 const char* nsid_debug_counter_key(int i);
+/* debug: the kernel the last entry that chooses between kernels took (the nsid_linear_* GEMMs, nsid_knn_graph, nsid_mr_aggregate_bwd
+   and _bwd_bn), as its profile family: the kernel's name with the template arguments that tell the families apart, e.g.
+   "gemm_kernel<128,64,true,true>", "ws_bwd_kernel +bn_apply_load", "wgrad3_kernel", "knn_sel_kernel", "mr_bwd_sorted_kernel +bn_sums".
+   A helper kernel of the same entry (zero fill, ELU pass) does not change it; "" before any such entry has run. A string literal of
+   the library: valid for the life of the process. */
+const char* nsid_debug_last_kernel(void);
+/* 1 when (cin, cout, groups) is a layer of the weight-stationary GEMMs (csrc/wsgemm.hip NSID_WS_LAYERS: forward, backward-data and
+   backward-data with the BatchNorm backward on its operand load serve the same nine layers), else 0 */
+int nsid_ws_layer(int cin, int cout, int groups);
 /* launches of nsid_linear_fwd / nsid_linear_fwd_res that took the 256x256-tile LDS-DMA kernel (csrc/gemm256.hip) so far */
 long nsid_gemm_g256_launches(void);
 /* number of NSID_ROW_TILE row tiles of an M-row matrix: size of the partial-statistics buffers */
@@ -115,7 +129,7 @@ int nsid_linear_fwd_res(const void* x, int ldx, const void* w, int w_dtype, cons
                         const float* in_shift, int act_in, int act_dtype, void* stream);
 /* eval-mode FFN in ONE launch: out = x + W2 relu(W1 x + b1) + b2 with both BatchNorms folded into (W1, b1) (H x C) and (W2, b2)
    (C x H) — FFN.forward, encoder/graph_encoder.py:82-89, in eval mode. x, out: M x C bf16 contiguous; W1, W2: bf16 row-major;
-   b1, b2 fp32. The M x H hidden tensor never reaches HBM. Returns 1 (nothing launched) outside C in {64, 128} with M % 128 == 0 or
+   b1, b2 fp32. The M x H hidden tensor never reaches HBM. Returns NSID_DECLINED (nothing launched) outside C in {64, 128} with M % 128 == 0 or
    C = 256 with M % 256 == 0 (csrc/ffn256_fused.hip; tuning key "ffn256"), H = 4C: the caller then runs nsid_linear_fwd +
    nsid_linear_fwd_res. */
 int nsid_ffn_fused_fwd(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int M, int C,
@@ -123,7 +137,7 @@ int nsid_ffn_fused_fwd(const void* x, const void* w1, const float* b1, const voi
 /* eval-mode MRConv2d in ONE launch, one workgroup per clip: v = relu(W (*)_4 [y, max_j(y[idx_j] - y)] + b) with the BatchNorm folded
    into (W, b) — MRConv2d.forward (gcn_lib/torch_vertex.py:19-34) + BasicConv (torch_nn.py:52-76) in eval mode. y: (B*N, C) bf16 plain
    values (the producer's BatchNorm folded too), idx: (B, N, k) clip-local, w: (2C, C/2) bf16, bias: (2C) fp32, out: (B*N, 2C) bf16.
-   The interleaved (B*N, 2C) tensor of nsid_mr_aggregate_fwd is never formed. Returns 1 (nothing launched) outside C in {64, 128, 256},
+   The interleaved (B*N, 2C) tensor of nsid_mr_aggregate_fwd is never formed. Returns NSID_DECLINED (nothing launched) outside C in {64, 128, 256},
    N*C = 16384, k <= 64: the caller then runs nsid_mr_aggregate_fwd + nsid_linear_fwd. */
 int nsid_mrconv_fused_fwd(const void* y, const int32_t* idx, int B, int N, int C, int k, const void* w, const float* bias, void* out,
                           void* stream);
@@ -146,7 +160,7 @@ int nsid_linear_bwd_data_bn(const void* dout, int ldd, const void* w, int w_dtyp
  * nsid_bn_bwd_apply pass + nsid_linear_bwd_data[_bn] pair of a Conv2d+BatchNorm2d(+ReLU) site (encoder/graph_encoder.py:74-77,
  * gcn_lib/torch_nn.py:56-60, torch_vertex.py:152-155). bn_* as in nsid_linear_bwd_data_bn (bn_r NULL: none).
  * dr must not alias dy or r (NSID_EINVAL): only column tile 0 of a row panel writes dr while the other column tiles read dy and r.
- * Returns 1, having launched nothing, when the shape is outside the fused form (caller: run the two-call form). */
+ * Returns NSID_DECLINED, having launched nothing, when the shape is outside the fused form (caller: run the two-call form). */
 int nsid_linear_bwd_data_bnapply(const void* dy, const void* r, const float* coef4, int act, void* dr, const void* w, int w_dtype,
                                  const void* addend, int ldadd, void* din, int ldi, int M, int Nout, int K, int groups,
                                  int act_dtype, const void* bn_r, const float* bn_scale, const float* bn_shift,
@@ -249,7 +263,9 @@ int nsid_mr_aggregate_bwd(const void* du, const int32_t* idx, const uint8_t* arg
 /* backward of the aggregation when its input was y = act(BN(r)) of a conv+BatchNorm layer (Grapher fc1, encoder/gcn_lib/torch_vertex.py:
  * 183-195): dy as above, plus step 1 of that BatchNorm's backward over the clip's rows, partial[2][B][C] (one row per clip:
  * nsid_bn_bwd_finalize[_fused] takes tiles = B), from the ROUNDED dy -- what nsid_bn_bwd_reduce would compute from the stored dy.
- * bf16 storage, N*C = 16384, C a power of two in [64, 512] (the encoder's clip at every stage); NSID_EINVAL otherwise. */
+ * bf16 storage only (another dtype, a null or misaligned pointer: NSID_EINVAL). Served by the degree-ranked kernel alone: N*C = 16384,
+ * C a power of two in [64, 512] (the encoder's clip at every stage), k >= tuning key "mr_bwd_sorted_min_k" > 0; NSID_DECLINED, nothing
+ * launched or written, otherwise (caller: nsid_mr_aggregate_bwd, and nsid_bn_bwd_reduce for the sums). */
 int nsid_mr_aggregate_bwd_bn(const void* du, const int32_t* idx, const uint8_t* argmax, int B, int N, int C, int k, void* dy,
                              const void* bn_r, int bn_ldr, const float* bn_scale, const float* bn_shift, const float* bn_mean,
                              const float* bn_invstd, int bn_act, float* partial, int dtype, void* stream);

@@ -126,7 +126,8 @@ def _load():
 lib = _load()
 
 _ERR = {DEFINES["NSID_EINVAL"]: "NSID_EINVAL (unsupported shape, misaligned pointer or bad argument)",
-        DEFINES["NSID_ELAUNCH"]: "NSID_ELAUNCH (HIP runtime refused the launch)"}
+        DEFINES["NSID_ELAUNCH"]: "NSID_ELAUNCH (HIP runtime refused the launch)",
+        DEFINES["NSID_DECLINED"]: "NSID_DECLINED (the fused form does not serve this call; nothing was launched)"}
 
 
 def call(name, *args):

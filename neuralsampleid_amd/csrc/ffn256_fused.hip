@@ -275,13 +275,13 @@ void ffn256_fused_kernel(const F256Args p) {
 
 }  // namespace
 
-// returns NSID_OK / NSID_ELAUNCH, or 1 (nothing launched) outside {C = 256 or 128, M % 256 == 0} / {C = 64, M % 512 == 0} with H = 4 C.
+// returns NSID_OK / NSID_ELAUNCH, or NSID_DECLINED (nothing launched) outside {C = 256 or 128, M % 256 == 0} / {C = 64, M % 512 == 0} with H = 4 C.
 __attribute__((visibility("hidden")))
 int nsid_ffn256_fused_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int M, int C,
                              int H, hipStream_t stream) {
-  if (!(C == 256 || C == 128 || C == 64) || H != 4 * C || M <= 0) return 1;
+  if (!(C == 256 || C == 128 || C == 64) || H != 4 * C || M <= 0) return NSID_DECLINED;
   const int tr = C == 64 ? 512 : 256;         // rows per workgroup tile
-  if (M % tr != 0) return 1;
+  if (M % tr != 0) return NSID_DECLINED;
   F256Args p{static_cast<const __bf16*>(x), static_cast<const __bf16*>(w1), b1, static_cast<const __bf16*>(w2), b2,
              static_cast<__bf16*>(out), M};
   static int n_cu = 0;

@@ -177,7 +177,7 @@ int ffn_launch(const FfnArgs& p, hipStream_t s) {
 
 }  // namespace
 
-// Returns 1 (nothing launched) for shapes outside the fused form: C in {64, 128}, H = 4C, M % 128 == 0, contiguous bf16 rows.
+// Returns NSID_DECLINED (nothing launched) for shapes outside the fused form: C in {64, 128}, H = 4C, M % 128 == 0, contiguous bf16 rows.
 extern "C" int nsid_ffn_fused_fwd(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int M,
                                   int C, int H, void* stream) {
   NSID_REQUIRE(x && w1 && b1 && w2 && b2 && out && M > 0);
@@ -193,7 +193,7 @@ extern "C" int nsid_ffn_fused_fwd(const void* x, const void* w1, const float* b1
     if (rc == NSID_OK) nsid_count(NSID_C_ffn_fused);
     return rc;
   }
-  if (!(C == 64 || C == 128) || H != 4 * C || M % FF_TM != 0) return 1;
+  if (!(C == 64 || C == 128) || H != 4 * C || M % FF_TM != 0) return NSID_DECLINED;
   NSID_REQUIRE(nsid_aligned16(x) && nsid_aligned16(w1) && nsid_aligned16(w2) && nsid_aligned16(out) && nsid_aligned16(b1) &&
                nsid_aligned16(b2));
   FfnArgs p{static_cast<const __bf16*>(x), static_cast<const __bf16*>(w1), b1, static_cast<const __bf16*>(w2), b2,

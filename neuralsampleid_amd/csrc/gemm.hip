@@ -927,6 +927,21 @@ int g_gemm_precision = NSID_GEMM_FP32;     // process-wide (nsid_set_gemm_precis
 // so that the arithmetic of a training step does not depend on the batch size.
 long g_g256_launches = 0;     // launches that took gemm256.hip (tests check that the kernel under test really ran)
 
+// profile family of launch<BM, BN, AR, BR> (nsid_took): the four template arguments every kernel-table row of this file is keyed by
+template <int BM, int BN, bool AR, bool BR>
+const char* gemm_family(bool abn) {
+  static_assert(AR == BR || AR, "kinds: forward (true, true), backward-data (true, false), weight gradient (false, false)");
+  static_assert(AR ? (BM == 128 && (BN == 64 || BN == 128)) : ((BM == 64 && BN == 64) || (BM == 128 && (BN == 64 || BN == 128))),
+                "a tile shape without a family name");
+  if constexpr (AR && BR) return BN == 64 ? "gemm_kernel<128,64,true,true>" : "gemm_kernel<128,128,true,true>";
+  else if constexpr (AR) {
+    if (abn) return BN == 64 ? "gemm_kernel<128,64,true,false> +bn_apply_load" : "gemm_kernel<128,128,true,false> +bn_apply_load";
+    return BN == 64 ? "gemm_kernel<128,64,true,false>" : "gemm_kernel<128,128,true,false>";
+  } else {
+    return BM == 64 ? "gemm_kernel<64,64,false,false>" : (BN == 64 ? "gemm_kernel<128,64,false,false>" : "gemm_kernel<128,128,false,false>");
+  }
+}
+
 template <int BM, int BN, bool AR, bool BR>
 int launch(GemmArgs p, int groups, hipStream_t s, int act_dtype, bool w_bf16 = false) {
   const int tiles = ((p.I + BM - 1) / BM) * ((p.J + BN - 1) / BN);
@@ -970,10 +985,11 @@ int launch(GemmArgs p, int groups, hipStream_t s, int act_dtype, bool w_bf16 = f
   const long wgs = (long)tiles * p.rsplit * groups;
   // (rchunk % 128: whole rounds of two 64-deep stages)
   const int ks = (full && wgs <= deep_maxwg && nsid_tune(NSID_T_gemm_deep_ks) == 2 && (deep_kinds & kind_bit) && p.rchunk % 128 == 0) ? 2 : 1;
-  if (p.abn_r != nullptr) {     // outside the fused BatchNorm-backward form: 1 = nothing launched, the caller runs the unfused pair
+  if (p.abn_r != nullptr) {     // outside the fused BatchNorm-backward form: nothing launched, the caller runs the unfused pair
     if (!(AR && !BR && BM == 128)) return NSID_EINVAL;
-    if (!(st16 && w_bf16 && full)) return 1;
+    if (!(st16 && w_bf16 && full)) return NSID_DECLINED;
   }
+  nsid_took(gemm_family<BM, BN, AR, BR>(p.abn_r != nullptr));
   nsid_count(AR ? (BR ? NSID_C_gemm_fwd : NSID_C_gemm_bwd_data) : NSID_C_gemm_bwd_weight);
   if (p.split_major) nsid_count(NSID_C_gemm_split_major);
   if (aff) nsid_count(NSID_C_gemm_affine_load);
@@ -1248,7 +1264,7 @@ static int linear_fwd_impl(const void* x, int ldx, const void* w, int w_dtype, c
       act_in != NSID_ACT_ELU) {
     const int rcw = nsid_ws_fwd_launch(x, ldx, w, bias, out, ldo, M, Nout, K, groups, in_scale, in_shift, act_slope(act_in), stat,
                                        p.stat_plane, p.stat_ld, s);
-    if (rcw != 1) { nsid_count(NSID_C_ws_fwd); return rcw; }
+    if (rcw != NSID_DECLINED) { nsid_count(NSID_C_ws_fwd); return rcw; }
   }
   const long g256_min = nsid_tune(NSID_T_g256_min);
   if (g256_min > 0 && (stat == nullptr || nsid_tune(NSID_T_g256_train) != 0) && act_dtype == NSID_BF16 && wb && groups == 1 && in_scale == nullptr && ksplit == 1 &&
@@ -1256,7 +1272,7 @@ static int linear_fwd_impl(const void* x, int ldx, const void* w, int w_dtype, c
       (long)(M / 256) * (Nout / 256) >= g256_min) {
     const int rc256 = nsid_gemm256_fwd_launch(x, ldx, w, bias, addend, ldadd, out, ldo, M, Nout, K, act_out == NSID_ACT_RELU, stat,
                                               p.stat_plane, p.stat_ld, s);
-    if (rc256 != 1) { ++g_g256_launches; nsid_count(NSID_C_gemm256); return rc256; }
+    if (rc256 != NSID_DECLINED) { ++g_g256_launches; nsid_count(NSID_C_gemm256); return rc256; }
   }
   const int rc = narrow ? launch<128, 64, true, true>(p, groups, s, act_dtype, wb) : launch<128, 128, true, true>(p, groups, s, act_dtype, wb);
   if (rc != NSID_OK || act_out != NSID_ACT_ELU) return rc;
@@ -1296,7 +1312,7 @@ extern "C" int nsid_linear_bwd_data_bn(const void* dout, int ldd, const void* w,
 // Backward-data of a conv whose OUTPUT gradient still has to go through the BatchNorm(+activation) backward of that conv's own
 // BatchNorm: din = addend + dr w with dr = BN-backward(dy, r) evaluated on the operand load (no bn_bwd_apply pass), dr written once as
 // a side output for the weight gradient. coef4[4][groups*Nout] = {sc, sh, P, Q} from nsid_bn_bwd_finalize_fused. The optional bn_*
-// arguments are nsid_linear_bwd_data_bn's (column sums for the NEXT BatchNorm backward). Returns 1 (nothing launched) when the shape is
+// arguments are nsid_linear_bwd_data_bn's (column sums for the NEXT BatchNorm backward). Returns NSID_DECLINED (nothing launched) when the shape is
 // outside the fused form: bf16 storage and weights, M % 128 == 0, Nout % 64 == 0, K a multiple of the tile width, ldd == groups*Nout.
 extern "C" int nsid_linear_bwd_data_bnapply(const void* dy, const void* r, const float* coef4, int act, void* dr, const void* w,
                                             int w_dtype, const void* addend, int ldadd, void* din, int ldi, int M, int Nout, int K,
@@ -1307,7 +1323,7 @@ extern "C" int nsid_linear_bwd_data_bnapply(const void* dy, const void* r, const
   // only column tile 0 writes dr while every column tile of the row panel reads dy and r, unordered: an aliased call would race
   NSID_REQUIRE(dr != dy && dr != r);
   NSID_REQUIRE(act == NSID_ACT_NONE || act == NSID_ACT_RELU || act == NSID_ACT_LEAKY);
-  if (act_dtype != NSID_BF16 || w_dtype != NSID_BF16 || (groups * Nout) % 8 != 0) return 1;
+  if (act_dtype != NSID_BF16 || w_dtype != NSID_BF16 || (groups * Nout) % 8 != 0) return NSID_DECLINED;
   if (bn_r != nullptr) {
     NSID_REQUIRE(bn_scale && bn_shift && bn_mean && bn_invstd && bn_partial && ldi == groups * K && (groups * K) % 8 == 0 &&
                  nsid_aligned16(bn_r));
@@ -1355,14 +1371,14 @@ static int linear_bwd_data_impl(const void* dout, int ldd, const void* w, int w_
                                             bn_mean, bn_invstd, p.bn_slope, bn_partial, p.bn_plane, p.bn_ld, abn ? abn->r : nullptr,
                                             abn ? abn->coef4 : nullptr, (long)groups * Nout, abn ? act_slope(abn->act) : 1.f,
                                             abn ? abn->dr : nullptr, (long)groups * Nout, s);
-    if (rcw != 1) { nsid_count(abn ? NSID_C_ws_bwd_bnapply : NSID_C_ws_bwd_data); return rcw; }
+    if (rcw != NSID_DECLINED) { nsid_count(abn ? NSID_C_ws_bwd_bnapply : NSID_C_ws_bwd_data); return rcw; }
   }
   if (abn != nullptr) {
     // every column tile re-evaluates the BatchNorm backward of its row panel: as few column tiles as the tile family offers
     narrow = K <= 64;
     p.abn_r = abn->r; p.abn_coef = abn->coef4; p.abn_plane = (long)groups * Nout; p.abn_slope = act_slope(abn->act);
     p.abn_dr = abn->dr; p.abn_lddr = (long)groups * Nout;
-    if (K % (narrow ? 64 : 128) != 0 || M % 128 != 0 || Nout % 64 != 0) return 1;
+    if (K % (narrow ? 64 : 128) != 0 || M % 128 != 0 || Nout % 64 != 0) return NSID_DECLINED;
   }
   // A handful of tiles with a long reduction (the projector head: M = batch rows, Nout = 4096 -> K = 1024 was 32 workgroups of 64 stages
   // each, 61 us on the turnaround between forward and backward where nothing else runs): split the reduction over up to 256
@@ -1408,7 +1424,7 @@ extern "C" int nsid_linear_bwd_weight(const void* dout, int ldd, const void* x, 
       (in_scale == nullptr || (nsid_aligned16(in_scale) && nsid_aligned16(in_shift)))) {
     const int rc = nsid_wgrad2_launch(dout, ldd, x, ldx, dw, M, Nout, K, groups, in_scale, in_shift, act_slope(act_in),
                                       static_cast<hipStream_t>(stream));
-    if (rc != 1) return rc;                  // 1 = shape outside the fast form's preconditions
+    if (rc != NSID_DECLINED) return rc;      // declined: the shape is outside the fast form's preconditions
   }
   // 128x64 tiles (a quarter fewer operand bytes per flop than 64x64) where they still give >= 256 workgroups of >= 1024
   // rows, i.e. without more splits = atomic bytes than the square tiles need

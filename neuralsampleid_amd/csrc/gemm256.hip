@@ -24,7 +24,7 @@
 //   * PERSISTENT: a workgroup walks the tiles b, b + grid, ...; when the main loop of a tile ends the ring is free, so the first two
 //     stages of the NEXT tile are issued BEFORE the epilogue (which only touches its own LDS region): the 2-4 us a tile waits for
 //     its first operands from HBM and the 1-2 us of epilogue overlap instead of adding up. vmcnt is counted across the boundary.
-// Preconditions (host-checked, nsid_gemm256_fwd_launch returns 1 otherwise): M % 256 == 0, N % 256 == 0, K % 128 == 0.
+// Preconditions (host-checked, nsid_gemm256_fwd_launch returns NSID_DECLINED otherwise): M % 256 == 0, N % 256 == 0, K % 128 == 0.
 #include <cstdlib>
 #include "nsid_common.h"
 
@@ -332,14 +332,14 @@ __global__ __launch_bounds__(512, 2) void gemm256_fwd_kernel(const G256Args p) {
 
 }  // namespace
 
-// returns NSID_OK / NSID_ELAUNCH, or 1 when the shape is outside the kernel's preconditions (the caller then takes gemm.hip)
+// returns NSID_OK / NSID_ELAUNCH, or NSID_DECLINED when the shape is outside the kernel's preconditions (the caller then takes gemm.hip)
 __attribute__((visibility("hidden")))
 int nsid_gemm256_fwd_launch(const void* x, int ldx, const void* w, const float* bias, const void* addend, int ldadd, void* out,
                             int ldo, int M, int Nout, int K, bool relu_out, float* stat, long stat_plane, long stat_ld,
                             hipStream_t stream) {
-  if (M % 256 != 0 || Nout % 256 != 0 || K % 128 != 0 || ldx % 8 != 0 || ldo % 8 != 0 || (addend && ldadd % 8 != 0)) return 1;
-  if (!nsid_aligned16(x) || !nsid_aligned16(w) || !nsid_aligned16(out) || (addend && !nsid_aligned16(addend))) return 1;
-  if (bias && !nsid_aligned16(bias)) return 1;
+  if (M % 256 != 0 || Nout % 256 != 0 || K % 128 != 0 || ldx % 8 != 0 || ldo % 8 != 0 || (addend && ldadd % 8 != 0)) return NSID_DECLINED;
+  if (!nsid_aligned16(x) || !nsid_aligned16(w) || !nsid_aligned16(out) || (addend && !nsid_aligned16(addend))) return NSID_DECLINED;
+  if (bias && !nsid_aligned16(bias)) return NSID_DECLINED;
   G256Args p{};
   p.A = static_cast<const __bf16*>(x); p.lda = ldx;
   p.B = static_cast<const __bf16*>(w); p.ldb = K;
@@ -360,11 +360,12 @@ int nsid_gemm256_fwd_launch(const void* x, int ldx, const void* w, const float* 
   const int ntiles = (M / 256) * (Nout / 256);
   const int wgs = nsid_tune(NSID_T_g256_grid) > 0 ? (int)nsid_tune(NSID_T_g256_grid) : n_cu;
   const dim3 grid(ntiles < wgs ? ntiles : wgs);       // one workgroup per CU (155 KB of LDS), persistent over the tiles
-  if (addend && (stat || relu_out)) return 1;
-  if (stat && relu_out) return 1;
+  if (addend && (stat || relu_out)) return NSID_DECLINED;
+  if (stat && relu_out) return NSID_DECLINED;
   if (addend) NSID_LAUNCH(gemm256_fwd_kernel<G256_ADD>, grid, dim3(512), 0, stream, p);
   else if (stat) NSID_LAUNCH(gemm256_fwd_kernel<G256_STAT>, grid, dim3(512), 0, stream, p);
   else if (relu_out) NSID_LAUNCH(gemm256_fwd_kernel<G256_RELU>, grid, dim3(512), 0, stream, p);
   else NSID_LAUNCH(gemm256_fwd_kernel<G256_PLAIN>, grid, dim3(512), 0, stream, p);
+  nsid_took("gemm256_fwd_kernel");
   return nsid_launch_status();
 }

@@ -1214,7 +1214,7 @@ int launch_knn_sel(const void* r, int ldr, const float* scale, const float* shif
                    int dilation, int32_t* idx, hipStream_t s) {
   const size_t bytes = (size_t)2 * N * C * 2 + (size_t)N * sizeof(float) +
                        (size_t)KNN2_WAVES * 4 * (16 * TILES + 2 * KSEL_CH) * sizeof(unsigned long long);
-  if (bytes > NSID_LDS_MAX || N != 16 * TILES) return 1;
+  if (bytes > NSID_LDS_MAX || N != 16 * TILES) return NSID_DECLINED;
   NSID_LAUNCH_LDS((knn_sel_kernel<T, TILES>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
                   shift, N, C, k, dilation, idx);
   return nsid_launch_status();
@@ -1251,6 +1251,7 @@ int launch_knn2_nt(const void* r, int ldr, const float* scale, const float* shif
     if (scale == nullptr && nsid_tune(NSID_T_knn_raw16) != 0 && pair_min > 0 && B >= pair_min) {
       const size_t rbytes = (size_t)N * C * 2 + ((size_t)2 * N + 2 * 4 * 16 * KD) * sizeof(float);
       nsid_count(NSID_C_knn2_raw);
+      nsid_took("knn2_raw_kernel");
       const long wpe = nsid_tune(NSID_T_knn_raw_wpe);
 #define NSID_KNN_RAW_GO(W_)                                                                                                         \
       NSID_LAUNCH_LDS((knn2_raw_kernel<KD, NT, W_>), dim3(B), dim3(KNN2_THREADS), rbytes, s, static_cast<const __bf16*>(r), (long)ldr, N, \
@@ -1263,10 +1264,12 @@ int launch_knn2_nt(const void* r, int ldr, const float* scale, const float* shif
   }
   if (pair_min > 0 && B >= pair_min && 2 * bytes <= NSID_LDS_MAX) {
     nsid_count(NSID_C_knn2_pair);
+    nsid_took("knn2_pair_kernel");
     NSID_LAUNCH_LDS((knn2_pair_kernel<T, KD, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr,
                     scale, shift, N, C, k, dilation, idx);
     return nsid_launch_status();
   }
+  nsid_took("knn2_kernel");
   NSID_LAUNCH_LDS((knn2_kernel<T, KD, NT>), dim3(B), dim3(KNN2_THREADS), bytes, s, static_cast<const T*>(r), (long)ldr, scale,
                   shift, N, C, k, dilation, idx);
   return nsid_launch_status();
@@ -1299,6 +1302,7 @@ static int knn_graph_impl(const void* r, int ldr, const float* scale, const floa
     const size_t bytes = ((size_t)16 * (C + 4) + 3 * (size_t)N + (size_t)16 * (N + 4)) * sizeof(float);
     NSID_REQUIRE(bytes <= NSID_LDS_MAX && B <= 65535);
     nsid_count(NSID_C_knn_big);
+    nsid_took("knn_big_kernel");
     NSID_DISPATCH_DTYPE(dtype, T, {
       NSID_LAUNCH_LDS((knn_big_kernel<T>), dim3(N / 16, B), dim3(256), bytes, static_cast<hipStream_t>(stream),
                       static_cast<const T*>(r), (long)ldr, scale, shift, N, C, k, dilation, idx);
@@ -1312,17 +1316,18 @@ static int knn_graph_impl(const void* r, int ldr, const float* scale, const floa
   // rank counting where k*d is most of the row (64 and 32 nodes)
   if (use_fast && pow2 && kd > 8 && kd <= 64 && N >= nsid_tune(NSID_T_knn_sel_min_n)) {
     hipStream_t s = static_cast<hipStream_t>(stream);
-    int rc = 1;
+    int rc = NSID_DECLINED;
 #define NSID_KSEL_CASE(TL)                                                                                            \
     case 16 * TL:                                                                                                    \
       NSID_DISPATCH_DTYPE(dtype, T, rc = launch_knn_sel<T, TL>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s)); \
       break;
     switch (N) { NSID_KSEL_CASE(16) NSID_KSEL_CASE(8) NSID_KSEL_CASE(4) NSID_KSEL_CASE(2) default: break; }
 #undef NSID_KSEL_CASE
-    if (rc != 1) { nsid_count(NSID_C_knn_sel); return rc; }
+    if (rc != NSID_DECLINED) { nsid_count(NSID_C_knn_sel); nsid_took("knn_sel_kernel"); return rc; }
   }
   if (use_fast && pow2 && kd > 8 && N <= 128) {              // small graphs: rank counting
     nsid_count(NSID_C_knn_rank);
+    nsid_took("knn_rank_kernel");
     hipStream_t s = static_cast<hipStream_t>(stream);
     NSID_DISPATCH_DTYPE(dtype, T, return launch_knn_rank<T>(r, ldr, scale, shift, B, N, C, k, dilation, idx, s));
   }
@@ -1341,6 +1346,7 @@ static int knn_graph_impl(const void* r, int ldr, const float* scale, const floa
   const size_t bytes = lds_bytes(waves);
   NSID_REQUIRE(bytes <= NSID_LDS_MAX);
   nsid_count(NSID_C_knn_strips);
+  nsid_took("knn_kernel");
   NSID_DISPATCH_DTYPE(dtype, T, {
     NSID_LAUNCH_LDS((knn_kernel<T>), dim3(B), dim3(64 * waves), bytes, static_cast<hipStream_t>(stream),
                     static_cast<const T*>(r), (long)ldr, scale, shift, N, C, k, dilation, idx);

@@ -714,17 +714,18 @@ extern "C" int nsid_mr_aggregate_fwd(const void* r, int ldr, const float* scale,
   return nsid_launch_status();
 }
 
-// the degree-ranked gather where it applies (bf16 storage, the encoder's clip size, k >= tuning key mr_bwd_sorted_min_k); 1 otherwise
+// the degree-ranked gather where it applies (bf16 storage, the encoder's clip size, k >= tuning key mr_bwd_sorted_min_k); NSID_DECLINED otherwise
 static int mrs_launch(const void* du, const int32_t* idx, const uint8_t* argmax, int B, int N, int C, int k, void* dy, int dtype,
                       const MrsBn* bn, void* stream) {
   const long sorted_min = nsid_tune(NSID_T_mr_bwd_sorted_min_k);
   const size_t sbytes = (size_t)3 * 16384 + ((size_t)5 * N + 1 + (size_t)N * k) * sizeof(int) + 16;
   if (!(dtype == NSID_BF16 && sorted_min > 0 && k >= sorted_min && (long)N * C == 16384 && (C & (C - 1)) == 0 && C >= 64 && C <= 512 &&
         sbytes <= NSID_LDS_MAX))
-    return 1;
+    return NSID_DECLINED;
   int cshift = 0;
   while ((1 << cshift) < C) ++cshift;
   nsid_count(NSID_C_mr_bwd_sorted);
+  nsid_took(bn != nullptr ? "mr_bwd_sorted_kernel +bn_sums" : "mr_bwd_sorted_kernel");
   if (bn != nullptr)
     NSID_LAUNCH_LDS(mr_bwd_sorted_kernel<true>, dim3(B), dim3(MRS_THREADS), sbytes, static_cast<hipStream_t>(stream),
                     static_cast<const __bf16*>(du), idx, argmax, N, C, cshift, k, static_cast<__bf16*>(dy), *bn);
@@ -838,6 +839,7 @@ extern "C" int nsid_mr_aggregate_bwd(const void* du, const int32_t* idx, const u
   if (bytes > NSID_LDS_MAX && dtype == NSID_F32) {
     const long total = (long)B * N * C;
     const int grid = (int)std::min<long>((total + 255) / 256, 4096);
+    nsid_took("mr_bwd_scatter_kernel");
     NSID_LAUNCH(mr_bwd_own_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(du), total,
                 static_cast<float*>(dy));
     NSID_LAUNCH(mr_bwd_scatter_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<const float*>(du), idx,
@@ -847,6 +849,7 @@ extern "C" int nsid_mr_aggregate_bwd(const void* du, const int32_t* idx, const u
   if (bytes > NSID_LDS_MAX) {                // bf16 storage, a clip beyond the LDS: the edge list alone stays there
     const size_t gbytes = ((size_t)2 * N + 1 + (size_t)N * k) * sizeof(int);
     NSID_REQUIRE(gbytes <= NSID_LDS_MAX && C % 8 == 0 && N < (1 << 23));
+    nsid_took("mr_bwd_big_kernel");
     NSID_LAUNCH_LDS((mr_bwd_big_kernel<__bf16>), dim3(B), dim3(MRB_THREADS), gbytes, static_cast<hipStream_t>(stream),
                     static_cast<const __bf16*>(du), idx, argmax, N, C, k, static_cast<__bf16*>(dy));
     return nsid_launch_status();
@@ -854,8 +857,9 @@ extern "C" int nsid_mr_aggregate_bwd(const void* du, const int32_t* idx, const u
   NSID_REQUIRE(C % 4 == 0 && ((size_t)N * C * (esz + 1)) % 4 == 0);
   {
     const int rc = mrs_launch(du, idx, argmax, B, N, C, k, dy, dtype, nullptr, stream);
-    if (rc != 1) return rc;
+    if (rc != NSID_DECLINED) return rc;
   }
+  nsid_took("mr_bwd_kernel");
   NSID_DISPATCH_DTYPE(dtype, T, {
     NSID_LAUNCH_LDS((mr_bwd_kernel<T>), dim3(B), dim3(MRB_THREADS), bytes, static_cast<hipStream_t>(stream),
                     static_cast<const T*>(du), idx, argmax, N, C, k, static_cast<T*>(dy));
@@ -864,7 +868,7 @@ extern "C" int nsid_mr_aggregate_bwd(const void* du, const int32_t* idx, const u
 }
 
 // nsid_mr_aggregate_bwd + the BatchNorm-backward column sums of the layer whose output the aggregation read (MrsBn above): one partial
-// row per clip. NSID_EINVAL outside the degree-ranked form (the caller then runs nsid_mr_aggregate_bwd and nsid_bn_bwd_reduce).
+// row per clip. NSID_DECLINED outside the degree-ranked form (the caller then runs nsid_mr_aggregate_bwd and nsid_bn_bwd_reduce).
 extern "C" int nsid_mr_aggregate_bwd_bn(const void* du, const int32_t* idx, const uint8_t* argmax, int B, int N, int C, int k, void* dy,
                                         const void* bn_r, int bn_ldr, const float* bn_scale, const float* bn_shift, const float* bn_mean,
                                         const float* bn_invstd, int bn_act, float* partial, int dtype, void* stream) {
@@ -875,6 +879,5 @@ extern "C" int nsid_mr_aggregate_bwd_bn(const void* du, const int32_t* idx, cons
   NSID_REQUIRE(bn_act == NSID_ACT_NONE || bn_act == NSID_ACT_RELU || bn_act == NSID_ACT_LEAKY);
   const float slope = bn_act == NSID_ACT_RELU ? 0.f : (bn_act == NSID_ACT_LEAKY ? 0.2f : 1.f);
   MrsBn bn{static_cast<const __bf16*>(bn_r), bn_ldr, bn_scale, bn_shift, bn_mean, bn_invstd, slope, partial, (long)B * C};
-  const int rc = mrs_launch(du, idx, argmax, B, N, C, k, dy, dtype, &bn, stream);
-  return rc == 1 ? NSID_EINVAL : rc;
+  return mrs_launch(du, idx, argmax, B, N, C, k, dy, dtype, &bn, stream);
 }

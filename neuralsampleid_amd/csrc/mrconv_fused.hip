@@ -314,9 +314,9 @@ __global__ __launch_bounds__(64 * NW) void mrconv_pg_kernel(const MrcPgArgs p) {
 template <int C, int NW>
 int mrc_launch_pg(const MrcArgs& p, int B, hipStream_t s) {
   constexpr int N = 16384 / C, K = C / 2, CS = C / 4;
-  if (p.k > 8) return 1;
+  if (p.k > 8) return NSID_DECLINED;
   const size_t bytes = (size_t)K * (K * 2 + 32) + (size_t)N * (CS * 2 + 16) + (size_t)N * p.k * 4;
-  if (bytes > NSID_LDS_MAX) return 1;
+  if (bytes > NSID_LDS_MAX) return NSID_DECLINED;
   const long target = std::max<long>(1, nsid_tune(NSID_T_mrconv_pg_wgs) / 4);       // clip ranges
   const int per = (int)std::max<long>(1, (B + target - 1) / target);
   const int ranges = (B + per - 1) / per;
@@ -329,7 +329,7 @@ template <int C, int NW, bool DIRECT>
 int mrc_launch_v(const MrcArgs& p, int B, hipStream_t s) {
   constexpr int N = 16384 / C, K = C / 2;
   const size_t bytes = (size_t)N * (C * 2 + 16) + (size_t)K * (K * 2 + 32) + (DIRECT ? 0 : (size_t)N * (K * 2 + 16)) + (size_t)N * p.k * 4;
-  if (bytes > NSID_LDS_MAX) return 1;
+  if (bytes > NSID_LDS_MAX) return NSID_DECLINED;
   NSID_LAUNCH_LDS((mrconv_fused_kernel<C, NW, DIRECT>), dim3(B), dim3(64 * NW), bytes, s, p);
   return nsid_launch_status();
 }
@@ -341,7 +341,7 @@ int mrc_launch(const MrcArgs& p, int B, hipStream_t s) {
   // (a slice row is only 32 bytes there): the wide stage only, unless bit 3 asks for every width
   if ((v & 4) && (C == 256 || (v & 8))) {
     const int rc = mrc_launch_pg<C, 8>(p, B, s);
-    if (rc != 1) return rc;
+    if (rc != NSID_DECLINED) return rc;
   }
   switch (v & 3) {
     case 0: return mrc_launch_v<C, 4, false>(p, B, s);
@@ -354,11 +354,11 @@ int mrc_launch(const MrcArgs& p, int B, hipStream_t s) {
 }  // namespace
 // y: (B*N, C) bf16 contiguous node-major features (BatchNorm already folded: plain values); idx: (B, N, k) clip-local int32;
 // w: (2C, C/2) bf16 = the grouped conv's weight with its BatchNorm folded in, bias: (2C) fp32; out: (B*N, 2C) bf16.
-// Returns 1 (nothing launched) outside the fused form: C in {64, 128, 256} with N * C = 16 384, k <= 64.
+// Returns NSID_DECLINED (nothing launched) outside the fused form: C in {64, 128, 256} with N * C = 16 384, k <= 64.
 extern "C" int nsid_mrconv_fused_fwd(const void* y, const int32_t* idx, int B, int N, int C, int k, const void* w, const float* bias,
                                      void* out, void* stream) {
   NSID_REQUIRE(y && idx && w && bias && out && B > 0 && k > 0);
-  if (!(C == 64 || C == 128 || C == 256) || (long)N * C != 16384 || k > 64) return 1;
+  if (!(C == 64 || C == 128 || C == 256) || (long)N * C != 16384 || k > 64) return NSID_DECLINED;
   NSID_REQUIRE(nsid_aligned16(y) && nsid_aligned16(w) && nsid_aligned16(bias) && nsid_aligned16(out));
   MrcArgs p{static_cast<const __bf16*>(y), idx, static_cast<const __bf16*>(w), bias, static_cast<__bf16*>(out), k};
   hipStream_t s = static_cast<hipStream_t>(stream);

@@ -304,6 +304,13 @@ enum NsidCounterKey {
 extern long g_nsid_counter[NSID_C_COUNT];
 static inline void nsid_count(NsidCounterKey k) { ++g_nsid_counter[k]; }
 
+// ---- which kernel an entry took (include/nsid.h nsid_debug_last_kernel): a launcher that chooses between kernels stores the profile
+// family of its MAIN kernel where it decides, as a string literal: the kernel's name with the template arguments that tell the families
+// apart (the host's kernel table joins on it with the profiler's rows). Not part of NSID_LAUNCH: an entry's helper kernels (zero fill,
+// ELU pass) must not overwrite it.
+inline const char* g_nsid_took = "";
+static inline void nsid_took(const char* family) { g_nsid_took = family; }
+
 // ---- packs of songs (include/nsid.h nsid_logmel_fft_ragged / nsid_cqt_ragged): the device table has NSID_PACK_COLS longs per song,
 // {first sample in the pack, samples, first output column, work items (runs / tiles) of the songs before it}. The song of work item
 // b is the last one whose prefix is <= b (prefix[0] = 0, strictly increasing: every song has at least one item). The result
@@ -374,16 +381,17 @@ int nsid_wgrad3_grouped_launch(const WgGroupArgs& ga, int grid, bool affine, hip
 // problems in one launch)
 int nsid_wgrad4_grouped_launch(const WgGroupArgs& ga, int grid, hipStream_t stream);
 
-// wgrad.hip: 128x128-tile form of the bf16 weight-gradient GEMM; returns 1 when the shape is outside its preconditions
+// wgrad.hip: 128x128-tile form of the bf16 weight-gradient GEMM; NSID_DECLINED when the shape is outside its preconditions
 int nsid_wgrad2_launch(const void* dout, int ldd, const void* x, int ldx, float* dw, int M, int Nout, int K, int groups,
                        const float* in_scale, const float* in_shift, float slope, hipStream_t stream);
 
-// gemm256.hip: forward GEMM on 256x256 tiles with LDS-DMA staging (bf16 activations and weights, one group); returns 1 when the
+// gemm256.hip: forward GEMM on 256x256 tiles with LDS-DMA staging (bf16 activations and weights, one group); NSID_DECLINED when the
 // shape is outside its preconditions
 int nsid_gemm256_fwd_launch(const void* x, int ldx, const void* w, const float* bias, const void* addend, int ldadd, void* out,
                             int ldo, int M, int Nout, int K, bool relu_out, float* stat, long stat_plane, long stat_ld,
                             hipStream_t stream);
-// wsgemm.hip: weight-stationary streaming forward GEMM of the small-K training layers; returns 1 outside its shapes
+// wsgemm.hip: weight-stationary streaming forward GEMM of the small-K training layers (the table NSID_WS_LAYERS there), and its backward-data;
+// NSID_DECLINED outside their shapes
 int nsid_ws_fwd_launch(const void* x, int ldx, const void* w, const float* bias, void* out, int ldo, int M, int Nout, int K,
                        int groups, const float* in_scale, const float* in_shift, float in_slope, float* stat, long stat_plane,
                        long stat_ld, hipStream_t stream);
@@ -392,7 +400,7 @@ int nsid_ws_bwd_data_launch(const void* dout, int ldd, const void* w, const void
                             const float* bn_mean, const float* bn_invstd, float bn_slope, float* bn_partial, long bn_plane, long bn_ld,
                             const void* abn_r, const float* abn_coef, long abn_plane, float abn_slope, void* abn_dr, long abn_lddr,
                             hipStream_t stream);
-// ffn256_fused.hip: eval-mode FFN of the C = 256 stage in one launch; returns 1 outside C = 256, H = 1024, M % 256 == 0
+// ffn256_fused.hip: eval-mode FFN of the C = 256 stage in one launch; NSID_DECLINED outside C = 256, H = 1024, M % 256 == 0
 int nsid_ffn256_fused_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int M, int C,
                              int H, hipStream_t stream);
 // search.hip: the database split of nsid_flat_l2_topk's first phase, and its workspace for k entries per (row, split)

@@ -61,6 +61,7 @@ extern "C" int nsid_debug_counters_reset(void) {
 }
 extern "C" int nsid_debug_counter_count(void) { return NSID_C_COUNT; }
 extern "C" const char* nsid_debug_counter_key(int i) { return (i >= 0 && i < NSID_C_COUNT) ? kCounterNames[i] : nullptr; }
+extern "C" const char* nsid_debug_last_kernel(void) { return g_nsid_took; }
 
 extern "C" int nsid_tuning_count(void) { return NSID_T_COUNT; }
 extern "C" const char* nsid_tuning_key(int i) { return (i >= 0 && i < NSID_T_COUNT) ? kTable[i].name : nullptr; }

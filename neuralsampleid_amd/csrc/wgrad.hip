@@ -207,11 +207,11 @@ int nsid_wgrad3_grouped_launch(const WgGroupArgs& ga, int grid, bool affine, hip
   return nsid_launch_status();
 }
 
-// returns NSID_OK when launched, 1 when the shape is outside this kernel's preconditions (the caller then runs the
+// returns NSID_OK when launched, NSID_DECLINED when the shape is outside this kernel's preconditions (the caller then runs the
 // first form), or an error code
 int nsid_wgrad2_launch(const void* dout, int ldd, const void* x, int ldx, float* dw, int M, int Nout, int K, int groups,
                        const float* in_scale, const float* in_shift, float slope, hipStream_t stream) {
-  if (ldd % 8 != 0 || ldx % 8 != 0) return 1;
+  if (ldd % 8 != 0 || ldx % 8 != 0) return NSID_DECLINED;
   const long w3_wgs = nsid_tune(NSID_T_w3_wgs);
   const long w3_min_tiles = nsid_tune(NSID_T_w3_min_tiles);
   const long tiles3 = (long)(Nout / W3_T) * (K / W3_T) * groups;
@@ -232,10 +232,11 @@ int nsid_wgrad2_launch(const void* dout, int ldd, const void* x, int ldx, float*
       p.b_scale = in_scale; p.b_shift = in_shift; p.b_slope = slope; p.b_aff_goff = K;
       dim3 grid(M / rc3, (Nout / W3_T) * (K / W3_T), groups);
       nsid_count(NSID_C_wgrad3);
+      nsid_took("wgrad3_kernel");
       if (in_scale != nullptr) NSID_LAUNCH((wgrad3_kernel<true>), grid, dim3(W3_THREADS), 0, stream, p);
       else NSID_LAUNCH((wgrad3_kernel<false>), grid, dim3(W3_THREADS), 0, stream, p);
       return nsid_launch_status();
     }
   }
-  return 1;
+  return NSID_DECLINED;
 }

@@ -463,6 +463,7 @@ int ws_bwd_launch_t(const WsBwdArgs& p, int gy, hipStream_t s) {
   if (p.abn_r != nullptr) WS_BWD_GO(true);
   else WS_BWD_GO(false);
 #undef WS_BWD_GO
+  nsid_took(p.abn_r != nullptr ? "ws_bwd_kernel +bn_apply_load" : "ws_bwd_kernel");
   return nsid_launch_status();
 }
 
@@ -473,7 +474,7 @@ int ws_launch(const WsArgs& p, int gy, bool aff, bool stat, hipStream_t s) {
     // several groups per workgroup hold GI * K / 16 operand fragments per lane; with the affine's constants beside them the K = 64
     // form spilled 18-24 registers. No layer of the encoder feeds a grouped conv through a pending BatchNorm (its input is
     // the aggregation's output): those launches keep gemm.hip's tile kernel.
-    if constexpr (GI > 1) return 1;
+    if constexpr (GI > 1) return NSID_DECLINED;
     else {
       if (stat) NSID_LAUNCH((ws_fwd_kernel<K, NOUT, GI, true, true>), grid, block, 0, s, p);
       else NSID_LAUNCH((ws_fwd_kernel<K, NOUT, GI, true, false>), grid, block, 0, s, p);
@@ -482,20 +483,42 @@ int ws_launch(const WsArgs& p, int gy, bool aff, bool stat, hipStream_t s) {
     if (stat) NSID_LAUNCH((ws_fwd_kernel<K, NOUT, GI, false, true>), grid, block, 0, s, p);
     else NSID_LAUNCH((ws_fwd_kernel<K, NOUT, GI, false, false>), grid, block, 0, s, p);
   }
+  nsid_took("ws_fwd_kernel");
   return nsid_launch_status();
 }
 
 }  // namespace
 
-// returns NSID_OK / NSID_ELAUNCH, or 1 when the shape is outside the weight-stationary forms (the caller then takes gemm.hip)
+// The layers whose whole weight matrix stays in LDS: X(Cin, Cout, groups, groups per workgroup). The forward launcher reads a row as
+// (K = Cin, Nout = Cout), the backward-data launcher as (Nout = Cout, K = Cin): one list for both and for nsid_ws_layer.
+#define NSID_WS_LAYERS(X)                                                                       \
+  X(64, 64, 1, 1)        /* Grapher fc1, C = 64 */                                              \
+  X(32, 32, 4, 4)        /* grouped conv, C = 64 */                                             \
+  X(128, 64, 1, 1)       /* Grapher fc2, C = 64 */                                              \
+  X(64, 256, 1, 1)       /* FFN fc1, C = 64 */                                                  \
+  X(256, 64, 1, 1)       /* FFN fc2, C = 64 */                                                  \
+  X(128, 128, 1, 1)      /* Grapher fc1, C = 128 */                                             \
+  X(64, 64, 4, 4)        /* grouped conv, C = 128 */                                            \
+  X(256, 128, 1, 1)      /* Grapher fc2, C = 128 (64 KB of weights: one workgroup per CU) */    \
+  X(128, 128, 4, 1)      /* grouped conv, C = 256 (one group per workgroup: grid.y = 4) */
+
+extern "C" int nsid_ws_layer(int cin, int cout, int groups) {
+#define WS_CASE(CIN_, COUT_, G_, GI_) \
+  if (cin == CIN_ && cout == COUT_ && groups == G_) return 1;
+  NSID_WS_LAYERS(WS_CASE)
+#undef WS_CASE
+  return 0;
+}
+
+// returns NSID_OK / NSID_ELAUNCH, or NSID_DECLINED when the shape is outside the weight-stationary forms (the caller then takes gemm.hip)
 __attribute__((visibility("hidden")))
 int nsid_ws_fwd_launch(const void* x, int ldx, const void* w, const float* bias, void* out, int ldo, int M, int Nout, int K,
                        int groups, const float* in_scale, const float* in_shift, float in_slope, float* stat, long stat_plane,
                        long stat_ld, hipStream_t stream) {
-  if (M % 128 != 0 || ldx % 8 != 0 || ldo % 8 != 0 || ldx < groups * K || ldo < groups * Nout) return 1;
-  if (!nsid_aligned16(x) || !nsid_aligned16(w) || !nsid_aligned16(out)) return 1;
-  if ((in_scale != nullptr) != (in_shift != nullptr)) return 1;
-  if (in_scale && (!nsid_aligned16(in_scale) || !nsid_aligned16(in_shift))) return 1;
+  if (M % 128 != 0 || ldx % 8 != 0 || ldo % 8 != 0 || ldx < groups * K || ldo < groups * Nout) return NSID_DECLINED;
+  if (!nsid_aligned16(x) || !nsid_aligned16(w) || !nsid_aligned16(out)) return NSID_DECLINED;
+  if ((in_scale != nullptr) != (in_shift != nullptr)) return NSID_DECLINED;
+  if (in_scale && (!nsid_aligned16(in_scale) || !nsid_aligned16(in_shift))) return NSID_DECLINED;
   WsArgs p{};
   p.x = static_cast<const __bf16*>(x); p.ldx = ldx;
   p.w = static_cast<const __bf16*>(w);
@@ -505,23 +528,15 @@ int nsid_ws_fwd_launch(const void* x, int ldx, const void* w, const float* bias,
   p.stat = stat; p.stat_plane = stat_plane; p.stat_ld = stat_ld;
   p.M = M;
   const bool aff = in_scale != nullptr, st = stat != nullptr;
-  if (!aff && in_slope != 1.f) return 1;            // an activation without an affine: gemm.hip's ReLU-on-load form
-#define WS_CASE(K_, N_, G_, GI_)                                                   \
-  if (K == K_ && Nout == N_ && groups == G_) return ws_launch<K_, N_, GI_>(p, G_ / GI_, aff, st, stream)
-  WS_CASE(64, 64, 1, 1);          // Grapher fc1, C = 64
-  WS_CASE(32, 32, 4, 4);          // grouped conv, C = 64
-  WS_CASE(128, 64, 1, 1);         // Grapher fc2, C = 64
-  WS_CASE(64, 256, 1, 1);         // FFN fc1, C = 64
-  WS_CASE(256, 64, 1, 1);         // FFN fc2, C = 64
-  WS_CASE(128, 128, 1, 1);        // Grapher fc1, C = 128
-  WS_CASE(64, 64, 4, 4);          // grouped conv, C = 128
-  WS_CASE(256, 128, 1, 1);        // Grapher fc2, C = 128 (64 KB of weights: one workgroup per CU)
-  WS_CASE(128, 128, 4, 1);        // grouped conv, C = 256 (one group per workgroup: grid.y = 4)
+  if (!aff && in_slope != 1.f) return NSID_DECLINED;            // an activation without an affine: gemm.hip's ReLU-on-load form
+#define WS_CASE(CIN_, COUT_, G_, GI_)                                              \
+  if (K == CIN_ && Nout == COUT_ && groups == G_) return ws_launch<CIN_, COUT_, GI_>(p, G_ / GI_, aff, st, stream);
+  NSID_WS_LAYERS(WS_CASE)
 #undef WS_CASE
-  return 1;
+  return NSID_DECLINED;
 }
 
-// backward-data: returns NSID_OK / NSID_ELAUNCH, or 1 outside the weight-stationary forms
+// backward-data: returns NSID_OK / NSID_ELAUNCH, or NSID_DECLINED outside the weight-stationary forms
 __attribute__((visibility("hidden")))
 int nsid_ws_bwd_data_launch(const void* dout, int ldd, const void* w, const void* addend, int ldadd, void* din, int ldi, int M, int Nout,
                             int K, int groups, const void* bn_r, long bn_ldr, const float* bn_scale, const float* bn_shift,
@@ -529,11 +544,11 @@ int nsid_ws_bwd_data_launch(const void* dout, int ldd, const void* w, const void
                             const void* abn_r, const float* abn_coef, long abn_plane, float abn_slope, void* abn_dr, long abn_lddr,
                             hipStream_t stream) {
   if (abn_r && (!abn_coef || !abn_dr || ldd != groups * Nout || abn_lddr % 8 != 0 || !nsid_aligned16(abn_r) || !nsid_aligned16(abn_dr) ||
-                !nsid_aligned16(abn_coef) || abn_plane % 4 != 0)) return 1;
-  if (M % 128 != 0 || ldd % 8 != 0 || ldi % 8 != 0 || ldd < groups * Nout || ldi < groups * K) return 1;
-  if (!nsid_aligned16(dout) || !nsid_aligned16(w) || !nsid_aligned16(din)) return 1;
-  if (addend && (ldadd % 8 != 0 || ldadd < groups * K || !nsid_aligned16(addend))) return 1;
-  if (bn_r && (bn_ldr % 8 != 0 || !nsid_aligned16(bn_r) || !bn_scale || !bn_shift || !bn_mean || !bn_invstd || !bn_partial)) return 1;
+                !nsid_aligned16(abn_coef) || abn_plane % 4 != 0)) return NSID_DECLINED;
+  if (M % 128 != 0 || ldd % 8 != 0 || ldi % 8 != 0 || ldd < groups * Nout || ldi < groups * K) return NSID_DECLINED;
+  if (!nsid_aligned16(dout) || !nsid_aligned16(w) || !nsid_aligned16(din)) return NSID_DECLINED;
+  if (addend && (ldadd % 8 != 0 || ldadd < groups * K || !nsid_aligned16(addend))) return NSID_DECLINED;
+  if (bn_r && (bn_ldr % 8 != 0 || !nsid_aligned16(bn_r) || !bn_scale || !bn_shift || !bn_mean || !bn_invstd || !bn_partial)) return NSID_DECLINED;
   WsBwdArgs p{};
   p.dy = static_cast<const __bf16*>(dout); p.ldd = ldd;
   p.w = static_cast<const __bf16*>(w);
@@ -545,17 +560,9 @@ int nsid_ws_bwd_data_launch(const void* dout, int ldd, const void* w, const void
   p.abn_r = static_cast<const __bf16*>(abn_r); p.abn_coef = abn_coef; p.abn_plane = abn_plane; p.abn_slope = abn_slope;
   p.abn_dr = static_cast<__bf16*>(abn_dr); p.abn_lddr = abn_lddr;
   p.M = M;
-#define WS_CASE(N_, K_, G_, GI_)                                                   \
-  if (Nout == N_ && K == K_ && groups == G_) return ws_bwd_launch_t<N_, K_, GI_>(p, G_ / GI_, stream)
-  WS_CASE(64, 64, 1, 1);          // Grapher fc1, C = 64
-  WS_CASE(32, 32, 4, 4);          // grouped conv, C = 64
-  WS_CASE(64, 128, 1, 1);         // Grapher fc2, C = 64
-  WS_CASE(256, 64, 1, 1);         // FFN fc1, C = 64
-  WS_CASE(64, 256, 1, 1);         // FFN fc2, C = 64
-  WS_CASE(128, 128, 1, 1);        // Grapher fc1, C = 128
-  WS_CASE(64, 64, 4, 4);          // grouped conv, C = 128
-  WS_CASE(128, 256, 1, 1);        // Grapher fc2, C = 128
-  WS_CASE(128, 128, 4, 1);        // grouped conv, C = 256
+#define WS_CASE(CIN_, COUT_, G_, GI_)                                              \
+  if (Nout == COUT_ && K == CIN_ && groups == G_) return ws_bwd_launch_t<COUT_, CIN_, GI_>(p, G_ / GI_, stream);
+  NSID_WS_LAYERS(WS_CASE)
 #undef WS_CASE
-  return 1;
+  return NSID_DECLINED;
 }

@@ -447,7 +447,7 @@ def grapher_backward(dx1: Tensor, P, S, G) -> Tensor:
     pre = "graph_conv.gconv.nn."
     # fc2 (+BN), input = relu(BN(r2))
     # dv is dL/d(relu(BN(r2))): the GEMM that writes it also emits that BatchNorm's backward column sums; where the weight-stationary
-    # form serves the shape (ops.WS_BWD_SHAPES) it evaluates fc2's own BatchNorm backward on its operand load too (no apply pass)
+    # form serves the layer (nsid_ws_layer: the table in csrc/wsgemm.hip) it evaluates fc2's own BatchNorm backward on its operand load too (no apply pass)
     dr3, dv, part2 = ops.bn_backward_linear_bwd_data(dx1, r3, a3, ACT_NONE, G["fc2.1.weight"], G["fc2.1.bias"], _link_partial(S),
                                                      ops.w2d(P["fc2.0.weight"]), M, C, 2 * C, 1, bn=(r2, a2, ACT_RELU),
                                                      site=ops.SITE_FC2, inplace=False)

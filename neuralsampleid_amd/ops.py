@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from ._lib import DEFINES as _H        # the integer #defines of include/nsid.h: every kernel constant below is read from it
-from ._lib import call, get_tuning, launch_counters, lib, reset_tuning, set_tuning  # noqa: F401  (tuning, counters: re-exported)
+from ._lib import _ERR, call, get_tuning, launch_counters, lib, reset_tuning, set_tuning  # noqa: F401  (tuning, counters: re-exported)
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_ELU = _H["NSID_ACT_NONE"], _H["NSID_ACT_RELU"], _H["NSID_ACT_LEAKY"], _H["NSID_ACT_ELU"]
 ROW_TILE = _H["NSID_ROW_TILE"]
@@ -19,7 +19,8 @@ BN_EPS = 1e-5
 
 class KernelProfile:
     """Opt-in per-launch timing of the GEMM family with HIP events recorded on the launch stream (bench.py roofline).
-    Keys follow the kernel template instantiation that the C side dispatches to (csrc/gemm.hip)."""
+    Keys follow the kernel template instantiation that the C side dispatches to: where an entry chooses between kernels the library
+    itself names the one it took (include/nsid.h nsid_debug_last_kernel), nothing here restates a launch heuristic."""
 
     def __init__(self):
         self.records = []          # (kernel, flops, algorithmic bytes, start event, end event, shape)
@@ -86,19 +87,29 @@ PROFILE: Optional[KernelProfile] = None
 
 
 def _timed(name, flops, nbytes, fn, shape=()):
-    """name: a string, or a callable evaluated AFTER the launch (a launcher that picks its kernel in C reports it then)"""
+    """name None: the entry picks its kernel in C, and the library says AFTER the launch which one it took (profiling only: an
+    unprofiled step makes no extra call). fn returning False launched nothing: no record is kept (_try_fused)."""
     if PROFILE is None:
         return fn()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    fn()
+    ran = fn()
     e1.record()
-    PROFILE.records.append((name() if callable(name) else name, flops, nbytes, e0, e1, shape))
+    if ran is not False:
+        PROFILE.records.append((lib.nsid_debug_last_kernel().decode() if name is None else name, flops, nbytes, e0, e1, shape))
+    return ran
 
 
-def _cnt(key: str) -> int:
-    """a launch counter of the library (profiling only: which kernel a launcher that decides in C has just taken)"""
-    return int(lib.nsid_debug_counter(key.encode())) if PROFILE is not None else 0
+def _try_fused(name, flops, nbytes, entry, args, shape=()) -> bool:
+    """Time a library entry that may decline (include/nsid.h NSID_DECLINED). True: its fused form ran and is in the profile. False: it
+    launched and wrote nothing, the profile has no record of it, and the caller runs the unfused sequence. Any other code raises, as
+    call() does."""
+    def launch():
+        rc = getattr(lib, entry)(*args)
+        if rc not in (_H["NSID_OK"], _H["NSID_DECLINED"]):
+            raise RuntimeError(f"{entry} failed: {_ERR.get(rc, rc)}")
+        return rc == _H["NSID_OK"]
+    return _timed(name, flops, nbytes, launch, shape)
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -291,32 +302,22 @@ def linear_fwd(x, w, bias, M, Nout, K, groups=1, in_scale=None, in_shift=None, a
         if ksplit > 1:
             fill_zero(out)
     stat = torch.empty((2, row_tiles(M), groups * Nout), device=x.device, dtype=torch.float32) if want_stat else None
-    half = dt == BF16 or lib.nsid_get_gemm_precision() == GEMM_BF16
-    narrow = (Nout <= 64 or (Nout <= 128 and K <= 256 and in_scale is None)) if half else Nout <= 64
-    if half and row_tiles(M) * ((Nout + 127) // 128) * groups < 128:
-        narrow = True
     esz = x.element_size()
     wop, wdt = _weight(w, dt, K)
-    name_ = "gemm_kernel<128,%d,true,true>" % (64 if narrow else 128)
-    n256 = lib.nsid_gemm_g256_launches() if PROFILE is not None else 0
-    nws = _cnt("ws_fwd")
-    # csrc/gemm.hip decides between the kernel families; the launch counters say which one ran
-    name = lambda: ("ws_fwd_kernel" if _cnt("ws_fwd") > nws else
-                    ("gemm256_fwd_kernel" if lib.nsid_gemm_g256_launches() > n256 else name_))
     if in_scale is None and act_in != ACT_NONE:
-        # activation on load without an affine: only ReLU on bf16 operands, bf16 weights and whole tiles (csrc/gemm.hip ARELU)
-        bn_ = 64 if narrow else 128
-        bm_ = 128
-        if not (act_in == ACT_RELU and dt == BF16 and wdt == BF16 and M % bm_ == 0 and Nout % bn_ == 0 and K % 64 == 0
+        # activation on load without an affine: only ReLU on bf16 operands, bf16 weights and whole tiles (csrc/gemm.hip ARELU). The tile
+        # width is the library's choice: this check covers the narrowest tile, and the library answers NSID_EINVAL for a wider one
+        # that the shape does not fill.
+        if not (act_in == ACT_RELU and dt == BF16 and wdt == BF16 and M % 128 == 0 and Nout % 64 == 0 and K % 64 == 0
                 and ksplit == 1):
             raise ValueError("activation-on-load without an affine needs ReLU, bf16 storage, bf16 weights and whole tiles")
     if addend is not None:
-        _timed(name, 2.0 * M * Nout * K * groups,
+        _timed(None, 2.0 * M * Nout * K * groups,
                groups * (esz * M * K + float(wop.element_size()) * Nout * K + 2 * esz * M * Nout), lambda: call(
             "nsid_linear_fwd_res", _p(x), ldx, _p(wop), wdt, _p(bias), _p(addend), addend.shape[-1], _p(out),
             out.shape[-1], M, Nout, K, groups, _p(in_scale), _p(in_shift), act_in, dt, _stream()), (M, Nout, K, groups))
         return out, None
-    _timed(name, 2.0 * M * Nout * K * groups,
+    _timed(None, 2.0 * M * Nout * K * groups,
            groups * (esz * M * K + float(wop.element_size()) * Nout * K + esz * M * Nout), lambda: call(
         "nsid_linear_fwd", _p(x), ldx, _p(wop), wdt, _p(bias), _p(out), out.shape[-1], M, Nout, K, groups, _p(in_scale),
         _p(in_shift), act_in, act_out, _p(stat), ksplit, dt, _stream()), (M, Nout, K, groups))
@@ -336,18 +337,9 @@ def ffn_fused_fwd(x, w1f, b1f, w2f, b2f, M, C, H):
     if d1 != BF16 or d2 != BF16:
         return None
     out = torch.empty_like(x)
-    rc = [0]
-
-    def launch():
-        rc[0] = lib.nsid_ffn_fused_fwd(_p(x), _p(w1), _p(b1f), _p(w2), _p(b2f), _p(out), M, C, H, _stream())
-    _timed("ffn_fused_kernel", 4.0 * M * C * H, 2.0 * x.element_size() * M * C + 4.0 * C * H, launch, (M, C, H, 1))
-    if rc[0] == 1:
-        if PROFILE is not None:
-            PROFILE.records.pop()
-        return None
-    if rc[0] != 0:
-        raise RuntimeError(f"nsid_ffn_fused_fwd failed: {rc[0]}")
-    return out
+    ran = _try_fused("ffn_fused_kernel", 4.0 * M * C * H, 2.0 * x.element_size() * M * C + 4.0 * C * H, "nsid_ffn_fused_fwd",
+                     (_p(x), _p(w1), _p(b1f), _p(w2), _p(b2f), _p(out), M, C, H, _stream()), (M, C, H, 1))
+    return out if ran else None
 
 
 FUSE_EVAL_MRCONV = True       # eval-mode max-relative aggregation + grouped conv as one launch (csrc/mrconv_fused.hip)
@@ -364,19 +356,10 @@ def mrconv_fused_fwd(y, idx, B, N, C, wf, bf):
         return None
     k = idx.shape[-1]
     out = torch.empty((B * N, 2 * C), device=y.device, dtype=y.dtype)
-    rc = [0]
-
-    def launch():
-        rc[0] = lib.nsid_mrconv_fused_fwd(_p(y), _p(idx), B, N, C, k, _p(w), _p(bf), _p(out), _stream())
-    _timed("mrconv_fused_kernel", 2.0 * B * N * (C // 2) * (C // 2) * 4, float(B) * N * (3 * C * y.element_size() + k * 4), launch,
-           (B * N, C // 2, C // 2, 4))
-    if rc[0] == 1:
-        if PROFILE is not None:
-            PROFILE.records.pop()
-        return None
-    if rc[0] != 0:
-        raise RuntimeError(f"nsid_mrconv_fused_fwd failed: {rc[0]}")
-    return out
+    ran = _try_fused("mrconv_fused_kernel", 2.0 * B * N * (C // 2) * (C // 2) * 4, float(B) * N * (3 * C * y.element_size() + k * 4),
+                     "nsid_mrconv_fused_fwd", (_p(y), _p(idx), B, N, C, k, _p(w), _p(bf), _p(out), _stream()),
+                     (B * N, C // 2, C // 2, 4))
+    return out if ran else None
 
 
 FUSE_BN_BWD_REDUCE = True     # backward-data GEMMs emit the next BatchNorm-backward's column sums (bf16 storage only)
@@ -389,13 +372,6 @@ def linear_bwd_data(dout, w, M, Nout, K, groups=1, addend=None, out=None, bn=Non
     dt = _act(dout, addend, out)
     if out is None:
         out = torch.empty((M, groups * K), device=dout.device, dtype=dout.dtype)
-    half = dt == BF16 or lib.nsid_get_gemm_precision() == GEMM_BF16
-    narrow = (K <= 64 or (K <= 128 and Nout <= 256)) if half else K <= 64
-    if half and row_tiles(M) * ((K + 127) // 128) * groups < 128:
-        narrow = True
-    name_ = "gemm_kernel<128,%d,true,false>" % (64 if narrow else 128)
-    nws = _cnt("ws_bwd_data")
-    name = lambda: "ws_bwd_kernel" if _cnt("ws_bwd_data") > nws else name_
     esz = dout.element_size()
     wop, wdt = _weight(w, dt, K)
     want_pair = bn is not None            # bn=False: "return a pair, nothing to fuse"
@@ -409,13 +385,13 @@ def linear_bwd_data(dout, w, M, Nout, K, groups=1, addend=None, out=None, bn=Non
         r, aff, act = bn
         _act(r, out)
         partial = torch.empty((2, row_tiles(M), groups * K), device=dout.device, dtype=torch.float32)
-        _timed(name, 2.0 * M * Nout * K * groups, nbytes, lambda: call(
+        _timed(None, 2.0 * M * Nout * K * groups, nbytes, lambda: call(
             "nsid_linear_bwd_data_bn", _p(dout), dout.shape[-1], _p(wop), wdt, _p(addend),
             0 if addend is None else addend.shape[-1], _p(out), out.shape[-1], M, Nout, K, groups, dt, _p(r),
             _p(aff.scale), _p(aff.shift), _p(aff.mean), _p(aff.invstd), act, _p(partial), _stream()),
             (M, Nout, K, groups))
         return out, partial
-    _timed(name, 2.0 * M * Nout * K * groups, nbytes, lambda: call(
+    _timed(None, 2.0 * M * Nout * K * groups, nbytes, lambda: call(
         "nsid_linear_bwd_data", _p(dout), dout.shape[-1], _p(wop), wdt, _p(addend),
         0 if addend is None else addend.shape[-1], _p(out), out.shape[-1], M, Nout, K, groups, dt, _stream()),
         (M, Nout, K, groups))
@@ -426,10 +402,8 @@ def linear_bwd_data(dout, w, M, Nout, K, groups=1, addend=None, out=None, bn=Non
 # (1: FFN hidden layer, 2: grouped conv, 4: Grapher fc1); True = all, False / 0 = none
 FUSE_BN_BWD_APPLY = 4        # measured in the two-stream step (round 3, one-box A/B x2): none 8.09 / 8.06 ms, FFN 8.35 / 8.35, grouped 8.14 / 8.13, fc1 8.08 / 8.09, all 8.33 / 8.32
 SITE_FFN, SITE_GCONV, SITE_FC1, SITE_FC2, SITE_FFN2 = 1, 2, 4, 8, 16
-# the backward-data shapes (Nout, K, groups) of csrc/wsgemm.hip: there the fused operand load costs one evaluation per ROW (a workgroup owns
-# all output columns), not one per column tile, so every call site takes it (tuning key ws_gemm bit 2); elsewhere FUSE_BN_BWD_APPLY decides
-WS_BWD_SHAPES = {(64, 64, 1), (32, 32, 4), (64, 128, 1), (256, 64, 1), (64, 256, 1), (128, 128, 1), (64, 64, 4), (128, 256, 1),
-                 (128, 128, 4)}
+# On the layers of csrc/wsgemm.hip (nsid_ws_layer) the fused operand load costs one evaluation per ROW (a workgroup owns all output
+# columns), not one per column tile, so every call site takes it (tuning key ws_gemm bit 2); elsewhere FUSE_BN_BWD_APPLY decides
 
 
 def bn_backward_linear_bwd_data(dy, r, aff: "BNAffine", act, dgamma, dbeta, partial, w, M, Nout, K, groups=1, addend=None,
@@ -448,7 +422,7 @@ def bn_backward_linear_bwd_data(dy, r, aff: "BNAffine", act, dgamma, dbeta, part
     s = _stream()
     wop, wdt = _weight(w, dt, K)
     enabled = FUSE_BN_BWD_APPLY is True or (FUSE_BN_BWD_APPLY and (int(FUSE_BN_BWD_APPLY) & site))
-    ws_form = (dt == BF16 and wdt == BF16 and M % 128 == 0 and (Nout, K, groups) in WS_BWD_SHAPES and (get_tuning("ws_gemm") & 4) != 0)
+    ws_form = (dt == BF16 and wdt == BF16 and M % 128 == 0 and lib.nsid_ws_layer(K, Nout, groups) == 1 and (get_tuning("ws_gemm") & 4) != 0)
     enabled = enabled or ws_form
     fusable = (enabled and dt == BF16 and wdt == BF16 and tuple(r.shape) == (M, groups * Nout) and
                tuple(dy.shape) == (M, groups * Nout) and M % 128 == 0 and
@@ -478,24 +452,15 @@ def bn_backward_linear_bwd_data(dy, r, aff: "BNAffine", act, dgamma, dbeta, part
     esz = dy.element_size()
     nbytes = groups * (3 * esz * M * Nout + float(wop.element_size()) * Nout * K
                        + esz * M * K * ((2 if addend is not None else 1) + (1 if fuse_sums else 0)))
-    rc = [0]
-
-    def launch():
-        rc[0] = lib.nsid_linear_bwd_data_bnapply(
-            _p(dy), _p(r), _p(coef[2]), act, _p(dr), _p(wop), wdt, _p(addend), 0 if addend is None else addend.shape[-1], _p(din),
-            din.shape[-1], M, Nout, K, groups, dt, _p(br), _p(baff.scale) if baff else None, _p(baff.shift) if baff else None,
-            _p(baff.mean) if baff else None, _p(baff.invstd) if baff else None, bact, _p(part_out), s)
-    _timed("ws_bwd_kernel +bn_apply_load" if ws_form else "gemm_kernel<128,%d,true,false> +bn_apply_load" % (64 if K <= 64 else 128),
-           2.0 * M * Nout * K * groups, nbytes, launch, (M, Nout, K, groups))
-    if rc[0] == 1:             # outside the fused form after all: apply with the coefficients already computed, then the plain GEMM
-        if PROFILE is not None:
-            PROFILE.records.pop()          # nothing was launched under that name
+    ran = _try_fused(None, 2.0 * M * Nout * K * groups, nbytes, "nsid_linear_bwd_data_bnapply", (
+        _p(dy), _p(r), _p(coef[2]), act, _p(dr), _p(wop), wdt, _p(addend), 0 if addend is None else addend.shape[-1], _p(din),
+        din.shape[-1], M, Nout, K, groups, dt, _p(br), _p(baff.scale) if baff else None, _p(baff.shift) if baff else None,
+        _p(baff.mean) if baff else None, _p(baff.invstd) if baff else None, bact, _p(part_out), s), (M, Nout, K, groups))
+    if not ran:                # outside the fused form after all: apply with the coefficients already computed, then the plain GEMM
         call("nsid_bn_bwd_apply", _p(dy), _p(r), M, C, _p(aff.scale), _p(aff.shift), _p(aff.mean), _p(aff.invstd), act, _p(coef),
              _p(dr), dt, s)
         res = linear_bwd_data(dr, w, M, Nout, K, groups, addend=addend, out=din, bn=bn if bn is not None else False)
         return (dr,) + res
-    if rc[0] != 0:
-        raise RuntimeError(f"nsid_linear_bwd_data_bnapply failed: {rc[0]}")
     return dr, din, part_out
 
 
@@ -503,18 +468,8 @@ def linear_bwd_weight(dout, x, dw, M, Nout, K, groups=1, in_scale=None, in_shift
     """dw += dout^T f(x)"""
     _chk(dw, in_scale, in_shift)
     dt = _act(dout, x)
-    t128 = ((Nout + 127) // 128) * ((K + 127) // 128) * groups
-    half = dt == BF16 or lib.nsid_get_gemm_precision() == GEMM_BF16
-    small = half or Nout <= 64 or K <= 64 or t128 * ((M + 511) // 512) < 256
-    name = "gemm_kernel<%s,false,false>" % ("64,64" if small else "128,128")
-    if dt == BF16 and Nout % 128 == 0 and K % 64 == 0 and M % 1024 == 0:          # csrc/gemm.hip: 128x64 tiles
-        tiles_r = (Nout // 128) * (K // 64) * groups
-        if tiles_r * min(M // 1024, max(1, 512 // tiles_r)) >= 256 and get_tuning("wgrad_rect") != 0:
-            name = "gemm_kernel<128,64,false,false>"
-    if dt == BF16 and Nout % 128 == 0 and K % 128 == 0 and M % 128 == 0 and (Nout // 128) * (K // 128) * groups >= 64:
-        name = "wgrad3_kernel"              # csrc/wgrad.hip: 128x128 tiles, 8 waves
     esz = x.element_size()
-    _timed(name, 2.0 * M * Nout * K * groups, groups * (esz * M * Nout + esz * M * K + 4.0 * Nout * K), lambda: call(
+    _timed(None, 2.0 * M * Nout * K * groups, groups * (esz * M * Nout + esz * M * K + 4.0 * Nout * K), lambda: call(
         "nsid_linear_bwd_weight", _p(dout), dout.shape[-1], _p(x), x.shape[-1], _p(dw), M, Nout, K, groups,
         _p(in_scale), _p(in_shift), act_in, dt, _stream()), (M, Nout, K, groups))
 
@@ -800,13 +755,9 @@ def knn_graph(r, B, N, C, k, dilation=1, aff: Optional[BNAffine] = None) -> torc
     if aff is not None and aff.identity:
         aff = None
     idx = torch.empty((B, N, k), device=r.device, dtype=torch.int32)
-    kd = k * dilation
-    sel = 8 < kd <= 64 and N >= get_tuning("knn_sel_min_n")      # csrc/knn.hip nsid_knn_graph
-    name_ = "knn2_kernel" if kd <= 8 else ("knn_sel_kernel" if sel else ("knn_rank_kernel" if N <= 128 else "knn_kernel"))
-    nraw = _cnt("knn2_raw")
-    name = lambda: "knn2_raw_kernel" if _cnt("knn2_raw") > nraw else name_      # (one bf16 MFMA pass: executed flops = algorithmic)
-    # read the features once, write int32 ids; 2*N^2*C flop on the fp32 matrix pipe
-    _timed(name, 2.0 * B * N * N * C, float(B) * (N * C * r.element_size() + N * k * 4), lambda: call(
+    # read the features once, write int32 ids; 2*N^2*C flop on the fp32 matrix pipe (knn2_raw_kernel: one bf16 MFMA pass,
+    # executed flops = algorithmic)
+    _timed(None, 2.0 * B * N * N * C, float(B) * (N * C * r.element_size() + N * k * 4), lambda: call(
         "nsid_knn_graph", _p(r), r.shape[-1], _p(aff.scale) if aff else None, _p(aff.shift) if aff else None,
         B, N, C, k, dilation, _p(idx), dt, _stream()), (B * N, N, C, 1))
     return idx
@@ -827,13 +778,6 @@ def mr_aggregate_fwd(r, idx, B, N, C, aff: Optional[BNAffine] = None, want_argma
     return u, amax
 
 
-def mr_bwd_sums_fused(du, N, C, k) -> bool:
-    """csrc/mr.hip mrs_launch: does the degree-ranked backward (the form that can also emit BatchNorm column sums) take this launch?"""
-    kmin = get_tuning("mr_bwd_sorted_min_k")
-    return bool(FUSE_MR_BWD_SUMS and du.dtype == torch.bfloat16 and kmin > 0 and k >= kmin and N * C == 16384 and C & (C - 1) == 0
-                and 64 <= C <= 512)
-
-
 FUSE_MR_BWD_SUMS = True      # the aggregation backward also emits the backward column sums of the BatchNorm in front of it (no reduce launch)
 
 
@@ -845,23 +789,17 @@ def mr_aggregate_bwd(du, idx, amax, B, N, C, bn=None):
     k = idx.shape[-1]
     dy = torch.empty((B * N, C), device=du.device, dtype=du.dtype)
     nbytes = float(B) * N * (3 * C * du.element_size() + k * 4 + C)
-    if bn is not None and mr_bwd_sums_fused(du, N, C, k):
+    if bn is not None and FUSE_MR_BWD_SUMS and dt == BF16:
+        # whether the degree-ranked kernel serves the shape is csrc/mr.hip's rule (mrs_launch): a declined call launches nothing, then the
+        # plain launch below and a reduce by the caller
         r, aff, act = bn
         _chk(aff.scale, aff.shift, aff.mean, aff.invstd)
         partial = torch.empty((2, B, C), device=du.device, dtype=torch.float32)
-        rc = [0]
-
-        def launch():
-            rc[0] = lib.nsid_mr_aggregate_bwd_bn(_p(du), _p(idx), _p(amax), B, N, C, k, _p(dy), _p(r), r.shape[-1], _p(aff.scale),
-                                                 _p(aff.shift), _p(aff.mean), _p(aff.invstd), act, _p(partial), dt, _stream())
-        _timed("mr_bwd_sorted_kernel +bn_sums", 0.0, nbytes + float(B) * N * C * r.element_size(), launch, (B * N, C, 2 * C, 1))
-        if rc[0] == 0:
+        if _try_fused(None, 0.0, nbytes + float(B) * N * C * r.element_size(), "nsid_mr_aggregate_bwd_bn", (
+                _p(du), _p(idx), _p(amax), B, N, C, k, _p(dy), _p(r), r.shape[-1], _p(aff.scale), _p(aff.shift), _p(aff.mean),
+                _p(aff.invstd), act, _p(partial), dt, _stream()), (B * N, C, 2 * C, 1)):
             return dy, partial
-        # the C side declined (its own LDS / k bounds, which this predicate does not restate): the plain launch + a reduce by the caller
-        if PROFILE is not None:
-            PROFILE.records.pop()
-    c0 = _cnt("mr_bwd_sorted")
-    _timed(lambda: "mr_bwd_sorted_kernel" if _cnt("mr_bwd_sorted") > c0 else "mr_bwd_kernel", 0.0, nbytes, lambda: call(
+    _timed(None, 0.0, nbytes, lambda: call(
         "nsid_mr_aggregate_bwd", _p(du), _p(idx), _p(amax), B, N, C, k, _p(dy), dt, _stream()),
         (B * N, C, 2 * C, 1))
     return (dy, None) if bn is not None else dy

@@ -148,7 +148,7 @@ def test_defines_of_the_real_header(L):
     from neuralsampleid_amd import ops
     D = L.DEFINES
     assert "NSID_H" not in D and D["NSID_OK"] == 0 and D["NSID_EINVAL"] == -1 and D["NSID_ELAUNCH"] == -2
-    assert set(L._ERR) == {-1, -2}
+    assert D["NSID_DECLINED"] == 1 and set(L._ERR) == {-1, -2, 1}        # call() names a decline nobody expected, like an error
     assert (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_LEAKY, ops.ACT_ELU) == (0, 1, 2, 3) and ops.ROW_TILE == 128
     assert (ops.F32, ops.BF16, ops.GEMM_FP32, ops.GEMM_BF16) == (0, 1, 0, 1)
     # the limits the kernels are compiled with, at the values they had as literals on both sides

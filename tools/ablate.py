@@ -30,7 +30,7 @@ def main():
     if unknown:
         raise SystemExit(f"not exported by libnsid_hip.so: {unknown}")
     _lib.call = call
-    for n in skip:                       # entries that ops.py binds directly (they return 1 = "not this form" to ask for a fallback)
+    for n in skip:                       # entries that ops.py binds directly (they may answer NSID_DECLINED = "not this form" to ask for a fallback)
         setattr(_lib.lib, n, lambda *a: 0)
     sys.argv = [os.path.join(ROOT, "bench.py")] + sys.argv[cut + 1:]
     import bench

@@ -447,7 +447,7 @@ void ffn256_fused_kernel(const F256Args p) {
 
 }  // namespace
 
-// returns NSID_OK / NSID_ELAUNCH, or 1 (nothing launched) outside {C = 256 or 128, M % 256 == 0} / {C = 64, M % 512 == 0} with H = 4 C.
+// returns NSID_OK / NSID_ELAUNCH, or NSID_DECLINED (nothing launched) outside {C = 256 or 128, M % 256 == 0} / {C = 64, M % 512 == 0} with H = 4 C.
 // r2 != nullptr: the PRE form (x1 = x + wp r2 + bp in front of the FFN; r2: M x 512 bf16, wp: 256 x 512 bf16, bp: fp32[256]);
 // y != nullptr: the GR form (r2 evaluated from y (M x 256 bf16), idx (M x k, clip-local), wg (512 x 128 bf16), bg (fp32[512]); N nodes
 // per clip, 256 % N == 0) -- both C = 256 only
@@ -455,11 +455,11 @@ __attribute__((visibility("hidden")))
 int nsid_ffn256_fused_launch(const void* x, const void* w1, const float* b1, const void* w2, const float* b2, void* out, int M, int C,
                              int H, hipStream_t stream, const void* r2, const void* wp, const float* bp, const void* y,
                              const int32_t* idx, int k, int N, const void* wg, const float* bg) {
-  if (!(C == 256 || C == 128 || C == 64) || H != 4 * C || M <= 0) return 1;
+  if (!(C == 256 || C == 128 || C == 64) || H != 4 * C || M <= 0) return NSID_DECLINED;
   const int tr = C == 64 ? 512 : 256;         // rows per workgroup tile
-  if (M % tr != 0) return 1;
-  if ((r2 != nullptr || y != nullptr) && C != 256) return 1;
-  if (y != nullptr && (N <= 0 || 256 % N != 0 || k <= 0)) return 1;
+  if (M % tr != 0) return NSID_DECLINED;
+  if ((r2 != nullptr || y != nullptr) && C != 256) return NSID_DECLINED;
+  if (y != nullptr && (N <= 0 || 256 % N != 0 || k <= 0)) return NSID_DECLINED;
   F256Args p{static_cast<const __bf16*>(x), static_cast<const __bf16*>(w1), b1, static_cast<const __bf16*>(w2), b2,
              static_cast<__bf16*>(out), M, static_cast<const __bf16*>(r2), static_cast<const __bf16*>(wp), bp,
              static_cast<const __bf16*>(y), idx, static_cast<const __bf16*>(wg), bg, k, N};

@@ -1,7 +1,7 @@
 // NOT PART OF THE PRODUCT LIBRARY (round 5 experiment, measured slower inside the two-stream step: docs/experiments.md, "Round 5").
 // To time it again: copy to csrc/, add it to build.py SOURCES, declare nsid_wgs_launch + the tuning keys wgrad_stream / wgs_wgs /
 // wgs_min_rows / wgs_min_wgs / wgs_slots and the counter wgrad_stream in nsid_common.h, and call nsid_wgs_launch at the top of
-// nsid_linear_bwd_weight (rc == 1 falls through to the staged forms). tools/variants/wgrad_stream_test.py is its parity test (62 cases).
+// nsid_linear_bwd_weight (NSID_DECLINED falls through to the staged forms). tools/variants/wgrad_stream_test.py is its parity test (62 cases).
 //
 // Streaming weight gradient of the bf16 path (gfx950): dW[g][Nout][K] += dY[M][g*Nout ..]^T f(X[M][g*K ..]), fp32 accumulation.
 //
@@ -19,7 +19,7 @@
 //     of atomics;
 //   * a producer BatchNorm + activation of X is applied on the B FRAGMENT: after the transposing read a lane holds 8 rows of ONE
 //     channel, so scale / shift are per-lane scalars (packed fp32 math, one rounding to bf16 as the staged forms do).
-// Preconditions (host-checked; nsid_wgs_launch returns 1 otherwise): bf16 operands, Nout % 128 == 0, K % 128 == 0 (per group),
+// Preconditions (host-checked; nsid_wgs_launch returns NSID_DECLINED otherwise): bf16 operands, Nout % 128 == 0, K % 128 == 0 (per group),
 // M % (64 * splits) == 0, 16-byte aligned rows.
 #include <algorithm>
 #include <cstdlib>
@@ -193,16 +193,16 @@ __global__ __launch_bounds__(512, 2) void wgs_kernel(const WgsArgs p) {
 
 }  // namespace
 
-// returns 0 / NSID_ELAUNCH, or 1 when the shape is outside this form's preconditions (the caller falls back to gemm.hip / wgrad.hip)
+// returns NSID_OK / NSID_ELAUNCH, or NSID_DECLINED when the shape is outside this form's preconditions (the caller falls back to gemm.hip / wgrad.hip)
 int nsid_wgs_launch(const void* dout, int ldd, const void* x, int ldx, float* dw, int M, int Nout, int K, int groups,
                     const float* in_scale, const float* in_shift, float slope, hipStream_t stream) {
-  if (Nout % 128 != 0 || K % 128 != 0 || M % 64 != 0 || ldd % 8 != 0 || ldx % 8 != 0) return 1;
+  if (Nout % 128 != 0 || K % 128 != 0 || M % 64 != 0 || ldd % 8 != 0 || ldx % 8 != 0) return NSID_DECLINED;
   const long tiles = (long)(Nout / 128) * (K / 128) * groups;
   const long target = nsid_tune(NSID_T_wgs_wgs);
   const long min_rows = std::max<long>(64, nsid_tune(NSID_T_wgs_min_rows));
   long S = std::max<long>(1, target / tiles);
   while (S > 1 && (M % (64 * S) != 0 || M / S < min_rows)) --S;
-  if (tiles * S < nsid_tune(NSID_T_wgs_min_wgs)) return 1;
+  if (tiles * S < nsid_tune(NSID_T_wgs_min_wgs)) return NSID_DECLINED;
   WgsArgs p{};
   p.dy = static_cast<const __bf16*>(dout); p.ldd = ldd;
   p.x = static_cast<const __bf16*>(x); p.ldx = ldx;
