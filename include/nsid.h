@@ -762,6 +762,42 @@ int nsid_pair_sim(const float* q, int ldq, int nq, const float* x, int ldx, long
 int nsid_local_align(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len, int npairs,
                      int max_q_len, int max_x_len, float theta, float min_score, int top, const int64_t* row_off, float* row_h,
                      int* row_j, int* row_org, int* occ, float* occ_score, int* n_occ, void* stream);
+/* The same rule in strips, for a recording of any length (csrc/align.hip). The rule reads rows i - 1 and i - 2 only, so a walk that
+ * starts from two carried rows and leaves two carried rows is, chained, bit for bit the rule on the whole matrix.
+ * local_align_strip: pair p holds rows row_base[p] .. row_base[p] + q_len[p] - 1 (GLOBAL query rows; device int32, row_base >= 0 and
+ *   row_base + q_len <= 2^31 - 1) of the matrix in S_p = S + s_off[p] (q_len[p] x x_len[p], row stride s_ld[p]). The carry is three
+ *   arrays, carry_h (fp32 H), carry_i0 and carry_j0 (int32: a cell's origin as global query row and song row, -1 / -1 = none); pair p's
+ *   part starts at carry_off[p] (device int64), row "i - 1" in elements [0, x_len), row "i - 2" in [x_len, 2 x_len). fresh[p] != 0
+ *   (device int32): the carry is not read, rows -1 and -2 are "H = +0, no origin". The carry is read and written in place: after a strip
+ *   of n rows it holds the last two rows of (old row -2, old row -1, the strip's rows); n = 1 moves the old row -1 down; n = 0 leaves
+ *   the carry untouched and writes open_h only (0 for a fresh pair). Per strip row i, at row_off[p] + i (device int64): row_h, row_j,
+ *   and the origin of that cell unpacked and global, row_i0 and row_j0; a row without a passing cell gets 0, -1, -1, -1. open_h[p] = the
+ *   largest H in the two rows carried out (0: no path is open, a following strip may start fresh). Chaining strips of any lengths
+ *   (0, 1 and 2 included) over a pair gives for every global row exactly the rule's row result on the whole matrix, row 0 being the
+ *   first row of the first fresh strip.
+ *   The origin row in a cell: every step of a path advances j by at least 1 and i by at most 2, so a cell of row i has
+ *   i - i0 <= 2 (Lr - 1) <= 8190 < 2^15; the walk keeps m = i0 mod 2^15 beside j0 and i0 = i - ((i - m) mod 2^15).
+ *   max_q_len (rows of ONE strip) <= NSID_ALIGN_MAX_ROWS, max_x_len <= NSID_ALIGN_MAX_COLS. A pair whose device lengths exceed the host
+ *   maxima (or with a negative length or row_base) reads nothing, writes its min(q_len, max_q_len) rows as empty, leaves its carry and
+ *   gets open_h = -1. x_len == 0: empty rows, open_h = 0. No atomics; a pair's result depends on nothing but the pair and its carry.
+ * align_occurrences: the occurrences of a run of rows of any length (up to NSID_ALIGN_OCC_MAX_ROWS) from its row results, by the rule
+ *   above restated for unpacked origins: the rows with row_i0 >= 0 are grouped by (row_i0, row_j0); a group's representative is its row
+ *   of largest row_h, ties to the smallest i; those with row_h >= min_score are kept and ordered by score descending, then i0, then j0.
+ *   Run p is rows row_off[p] .. row_off[p] + n_rows[p] - 1 of the four arrays (device int64 / int32); its local row r is global row
+ *   first_row[p] + r (device int32 >= 0, first_row + n_rows <= 2^31 - 1). n_occ (it can exceed top), occ (npairs x top x 4: i0, i1 =
+ *   first_row + r, j0, j1 = row_j[r]) and occ_score as local_align writes them, unused slots -1 and score 0. A group's rows lie within
+ *   global rows [i0, i0 + 8190] (the bound above), so a row is compared with that window only. A run whose n_rows is negative or above
+ *   max_rows gets n_occ = -1. One launch, no atomics, no host sort; the output is a pure function of the rows.
+ * Both: a NaN theta / min_score, a length over the limits, top outside [1, 64], a null or misaligned pointer: NSID_EINVAL before any
+ * launch; npairs == 0 launches nothing. */
+#define NSID_ALIGN_OCC_MAX_ROWS 1048576 /* rows of one run at most (one bit per row in LDS) */
+int nsid_local_align_strip(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len,
+                           const int* row_base, const int* fresh, int npairs, int max_q_len, int max_x_len, float theta,
+                           const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0, const int64_t* row_off, float* row_h,
+                           int* row_j, int* row_i0, int* row_j0, float* open_h, void* stream);
+int nsid_align_occurrences(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0, const int64_t* row_off,
+                           const int* n_rows, const int* first_row, int npairs, int max_rows, float min_score, int top, int* occ,
+                           float* occ_score, int* n_occ, void* stream);
 
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed

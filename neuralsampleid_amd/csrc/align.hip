@@ -14,6 +14,9 @@
 // passes the threshold) is reduced per wave (DPP), left in LDS, and combined during the next row. After the walk the same workgroup
 // reads the row results back and forms the occurrences with the quadratic compares of csrc/vote.hip. No atomics; a pair's result
 // depends on nothing but the pair.
+//
+// local_align_strip / align_occurrences: the same walk from two carried rows to two carried rows, so that a recording of any length goes
+// through in strips, and the occurrences of a run of rows of any length from its row results (include/nsid.h, below nsid_local_align).
 #include "nsid_common.h"
 
 namespace {
@@ -346,6 +349,294 @@ int launch_align(size_t lds, hipStream_t st, int npairs, const float* S, const i
   return nsid_launch_status();
 }
 
+// ---- local_align_strip ------------------------------------------------------------------------------------------------------------
+// The walk of local_align_kernel from two carried rows to two carried rows (include/nsid.h nsid_local_align_strip): the carry load
+// stands where the zero fill stood, and after the walk the two LDS rows that are rows -1 and -2 at that point go back to the carry.
+// local_align_kernel itself is untouched. A cell keeps its origin as (i0 mod 2^15) << 16 | j0 (sign bit clear, -1 = none): every step
+// of a path advances j by at least 1 and i by at most 2, so i - i0 <= 2 (Lr - 1) <= 8190 < 2^15 and i0 = i - ((i - m) mod 2^15).
+constexpr int AL_I0_MOD = 1 << 15;
+constexpr int AL_SPAN = 2 * (AL_MAX_COLS - 1);    // i - i0 of a cell at the most
+static_assert(AL_SPAN < AL_I0_MOD && AL_MAX_COLS <= (1 << 16), "a cell's origin row is recovered from its low 15 bits");
+
+__device__ __forceinline__ int al_pack_org(int i0, int j0) { return (i0 < 0 || j0 < 0) ? -1 : (((i0 & (AL_I0_MOD - 1)) << 16) | j0); }
+// the origin row of a cell of global row i (org >= 0)
+__device__ __forceinline__ int al_org_row(int i, int org) { return i - ((i - (org >> 16)) & (AL_I0_MOD - 1)); }
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void local_align_strip_kernel(
+    const float* __restrict__ S, const int64_t* __restrict__ s_off, const int* __restrict__ s_ld, const int* __restrict__ q_len,
+    const int* __restrict__ x_len, const int* __restrict__ row_base, const int* __restrict__ fresh, int max_q, int max_x, int cols,
+    float theta, const int64_t* __restrict__ carry_off, float* carry_h, int* carry_i0, int* carry_j0,
+    const int64_t* __restrict__ row_off, float* __restrict__ row_h, int* __restrict__ row_j, int* __restrict__ row_i0,
+    int* __restrict__ row_j0, float* __restrict__ open_h) {
+  constexpr int NW = THREADS / NSID_WAVE;
+  extern __shared__ __attribute__((aligned(16))) char al_smem[];
+  __shared__ unsigned long long part[2][NW];
+  __shared__ float wmax[NW];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
+  const int Lq = q_len[p], Lr = x_len[p], base = row_base[p];
+  const int64_t ro = row_off[p];
+  // every return below is uniform over the workgroup and ahead of every barrier
+  const bool bad = Lq < 0 || Lr < 0 || Lq > max_q || Lr > max_x || base < 0 || (int64_t)base + Lq > 0x7fffffffLL;
+  if (bad || Lr == 0) {                       // the caller checks the lengths (this only keeps a bad pair in bounds); no column: no cell
+    const int n = bad ? min(max(Lq, 0), max_q) : Lq;
+    for (int i = tid; i < n; i += THREADS) {
+      row_h[ro + i] = 0.f;
+      row_j[ro + i] = -1;
+      row_i0[ro + i] = -1;
+      row_j0[ro + i] = -1;
+    }
+    if (tid == 0) open_h[p] = bad ? -1.f : 0.f;
+    return;
+  }
+  const float* Sp = S + s_off[p];
+  const size_t ld = (size_t)s_ld[p];
+  const int64_t co = carry_off[p];
+  const bool carried = fresh[p] == 0;
+
+  // LDS row 0 = row i, row 1 = row i - 2, row 2 = row i - 1; two cells in front of each stand for j - 1, j - 2 < 0
+  int2* cell = reinterpret_cast<int2*>(al_smem);
+  for (int t = tid; t < 3 * cols; t += THREADS) {
+    const int r = t / cols, j = t - r * cols - 2;
+    int2 v = int2{0, -1};                                                       // H = +0.0, no origin
+    if (carried && r > 0 && j >= 0 && j < Lr) {
+      const int64_t a = co + (r == 2 ? 0 : Lr) + j;
+      v = int2{__builtin_bit_cast(int, carry_h[a]), al_pack_org(carry_i0[a], carry_j0[a])};
+    }
+    cell[t] = v;
+  }
+  __syncthreads();
+
+  // as in local_align_kernel: between the barriers of rows `row` and `row + 1` the waves' keys of the row become its result
+  auto combine = [&](int row, const int2* buf) {
+    unsigned long long k = 0;
+#pragma unroll
+    for (int u = 0; u < NW; ++u) {
+      const unsigned long long v = part[row & 1][u];
+      k = v > k ? v : k;
+    }
+    const int j = k ? (int)(0xffffffffu - (unsigned)k) : -1;
+    const int org = buf[max(j, 0) + 2].y;
+    if (tid == 0) {
+      const bool has = k != 0 && org >= 0;
+      row_h[ro + row] = __builtin_bit_cast(float, (unsigned)(k >> 32));
+      row_j[ro + row] = j;
+      row_i0[ro + row] = has ? al_org_row(base + row, org) : -1;
+      row_j0[ro + row] = has ? (org & 0xffff) : -1;
+    }
+  };
+
+  int2* cur = cell;
+  int2* prev1 = cell + 2 * cols;
+  int2* prev2 = cell + cols;
+  for (int ib = 0; ib < Lq; ib += AL_RB) {
+    float sv[AL_RB][AL_CPT];
+#pragma unroll
+    for (int r = 0; r < AL_RB; ++r) {
+      const float* rp = Sp + (size_t)min(ib + r, Lq - 1) * ld;
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) sv[r][c] = rp[min(tid + c * THREADS, Lr - 1)];
+    }
+#pragma unroll
+    for (int r = 0; r < AL_RB; ++r) {
+      const int i = ib + r;
+      if (i >= Lq) break;              // uniform
+      if (i > 0) combine(i - 1, prev1);
+      const int own = ((base + i) & (AL_I0_MOD - 1)) << 16;                       // a path that starts in this row
+      unsigned long long key = 0;
+      int2 d11[AL_CPT], d12[AL_CPT], d21[AL_CPT];
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) {
+        const int jc = min(tid + c * THREADS, Lr - 1);
+        d11[c] = prev1[jc + 1];
+        d12[c] = prev1[jc];
+        d21[c] = prev2[jc + 1];
+      }
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) {
+        const int j = tid + c * THREADS;
+        const float e = sv[r][c] - theta;
+        float best = 0.f;
+        int from = -1;
+        const float h11 = __builtin_bit_cast(float, d11[c].x), h12 = __builtin_bit_cast(float, d12[c].x),
+                    h21 = __builtin_bit_cast(float, d21[c].x);
+        if (h11 > best) {
+          best = h11;
+          from = d11[c].y;
+        }
+        if (h12 > best) {
+          best = h12;
+          from = d12[c].y;
+        }
+        if (h21 > best) {
+          best = h21;
+          from = d21[c].y;
+        }
+        const float v = best + e;
+        const bool pos = v > 0.f;
+        if (j < Lr) cur[j + 2] = int2{pos ? __builtin_bit_cast(int, v) : 0, pos ? (from >= 0 ? from : (own | j)) : -1};
+        const unsigned long long k = (j < Lr && e > 0.f) ? al_key(v, j) : 0ull;
+        key = k > key ? k : key;
+      }
+      key = al_wave_key_max(key);
+      if (lane == 0) part[i & 1][w] = key;
+      int2* t = prev2;
+      prev2 = prev1;
+      prev1 = cur;
+      cur = t;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    }
+  }
+  if (Lq > 0) combine(Lq - 1, prev1);
+
+  // the carry out: prev1 / prev2 are rows base + Lq - 1 and base + Lq - 2 of the concatenation (with Lq == 1 the latter is the old row
+  // -1, with Lq == 0 nothing moved and nothing is stored); open_h = the largest H in them
+  float m = 0.f;
+  for (int j = tid; j < Lr; j += THREADS) {
+    const int2 c1 = prev1[j + 2], c2 = prev2[j + 2];
+    const float h1 = __builtin_bit_cast(float, c1.x), h2 = __builtin_bit_cast(float, c2.x);
+    m = fmaxf(m, fmaxf(h1, h2));
+    if (Lq > 0) {
+      carry_h[co + j] = h1;
+      carry_i0[co + j] = c1.y >= 0 ? al_org_row(base + Lq - 1, c1.y) : -1;
+      carry_j0[co + j] = c1.y >= 0 ? (c1.y & 0xffff) : -1;
+      carry_h[co + Lr + j] = h2;
+      carry_i0[co + Lr + j] = c2.y >= 0 ? al_org_row(base + Lq - 2, c2.y) : -1;
+      carry_j0[co + Lr + j] = c2.y >= 0 ? (c2.y & 0xffff) : -1;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, NSID_WAVE));
+  if (lane == 0) wmax[w] = m;
+  __syncthreads();
+  if (tid == 0) {
+    float v = 0.f;
+    for (int u = 0; u < NW; ++u) v = fmaxf(v, wmax[u]);
+    open_h[p] = v;
+  }
+}
+
+template <int THREADS>
+int launch_align_strip(hipStream_t st, int npairs, const float* S, const int64_t* s_off, const int* s_ld, const int* q_len,
+                       const int* x_len, const int* row_base, const int* fresh, int max_q, int max_x, float theta,
+                       const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0, const int64_t* row_off, float* row_h,
+                       int* row_j, int* row_i0, int* row_j0, float* open_h) {
+  const size_t lds = (3 * (size_t)(max_x + 2) * sizeof(int2) + 15) / 16 * 16;
+  NSID_LAUNCH_LDS((local_align_strip_kernel<THREADS>), dim3(npairs), dim3(THREADS), lds, st, S, s_off, s_ld, q_len, x_len, row_base,
+                  fresh, max_q, max_x, max_x + 2, theta, carry_off, carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0,
+                  open_h);
+  return nsid_launch_status();
+}
+
+// ---- align_occurrences ------------------------------------------------------------------------------------------------------------
+// One workgroup per run of rows. A group's rows lie within [i0, i0 + AL_SPAN], so a row is its group's representative when no row of
+// that window with the same origin beats it; the kept rows are one bit each in LDS (a wave's ballot per 64 rows), and a kept row's rank
+// is a walk over the set bits. The rows themselves are read from memory (they stay in the caches).
+constexpr int AL_OCC_THREADS = 1024;
+static_assert(NSID_ALIGN_OCC_MAX_ROWS / 8 + 4096 <= NSID_LDS_MAX, "one bit per row of the longest run in LDS");
+
+__global__ __launch_bounds__(AL_OCC_THREADS) void align_occurrences_kernel(
+    const float* __restrict__ row_h, const int* __restrict__ row_j, const int* __restrict__ row_i0, const int* __restrict__ row_j0,
+    const int64_t* __restrict__ row_off, const int* __restrict__ n_rows, const int* __restrict__ first_row, int max_rows,
+    float min_score, int top, int* __restrict__ occ, float* __restrict__ occ_score, int* __restrict__ n_occ) {
+  constexpr int NW = AL_OCC_THREADS / NSID_WAVE;
+  extern __shared__ __attribute__((aligned(16))) unsigned al_keep[];
+  __shared__ int o_occ[AL_MAX_TOP][4];
+  __shared__ float o_sc[AL_MAX_TOP];
+  __shared__ int wcnt[NW];
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
+  const int n = n_rows[p], first = first_row[p];
+  // every return below is uniform over the workgroup and ahead of every barrier
+  if (n < 0 || n > max_rows || first < 0 || (int64_t)first + n > 0x7fffffffLL) {
+    al_empty(p, top, -1, tid, occ, occ_score, n_occ);
+    return;
+  }
+  if (n == 0) {
+    al_empty(p, top, 0, tid, occ, occ_score, n_occ);
+    return;
+  }
+  const int64_t ro = row_off[p];
+  const float* rh = row_h + ro;
+  const int* rj = row_j + ro;
+  const int* ri = row_i0 + ro;
+  const int* rc = row_j0 + ro;
+  if (tid < AL_MAX_TOP) {
+    o_occ[tid][0] = o_occ[tid][1] = o_occ[tid][2] = o_occ[tid][3] = -1;
+    o_sc[tid] = 0.f;
+  }
+  const int nblk = (n + NSID_WAVE - 1) / NSID_WAVE;
+  int cnt = 0;
+  for (int b = w; b < nblk; b += NW) {
+    const int i = b * NSID_WAVE + lane;
+    bool rep = false;
+    if (i < n) {
+      const int gi = ri[i], gj = rc[i];
+      const float hi = rh[i];
+      rep = gi >= 0 && hi >= min_score;
+      const int64_t lo = max((int64_t)0, (int64_t)gi - first), last = min((int64_t)n - 1, (int64_t)gi + AL_SPAN - first);
+      for (int64_t a0 = lo; a0 <= last && rep; a0 += AL_CHUNK) {
+        bool hit = false;
+#pragma unroll
+        for (int u = 0; u < AL_CHUNK; ++u) {
+          const int64_t a = a0 + u, ac = min(a, last);
+          const float ha = rh[ac];
+          hit |= (a <= last) & (ri[ac] == gi) & (rc[ac] == gj) & ((ha > hi) | ((ha == hi) & (ac < i)));
+        }
+        rep = !hit;
+      }
+    }
+    const unsigned long long m = __ballot(rep);
+    if (lane == 0) {
+      al_keep[2 * b] = (unsigned)m;
+      al_keep[2 * b + 1] = (unsigned)(m >> 32);
+      cnt += __popcll(m);
+    }
+  }
+  if (lane == 0) wcnt[w] = cnt;
+  __syncthreads();
+  const int nwords = 2 * nblk;
+  for (int b = w; b < nblk; b += NW) {
+    const int i = b * NSID_WAVE + lane;
+    if (!((al_keep[i >> 5] >> (i & 31)) & 1u)) continue;       // bits past the run's end are 0; no barrier inside the loop
+    const int gi = ri[i], gj = rc[i];
+    const float hi = rh[i];
+    int rank = 0;
+    for (int wd = 0; wd < nwords && rank < top; ++wd) {
+      unsigned bits = al_keep[wd];
+      while (bits) {
+        const int a = wd * 32 + __builtin_ctz(bits);
+        bits &= bits - 1;
+        const float ha = rh[a];
+        const int ai = ri[a], aj = rc[a];
+        rank += ((ha > hi) | ((ha == hi) & ((ai < gi) | ((ai == gi) & (aj < gj))))) ? 1 : 0;
+      }
+    }
+    if (rank < top) {
+      o_occ[rank][0] = gi;
+      o_occ[rank][1] = first + i;
+      o_occ[rank][2] = gj;
+      o_occ[rank][3] = rj[i];
+      o_sc[rank] = hi;
+    }
+  }
+  __syncthreads();
+  if (tid < top) {
+    int* o = occ + ((size_t)p * top + tid) * 4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) o[u] = o_occ[tid][u];
+    occ_score[(size_t)p * top + tid] = o_sc[tid];
+  }
+  if (tid == 0) {
+    int k = 0;
+    for (int u = 0; u < NW; ++u) k += wcnt[u];
+    n_occ[p] = k;
+  }
+}
+
+static inline bool al_aligned(const void* p, unsigned n) { return (reinterpret_cast<uintptr_t>(p) & (n - 1)) == 0; }
+
 bool sim_d_ok(int d) { return (d % 16 == 0 && d >= 16 && d <= 256) || (d % 64 == 0 && d > 256 && d <= 2048); }
 
 }  // namespace
@@ -386,4 +677,54 @@ extern "C" int nsid_local_align(const float* S, const int64_t* s_off, const int*
                              row_j, row_org, occ, occ_score, n_occ);
   return launch_align<1024>(lds, st, npairs, S, s_off, s_ld, q_len, x_len, max_q_len, max_x_len, theta, min_score, top, row_off, row_h,
                             row_j, row_org, occ, occ_score, n_occ);
+}
+
+extern "C" int nsid_local_align_strip(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len,
+                                      const int* row_base, const int* fresh, int npairs, int max_q_len, int max_x_len, float theta,
+                                      const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0, const int64_t* row_off,
+                                      float* row_h, int* row_j, int* row_i0, int* row_j0, float* open_h, void* stream) {
+  NSID_REQUIRE(npairs >= 0 && max_q_len >= 0 && max_q_len <= AL_MAX_ROWS && max_x_len >= 0 && max_x_len <= AL_MAX_COLS &&
+               theta == theta);
+  if (npairs == 0) return NSID_OK;
+  NSID_REQUIRE(s_off && s_ld && q_len && x_len && row_base && fresh && carry_off && row_off && open_h);
+  NSID_REQUIRE(max_q_len == 0 || (row_h && row_j && row_i0 && row_j0));
+  NSID_REQUIRE(max_x_len == 0 || (carry_h && carry_i0 && carry_j0));
+  NSID_REQUIRE((max_q_len == 0 || max_x_len == 0) || S);
+  NSID_REQUIRE(al_aligned(s_off, 8) && al_aligned(carry_off, 8) && al_aligned(row_off, 8));
+  for (const void* q : {(const void*)S, (const void*)s_ld, (const void*)q_len, (const void*)x_len, (const void*)row_base,
+                        (const void*)fresh, (const void*)carry_h, (const void*)carry_i0, (const void*)carry_j0, (const void*)row_h,
+                        (const void*)row_j, (const void*)row_i0, (const void*)row_j0, (const void*)open_h})
+    NSID_REQUIRE(al_aligned(q, 4));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  nsid_count(NSID_C_local_align_strip);
+  // 256 threads own every column of a pair up to 1024; above that 1024 threads do (the results do not depend on it)
+  if (max_x_len <= 256 * AL_CPT) {
+    nsid_took("local_align_strip_kernel<256>");
+    return launch_align_strip<256>(st, npairs, S, s_off, s_ld, q_len, x_len, row_base, fresh, max_q_len, max_x_len, theta, carry_off,
+                                   carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
+  }
+  nsid_took("local_align_strip_kernel<1024>");
+  return launch_align_strip<1024>(st, npairs, S, s_off, s_ld, q_len, x_len, row_base, fresh, max_q_len, max_x_len, theta, carry_off,
+                                  carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
+}
+
+extern "C" int nsid_align_occurrences(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0,
+                                      const int64_t* row_off, const int* n_rows, const int* first_row, int npairs, int max_rows,
+                                      float min_score, int top, int* occ, float* occ_score, int* n_occ, void* stream) {
+  NSID_REQUIRE(npairs >= 0 && max_rows >= 0 && max_rows <= NSID_ALIGN_OCC_MAX_ROWS && top >= 1 && top <= AL_MAX_TOP &&
+               min_score == min_score);
+  if (npairs == 0) return NSID_OK;
+  NSID_REQUIRE(row_off && n_rows && first_row && occ && occ_score && n_occ);
+  NSID_REQUIRE(max_rows == 0 || (row_h && row_j && row_i0 && row_j0));
+  NSID_REQUIRE(al_aligned(row_off, 8));
+  for (const void* q : {(const void*)row_h, (const void*)row_j, (const void*)row_i0, (const void*)row_j0, (const void*)n_rows,
+                        (const void*)first_row, (const void*)occ, (const void*)occ_score, (const void*)n_occ})
+    NSID_REQUIRE(al_aligned(q, 4));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t lds = ((size_t)(max_rows + NSID_WAVE - 1) / NSID_WAVE * 8 + 15) / 16 * 16;
+  nsid_count(NSID_C_align_occurrences);
+  nsid_took("align_occurrences_kernel");
+  NSID_LAUNCH_LDS(align_occurrences_kernel, dim3(npairs), dim3(AL_OCC_THREADS), lds, st, row_h, row_j, row_i0, row_j0, row_off, n_rows,
+                  first_row, max_rows, min_score, top, occ, occ_score, n_occ);
+  return nsid_launch_status();
 }

@@ -28,8 +28,14 @@ the vote, after its rows took the k_probe slots), and links runs every song agai
     occs = idx.locate(fp=idx.fingerprints[lo:lo + n], leave_out="song a", threshold=0.6, min_score=2.0)
     res = idx.links(threshold=0.6, min_score=2.0)                    # res.occurrences[name], res.skipped
 
-Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs or queries past 4096 rows
-(refused, not split), gap steps other than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated
+A recording of any length (a mix, a broadcast): scan / scanner run the same alignment in windows, the last two rows of every open
+song carried from window to window, so an occurrence that crosses a window boundary is found once, in rows of the whole recording.
+
+    occs = idx.scan(wave=recording, threshold=0.6, min_score=2.0)
+    sc = idx.scanner(threshold=0.6, min_score=2.0); sc.push(fp_piece); ...; occs = sc.finish()
+
+Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs past 4096 rows, and queries
+past 4096 rows outside scan (refused, not split), gap steps other than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated
 on real audio, parsing sample100-ext's annotation files."""
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
@@ -625,6 +631,61 @@ class SampleIndex:
         order = self._best_songs(pv.codes.cpu().numpy().reshape(-1).tolist(), pv.totals.cpu().numpy().reshape(-1).tolist())
         return [self.names[c] for c in order[:n_songs]]
 
+    # ------------------------------------------------------------------------------------------------ scanning a long recording
+    def scanner(self, threshold: Optional[float] = None, min_score: float = 0.0, k_probe: int = 20, n_songs: int = 5, top: int = 16,
+                window_rows: Optional[int] = None, songs: Optional[Sequence[str]] = None, exclude: Optional[str] = None,
+                max_active: int = 64, row_hop_s=None, row_len_s=None) -> "Scanner":
+        """A Scanner over this index: a recording of any length, pushed in pieces of any sizes, is voted on and aligned in windows of
+        W = window_rows or VOTE_MAX_CAND // k_probe rows (at most min(VOTE_MAX_CAND // k_probe, ALIGN_MAX_ROWS)), aligned to the global
+        row index, so the result depends on the rows alone. The alignment is locate's rule, carried from window to window
+        (ops.local_align_strip): a path that crosses a window boundary is one occurrence, found once. See Scanner for the active-set
+        and run rules. songs=[names]: exactly these songs are aligned in every window and nothing is voted (the streaming form of
+        align). exclude: a song name that never votes. threshold has no default, as in align. Every refusal comes before any launch."""
+        if threshold is None:
+            raise ValueError("scanner: threshold has no default for fingerprint scores (the reference has no such number and none has "
+                             "been measured on real audio): pass one")
+        threshold, min_score = float(threshold), float(min_score)
+        if threshold != threshold or min_score != min_score:
+            raise ValueError("scanner: threshold or min_score is NaN")
+        n_songs, k, top, max_active = int(n_songs), int(k_probe), int(top), int(max_active)
+        if n_songs < 1 or max_active < 1:
+            raise ValueError(f"scanner: n_songs = {n_songs} and max_active = {max_active} must be at least 1")
+        if not 1 <= k <= ops.SEARCH_MAX_K:
+            raise ValueError(f"k_probe = {k} is outside [1, {ops.SEARCH_MAX_K}]")
+        if not 1 <= top <= ops.ALIGN_MAX_TOP:
+            raise ValueError(f"scanner: top = {top} is outside [1, {ops.ALIGN_MAX_TOP}]")
+        if songs is not None and exclude is not None:
+            raise ValueError("scanner: exclude applies to the vote; with songs= leave the song out")
+        cap = min(max(1, ops.VOTE_MAX_CAND // k), ops.ALIGN_MAX_ROWS)
+        W = cap if window_rows is None else int(window_rows)
+        if W < 1:
+            raise ValueError(f"scanner: window_rows = {W} must be at least 1")
+        fixed = None
+        if songs is not None:
+            if isinstance(songs, str):
+                raise TypeError("scanner: songs must be a sequence of names, not one string")
+            fixed = [self.code(s) for s in songs]
+            if len(set(fixed)) != len(fixed):
+                raise ValueError("scanner: a song is named twice")
+            for c in fixed:
+                self._scan_song_ok(c)
+        return Scanner(self, fixed, threshold, min_score, k, n_songs, top, min(W, cap), None if exclude is None else self.code(exclude),
+                       max_active, self._row_timing(row_hop_s, row_len_s))
+
+    def _scan_song_ok(self, c):
+        if self._song_rows[c][1] > ops.ALIGN_MAX_COLS:
+            raise ValueError(f"scanner: song {self.names[c]!r} has {self._song_rows[c][1]} rows, past the limit of {ops.ALIGN_MAX_COLS}; "
+                             "longer inputs are refused, not split")
+
+    @torch.no_grad()
+    def scan(self, specs=None, wave=None, fp=None, **kw) -> List["Occurrence"]:
+        """The occurrences of resident songs in a recording of any length: encodes as identify does (the whole recording first), then
+        scanner(**kw).push(rows) and finish()."""
+        sc = self.scanner(**kw)
+        fp, _ = self._query(specs, wave, fp, None, False)
+        sc.push(fp)
+        return sc.finish()
+
     # ------------------------------------------------------------------------------------------------ the catalogue against itself
     @torch.no_grad()
     def links(self, names: Optional[Sequence[str]] = None, k_probe: int = 20, n_songs: int = 5, threshold: Optional[float] = None,
@@ -742,6 +803,152 @@ class SampleIndex:
 class CatalogueLinks(NamedTuple):
     occurrences: dict                             # {song name: [Occurrence], as locate(fp=its rows, leave_out=name) returns them}
     skipped: List[str]                            # songs past ALIGN_MAX_ROWS / ALIGN_MAX_COLS rows: not queried, no candidates
+
+
+class Scanner:
+    """The state of one scan (SampleIndex.scanner). push(fp) takes (n, d) fp32 device rows, any n >= 0; finish() flushes the last,
+    partial window and returns the occurrences, sorted by (-score, song code, i0, j0), in global rows of the recording.
+
+    Per window t: one identify_pairs vote over the window (none with songs=). The active set is the songs active in window t - 1
+    whose open_h > 0 (a path is still open in their carried rows), by open_h descending, then code, followed by the vote's first n_songs
+    songs that are not among them, in the vote's order; what lies past max_active is closed and counted in stats["closed_at_cap"].
+    Then one pair_sim and one local_align_strip for all active songs; a song that was not active in t - 1 starts fresh. A song's
+    maximal stretch of consecutive active windows is a run; the rows of every run go through one align_occurrences call at finish().
+
+    trace: one dict per window, host values: start, rows, vote_codes, vote_totals, active (codes, in order), open_h (after the strip).
+    stats: windows, strips (pairs aligned), runs, rows, closed_at_cap. runs (after finish): per run a dict with song, code, first_row,
+    n_rows and the device row results row_h, row_j, row_i0, row_j0.
+    Not here: rerank cells, leave_out, songs of more than ALIGN_MAX_COLS rows, a streaming front end, hipGraph capture, several GPUs;
+    a run is at most ops.ALIGN_OCC_MAX_ROWS rows."""
+
+    def __init__(self, index, fixed, threshold, min_score, k, n_songs, top, W, exclude, max_active, timing):
+        self.index, self._fixed, self._theta, self._min_score = index, fixed, threshold, min_score
+        self._k, self._n_songs, self._top, self.window_rows, self._exclude, self._max_active = k, n_songs, top, W, exclude, max_active
+        self._timing = timing
+        self._pend = None                 # rows pushed and not yet in a window
+        self._next = 0                    # global index of the first pending row
+        self._active: List[int] = []      # window t - 1
+        self._open = {}                   # code -> open_h after window t - 1
+        self._slot = {}                   # code -> slot of the carry pool
+        self._free: List[int] = []
+        self._pool = None
+        self._run = {}                    # code -> the open run: [first_row, parts]; a part = (rows of a window, offset, n)
+        self._closed = []                 # (code, first_row, parts)
+        self._done = False
+        self.trace: List[dict] = []
+        self.stats = {"windows": 0, "strips": 0, "runs": 0, "rows": 0, "closed_at_cap": 0}
+        self.runs: List[dict] = []
+
+    def push(self, fp: torch.Tensor) -> None:
+        if self._done:
+            raise RuntimeError("Scanner.push: the scan is finished")
+        self.index._check_fp(fp, "Scanner.push")
+        if fp.shape[0] == 0:
+            return
+        self._pend = fp if self._pend is None else torch.cat([self._pend, fp])
+        W = self.window_rows
+        while self._pend.shape[0] >= W:
+            self._window(self._pend[:W])
+            self._pend = self._pend[W:]
+        if self._pend.shape[0] == 0:
+            self._pend = None
+        else:
+            self._pend = self._pend.clone()          # the caller's tensor is not kept
+
+    def _carry_pool(self):
+        if self._pool is None:
+            slots = max(self._max_active, len(self._fixed or ()))
+            self._pool, _ = ops.align_carry([ops.ALIGN_MAX_COLS] * slots, self.index.device)
+            self._free = list(range(slots - 1, -1, -1))
+        return self._pool
+
+    def _close(self, c):
+        first, parts = self._run.pop(c)
+        self._closed.append((c, first, parts))
+        self._free.append(self._slot.pop(c))
+        self._open.pop(c, None)
+
+    @torch.no_grad()
+    def _window(self, rows):
+        idx, start, n = self.index, self._next, int(rows.shape[0])
+        rows = rows.contiguous()
+        vote_codes, vote_totals = [], []
+        if self._fixed is not None:
+            want = list(self._fixed)
+        else:
+            pv = idx.identify_pairs(rows, [0], [n], k_probe=self._k, top=min(ops.VOTE_MAX_TOP, self._n_songs),
+                                    exclude=None if self._exclude is None else [idx.names[self._exclude]])
+            codes, totals = pv.codes.cpu().numpy()[0], pv.totals.cpu().numpy()[0]
+            m = int((codes >= 0).sum())
+            vote_codes, vote_totals = codes[:m].tolist(), totals[:m].tolist()
+            cont = sorted((c for c in self._active if self._open[c] > 0), key=lambda c: (-self._open[c], c))
+            want = cont + [c for c in vote_codes[: self._n_songs] if c not in cont]
+            self.stats["closed_at_cap"] += max(0, len(want) - self._max_active)
+            want = want[: self._max_active]
+            for c in want:
+                idx._scan_song_ok(c)
+        pool = self._carry_pool()
+        for c in [c for c in self._active if c not in want]:
+            self._close(c)
+        fresh = []
+        for c in want:
+            fresh.append(0 if c in self._run else 1)
+            if c not in self._run:
+                self._run[c] = [start, []]
+                self._slot[c] = self._free.pop()
+                self.stats["runs"] += 1
+        open_h = []
+        if want:
+            P = len(want)
+            x_start = np.asarray([idx._song_rows[c][0] for c in want], dtype=np.int64)
+            x_len = np.asarray([idx._song_rows[c][1] for c in want], dtype=np.int64)
+            q_len = np.full(P, n, dtype=np.int64)
+            S, s_off, s_ld = ops.pair_sim(rows, idx.fingerprints, np.zeros(P, np.int64), q_len, x_start, x_len)
+            carry_off = np.asarray([self._slot[c] for c in want], dtype=np.int64) * (2 * ops.ALIGN_MAX_COLS)
+            *res, row_off, oh = ops.local_align_strip(S, s_off, s_ld, q_len, x_len, self._theta, np.full(P, start, np.int64), fresh,
+                                                      pool, carry_off)
+            open_h = oh.cpu().numpy().astype(np.float64).tolist()
+            for p, c in enumerate(want):
+                self._run[c][1].append((res, int(row_off[p]), n))
+                self._open[c] = open_h[p]
+        self._active = want
+        self._next = start + n
+        self.trace.append({"start": start, "rows": n, "vote_codes": vote_codes, "vote_totals": vote_totals, "active": list(want),
+                           "open_h": open_h})
+        self.stats["windows"] += 1
+        self.stats["strips"] += len(want)
+        self.stats["rows"] += n
+
+    @torch.no_grad()
+    def finish(self) -> List["Occurrence"]:
+        if self._done:
+            raise RuntimeError("Scanner.finish: the scan is finished")
+        if self._pend is not None:
+            self._window(self._pend)
+            self._pend = None
+        for c in list(self._active):
+            self._close(c)
+        self._active, self._done = [], True
+        runs = [r for r in self._closed if r[2]]
+        out = []
+        if runs:
+            flat = [torch.cat([res[u][off:off + n] for _, _, parts in runs for res, off, n in parts]) for u in range(4)]
+            n_rows = np.asarray([sum(n for _, _, n in parts) for _, _, parts in runs], dtype=np.int64)
+            row_off = np.cumsum(n_rows) - n_rows
+            first = np.asarray([f for _, f, _ in runs], dtype=np.int64)
+            occ, sc, _ = ops.align_occurrences(*flat, row_off, n_rows, first, self._min_score, self._top)
+            occ, sc = occ.cpu().numpy(), sc.cpu().numpy()
+            for r, (c, f, _) in enumerate(runs):
+                lo, hi = int(row_off[r]), int(row_off[r] + n_rows[r])
+                self.runs.append({"song": self.index.names[c], "code": c, "first_row": int(f), "n_rows": int(n_rows[r]),
+                                  "row_h": flat[0][lo:hi], "row_j": flat[1][lo:hi], "row_i0": flat[2][lo:hi], "row_j0": flat[3][lo:hi]})
+                for (i0, i1, j0, j1), s in zip(occ[r].tolist(), sc[r].tolist()):
+                    if i0 < 0:
+                        break
+                    out.append((c, _occurrence(self.index.names[c], s, i0, i1, j0, j1, self._timing)))
+        self._closed = []
+        out.sort(key=lambda t: (-t[1].score, t[0], t[1].q_rows[0], t[1].r_rows[0]))
+        return [o for _, o in out]
 
 
 class Occurrence(NamedTuple):

@@ -2244,6 +2244,151 @@ def local_align(S, s_off, s_ld, q_len, x_len, theta, min_score=0.0, top=16):
     return occ, occ_score, n_occ, row_h, row_j, row_org, row_off
 
 
+ALIGN_OCC_MAX_ROWS = _H["NSID_ALIGN_OCC_MAX_ROWS"]      # rows of one run of align_occurrences at most
+
+
+def align_carry(x_len, device):
+    """a carry for local_align_strip: ((carry_h fp32, carry_i0 int32, carry_j0 int32) flat device tensors, carry_off int64 numpy);
+    pair p's two rows of x_len[p] cells start at carry_off[p]. The content is not initialised: a pair's first strip is fresh."""
+    x_len = _align_seq("align_carry", "x_len", x_len)
+    if x_len.size and (x_len.min() < 0 or x_len.max() > ALIGN_MAX_COLS):
+        raise ValueError(f"align_carry: a song of {int(x_len.max())} rows is outside [0, {ALIGN_MAX_COLS}]")
+    size = 2 * x_len
+    n = int(size.sum())
+    carry = (torch.empty((n,), device=device, dtype=torch.float32), torch.empty((n,), device=device, dtype=torch.int32),
+             torch.empty((n,), device=device, dtype=torch.int32))
+    return carry, np.cumsum(size) - size
+
+
+def _flat_dev(name, what, t, dtype):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: {what} must be a torch tensor on the GPU")
+    if not t.is_cuda:
+        raise RuntimeError("neuralsampleid_amd ops need tensors on the MI355X (cuda) device; there is no CPU path")
+    if t.dtype != dtype or t.dim() != 1 or not t.is_contiguous():
+        raise RuntimeError(f"{name}: {what} must be a flat contiguous {dtype} tensor")
+
+
+def local_align_strip(S, s_off, s_ld, q_len, x_len, theta, row_base, fresh, carry, carry_off, rows=None, row_off=None):
+    """One strip of the local alignment of include/nsid.h for many pairs in one launch (nsid_local_align_strip): pair p's q_len[p] rows
+    are the GLOBAL query rows row_base[p] .. of its matrix, and the walk starts from the pair's carried rows (fresh[p]: from zeros) and
+    leaves the last two rows in the carry, in place. Chained over strips of any lengths this is the rule on the whole matrix, bit for
+    bit, whatever the cuts.
+
+    S, s_off, s_ld, q_len, x_len, theta: as local_align takes them (q_len: the rows of this strip, at most ALIGN_MAX_ROWS). row_base,
+    fresh, carry_off: host integer sequences, one entry per pair. carry: (carry_h fp32, carry_i0 int32, carry_j0 int32), flat device
+    tensors of one length (align_carry); pair p's part is [carry_off[p], carry_off[p] + 2 x_len[p]), and the parts must not overlap.
+    rows / row_off: four flat device tensors (fp32, int32, int32, int32) and per pair the first element to write the row results into
+    (default: new tensors, the pairs one after the other). Returns (row_h, row_j, row_i0, row_j0, row_off int64 numpy, open_h (pairs,)
+    fp32 on the device): a row without a passing cell holds 0, -1, -1, -1; the rows of a pair with q_len = 0 are not written; open_h is
+    the largest H carried out (0: no path is open)."""
+    if not isinstance(S, torch.Tensor):
+        raise TypeError("local_align_strip: S must be a torch tensor on the GPU")
+    _chk(S)
+    S = S.reshape(-1)
+    name = "local_align_strip"
+    s_off = _align_seq(name, "s_off", s_off)
+    npairs = s_off.size
+    s_ld, q_len, x_len, row_base, fresh, carry_off = (_align_seq(name, w, v, npairs) for w, v in (
+        ("s_ld", s_ld), ("q_len", q_len), ("x_len", x_len), ("row_base", row_base), ("fresh", fresh), ("carry_off", carry_off)))
+    theta = float(theta)
+    if theta != theta:
+        raise ValueError("local_align_strip: theta is NaN")
+    if npairs and (q_len.min() < 0 or x_len.min() < 0):
+        raise ValueError("local_align_strip: a length is negative")
+    if npairs and (q_len.max() > ALIGN_MAX_ROWS or x_len.max() > ALIGN_MAX_COLS):
+        raise ValueError(f"local_align_strip: a strip of {int(q_len.max())} x {int(x_len.max())} rows is outside the limits "
+                         f"({ALIGN_MAX_ROWS} query rows per strip, {ALIGN_MAX_COLS} song rows)")
+    if npairs and (row_base.min() < 0 or (row_base + q_len).max() > 2 ** 31 - 1):
+        raise ValueError("local_align_strip: every pair needs 0 <= row_base and row_base + q_len <= 2^31 - 1")
+    full = (q_len > 0) & (x_len > 0)
+    if npairs and full.any() and (s_off[full].min() < 0 or (s_ld[full] < x_len[full]).any() or s_ld.max() >= 2 ** 31
+                                  or (s_off + (q_len - 1) * s_ld + x_len)[full].max() > S.numel()):
+        raise ValueError("local_align_strip: a pair's score block (q_len rows of s_ld >= x_len floats) leaves S")
+    if not isinstance(carry, (tuple, list)) or len(carry) != 3:
+        raise TypeError("local_align_strip: carry must be (carry_h, carry_i0, carry_j0)")
+    for what, t, dt in zip(("carry_h", "carry_i0", "carry_j0"), carry, (torch.float32, torch.int32, torch.int32)):
+        _flat_dev(name, what, t, dt)
+    if not carry[0].numel() == carry[1].numel() == carry[2].numel():
+        raise ValueError("local_align_strip: the three carry tensors must have one length")
+    if npairs:
+        order = np.argsort(carry_off, kind="stable")
+        lo, hi = carry_off[order], (carry_off + 2 * x_len)[order]
+        if lo[0] < 0 or hi.max() > carry[0].numel() or (lo[1:] < hi[:-1]).any():
+            raise ValueError("local_align_strip: a pair's carry (2 x_len cells at carry_off) leaves the carry tensors or overlaps another's")
+    dev = S.device
+    total = int(q_len.sum())
+    if rows is None:
+        if row_off is not None:
+            raise ValueError("local_align_strip: row_off needs rows")
+        row_off = np.cumsum(q_len) - q_len
+        rows = (torch.empty((total,), device=dev, dtype=torch.float32),) + tuple(
+            torch.empty((total,), device=dev, dtype=torch.int32) for _ in range(3))
+    else:
+        if not isinstance(rows, (tuple, list)) or len(rows) != 4 or row_off is None:
+            raise TypeError("local_align_strip: rows must be (row_h, row_j, row_i0, row_j0), given together with row_off")
+        for what, t, dt in zip(("row_h", "row_j", "row_i0", "row_j0"), rows, (torch.float32, torch.int32, torch.int32, torch.int32)):
+            _flat_dev(name, what, t, dt)
+        row_off = _align_seq(name, "row_off", row_off, npairs)
+        least = min(t.numel() for t in rows)
+        if npairs:
+            order = np.argsort(row_off, kind="stable")
+            lo, hi = row_off[order], (row_off + q_len)[order]
+            if lo[0] < 0 or hi.max() > least or (lo[1:] < hi[:-1]).any():
+                raise ValueError("local_align_strip: a pair's rows (q_len at row_off) leave the row tensors or overlap another's")
+    open_h = torch.empty((npairs,), device=dev, dtype=torch.float32)
+    if npairs == 0:
+        return rows[0], rows[1], rows[2], rows[3], row_off, open_h
+    t32 = torch.from_numpy(np.stack([s_ld, q_len, x_len, row_base, (fresh != 0).astype(np.int64)]).astype(np.int32)).to(dev)
+    t64 = torch.from_numpy(np.stack([np.where(full, s_off, 0), carry_off, row_off])).to(dev)
+    cells = float((q_len * x_len).sum())
+    _tk(None, 4.0 * cells + 16.0 * total + 48.0 * float(x_len.sum()), lambda: call(
+        "nsid_local_align_strip", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), npairs,
+        int(q_len.max()), int(x_len.max()), theta, _p(t64[1]), _p(carry[0]), _p(carry[1]), _p(carry[2]), _p(t64[2]), _p(rows[0]),
+        _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(open_h), _stream()), (npairs, int(q_len.max()), int(x_len.max()), 1))
+    return rows[0], rows[1], rows[2], rows[3], row_off, open_h
+
+
+def align_occurrences(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, min_score=0.0, top=16):
+    """The occurrences of many runs of rows in one launch (nsid_align_occurrences): run p is rows row_off[p] .. row_off[p] + n_rows[p] - 1
+    of the four flat device tensors (local_align_strip's row results, the strips of a run one after the other), its local row r is
+    global row first_row[p] + r. Grouping by (row_i0, row_j0), a group's best row, min_score, the order and the unused slots as
+    local_align has them. Returns (occ (runs, top, 4) int32 = (i0, i1, j0, j1) in global rows, occ_score (runs, top) fp32, n_occ
+    (runs,) int32, it can exceed top)."""
+    name = "align_occurrences"
+    for what, t, dt in zip(("row_h", "row_j", "row_i0", "row_j0"), (row_h, row_j, row_i0, row_j0),
+                           (torch.float32, torch.int32, torch.int32, torch.int32)):
+        _flat_dev(name, what, t, dt)
+    row_off = _align_seq(name, "row_off", row_off)
+    npairs = row_off.size
+    n_rows, first_row = (_align_seq(name, w, v, npairs) for w, v in (("n_rows", n_rows), ("first_row", first_row)))
+    top = int(top)
+    if not 1 <= top <= ALIGN_MAX_TOP:
+        raise ValueError(f"align_occurrences: top = {top} is outside [1, {ALIGN_MAX_TOP}]")
+    min_score = float(min_score)
+    if min_score != min_score:
+        raise ValueError("align_occurrences: min_score is NaN")
+    if npairs and (n_rows.min() < 0 or n_rows.max() > ALIGN_OCC_MAX_ROWS):
+        raise ValueError(f"align_occurrences: a run of {int(n_rows.max())} rows is outside [0, {ALIGN_OCC_MAX_ROWS}]")
+    if npairs and (first_row.min() < 0 or (first_row + n_rows).max() > 2 ** 31 - 1):
+        raise ValueError("align_occurrences: every run needs 0 <= first_row and first_row + n_rows <= 2^31 - 1")
+    least = min(t.numel() for t in (row_h, row_j, row_i0, row_j0))
+    if npairs and (row_off.min() < 0 or (row_off + n_rows).max() > least):
+        raise ValueError("align_occurrences: a run (n_rows at row_off) leaves the row tensors")
+    dev = row_h.device
+    occ = torch.empty((npairs, top, 4), device=dev, dtype=torch.int32)
+    occ_score = torch.empty((npairs, top), device=dev, dtype=torch.float32)
+    n_occ = torch.empty((npairs,), device=dev, dtype=torch.int32)
+    if npairs == 0:
+        return occ, occ_score, n_occ
+    t32 = torch.from_numpy(np.stack([n_rows, first_row]).astype(np.int32)).to(dev)
+    t64 = torch.from_numpy(np.ascontiguousarray(row_off)).to(dev)
+    _tk("align_occurrences_kernel", 16.0 * float(n_rows.sum()), lambda: call(
+        "nsid_align_occurrences", _p(row_h), _p(row_j), _p(row_i0), _p(row_j0), _p(t64), _p(t32[0]), _p(t32[1]), npairs,
+        int(n_rows.max()), min_score, top, _p(occ), _p(occ_score), _p(n_occ), _stream()), (npairs, int(n_rows.max()), 0, top))
+    return occ, occ_score, n_occ
+
+
 # ------------------------------------------------------------------------------------------------ classifier re-rank (csrc/rerank.hip)
 CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = _H["NSID_CLF_C"], _H["NSID_CLF_KP"], _H["NSID_CLF_MAX_N"], _H["NSID_CLF_QCHUNK"]
 CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
