@@ -721,6 +721,35 @@ int nsid_song_vote_clf(const int64_t* I, int k, const float* S, const int64_t* s
                        int top, int* songs, double* totals, int* n_songs, void* stream);
 int nsid_vote_candidates(const int64_t* I, long n, int n_dummy, int n_ref, int* cidx, void* stream);
 
+/* ---- diagonal-histogram vote of a search result (csrc/diag_vote.hip). The reference keeps the retrieved indices "for calculating
+ * histogram-based matching score" in "future implementations" (eval.py:249-258); this is that score: the hits (query row i, reference
+ * row r) of one song that line up along a diagonal r - i = const vote together, wherever in the window the diagonal starts. It takes
+ * song_vote's pair table and skip conditions, and no scores. The rule, for pair p = (s = starts[p], L = lens[p]) (device int32; the
+ * caller guarantees s + L <= the rows of I):
+ *   Walk: positions j < L k, i = s + j / k, cid = I[i][j % k].
+ *   Skipped hits, exactly song_vote's: cid < 0, cid < n_dummy, cid >= n_dummy + n_ref, song_of[cid - n_dummy] < 0, or
+ *     song_of[cid - n_dummy] == exclude[p] (-1 = none; exclude may be NULL).
+ *   Bins: otherwise r = cid - n_dummy, c = song_of[r], delta = r - (i - s) + (L - 1) >= 0, narrow bin n = delta / B (B = bin_rows,
+ *     integer division). The bin phase is tied to reference rows, not to a song's rows, so no per-song table is needed; the song code
+ *     is part of the key. cnt[c][n] = the hits of song c in narrow bin n, a repeated candidate counted again.
+ *     wide[c][b] = cnt[c][b] + cnt[c][b + 1] for b >= 0: half-overlapping bins of 2 B rows, so a diagonal that drifts by up to B rows
+ *     (time stretch) stays inside one of them.
+ *   Ranking: a song's score is max over b of wide[c][b], equal maxima to the smaller b; the songs rank by score descending, equal
+ *     scores to the smaller code.
+ *   Outputs, each npairs x top, int32: songs (the codes best first, -1 past the last), counts (their scores, 0 past the last), and
+ *     i_lo, i_hi, r_lo, r_hi = the smallest and largest query row i (an index into the table I) and reference row r over the hits of
+ *     the song's winning wide bin (-1 past the last). n_songs[p] = the distinct songs that entered (it can exceed top).
+ * Everything is an integer: equal to the rule means equal in every bit; the order of summation is free. No global atomics; a pair's
+ * result depends on nothing but the pair.
+ * Limits: 1 <= k <= 64, 1 <= top <= NSID_VOTE_MAX_TOP, 1 <= bin_rows <= NSID_DIAG_MAX_BIN, n_ref + 4096 < 2^31 (delta stays an int32),
+ * n_ref, n_dummy, npairs >= 0: NSID_EINVAL before any launch otherwise. L k <= NSID_VOTE_MAX_CAND: the lengths live on the device, the
+ * caller checks them (ops.py does); a pair with L < 1 or L k > 4096 reads nothing and gets n_songs[p] = -1 and an empty row, as in
+ * song_vote. npairs == 0 launches nothing. Launches count on "diag_vote". */
+#define NSID_DIAG_MAX_BIN 4096 /* bin_rows at most */
+int nsid_diag_vote(const int64_t* I, int k, const int* starts, const int* lens, int npairs, const int* song_of, int n_ref, int n_dummy,
+                   const int* exclude, int bin_rows, int top, int* songs, int* counts, int* i_lo, int* i_hi, int* r_lo, int* r_hi,
+                   int* n_songs, void* stream);
+
 /* ---- locating a sample in time (csrc/align.hip): the score matrices of many (query, song) pairs and their local alignment. The
  * reference stops at the song (eval.py:250-258 leaves a "histogram-based matching score" to "future implementations"); sample100-ext
  * annotates where every occurrence lies in both tracks, with a tempo ratio.

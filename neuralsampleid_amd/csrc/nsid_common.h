@@ -287,6 +287,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(resample_sinc) X(stem_pairs_gate) X(stem_pairs_build)   /* stems.hip: sinc resampler, stem-pair sampler */ \
   X(logmel_fft_ragged) X(cqt_ragged) X(unfold_segments_ragged)   /* frontend.hip, cqt.hip, misc.hip: a pack of songs of different lengths in one launch, and its segment gather */ \
   X(song_vote) X(song_vote_clf) X(vote_candidates)   /* vote.hip: the song-level vote of a search result, and the device candidate list of the re-rank */ \
+  X(diag_vote)            /* diag_vote.hip: the diagonal-histogram vote of a search result */ \
   X(pair_sim) X(local_align)   /* align.hip: the score matrices of (query, song) pairs and their local alignment */ \
   X(local_align_strip) X(align_occurrences)   /* align.hip: the alignment in strips with carried rows, and the occurrences of a run of rows */ \
   X(bf16_rows) X(flat_l2_topk_coarse) X(flat_l2_rescore)   /* search.hip: the certified bf16 pre-filter of the exact search */ \

@@ -34,6 +34,12 @@ song carried from window to window, so an occurrence that crosses a window bound
     occs = idx.scan(wave=recording, threshold=0.6, min_score=2.0)
     sc = idx.scanner(threshold=0.6, min_score=2.0); sc.push(fp_piece); ...; occs = sc.finish()
 
+Which songs are aligned is decided by window votes. The default is the reference's sequence score, which sees an excerpt only where
+it starts a window; vote="diagonal" on locate / scan / links votes by the histogram of the hits' diagonals instead (csrc/diag_vote.hip,
+the score eval.py:249-258 leaves to "future implementations"), which sees it anywhere in the window; diag_votes is that vote alone.
+
+    occs = idx.scan(wave=recording, threshold=0.6, min_score=2.0, vote="diagonal")
+
 Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs past 4096 rows, and queries
 past 4096 rows outside scan (refused, not split), gap steps other than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated
 on real audio, parsing sample100-ext's annotation files."""
@@ -74,6 +80,57 @@ class PairVotes:
             m = int((codes[p] >= 0).sum())
             out.append(Identification([self.names[c] for c in codes[p, :m].tolist()], totals[p, :m].copy(), int(n[p])))
         return out
+
+
+class DiagIdentification(NamedTuple):
+    songs: List[str]          # names, best first (at most `top`)
+    counts: np.ndarray        # int32: the hits in each song's best diagonal bin
+    q_rows: np.ndarray        # (songs, 2) int32: first and last row of the query table among those hits
+    r_rows: np.ndarray        # (songs, 2) int32: first and last reference row (index order, dummies not counted) among them
+    n_songs: int              # the distinct songs that voted (can exceed `top`)
+
+
+class DiagVotes:
+    """the diagonal-histogram votes of many (start, length) pairs (ops.diag_vote): device tensors codes, counts, i_lo, i_hi, r_lo, r_hi
+    (pairs, top) int32 (-1, or 0 for counts, past the last song) and n_songs (pairs,) int32"""
+
+    def __init__(self, names, codes, counts, i_lo, i_hi, r_lo, r_hi, n_songs):
+        self.names, self.codes, self.counts, self.n_songs = names, codes, counts, n_songs
+        self.i_lo, self.i_hi, self.r_lo, self.r_hi = i_lo, i_hi, r_lo, r_hi
+
+    def __len__(self):
+        return self.codes.shape[0]
+
+    def results(self) -> List[DiagIdentification]:
+        codes, counts, n = self.codes.cpu().numpy(), self.counts.cpu().numpy(), self.n_songs.cpu().numpy()
+        q = torch.stack([self.i_lo, self.i_hi], dim=2).cpu().numpy()
+        r = torch.stack([self.r_lo, self.r_hi], dim=2).cpu().numpy()
+        out = []
+        for p in range(codes.shape[0]):
+            m = int((codes[p] >= 0).sum())
+            out.append(DiagIdentification([self.names[c] for c in codes[p, :m].tolist()], counts[p, :m].copy(), q[p, :m].copy(),
+                                          r[p, :m].copy(), int(n[p])))
+        return out
+
+
+VOTES = ("sequence", "diagonal")
+DIAG_BIN_ROWS = 16            # no measurement on real audio stands behind it: an excerpt of up to 64 rows at 1.25x drifts 16 rows
+DIAG_MIN_HITS = 2             # nor behind this: one hit is no diagonal
+
+
+def _vote_options(what, vote, bin_rows, min_hits, rerank=False):
+    """the refusals of the vote keywords, before anything is launched; returns (vote, bin_rows, min_hits)"""
+    if vote not in VOTES:
+        raise ValueError(f"{what}: vote = {vote!r} is not one of {VOTES}")
+    if vote == "diagonal" and rerank:
+        raise ValueError(f"{what}: vote='diagonal' counts search hits and has no re-ranked form (the classifier vote is a different "
+                         "rule): use vote='sequence' with rerank=True")
+    bin_rows, min_hits = int(bin_rows), int(min_hits)
+    if not 1 <= bin_rows <= ops.DIAG_MAX_BIN:
+        raise ValueError(f"{what}: bin_rows = {bin_rows} is outside [1, {ops.DIAG_MAX_BIN}]")
+    if min_hits < 1:
+        raise ValueError(f"{what}: min_hits = {min_hits} must be at least 1")
+    return vote, bin_rows, min_hits
 
 
 def _is_baseline(model) -> bool:
@@ -351,28 +408,7 @@ class SampleIndex:
                 raise ValueError(f"identify_pairs: {fp.shape[0]} fingerprints but {nodes.shape[0]} node matrices")
             if self._kp is None:
                 raise RuntimeError("identify_pairs: rerank=True, but no song of the index has node matrices")
-        k, top = int(k_probe), int(top)
-        if not 1 <= k <= ops.SEARCH_MAX_K:
-            raise ValueError(f"k_probe = {k} is outside [1, {ops.SEARCH_MAX_K}]")
-        if not 1 <= top <= ops.VOTE_MAX_TOP:
-            raise ValueError(f"top = {top} is outside [1, {ops.VOTE_MAX_TOP}]")
-        starts = np.asarray(starts, dtype=np.int64).reshape(-1)
-        lens = np.asarray(lens, dtype=np.int64).reshape(-1)
-        if starts.shape != lens.shape:
-            raise ValueError("identify_pairs: starts and lens differ in length")
-        if starts.size and (starts.min() < 0 or lens.min() < 1 or (starts + lens).max() > fp.shape[0]):
-            raise ValueError("identify_pairs: every pair needs 0 <= start, 1 <= length and start + length <= the rows of fp")
-        if starts.size and int(lens.max()) * k > ops.VOTE_MAX_CAND:
-            raise ValueError(f"identify_pairs: {int(lens.max())} segments x k_probe = {k} is more than {ops.VOTE_MAX_CAND} candidates per "
-                             "vote: lower k_probe or split the query")
-        ex = None
-        if exclude is not None:
-            if len(exclude) != starts.size:
-                raise ValueError("identify_pairs: exclude must hold one song name (or None) per pair")
-            ex = np.asarray([-1 if e is None else self.code(e) for e in exclude], dtype=np.int64)
-        left = None if leave_out is None else self._leave_out_ranges(leave_out, starts, lens, int(fp.shape[0]))
-        if self.n_ref == 0:
-            raise RuntimeError("SampleIndex: the index holds no song")
+        k, top, starts, lens, ex, left = self._pair_args("identify_pairs", fp, starts, lens, k_probe, top, exclude, leave_out)
         npairs = starts.size
         if npairs == 0:
             return PairVotes(self.names, torch.empty((0, top), device=self.device, dtype=torch.int32),
@@ -397,6 +433,63 @@ class SampleIndex:
         votes = ops.song_vote_clf(I, out, s_off, s_ld, starts, lens, self._song_of_nodes[: self.n_ref], self.n_dummy, ex,
                                   CLF_THRESHOLD, top)
         return PairVotes(self.names, *votes, scores=out, s_off=s_off, s_ld=s_ld)
+
+    def _pair_args(self, what, fp, starts, lens, k_probe, top, exclude, leave_out):
+        """the checks of a table of (start, length) pairs that every vote shares; returns (k, top, starts, lens as int64 numpy, the
+        exclude codes or None, the leave-out ranges or None)"""
+        k, top = int(k_probe), int(top)
+        if not 1 <= k <= ops.SEARCH_MAX_K:
+            raise ValueError(f"k_probe = {k} is outside [1, {ops.SEARCH_MAX_K}]")
+        if not 1 <= top <= ops.VOTE_MAX_TOP:
+            raise ValueError(f"top = {top} is outside [1, {ops.VOTE_MAX_TOP}]")
+        starts = np.asarray(starts, dtype=np.int64).reshape(-1)
+        lens = np.asarray(lens, dtype=np.int64).reshape(-1)
+        if starts.shape != lens.shape:
+            raise ValueError(f"{what}: starts and lens differ in length")
+        if starts.size and (starts.min() < 0 or lens.min() < 1 or (starts + lens).max() > fp.shape[0]):
+            raise ValueError(f"{what}: every pair needs 0 <= start, 1 <= length and start + length <= the rows of fp")
+        if starts.size and int(lens.max()) * k > ops.VOTE_MAX_CAND:
+            raise ValueError(f"{what}: {int(lens.max())} segments x k_probe = {k} is more than {ops.VOTE_MAX_CAND} candidates per "
+                             "vote: lower k_probe or split the query")
+        ex = None
+        if exclude is not None:
+            if len(exclude) != starts.size:
+                raise ValueError(f"{what}: exclude must hold one song name (or None) per pair")
+            ex = np.asarray([-1 if e is None else self.code(e) for e in exclude], dtype=np.int64)
+        left = None if leave_out is None else self._leave_out_ranges(leave_out, starts, lens, int(fp.shape[0]))
+        if self.n_ref == 0:
+            raise RuntimeError("SampleIndex: the index holds no song")
+        return k, top, starts, lens, ex, left
+
+    @torch.no_grad()
+    def diag_votes(self, fp: torch.Tensor, starts: Sequence[int], lens: Sequence[int], k_probe: int = 20, top: int = 10,
+                   bin_rows: int = DIAG_BIN_ROWS, exclude: Optional[Sequence[Optional[str]]] = None,
+                   leave_out: Optional[Sequence[Optional[str]]] = None) -> DiagVotes:
+        """The diagonal-histogram vote (include/nsid.h nsid_diag_vote) of many (start, length) pairs of one query table: one search and
+        one ops.diag_vote, no seq_scores. A song's count is the largest number of its retrieved rows whose offset to the query row
+        falls into one bin of 2 bin_rows rows, so an excerpt votes wherever in the pair's rows it starts, and under a time stretch of
+        up to bin_rows rows of drift. fp, starts, lens, exclude, leave_out: identify_pairs'. bin_rows = 16 keeps an excerpt of up to 64
+        rows at 1.25x in one bin; no measurement on real audio stands behind the number."""
+        self._check_fp(fp, "diag_votes")
+        bin_rows = _vote_options("diag_votes", "diagonal", bin_rows, 1)[1]
+        k, top, starts, lens, ex, left = self._pair_args("diag_votes", fp, starts, lens, k_probe, top, exclude, leave_out)
+        if starts.size == 0:
+            e = lambda: torch.empty((0, top), device=self.device, dtype=torch.int32)
+            return DiagVotes(self.names, e(), e(), e(), e(), e(), e(), torch.empty((0,), device=self.device, dtype=torch.int32))
+        _, I = self._index.search(fp.contiguous(), k, exclude=left)
+        return DiagVotes(self.names, *ops.diag_vote(I, starts, lens, self._song_of[: self.n_ref], self.n_dummy, ex, bin_rows, top))
+
+    def _window_votes(self, fp, starts, lens, k, top, exclude, leave_out, rerank, nodes, vote, bin_rows, min_hits):
+        """the votes of some windows on the host: (codes (pairs, top), -1 = none; totals (pairs, top); hints (pairs, top, 4) = i_lo, i_hi,
+        r_lo, r_hi, or None). vote='sequence': identify_pairs' totals. vote='diagonal': diag_votes' counts, and a song with fewer than
+        min_hits hits in its best bin is no candidate."""
+        if vote == "sequence":
+            pv = self.identify_pairs(fp, starts, lens, k_probe=k, top=top, exclude=exclude, rerank=rerank, nodes=nodes, leave_out=leave_out)
+            return pv.codes.cpu().numpy(), pv.totals.cpu().numpy(), None
+        dv = self.diag_votes(fp, starts, lens, k_probe=k, top=top, bin_rows=bin_rows, exclude=exclude, leave_out=leave_out)
+        packed = torch.stack([dv.codes, dv.counts, dv.i_lo, dv.i_hi, dv.r_lo, dv.r_hi], dim=2).cpu().numpy()      # one copy
+        codes, counts = packed[:, :, 0], packed[:, :, 1]
+        return np.where(counts >= min_hits, codes, -1), counts, packed[:, :, 2:]
 
     def _leave_out_ranges(self, leave_out, starts, lens, rows):
         """identify_pairs' leave_out as FlatL2Index.search's exclude: per row of the query table the index rows (dummy ++ ref ids) of
@@ -561,7 +654,8 @@ class SampleIndex:
     def locate(self, specs=None, wave=None, fp=None, nodes=None, songs: Optional[Sequence[str]] = None, k_probe: int = 20,
                n_songs: int = 5, exclude: Optional[str] = None, threshold: Optional[float] = None, min_score: float = 0.0,
                top: int = 16, rerank: bool = False, row_hop_s=None, row_len_s=None,
-               leave_out: Optional[str] = None) -> List["Occurrence"]:
+               leave_out: Optional[str] = None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
+               min_hits: int = DIAG_MIN_HITS) -> List["Occurrence"]:
         """The occurrences of resident songs in a query, one flat list sorted by score: encodes as identify does, finds the candidate
         songs (songs=None) and aligns the query against them.
 
@@ -570,7 +664,14 @@ class SampleIndex:
         window total (descending, then by code); the first n_songs are aligned. This is also what lets a whole track through at
         k_probe = 20. exclude: a song name that is never a candidate. leave_out: a song name whose rows do not compete in the search
         (identify's leave_out: the query is that resident song), so it is never a candidate either and the other songs get its slots;
-        refused with songs=, as exclude is. threshold: see align (no default without rerank)."""
+        refused with songs=, as exclude is. threshold: see align (no default without rerank).
+
+        vote="diagonal": the windows are voted by diag_votes instead (no seq_scores): a window's candidates are its songs with at least
+        min_hits hits in one diagonal bin of 2 bin_rows rows, ordered across windows by their best window count, then code. The
+        sequence vote scores a candidate against the window's first rows, so it sees an excerpt only where it starts a window; the
+        diagonal vote sees it anywhere in the window. Refused with rerank=True. bin_rows and min_hits have no measurement on real
+        audio behind them."""
+        vote, bin_rows, min_hits = _vote_options("locate", vote, bin_rows, min_hits, rerank)
         if rerank:
             self._check_rerank()
         elif threshold is None:
@@ -595,7 +696,7 @@ class SampleIndex:
             if fp.shape[0] > ops.ALIGN_MAX_ROWS:
                 raise ValueError(f"locate: a query of {fp.shape[0]} rows is past the limit of {ops.ALIGN_MAX_ROWS}; longer inputs are "
                                  "refused, not split")
-            songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank, leave_out)
+            songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank, leave_out, vote, bin_rows, min_hits)
         per_song = self.align(fp, songs, threshold, min_score, top, nodes, rerank, row_hop_s=row_hop_s, row_len_s=row_len_s)
         flat = [(o, c, n) for c, occs in enumerate(per_song) for n, o in enumerate(occs)]
         flat.sort(key=lambda t: (-t[0].score, t[1], t[2]))
@@ -619,28 +720,34 @@ class SampleIndex:
                 best[c] = total
         return sorted(best, key=lambda c: (-best[c], c))
 
-    def _candidates(self, fp, nodes, k, n_songs, exclude, rerank, leave_out=None) -> List[str]:
+    def _candidates(self, fp, nodes, k, n_songs, exclude, rerank, leave_out=None, vote="sequence", bin_rows=DIAG_BIN_ROWS,
+                    min_hits=DIAG_MIN_HITS) -> List[str]:
         """the songs of any window's top list, by their best window total (descending, then by code), at most n_songs"""
         Lq = int(fp.shape[0])
         if Lq == 0:
             raise ValueError("locate: the query has no row")
         starts, W = self._windows(Lq, k)
-        pv = self.identify_pairs(fp, starts, [W] * len(starts), k_probe=k, top=min(ops.VOTE_MAX_TOP, max(n_songs, 1)),
-                                 exclude=None if exclude is None else [exclude] * len(starts), rerank=rerank, nodes=nodes,
-                                 leave_out=None if leave_out is None else [leave_out] * len(starts))
-        order = self._best_songs(pv.codes.cpu().numpy().reshape(-1).tolist(), pv.totals.cpu().numpy().reshape(-1).tolist())
+        codes, totals, _ = self._window_votes(fp, starts, [W] * len(starts), k, min(ops.VOTE_MAX_TOP, max(n_songs, 1)),
+                                              None if exclude is None else [exclude] * len(starts),
+                                              None if leave_out is None else [leave_out] * len(starts), rerank, nodes, vote, bin_rows,
+                                              min_hits)
+        order = self._best_songs(codes.reshape(-1).tolist(), totals.reshape(-1).tolist())
         return [self.names[c] for c in order[:n_songs]]
 
     # ------------------------------------------------------------------------------------------------ scanning a long recording
     def scanner(self, threshold: Optional[float] = None, min_score: float = 0.0, k_probe: int = 20, n_songs: int = 5, top: int = 16,
                 window_rows: Optional[int] = None, songs: Optional[Sequence[str]] = None, exclude: Optional[str] = None,
-                max_active: int = 64, row_hop_s=None, row_len_s=None) -> "Scanner":
+                max_active: int = 64, row_hop_s=None, row_len_s=None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
+                min_hits: int = DIAG_MIN_HITS) -> "Scanner":
         """A Scanner over this index: a recording of any length, pushed in pieces of any sizes, is voted on and aligned in windows of
         W = window_rows or VOTE_MAX_CAND // k_probe rows (at most min(VOTE_MAX_CAND // k_probe, ALIGN_MAX_ROWS)), aligned to the global
         row index, so the result depends on the rows alone. The alignment is locate's rule, carried from window to window
         (ops.local_align_strip): a path that crosses a window boundary is one occurrence, found once. See Scanner for the active-set
         and run rules. songs=[names]: exactly these songs are aligned in every window and nothing is voted (the streaming form of
-        align). exclude: a song name that never votes. threshold has no default, as in align. Every refusal comes before any launch."""
+        align). exclude: a song name that never votes. threshold has no default, as in align. vote="diagonal", bin_rows, min_hits:
+        locate's (the window's vote is diag_votes', so an excerpt that starts deep inside a window, or lies wholly inside one, is
+        aligned in that window). Every refusal comes before any launch."""
+        vote, bin_rows, min_hits = _vote_options("scanner", vote, bin_rows, min_hits)
         if threshold is None:
             raise ValueError("scanner: threshold has no default for fingerprint scores (the reference has no such number and none has "
                              "been measured on real audio): pass one")
@@ -670,7 +777,7 @@ class SampleIndex:
             for c in fixed:
                 self._scan_song_ok(c)
         return Scanner(self, fixed, threshold, min_score, k, n_songs, top, min(W, cap), None if exclude is None else self.code(exclude),
-                       max_active, self._row_timing(row_hop_s, row_len_s))
+                       max_active, self._row_timing(row_hop_s, row_len_s), vote, bin_rows, min_hits)
 
     def _scan_song_ok(self, c):
         if self._song_rows[c][1] > ops.ALIGN_MAX_COLS:
@@ -690,7 +797,8 @@ class SampleIndex:
     @torch.no_grad()
     def links(self, names: Optional[Sequence[str]] = None, k_probe: int = 20, n_songs: int = 5, threshold: Optional[float] = None,
               min_score: float = 0.0, top: int = 16, block_rows: int = 1 << 16, s_budget_bytes: int = 1 << 30, row_hop_s=None,
-              row_len_s=None) -> "CatalogueLinks":
+              row_len_s=None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
+              min_hits: int = DIAG_MIN_HITS) -> "CatalogueLinks":
         """Which resident songs share material with which others? The self-join of the catalogue: for every named song (default: all,
         in add order) the query is the song's own resident fingerprint rows (nothing is encoded again or copied to the host), and
         occurrences[name] is what locate(fp=those rows, leave_out=name, k_probe=..., n_songs=..., threshold=..., min_score=..., top=...)
@@ -706,7 +814,11 @@ class SampleIndex:
         skipped: the songs of more than ALIGN_MAX_ROWS rows, which are not queried, and those of more than ALIGN_MAX_COLS rows, which
         are no candidates either (they are dropped from a song's candidate list before it is cut to n_songs, where locate would refuse
         the call); both limits stay. threshold has no default, as in locate. There is no rerank here: the index keeps the candidates'
-        [K | P] rows, not the queries' projection, so a song's rows cannot be the classifier's query side."""
+        [K | P] rows, not the queries' projection, so a song's rows cannot be the classifier's query side.
+
+        vote="diagonal", bin_rows, min_hits: locate's; the block's windows go through one diag_vote instead of seq_scores + song_vote,
+        and a partner sampled in the middle of a long song is a candidate by its diagonal, not by chance."""
+        vote, bin_rows, min_hits = _vote_options("links", vote, bin_rows, min_hits)
         if threshold is None:
             raise ValueError("links: threshold has no default for fingerprint scores (the reference has no such number and none has "
                              "been measured on real audio): pass one")
@@ -742,11 +854,13 @@ class SampleIndex:
             while hi < len(query) and (hi == lo or used + rows_of[query[hi]] <= block_rows):
                 used += rows_of[query[hi]]
                 hi += 1
-            self._links_block(query[lo:hi], k, n_songs, vote_top, too_long, threshold, min_score, top, int(s_budget_bytes), timing, out)
+            self._links_block(query[lo:hi], k, n_songs, vote_top, too_long, threshold, min_score, top, int(s_budget_bytes), timing, out,
+                              vote, bin_rows, min_hits)
             lo = hi
         return CatalogueLinks(out, skipped)
 
-    def _links_block(self, block, k, n_songs, vote_top, too_long, threshold, min_score, top, budget, timing, out):
+    def _links_block(self, block, k, n_songs, vote_top, too_long, threshold, min_score, top, budget, timing, out, vote="sequence",
+                     bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS):
         """one block of links: the songs `block` (codes) as queries; fills out[name]"""
         first = np.asarray([self._song_rows[c][0] for c in block], dtype=np.int64)
         count = np.asarray([self._song_rows[c][1] for c in block], dtype=np.int64)
@@ -763,8 +877,8 @@ class SampleIndex:
             starts += [int(base[b]) + v for v in s]
             lens += [W] * len(s)
             owner += [b] * len(s)
-        pv = self.identify_pairs(fp, starts, lens, k_probe=k, top=vote_top, leave_out=[self.names[block[b]] for b in owner])
-        codes, totals = pv.codes.cpu().numpy(), pv.totals.cpu().numpy()
+        codes, totals, _ = self._window_votes(fp, starts, lens, k, vote_top, None, [self.names[block[b]] for b in owner], False, None,
+                                              vote, bin_rows, min_hits)
         owner = np.asarray(owner)
         pairs = []                                                # (song of the block, candidate code), a song's candidates in order
         for b in range(len(block)):
@@ -815,16 +929,21 @@ class Scanner:
     Then one pair_sim and one local_align_strip for all active songs; a song that was not active in t - 1 starts fresh. A song's
     maximal stretch of consecutive active windows is a run; the rows of every run go through one align_occurrences call at finish().
 
-    trace: one dict per window, host values: start, rows, vote_codes, vote_totals, active (codes, in order), open_h (after the strip).
+    trace: one dict per window, host values: start, rows, vote_codes, vote_totals, active (codes, in order), open_h (after the strip),
+    vote_hints. With vote="diagonal" the window's vote is diag_votes' (songs of at least min_hits hits in one bin), vote_totals are
+    the counts, and vote_hints holds per voted song (first, last row of the recording; first, last row of the song) over the hits of
+    its winning bin; with the sequence vote vote_hints is empty.
     stats: windows, strips (pairs aligned), runs, rows, closed_at_cap. runs (after finish): per run a dict with song, code, first_row,
     n_rows and the device row results row_h, row_j, row_i0, row_j0.
     Not here: rerank cells, leave_out, songs of more than ALIGN_MAX_COLS rows, a streaming front end, hipGraph capture, several GPUs;
     a run is at most ops.ALIGN_OCC_MAX_ROWS rows."""
 
-    def __init__(self, index, fixed, threshold, min_score, k, n_songs, top, W, exclude, max_active, timing):
+    def __init__(self, index, fixed, threshold, min_score, k, n_songs, top, W, exclude, max_active, timing, vote="sequence",
+                 bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS):
         self.index, self._fixed, self._theta, self._min_score = index, fixed, threshold, min_score
         self._k, self._n_songs, self._top, self.window_rows, self._exclude, self._max_active = k, n_songs, top, W, exclude, max_active
         self._timing = timing
+        self._vote, self._bin_rows, self._min_hits = vote, bin_rows, min_hits
         self._pend = None                 # rows pushed and not yet in a window
         self._next = 0                    # global index of the first pending row
         self._active: List[int] = []      # window t - 1
@@ -872,15 +991,19 @@ class Scanner:
     def _window(self, rows):
         idx, start, n = self.index, self._next, int(rows.shape[0])
         rows = rows.contiguous()
-        vote_codes, vote_totals = [], []
+        vote_codes, vote_totals, vote_hints = [], [], []
         if self._fixed is not None:
             want = list(self._fixed)
         else:
-            pv = idx.identify_pairs(rows, [0], [n], k_probe=self._k, top=min(ops.VOTE_MAX_TOP, self._n_songs),
-                                    exclude=None if self._exclude is None else [idx.names[self._exclude]])
-            codes, totals = pv.codes.cpu().numpy()[0], pv.totals.cpu().numpy()[0]
-            m = int((codes >= 0).sum())
+            codes, totals, hints = idx._window_votes(rows, [0], [n], self._k, min(ops.VOTE_MAX_TOP, self._n_songs),
+                                                     None if self._exclude is None else [idx.names[self._exclude]], None, False, None,
+                                                     self._vote, self._bin_rows, self._min_hits)
+            codes, totals = codes[0], totals[0]
+            m = int((codes >= 0).sum())                              # the diagonal vote's songs below min_hits are a tail: counts descend
             vote_codes, vote_totals = codes[:m].tolist(), totals[:m].tolist()
+            if hints is not None:
+                vote_hints = [(start + int(h[0]), start + int(h[1]), int(h[2]) - idx._song_rows[c][0], int(h[3]) - idx._song_rows[c][0])
+                              for c, h in zip(vote_codes, hints[0][:m])]
             cont = sorted((c for c in self._active if self._open[c] > 0), key=lambda c: (-self._open[c], c))
             want = cont + [c for c in vote_codes[: self._n_songs] if c not in cont]
             self.stats["closed_at_cap"] += max(0, len(want) - self._max_active)
@@ -914,7 +1037,7 @@ class Scanner:
         self._active = want
         self._next = start + n
         self.trace.append({"start": start, "rows": n, "vote_codes": vote_codes, "vote_totals": vote_totals, "active": list(want),
-                           "open_h": open_h})
+                           "open_h": open_h, "vote_hints": vote_hints})
         self.stats["windows"] += 1
         self.stats["strips"] += len(want)
         self.stats["rows"] += n

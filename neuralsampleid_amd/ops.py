@@ -2095,6 +2095,36 @@ def song_vote_clf(I, S, s_off, s_ld, starts, lens, song_of, n_dummy, exclude=Non
     return songs, totals, n_songs
 
 
+DIAG_MAX_BIN = _H["NSID_DIAG_MAX_BIN"]
+
+
+def diag_vote(I, starts, lens, song_of, n_dummy, exclude=None, bin_rows=16, top=10):
+    """The diagonal-histogram vote (include/nsid.h nsid_diag_vote) for every (start, length) pair at once: a song's score is the
+    largest number of its hits (query row i, reference row r) whose diagonal r - i falls into one bin of 2 bin_rows rows (bins
+    overlap by half), wherever in the pair's rows the diagonal starts. It needs no scores.
+
+    I, starts, lens, song_of, n_dummy, exclude: song_vote's. Returns (songs (pairs, top) int32, best first, -1 past the last; counts
+    (pairs, top) int32; i_lo, i_hi, r_lo, r_hi (pairs, top) int32: the first and last query row (index into I) and reference row of
+    the hits in the song's winning bin, -1 past the last; n_songs (pairs,) int32 = the distinct songs that voted), on the device."""
+    k, starts, lens, exclude, n_ref, n_dummy, top = _vote_args("diag_vote", I, starts, lens, song_of, n_dummy, exclude, top)
+    bin_rows = int(bin_rows)
+    if not 1 <= bin_rows <= DIAG_MAX_BIN:
+        raise ValueError(f"diag_vote: bin_rows = {bin_rows} is outside [1, {DIAG_MAX_BIN}]")
+    if n_ref + VOTE_MAX_CAND >= 2 ** 31:
+        raise ValueError(f"diag_vote: {n_ref} reference rows + {VOTE_MAX_CAND} must stay below 2^31")
+    npairs = starts.size
+    out = tuple(torch.empty((npairs, top), device=I.device, dtype=torch.int32) for _ in range(6))
+    n_songs = torch.empty((npairs,), device=I.device, dtype=torch.int32)
+    if npairs == 0:
+        return (*out, n_songs)
+    st, ln, ex = _vote_table(I.device, starts, lens, exclude)
+    ncand = float((lens * k).sum())
+    _tk("diag_vote_kernel", 2 * 12.0 * ncand + 24.0 * npairs * top, lambda: call(
+        "nsid_diag_vote", _p(I), k, _p(st), _p(ln), npairs, _p(song_of), n_ref, n_dummy, _p(ex), bin_rows, top, *(_p(t) for t in out),
+        _p(n_songs), _stream()), (npairs, int(lens.max()) * k, top, bin_rows))
+    return (*out, n_songs)
+
+
 def vote_candidates(I, n_dummy, n_ref) -> torch.Tensor:
     """the device candidate list of a search result: I (any shape) int64 ids over dummy ++ ref -> int32 of the same shape, I - n_dummy
     for a ref row and 0 elsewhere (the votes skip those positions from I, so what is scored there is never read)"""

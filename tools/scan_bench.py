@@ -1,6 +1,6 @@
 """Times the scan of a long recording (SampleIndex.scanner, ops.local_align_strip) on synthetic rows at d = 128.
 
-    python tools/scan_bench.py [--reps 9] [--quick]
+    python tools/scan_bench.py [--reps 9] [--quick] [--vote diagonal] [--no-walk]
 
 (a) The walk. 32 pairs of 4096 x 4096 through nsid_local_align in one launch, against the same S through nsid_local_align_strip in
     strips of 204 rows (the scanner's window at k_probe = 20) with the carry chained: 21 launches. Device events around the launches
@@ -10,7 +10,9 @@
     (2 rows x 12 bytes x the song's rows, read and written), and a walk that starts with an empty pipeline.
 (b) End to end. A 2-hour recording (14 063 rows at 0.512 s per row) with planted excerpts against a catalogue of the size
     tools/identify_bench.py uses (90 000 dummy rows + 250 songs x 40 rows): scan(fp=...) at the defaults, host clock, results on the
-    host: ms per window, the total, and the multiple of real time.
+    host: ms per window, the total, and the multiple of real time. The excerpts are planted at a window's second row and 100 rows
+    inside a window. With --vote diagonal the same scan is also timed with vote="diagonal" (ops.diag_vote instead of seq_scores +
+    song_vote per window), the two votes' repetitions interleaved, and the found / planted counts are printed for both votes.
 
 The repetitions of the two sides of (a) are interleaved; medians with min and max; the profiler is off."""
 import argparse
@@ -148,42 +150,51 @@ def scan_case(g, a):
     for a0, song, b, n, rate, _ in plants:
         _plant(g, q, ref[song * seg:(song + 1) * seg], a0, b, n, rate)
     kw = dict(threshold=THETA, min_score=MIN_SCORE, row_hop_s=ROW_S, row_len_s=2 * ROW_S)
-    run = lambda: idx.scan(fp=q, **kw)
-    occs = run()
+    votes = ("sequence", "diagonal") if a.vote == "diagonal" else ("sequence",)
+    run = lambda vote: idx.scan(fp=q, vote=vote, **kw)
+    occs = {v: run(v) for v in votes}
     torch.cuda.synchronize()
-    t = []
-    for _ in range(a.reps):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        run()
-        torch.cuda.synchronize()
-        t.append(1e3 * (time.perf_counter() - t0))
-    sc = idx.scanner(**kw)
-    sc.push(q)
-    sc.finish()
-    m = _st(t)
-    found = {"start": 0, "inside": 0}
-    for a0, song, b, n, rate, kind in plants:
-        want = (a0, a0 + n - 1)
-        found[kind] += any(o.song == f"s{song}" and abs(o.q_rows[0] - want[0]) <= 1 and abs(o.q_rows[1] - want[1]) <= 1 for o in occs)
+    t = {v: [] for v in votes}
+    for _ in range(a.reps):                                      # interleaved: A B A B ...
+        for v in votes:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            run(v)
+            torch.cuda.synchronize()
+            t[v].append(1e3 * (time.perf_counter() - t0))
     print(f"(b) scan end to end: {rows} rows ({rows * ROW_S / 3600:.2f} h) against {n_songs} songs x {seg} rows + {dummy} dummy rows; "
-          f"k_probe 20, n_songs 5, {sc.stats['windows']} windows of {W} rows, {sc.stats['strips']} strips, {sc.stats['runs']} runs")
-    print(f"  scan, total (host clock, results on the host)      {_fmt(m)}")
-    print(f"  per window {m[0] / sc.stats['windows']:.3f} ms; {rows * ROW_S / (m[0] / 1e3):.0f} x real time")
-    print(f"  {len(occs)} occurrences; planted at a window's second row: {found['start']} of {len(plants) // 2} found within one row; "
-          f"planted 100 rows inside a window: {found['inside']} of {len(plants) // 2}", flush=True)
+          f"k_probe 20, n_songs 5, windows of {W} rows")
+    for v in votes:
+        sc = idx.scanner(vote=v, **kw)
+        sc.push(q)
+        sc.finish()
+        m = _st(t[v])
+        found = {"start": 0, "inside": 0}
+        for a0, song, b, n, rate, kind in plants:
+            want = (a0, a0 + n - 1)
+            found[kind] += any(o.song == f"s{song}" and abs(o.q_rows[0] - want[0]) <= 1 and abs(o.q_rows[1] - want[1]) <= 1
+                               for o in occs[v])
+        print(f"  vote = {v}: {sc.stats['windows']} windows, {sc.stats['strips']} strips, {sc.stats['runs']} runs")
+        print(f"  scan, total (host clock, results on the host)      {_fmt(m)}")
+        print(f"  per window {m[0] / sc.stats['windows']:.3f} ms; {rows * ROW_S / (m[0] / 1e3):.0f} x real time")
+        print(f"  {len(occs[v])} occurrences; planted at a window's second row: {found['start']} of {len(plants) // 2} found within one "
+              f"row; planted 100 rows inside a window: {found['inside']} of {len(plants) // 2}", flush=True)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--quick", action="store_true", help="fewer repetitions, 4 pairs of 1024 x 1024, a 10-minute recording, a small index")
+    ap.add_argument("--vote", choices=("sequence", "diagonal"), default="sequence",
+                    help="diagonal: part (b) also with vote='diagonal', interleaved with the sequence vote")
+    ap.add_argument("--no-walk", action="store_true", help="skip part (a)")
     a = ap.parse_args()
     if a.quick:
         a.reps = min(a.reps, 3)
     g = torch.Generator(device=DEV).manual_seed(0)
     with torch.no_grad():
-        walk_case(g, *((4, 1024) if a.quick else (32, 4096)), 204, a.reps)
+        if not a.no_walk:
+            walk_case(g, *((4, 1024) if a.quick else (32, 4096)), 204, a.reps)
         scan_case(g, a)
 
 
