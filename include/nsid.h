@@ -827,6 +827,35 @@ int nsid_local_align_strip(const float* S, const int64_t* s_off, const int* s_ld
 int nsid_align_occurrences(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0, const int64_t* row_off,
                            const int* n_rows, const int* first_row, int npairs, int max_rows, float min_score, int top, int* occ,
                            float* occ_score, int* n_occ, void* stream);
+/* The strip walk against songs of more than NSID_ALIGN_MAX_COLS rows: column panels with two carried columns (csrc/align.hip). The
+ * rule reads (i-1, j-1), (i-1, j-2) and (i-2, j-1) only, so a panel of columns [c0, c0 + w) needs from everything to its left the cells
+ * of columns c0 - 2 and c0 - 1 alone, for every row including the two carried ones; with that halo a panel is bit for bit the rule.
+ * local_align_panels: nsid_local_align_strip's text above is the specification; what differs:
+ *   max_x_len <= NSID_ALIGN_MAX_SONG_ROWS = 16384 (x_len[p] likewise). That is the largest bound under which a cell keeps its 8 bytes:
+ *   the origin column needs j0 < 2^16, and the origin row, kept mod 2^15, needs i - i0 <= 2 (Lr - 1) = 32766 < 2^15.
+ *   panel_cols (host int, in [2, NSID_ALIGN_MAX_COLS]): the columns of a panel; one workgroup per pair walks the pair's panels left to
+ *   right inside the launch. The outputs (row_h, row_j, row_i0, row_j0, the carry in place, open_h) are those of the rule on the whole
+ *   q_len x x_len matrix from the carried rows, the same bits for every panel_cols and every chain of strips (0, 1 and 2 rows included).
+ *   A row's result across panels: a later panel replaces it only with a strictly larger H (ties stay with the smaller j); open_h is
+ *   the maximum over the panels.
+ *   The halo: workspace of the launch, three arrays as the carry is (halo_h fp32, halo_i0 / halo_j0 int32, global origins), pair p's
+ *   part at halo_off[p] (device int64) of (q_len[p] + 2) x 2 cells: rows -2, -1, 0 .. q_len - 1, two columns each. Its content before
+ *   and after the launch means nothing; the parts of two pairs must not overlap.
+ *   Bad pairs, x_len == 0, npairs == 0, atomics (none) as in local_align_strip; no workgroup waits on another. panel_cols outside its
+ *   range, max_x_len > 16384, max_q_len > 4096, a NaN theta, a null or misaligned pointer: NSID_EINVAL before any launch. Launches count
+ *   on "local_align_panels".
+ * align_occurrences_span: align_occurrences with the width of the window a row is compared in per run: span[p] (device int32). A
+ *   group's rows lie within [i0, i0 + 2 (x_len - 1)] for a song of x_len rows; the caller passes that, and any larger value gives the
+ *   same output. span[p] < 0: n_occ = -1. Launches count on "align_occurrences_span". */
+#define NSID_ALIGN_MAX_SONG_ROWS 16384 /* song rows of a pair at most in local_align_panels */
+int nsid_local_align_panels(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len,
+                            const int* row_base, const int* fresh, int npairs, int max_q_len, int max_x_len, int panel_cols,
+                            float theta, const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0,
+                            const int64_t* halo_off, float* halo_h, int* halo_i0, int* halo_j0, const int64_t* row_off, float* row_h,
+                            int* row_j, int* row_i0, int* row_j0, float* open_h, void* stream);
+int nsid_align_occurrences_span(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0, const int64_t* row_off,
+                                const int* n_rows, const int* first_row, const int* span, int npairs, int max_rows, float min_score,
+                                int top, int* occ, float* occ_score, int* n_occ, void* stream);
 
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed

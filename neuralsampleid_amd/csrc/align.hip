@@ -17,6 +17,11 @@
 //
 // local_align_strip / align_occurrences: the same walk from two carried rows to two carried rows, so that a recording of any length goes
 // through in strips, and the occurrences of a run of rows of any length from its row results (include/nsid.h, below nsid_local_align).
+//
+// local_align_panels / align_occurrences_span: the strip walk turned by 90 degrees for songs of up to 16384 rows. One workgroup still
+// owns a pair, but walks the strip once per panel of at most 4096 columns with two carried columns (the halo) between panels, so the
+// LDS rows keep their width; the occurrence kernel takes the width of a group's window per run (include/nsid.h, below
+// nsid_align_occurrences).
 #include "nsid_common.h"
 
 namespace {
@@ -530,26 +535,256 @@ int launch_align_strip(hipStream_t st, int npairs, const float* S, const int64_t
   return nsid_launch_status();
 }
 
+// ---- local_align_panels -----------------------------------------------------------------------------------------------------------
+// The strip walk for songs of up to AL_MAX_SONG_ROWS rows (include/nsid.h nsid_local_align_panels): the workgroup walks the strip once
+// per panel of pcols columns, left to right. The rule reads (i-1, j-1), (i-1, j-2) and (i-2, j-1), so a panel that starts at column c0
+// needs from its left only columns c0 - 2 and c0 - 1 of every row, the two carried ones included: the halo. The two cells in front of
+// each LDS row, zeros in the first panel, hold the halo of that row in every later one. The halo cells of a block of AL_RB rows are
+// loaded during the block before, a cell a thread, and left packed in LDS before that block's last barrier; threads
+// 0 and 1 put them in front of the row being computed and, after the row's barrier, store the row's last two cells over them for the
+// next panel (a row's halo is consumed at least one barrier before it is overwritten). A panel stores the halo of the carried rows
+// before its slice of the carry is overwritten. A row's best key over the panels so far and that cell's origin stay
+// in LDS behind the cells; a later panel replaces them only with a strictly larger H (it has the larger j), and the rows go to memory
+// once, after the last panel. The packing of a cell is the strip kernel's: j0 < 2^16, and i - i0 <= 2 (Lr - 1) <= 32766 < 2^15.
+constexpr int AL_MAX_SONG_ROWS = NSID_ALIGN_MAX_SONG_ROWS;
+static_assert(AL_MAX_SONG_ROWS <= (1 << 16), "a cell's origin column keeps its 16 bits");
+static_assert(2 * (AL_MAX_SONG_ROWS - 1) < AL_I0_MOD, "a cell's origin row is recovered from its low 15 bits: i - i0 <= 2 (Lr - 1)");
+static_assert(3 * (AL_MAX_COLS + 2) * 8 + AL_MAX_ROWS * 12 + 4096 <= NSID_LDS_MAX, "three rows of cells and the strip's row results in LDS");
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void local_align_panels_kernel(
+    const float* __restrict__ S, const int64_t* __restrict__ s_off, const int* __restrict__ s_ld, const int* __restrict__ q_len,
+    const int* __restrict__ x_len, const int* __restrict__ row_base, const int* __restrict__ fresh, int max_q, int max_x, int pcols,
+    float theta, const int64_t* __restrict__ carry_off, float* carry_h, int* carry_i0, int* carry_j0,
+    const int64_t* __restrict__ halo_off, float* halo_h, int* halo_i0, int* halo_j0, const int64_t* __restrict__ row_off,
+    float* __restrict__ row_h, int* __restrict__ row_j, int* __restrict__ row_i0, int* __restrict__ row_j0,
+    float* __restrict__ open_h) {
+  constexpr int NW = THREADS / NSID_WAVE;
+  extern __shared__ __attribute__((aligned(16))) char al_smem[];
+  __shared__ unsigned long long part[2][NW];
+  __shared__ float wmax[NW];
+  __shared__ int2 hst[2][2 * AL_RB];          // the packed halo cells of the current and the next block of rows
+  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
+  const int Lq = q_len[p], Lr = x_len[p], base = row_base[p];
+  const int64_t ro = row_off[p];
+  // every return below is uniform over the workgroup and ahead of every barrier
+  const bool bad = Lq < 0 || Lr < 0 || Lq > max_q || Lr > max_x || base < 0 || (int64_t)base + Lq > 0x7fffffffLL;
+  if (bad || Lr == 0) {                       // as in local_align_strip_kernel
+    const int n = bad ? min(max(Lq, 0), max_q) : Lq;
+    for (int i = tid; i < n; i += THREADS) {
+      row_h[ro + i] = 0.f;
+      row_j[ro + i] = -1;
+      row_i0[ro + i] = -1;
+      row_j0[ro + i] = -1;
+    }
+    if (tid == 0) open_h[p] = bad ? -1.f : 0.f;
+    return;
+  }
+  const float* Sp = S + s_off[p];
+  const size_t ld = (size_t)s_ld[p];
+  const int64_t co = carry_off[p], ho = halo_off[p];
+  const bool carried = fresh[p] == 0;
+  const int cols = pcols + 2;
+
+  // LDS: three rows of cells as in the strip kernel, then per strip row the best key so far and that cell's packed origin
+  int2* cell = reinterpret_cast<int2*>(al_smem);
+  unsigned long long* rkey = reinterpret_cast<unsigned long long*>(cell + 3 * cols);
+  int* rorg = reinterpret_cast<int*>(rkey + max_q);
+  for (int i = tid; i < Lq; i += THREADS) {
+    rkey[i] = 0ull;
+    rorg[i] = -1;
+  }
+  // the halo cell (row, k): column c0 - 2 + k of strip row `row` (-2, -1: the carried rows) for the panel that starts at c0
+  auto halo_load = [&](int row, int k) {
+    const int64_t a = ho + 2 * (int64_t)(row + 2) + k;
+    return int2{__builtin_bit_cast(int, halo_h[a]), al_pack_org(halo_i0[a], halo_j0[a])};
+  };
+  auto halo_store = [&](int row, int k, int2 c) {
+    const int64_t a = ho + 2 * (int64_t)(row + 2) + k;
+    halo_h[a] = __builtin_bit_cast(float, c.x);
+    halo_i0[a] = c.y >= 0 ? al_org_row(base + row, c.y) : -1;
+    halo_j0[a] = c.y >= 0 ? (c.y & 0xffff) : -1;
+  };
+
+  float m = 0.f;
+  for (int c0 = 0; c0 < Lr; c0 += pcols) {
+    const int pw = min(pcols, Lr - c0);                       // only the last panel can be narrower (and only it can have one column)
+    const bool first = c0 == 0, last = c0 + pw >= Lr;
+    for (int t = tid; t < 3 * cols; t += THREADS) {
+      const int r = t / cols, j = t - r * cols - 2;
+      int2 v = int2{0, -1};                                                       // H = +0.0, no origin
+      if (r > 0 && j >= 0) {
+        if (carried && j < pw) {
+          const int64_t a = co + (r == 2 ? 0 : Lr) + c0 + j;
+          v = int2{__builtin_bit_cast(int, carry_h[a]), al_pack_org(carry_i0[a], carry_j0[a])};
+        }
+      } else if (r > 0 && !first) {
+        v = halo_load(r == 2 ? -1 : -2, j + 2);
+      }
+      cell[t] = v;
+    }
+    const bool stage = !first && tid < 2 * AL_RB;              // this thread loads the halo cell (row tid / 2, column tid % 2) of a block
+    if (stage && Lq > 0) hst[0][tid] = halo_load(min(tid >> 1, Lq - 1), tid & 1);
+    __syncthreads();
+    // the carried rows' cells for the next panel, before this panel's slice of the carry is overwritten
+    if (!last && tid < 2) {
+      halo_store(-2, tid, cell[cols + pw + tid]);
+      halo_store(-1, tid, cell[2 * cols + pw + tid]);
+    }
+
+    // between the barriers of rows `row` and `row + 1`: the waves' keys of the row against the row's best of the earlier panels
+    auto combine = [&](int row, const int2* buf) {
+      unsigned long long k = 0;
+#pragma unroll
+      for (int u = 0; u < NW; ++u) {
+        const unsigned long long v = part[row & 1][u];
+        k = v > k ? v : k;
+      }
+      const int j = k ? (int)(0xffffffffu - (unsigned)k) : c0;
+      const int org = buf[j - c0 + 2].y;
+      if (tid == 0 && (k >> 32) > (rkey[row] >> 32)) {
+        rkey[row] = k;
+        rorg[row] = org;
+      }
+      if (!last && tid < 2) halo_store(row, tid, buf[pw + tid]);
+    };
+
+    int2* cur = cell;
+    int2* prev1 = cell + 2 * cols;
+    int2* prev2 = cell + cols;
+    for (int ib = 0; ib < Lq; ib += AL_RB) {
+      float sv[AL_RB][AL_CPT];
+#pragma unroll
+      for (int r = 0; r < AL_RB; ++r) {
+        const float* rp = Sp + (size_t)min(ib + r, Lq - 1) * ld + c0;       // a column past the panel's end reads its last one
+#pragma unroll
+        for (int c = 0; c < AL_CPT; ++c) sv[r][c] = rp[min(tid + c * THREADS, pw - 1)];
+      }
+      const int hb = (ib / AL_RB) & 1;
+      const bool more = stage && ib + AL_RB < Lq;              // the halo of the next block of rows is loaded during this one
+      int2 hnext = int2{0, -1};
+#pragma unroll
+      for (int r = 0; r < AL_RB; ++r) {
+        const int i = ib + r;
+        if (i >= Lq) break;              // uniform
+        if (i > 0) combine(i - 1, prev1);
+        // issued when half of the block's S is consumed (the registers are free by then), stored four rows later
+        if (r == AL_RB / 2 && more) hnext = halo_load(min(ib + AL_RB + (tid >> 1), Lq - 1), tid & 1);
+        const int own = (((base + i) & (AL_I0_MOD - 1)) << 16) | c0;               // a path that starts in this row, at local column 0
+        unsigned long long key = 0;
+        int2 d11[AL_CPT], d12[AL_CPT], d21[AL_CPT];
+#pragma unroll
+        for (int c = 0; c < AL_CPT; ++c) {
+          const int jc = min(tid + c * THREADS, pw - 1);
+          d11[c] = prev1[jc + 1];
+          d12[c] = prev1[jc];
+          d21[c] = prev2[jc + 1];
+        }
+        if (tid < 2) cur[tid] = first ? int2{0, -1} : hst[hb][2 * r + tid];
+        if (r == AL_RB - 1 && more) hst[hb ^ 1][tid] = hnext;                      // read from the next row on, after this row's barrier
+#pragma unroll
+        for (int c = 0; c < AL_CPT; ++c) {
+          const int j = tid + c * THREADS;
+          const float e = sv[r][c] - theta;
+          float best = 0.f;
+          int from = -1;
+          const float h11 = __builtin_bit_cast(float, d11[c].x), h12 = __builtin_bit_cast(float, d12[c].x),
+                      h21 = __builtin_bit_cast(float, d21[c].x);
+          if (h11 > best) {
+            best = h11;
+            from = d11[c].y;
+          }
+          if (h12 > best) {
+            best = h12;
+            from = d12[c].y;
+          }
+          if (h21 > best) {
+            best = h21;
+            from = d21[c].y;
+          }
+          const float v = best + e;
+          const bool pos = v > 0.f;
+          if (j < pw) cur[j + 2] = int2{pos ? __builtin_bit_cast(int, v) : 0, pos ? (from >= 0 ? from : (own + j)) : -1};
+          const unsigned long long k = (j < pw && e > 0.f) ? al_key(v, c0 + j) : 0ull;
+          key = k > key ? k : key;
+        }
+        key = al_wave_key_max(key);
+        if (lane == 0) part[i & 1][w] = key;
+        int2* t = prev2;
+        prev2 = prev1;
+        prev1 = cur;
+        cur = t;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      }
+    }
+    if (Lq > 0) combine(Lq - 1, prev1);
+
+    // the panel's slice of the carry out, as the strip kernel writes the whole of it
+    for (int j = tid; j < pw; j += THREADS) {
+      const int2 c1 = prev1[j + 2], c2 = prev2[j + 2];
+      const float h1 = __builtin_bit_cast(float, c1.x), h2 = __builtin_bit_cast(float, c2.x);
+      m = fmaxf(m, fmaxf(h1, h2));
+      if (Lq > 0) {
+        const int64_t a = co + c0 + j;
+        carry_h[a] = h1;
+        carry_i0[a] = c1.y >= 0 ? al_org_row(base + Lq - 1, c1.y) : -1;
+        carry_j0[a] = c1.y >= 0 ? (c1.y & 0xffff) : -1;
+        carry_h[a + Lr] = h2;
+        carry_i0[a + Lr] = c2.y >= 0 ? al_org_row(base + Lq - 2, c2.y) : -1;
+        carry_j0[a + Lr] = c2.y >= 0 ? (c2.y & 0xffff) : -1;
+      }
+    }
+    __syncthreads();                   // the cells are dead, the halo and the row keys are written: the next panel may start
+  }
+
+  for (int i = tid; i < Lq; i += THREADS) {
+    const unsigned long long k = rkey[i];
+    const int org = rorg[i];
+    const bool has = k != 0 && org >= 0;
+    row_h[ro + i] = __builtin_bit_cast(float, (unsigned)(k >> 32));
+    row_j[ro + i] = k ? (int)(0xffffffffu - (unsigned)k) : -1;
+    row_i0[ro + i] = has ? al_org_row(base + i, org) : -1;
+    row_j0[ro + i] = has ? (org & 0xffff) : -1;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, NSID_WAVE));
+  if (lane == 0) wmax[w] = m;
+  __syncthreads();
+  if (tid == 0) {
+    float v = 0.f;
+    for (int u = 0; u < NW; ++u) v = fmaxf(v, wmax[u]);
+    open_h[p] = v;
+  }
+}
+
+size_t align_panels_lds_bytes(int max_q, int pcols) {
+  return (3 * (size_t)(pcols + 2) * sizeof(int2) + (size_t)max_q * 12 + 15) / 16 * 16;
+}
+
 // ---- align_occurrences ------------------------------------------------------------------------------------------------------------
 // One workgroup per run of rows. A group's rows lie within [i0, i0 + AL_SPAN], so a row is its group's representative when no row of
 // that window with the same origin beats it; the kept rows are one bit each in LDS (a wave's ballot per 64 rows), and a kept row's rank
-// is a walk over the set bits. The rows themselves are read from memory (they stay in the caches).
+// is a walk over the set bits. The rows themselves are read from memory (they stay in the caches). span: per run the width of that
+// window (nsid_align_occurrences_span: 2 (x_len - 1) for a song of x_len rows); null = AL_SPAN, the bound of a song of AL_MAX_COLS rows.
 constexpr int AL_OCC_THREADS = 1024;
 static_assert(NSID_ALIGN_OCC_MAX_ROWS / 8 + 4096 <= NSID_LDS_MAX, "one bit per row of the longest run in LDS");
 
 __global__ __launch_bounds__(AL_OCC_THREADS) void align_occurrences_kernel(
     const float* __restrict__ row_h, const int* __restrict__ row_j, const int* __restrict__ row_i0, const int* __restrict__ row_j0,
-    const int64_t* __restrict__ row_off, const int* __restrict__ n_rows, const int* __restrict__ first_row, int max_rows,
-    float min_score, int top, int* __restrict__ occ, float* __restrict__ occ_score, int* __restrict__ n_occ) {
+    const int64_t* __restrict__ row_off, const int* __restrict__ n_rows, const int* __restrict__ first_row,
+    const int* __restrict__ span, int max_rows, float min_score, int top, int* __restrict__ occ, float* __restrict__ occ_score,
+    int* __restrict__ n_occ) {
   constexpr int NW = AL_OCC_THREADS / NSID_WAVE;
   extern __shared__ __attribute__((aligned(16))) unsigned al_keep[];
   __shared__ int o_occ[AL_MAX_TOP][4];
   __shared__ float o_sc[AL_MAX_TOP];
   __shared__ int wcnt[NW];
   const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
-  const int n = n_rows[p], first = first_row[p];
+  const int n = n_rows[p], first = first_row[p], sp = span ? span[p] : AL_SPAN;
   // every return below is uniform over the workgroup and ahead of every barrier
-  if (n < 0 || n > max_rows || first < 0 || (int64_t)first + n > 0x7fffffffLL) {
+  if (n < 0 || n > max_rows || first < 0 || (int64_t)first + n > 0x7fffffffLL || sp < 0) {
     al_empty(p, top, -1, tid, occ, occ_score, n_occ);
     return;
   }
@@ -575,7 +810,7 @@ __global__ __launch_bounds__(AL_OCC_THREADS) void align_occurrences_kernel(
       const int gi = ri[i], gj = rc[i];
       const float hi = rh[i];
       rep = gi >= 0 && hi >= min_score;
-      const int64_t lo = max((int64_t)0, (int64_t)gi - first), last = min((int64_t)n - 1, (int64_t)gi + AL_SPAN - first);
+      const int64_t lo = max((int64_t)0, (int64_t)gi - first), last = min((int64_t)n - 1, (int64_t)gi + sp - first);
       for (int64_t a0 = lo; a0 <= last && rep; a0 += AL_CHUNK) {
         bool hit = false;
 #pragma unroll
@@ -708,23 +943,77 @@ extern "C" int nsid_local_align_strip(const float* S, const int64_t* s_off, cons
                                   carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
 }
 
-extern "C" int nsid_align_occurrences(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0,
-                                      const int64_t* row_off, const int* n_rows, const int* first_row, int npairs, int max_rows,
-                                      float min_score, int top, int* occ, float* occ_score, int* n_occ, void* stream) {
+namespace {
+int align_occurrences_launch(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0, const int64_t* row_off,
+                             const int* n_rows, const int* first_row, const int* span, bool with_span, int npairs, int max_rows,
+                             float min_score, int top, int* occ, float* occ_score, int* n_occ, void* stream) {
   NSID_REQUIRE(npairs >= 0 && max_rows >= 0 && max_rows <= NSID_ALIGN_OCC_MAX_ROWS && top >= 1 && top <= AL_MAX_TOP &&
                min_score == min_score);
   if (npairs == 0) return NSID_OK;
-  NSID_REQUIRE(row_off && n_rows && first_row && occ && occ_score && n_occ);
+  NSID_REQUIRE(row_off && n_rows && first_row && occ && occ_score && n_occ && (!with_span || span));
   NSID_REQUIRE(max_rows == 0 || (row_h && row_j && row_i0 && row_j0));
   NSID_REQUIRE(al_aligned(row_off, 8));
   for (const void* q : {(const void*)row_h, (const void*)row_j, (const void*)row_i0, (const void*)row_j0, (const void*)n_rows,
-                        (const void*)first_row, (const void*)occ, (const void*)occ_score, (const void*)n_occ})
+                        (const void*)first_row, (const void*)span, (const void*)occ, (const void*)occ_score, (const void*)n_occ})
     NSID_REQUIRE(al_aligned(q, 4));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const size_t lds = ((size_t)(max_rows + NSID_WAVE - 1) / NSID_WAVE * 8 + 15) / 16 * 16;
-  nsid_count(NSID_C_align_occurrences);
+  nsid_count(with_span ? NSID_C_align_occurrences_span : NSID_C_align_occurrences);
   nsid_took("align_occurrences_kernel");
   NSID_LAUNCH_LDS(align_occurrences_kernel, dim3(npairs), dim3(AL_OCC_THREADS), lds, st, row_h, row_j, row_i0, row_j0, row_off, n_rows,
-                  first_row, max_rows, min_score, top, occ, occ_score, n_occ);
+                  first_row, span, max_rows, min_score, top, occ, occ_score, n_occ);
+  return nsid_launch_status();
+}
+}  // namespace
+
+extern "C" int nsid_align_occurrences(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0,
+                                      const int64_t* row_off, const int* n_rows, const int* first_row, int npairs, int max_rows,
+                                      float min_score, int top, int* occ, float* occ_score, int* n_occ, void* stream) {
+  return align_occurrences_launch(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, nullptr, false, npairs, max_rows, min_score,
+                                  top, occ, occ_score, n_occ, stream);
+}
+
+extern "C" int nsid_align_occurrences_span(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0,
+                                           const int64_t* row_off, const int* n_rows, const int* first_row, const int* span,
+                                           int npairs, int max_rows, float min_score, int top, int* occ, float* occ_score, int* n_occ,
+                                           void* stream) {
+  return align_occurrences_launch(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, span, true, npairs, max_rows, min_score, top,
+                                  occ, occ_score, n_occ, stream);
+}
+
+extern "C" int nsid_local_align_panels(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len,
+                                       const int* row_base, const int* fresh, int npairs, int max_q_len, int max_x_len, int panel_cols,
+                                       float theta, const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0,
+                                       const int64_t* halo_off, float* halo_h, int* halo_i0, int* halo_j0, const int64_t* row_off,
+                                       float* row_h, int* row_j, int* row_i0, int* row_j0, float* open_h, void* stream) {
+  NSID_REQUIRE(npairs >= 0 && max_q_len >= 0 && max_q_len <= AL_MAX_ROWS && max_x_len >= 0 && max_x_len <= AL_MAX_SONG_ROWS &&
+               panel_cols >= 2 && panel_cols <= AL_MAX_COLS && theta == theta);
+  if (npairs == 0) return NSID_OK;
+  NSID_REQUIRE(s_off && s_ld && q_len && x_len && row_base && fresh && carry_off && halo_off && row_off && open_h);
+  NSID_REQUIRE(halo_h && halo_i0 && halo_j0);                 // every pair has the two carried rows' cells
+  NSID_REQUIRE(max_q_len == 0 || (row_h && row_j && row_i0 && row_j0));
+  NSID_REQUIRE(max_x_len == 0 || (carry_h && carry_i0 && carry_j0));
+  NSID_REQUIRE((max_q_len == 0 || max_x_len == 0) || S);
+  NSID_REQUIRE(al_aligned(s_off, 8) && al_aligned(carry_off, 8) && al_aligned(halo_off, 8) && al_aligned(row_off, 8));
+  for (const void* q : {(const void*)S, (const void*)s_ld, (const void*)q_len, (const void*)x_len, (const void*)row_base,
+                        (const void*)fresh, (const void*)carry_h, (const void*)carry_i0, (const void*)carry_j0, (const void*)halo_h,
+                        (const void*)halo_i0, (const void*)halo_j0, (const void*)row_h, (const void*)row_j, (const void*)row_i0,
+                        (const void*)row_j0, (const void*)open_h})
+    NSID_REQUIRE(al_aligned(q, 4));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t lds = align_panels_lds_bytes(max_q_len, panel_cols);
+  nsid_count(NSID_C_local_align_panels);
+  // 256 threads own every column of a panel up to 1024; above that 1024 threads do (the results do not depend on it)
+  if (panel_cols <= 256 * AL_CPT) {
+    nsid_took("local_align_panels_kernel<256>");
+    NSID_LAUNCH_LDS((local_align_panels_kernel<256>), dim3(npairs), dim3(256), lds, st, S, s_off, s_ld, q_len, x_len, row_base, fresh,
+                    max_q_len, max_x_len, panel_cols, theta, carry_off, carry_h, carry_i0, carry_j0, halo_off, halo_h, halo_i0, halo_j0,
+                    row_off, row_h, row_j, row_i0, row_j0, open_h);
+    return nsid_launch_status();
+  }
+  nsid_took("local_align_panels_kernel<1024>");
+  NSID_LAUNCH_LDS((local_align_panels_kernel<1024>), dim3(npairs), dim3(1024), lds, st, S, s_off, s_ld, q_len, x_len, row_base, fresh,
+                  max_q_len, max_x_len, panel_cols, theta, carry_off, carry_h, carry_i0, carry_j0, halo_off, halo_h, halo_i0, halo_j0,
+                  row_off, row_h, row_j, row_i0, row_j0, open_h);
   return nsid_launch_status();
 }

@@ -40,9 +40,16 @@ the score eval.py:249-258 leaves to "future implementations"), which sees it any
 
     occs = idx.scan(wave=recording, threshold=0.6, min_score=2.0, vote="diagonal")
 
-Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs past 4096 rows, and queries
-past 4096 rows outside scan (refused, not split), gap steps other than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated
-on real audio, parsing sample100-ext's annotation files."""
+Songs of more than 4096 rows (about 35 minutes: a mix, a live set, an audiobook chapter) are columns of the alignment only in an index
+made with long_songs=True, up to 16384 rows (2 h 19 min; the bound under which a cell of the walk keeps its 8 bytes, include/nsid.h
+nsid_local_align_panels). The walk then goes over the song in panels of 4096 columns and over a long query in strips of 4096 rows.
+
+    idx = SampleIndex(model, long_songs=True)
+
+Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs past 16384 rows (past 4096
+without long_songs), queries past that outside scan (refused, not split), rerank=True against a song past 4096 rows, gap steps other
+than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated on real audio, parsing sample100-ext's
+annotation files."""
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -158,15 +165,22 @@ class SampleIndex:
     CrossAttentionClassifier for rerank=True and match_score; front: LogMelFrontEnd / CQTFrontEnd, needed only for waveforms.
     model may be None for an index fed with precomputed rows only (add_rows, identify(fp=...)); then d is taken from the first
     rows. prefilter: the index's searches (identify, identify_pairs, locate, links) run through FlatL2Index's certified bf16
-    pre-filter; the results are the same bits."""
+    pre-filter; the results are the same bits. long_songs: align, locate, scan / scanner and links take resident songs of up to
+    ops.ALIGN_MAX_SONG_ROWS rows as columns (align / locate also such queries, links such songs as queries) instead of
+    ops.ALIGN_MAX_COLS; False is the behaviour without the argument in every respect."""
 
-    def __init__(self, model, classifier=None, front=None, device="cuda", micro_batch: int = 1024, prefilter: bool = False):
+    def __init__(self, model, classifier=None, front=None, device="cuda", micro_batch: int = 1024, prefilter: bool = False,
+                 long_songs: bool = False):
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SampleIndex runs on the MI355X (cuda) device; there is no CPU path")
         self.model, self.classifier, self.front = model, classifier, front
         self.micro_batch = int(micro_batch)
         self.prefilter = bool(prefilter)
+        self.long_songs = bool(long_songs)
+        # the most rows of a song as the columns, and of a query, of the alignment
+        self._max_cols = ops.ALIGN_MAX_SONG_ROWS if self.long_songs else ops.ALIGN_MAX_COLS
+        self._max_q = ops.ALIGN_MAX_SONG_ROWS if self.long_songs else ops.ALIGN_MAX_ROWS
         self.names: List[str] = []
         self._code = {}
         self._song_rows = []                  # per song: (first ref row, rows, rows with node matrices)
@@ -568,8 +582,9 @@ class SampleIndex:
             raise ValueError(f"{what}: threshold has no default for fingerprint scores (the reference has no such number and none has "
                              "been measured on real audio): pass one, or use rerank=True")
         self._check_fp(fp, what, device=False)
-        if fp.shape[0] > ops.ALIGN_MAX_ROWS:
-            raise ValueError(f"{what}: a query of {fp.shape[0]} rows is past the limit of {ops.ALIGN_MAX_ROWS}; longer inputs are refused, "
+        max_q = ops.ALIGN_MAX_ROWS if rerank else self._max_q
+        if fp.shape[0] > max_q:
+            raise ValueError(f"{what}: a query of {fp.shape[0]} rows is past the limit of {max_q}; longer inputs are refused, "
                              "not split")
         top = int(top)
         if not 1 <= top <= ops.ALIGN_MAX_TOP:
@@ -577,10 +592,11 @@ class SampleIndex:
         if isinstance(songs, str):
             raise TypeError(f"{what}: songs must be a sequence of names, not one string")
         codes = [self.code(s) for s in songs]
+        max_cols = ops.ALIGN_MAX_COLS if rerank else self._max_cols          # the classifier's cells go through local_align alone
         for c in codes:
-            if self._song_rows[c][1] > ops.ALIGN_MAX_COLS:
+            if self._song_rows[c][1] > max_cols:
                 raise ValueError(f"{what}: song {self.names[c]!r} has {self._song_rows[c][1]} rows, past the limit of "
-                                 f"{ops.ALIGN_MAX_COLS}; longer inputs are refused, not split")
+                                 f"{max_cols}; longer inputs are refused, not split")
         if rerank:
             if nodes is None:
                 raise ValueError(f"{what}: rerank=True needs the query's node matrices")
@@ -609,7 +625,13 @@ class SampleIndex:
         of (query row, song row with node matrices) pairs, the song rows without node matrices are not columns, and threshold defaults
         to CLF_THRESHOLD. Returns a list of Occurrence lists, one per song, best first; with return_rows=True also a dict of the per-row
         tensors and the S used, per chunk: {"chunks": [(codes, S, s_off, s_ld, x_len, row_h, row_j, row_org, row_off, occ, occ_score,
-        n_occ), ...]}."""
+        n_occ), ...]}.
+
+        long_songs: a pair with more than ALIGN_MAX_ROWS query rows or more than ALIGN_MAX_COLS song rows goes through
+        local_align_panels in strips of ALIGN_MAX_ROWS query rows chained through the carry, then align_occurrences with its span; the
+        workspace is then per strip. Such pairs are reported in chunks of their own, whose tuples are (codes, S, s_off, s_ld, x_len,
+        row_h, row_j, row_i0, row_j0, row_off, occ, occ_score, n_occ): the origin unpacked (row_i0, row_j0) where the others have
+        row_org, and S, s_off, s_ld as lists with one entry per strip. Refused with rerank=True."""
         timing = self._row_timing(row_hop_s, row_len_s)
         codes, threshold = self._align_checks("align", fp, songs, threshold, top, nodes, rerank)
         Lq, top = int(fp.shape[0]), int(top)
@@ -618,9 +640,17 @@ class SampleIndex:
         if Lq == 0 or not codes:
             return (out, {"chunks": chunks}) if return_rows else out
         fp = fp.contiguous()
-        if rerank:
-            qproj = self._project(self.classifier.project_queries, nodes)
-        x_len_all = [self._song_rows[c][2 if rerank else 1] for c in codes]
+        if not rerank:
+            occ, sc = self._align_pairs(fp, np.zeros(len(codes), np.int64), np.full(len(codes), Lq, np.int64), codes, threshold,
+                                        min_score, top, int(s_budget_bytes), chunks if return_rows else None)
+            for p, c in enumerate(codes):
+                for (i0, i1, j0, j1), s in zip(occ[p].tolist(), sc[p].tolist()):
+                    if i0 < 0:
+                        break
+                    out[p].append(_occurrence(self.names[c], s, i0, i1, j0, j1, timing))
+            return (out, {"chunks": chunks}) if return_rows else out
+        qproj = self._project(self.classifier.project_queries, nodes)
+        x_len_all = [self._song_rows[c][2] for c in codes]
         lo = 0
         while lo < len(codes):
             hi, used = lo, 0
@@ -631,14 +661,11 @@ class SampleIndex:
             x_start = np.asarray([self._song_rows[c][0] for c in part], dtype=np.int64)
             x_len = np.asarray(x_len_all[lo:hi], dtype=np.int64)
             q_len = np.full(len(part), Lq, dtype=np.int64)
-            if rerank:
-                cand = np.concatenate([np.arange(s, s + n) for s, n in zip(x_start.tolist(), x_len.tolist())]) if x_len.sum() else \
-                    np.zeros(0, dtype=np.int64)
-                S, s_off = self.classifier.score_blocks(qproj, self._kp[: self.n_ref * self.N], self.N, np.zeros(len(part), np.int64),
-                                                        q_len, cand, np.cumsum(x_len) - x_len, x_len)
-                s_off, s_ld = np.asarray(s_off, dtype=np.int64), x_len
-            else:
-                S, s_off, s_ld = ops.pair_sim(fp, self.fingerprints, np.zeros(len(part), np.int64), q_len, x_start, x_len)
+            cand = np.concatenate([np.arange(s, s + n) for s, n in zip(x_start.tolist(), x_len.tolist())]) if x_len.sum() else \
+                np.zeros(0, dtype=np.int64)
+            S, s_off = self.classifier.score_blocks(qproj, self._kp[: self.n_ref * self.N], self.N, np.zeros(len(part), np.int64),
+                                                    q_len, cand, np.cumsum(x_len) - x_len, x_len)
+            s_off, s_ld = np.asarray(s_off, dtype=np.int64), x_len
             res = ops.local_align(S, s_off, s_ld, q_len, x_len, threshold, min_score, top)
             occ, sc = res[0].cpu().numpy(), res[1].cpu().numpy()
             for p, c in enumerate(part):
@@ -649,6 +676,68 @@ class SampleIndex:
             chunks.append((part, S, s_off, s_ld, x_len) + tuple(res[3:]) + tuple(res[:3]))
             lo = hi
         return (out, {"chunks": chunks}) if return_rows else out
+
+    def _align_pairs(self, q, q_start, q_len, codes, threshold, min_score, top, budget, chunks=None):
+        """The alignment of pairs (rows q_start[p] .. + q_len[p] of q, resident song codes[p]) over fingerprint scores, for align and
+        links: (occ (pairs, top, 4), occ_score (pairs, top)) on the host. Consecutive pairs go in chunks whose score workspace stays
+        under `budget` bytes (one pair is always allowed). A chunk of pairs within ALIGN_MAX_ROWS x ALIGN_MAX_COLS is one pair_sim and
+        one local_align; a chunk of longer pairs (long_songs) goes strip by strip of ALIGN_MAX_ROWS query rows, all its pairs in one
+        pair_sim and one local_align_panels per strip, the first fresh and the others from the carry, and then through
+        align_occurrences with the span 2 (x_len - 1); its workspace is that of one strip. chunks: a list that receives align's
+        return_rows tuples."""
+        ref = self.fingerprints
+        P = len(codes)
+        x_start_all = np.asarray([self._song_rows[c][0] for c in codes], dtype=np.int64)
+        x_len_all = np.asarray([self._song_rows[c][1] for c in codes], dtype=np.int64)
+        strip_all = np.minimum(q_len, ops.ALIGN_MAX_ROWS)
+        long = (q_len > ops.ALIGN_MAX_ROWS) | (x_len_all > ops.ALIGN_MAX_COLS)
+        occ_all = np.full((P, top, 4), -1, dtype=np.int32)
+        sc_all = np.zeros((P, top), dtype=np.float32)
+        lo = 0
+        while lo < P:
+            hi, used = lo, 0
+            while hi < P and long[hi] == long[lo]:
+                cells = 4 * int(strip_all[hi]) * int(x_len_all[hi])
+                if hi > lo and used + cells > budget:
+                    break
+                used += cells
+                hi += 1
+            qs, ql, x_start, x_len = q_start[lo:hi], q_len[lo:hi], x_start_all[lo:hi], x_len_all[lo:hi]
+            if not long[lo]:
+                S, s_off, s_ld = ops.pair_sim(q, ref, qs, ql, x_start, x_len)
+                res = ops.local_align(S, s_off, s_ld, ql, x_len, threshold, min_score, top)
+                if chunks is not None:
+                    chunks.append((list(codes[lo:hi]), S, s_off, s_ld, x_len) + tuple(res[3:]) + tuple(res[:3]))
+            else:
+                res, kept = self._align_strips(q, ref, qs, ql, x_start, x_len, threshold, min_score, top, chunks is not None)
+                if chunks is not None:
+                    chunks.append((list(codes[lo:hi]),) + kept + (x_len,) + tuple(res[3:]) + tuple(res[:3]))
+            occ_all[lo:hi], sc_all[lo:hi] = res[0].cpu().numpy(), res[1].cpu().numpy()
+            lo = hi
+        return occ_all, sc_all
+
+    def _align_strips(self, q, ref, q_start, q_len, x_start, x_len, threshold, min_score, top, keep):
+        """one chunk of long pairs: ((occ, occ_score, n_occ, row_h, row_j, row_i0, row_j0, row_off), (S, s_off, s_ld lists per strip))"""
+        dev, R = q.device, ops.ALIGN_MAX_ROWS
+        carry, carry_off = ops.align_carry(x_len, dev, long_songs=True)
+        row_off = np.cumsum(q_len) - q_len
+        total = int(q_len.sum())
+        rows = (torch.empty((total,), device=dev, dtype=torch.float32),) + tuple(
+            torch.empty((total,), device=dev, dtype=torch.int32) for _ in range(3))
+        kept = ([], [], [])
+        for lo in range(0, int(q_len.max()), R):
+            n = np.clip(q_len - lo, 0, R)
+            on = n > 0
+            S, s_off, s_ld = ops.pair_sim(q, ref, q_start[on] + lo, n[on], x_start[on], x_len[on], long_songs=True)
+            ops.local_align_panels(S, s_off, s_ld, n[on], x_len[on], threshold, np.full(int(on.sum()), lo, np.int64),
+                                   np.full(int(on.sum()), 1 if lo == 0 else 0, np.int64), carry, carry_off[on], rows=rows,
+                                   row_off=row_off[on] + lo)
+            if keep:
+                for u, v in zip(kept, (S, s_off, s_ld)):
+                    u.append(v)
+        occ = ops.align_occurrences(*rows, row_off, q_len, np.zeros(len(q_len), np.int64), min_score, top,
+                                    span=np.maximum(2 * (x_len - 1), 0))
+        return tuple(occ) + rows + (row_off,), kept
 
     @torch.no_grad()
     def locate(self, specs=None, wave=None, fp=None, nodes=None, songs: Optional[Sequence[str]] = None, k_probe: int = 20,
@@ -693,8 +782,9 @@ class SampleIndex:
         fp, nodes = self._query(specs, wave, fp, nodes, rerank)
         if songs is None:
             self._check_fp(fp, "locate", device=False)
-            if fp.shape[0] > ops.ALIGN_MAX_ROWS:
-                raise ValueError(f"locate: a query of {fp.shape[0]} rows is past the limit of {ops.ALIGN_MAX_ROWS}; longer inputs are "
+            max_q = ops.ALIGN_MAX_ROWS if rerank else self._max_q
+            if fp.shape[0] > max_q:
+                raise ValueError(f"locate: a query of {fp.shape[0]} rows is past the limit of {max_q}; longer inputs are "
                                  "refused, not split")
             songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank, leave_out, vote, bin_rows, min_hits)
         per_song = self.align(fp, songs, threshold, min_score, top, nodes, rerank, row_hop_s=row_hop_s, row_len_s=row_len_s)
@@ -744,7 +834,8 @@ class SampleIndex:
         row index, so the result depends on the rows alone. The alignment is locate's rule, carried from window to window
         (ops.local_align_strip): a path that crosses a window boundary is one occurrence, found once. See Scanner for the active-set
         and run rules. songs=[names]: exactly these songs are aligned in every window and nothing is voted (the streaming form of
-        align). exclude: a song name that never votes. threshold has no default, as in align. vote="diagonal", bin_rows, min_hits:
+        align). exclude: a song name that never votes. threshold has no default, as in align. With long_songs a window whose active
+        songs include one of more than ALIGN_MAX_COLS rows goes through local_align_panels. vote="diagonal", bin_rows, min_hits:
         locate's (the window's vote is diag_votes', so an excerpt that starts deep inside a window, or lies wholly inside one, is
         aligned in that window). Every refusal comes before any launch."""
         vote, bin_rows, min_hits = _vote_options("scanner", vote, bin_rows, min_hits)
@@ -780,8 +871,8 @@ class SampleIndex:
                        max_active, self._row_timing(row_hop_s, row_len_s), vote, bin_rows, min_hits)
 
     def _scan_song_ok(self, c):
-        if self._song_rows[c][1] > ops.ALIGN_MAX_COLS:
-            raise ValueError(f"scanner: song {self.names[c]!r} has {self._song_rows[c][1]} rows, past the limit of {ops.ALIGN_MAX_COLS}; "
+        if self._song_rows[c][1] > self._max_cols:
+            raise ValueError(f"scanner: song {self.names[c]!r} has {self._song_rows[c][1]} rows, past the limit of {self._max_cols}; "
                              "longer inputs are refused, not split")
 
     @torch.no_grad()
@@ -813,7 +904,7 @@ class SampleIndex:
 
         skipped: the songs of more than ALIGN_MAX_ROWS rows, which are not queried, and those of more than ALIGN_MAX_COLS rows, which
         are no candidates either (they are dropped from a song's candidate list before it is cut to n_songs, where locate would refuse
-        the call); both limits stay. threshold has no default, as in locate. There is no rerank here: the index keeps the candidates'
+        the call); with long_songs both limits are ALIGN_MAX_SONG_ROWS, and a long song is queried in strips (align). threshold has no default, as in locate. There is no rerank here: the index keeps the candidates'
         [K | P] rows, not the queries' projection, so a song's rows cannot be the classifier's query side.
 
         vote="diagonal", bin_rows, min_hits: locate's; the block's windows go through one diag_vote instead of seq_scores + song_vote,
@@ -843,9 +934,9 @@ class SampleIndex:
         if self.n_ref == 0:
             raise RuntimeError("SampleIndex: the index holds no song")
         rows_of = [n for _, n, _ in self._song_rows]
-        too_long = {c for c, n in enumerate(rows_of) if n > ops.ALIGN_MAX_COLS}
-        skipped = [self.names[c] for c in codes if rows_of[c] > ops.ALIGN_MAX_ROWS or c in too_long]
-        query = [c for c in codes if rows_of[c] <= ops.ALIGN_MAX_ROWS and c not in too_long]
+        too_long = {c for c, n in enumerate(rows_of) if n > self._max_cols}
+        skipped = [self.names[c] for c in codes if rows_of[c] > self._max_q or c in too_long]
+        query = [c for c in codes if rows_of[c] <= self._max_q and c not in too_long]
         out = {self.names[c]: [] for c in query}
         vote_top = min(ops.VOTE_MAX_TOP, max(n_songs, 1))
         lo = 0
@@ -886,29 +977,14 @@ class SampleIndex:
             order = self._best_songs(codes[mine].reshape(-1).tolist(), totals[mine].reshape(-1).tolist())
             pairs += [(b, c) for c in [c for c in order if c not in too_long][:n_songs]]
         found = {b: [] for b in range(len(block))}
-        lo = 0
-        while lo < len(pairs):
-            hi, used = lo, 0
-            while hi < len(pairs):
-                cells = 4 * int(count[pairs[hi][0]]) * self._song_rows[pairs[hi][1]][1]
-                if hi > lo and used + cells > budget:
+        occ, sc = self._align_pairs(ref, np.asarray([first[b] for b, _ in pairs], dtype=np.int64),
+                                    np.asarray([count[b] for b, _ in pairs], dtype=np.int64), [c for _, c in pairs], threshold, min_score,
+                                    top, budget)
+        for p, (b, c) in enumerate(pairs):
+            for n, ((i0, i1, j0, j1), s) in enumerate(zip(occ[p].tolist(), sc[p].tolist())):
+                if i0 < 0:
                     break
-                used += cells
-                hi += 1
-            part = pairs[lo:hi]
-            q_start = np.asarray([first[b] for b, _ in part], dtype=np.int64)
-            q_len = np.asarray([count[b] for b, _ in part], dtype=np.int64)
-            x_start = np.asarray([self._song_rows[c][0] for _, c in part], dtype=np.int64)
-            x_len = np.asarray([self._song_rows[c][1] for _, c in part], dtype=np.int64)
-            S, s_off, s_ld = ops.pair_sim(ref, ref, q_start, q_len, x_start, x_len)
-            res = ops.local_align(S, s_off, s_ld, q_len, x_len, threshold, min_score, top)
-            occ, sc = res[0].cpu().numpy(), res[1].cpu().numpy()
-            for p, (b, c) in enumerate(part):
-                for n, ((i0, i1, j0, j1), s) in enumerate(zip(occ[p].tolist(), sc[p].tolist())):
-                    if i0 < 0:
-                        break
-                    found[b].append((_occurrence(self.names[c], s, i0, i1, j0, j1, timing), lo + p, n))
-            lo = hi
+                found[b].append((_occurrence(self.names[c], s, i0, i1, j0, j1, timing), p, n))
         for b, c in enumerate(block):                             # locate's order: by score, then candidate rank, then occurrence rank
             found[b].sort(key=lambda t: (-t[0].score, t[1], t[2]))
             out[self.names[c]] = [t[0] for t in found[b]]
@@ -916,7 +992,7 @@ class SampleIndex:
 
 class CatalogueLinks(NamedTuple):
     occurrences: dict                             # {song name: [Occurrence], as locate(fp=its rows, leave_out=name) returns them}
-    skipped: List[str]                            # songs past ALIGN_MAX_ROWS / ALIGN_MAX_COLS rows: not queried, no candidates
+    skipped: List[str]                            # songs past ALIGN_MAX_ROWS / ALIGN_MAX_COLS rows (long_songs: ALIGN_MAX_SONG_ROWS): not queried, no candidates
 
 
 class Scanner:
@@ -935,7 +1011,10 @@ class Scanner:
     its winning bin; with the sequence vote vote_hints is empty.
     stats: windows, strips (pairs aligned), runs, rows, closed_at_cap. runs (after finish): per run a dict with song, code, first_row,
     n_rows and the device row results row_h, row_j, row_i0, row_j0.
-    Not here: rerank cells, leave_out, songs of more than ALIGN_MAX_COLS rows, a streaming front end, hipGraph capture, several GPUs;
+    With long_songs the carry pool has ALIGN_MAX_SONG_ROWS columns per slot, a window with a song of more than ALIGN_MAX_COLS rows among
+    its active ones is one local_align_panels launch instead, and finish() gives align_occurrences every run's span.
+    Not here: rerank cells, leave_out, songs of more than ALIGN_MAX_COLS rows (long_songs: ALIGN_MAX_SONG_ROWS), a streaming front end,
+    hipGraph capture, several GPUs;
     a run is at most ops.ALIGN_OCC_MAX_ROWS rows."""
 
     def __init__(self, index, fixed, threshold, min_score, k, n_songs, top, W, exclude, max_active, timing, vote="sequence",
@@ -977,7 +1056,7 @@ class Scanner:
     def _carry_pool(self):
         if self._pool is None:
             slots = max(self._max_active, len(self._fixed or ()))
-            self._pool, _ = ops.align_carry([ops.ALIGN_MAX_COLS] * slots, self.index.device)
+            self._pool, _ = ops.align_carry([self.index._max_cols] * slots, self.index.device, long_songs=self.index.long_songs)
             self._free = list(range(slots - 1, -1, -1))
         return self._pool
 
@@ -1026,10 +1105,11 @@ class Scanner:
             x_start = np.asarray([idx._song_rows[c][0] for c in want], dtype=np.int64)
             x_len = np.asarray([idx._song_rows[c][1] for c in want], dtype=np.int64)
             q_len = np.full(P, n, dtype=np.int64)
-            S, s_off, s_ld = ops.pair_sim(rows, idx.fingerprints, np.zeros(P, np.int64), q_len, x_start, x_len)
-            carry_off = np.asarray([self._slot[c] for c in want], dtype=np.int64) * (2 * ops.ALIGN_MAX_COLS)
-            *res, row_off, oh = ops.local_align_strip(S, s_off, s_ld, q_len, x_len, self._theta, np.full(P, start, np.int64), fresh,
-                                                      pool, carry_off)
+            panels = bool((x_len > ops.ALIGN_MAX_COLS).any())              # a long song among them: every pair in one panels launch
+            S, s_off, s_ld = ops.pair_sim(rows, idx.fingerprints, np.zeros(P, np.int64), q_len, x_start, x_len, long_songs=panels)
+            carry_off = np.asarray([self._slot[c] for c in want], dtype=np.int64) * (2 * idx._max_cols)
+            strip = ops.local_align_panels if panels else ops.local_align_strip
+            *res, row_off, oh = strip(S, s_off, s_ld, q_len, x_len, self._theta, np.full(P, start, np.int64), fresh, pool, carry_off)
             open_h = oh.cpu().numpy().astype(np.float64).tolist()
             for p, c in enumerate(want):
                 self._run[c][1].append((res, int(row_off[p]), n))
@@ -1059,7 +1139,10 @@ class Scanner:
             n_rows = np.asarray([sum(n for _, _, n in parts) for _, _, parts in runs], dtype=np.int64)
             row_off = np.cumsum(n_rows) - n_rows
             first = np.asarray([f for _, f, _ in runs], dtype=np.int64)
-            occ, sc, _ = ops.align_occurrences(*flat, row_off, n_rows, first, self._min_score, self._top)
+            span = None
+            if self.index.long_songs:
+                span = np.asarray([max(2 * (self.index._song_rows[c][1] - 1), 0) for c, _, _ in runs], dtype=np.int64)
+            occ, sc, _ = ops.align_occurrences(*flat, row_off, n_rows, first, self._min_score, self._top, span=span)
             occ, sc = occ.cpu().numpy(), sc.cpu().numpy()
             for r, (c, f, _) in enumerate(runs):
                 lo, hi = int(row_off[r]), int(row_off[r] + n_rows[r])

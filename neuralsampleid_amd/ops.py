@@ -2147,6 +2147,7 @@ def vote_candidates(I, n_dummy, n_ref) -> torch.Tensor:
 ALIGN_MAX_ROWS = _H["NSID_ALIGN_MAX_ROWS"]        # query rows of a pair at most
 ALIGN_MAX_COLS = _H["NSID_ALIGN_MAX_COLS"]        # song rows of a pair at most
 ALIGN_MAX_TOP = _H["NSID_ALIGN_MAX_TOP"]
+ALIGN_MAX_SONG_ROWS = _H["NSID_ALIGN_MAX_SONG_ROWS"]   # song rows of a pair at most where the walk goes in column panels (local_align_panels)
 ALIGN_TILE = 32                                   # pair_sim's tiles (one wave each)
 
 
@@ -2173,23 +2174,25 @@ def pair_sim_tiles(q_len, x_len) -> np.ndarray:
     return np.stack([pair, (local // w) * ALIGN_TILE, (local % w) * ALIGN_TILE], axis=1).astype(np.int32)
 
 
-def pair_sim(q, x, q_start, q_len, x_start, x_len, s_ld=None, out=None):
+def pair_sim(q, x, q_start, q_len, x_start, x_len, s_ld=None, out=None, long_songs=False):
     """The score matrices of many (query rows, song rows) pairs in one launch: S_p[i, j] = q[q_start[p] + i] . x[x_start[p] + j], the
     dot of flat_l2_topk (one k-ordered fp32 fmaf chain; an element's bits depend on its two rows alone).
 
     q (nq, d), x (nx, d): fp32 rows as the search takes them. q_start / q_len / x_start / x_len: host integer sequences, one entry per
     pair, checked here and then uploaded; lengths may be 0, and are at most ALIGN_MAX_ROWS / ALIGN_MAX_COLS. s_ld: per pair the row
     stride of its block (default x_len). out: a flat fp32 device tensor to write into (default: a new one; what lies between x_len
-    and s_ld is not written). Returns (S flat fp32, s_off int64 numpy, s_ld int64 numpy): pair p's block starts at S[s_off[p]]."""
+    and s_ld is not written). long_songs=True: x_len may be up to ALIGN_MAX_SONG_ROWS (the kernel has no width limit; the matrices
+    are local_align_panels' input). Returns (S flat fp32, s_off int64 numpy, s_ld int64 numpy): pair p's block starts at S[s_off[p]]."""
+    max_cols = ALIGN_MAX_SONG_ROWS if long_songs else ALIGN_MAX_COLS
     q_start = _align_seq("pair_sim", "q_start", q_start)
     npairs = q_start.size
     q_len, x_start, x_len = (_align_seq("pair_sim", w, v, npairs) for w, v in (("q_len", q_len), ("x_start", x_start), ("x_len", x_len)))
     s_ld = x_len.copy() if s_ld is None else _align_seq("pair_sim", "s_ld", s_ld, npairs)
     if npairs and (q_start.min() < 0 or q_len.min() < 0 or x_start.min() < 0 or x_len.min() < 0):
         raise ValueError("pair_sim: every pair needs 0 <= start and 0 <= length")
-    if npairs and (q_len.max() > ALIGN_MAX_ROWS or x_len.max() > ALIGN_MAX_COLS):
+    if npairs and (q_len.max() > ALIGN_MAX_ROWS or x_len.max() > max_cols):
         raise ValueError(f"pair_sim: a pair of {int(q_len.max())} x {int(x_len.max())} rows is outside the limits "
-                         f"({ALIGN_MAX_ROWS} query rows, {ALIGN_MAX_COLS} song rows); longer inputs are refused, not split")
+                         f"({ALIGN_MAX_ROWS} query rows, {max_cols} song rows); longer inputs are refused, not split")
     ldq, ldx = _search_rows(q, "pair_sim q"), _search_rows(x, "pair_sim x")
     if q.shape[1] != x.shape[1]:
         raise ValueError(f"pair_sim: query d = {q.shape[1]} != song d = {x.shape[1]}")
@@ -2277,12 +2280,14 @@ def local_align(S, s_off, s_ld, q_len, x_len, theta, min_score=0.0, top=16):
 ALIGN_OCC_MAX_ROWS = _H["NSID_ALIGN_OCC_MAX_ROWS"]      # rows of one run of align_occurrences at most
 
 
-def align_carry(x_len, device):
+def align_carry(x_len, device, long_songs=False):
     """a carry for local_align_strip: ((carry_h fp32, carry_i0 int32, carry_j0 int32) flat device tensors, carry_off int64 numpy);
-    pair p's two rows of x_len[p] cells start at carry_off[p]. The content is not initialised: a pair's first strip is fresh."""
+    pair p's two rows of x_len[p] cells start at carry_off[p]. The content is not initialised: a pair's first strip is fresh.
+    long_songs=True: a carry for local_align_panels, lengths up to ALIGN_MAX_SONG_ROWS."""
     x_len = _align_seq("align_carry", "x_len", x_len)
-    if x_len.size and (x_len.min() < 0 or x_len.max() > ALIGN_MAX_COLS):
-        raise ValueError(f"align_carry: a song of {int(x_len.max())} rows is outside [0, {ALIGN_MAX_COLS}]")
+    max_cols = ALIGN_MAX_SONG_ROWS if long_songs else ALIGN_MAX_COLS
+    if x_len.size and (x_len.min() < 0 or x_len.max() > max_cols):
+        raise ValueError(f"align_carry: a song of {int(x_len.max())} rows is outside [0, {max_cols}]")
     size = 2 * x_len
     n = int(size.sum())
     carry = (torch.empty((n,), device=device, dtype=torch.float32), torch.empty((n,), device=device, dtype=torch.int32),
@@ -2312,51 +2317,69 @@ def local_align_strip(S, s_off, s_ld, q_len, x_len, theta, row_base, fresh, carr
     (default: new tensors, the pairs one after the other). Returns (row_h, row_j, row_i0, row_j0, row_off int64 numpy, open_h (pairs,)
     fp32 on the device): a row without a passing cell holds 0, -1, -1, -1; the rows of a pair with q_len = 0 are not written; open_h is
     the largest H carried out (0: no path is open)."""
+    return _align_strip("local_align_strip", None, S, s_off, s_ld, q_len, x_len, theta, row_base, fresh, carry, carry_off, rows, row_off)
+
+
+def local_align_panels(S, s_off, s_ld, q_len, x_len, theta, row_base, fresh, carry, carry_off, panel_cols=ALIGN_MAX_COLS, rows=None,
+                       row_off=None):
+    """local_align_strip for songs of up to ALIGN_MAX_SONG_ROWS rows (nsid_local_align_panels): the same arguments, the same outputs
+    and the same bits, the walk going over the song in panels of panel_cols columns (2 .. ALIGN_MAX_COLS) with two carried columns
+    between them. The result does not depend on panel_cols. carry: align_carry(..., long_songs=True). The halo workspace
+    ((q_len + 2) x 2 cells per pair) is allocated here and dropped after the launch."""
+    panel_cols = int(panel_cols)
+    if not 2 <= panel_cols <= ALIGN_MAX_COLS:
+        raise ValueError(f"local_align_panels: panel_cols = {panel_cols} is outside [2, {ALIGN_MAX_COLS}]")
+    return _align_strip("local_align_panels", panel_cols, S, s_off, s_ld, q_len, x_len, theta, row_base, fresh, carry, carry_off, rows,
+                        row_off)
+
+
+def _align_strip(name, panel_cols, S, s_off, s_ld, q_len, x_len, theta, row_base, fresh, carry, carry_off, rows, row_off):
+    """the checks and the launch of local_align_strip (panel_cols None) and local_align_panels"""
+    max_cols = ALIGN_MAX_COLS if panel_cols is None else ALIGN_MAX_SONG_ROWS
     if not isinstance(S, torch.Tensor):
-        raise TypeError("local_align_strip: S must be a torch tensor on the GPU")
+        raise TypeError(f"{name}: S must be a torch tensor on the GPU")
     _chk(S)
     S = S.reshape(-1)
-    name = "local_align_strip"
     s_off = _align_seq(name, "s_off", s_off)
     npairs = s_off.size
     s_ld, q_len, x_len, row_base, fresh, carry_off = (_align_seq(name, w, v, npairs) for w, v in (
         ("s_ld", s_ld), ("q_len", q_len), ("x_len", x_len), ("row_base", row_base), ("fresh", fresh), ("carry_off", carry_off)))
     theta = float(theta)
     if theta != theta:
-        raise ValueError("local_align_strip: theta is NaN")
+        raise ValueError(f"{name}: theta is NaN")
     if npairs and (q_len.min() < 0 or x_len.min() < 0):
-        raise ValueError("local_align_strip: a length is negative")
-    if npairs and (q_len.max() > ALIGN_MAX_ROWS or x_len.max() > ALIGN_MAX_COLS):
-        raise ValueError(f"local_align_strip: a strip of {int(q_len.max())} x {int(x_len.max())} rows is outside the limits "
-                         f"({ALIGN_MAX_ROWS} query rows per strip, {ALIGN_MAX_COLS} song rows)")
+        raise ValueError(f"{name}: a length is negative")
+    if npairs and (q_len.max() > ALIGN_MAX_ROWS or x_len.max() > max_cols):
+        raise ValueError(f"{name}: a strip of {int(q_len.max())} x {int(x_len.max())} rows is outside the limits "
+                         f"({ALIGN_MAX_ROWS} query rows per strip, {max_cols} song rows)")
     if npairs and (row_base.min() < 0 or (row_base + q_len).max() > 2 ** 31 - 1):
-        raise ValueError("local_align_strip: every pair needs 0 <= row_base and row_base + q_len <= 2^31 - 1")
+        raise ValueError(f"{name}: every pair needs 0 <= row_base and row_base + q_len <= 2^31 - 1")
     full = (q_len > 0) & (x_len > 0)
     if npairs and full.any() and (s_off[full].min() < 0 or (s_ld[full] < x_len[full]).any() or s_ld.max() >= 2 ** 31
                                   or (s_off + (q_len - 1) * s_ld + x_len)[full].max() > S.numel()):
-        raise ValueError("local_align_strip: a pair's score block (q_len rows of s_ld >= x_len floats) leaves S")
+        raise ValueError(f"{name}: a pair's score block (q_len rows of s_ld >= x_len floats) leaves S")
     if not isinstance(carry, (tuple, list)) or len(carry) != 3:
-        raise TypeError("local_align_strip: carry must be (carry_h, carry_i0, carry_j0)")
+        raise TypeError(f"{name}: carry must be (carry_h, carry_i0, carry_j0)")
     for what, t, dt in zip(("carry_h", "carry_i0", "carry_j0"), carry, (torch.float32, torch.int32, torch.int32)):
         _flat_dev(name, what, t, dt)
     if not carry[0].numel() == carry[1].numel() == carry[2].numel():
-        raise ValueError("local_align_strip: the three carry tensors must have one length")
+        raise ValueError(f"{name}: the three carry tensors must have one length")
     if npairs:
         order = np.argsort(carry_off, kind="stable")
         lo, hi = carry_off[order], (carry_off + 2 * x_len)[order]
         if lo[0] < 0 or hi.max() > carry[0].numel() or (lo[1:] < hi[:-1]).any():
-            raise ValueError("local_align_strip: a pair's carry (2 x_len cells at carry_off) leaves the carry tensors or overlaps another's")
+            raise ValueError(f"{name}: a pair's carry (2 x_len cells at carry_off) leaves the carry tensors or overlaps another's")
     dev = S.device
     total = int(q_len.sum())
     if rows is None:
         if row_off is not None:
-            raise ValueError("local_align_strip: row_off needs rows")
+            raise ValueError(f"{name}: row_off needs rows")
         row_off = np.cumsum(q_len) - q_len
         rows = (torch.empty((total,), device=dev, dtype=torch.float32),) + tuple(
             torch.empty((total,), device=dev, dtype=torch.int32) for _ in range(3))
     else:
         if not isinstance(rows, (tuple, list)) or len(rows) != 4 or row_off is None:
-            raise TypeError("local_align_strip: rows must be (row_h, row_j, row_i0, row_j0), given together with row_off")
+            raise TypeError(f"{name}: rows must be (row_h, row_j, row_i0, row_j0), given together with row_off")
         for what, t, dt in zip(("row_h", "row_j", "row_i0", "row_j0"), rows, (torch.float32, torch.int32, torch.int32, torch.int32)):
             _flat_dev(name, what, t, dt)
         row_off = _align_seq(name, "row_off", row_off, npairs)
@@ -2365,26 +2388,41 @@ def local_align_strip(S, s_off, s_ld, q_len, x_len, theta, row_base, fresh, carr
             order = np.argsort(row_off, kind="stable")
             lo, hi = row_off[order], (row_off + q_len)[order]
             if lo[0] < 0 or hi.max() > least or (lo[1:] < hi[:-1]).any():
-                raise ValueError("local_align_strip: a pair's rows (q_len at row_off) leave the row tensors or overlap another's")
+                raise ValueError(f"{name}: a pair's rows (q_len at row_off) leave the row tensors or overlap another's")
     open_h = torch.empty((npairs,), device=dev, dtype=torch.float32)
     if npairs == 0:
         return rows[0], rows[1], rows[2], rows[3], row_off, open_h
     t32 = torch.from_numpy(np.stack([s_ld, q_len, x_len, row_base, (fresh != 0).astype(np.int64)]).astype(np.int32)).to(dev)
     t64 = torch.from_numpy(np.stack([np.where(full, s_off, 0), carry_off, row_off])).to(dev)
     cells = float((q_len * x_len).sum())
-    _tk(None, 4.0 * cells + 16.0 * total + 48.0 * float(x_len.sum()), lambda: call(
-        "nsid_local_align_strip", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), npairs,
-        int(q_len.max()), int(x_len.max()), theta, _p(t64[1]), _p(carry[0]), _p(carry[1]), _p(carry[2]), _p(t64[2]), _p(rows[0]),
-        _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(open_h), _stream()), (npairs, int(q_len.max()), int(x_len.max()), 1))
+    if panel_cols is None:
+        _tk(None, 4.0 * cells + 16.0 * total + 48.0 * float(x_len.sum()), lambda: call(
+            "nsid_local_align_strip", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), npairs,
+            int(q_len.max()), int(x_len.max()), theta, _p(t64[1]), _p(carry[0]), _p(carry[1]), _p(carry[2]), _p(t64[2]), _p(rows[0]),
+            _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(open_h), _stream()), (npairs, int(q_len.max()), int(x_len.max()), 1))
+        return rows[0], rows[1], rows[2], rows[3], row_off, open_h
+    hsize = 2 * (q_len + 2)
+    halo_off = torch.from_numpy(np.cumsum(hsize) - hsize).to(dev)
+    hn = int(hsize.sum())
+    halo = (torch.empty((hn,), device=dev, dtype=torch.float32), torch.empty((hn,), device=dev, dtype=torch.int32),
+            torch.empty((hn,), device=dev, dtype=torch.int32))
+    panels = float(((x_len + panel_cols - 1) // panel_cols).sum())
+    _tk(None, 4.0 * cells + 16.0 * total + 48.0 * float(x_len.sum()) + 24.0 * panels * float(hn), lambda: call(
+        "nsid_local_align_panels", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), npairs,
+        int(q_len.max()), int(x_len.max()), panel_cols, theta, _p(t64[1]), _p(carry[0]), _p(carry[1]), _p(carry[2]), _p(halo_off),
+        _p(halo[0]), _p(halo[1]), _p(halo[2]), _p(t64[2]), _p(rows[0]), _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(open_h), _stream()),
+        (npairs, int(q_len.max()), int(x_len.max()), panel_cols))
     return rows[0], rows[1], rows[2], rows[3], row_off, open_h
 
 
-def align_occurrences(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, min_score=0.0, top=16):
+def align_occurrences(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, min_score=0.0, top=16, span=None):
     """The occurrences of many runs of rows in one launch (nsid_align_occurrences): run p is rows row_off[p] .. row_off[p] + n_rows[p] - 1
     of the four flat device tensors (local_align_strip's row results, the strips of a run one after the other), its local row r is
     global row first_row[p] + r. Grouping by (row_i0, row_j0), a group's best row, min_score, the order and the unused slots as
-    local_align has them. Returns (occ (runs, top, 4) int32 = (i0, i1, j0, j1) in global rows, occ_score (runs, top) fp32, n_occ
-    (runs,) int32, it can exceed top)."""
+    local_align has them. span: per run the rows over which one group can stretch, 2 (x_len - 1) against a song of x_len rows (any
+    larger value gives the same output); None: nsid_align_occurrences, whose window is that of a song of ALIGN_MAX_COLS rows; given:
+    nsid_align_occurrences_span. Returns (occ (runs, top, 4) int32 = (i0, i1, j0, j1) in global rows, occ_score (runs, top) fp32,
+    n_occ (runs,) int32, it can exceed top)."""
     name = "align_occurrences"
     for what, t, dt in zip(("row_h", "row_j", "row_i0", "row_j0"), (row_h, row_j, row_i0, row_j0),
                            (torch.float32, torch.int32, torch.int32, torch.int32)):
@@ -2405,14 +2443,23 @@ def align_occurrences(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, 
     least = min(t.numel() for t in (row_h, row_j, row_i0, row_j0))
     if npairs and (row_off.min() < 0 or (row_off + n_rows).max() > least):
         raise ValueError("align_occurrences: a run (n_rows at row_off) leaves the row tensors")
+    if span is not None:
+        span = _align_seq(name, "span", span, npairs)
+        if npairs and (span.min() < 0 or span.max() > 2 ** 31 - 1):
+            raise ValueError("align_occurrences: every span must be in [0, 2^31 - 1]")
     dev = row_h.device
     occ = torch.empty((npairs, top, 4), device=dev, dtype=torch.int32)
     occ_score = torch.empty((npairs, top), device=dev, dtype=torch.float32)
     n_occ = torch.empty((npairs,), device=dev, dtype=torch.int32)
     if npairs == 0:
         return occ, occ_score, n_occ
-    t32 = torch.from_numpy(np.stack([n_rows, first_row]).astype(np.int32)).to(dev)
+    t32 = torch.from_numpy(np.stack([n_rows, first_row] + ([] if span is None else [span])).astype(np.int32)).to(dev)
     t64 = torch.from_numpy(np.ascontiguousarray(row_off)).to(dev)
+    if span is not None:
+        _tk("align_occurrences_kernel", 16.0 * float(n_rows.sum()), lambda: call(
+            "nsid_align_occurrences_span", _p(row_h), _p(row_j), _p(row_i0), _p(row_j0), _p(t64), _p(t32[0]), _p(t32[1]), _p(t32[2]),
+            npairs, int(n_rows.max()), min_score, top, _p(occ), _p(occ_score), _p(n_occ), _stream()), (npairs, int(n_rows.max()), 0, top))
+        return occ, occ_score, n_occ
     _tk("align_occurrences_kernel", 16.0 * float(n_rows.sum()), lambda: call(
         "nsid_align_occurrences", _p(row_h), _p(row_j), _p(row_i0), _p(row_j0), _p(t64), _p(t32[0]), _p(t32[1]), npairs,
         int(n_rows.max()), min_score, top, _p(occ), _p(occ_score), _p(n_occ), _stream()), (npairs, int(n_rows.max()), 0, top))
