@@ -8,20 +8,28 @@
 // The dot is the chain of csrc/search.hip: one k-ordered fp32 fmaf chain on v_mfma_f32_32x32x2_f32, the same for every (i, j) whichever
 // tile, lane or pair holds it (up to d = 256 the pairing of l2_topk_split_kernel, above it the pairing of l2_topk_wide_kernel).
 //
-// local_align: one workgroup per pair walks the rows of S_p; threads own columns. The rule (stated in include/nsid.h) needs rows i - 1
-// and i - 2 only, so all columns of a row are independent: three rotating rows of (H, origin) cells in LDS, 8 bytes a cell, one barrier per
-// row (it orders LDS only), S read eight rows at a time with all loads in flight together. A row's result (its best cell that itself
-// passes the threshold) is reduced per wave (DPP), left in LDS, and combined during the next row. After the walk the same workgroup
-// reads the row results back and forms the occurrences with the quadratic compares of csrc/vote.hip. No atomics; a pair's result
-// depends on nothing but the pair.
+// The walk (al_walk): one workgroup per pair walks the rows of S_p; threads own columns. The rule (stated in include/nsid.h) needs rows
+// i - 1 and i - 2 only, so all columns of a row are independent: three rotating rows of (H, origin) cells in LDS, 8 bytes a cell, one
+// barrier per row (it orders LDS only), S read eight rows at a time with all loads in flight together. A row's result (its best cell
+// that itself passes the threshold) is reduced per wave (DPP), left in LDS, combined during the next row and handed to the caller's
+// sink. No atomics; a pair's result depends on nothing but the pair. The rule is written once, there; a pass of the walk covers the
+// rows of a strip over a range of columns, and three kernels call it:
 //
-// local_align_strip / align_occurrences: the same walk from two carried rows to two carried rows, so that a recording of any length goes
-// through in strips, and the occurrences of a run of rows of any length from its row results (include/nsid.h, below nsid_local_align).
+// local_align: one pass over the whole matrix from zeros; the sink stores (H, j, packed origin) per row. After the walk the same
+// workgroup reads the row results back and forms the occurrences with the quadratic compares of csrc/vote.hip.
 //
-// local_align_panels / align_occurrences_span: the strip walk turned by 90 degrees for songs of up to 16384 rows. One workgroup still
-// owns a pair, but walks the strip once per panel of at most 4096 columns with two carried columns (the halo) between panels, so the
-// LDS rows keep their width; the occurrence kernel takes the width of a group's window per run (include/nsid.h, below
+// local_align_strip / align_occurrences: one pass from two carried rows to two carried rows, so that a recording of any length goes
+// through in strips; the sink stores (H, j, i0, j0) with i0 a global row. The occurrences of a run of rows of any length come from
+// its row results (include/nsid.h, below nsid_local_align).
+//
+// local_align_panels / align_occurrences_span: for songs of up to 16384 rows, the strip in one pass per panel of at most 4096 columns
+// with two carried columns (the halo) between panels, so the LDS rows keep their width; the sink keeps a row's best over the panels
+// in LDS and stores the row's halo. The occurrence kernel takes the width of a group's window per run (include/nsid.h, below
 // nsid_align_occurrences).
+//
+// The helpers beside the walk are what the strip and the panels share: the rows of a pair without cells (al_no_cells), the fill of
+// the three LDS rows (al_fill), the carry out (al_carry_out) and open_h (al_open_h). On the host one macro picks 256 or 1024 threads
+// for all three entries (AL_LAUNCH), and one function checks the arguments the strip and the panels share (align_strip_args).
 #include "nsid_common.h"
 
 namespace {
@@ -90,7 +98,7 @@ __global__ __launch_bounds__(64) void pair_sim_kernel(const float* __restrict__ 
   }
 }
 
-// ---- local_align ----------------------------------------------------------------------------------------------------------------
+// ---- local alignment: a row's key, the empty result ----------------------------------------------------------------------------------
 // a row's best cell as one key: H's bits (H > 0, so they order as the floats do) above the complement of j (ties: the smaller j wins a max);
 // 0 = the row has no cell that passes the threshold
 __device__ __forceinline__ unsigned long long al_key(float h, int j) {
@@ -128,8 +136,232 @@ __device__ __forceinline__ void al_empty(int p, int top, int n, int tid, int* __
   if (tid == 0) n_occ[p] = n;
 }
 
-// cols: cells per LDS row = max_x + 2 (two zero cells in front stand for j - 1, j - 2 < 0). Dynamic LDS: three rows of cells during the
-// walk, then the row results (h, origin) of the pair.
+// ---- the walk ---------------------------------------------------------------------------------------------------------------------
+// A cell keeps its origin as (i0 mod 2^15) << 16 | j0 (sign bit clear, -1 = none), i0 a GLOBAL query row: every step of a path advances
+// j by at least 1 and i by at most 2, so i - i0 <= 2 (Lr - 1) < 2^15 and i0 = i - ((i - m) mod 2^15).
+constexpr int AL_I0_MOD = 1 << 15;
+constexpr int AL_SPAN = 2 * (AL_MAX_COLS - 1);    // i - i0 of a cell at the most, songs of up to AL_MAX_COLS rows
+constexpr int AL_MAX_SONG_ROWS = NSID_ALIGN_MAX_SONG_ROWS;
+static_assert(AL_SPAN < AL_I0_MOD && AL_MAX_COLS <= (1 << 16), "a cell's origin row is recovered from its low 15 bits");
+static_assert(AL_MAX_SONG_ROWS <= (1 << 16), "a cell's origin column keeps its 16 bits");
+static_assert(2 * (AL_MAX_SONG_ROWS - 1) < AL_I0_MOD, "a cell's origin row is recovered from its low 15 bits: i - i0 <= 2 (Lr - 1)");
+// local_align_kernel's rows are global rows 0 .. AL_MAX_ROWS - 1 < 2^15 (the first static_assert of this file), so there the packing
+// is (i0 << 16) | j0 itself: row_org's documented packing, bit for bit.
+static_assert(3 * (AL_MAX_COLS + 2) * 8 + AL_MAX_ROWS * 12 + 4096 <= NSID_LDS_MAX, "three rows of cells and the strip's row results in LDS");
+
+__device__ __forceinline__ int al_pack_org(int i0, int j0) { return (i0 < 0 || j0 < 0) ? -1 : (((i0 & (AL_I0_MOD - 1)) << 16) | j0); }
+// the origin row of a cell of global row i (org >= 0)
+__device__ __forceinline__ int al_org_row(int i, int org) { return i - ((i - (org >> 16)) & (AL_I0_MOD - 1)); }
+
+// A pair's cells in memory, (H, i0, j0) each: the two carried rows (the carry) or the two columns between panels (the halo).
+struct AlCells {
+  float* h;                    // the pair's first cell
+  int* i0;
+  int* j0;
+  __device__ __forceinline__ AlCells(float* h_, int* i0_, int* j0_, int64_t off) : h(h_ + off), i0(i0_ + off), j0(j0_ + off) {}
+  __device__ __forceinline__ AlCells() : h(nullptr), i0(nullptr), j0(nullptr) {}
+  __device__ __forceinline__ int2 load(int64_t a) const { return int2{__builtin_bit_cast(int, h[a]), al_pack_org(i0[a], j0[a])}; }
+  // row: the global row of the cell
+  __device__ __forceinline__ void store(int64_t a, int row, int2 c) const {
+    h[a] = __builtin_bit_cast(float, c.x);
+    i0[a] = c.y >= 0 ? al_org_row(row, c.y) : -1;
+    j0[a] = c.y >= 0 ? (c.y & 0xffff) : -1;
+  }
+  // the halo cell (row, k): column c0 - 2 + k of strip row `row` (-2, -1: the carried rows) for the panel that starts at c0
+  __device__ __forceinline__ int64_t at(int row, int k) const { return 2 * (int64_t)(row + 2) + k; }
+};
+
+// One pass of the walk: rows [0, Lq) of the columns [c0, c0 + pw) of a pair's S; row 0 is global row `base`. cell: three LDS rows of
+// `cols` cells (row 0 = row i, row 1 = row i - 2, row 2 = row i - 1 at the start), two cells in front of each standing for columns
+// c0 - 1 and c0 - 2. The last three members are read by al_walk<., true> only.
+struct AlPass {
+  const float* Sp;
+  size_t ld;
+  float theta;
+  int Lq, base, c0, pw;
+  int2* cell;
+  int cols;
+  bool first;                  // the panel at c0 == 0: zeros in front of every row
+  AlCells halo;
+  int2 (*hst)[2 * AL_RB];      // the packed halo cells of the current and the next block of rows
+};
+struct AlRows {
+  int2* prev1;                 // rows Lq - 1 and Lq - 2 after the walk (the rows the fill left, where the pass has fewer rows)
+  int2* prev2;
+};
+
+// The rows of a pair without cells (bad: its lengths are outside the launch's limits, which the caller checks: this only keeps it in
+// bounds; or it has no column) and its open_h.
+template <int THREADS>
+__device__ __forceinline__ void al_no_cells(bool bad, int Lq, int max_q, float* __restrict__ row_h, int* __restrict__ row_j,
+                                            int* __restrict__ row_i0, int* __restrict__ row_j0, float* __restrict__ open_h) {
+  const int n = bad ? min(max(Lq, 0), max_q) : Lq;
+  for (int i = threadIdx.x; i < n; i += THREADS) {
+    row_h[i] = 0.f;
+    row_j[i] = -1;
+    row_i0[i] = -1;
+    row_j0[i] = -1;
+  }
+  if (threadIdx.x == 0) *open_h = bad ? -1.f : 0.f;
+}
+
+// The three LDS rows before a pass: zeros (H = +0.0, no origin), in rows i - 1 and i - 2 the pass's slice of the carry if the pair is
+// carried, and in front of them the carried rows' halo in every panel but the first. The caller's barrier follows.
+template <int THREADS>
+__device__ __forceinline__ void al_fill(const AlPass& w, bool carried, const AlCells& carry, int Lr) {
+  for (int t = threadIdx.x; t < 3 * w.cols; t += THREADS) {
+    const int r = t / w.cols, j = t - r * w.cols - 2;
+    int2 v = int2{0, -1};
+    if (r > 0 && j >= 0) {
+      if (carried && j < w.pw) v = carry.load((r == 2 ? 0 : Lr) + w.c0 + j);
+    } else if (r > 0 && !w.first) {
+      v = w.halo.load(w.halo.at(r == 2 ? -1 : -2, j + 2));
+    }
+    w.cell[t] = v;
+  }
+}
+
+// The pass's slice of the carry out: rows.prev1 / prev2 are global rows last and last - 1 (with Lq == 1 the latter is the old row -1;
+// store = false with Lq == 0: nothing moved and nothing is stored). Returns m joined with the largest H of the thread's cells.
+template <int THREADS>
+__device__ __forceinline__ float al_carry_out(const AlPass& w, const AlRows& rows, const AlCells& carry, int Lr, int last, bool store,
+                                              float m) {
+  for (int j = threadIdx.x; j < w.pw; j += THREADS) {
+    const int2 c1 = rows.prev1[j + 2], c2 = rows.prev2[j + 2];
+    m = fmaxf(m, fmaxf(__builtin_bit_cast(float, c1.x), __builtin_bit_cast(float, c2.x)));
+    if (store) {
+      carry.store(w.c0 + j, last, c1);
+      carry.store(Lr + w.c0 + j, last - 1, c2);
+    }
+  }
+  return m;
+}
+
+// open_h = the workgroup's largest m
+template <int THREADS>
+__device__ __forceinline__ void al_open_h(float m, float* __restrict__ open_h) {
+  constexpr int NW = THREADS / NSID_WAVE;
+  __shared__ float wmax[NW];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, NSID_WAVE));
+  if ((threadIdx.x & (NSID_WAVE - 1)) == 0) wmax[threadIdx.x / NSID_WAVE] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float v = 0.f;
+    for (int u = 0; u < NW; ++u) v = fmaxf(v, wmax[u]);
+    *open_h = v;
+  }
+}
+
+// The walk itself, the one place where the rule of include/nsid.h is written: threads own columns, one barrier per row. A row's best
+// key and that cell's origin reach sink(row, key, org, buf) between the barriers of rows `row` and `row + 1` (the last row's after the
+// last barrier); buf is the row's cells. HALO: the pass is a panel; the cells in front of each row come from w.hst (w.first: zeros),
+// a block of rows ahead of their use.
+template <int THREADS, bool HALO, class Sink>
+__device__ __forceinline__ AlRows al_walk(const AlPass& w, Sink&& sink) {
+  constexpr int NW = THREADS / NSID_WAVE;
+  __shared__ unsigned long long part[2][NW];
+  const int tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), wave = tid / NSID_WAVE;
+
+  // the waves' keys of the row -> its result. Every wave does the (broadcast) reads, so that they are scheduled among the row's own
+  // reads and no wave is later at the barrier than the others; the sink says which threads store
+  auto combine = [&](int row, const int2* buf) {
+    unsigned long long k = 0;
+#pragma unroll
+    for (int u = 0; u < NW; ++u) {
+      const unsigned long long v = part[row & 1][u];
+      k = v > k ? v : k;
+    }
+    const int j = k ? (int)(0xffffffffu - (unsigned)k) : -1;
+    sink(row, k, buf[max(j - w.c0, 0) + 2].y, buf);
+  };
+
+  int2* cur = w.cell;                    // row i
+  int2* prev1 = w.cell + 2 * w.cols;     // row i - 1
+  int2* prev2 = w.cell + w.cols;         // row i - 2
+  const bool stage = HALO && !w.first && tid < 2 * AL_RB;      // this thread loads the halo cell (row tid / 2, column tid % 2) of a block
+  // AL_RB rows of S per thread at a time, all their loads in flight together: the memory latency is paid once per AL_RB rows, not per row
+  // (columns past the pass's end read its last column and are not used)
+  for (int ib = 0; ib < w.Lq; ib += AL_RB) {
+    float sv[AL_RB][AL_CPT];
+#pragma unroll
+    for (int r = 0; r < AL_RB; ++r) {
+      const float* rp = w.Sp + (size_t)min(ib + r, w.Lq - 1) * w.ld + w.c0;
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) sv[r][c] = rp[min(tid + c * THREADS, w.pw - 1)];
+    }
+    const int hb = (ib / AL_RB) & 1;
+    const bool more = stage && ib + AL_RB < w.Lq;              // the halo of the next block of rows is loaded during this one
+    int2 hnext = int2{0, -1};
+#pragma unroll
+    for (int r = 0; r < AL_RB; ++r) {
+      const int i = ib + r;
+      if (i >= w.Lq) break;              // uniform
+      if (i > 0) combine(i - 1, prev1);
+      if constexpr (HALO) {
+        // issued when half of the block's S is consumed (the registers are free by then), stored four rows later
+        if (r == AL_RB / 2 && more) hnext = w.halo.load(w.halo.at(min(ib + AL_RB + (tid >> 1), w.Lq - 1), tid & 1));
+      }
+      const int own = (((w.base + i) & (AL_I0_MOD - 1)) << 16) | w.c0;      // a path that starts in this row, at local column 0
+      unsigned long long key = 0;
+      // branch-free over the thread's columns (a column past the pass's end reads the last one and writes nothing), so that the LDS
+      // reads of all of them are in flight together
+      int2 d11[AL_CPT], d12[AL_CPT], d21[AL_CPT];
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) {
+        const int jc = min(tid + c * THREADS, w.pw - 1);
+        d11[c] = prev1[jc + 1];
+        d12[c] = prev1[jc];
+        d21[c] = prev2[jc + 1];
+      }
+      if constexpr (HALO) {
+        if (tid < 2) cur[tid] = w.first ? int2{0, -1} : w.hst[hb][2 * r + tid];
+        if (r == AL_RB - 1 && more) w.hst[hb ^ 1][tid] = hnext;             // read from the next row on, after this row's barrier
+      }
+#pragma unroll
+      for (int c = 0; c < AL_CPT; ++c) {
+        const int j = tid + c * THREADS;
+        const float e = sv[r][c] - w.theta;
+        float best = 0.f;
+        int from = -1;
+        const float h11 = __builtin_bit_cast(float, d11[c].x), h12 = __builtin_bit_cast(float, d12[c].x),
+                    h21 = __builtin_bit_cast(float, d21[c].x);
+        if (h11 > best) {
+          best = h11;
+          from = d11[c].y;
+        }
+        if (h12 > best) {
+          best = h12;
+          from = d12[c].y;
+        }
+        if (h21 > best) {
+          best = h21;
+          from = d21[c].y;
+        }
+        const float v = best + e;
+        const bool pos = v > 0.f;
+        if (j < w.pw) cur[j + 2] = int2{pos ? __builtin_bit_cast(int, v) : 0, pos ? (from >= 0 ? from : (own + j)) : -1};
+        const unsigned long long k = (j < w.pw && e > 0.f) ? al_key(v, w.c0 + j) : 0ull;
+        key = k > key ? k : key;
+      }
+      key = al_wave_key_max(key);
+      if (lane == 0) part[i & 1][wave] = key;
+      int2* t = prev2;
+      prev2 = prev1;
+      prev1 = cur;
+      cur = t;
+      // the row's barrier orders LDS only: a sink's stores to memory, which nobody reads before the walk ends, stay in flight over it
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    }
+  }
+  if (w.Lq > 0) combine(w.Lq - 1, prev1);
+  return AlRows{prev1, prev2};
+}
+
+// ---- local_align: the walk over the whole matrix from zeros, then the pair's occurrences -------------------------------------------
+// cols: cells per LDS row = max_x + 2. Dynamic LDS: three rows of cells during the walk, then the row results (h, origin) of the pair.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void local_align_kernel(const float* __restrict__ S, const int64_t* __restrict__ s_off,
                                                               const int* __restrict__ s_ld, const int* __restrict__ q_len,
@@ -140,7 +372,6 @@ __global__ __launch_bounds__(THREADS) void local_align_kernel(const float* __res
                                                               float* __restrict__ occ_score, int* __restrict__ n_occ) {
   constexpr int NW = THREADS / NSID_WAVE;
   extern __shared__ __attribute__((aligned(16))) char al_smem[];
-  __shared__ unsigned long long part[2][NW];
   __shared__ int o_occ[AL_MAX_TOP][4];
   __shared__ float o_sc[AL_MAX_TOP];
   __shared__ int wcnt[NW];
@@ -160,8 +391,6 @@ __global__ __launch_bounds__(THREADS) void local_align_kernel(const float* __res
     }
     return;
   }
-  const float* Sp = S + s_off[p];
-  const size_t ld = (size_t)s_ld[p];
   const int64_t ro = row_off[p];
 
   int2* cell = reinterpret_cast<int2*>(al_smem);
@@ -172,92 +401,14 @@ __global__ __launch_bounds__(THREADS) void local_align_kernel(const float* __res
   }
   __syncthreads();
 
-  // between the barriers of rows `row` and `row + 1`: the waves' keys of the row -> its result. Every wave does the (broadcast) reads, so
-  // that they are scheduled among the row's own reads and no wave is later at the barrier than the others; thread 0 stores
-  auto combine = [&](int row, const int2* buf) {
-    unsigned long long k = 0;
-#pragma unroll
-    for (int u = 0; u < NW; ++u) {
-      const unsigned long long v = part[row & 1][u];
-      k = v > k ? v : k;
-    }
-    const int j = k ? (int)(0xffffffffu - (unsigned)k) : -1;
-    const int org = buf[max(j, 0) + 2].y;
-    if (tid == 0) {
-      row_h[ro + row] = __builtin_bit_cast(float, (unsigned)(k >> 32));
-      row_j[ro + row] = j;
-      row_org[ro + row] = k ? org : -1;
-    }
-  };
-
-  int2* cur = cell;                  // row i
-  int2* prev1 = cell + 2 * cols;     // row i - 1
-  int2* prev2 = cell + cols;         // row i - 2
-  // AL_RB rows of S per thread at a time, all their loads in flight together: the memory latency is paid once per AL_RB rows, not per row
-  // (columns past the pair's end read its last column and are not used)
-  for (int ib = 0; ib < Lq; ib += AL_RB) {
-    float sv[AL_RB][AL_CPT];
-#pragma unroll
-    for (int r = 0; r < AL_RB; ++r) {
-      const float* rp = Sp + (size_t)min(ib + r, Lq - 1) * ld;
-#pragma unroll
-      for (int c = 0; c < AL_CPT; ++c) sv[r][c] = rp[min(tid + c * THREADS, Lr - 1)];
-    }
-#pragma unroll
-    for (int r = 0; r < AL_RB; ++r) {
-      const int i = ib + r;
-      if (i >= Lq) break;              // uniform
-      if (i > 0) combine(i - 1, prev1);
-      unsigned long long key = 0;
-      // branch-free over the thread's columns (a column past the pair's end reads the last one and writes nothing), so that the LDS
-      // reads of all of them are in flight together
-      int2 d11[AL_CPT], d12[AL_CPT], d21[AL_CPT];
-#pragma unroll
-      for (int c = 0; c < AL_CPT; ++c) {
-        const int jc = min(tid + c * THREADS, Lr - 1);
-        d11[c] = prev1[jc + 1];
-        d12[c] = prev1[jc];
-        d21[c] = prev2[jc + 1];
-      }
-#pragma unroll
-      for (int c = 0; c < AL_CPT; ++c) {
-        const int j = tid + c * THREADS;
-        const float e = sv[r][c] - theta;
-        float best = 0.f;
-        int from = -1;
-        const float h11 = __builtin_bit_cast(float, d11[c].x), h12 = __builtin_bit_cast(float, d12[c].x),
-                    h21 = __builtin_bit_cast(float, d21[c].x);
-        if (h11 > best) {
-          best = h11;
-          from = d11[c].y;
-        }
-        if (h12 > best) {
-          best = h12;
-          from = d12[c].y;
-        }
-        if (h21 > best) {
-          best = h21;
-          from = d21[c].y;
-        }
-        const float v = best + e;
-        const bool pos = v > 0.f;
-        if (j < Lr) cur[j + 2] = int2{pos ? __builtin_bit_cast(int, v) : 0, pos ? (from >= 0 ? from : ((i << 16) | j)) : -1};
-        const unsigned long long k = (j < Lr && e > 0.f) ? al_key(v, j) : 0ull;
-        key = k > key ? k : key;
-      }
-      key = al_wave_key_max(key);
-      if (lane == 0) part[i & 1][w] = key;
-      int2* t = prev2;
-      prev2 = prev1;
-      prev1 = cur;
-      cur = t;
-      // the row's barrier orders LDS only: wave 0's row results, which nobody reads before the walk ends, stay in flight over it
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    }
-  }
-  combine(Lq - 1, prev1);
+  al_walk<THREADS, false>(AlPass{S + s_off[p], (size_t)s_ld[p], theta, Lq, 0, 0, Lr, cell, cols, true, {}, nullptr},
+                          [&](int row, unsigned long long k, int org, const int2*) {
+                            if (tid == 0) {
+                              row_h[ro + row] = __builtin_bit_cast(float, (unsigned)(k >> 32));
+                              row_j[ro + row] = k ? (int)(0xffffffffu - (unsigned)k) : -1;
+                              row_org[ro + row] = k ? org : -1;
+                            }
+                          });
   __syncthreads();                   // the row results are in memory for the whole workgroup; the cells are dead
 
   // ---- occurrences: the rows grouped by origin, a group's best row, the kept ones ranked
@@ -340,33 +491,9 @@ __global__ __launch_bounds__(THREADS) void local_align_kernel(const float* __res
   }
 }
 
-size_t align_lds_bytes(int max_q, int max_x) {
-  const size_t walk = 3 * (size_t)(max_x + 2) * sizeof(int2), rows = 2 * (size_t)max_q * sizeof(int);
-  return (std::max(walk, rows) + 15) / 16 * 16;
-}
-
-template <int THREADS>
-int launch_align(size_t lds, hipStream_t st, int npairs, const float* S, const int64_t* s_off, const int* s_ld, const int* q_len,
-                 const int* x_len, int max_q, int max_x, float theta, float min_score, int top, const int64_t* row_off, float* row_h,
-                 int* row_j, int* row_org, int* occ, float* occ_score, int* n_occ) {
-  NSID_LAUNCH_LDS((local_align_kernel<THREADS>), dim3(npairs), dim3(THREADS), lds, st, S, s_off, s_ld, q_len, x_len, max_q, max_x,
-                  max_x + 2, theta, min_score, top, row_off, row_h, row_j, row_org, occ, occ_score, n_occ);
-  return nsid_launch_status();
-}
-
-// ---- local_align_strip ------------------------------------------------------------------------------------------------------------
-// The walk of local_align_kernel from two carried rows to two carried rows (include/nsid.h nsid_local_align_strip): the carry load
-// stands where the zero fill stood, and after the walk the two LDS rows that are rows -1 and -2 at that point go back to the carry.
-// local_align_kernel itself is untouched. A cell keeps its origin as (i0 mod 2^15) << 16 | j0 (sign bit clear, -1 = none): every step
-// of a path advances j by at least 1 and i by at most 2, so i - i0 <= 2 (Lr - 1) <= 8190 < 2^15 and i0 = i - ((i - m) mod 2^15).
-constexpr int AL_I0_MOD = 1 << 15;
-constexpr int AL_SPAN = 2 * (AL_MAX_COLS - 1);    // i - i0 of a cell at the most
-static_assert(AL_SPAN < AL_I0_MOD && AL_MAX_COLS <= (1 << 16), "a cell's origin row is recovered from its low 15 bits");
-
-__device__ __forceinline__ int al_pack_org(int i0, int j0) { return (i0 < 0 || j0 < 0) ? -1 : (((i0 & (AL_I0_MOD - 1)) << 16) | j0); }
-// the origin row of a cell of global row i (org >= 0)
-__device__ __forceinline__ int al_org_row(int i, int org) { return i - ((i - (org >> 16)) & (AL_I0_MOD - 1)); }
-
+// ---- local_align_strip: the walk over the whole width from two carried rows to two carried rows ------------------------------------
+// (include/nsid.h nsid_local_align_strip.) The carry stands where local_align's zeros stand, and after the walk the two LDS rows that
+// are rows -1 and -2 at that point go back to the carry; open_h = the largest H in them.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void local_align_strip_kernel(
     const float* __restrict__ S, const int64_t* __restrict__ s_off, const int* __restrict__ s_ld, const int* __restrict__ q_len,
@@ -374,183 +501,42 @@ __global__ __launch_bounds__(THREADS) void local_align_strip_kernel(
     float theta, const int64_t* __restrict__ carry_off, float* carry_h, int* carry_i0, int* carry_j0,
     const int64_t* __restrict__ row_off, float* __restrict__ row_h, int* __restrict__ row_j, int* __restrict__ row_i0,
     int* __restrict__ row_j0, float* __restrict__ open_h) {
-  constexpr int NW = THREADS / NSID_WAVE;
   extern __shared__ __attribute__((aligned(16))) char al_smem[];
-  __shared__ unsigned long long part[2][NW];
-  __shared__ float wmax[NW];
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
+  const int p = blockIdx.x, tid = threadIdx.x;
   const int Lq = q_len[p], Lr = x_len[p], base = row_base[p];
   const int64_t ro = row_off[p];
   // every return below is uniform over the workgroup and ahead of every barrier
   const bool bad = Lq < 0 || Lr < 0 || Lq > max_q || Lr > max_x || base < 0 || (int64_t)base + Lq > 0x7fffffffLL;
-  if (bad || Lr == 0) {                       // the caller checks the lengths (this only keeps a bad pair in bounds); no column: no cell
-    const int n = bad ? min(max(Lq, 0), max_q) : Lq;
-    for (int i = tid; i < n; i += THREADS) {
-      row_h[ro + i] = 0.f;
-      row_j[ro + i] = -1;
-      row_i0[ro + i] = -1;
-      row_j0[ro + i] = -1;
-    }
-    if (tid == 0) open_h[p] = bad ? -1.f : 0.f;
+  if (bad || Lr == 0) {
+    al_no_cells<THREADS>(bad, Lq, max_q, row_h + ro, row_j + ro, row_i0 + ro, row_j0 + ro, open_h + p);
     return;
   }
-  const float* Sp = S + s_off[p];
-  const size_t ld = (size_t)s_ld[p];
-  const int64_t co = carry_off[p];
-  const bool carried = fresh[p] == 0;
-
-  // LDS row 0 = row i, row 1 = row i - 2, row 2 = row i - 1; two cells in front of each stand for j - 1, j - 2 < 0
-  int2* cell = reinterpret_cast<int2*>(al_smem);
-  for (int t = tid; t < 3 * cols; t += THREADS) {
-    const int r = t / cols, j = t - r * cols - 2;
-    int2 v = int2{0, -1};                                                       // H = +0.0, no origin
-    if (carried && r > 0 && j >= 0 && j < Lr) {
-      const int64_t a = co + (r == 2 ? 0 : Lr) + j;
-      v = int2{__builtin_bit_cast(int, carry_h[a]), al_pack_org(carry_i0[a], carry_j0[a])};
-    }
-    cell[t] = v;
-  }
+  const AlCells carry(carry_h, carry_i0, carry_j0, carry_off[p]);
+  const AlPass w{S + s_off[p], (size_t)s_ld[p], theta, Lq, base, 0, Lr, reinterpret_cast<int2*>(al_smem), cols, true, {}, nullptr};
+  al_fill<THREADS>(w, fresh[p] == 0, carry, Lr);
   __syncthreads();
-
-  // as in local_align_kernel: between the barriers of rows `row` and `row + 1` the waves' keys of the row become its result
-  auto combine = [&](int row, const int2* buf) {
-    unsigned long long k = 0;
-#pragma unroll
-    for (int u = 0; u < NW; ++u) {
-      const unsigned long long v = part[row & 1][u];
-      k = v > k ? v : k;
-    }
-    const int j = k ? (int)(0xffffffffu - (unsigned)k) : -1;
-    const int org = buf[max(j, 0) + 2].y;
+  const AlRows rows = al_walk<THREADS, false>(w, [&](int row, unsigned long long k, int org, const int2*) {
     if (tid == 0) {
       const bool has = k != 0 && org >= 0;
       row_h[ro + row] = __builtin_bit_cast(float, (unsigned)(k >> 32));
-      row_j[ro + row] = j;
+      row_j[ro + row] = k ? (int)(0xffffffffu - (unsigned)k) : -1;
       row_i0[ro + row] = has ? al_org_row(base + row, org) : -1;
       row_j0[ro + row] = has ? (org & 0xffff) : -1;
     }
-  };
-
-  int2* cur = cell;
-  int2* prev1 = cell + 2 * cols;
-  int2* prev2 = cell + cols;
-  for (int ib = 0; ib < Lq; ib += AL_RB) {
-    float sv[AL_RB][AL_CPT];
-#pragma unroll
-    for (int r = 0; r < AL_RB; ++r) {
-      const float* rp = Sp + (size_t)min(ib + r, Lq - 1) * ld;
-#pragma unroll
-      for (int c = 0; c < AL_CPT; ++c) sv[r][c] = rp[min(tid + c * THREADS, Lr - 1)];
-    }
-#pragma unroll
-    for (int r = 0; r < AL_RB; ++r) {
-      const int i = ib + r;
-      if (i >= Lq) break;              // uniform
-      if (i > 0) combine(i - 1, prev1);
-      const int own = ((base + i) & (AL_I0_MOD - 1)) << 16;                       // a path that starts in this row
-      unsigned long long key = 0;
-      int2 d11[AL_CPT], d12[AL_CPT], d21[AL_CPT];
-#pragma unroll
-      for (int c = 0; c < AL_CPT; ++c) {
-        const int jc = min(tid + c * THREADS, Lr - 1);
-        d11[c] = prev1[jc + 1];
-        d12[c] = prev1[jc];
-        d21[c] = prev2[jc + 1];
-      }
-#pragma unroll
-      for (int c = 0; c < AL_CPT; ++c) {
-        const int j = tid + c * THREADS;
-        const float e = sv[r][c] - theta;
-        float best = 0.f;
-        int from = -1;
-        const float h11 = __builtin_bit_cast(float, d11[c].x), h12 = __builtin_bit_cast(float, d12[c].x),
-                    h21 = __builtin_bit_cast(float, d21[c].x);
-        if (h11 > best) {
-          best = h11;
-          from = d11[c].y;
-        }
-        if (h12 > best) {
-          best = h12;
-          from = d12[c].y;
-        }
-        if (h21 > best) {
-          best = h21;
-          from = d21[c].y;
-        }
-        const float v = best + e;
-        const bool pos = v > 0.f;
-        if (j < Lr) cur[j + 2] = int2{pos ? __builtin_bit_cast(int, v) : 0, pos ? (from >= 0 ? from : (own | j)) : -1};
-        const unsigned long long k = (j < Lr && e > 0.f) ? al_key(v, j) : 0ull;
-        key = k > key ? k : key;
-      }
-      key = al_wave_key_max(key);
-      if (lane == 0) part[i & 1][w] = key;
-      int2* t = prev2;
-      prev2 = prev1;
-      prev1 = cur;
-      cur = t;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-      __builtin_amdgcn_s_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-    }
-  }
-  if (Lq > 0) combine(Lq - 1, prev1);
-
-  // the carry out: prev1 / prev2 are rows base + Lq - 1 and base + Lq - 2 of the concatenation (with Lq == 1 the latter is the old row
-  // -1, with Lq == 0 nothing moved and nothing is stored); open_h = the largest H in them
-  float m = 0.f;
-  for (int j = tid; j < Lr; j += THREADS) {
-    const int2 c1 = prev1[j + 2], c2 = prev2[j + 2];
-    const float h1 = __builtin_bit_cast(float, c1.x), h2 = __builtin_bit_cast(float, c2.x);
-    m = fmaxf(m, fmaxf(h1, h2));
-    if (Lq > 0) {
-      carry_h[co + j] = h1;
-      carry_i0[co + j] = c1.y >= 0 ? al_org_row(base + Lq - 1, c1.y) : -1;
-      carry_j0[co + j] = c1.y >= 0 ? (c1.y & 0xffff) : -1;
-      carry_h[co + Lr + j] = h2;
-      carry_i0[co + Lr + j] = c2.y >= 0 ? al_org_row(base + Lq - 2, c2.y) : -1;
-      carry_j0[co + Lr + j] = c2.y >= 0 ? (c2.y & 0xffff) : -1;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, NSID_WAVE));
-  if (lane == 0) wmax[w] = m;
-  __syncthreads();
-  if (tid == 0) {
-    float v = 0.f;
-    for (int u = 0; u < NW; ++u) v = fmaxf(v, wmax[u]);
-    open_h[p] = v;
-  }
+  });
+  al_open_h<THREADS>(al_carry_out<THREADS>(w, rows, carry, Lr, base + Lq - 1, Lq > 0, 0.f), open_h + p);
 }
 
-template <int THREADS>
-int launch_align_strip(hipStream_t st, int npairs, const float* S, const int64_t* s_off, const int* s_ld, const int* q_len,
-                       const int* x_len, const int* row_base, const int* fresh, int max_q, int max_x, float theta,
-                       const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0, const int64_t* row_off, float* row_h,
-                       int* row_j, int* row_i0, int* row_j0, float* open_h) {
-  const size_t lds = (3 * (size_t)(max_x + 2) * sizeof(int2) + 15) / 16 * 16;
-  NSID_LAUNCH_LDS((local_align_strip_kernel<THREADS>), dim3(npairs), dim3(THREADS), lds, st, S, s_off, s_ld, q_len, x_len, row_base,
-                  fresh, max_q, max_x, max_x + 2, theta, carry_off, carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0,
-                  open_h);
-  return nsid_launch_status();
-}
-
-// ---- local_align_panels -----------------------------------------------------------------------------------------------------------
-// The strip walk for songs of up to AL_MAX_SONG_ROWS rows (include/nsid.h nsid_local_align_panels): the workgroup walks the strip once
-// per panel of pcols columns, left to right. The rule reads (i-1, j-1), (i-1, j-2) and (i-2, j-1), so a panel that starts at column c0
+// ---- local_align_panels: the strip in passes of pcols columns, for songs of up to AL_MAX_SONG_ROWS rows -----------------------------
+// (include/nsid.h nsid_local_align_panels.) The rule reads (i-1, j-1), (i-1, j-2) and (i-2, j-1), so a panel that starts at column c0
 // needs from its left only columns c0 - 2 and c0 - 1 of every row, the two carried ones included: the halo. The two cells in front of
 // each LDS row, zeros in the first panel, hold the halo of that row in every later one. The halo cells of a block of AL_RB rows are
-// loaded during the block before, a cell a thread, and left packed in LDS before that block's last barrier; threads
-// 0 and 1 put them in front of the row being computed and, after the row's barrier, store the row's last two cells over them for the
-// next panel (a row's halo is consumed at least one barrier before it is overwritten). A panel stores the halo of the carried rows
-// before its slice of the carry is overwritten. A row's best key over the panels so far and that cell's origin stay
-// in LDS behind the cells; a later panel replaces them only with a strictly larger H (it has the larger j), and the rows go to memory
-// once, after the last panel. The packing of a cell is the strip kernel's: j0 < 2^16, and i - i0 <= 2 (Lr - 1) <= 32766 < 2^15.
-constexpr int AL_MAX_SONG_ROWS = NSID_ALIGN_MAX_SONG_ROWS;
-static_assert(AL_MAX_SONG_ROWS <= (1 << 16), "a cell's origin column keeps its 16 bits");
-static_assert(2 * (AL_MAX_SONG_ROWS - 1) < AL_I0_MOD, "a cell's origin row is recovered from its low 15 bits: i - i0 <= 2 (Lr - 1)");
-static_assert(3 * (AL_MAX_COLS + 2) * 8 + AL_MAX_ROWS * 12 + 4096 <= NSID_LDS_MAX, "three rows of cells and the strip's row results in LDS");
-
+// loaded during the block before, a cell a thread, and left packed in LDS before that block's last barrier; threads 0 and 1 put them
+// in front of the row being computed (al_walk<., true>) and, after the row's barrier, store the row's last two cells over them for
+// the next panel (the sink; a row's halo is consumed at least one barrier before it is overwritten). A panel stores the halo of the
+// carried rows before its slice of the carry is overwritten. A row's best key over the panels so far and that cell's origin stay in
+// LDS behind the cells; a later panel replaces them only with a strictly larger H (it has the larger j), and the rows go to memory
+// once, after the last panel.
 template <int THREADS>
 __global__ __launch_bounds__(THREADS) void local_align_panels_kernel(
     const float* __restrict__ S, const int64_t* __restrict__ s_off, const int* __restrict__ s_ld, const int* __restrict__ q_len,
@@ -559,34 +545,22 @@ __global__ __launch_bounds__(THREADS) void local_align_panels_kernel(
     const int64_t* __restrict__ halo_off, float* halo_h, int* halo_i0, int* halo_j0, const int64_t* __restrict__ row_off,
     float* __restrict__ row_h, int* __restrict__ row_j, int* __restrict__ row_i0, int* __restrict__ row_j0,
     float* __restrict__ open_h) {
-  constexpr int NW = THREADS / NSID_WAVE;
   extern __shared__ __attribute__((aligned(16))) char al_smem[];
-  __shared__ unsigned long long part[2][NW];
-  __shared__ float wmax[NW];
-  __shared__ int2 hst[2][2 * AL_RB];          // the packed halo cells of the current and the next block of rows
-  const int p = blockIdx.x, tid = threadIdx.x, lane = tid & (NSID_WAVE - 1), w = tid / NSID_WAVE;
+  __shared__ int2 hst[2][2 * AL_RB];
+  const int p = blockIdx.x, tid = threadIdx.x;
   const int Lq = q_len[p], Lr = x_len[p], base = row_base[p];
   const int64_t ro = row_off[p];
   // every return below is uniform over the workgroup and ahead of every barrier
   const bool bad = Lq < 0 || Lr < 0 || Lq > max_q || Lr > max_x || base < 0 || (int64_t)base + Lq > 0x7fffffffLL;
-  if (bad || Lr == 0) {                       // as in local_align_strip_kernel
-    const int n = bad ? min(max(Lq, 0), max_q) : Lq;
-    for (int i = tid; i < n; i += THREADS) {
-      row_h[ro + i] = 0.f;
-      row_j[ro + i] = -1;
-      row_i0[ro + i] = -1;
-      row_j0[ro + i] = -1;
-    }
-    if (tid == 0) open_h[p] = bad ? -1.f : 0.f;
+  if (bad || Lr == 0) {
+    al_no_cells<THREADS>(bad, Lq, max_q, row_h + ro, row_j + ro, row_i0 + ro, row_j0 + ro, open_h + p);
     return;
   }
-  const float* Sp = S + s_off[p];
-  const size_t ld = (size_t)s_ld[p];
-  const int64_t co = carry_off[p], ho = halo_off[p];
+  const AlCells carry(carry_h, carry_i0, carry_j0, carry_off[p]), halo(halo_h, halo_i0, halo_j0, halo_off[p]);
   const bool carried = fresh[p] == 0;
   const int cols = pcols + 2;
 
-  // LDS: three rows of cells as in the strip kernel, then per strip row the best key so far and that cell's packed origin
+  // LDS: three rows of cells, then per strip row the best key so far and that cell's packed origin
   int2* cell = reinterpret_cast<int2*>(al_smem);
   unsigned long long* rkey = reinterpret_cast<unsigned long long*>(cell + 3 * cols);
   int* rorg = reinterpret_cast<int*>(rkey + max_q);
@@ -594,148 +568,29 @@ __global__ __launch_bounds__(THREADS) void local_align_panels_kernel(
     rkey[i] = 0ull;
     rorg[i] = -1;
   }
-  // the halo cell (row, k): column c0 - 2 + k of strip row `row` (-2, -1: the carried rows) for the panel that starts at c0
-  auto halo_load = [&](int row, int k) {
-    const int64_t a = ho + 2 * (int64_t)(row + 2) + k;
-    return int2{__builtin_bit_cast(int, halo_h[a]), al_pack_org(halo_i0[a], halo_j0[a])};
-  };
-  auto halo_store = [&](int row, int k, int2 c) {
-    const int64_t a = ho + 2 * (int64_t)(row + 2) + k;
-    halo_h[a] = __builtin_bit_cast(float, c.x);
-    halo_i0[a] = c.y >= 0 ? al_org_row(base + row, c.y) : -1;
-    halo_j0[a] = c.y >= 0 ? (c.y & 0xffff) : -1;
-  };
 
   float m = 0.f;
   for (int c0 = 0; c0 < Lr; c0 += pcols) {
     const int pw = min(pcols, Lr - c0);                       // only the last panel can be narrower (and only it can have one column)
     const bool first = c0 == 0, last = c0 + pw >= Lr;
-    for (int t = tid; t < 3 * cols; t += THREADS) {
-      const int r = t / cols, j = t - r * cols - 2;
-      int2 v = int2{0, -1};                                                       // H = +0.0, no origin
-      if (r > 0 && j >= 0) {
-        if (carried && j < pw) {
-          const int64_t a = co + (r == 2 ? 0 : Lr) + c0 + j;
-          v = int2{__builtin_bit_cast(int, carry_h[a]), al_pack_org(carry_i0[a], carry_j0[a])};
-        }
-      } else if (r > 0 && !first) {
-        v = halo_load(r == 2 ? -1 : -2, j + 2);
-      }
-      cell[t] = v;
-    }
-    const bool stage = !first && tid < 2 * AL_RB;              // this thread loads the halo cell (row tid / 2, column tid % 2) of a block
-    if (stage && Lq > 0) hst[0][tid] = halo_load(min(tid >> 1, Lq - 1), tid & 1);
+    const AlPass w{S + s_off[p], (size_t)s_ld[p], theta, Lq, base, c0, pw, cell, cols, first, halo, hst};
+    al_fill<THREADS>(w, carried, carry, Lr);
+    if (!first && tid < 2 * AL_RB && Lq > 0) hst[0][tid] = halo.load(halo.at(min(tid >> 1, Lq - 1), tid & 1));      // the first block's halo
     __syncthreads();
     // the carried rows' cells for the next panel, before this panel's slice of the carry is overwritten
     if (!last && tid < 2) {
-      halo_store(-2, tid, cell[cols + pw + tid]);
-      halo_store(-1, tid, cell[2 * cols + pw + tid]);
+      halo.store(halo.at(-2, tid), base - 2, cell[cols + pw + tid]);
+      halo.store(halo.at(-1, tid), base - 1, cell[2 * cols + pw + tid]);
     }
-
-    // between the barriers of rows `row` and `row + 1`: the waves' keys of the row against the row's best of the earlier panels
-    auto combine = [&](int row, const int2* buf) {
-      unsigned long long k = 0;
-#pragma unroll
-      for (int u = 0; u < NW; ++u) {
-        const unsigned long long v = part[row & 1][u];
-        k = v > k ? v : k;
-      }
-      const int j = k ? (int)(0xffffffffu - (unsigned)k) : c0;
-      const int org = buf[j - c0 + 2].y;
+    // the row's best of this panel against its best of the earlier panels; its last two cells for the next panel
+    const AlRows rows = al_walk<THREADS, true>(w, [&](int row, unsigned long long k, int org, const int2* buf) {
       if (tid == 0 && (k >> 32) > (rkey[row] >> 32)) {
         rkey[row] = k;
         rorg[row] = org;
       }
-      if (!last && tid < 2) halo_store(row, tid, buf[pw + tid]);
-    };
-
-    int2* cur = cell;
-    int2* prev1 = cell + 2 * cols;
-    int2* prev2 = cell + cols;
-    for (int ib = 0; ib < Lq; ib += AL_RB) {
-      float sv[AL_RB][AL_CPT];
-#pragma unroll
-      for (int r = 0; r < AL_RB; ++r) {
-        const float* rp = Sp + (size_t)min(ib + r, Lq - 1) * ld + c0;       // a column past the panel's end reads its last one
-#pragma unroll
-        for (int c = 0; c < AL_CPT; ++c) sv[r][c] = rp[min(tid + c * THREADS, pw - 1)];
-      }
-      const int hb = (ib / AL_RB) & 1;
-      const bool more = stage && ib + AL_RB < Lq;              // the halo of the next block of rows is loaded during this one
-      int2 hnext = int2{0, -1};
-#pragma unroll
-      for (int r = 0; r < AL_RB; ++r) {
-        const int i = ib + r;
-        if (i >= Lq) break;              // uniform
-        if (i > 0) combine(i - 1, prev1);
-        // issued when half of the block's S is consumed (the registers are free by then), stored four rows later
-        if (r == AL_RB / 2 && more) hnext = halo_load(min(ib + AL_RB + (tid >> 1), Lq - 1), tid & 1);
-        const int own = (((base + i) & (AL_I0_MOD - 1)) << 16) | c0;               // a path that starts in this row, at local column 0
-        unsigned long long key = 0;
-        int2 d11[AL_CPT], d12[AL_CPT], d21[AL_CPT];
-#pragma unroll
-        for (int c = 0; c < AL_CPT; ++c) {
-          const int jc = min(tid + c * THREADS, pw - 1);
-          d11[c] = prev1[jc + 1];
-          d12[c] = prev1[jc];
-          d21[c] = prev2[jc + 1];
-        }
-        if (tid < 2) cur[tid] = first ? int2{0, -1} : hst[hb][2 * r + tid];
-        if (r == AL_RB - 1 && more) hst[hb ^ 1][tid] = hnext;                      // read from the next row on, after this row's barrier
-#pragma unroll
-        for (int c = 0; c < AL_CPT; ++c) {
-          const int j = tid + c * THREADS;
-          const float e = sv[r][c] - theta;
-          float best = 0.f;
-          int from = -1;
-          const float h11 = __builtin_bit_cast(float, d11[c].x), h12 = __builtin_bit_cast(float, d12[c].x),
-                      h21 = __builtin_bit_cast(float, d21[c].x);
-          if (h11 > best) {
-            best = h11;
-            from = d11[c].y;
-          }
-          if (h12 > best) {
-            best = h12;
-            from = d12[c].y;
-          }
-          if (h21 > best) {
-            best = h21;
-            from = d21[c].y;
-          }
-          const float v = best + e;
-          const bool pos = v > 0.f;
-          if (j < pw) cur[j + 2] = int2{pos ? __builtin_bit_cast(int, v) : 0, pos ? (from >= 0 ? from : (own + j)) : -1};
-          const unsigned long long k = (j < pw && e > 0.f) ? al_key(v, c0 + j) : 0ull;
-          key = k > key ? k : key;
-        }
-        key = al_wave_key_max(key);
-        if (lane == 0) part[i & 1][w] = key;
-        int2* t = prev2;
-        prev2 = prev1;
-        prev1 = cur;
-        cur = t;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
-      }
-    }
-    if (Lq > 0) combine(Lq - 1, prev1);
-
-    // the panel's slice of the carry out, as the strip kernel writes the whole of it
-    for (int j = tid; j < pw; j += THREADS) {
-      const int2 c1 = prev1[j + 2], c2 = prev2[j + 2];
-      const float h1 = __builtin_bit_cast(float, c1.x), h2 = __builtin_bit_cast(float, c2.x);
-      m = fmaxf(m, fmaxf(h1, h2));
-      if (Lq > 0) {
-        const int64_t a = co + c0 + j;
-        carry_h[a] = h1;
-        carry_i0[a] = c1.y >= 0 ? al_org_row(base + Lq - 1, c1.y) : -1;
-        carry_j0[a] = c1.y >= 0 ? (c1.y & 0xffff) : -1;
-        carry_h[a + Lr] = h2;
-        carry_i0[a + Lr] = c2.y >= 0 ? al_org_row(base + Lq - 2, c2.y) : -1;
-        carry_j0[a + Lr] = c2.y >= 0 ? (c2.y & 0xffff) : -1;
-      }
-    }
+      if (!last && tid < 2) halo.store(halo.at(row, tid), base + row, buf[pw + tid]);
+    });
+    m = al_carry_out<THREADS>(w, rows, carry, Lr, base + Lq - 1, Lq > 0, m);
     __syncthreads();                   // the cells are dead, the halo and the row keys are written: the next panel may start
   }
 
@@ -748,20 +603,32 @@ __global__ __launch_bounds__(THREADS) void local_align_panels_kernel(
     row_i0[ro + i] = has ? al_org_row(base + i, org) : -1;
     row_j0[ro + i] = has ? (org & 0xffff) : -1;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, NSID_WAVE));
-  if (lane == 0) wmax[w] = m;
-  __syncthreads();
-  if (tid == 0) {
-    float v = 0.f;
-    for (int u = 0; u < NW; ++u) v = fmaxf(v, wmax[u]);
-    open_h[p] = v;
-  }
+  al_open_h<THREADS>(m, open_h + p);
 }
 
+// The dynamic LDS of the three, as each entry asks for it.
+size_t align_lds_bytes(int max_q, int max_x) {
+  const size_t walk = 3 * (size_t)(max_x + 2) * sizeof(int2), rows = 2 * (size_t)max_q * sizeof(int);
+  return (std::max(walk, rows) + 15) / 16 * 16;
+}
+size_t align_strip_lds_bytes(int max_x) { return (3 * (size_t)(max_x + 2) * sizeof(int2) + 15) / 16 * 16; }
 size_t align_panels_lds_bytes(int max_q, int pcols) {
   return (3 * (size_t)(pcols + 2) * sizeof(int2) + (size_t)max_q * 12 + 15) / 16 * 16;
 }
+
+// 256 threads own every column (in local_align also every row) of a pass up to `width` = 1024; above that 1024 threads do. The results
+// do not depend on it. The entry ends here.
+#define AL_LAUNCH(kernel, width, npairs, lds, st, ...)                                                  \
+  do {                                                                                                  \
+    if ((width) <= 256 * AL_CPT) {                                                                      \
+      nsid_took(#kernel "<256>");                                                                       \
+      NSID_LAUNCH_LDS((kernel<256>), dim3(npairs), dim3(256), lds, st, __VA_ARGS__);                    \
+    } else {                                                                                            \
+      nsid_took(#kernel "<1024>");                                                                      \
+      NSID_LAUNCH_LDS((kernel<1024>), dim3(npairs), dim3(1024), lds, st, __VA_ARGS__);                  \
+    }                                                                                                   \
+    return nsid_launch_status();                                                                        \
+  } while (0)
 
 // ---- align_occurrences ------------------------------------------------------------------------------------------------------------
 // One workgroup per run of rows. A group's rows lie within [i0, i0 + AL_SPAN], so a row is its group's representative when no row of
@@ -903,23 +770,20 @@ extern "C" int nsid_local_align(const float* S, const int64_t* s_off, const int*
   if (npairs == 0) return NSID_OK;
   NSID_REQUIRE(s_off && s_ld && q_len && x_len && row_off && occ && occ_score && n_occ);
   NSID_REQUIRE((max_q_len == 0 || max_x_len == 0) || (S && row_h && row_j && row_org));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t lds = align_lds_bytes(max_q_len, max_x_len);
   nsid_count(NSID_C_local_align);
-  // 256 threads own every column and every row of a pair up to 1024; above that 1024 threads do (the results do not depend on it)
-  if (std::max(max_q_len, max_x_len) <= 256 * AL_CPT)
-    return launch_align<256>(lds, st, npairs, S, s_off, s_ld, q_len, x_len, max_q_len, max_x_len, theta, min_score, top, row_off, row_h,
-                             row_j, row_org, occ, occ_score, n_occ);
-  return launch_align<1024>(lds, st, npairs, S, s_off, s_ld, q_len, x_len, max_q_len, max_x_len, theta, min_score, top, row_off, row_h,
-                            row_j, row_org, occ, occ_score, n_occ);
+  AL_LAUNCH(local_align_kernel, std::max(max_q_len, max_x_len), npairs, align_lds_bytes(max_q_len, max_x_len),
+            static_cast<hipStream_t>(stream), S, s_off, s_ld, q_len, x_len, max_q_len, max_x_len, max_x_len + 2, theta, min_score, top,
+            row_off, row_h, row_j, row_org, occ, occ_score, n_occ);
 }
 
-extern "C" int nsid_local_align_strip(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len,
-                                      const int* row_base, const int* fresh, int npairs, int max_q_len, int max_x_len, float theta,
-                                      const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0, const int64_t* row_off,
-                                      float* row_h, int* row_j, int* row_i0, int* row_j0, float* open_h, void* stream) {
-  NSID_REQUIRE(npairs >= 0 && max_q_len >= 0 && max_q_len <= AL_MAX_ROWS && max_x_len >= 0 && max_x_len <= AL_MAX_COLS &&
-               theta == theta);
+namespace {
+// The arguments nsid_local_align_strip and nsid_local_align_panels share (max_cols: the entry's bound of max_x_len). With npairs == 0
+// only the limits are looked at, as before either entry returns NSID_OK for it.
+int align_strip_args(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len, const int* row_base,
+                     const int* fresh, int npairs, int max_q_len, int max_x_len, int max_cols, float theta, const int64_t* carry_off,
+                     const float* carry_h, const int* carry_i0, const int* carry_j0, const int64_t* row_off, const float* row_h,
+                     const int* row_j, const int* row_i0, const int* row_j0, const float* open_h) {
+  NSID_REQUIRE(npairs >= 0 && max_q_len >= 0 && max_q_len <= AL_MAX_ROWS && max_x_len >= 0 && max_x_len <= max_cols && theta == theta);
   if (npairs == 0) return NSID_OK;
   NSID_REQUIRE(s_off && s_ld && q_len && x_len && row_base && fresh && carry_off && row_off && open_h);
   NSID_REQUIRE(max_q_len == 0 || (row_h && row_j && row_i0 && row_j0));
@@ -930,17 +794,21 @@ extern "C" int nsid_local_align_strip(const float* S, const int64_t* s_off, cons
                         (const void*)fresh, (const void*)carry_h, (const void*)carry_i0, (const void*)carry_j0, (const void*)row_h,
                         (const void*)row_j, (const void*)row_i0, (const void*)row_j0, (const void*)open_h})
     NSID_REQUIRE(al_aligned(q, 4));
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  return NSID_OK;
+}
+}  // namespace
+
+extern "C" int nsid_local_align_strip(const float* S, const int64_t* s_off, const int* s_ld, const int* q_len, const int* x_len,
+                                      const int* row_base, const int* fresh, int npairs, int max_q_len, int max_x_len, float theta,
+                                      const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0, const int64_t* row_off,
+                                      float* row_h, int* row_j, int* row_i0, int* row_j0, float* open_h, void* stream) {
+  const int rc = align_strip_args(S, s_off, s_ld, q_len, x_len, row_base, fresh, npairs, max_q_len, max_x_len, AL_MAX_COLS, theta,
+                                  carry_off, carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
+  if (rc != NSID_OK || npairs == 0) return rc;
   nsid_count(NSID_C_local_align_strip);
-  // 256 threads own every column of a pair up to 1024; above that 1024 threads do (the results do not depend on it)
-  if (max_x_len <= 256 * AL_CPT) {
-    nsid_took("local_align_strip_kernel<256>");
-    return launch_align_strip<256>(st, npairs, S, s_off, s_ld, q_len, x_len, row_base, fresh, max_q_len, max_x_len, theta, carry_off,
-                                   carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
-  }
-  nsid_took("local_align_strip_kernel<1024>");
-  return launch_align_strip<1024>(st, npairs, S, s_off, s_ld, q_len, x_len, row_base, fresh, max_q_len, max_x_len, theta, carry_off,
-                                  carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
+  AL_LAUNCH(local_align_strip_kernel, max_x_len, npairs, align_strip_lds_bytes(max_x_len), static_cast<hipStream_t>(stream), S, s_off,
+            s_ld, q_len, x_len, row_base, fresh, max_q_len, max_x_len, max_x_len + 2, theta, carry_off, carry_h, carry_i0, carry_j0,
+            row_off, row_h, row_j, row_i0, row_j0, open_h);
 }
 
 namespace {
@@ -986,34 +854,14 @@ extern "C" int nsid_local_align_panels(const float* S, const int64_t* s_off, con
                                        float theta, const int64_t* carry_off, float* carry_h, int* carry_i0, int* carry_j0,
                                        const int64_t* halo_off, float* halo_h, int* halo_i0, int* halo_j0, const int64_t* row_off,
                                        float* row_h, int* row_j, int* row_i0, int* row_j0, float* open_h, void* stream) {
-  NSID_REQUIRE(npairs >= 0 && max_q_len >= 0 && max_q_len <= AL_MAX_ROWS && max_x_len >= 0 && max_x_len <= AL_MAX_SONG_ROWS &&
-               panel_cols >= 2 && panel_cols <= AL_MAX_COLS && theta == theta);
-  if (npairs == 0) return NSID_OK;
-  NSID_REQUIRE(s_off && s_ld && q_len && x_len && row_base && fresh && carry_off && halo_off && row_off && open_h);
-  NSID_REQUIRE(halo_h && halo_i0 && halo_j0);                 // every pair has the two carried rows' cells
-  NSID_REQUIRE(max_q_len == 0 || (row_h && row_j && row_i0 && row_j0));
-  NSID_REQUIRE(max_x_len == 0 || (carry_h && carry_i0 && carry_j0));
-  NSID_REQUIRE((max_q_len == 0 || max_x_len == 0) || S);
-  NSID_REQUIRE(al_aligned(s_off, 8) && al_aligned(carry_off, 8) && al_aligned(halo_off, 8) && al_aligned(row_off, 8));
-  for (const void* q : {(const void*)S, (const void*)s_ld, (const void*)q_len, (const void*)x_len, (const void*)row_base,
-                        (const void*)fresh, (const void*)carry_h, (const void*)carry_i0, (const void*)carry_j0, (const void*)halo_h,
-                        (const void*)halo_i0, (const void*)halo_j0, (const void*)row_h, (const void*)row_j, (const void*)row_i0,
-                        (const void*)row_j0, (const void*)open_h})
-    NSID_REQUIRE(al_aligned(q, 4));
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t lds = align_panels_lds_bytes(max_q_len, panel_cols);
+  NSID_REQUIRE(panel_cols >= 2 && panel_cols <= AL_MAX_COLS);
+  const int rc = align_strip_args(S, s_off, s_ld, q_len, x_len, row_base, fresh, npairs, max_q_len, max_x_len, AL_MAX_SONG_ROWS, theta,
+                                  carry_off, carry_h, carry_i0, carry_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
+  if (rc != NSID_OK || npairs == 0) return rc;
+  NSID_REQUIRE(halo_off && halo_h && halo_i0 && halo_j0);     // every pair has the two carried rows' cells
+  NSID_REQUIRE(al_aligned(halo_off, 8) && al_aligned(halo_h, 4) && al_aligned(halo_i0, 4) && al_aligned(halo_j0, 4));
   nsid_count(NSID_C_local_align_panels);
-  // 256 threads own every column of a panel up to 1024; above that 1024 threads do (the results do not depend on it)
-  if (panel_cols <= 256 * AL_CPT) {
-    nsid_took("local_align_panels_kernel<256>");
-    NSID_LAUNCH_LDS((local_align_panels_kernel<256>), dim3(npairs), dim3(256), lds, st, S, s_off, s_ld, q_len, x_len, row_base, fresh,
-                    max_q_len, max_x_len, panel_cols, theta, carry_off, carry_h, carry_i0, carry_j0, halo_off, halo_h, halo_i0, halo_j0,
-                    row_off, row_h, row_j, row_i0, row_j0, open_h);
-    return nsid_launch_status();
-  }
-  nsid_took("local_align_panels_kernel<1024>");
-  NSID_LAUNCH_LDS((local_align_panels_kernel<1024>), dim3(npairs), dim3(1024), lds, st, S, s_off, s_ld, q_len, x_len, row_base, fresh,
-                  max_q_len, max_x_len, panel_cols, theta, carry_off, carry_h, carry_i0, carry_j0, halo_off, halo_h, halo_i0, halo_j0,
-                  row_off, row_h, row_j, row_i0, row_j0, open_h);
-  return nsid_launch_status();
+  AL_LAUNCH(local_align_panels_kernel, panel_cols, npairs, align_panels_lds_bytes(max_q_len, panel_cols),
+            static_cast<hipStream_t>(stream), S, s_off, s_ld, q_len, x_len, row_base, fresh, max_q_len, max_x_len, panel_cols, theta,
+            carry_off, carry_h, carry_i0, carry_j0, halo_off, halo_h, halo_i0, halo_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
 }

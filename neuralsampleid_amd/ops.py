@@ -2394,24 +2394,19 @@ def _align_strip(name, panel_cols, S, s_off, s_ld, q_len, x_len, theta, row_base
         return rows[0], rows[1], rows[2], rows[3], row_off, open_h
     t32 = torch.from_numpy(np.stack([s_ld, q_len, x_len, row_base, (fresh != 0).astype(np.int64)]).astype(np.int32)).to(dev)
     t64 = torch.from_numpy(np.stack([np.where(full, s_off, 0), carry_off, row_off])).to(dev)
-    cells = float((q_len * x_len).sum())
-    if panel_cols is None:
-        _tk(None, 4.0 * cells + 16.0 * total + 48.0 * float(x_len.sum()), lambda: call(
-            "nsid_local_align_strip", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), npairs,
-            int(q_len.max()), int(x_len.max()), theta, _p(t64[1]), _p(carry[0]), _p(carry[1]), _p(carry[2]), _p(t64[2]), _p(rows[0]),
-            _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(open_h), _stream()), (npairs, int(q_len.max()), int(x_len.max()), 1))
-        return rows[0], rows[1], rows[2], rows[3], row_off, open_h
-    hsize = 2 * (q_len + 2)
-    halo_off = torch.from_numpy(np.cumsum(hsize) - hsize).to(dev)
-    hn = int(hsize.sum())
-    halo = (torch.empty((hn,), device=dev, dtype=torch.float32), torch.empty((hn,), device=dev, dtype=torch.int32),
-            torch.empty((hn,), device=dev, dtype=torch.int32))
-    panels = float(((x_len + panel_cols - 1) // panel_cols).sum())
-    _tk(None, 4.0 * cells + 16.0 * total + 48.0 * float(x_len.sum()) + 24.0 * panels * float(hn), lambda: call(
-        "nsid_local_align_panels", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), npairs,
-        int(q_len.max()), int(x_len.max()), panel_cols, theta, _p(t64[1]), _p(carry[0]), _p(carry[1]), _p(carry[2]), _p(halo_off),
-        _p(halo[0]), _p(halo[1]), _p(halo[2]), _p(t64[2]), _p(rows[0]), _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(open_h), _stream()),
-        (npairs, int(q_len.max()), int(x_len.max()), panel_cols))
+    nbytes = 4.0 * float((q_len * x_len).sum()) + 16.0 * total + 48.0 * float(x_len.sum())
+    halo = ()                            # the entry's arguments behind the carry; the panels' (live until the launch is enqueued)
+    if panel_cols is not None:
+        hsize = 2 * (q_len + 2)
+        hn = int(hsize.sum())
+        halo = (torch.from_numpy(np.cumsum(hsize) - hsize).to(dev), torch.empty((hn,), device=dev, dtype=torch.float32),
+                torch.empty((hn,), device=dev, dtype=torch.int32), torch.empty((hn,), device=dev, dtype=torch.int32))
+        nbytes += 24.0 * float(((x_len + panel_cols - 1) // panel_cols).sum()) * float(hn)
+    _tk(None, nbytes, lambda: call(
+        "nsid_" + name, _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), npairs, int(q_len.max()),
+        int(x_len.max()), *(() if panel_cols is None else (panel_cols,)), theta, _p(t64[1]), _p(carry[0]), _p(carry[1]), _p(carry[2]),
+        *(_p(t) for t in halo), _p(t64[2]), _p(rows[0]), _p(rows[1]), _p(rows[2]), _p(rows[3]), _p(open_h), _stream()),
+        (npairs, int(q_len.max()), int(x_len.max()), 1 if panel_cols is None else panel_cols))
     return rows[0], rows[1], rows[2], rows[3], row_off, open_h
 
 
@@ -2455,13 +2450,9 @@ def align_occurrences(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, 
         return occ, occ_score, n_occ
     t32 = torch.from_numpy(np.stack([n_rows, first_row] + ([] if span is None else [span])).astype(np.int32)).to(dev)
     t64 = torch.from_numpy(np.ascontiguousarray(row_off)).to(dev)
-    if span is not None:
-        _tk("align_occurrences_kernel", 16.0 * float(n_rows.sum()), lambda: call(
-            "nsid_align_occurrences_span", _p(row_h), _p(row_j), _p(row_i0), _p(row_j0), _p(t64), _p(t32[0]), _p(t32[1]), _p(t32[2]),
-            npairs, int(n_rows.max()), min_score, top, _p(occ), _p(occ_score), _p(n_occ), _stream()), (npairs, int(n_rows.max()), 0, top))
-        return occ, occ_score, n_occ
+    entry, with_span = ("nsid_align_occurrences", ()) if span is None else ("nsid_align_occurrences_span", (_p(t32[2]),))
     _tk("align_occurrences_kernel", 16.0 * float(n_rows.sum()), lambda: call(
-        "nsid_align_occurrences", _p(row_h), _p(row_j), _p(row_i0), _p(row_j0), _p(t64), _p(t32[0]), _p(t32[1]), npairs,
+        entry, _p(row_h), _p(row_j), _p(row_i0), _p(row_j0), _p(t64), _p(t32[0]), _p(t32[1]), *with_span, npairs,
         int(n_rows.max()), min_score, top, _p(occ), _p(occ_score), _p(n_occ), _stream()), (npairs, int(n_rows.max()), 0, top))
     return occ, occ_score, n_occ
 
