@@ -99,7 +99,9 @@ int nsid_row_tiles(int M);
  * "stem7_stat" and "stem7_bwd" (rows = clips * pooled rows B*Hp, cols = pooled columns Wp: the [2][nsid_stem7_partials(rows, cols, 0)][64]
  * statistics sums / nsid_stem7_partials(rows, cols, 1) sets of the backward's partial sums, one per workgroup);
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
- * per-split top-64 lists of its first phase), "flat_l2_topk_coarse" (the same rows / cols: the pre-filter's per-split lists). */
+ * per-split top-64 lists of its first phase), "flat_l2_topk_coarse" (the same rows / cols: the pre-filter's per-split lists),
+ * "align_paths" (rows x cols = ONE box: its step codes, 2 bits a cell, rows x ceil(cols / 4) bytes; a launch needs the sum over its
+ * boxes). */
 long nsid_workspace_bytes(const char* op, long rows, long cols);
 
 /* ---- 1x1 convolution / Linear as a row GEMM on MFMA (fp32 accumulate) ------------------------------------
@@ -856,6 +858,32 @@ int nsid_local_align_panels(const float* S, const int64_t* s_off, const int* s_l
 int nsid_align_occurrences_span(const float* row_h, const int* row_j, const int* row_i0, const int* row_j0, const int64_t* row_off,
                                 const int* n_rows, const int* first_row, const int* span, int npairs, int max_rows, float min_score,
                                 int top, int* occ, float* occ_score, int* n_occ, void* stream);
+/* The path of an occurrence: which song row each of its query rows was aligned to (csrc/align.hip). The walks above keep a cell's
+ * origin and drop its predecessor; the path comes back from the occurrence's own box. For an occurrence (i0, i1, j0, j1) of a pair, the
+ * rule above on the box S[i0..i1][j0..j1] alone (everything outside it H = 0, no origin), with the predecessor ("from") of every cell
+ * kept, and the from pointers followed back from the box's last cell, gives cell for cell the path of the whole matrix; it ends at the
+ * box's first cell, and the last cell's H has the bits of the occurrence's score ("Alignment paths", has the proof).
+ * align_paths: one workgroup per box, many boxes in one launch. Box p is n_rows[p] x n_cols[p] cells at S + s_off[p] with row stride
+ *   s_ld[p] (device int64 / int32, as local_align takes them: a box of a larger matrix is an offset and that matrix's stride).
+ *   i_base[p], j_base[p] (device int32 >= 0, base + side <= 2^31 - 1; a null array stands for zeros) are added to every output
+ *   coordinate. The forward pass is the rule, every operation one fp32 operation; per cell it keeps the step taken, 2 bits: 0 none,
+ *   1 = (1,1), 2 = (1,2), 3 = (2,1); a cell with H = 0 keeps 0. The codes of box p are workspace: n_rows x ceil(n_cols / 4) bytes at
+ *   dirs + dir_off[p] (device int64; nsid_workspace_bytes("align_paths", n_rows, n_cols) per box), column c of row i in bits
+ *   2 (c % 4) .. of byte i ceil(n_cols / 4) + c / 4; its content after the launch means nothing, and two boxes' parts must not overlap.
+ *   Outputs: path_len[p] = the cells of the path, at most min(n_rows, n_cols) since every step advances both indices; the cells in
+ *   forward order at path_off[p] + t (device int64), t < path_len[p]: path_i, path_j (int32, base added) and path_s (S at the cell);
+ *   slots from path_len[p] on are not written; end_h[p] = the last cell's H. Status values of path_len:
+ *     0   the box has no row or no column (end_h = 0);
+ *    -1   the last cell's H is not positive, or the trace does not end at the box's first cell: the box is not an occurrence of this S
+ *         and theta. No path slot is written; end_h is still the last cell's H;
+ *    -2   a side is negative, n_rows > NSID_ALIGN_PATH_MAX, n_cols > max_cols (the host's bound for this launch, itself at most
+ *         NSID_ALIGN_PATH_MAX), or a base is outside its range: the box is not read, end_h = 0. A longer occurrence is refused, not split.
+ *   No atomics, no scratch; a box's result depends on nothing but the box. A NaN theta, max_cols outside [0, NSID_ALIGN_PATH_MAX], a
+ *   null or misaligned pointer: NSID_EINVAL before any launch; nboxes == 0 launches nothing. Launches count on "align_paths". */
+#define NSID_ALIGN_PATH_MAX 4096 /* rows, and columns, of a box at most */
+int nsid_align_paths(const float* S, const int64_t* s_off, const int* s_ld, const int* n_rows, const int* n_cols, const int* i_base,
+                     const int* j_base, int nboxes, int max_cols, float theta, const int64_t* path_off, const int64_t* dir_off,
+                     uint8_t* dirs, int* path_len, int* path_i, int* path_j, float* path_s, float* end_h, void* stream);
 
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed

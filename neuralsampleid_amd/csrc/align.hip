@@ -27,6 +27,11 @@
 // in LDS and stores the row's halo. The occurrence kernel takes the width of a group's window per run (include/nsid.h, below
 // nsid_align_occurrences).
 //
+// align_paths: the path of an occurrence (which song row each query row was aligned to), which the walk drops: the rule on the
+// occurrence's own box with every cell's step kept, 2 bits a cell in a byte workspace, then the steps followed back from the box's
+// last cell. That is cell for cell the path of the whole matrix (include/nsid.h, nsid_align_paths; the proof is in DESIGN.md,
+// "Alignment paths"). Its row is written beside al_walk, not through it: the three kernels above are measured and stay as they are.
+//
 // The helpers beside the walk are what the strip and the panels share: the rows of a pair without cells (al_no_cells), the fill of
 // the three LDS rows (al_fill), the carry out (al_carry_out) and open_h (al_open_h). On the host one macro picks 256 or 1024 threads
 // for all three entries (AL_LAUNCH), and one function checks the arguments the strip and the panels share (align_strip_args).
@@ -630,6 +635,157 @@ size_t align_panels_lds_bytes(int max_q, int pcols) {
     return nsid_launch_status();                                                                        \
   } while (0)
 
+// ---- align_paths: the path of an occurrence, traced back through its own box ----------------------------------------------------------
+// (include/nsid.h nsid_align_paths.) One workgroup per box. The forward pass is the rule on the box alone from zeros; a thread owns
+// AL_PATH_CPT = 4 neighbouring columns, so that their step codes (2 bits a cell: 0 none, 1 = (1,1), 2 = (1,2), 3 = (2,1)) are one
+// byte that it alone stores: no atomics. Three rotating LDS rows of H alone (two zeros in front of each, a row a multiple of 16 bytes),
+// one barrier per row that orders LDS only, S read AL_RB rows at a time as in al_walk. This is the second statement of the rule in
+// this file: al_walk keeps origins, reduces a row's best key and serves three measured kernels, so it stays as it is and the cell is
+// restated here in the same words. The traceback reads codes that other threads stored to memory, so it stands behind a
+// __syncthreads(), whose fences cover memory; thread 0 follows the codes from the last cell (a path has at most min(rows, columns)
+// cells: every step advances both indices) and leaves the cells in LDS, over the dead rows; the workgroup stores them in forward order.
+constexpr int AL_PATH_MAX = NSID_ALIGN_PATH_MAX;
+constexpr int AL_PATH_CPT = 4;
+static_assert(AL_PATH_MAX <= 1024 * AL_PATH_CPT, "1024 threads own AL_PATH_CPT columns each");
+static_assert(AL_PATH_MAX <= (1 << 15), "a path cell is kept as i << 16 | j in LDS");
+// floats of one LDS row: columns -2 .. max_cols + 3 (a thread writes its four columns whole), rounded to 16 bytes
+constexpr int al_path_ld(int max_cols) { return (max_cols + 2 + AL_PATH_CPT + 3) / 4 * 4; }
+size_t align_paths_lds_bytes(int max_cols) { return 3 * (size_t)al_path_ld(max_cols) * sizeof(float); }
+static_assert(3 * (size_t)al_path_ld(AL_PATH_MAX) * sizeof(float) + 1024 <= NSID_LDS_MAX, "three rows of H in LDS");
+
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void align_paths_kernel(
+    const float* __restrict__ S, const int64_t* __restrict__ s_off, const int* __restrict__ s_ld, const int* __restrict__ n_rows,
+    const int* __restrict__ n_cols, const int* __restrict__ i_base, const int* __restrict__ j_base, int max_cols, float theta,
+    const int64_t* __restrict__ path_off, const int64_t* __restrict__ dir_off, uint8_t* dirs, int* __restrict__ path_len,
+    int* __restrict__ path_i, int* __restrict__ path_j, float* __restrict__ path_s, float* __restrict__ end_h) {
+  extern __shared__ __attribute__((aligned(16))) char al_smem[];
+  __shared__ int s_n;
+  const int p = blockIdx.x, tid = threadIdx.x;
+  const int nr = n_rows[p], nc = n_cols[p];
+  const int ib0 = i_base ? i_base[p] : 0, jb0 = j_base ? j_base[p] : 0;
+  // every return below is uniform over the workgroup and ahead of every barrier
+  if (nr < 0 || nc < 0 || nr > AL_PATH_MAX || nc > max_cols || ib0 < 0 || jb0 < 0 || (int64_t)ib0 + nr > 0x7fffffffLL ||
+      (int64_t)jb0 + nc > 0x7fffffffLL) {                   // the box is not read
+    if (tid == 0) {
+      path_len[p] = -2;
+      end_h[p] = 0.f;
+    }
+    return;
+  }
+  if (nr == 0 || nc == 0) {
+    if (tid == 0) {
+      path_len[p] = 0;
+      end_h[p] = 0.f;
+    }
+    return;
+  }
+  const int ld = al_path_ld(max_cols);
+  float* row = reinterpret_cast<float*>(al_smem);
+  for (int t = tid; t < 3 * ld; t += THREADS) row[t] = 0.f;            // H = +0.0 everywhere, the two cells in front of each row for good
+  __syncthreads();
+
+  const float* Sp = S + s_off[p];
+  const size_t sld = (size_t)s_ld[p];
+  uint8_t* dp = dirs + dir_off[p];
+  const int dld = (nc + AL_PATH_CPT - 1) / AL_PATH_CPT;                // bytes of a row of step codes
+  const int j = AL_PATH_CPT * tid;                                      // this thread's first column
+  const bool mine = j < nc;                                             // tid < dld
+  float* cur = row;                      // row i; element c + 2 is column c
+  float* prev1 = row + 2 * ld;           // row i - 1
+  float* prev2 = row + ld;               // row i - 2
+  for (int ib = 0; ib < nr; ib += AL_RB) {
+    float sv[AL_RB][AL_PATH_CPT];
+    if (mine) {                          // columns past the box's end read its last column and are not used
+#pragma unroll
+      for (int r = 0; r < AL_RB; ++r) {
+        const float* rp = Sp + (size_t)min(ib + r, nr - 1) * sld;
+#pragma unroll
+        for (int c = 0; c < AL_PATH_CPT; ++c) sv[r][c] = rp[min(j + c, nc - 1)];
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < AL_RB; ++r) {
+      const int i = ib + r;
+      if (i >= nr) break;                // uniform
+      if (mine) {
+        // columns j - 2 .. j + 2 of row i - 1 and j - 1 .. j + 2 of row i - 2
+        const f32x4 a = *reinterpret_cast<const f32x4*>(prev1 + j), b = *reinterpret_cast<const f32x4*>(prev2 + j);
+        const float p1[AL_PATH_CPT + 1] = {a[0], a[1], a[2], a[3], prev1[j + 4]};
+        const float p2[AL_PATH_CPT + 1] = {b[0], b[1], b[2], b[3], prev2[j + 4]};
+        float h[AL_PATH_CPT];
+        unsigned codes = 0;
+#pragma unroll
+        for (int c = 0; c < AL_PATH_CPT; ++c) {
+          const float e = sv[r][c] - theta;
+          float best = 0.f;
+          unsigned from = 0;
+          const float h11 = p1[c + 1], h12 = p1[c], h21 = p2[c + 1];
+          if (h11 > best) {
+            best = h11;
+            from = 1;
+          }
+          if (h12 > best) {
+            best = h12;
+            from = 2;
+          }
+          if (h21 > best) {
+            best = h21;
+            from = 3;
+          }
+          const float v = best + e;
+          const bool pos = v > 0.f;
+          h[c] = pos ? v : 0.f;
+          codes |= ((pos && j + c < nc) ? from : 0u) << (2 * c);
+        }
+        *reinterpret_cast<float2*>(cur + j + 2) = float2{h[0], h[1]};
+        *reinterpret_cast<float2*>(cur + j + 4) = float2{h[2], h[3]};
+        dp[(size_t)i * dld + tid] = (uint8_t)codes;
+      }
+      float* t = prev2;
+      prev2 = prev1;
+      prev1 = cur;
+      cur = t;
+      // the row's barrier orders LDS only: the step codes, which nobody reads before the walk ends, stay in flight over it
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+    }
+  }
+  __syncthreads();                       // memory too: every thread's step codes are visible to the workgroup
+
+  int* cells = reinterpret_cast<int*>(al_smem);       // the path, last cell first; thread 0 has read the last H before it writes here
+  if (tid == 0) {
+    const float hl = prev1[nc - 1 + 2];
+    int n = -1;
+    if (hl > 0.f) {
+      int i = nr - 1, c = nc - 1;
+      n = 0;
+      for (;;) {
+        cells[n++] = (i << 16) | c;
+        const unsigned code = ((unsigned)dp[(size_t)i * dld + (c >> 2)] >> (2 * (c & 3))) & 3u;
+        if (code == 0) break;            // the path's first cell
+        i -= code == 3 ? 2 : 1;
+        c -= code == 2 ? 2 : 1;
+        if (i < 0 || c < 0) break;       // never with the codes of this pass (a chosen predecessor has H > 0, so it lies in the box)
+      }
+      if (i != 0 || c != 0) n = -1;      // the path starts elsewhere: the box is not an occurrence
+    }
+    s_n = n;
+    path_len[p] = n;
+    end_h[p] = hl;
+  }
+  __syncthreads();
+  const int n = s_n;
+  const int64_t po = path_off[p];
+  for (int k = tid; k < n; k += THREADS) {
+    const int cell = cells[n - 1 - k], i = cell >> 16, c = cell & 0xffff;
+    path_i[po + k] = ib0 + i;
+    path_j[po + k] = jb0 + c;
+    path_s[po + k] = Sp[(size_t)i * sld + c];
+  }
+}
+
 // ---- align_occurrences ------------------------------------------------------------------------------------------------------------
 // One workgroup per run of rows. A group's rows lie within [i0, i0 + AL_SPAN], so a row is its group's representative when no row of
 // that window with the same origin beats it; the kept rows are one bit each in LDS (a wave's ballot per 64 rows), and a kept row's rank
@@ -864,4 +1020,22 @@ extern "C" int nsid_local_align_panels(const float* S, const int64_t* s_off, con
   AL_LAUNCH(local_align_panels_kernel, panel_cols, npairs, align_panels_lds_bytes(max_q_len, panel_cols),
             static_cast<hipStream_t>(stream), S, s_off, s_ld, q_len, x_len, row_base, fresh, max_q_len, max_x_len, panel_cols, theta,
             carry_off, carry_h, carry_i0, carry_j0, halo_off, halo_h, halo_i0, halo_j0, row_off, row_h, row_j, row_i0, row_j0, open_h);
+}
+
+extern "C" int nsid_align_paths(const float* S, const int64_t* s_off, const int* s_ld, const int* n_rows, const int* n_cols,
+                                const int* i_base, const int* j_base, int nboxes, int max_cols, float theta, const int64_t* path_off,
+                                const int64_t* dir_off, uint8_t* dirs, int* path_len, int* path_i, int* path_j, float* path_s,
+                                float* end_h, void* stream) {
+  NSID_REQUIRE(nboxes >= 0 && max_cols >= 0 && max_cols <= AL_PATH_MAX && theta == theta);
+  if (nboxes == 0) return NSID_OK;
+  NSID_REQUIRE(s_off && s_ld && n_rows && n_cols && path_off && dir_off && path_len && end_h);
+  NSID_REQUIRE(max_cols == 0 || (S && dirs && path_i && path_j && path_s));
+  NSID_REQUIRE(al_aligned(s_off, 8) && al_aligned(path_off, 8) && al_aligned(dir_off, 8));
+  for (const void* q : {(const void*)S, (const void*)s_ld, (const void*)n_rows, (const void*)n_cols, (const void*)i_base,
+                        (const void*)j_base, (const void*)path_len, (const void*)path_i, (const void*)path_j, (const void*)path_s,
+                        (const void*)end_h})
+    NSID_REQUIRE(al_aligned(q, 4));
+  nsid_count(NSID_C_align_paths);
+  AL_LAUNCH(align_paths_kernel, max_cols, nboxes, align_paths_lds_bytes(max_cols), static_cast<hipStream_t>(stream), S, s_off, s_ld,
+            n_rows, n_cols, i_base, j_base, max_cols, theta, path_off, dir_off, dirs, path_len, path_i, path_j, path_s, end_h);
 }

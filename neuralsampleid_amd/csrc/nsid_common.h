@@ -291,6 +291,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(pair_sim) X(local_align)   /* align.hip: the score matrices of (query, song) pairs and their local alignment */ \
   X(local_align_strip) X(align_occurrences)   /* align.hip: the alignment in strips with carried rows, and the occurrences of a run of rows */ \
   X(local_align_panels) X(align_occurrences_span)   /* align.hip: the strip walk in column panels (songs past 4096 rows), and the occurrences with a span per run */ \
+  X(align_paths)          /* align.hip: the paths of occurrences, traced back through their boxes */ \
   X(bf16_rows) X(flat_l2_topk_coarse) X(flat_l2_rescore)   /* search.hip: the certified bf16 pre-filter of the exact search */ \
   X(flat_l2_topk_excl) X(flat_l2_topk_wide_excl)   /* search.hip: nsid_flat_l2_topk_excl (_wide: its d > 256 kernel) */
 

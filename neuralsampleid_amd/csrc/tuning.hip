@@ -107,5 +107,7 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
     return nsid_l2_ws_bytes(rows, cols, 64);
   if (strcmp(op, "flat_l2_topk_coarse") == 0)   // the same rows / cols: the pre-filter's candidate lists per (row, split)
     return nsid_l2_coarse_ws_bytes(rows, cols);
+  if (strcmp(op, "align_paths") == 0)        // rows x cols = one box: 2 bits a cell, a row of codes in whole bytes
+    return rows * ((cols + 3) / 4);
   return -1;
 }

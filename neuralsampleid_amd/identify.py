@@ -46,10 +46,17 @@ nsid_local_align_panels). The walk then goes over the song in panels of 4096 col
 
     idx = SampleIndex(model, long_songs=True)
 
+The alignment behind an occurrence's four corners: paths traces every occurrence back to its row-by-row mapping (which song row is
+query row i? a tempo estimate over all cells; how straight the path is), recomputed from the occurrence's own box, bit for bit the
+path of the walk that found it (include/nsid.h nsid_align_paths).
+
+    paths = idx.paths(q_fp, occs, threshold=0.6)                     # [AlignmentPath]: q_rows, r_rows, scores, slope, song_row(...)
+
 Not here: the MAP rule (rerank.vote_map_clf), audio decoding, a command line, sharding over GPUs; songs past 16384 rows (past 4096
 without long_songs), queries past that outside scan (refused, not split), rerank=True against a song past 4096 rows, gap steps other
 than (1,1), (1,2), (2,1), hipGraph capture of the alignment, an alignment threshold calibrated on real audio, parsing sample100-ext's
-annotation files."""
+annotation files; paths of rerank=True occurrences, of occurrences past 4096 rows on a side, and a Scanner that keeps its rows for
+paths (the caller passes the recording's rows)."""
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
@@ -792,6 +799,75 @@ class SampleIndex:
         flat.sort(key=lambda t: (-t[0].score, t[1], t[2]))
         return [t[0] for t in flat]
 
+    @torch.no_grad()
+    def paths(self, fp: torch.Tensor, occurrences: Sequence["Occurrence"], threshold: Optional[float] = None, row_hop_s=None,
+              row_len_s=None, s_budget_bytes: int = 1 << 30) -> List["AlignmentPath"]:
+        """The alignment path of every occurrence, in order: which song row each query row of the occurrence was aligned to
+        (AlignmentPath). occurrences: what align, locate, scan or links returned for these rows with this threshold, any selection of
+        them in any order; fp: the query's rows as align / locate / scan(fp=...) took them (for a scan the whole recording's rows, since
+        an occurrence's q_rows are global; for links the rows of the song that was the query). The song is Occurrence.song.
+
+        An occurrence's path is recovered from its own box: the scores of its query rows against its song rows are recomputed by
+        pair_sim (an element's bits depend on its two rows alone) and traced by align_paths, bit for bit the path of the walk that found
+        it. Consecutive occurrences go in chunks whose score workspace (4 bytes a cell) stays under s_budget_bytes (one occurrence is
+        always allowed): one pair_sim, one align_paths and one copy to the host per chunk.
+
+        Refused before anything is launched: CPU rows, a missing or NaN threshold, an unknown song (KeyError), an occurrence whose rows
+        leave fp or the song, an occurrence of more than ops.ALIGN_PATH_MAX rows on either side (not split). Refused afterwards
+        (ValueError naming the occurrence): a box that is not an occurrence of these rows at this threshold, or whose last H differs in
+        any bit from Occurrence.score; either means that the occurrences were not made from these rows with this threshold. That is
+        also what happens to the occurrences of rerank=True, whose cells are the classifier's scores: their paths are not built."""
+        if threshold is None:
+            raise ValueError("paths: threshold has no default: pass the one the occurrences were found with")
+        threshold = float(threshold)
+        if threshold != threshold:
+            raise ValueError("paths: threshold is NaN")
+        timing = self._row_timing(row_hop_s, row_len_s)
+        self._check_fp(fp, "paths")
+        occurrences = list(occurrences)
+        Lq, P = int(fp.shape[0]), len(occurrences)
+        box = np.zeros((P, 5), dtype=np.int64)          # i0, rows, first ref row, columns, j0
+        for n, o in enumerate(occurrences):
+            if not isinstance(o, Occurrence):
+                raise TypeError(f"paths: occurrences[{n}] is not an Occurrence")
+            first, rows = self._song_rows[self.code(o.song)][:2]
+            (i0, i1), (j0, j1) = o.q_rows, o.r_rows
+            if not (0 <= i0 <= i1 < Lq and 0 <= j0 <= j1 < rows):
+                raise ValueError(f"paths: occurrences[{n}] ({o.song!r}, query rows {o.q_rows}, song rows {o.r_rows}) leaves the "
+                                 f"{Lq} query rows or the song's {rows} rows")
+            if max(i1 - i0, j1 - j0) >= ops.ALIGN_PATH_MAX:
+                raise ValueError(f"paths: occurrences[{n}] ({o.song!r}) spans {i1 - i0 + 1} x {j1 - j0 + 1} rows, past the limit of "
+                                 f"{ops.ALIGN_PATH_MAX}; longer occurrences are refused, not split")
+            box[n] = (i0, i1 - i0 + 1, first + j0, j1 - j0 + 1, j0)
+        out: List[AlignmentPath] = []
+        if P == 0:
+            return out
+        fp, ref, budget = fp.contiguous(), self.fingerprints, int(s_budget_bytes)
+        lo = 0
+        while lo < P:
+            hi, used = lo, 0
+            while hi < P and (hi == lo or used + 4 * int(box[hi, 1] * box[hi, 3]) <= budget):
+                used += 4 * int(box[hi, 1] * box[hi, 3])
+                hi += 1
+            b = box[lo:hi]
+            S, s_off, s_ld = ops.pair_sim(fp, ref, b[:, 0], b[:, 1], b[:, 2], b[:, 3])
+            plen, poff, pi, pj, ps, end_h = ops.align_paths(S, s_off, s_ld, b[:, 1], b[:, 3], threshold, i_base=b[:, 0], j_base=b[:, 4])
+            host = torch.cat([plen, end_h.view(torch.int32), pi, pj, ps.view(torch.int32)]).cpu().numpy()      # the one copy
+            nb, total = hi - lo, int(pi.numel())
+            plen, end_h = host[:nb], host[nb:2 * nb].view(np.float32)
+            pi, pj, ps = (host[2 * nb + u * total: 2 * nb + (u + 1) * total] for u in range(3))
+            ps = ps.view(np.float32)
+            for n in range(nb):
+                o = occurrences[lo + n]
+                if plen[n] < 1 or end_h[n].tobytes() != np.float32(o.score).tobytes():
+                    raise ValueError(f"paths: occurrences[{lo + n}] ({o.song!r}, query rows {o.q_rows}, song rows {o.r_rows}, score "
+                                     f"{o.score!r}) is not an occurrence of these rows at threshold {threshold!r} (path_len "
+                                     f"{int(plen[n])}, last H {float(end_h[n])!r})")
+                a, e = int(poff[n]), int(poff[n]) + int(plen[n])
+                out.append(alignment_path(o, pi[a:e], pj[a:e], ps[a:e], threshold, timing))
+            lo = hi
+        return out
+
     @staticmethod
     def _windows(Lq, k):
         """the vote windows of a query of Lq rows: (starts, W)"""
@@ -1174,6 +1250,58 @@ def _occurrence(song, score, i0, i1, j0, j1, timing) -> Occurrence:
         qt, rt = (i0 * hop, i1 * hop + length), (j0 * hop, j1 * hop + length)
     return Occurrence(song, float(score), (int(i0), int(i1)), (int(j0), int(j1)), qt, rt,
                       (j1 - j0) / (i1 - i0) if i1 > i0 else float("nan"))
+
+
+class AlignmentPath(NamedTuple):
+    """The path of an occurrence (SampleIndex.paths): cell t aligns query row q_rows[t] with song row r_rows[t]; both arrays rise
+    strictly, by (1, 1), (1, 2) or (2, 1) a step, from the occurrence's first rows to its last. The statistics need no calibrated
+    score; no cut-off on them is set anywhere."""
+    occurrence: "Occurrence"
+    q_rows: np.ndarray                            # (cells,) int32, global query rows
+    r_rows: np.ndarray                            # (cells,) int32, song rows
+    scores: np.ndarray                            # (cells,) float32: S at the cell
+    steps: Tuple[int, int, int]                   # the steps taken: (1, 1), (1, 2), (2, 1); cells - 1 in all
+    passing: int                                  # the cells whose own fp32 S - threshold is positive
+    slope: Optional[float]                        # fp64 least-squares line, song row = slope * query row + intercept: song rows per query
+    intercept: Optional[float]                    # row, the tempo estimate over the whole path; None for a path of one cell
+    rms_rows: Optional[float]                     # root mean square of the path's deviation from that line, in song rows
+    q_time: Optional[np.ndarray]                  # (cells,) float64: the start of each row in seconds, when the row timing is known
+    r_time: Optional[np.ndarray]
+
+    def song_row(self, q_row):
+        """the song row (fractional) aligned with a query row: piecewise linear along the path, clamped to its ends"""
+        return np.interp(q_row, self.q_rows, self.r_rows)
+
+    def song_time(self, t):
+        """the second of the song aligned with second t of the query, as song_row; needs the row timing"""
+        if self.q_time is None:
+            raise ValueError("AlignmentPath.song_time: the row timing is not known (row_hop_s / row_len_s, or an index with a front end)")
+        return np.interp(t, self.q_time, self.r_time)
+
+
+def alignment_path(occurrence, q_rows, r_rows, scores, threshold, timing=None) -> AlignmentPath:
+    """an AlignmentPath from a path's cells in forward order; timing: (row hop, row length) in seconds or None"""
+    q = np.ascontiguousarray(q_rows, dtype=np.int32)
+    r = np.ascontiguousarray(r_rows, dtype=np.int32)
+    s = np.ascontiguousarray(scores, dtype=np.float32)
+    if not (q.ndim == 1 and q.size >= 1 and q.shape == r.shape == s.shape):
+        raise ValueError("alignment_path: q_rows, r_rows and scores must be three equal, non-empty one-dimensional arrays")
+    di, dj = np.diff(q.astype(np.int64)), np.diff(r.astype(np.int64))
+    steps = tuple(int(((di == a) & (dj == b)).sum()) for a, b in ((1, 1), (1, 2), (2, 1)))
+    if sum(steps) != q.size - 1:
+        raise ValueError("alignment_path: the cells do not follow one another by (1, 1), (1, 2) or (2, 1)")
+    passing = int(((s - np.float32(threshold)).astype(np.float32) > 0).sum())
+    slope = intercept = rms = None
+    if q.size > 1:
+        x, y = q.astype(np.float64), r.astype(np.float64)
+        xm, ym = x.mean(), y.mean()
+        slope = float(((x - xm) * (y - ym)).sum() / ((x - xm) ** 2).sum())
+        intercept = float(ym - slope * xm)
+        rms = float(np.sqrt(((y - (slope * x + intercept)) ** 2).mean()))
+    qt = rt = None
+    if timing is not None:
+        qt, rt = q.astype(np.float64) * timing[0], r.astype(np.float64) * timing[0]
+    return AlignmentPath(occurrence, q, r, s, steps, passing, slope, intercept, rms, qt, rt)
 
 
 def interval_recall(found, truth, min_cover: float = 0.5):

@@ -2457,6 +2457,73 @@ def align_occurrences(row_h, row_j, row_i0, row_j0, row_off, n_rows, first_row, 
     return occ, occ_score, n_occ
 
 
+ALIGN_PATH_MAX = _H["NSID_ALIGN_PATH_MAX"]             # rows, and columns, of a box of align_paths at most
+
+
+def align_paths(S, s_off, s_ld, n_rows, n_cols, theta, i_base=None, j_base=None):
+    """The paths of many occurrences in one launch (nsid_align_paths), one workgroup per box: box p is the n_rows[p] x n_cols[p] cells
+    of an occurrence (i1 - i0 + 1 by j1 - j0 + 1) at S[s_off[p]] with row stride s_ld[p], the rule of include/nsid.h runs on the box
+    alone with every cell's step kept, and the steps are followed back from the box's last cell; that is cell for cell the path of the
+    whole matrix.
+
+    S: flat fp32 scores on the device. s_off / s_ld / n_rows / n_cols / i_base / j_base: host integer sequences, one entry per box,
+    checked here, then uploaded; i_base / j_base (default zeros) are added to the output coordinates. Returns (path_len (boxes,) int32,
+    path_off int64 numpy, path_i, path_j int32, path_s fp32, end_h (boxes,) fp32): box p's cells in forward order at path_off[p] + t,
+    t < path_len[p], of the three flat tensors, which hold min(n_rows, n_cols) slots per box; the slots past path_len are not
+    written. path_len = 0: the box has no row or no column; -1: the box is not an occurrence of this S and theta (its last H is not
+    positive, or the trace does not end at its first cell); -2: a side is past ALIGN_PATH_MAX, the box was not read (such a box is
+    passed on, not refused, and where it lies is not looked at). end_h: the last cell's H, the occurrence's score bit for bit."""
+    name = "align_paths"
+    if not isinstance(S, torch.Tensor):
+        raise TypeError(f"{name}: S must be a torch tensor on the GPU")
+    _chk(S)
+    S = S.reshape(-1)
+    s_off = _align_seq(name, "s_off", s_off)
+    nb = s_off.size
+    s_ld, n_rows, n_cols = (_align_seq(name, w, v, nb) for w, v in (("s_ld", s_ld), ("n_rows", n_rows), ("n_cols", n_cols)))
+    i_base, j_base = (np.zeros(nb, np.int64) if v is None else _align_seq(name, w, v, nb) for w, v in (("i_base", i_base), ("j_base", j_base)))
+    theta = float(theta)
+    if theta != theta:
+        raise ValueError(f"{name}: theta is NaN")
+    if nb and (n_rows.min() < 0 or n_cols.min() < 0):
+        raise ValueError(f"{name}: a side is negative")
+    if nb and (n_rows.max() >= 2 ** 31 or n_cols.max() >= 2 ** 31):
+        raise ValueError(f"{name}: a side does not fit an int32")
+    ok = (n_rows <= ALIGN_PATH_MAX) & (n_cols <= ALIGN_PATH_MAX)       # the others get -2 from the kernel, which does not read them
+    full = ok & (n_rows > 0) & (n_cols > 0)
+    if nb and ok.any() and (i_base[ok].min() < 0 or j_base[ok].min() < 0 or (i_base + n_rows)[ok].max() > 2 ** 31 - 1
+                            or (j_base + n_cols)[ok].max() > 2 ** 31 - 1):
+        raise ValueError(f"{name}: every box needs 0 <= base and base + side <= 2^31 - 1")
+    if nb and full.any() and (s_off[full].min() < 0 or (s_ld[full] < n_cols[full]).any() or s_ld[full].max() >= 2 ** 31
+                              or (s_off + (n_rows - 1) * s_ld + n_cols)[full].max() > S.numel()):
+        raise ValueError(f"{name}: a box (n_rows rows of s_ld >= n_cols floats) leaves S")
+    dev = S.device
+    slots = np.where(ok, np.minimum(n_rows, n_cols), 0)
+    path_off = np.cumsum(slots) - slots
+    dsize = np.asarray([lib.nsid_workspace_bytes(b"align_paths", int(r), int(c)) if f else 0 for r, c, f in zip(n_rows, n_cols, full)],
+                       dtype=np.int64)
+    dir_off = np.cumsum(dsize) - dsize
+    total = int(slots.sum())
+    path_len = torch.empty((nb,), device=dev, dtype=torch.int32)
+    end_h = torch.empty((nb,), device=dev, dtype=torch.float32)
+    path_i = torch.empty((total,), device=dev, dtype=torch.int32)
+    path_j = torch.empty((total,), device=dev, dtype=torch.int32)
+    path_s = torch.empty((total,), device=dev, dtype=torch.float32)
+    if nb == 0:
+        return path_len, path_off, path_i, path_j, path_s, end_h
+    dirs = torch.empty((max(int(dsize.sum()), 1),), device=dev, dtype=torch.uint8)
+    keep = np.where(ok, 1, 0)            # a box past the limit keeps its sides (the kernel answers -2) and nothing else
+    t32 = torch.from_numpy(np.stack([np.where(full, s_ld, 0), n_rows, n_cols, i_base * keep, j_base * keep]).astype(np.int32)).to(dev)
+    t64 = torch.from_numpy(np.stack([np.where(full | ~ok, s_off, 0), path_off, dir_off])).to(dev)
+    max_cols = int(n_cols[ok].max()) if ok.any() else 0
+    cells = float((n_rows * n_cols)[full].sum())
+    _tk(None, 4.25 * cells + 12.0 * total, lambda: call(
+        "nsid_align_paths", _p(S), _p(t64[0]), _p(t32[0]), _p(t32[1]), _p(t32[2]), _p(t32[3]), _p(t32[4]), nb, max_cols, theta,
+        _p(t64[1]), _p(t64[2]), _p(dirs), _p(path_len), _p(path_i), _p(path_j), _p(path_s), _p(end_h), _stream()),
+        (nb, int(n_rows[ok].max()) if ok.any() else 0, max_cols, 1))
+    return path_len, path_off, path_i, path_j, path_s, end_h
+
+
 # ------------------------------------------------------------------------------------------------ classifier re-rank (csrc/rerank.hip)
 CLF_C, CLF_KP, CLF_MAX_N, CLF_QCHUNK = _H["NSID_CLF_C"], _H["NSID_CLF_KP"], _H["NSID_CLF_MAX_N"], _H["NSID_CLF_QCHUNK"]
 CLF_WIDTHS = (512, 640, 768, 1024)      # in_dim of the four encoder sizes ('t', 's', 'm', default); 4 heads of C / 4
