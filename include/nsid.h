@@ -101,7 +101,8 @@ int nsid_row_tiles(int M);
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
  * per-split top-64 lists of its first phase), "flat_l2_topk_coarse" (the same rows / cols: the pre-filter's per-split lists),
  * "align_paths" (rows x cols = ONE box: its step codes, 2 bits a cell, rows x ceil(cols / 4) bytes; a launch needs the sum over its
- * boxes). */
+ * boxes), "cohort_stats" (rows = the rows of the call, cols = the cohort's rows M: two fp64 sums per chunk of NSID_COHORT_CHUNK cohort
+ * rows and row, the rows padded to a multiple of 32). */
 long nsid_workspace_bytes(const char* op, long rows, long cols);
 
 /* ---- 1x1 convolution / Linear as a row GEMM on MFMA (fp32 accumulate) ------------------------------------
@@ -884,6 +885,47 @@ int nsid_align_occurrences_span(const float* row_h, const int* row_j, const int*
 int nsid_align_paths(const float* S, const int64_t* s_off, const int* s_ld, const int* n_rows, const int* n_cols, const int* i_base,
                      const int* j_base, int nboxes, int max_cols, float theta, const int64_t* path_off, const int64_t* dir_off,
                      uint8_t* dirs, int* path_len, int* path_i, int* path_j, float* path_s, float* end_h, void* stream);
+/* Cohort score normalisation (csrc/cohort.hip, csrc/align.hip): a cell of S read against the background of its two rows, so that
+ * theta, min_score and an occurrence's score are in background sigmas instead of raw dots (DESIGN.md section 7 has the reasoning). No
+ * sigma threshold has been measured on real audio.
+ * The cohort: M fp32 rows c_0 .. c_{M-1} of width d, NSID_COHORT_MIN <= M <= NSID_COHORT_MAX; d, ld and alignment as pair_sim takes them.
+ * The statistics of a row x:
+ *     s_m = x . c_m, pair_sim's dot for the same two rows bit for bit (the k-ordered fp32 fmaf chain on v_mfma_f32_32x32x2_f32, the
+ *           split pairing up to d = 256 and the wide pairing above; the chain is symmetric in its two rows)
+ *     in fp64:  A = sum_m s_m,  B = sum_m s_m s_m   (s_m s_m is exact in fp64, so fma(s, s, B) and B + s s are the same number)
+ *     mu64 = A / M;  var64 = max(B / M - mu64 mu64, 1e-12), every operation an fp64 operation rounded once to nearest, nothing contracted
+ *     mu = (float) mu64,  rs = (float)(1.0 / sqrt(var64)): an IEEE fp64 square root, an IEEE fp64 division, one rounding to fp32 each
+ *   The order of the two sums is part of the rule, a function of M and these constants alone (not of the rows of the call, of a row's
+ *   place in it or of the launch); A and B take it alike, every addition an fp64 addition:
+ *     the cohort is cut into chunks of NSID_COHORT_CHUNK = 256 rows, chunk c = rows [256 c, min(256 c + 256, M));
+ *     inside a chunk, column class r = m mod 32 is summed in ascending m from +0.0: a[r] = (..((0 + t_r) + t_{r+32}) + ..); a class
+ *       without a row (the last chunk) stays +0.0;
+ *     the 32 class sums are combined by the butterfly a[r] <- a[r] + a[r ^ dist] for dist = 1, 2, 4, 8, 16, all r at once per dist; the
+ *       chunk's sum is a[0] (all 32 are equal then);
+ *     the chunk sums are added in ascending chunk order, starting from chunk 0's value.
+ * cohort_stats: mu[i], rs[i] of row i of x (n x d) for i < n. ws: nsid_workspace_bytes("cohort_stats", n, M) bytes, 8-byte aligned; its
+ *   content before and after means nothing. One wave per (32 rows, chunk) leaves the chunk's sums in ws, a second launch adds the
+ *   chunks in order: no atomics, no scratch, a row's result depends on the row and the cohort alone. d outside pair_sim's widths, M
+ *   outside its range, n < 0, a null or misaligned pointer: NSID_EINVAL before any launch; n == 0 launches nothing. Counts on
+ *   "cohort_stats" (one per call).
+ * The normalised cell, for query row i and song row j of pair p with raw score s = pair_sim's S_p[i][j]; each line one fp32 operation
+ * rounded once, nothing contracted:
+ *     a = s - q_mu[q_start[p] + i];   zq = a * q_rs[q_start[p] + i]
+ *     b = s - x_mu[x_start[p] + j];   zx = b * x_rs[x_start[p] + j]
+ *     t = zq + zx;   S'_p[i][j] = 0.5f * t
+ * pair_sim_norm: pair_sim with S' stored in place of S. Every argument up to s_len is pair_sim's (the tile table, the bounds, the
+ *   widths); q_mu, q_rs (nq floats) and x_mu, x_rs (nx floats) are indexed by the ABSOLUTE row of q and x. pair_sim's refusals, and the
+ *   four arrays non-null and 4-byte aligned. Counts on "pair_sim_norm"; nsid_pair_sim itself is untouched. The walks, the strips, the
+ *   panels, the occurrences and the paths take S' as they take S. */
+#define NSID_COHORT_CHUNK 256   /* cohort rows per chunk of the ordered sums */
+#define NSID_COHORT_MIN 32      /* cohort rows at least */
+#define NSID_COHORT_MAX 65536   /* cohort rows at most */
+int nsid_cohort_stats(const float* x, int ldx, int n, const float* cohort, int ldc, int M, int d, float* mu, float* rs, void* ws,
+                      void* stream);
+int nsid_pair_sim_norm(const float* q, int ldq, int nq, const float* x, int ldx, long nx, int d, const int* q_start, const int* q_len,
+                       const int64_t* x_start, const int* x_len, const int64_t* s_off, const int* s_ld, int npairs, const int* tiles,
+                       int ntiles, float* S, int64_t s_len, const float* q_mu, const float* q_rs, const float* x_mu, const float* x_rs,
+                       void* stream);
 
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed

@@ -13,7 +13,7 @@ CSRC = os.path.join(PKG, "csrc")
 ROOT = os.path.dirname(PKG)
 LIB = os.path.join(PKG, "libnsid_hip.so")
 OBJ_DIR = os.path.join(PKG, "csrc", "_obj")
-SOURCES = ["tuning.hip", "gemm.hip", "gemm256.hip", "wsgemm.hip", "ffn_fused.hip", "ffn256_fused.hip", "mrconv_fused.hip", "wgrad.hip", "wgrad256.hip", "bn.hip", "knn.hip", "mr.hip", "ntxent.hip", "baseline_loss.hip", "misc.hip", "frontend.hip", "augment.hip", "augment_fx.hip", "stems.hip", "cqt.hip", "search.hip", "vote.hip", "diag_vote.hip", "align.hip", "rerank.hip", "clf_train.hip", "dsact.hip", "resnet.hip"]
+SOURCES = ["tuning.hip", "gemm.hip", "gemm256.hip", "wsgemm.hip", "ffn_fused.hip", "ffn256_fused.hip", "mrconv_fused.hip", "wgrad.hip", "wgrad256.hip", "bn.hip", "knn.hip", "mr.hip", "ntxent.hip", "baseline_loss.hip", "misc.hip", "frontend.hip", "augment.hip", "augment_fx.hip", "stems.hip", "cqt.hip", "search.hip", "vote.hip", "diag_vote.hip", "align.hip", "cohort.hip", "rerank.hip", "clf_train.hip", "dsact.hip", "resnet.hip"]
 HEADERS = ["nsid_common.h", "fft512.h", "clf_common.h"]         # internal headers: a change in one rebuilds every source
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function",

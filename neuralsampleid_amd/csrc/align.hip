@@ -7,6 +7,8 @@
 // pair_sim: one wave per 32x32 tile of one pair's S = q x^T; the tiles of all pairs come from a host-built table (largest pairs first).
 // The dot is the chain of csrc/search.hip: one k-ordered fp32 fmaf chain on v_mfma_f32_32x32x2_f32, the same for every (i, j) whichever
 // tile, lane or pair holds it (up to d = 256 the pairing of l2_topk_split_kernel, above it the pairing of l2_topk_wide_kernel).
+// pair_sim_norm is the same tile with another store epilogue: the cell normalised by the cohort statistics of its two rows
+// (csrc/cohort.hip computes them); the walks below do not know which of the two wrote their S.
 //
 // The walk (al_walk): one workgroup per pair walks the rows of S_p; threads own columns. The rule (stated in include/nsid.h) needs rows
 // i - 1 and i - 2 only, so all columns of a row are independent: three rotating rows of (H, origin) cells in LDS, 8 bytes a cell, one
@@ -100,6 +102,72 @@ __global__ __launch_bounds__(64) void pair_sim_kernel(const float* __restrict__ 
   for (int g = 0; g < 16; ++g) {
     const int row = i0 + (g & 3) + 8 * (g >> 2) + 4 * h;
     if (row < Lq && col < Lr) sp[(size_t)row * ld] = acc[g];
+  }
+}
+
+// ---- pair_sim_norm (nsid_pair_sim_norm): pair_sim_kernel with the cohort-normalised cell in its store epilogue, the statistics
+// indexed by the absolute rows of q and x. pair_sim_kernel is measured and stays as it is, instruction for instruction; the tile is
+// restated here in the same words, as align_paths restates the walk's cell.
+
+// the normalised cell of include/nsid.h ("cohort score normalisation"): five fp32 operations, each rounded once, none contracted
+__device__ __forceinline__ float sim_norm_cell(float s, float mq, float rq, float mx, float rx) {
+#pragma clang fp contract(off)
+  const float zq = (s - mq) * rq;
+  const float zx = (s - mx) * rx;
+  const float sum = zq + zx;
+  return 0.5f * sum;
+}
+
+template <bool WIDE>
+__global__ __launch_bounds__(64) void pair_sim_norm_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x,
+                                                           int ldx, long nx, int d, const int* __restrict__ q_start,
+                                                           const int* __restrict__ q_len, const int64_t* __restrict__ x_start,
+                                                           const int* __restrict__ x_len, const int64_t* __restrict__ s_off,
+                                                           const int* __restrict__ s_ld, int npairs, const int* __restrict__ tiles,
+                                                           float* __restrict__ S, int64_t s_len, const float* __restrict__ q_mu,
+                                                           const float* __restrict__ q_rs, const float* __restrict__ x_mu,
+                                                           const float* __restrict__ x_rs) {
+  const int lane = lane_id(), r = lane & 31, h = lane >> 5;
+  const int* t = tiles + 3 * (size_t)blockIdx.x;
+  const int p = t[0], i0 = t[1], j0 = t[2];
+  if (p < 0 || p >= npairs) return;
+  const int Lq = q_len[p], Lr = x_len[p];
+  const long qs = q_start[p], xs = x_start[p], so = s_off[p], ld = s_ld[p];
+  // the caller checks the table; this only keeps a bad entry in bounds (uniform)
+  if (i0 < 0 || j0 < 0 || i0 >= Lq || j0 >= Lr || qs < 0 || xs < 0 || qs + Lq > nq || xs + Lr > nx || ld < Lr || so < 0 ||
+      so + (long)(Lq - 1) * ld + Lr > s_len)
+    return;
+  const float* qp = q + (size_t)(qs + min(i0 + r, Lq - 1)) * ldq;
+  const float* xp = x + (size_t)(xs + min(j0 + r, Lr - 1)) * ldx;
+  f32x16 acc = {};
+  const int nb = d / 8;
+  if (!WIDE) {
+    qp += 4 * h;
+    xp += 4 * h;
+    for (int b = 0; b < nb; b += 2) {                 // d % 16 == 0: two blocks' loads in flight per step
+      const f32x4 a0 = ld4(qp + 8 * b), c0 = ld4(xp + 8 * b), a1 = ld4(qp + 8 * b + 8), c1 = ld4(xp + 8 * b + 8);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[e], c0[e], acc, 0, 0, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[e], c1[e], acc, 0, 0, 0);
+    }
+  } else {
+    for (int b = 0; b < nb; ++b) {
+      const f32x4 a0 = ld4(qp + 8 * b), a1 = ld4(qp + 8 * b + 4), c0 = ld4(xp + 8 * b), c1 = ld4(xp + 8 * b + 4);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a0[1] : a0[0], h ? c0[1] : c0[0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a0[3] : a0[2], h ? c0[3] : c0[2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a1[1] : a1[0], h ? c1[1] : c1[0], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(h ? a1[3] : a1[2], h ? c1[3] : c1[2], acc, 0, 0, 0);
+    }
+  }
+  const int col = j0 + r;
+  float* sp = S + so + col;
+  if (col >= Lr) return;                       // after the last MFMA: a lane without a column stores nothing
+  const float mx = x_mu[xs + col], rx = x_rs[xs + col];
+#pragma unroll
+  for (int g = 0; g < 16; ++g) {
+    const int row = i0 + (g & 3) + 8 * (g >> 2) + 4 * h;
+    if (row < Lq) sp[(size_t)row * ld] = sim_norm_cell(acc[g], q_mu[qs + row], q_rs[qs + row], mx, rx);
   }
 }
 
@@ -914,6 +982,27 @@ extern "C" int nsid_pair_sim(const float* q, int ldq, int nq, const float* x, in
   } else {
     NSID_LAUNCH(pair_sim_kernel<false>, dim3(ntiles), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, d, q_start, q_len, x_start, x_len, s_off,
                 s_ld, npairs, tiles, S, s_len);
+  }
+  return nsid_launch_status();
+}
+
+extern "C" int nsid_pair_sim_norm(const float* q, int ldq, int nq, const float* x, int ldx, long nx, int d, const int* q_start,
+                                  const int* q_len, const int64_t* x_start, const int* x_len, const int64_t* s_off, const int* s_ld,
+                                  int npairs, const int* tiles, int ntiles, float* S, int64_t s_len, const float* q_mu,
+                                  const float* q_rs, const float* x_mu, const float* x_rs, void* stream) {
+  NSID_REQUIRE(sim_d_ok(d) && nq >= 0 && nx >= 0 && npairs >= 0 && ntiles >= 0 && s_len >= 0);
+  if (npairs == 0 || ntiles == 0) return NSID_OK;
+  NSID_REQUIRE(q && x && q_start && q_len && x_start && x_len && s_off && s_ld && tiles && S && q_mu && q_rs && x_mu && x_rs);
+  NSID_REQUIRE(ldq >= d && ldq % 4 == 0 && ldx >= d && ldx % 4 == 0 && nsid_aligned16(q) && nsid_aligned16(x));
+  NSID_REQUIRE(al_aligned(q_mu, 4) && al_aligned(q_rs, 4) && al_aligned(x_mu, 4) && al_aligned(x_rs, 4));
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  nsid_count(NSID_C_pair_sim_norm);
+  if (d > 256) {
+    NSID_LAUNCH(pair_sim_norm_kernel<true>, dim3(ntiles), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, d, q_start, q_len, x_start, x_len,
+                s_off, s_ld, npairs, tiles, S, s_len, q_mu, q_rs, x_mu, x_rs);
+  } else {
+    NSID_LAUNCH(pair_sim_norm_kernel<false>, dim3(ntiles), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, d, q_start, q_len, x_start, x_len,
+                s_off, s_ld, npairs, tiles, S, s_len, q_mu, q_rs, x_mu, x_rs);
   }
   return nsid_launch_status();
 }

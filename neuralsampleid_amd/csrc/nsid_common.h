@@ -292,6 +292,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(local_align_strip) X(align_occurrences)   /* align.hip: the alignment in strips with carried rows, and the occurrences of a run of rows */ \
   X(local_align_panels) X(align_occurrences_span)   /* align.hip: the strip walk in column panels (songs past 4096 rows), and the occurrences with a span per run */ \
   X(align_paths)          /* align.hip: the paths of occurrences, traced back through their boxes */ \
+  X(cohort_stats) X(pair_sim_norm)   /* cohort.hip, align.hip: the cohort statistics of rows, and the score matrices normalised by them */ \
   X(bf16_rows) X(flat_l2_topk_coarse) X(flat_l2_rescore)   /* search.hip: the certified bf16 pre-filter of the exact search */ \
   X(flat_l2_topk_excl) X(flat_l2_topk_wide_excl)   /* search.hip: nsid_flat_l2_topk_excl (_wide: its d > 256 kernel) */
 
@@ -411,4 +412,6 @@ int nsid_ffn256_fused_launch(const void* x, const void* w1, const float* b1, con
 void nsid_l2_plan(long nq, long nx, int* splits, int* chunk);
 long nsid_l2_ws_bytes(long nq, long nx, int k);
 long nsid_l2_coarse_ws_bytes(long nq, long nx);      // the same for nsid_flat_l2_topk_coarse's lists of NSID_SEARCH_MAX_K entries
+// cohort.hip: the per-chunk partial sums of nsid_cohort_stats for n rows against a cohort of M rows
+long nsid_cohort_ws_bytes(long n, long M);
 extern void* g_gemm_trace_host;        // gemm.hip: the buffer installed by nsid_debug_gemm_trace (nullptr = none)

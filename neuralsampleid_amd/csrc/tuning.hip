@@ -109,5 +109,7 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
     return nsid_l2_coarse_ws_bytes(rows, cols);
   if (strcmp(op, "align_paths") == 0)        // rows x cols = one box: 2 bits a cell, a row of codes in whole bytes
     return rows * ((cols + 3) / 4);
+  if (strcmp(op, "cohort_stats") == 0)       // rows = the rows of the call, cols = the cohort's rows: two fp64 sums per (chunk, padded row)
+    return nsid_cohort_ws_bytes(rows, cols);
   return -1;
 }

@@ -199,6 +199,9 @@ class SampleIndex:
         self._song_of_nodes = None            # the same, -1 for a row without node matrices
         self._kp = None                       # (capacity N, C + 512): the candidates' [K | P] rows
         self.N = None                         # nodes per segment of the resident table
+        self._cohort = None                   # (M, d): the cohort of normalize=True, a copy (set_cohort)
+        self._stat = None                     # (mu, rs), (capacity,) fp32 each: the cohort statistics of the first _stat_done ref rows
+        self._stat_done = 0
         if model is not None:
             from .fingerprint import embedding_dim
             self._d = int(embedding_dim(model))
@@ -378,6 +381,65 @@ class SampleIndex:
         self._code[name] = code
         self._song_rows.append((lo, S, with_nodes))
         self.n_ref = hi
+
+    # ------------------------------------------------------------------------------------------------ cohort score normalisation
+    def set_cohort(self, rows: Optional[torch.Tensor] = None, size: int = 4096) -> None:
+        """The cohort of normalize=True (include/nsid.h, "cohort score normalisation"): unrelated rows against which every row's
+        scores are read, ops.COHORT_MIN <= M <= ops.COHORT_MAX of them. rows: an (M, d) device tensor, copied. Without rows:
+        M = min(size, n_dummy) of the dummy rows, those at positions floor(m n_dummy / M), copied, so that later adds change nothing.
+        One cohort per index; setting it drops the cached statistics of the resident rows."""
+        if rows is not None:
+            self._check_fp(rows, "set_cohort")
+            M = int(rows.shape[0])
+            if not ops.COHORT_MIN <= M <= ops.COHORT_MAX:
+                raise ValueError(f"set_cohort: a cohort of {M} rows is outside [{ops.COHORT_MIN}, {ops.COHORT_MAX}]")
+            cohort = rows.detach().clone().contiguous()
+        else:
+            size = int(size)
+            if not ops.COHORT_MIN <= size <= ops.COHORT_MAX:
+                raise ValueError(f"set_cohort: size = {size} is outside [{ops.COHORT_MIN}, {ops.COHORT_MAX}]")
+            M = min(size, self.n_dummy)
+            if M < ops.COHORT_MIN:
+                raise RuntimeError(f"set_cohort: the default cohort needs at least {ops.COHORT_MIN} dummy rows, the index holds "
+                                   f"{self.n_dummy}; pass rows=")
+            pos = (np.arange(M, dtype=np.int64) * self.n_dummy) // M
+            cohort = self._index.xb.index_select(0, torch.from_numpy(pos).to(self.device)).contiguous()
+        self._cohort, self._stat, self._stat_done = cohort, None, 0
+
+    def _need_cohort(self, what) -> torch.Tensor:
+        """the cohort of a normalize=True call: the one set, or the default one made now"""
+        if self._cohort is None:
+            if self.n_dummy < ops.COHORT_MIN:
+                raise RuntimeError(f"{what}: normalize=True needs a cohort and the index holds {self.n_dummy} dummy rows, fewer than "
+                                   f"the {ops.COHORT_MIN} of a default one: call set_cohort(rows=...) first")
+            self.set_cohort()
+        if self._d is not None and self._cohort.shape[1] != self._d:
+            raise ValueError(f"{what}: the cohort has d = {self._cohort.shape[1]}, the index d = {self._d}: call set_cohort again")
+        return self._cohort
+
+    def cohort_stats(self, fp: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(mu, rs) of every row of fp (rows, d) against the index's cohort: device fp32, what normalize=True uses for these rows"""
+        self._check_fp(fp, "cohort_stats")
+        return ops.cohort_stats(fp.contiguous(), self._need_cohort("cohort_stats"))
+
+    def _resident_stats(self, what):
+        """(mu, rs) of the n_ref resident rows: the rows added since the last normalised call are computed now, the others are kept"""
+        cohort = self._need_cohort(what)
+        if self._stat is None:
+            self._stat = tuple(torch.empty((0,), device=self.device, dtype=torch.float32) for _ in range(2))
+            self._stat_done = 0
+        if self._stat_done < self.n_ref:
+            new = ops.cohort_stats(self.fingerprints[self._stat_done:self.n_ref], cohort)
+            self._stat = tuple(self._grown(t, self.n_ref) for t in self._stat)
+            for t, v in zip(self._stat, new):
+                t[self._stat_done:self.n_ref].copy_(v)
+            self._stat_done = self.n_ref
+        return self._stat[0][: self.n_ref], self._stat[1][: self.n_ref]
+
+    def _norm(self, what, q, resident_query=False):
+        """ops.pair_sim's norm= for query rows q against the resident rows (resident_query: q is the resident rows themselves)"""
+        ref = self._resident_stats(what)
+        return (ref if resident_query else ops.cohort_stats(q, self._cohort)) + ref
 
     # ------------------------------------------------------------------------------------------------ asking
     def _query(self, specs, wave, fp, nodes, rerank):
@@ -581,8 +643,11 @@ class SampleIndex:
             return f.step * f.hop / f.fs, f.n_frames * f.hop / f.fs
         return None
 
-    def _align_checks(self, what, fp, songs, threshold, top, nodes, rerank):
+    def _align_checks(self, what, fp, songs, threshold, top, nodes, rerank, normalize=False):
         """every refusal of align, before the device is touched for the shapes; returns (song codes, threshold)"""
+        if normalize and rerank:
+            raise ValueError(f"{what}: normalize=True is not offered with rerank=True: the classifier's cells are probabilities and "
+                             "their threshold already has a meaning")
         if rerank:
             self._check_rerank()
         elif threshold is None:
@@ -622,7 +687,7 @@ class SampleIndex:
     @torch.no_grad()
     def align(self, fp: torch.Tensor, songs: Sequence[str], threshold: Optional[float] = None, min_score: float = 0.0, top: int = 16,
               nodes: Optional[torch.Tensor] = None, rerank: bool = False, return_rows: bool = False, row_hop_s=None, row_len_s=None,
-              s_budget_bytes: int = 1 << 30):
+              s_budget_bytes: int = 1 << 30, normalize: bool = False):
         """Where in the query, and where in each named resident song, does the query sample the song? The local alignment of
         include/nsid.h ("locating a sample") of the query's rows against each song's rows, one pair per song, all songs in one
         pair_sim + local_align per chunk; a chunk's score workspace (4 Lq Lr bytes per song) stays under s_budget_bytes.
@@ -638,9 +703,16 @@ class SampleIndex:
         local_align_panels in strips of ALIGN_MAX_ROWS query rows chained through the carry, then align_occurrences with its span; the
         workspace is then per strip. Such pairs are reported in chunks of their own, whose tuples are (codes, S, s_off, s_ld, x_len,
         row_h, row_j, row_i0, row_j0, row_off, occ, occ_score, n_occ): the origin unpacked (row_i0, row_j0) where the others have
-        row_org, and S, s_off, s_ld as lists with one entry per strip. Refused with rerank=True."""
+        row_org, and S, s_off, s_ld as lists with one entry per strip. Refused with rerank=True.
+
+        normalize=True: every cell is cohort-normalised (set_cohort; include/nsid.h, "cohort score normalisation"): the query rows'
+        statistics are computed in this call, the resident rows' are cached, and pair_sim stores 0.5 (zq + zx) in place of the dot, so
+        threshold, min_score and Occurrence.score are in background sigmas. threshold still has no default: no sigma threshold has
+        been measured on real audio either. Refused with rerank=True; without a cohort the default one is taken from the dummy rows."""
         timing = self._row_timing(row_hop_s, row_len_s)
-        codes, threshold = self._align_checks("align", fp, songs, threshold, top, nodes, rerank)
+        codes, threshold = self._align_checks("align", fp, songs, threshold, top, nodes, rerank, normalize)
+        if normalize:
+            self._need_cohort("align")
         Lq, top = int(fp.shape[0]), int(top)
         out: List[List[Occurrence]] = [[] for _ in codes]
         chunks = []
@@ -649,7 +721,8 @@ class SampleIndex:
         fp = fp.contiguous()
         if not rerank:
             occ, sc = self._align_pairs(fp, np.zeros(len(codes), np.int64), np.full(len(codes), Lq, np.int64), codes, threshold,
-                                        min_score, top, int(s_budget_bytes), chunks if return_rows else None)
+                                        min_score, top, int(s_budget_bytes), chunks if return_rows else None,
+                                        self._norm("align", fp) if normalize else None)
             for p, c in enumerate(codes):
                 for (i0, i1, j0, j1), s in zip(occ[p].tolist(), sc[p].tolist()):
                     if i0 < 0:
@@ -684,14 +757,14 @@ class SampleIndex:
             lo = hi
         return (out, {"chunks": chunks}) if return_rows else out
 
-    def _align_pairs(self, q, q_start, q_len, codes, threshold, min_score, top, budget, chunks=None):
+    def _align_pairs(self, q, q_start, q_len, codes, threshold, min_score, top, budget, chunks=None, norm=None):
         """The alignment of pairs (rows q_start[p] .. + q_len[p] of q, resident song codes[p]) over fingerprint scores, for align and
         links: (occ (pairs, top, 4), occ_score (pairs, top)) on the host. Consecutive pairs go in chunks whose score workspace stays
         under `budget` bytes (one pair is always allowed). A chunk of pairs within ALIGN_MAX_ROWS x ALIGN_MAX_COLS is one pair_sim and
         one local_align; a chunk of longer pairs (long_songs) goes strip by strip of ALIGN_MAX_ROWS query rows, all its pairs in one
         pair_sim and one local_align_panels per strip, the first fresh and the others from the carry, and then through
         align_occurrences with the span 2 (x_len - 1); its workspace is that of one strip. chunks: a list that receives align's
-        return_rows tuples."""
+        return_rows tuples. norm: ops.pair_sim's norm= for all rows of q and the resident rows (normalize=True), else None."""
         ref = self.fingerprints
         P = len(codes)
         x_start_all = np.asarray([self._song_rows[c][0] for c in codes], dtype=np.int64)
@@ -711,19 +784,19 @@ class SampleIndex:
                 hi += 1
             qs, ql, x_start, x_len = q_start[lo:hi], q_len[lo:hi], x_start_all[lo:hi], x_len_all[lo:hi]
             if not long[lo]:
-                S, s_off, s_ld = ops.pair_sim(q, ref, qs, ql, x_start, x_len)
+                S, s_off, s_ld = ops.pair_sim(q, ref, qs, ql, x_start, x_len, norm=norm)
                 res = ops.local_align(S, s_off, s_ld, ql, x_len, threshold, min_score, top)
                 if chunks is not None:
                     chunks.append((list(codes[lo:hi]), S, s_off, s_ld, x_len) + tuple(res[3:]) + tuple(res[:3]))
             else:
-                res, kept = self._align_strips(q, ref, qs, ql, x_start, x_len, threshold, min_score, top, chunks is not None)
+                res, kept = self._align_strips(q, ref, qs, ql, x_start, x_len, threshold, min_score, top, chunks is not None, norm)
                 if chunks is not None:
                     chunks.append((list(codes[lo:hi]),) + kept + (x_len,) + tuple(res[3:]) + tuple(res[:3]))
             occ_all[lo:hi], sc_all[lo:hi] = res[0].cpu().numpy(), res[1].cpu().numpy()
             lo = hi
         return occ_all, sc_all
 
-    def _align_strips(self, q, ref, q_start, q_len, x_start, x_len, threshold, min_score, top, keep):
+    def _align_strips(self, q, ref, q_start, q_len, x_start, x_len, threshold, min_score, top, keep, norm=None):
         """one chunk of long pairs: ((occ, occ_score, n_occ, row_h, row_j, row_i0, row_j0, row_off), (S, s_off, s_ld lists per strip))"""
         dev, R = q.device, ops.ALIGN_MAX_ROWS
         carry, carry_off = ops.align_carry(x_len, dev, long_songs=True)
@@ -735,7 +808,7 @@ class SampleIndex:
         for lo in range(0, int(q_len.max()), R):
             n = np.clip(q_len - lo, 0, R)
             on = n > 0
-            S, s_off, s_ld = ops.pair_sim(q, ref, q_start[on] + lo, n[on], x_start[on], x_len[on], long_songs=True)
+            S, s_off, s_ld = ops.pair_sim(q, ref, q_start[on] + lo, n[on], x_start[on], x_len[on], long_songs=True, norm=norm)
             ops.local_align_panels(S, s_off, s_ld, n[on], x_len[on], threshold, np.full(int(on.sum()), lo, np.int64),
                                    np.full(int(on.sum()), 1 if lo == 0 else 0, np.int64), carry, carry_off[on], rows=rows,
                                    row_off=row_off[on] + lo)
@@ -751,7 +824,7 @@ class SampleIndex:
                n_songs: int = 5, exclude: Optional[str] = None, threshold: Optional[float] = None, min_score: float = 0.0,
                top: int = 16, rerank: bool = False, row_hop_s=None, row_len_s=None,
                leave_out: Optional[str] = None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
-               min_hits: int = DIAG_MIN_HITS) -> List["Occurrence"]:
+               min_hits: int = DIAG_MIN_HITS, normalize: bool = False) -> List["Occurrence"]:
         """The occurrences of resident songs in a query, one flat list sorted by score: encodes as identify does, finds the candidate
         songs (songs=None) and aligns the query against them.
 
@@ -766,8 +839,16 @@ class SampleIndex:
         min_hits hits in one diagonal bin of 2 bin_rows rows, ordered across windows by their best window count, then code. The
         sequence vote scores a candidate against the window's first rows, so it sees an excerpt only where it starts a window; the
         diagonal vote sees it anywhere in the window. Refused with rerank=True. bin_rows and min_hits have no measurement on real
-        audio behind them."""
+        audio behind them.
+
+        normalize=True: align's (threshold and scores in background sigmas; refused with rerank=True). The candidate search and
+        both votes run on L2 distances and are untouched."""
         vote, bin_rows, min_hits = _vote_options("locate", vote, bin_rows, min_hits, rerank)
+        if normalize and rerank:
+            raise ValueError("locate: normalize=True is not offered with rerank=True: the classifier's cells are probabilities and "
+                             "their threshold already has a meaning")
+        if normalize:
+            self._need_cohort("locate")
         if rerank:
             self._check_rerank()
         elif threshold is None:
@@ -794,14 +875,15 @@ class SampleIndex:
                 raise ValueError(f"locate: a query of {fp.shape[0]} rows is past the limit of {max_q}; longer inputs are "
                                  "refused, not split")
             songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank, leave_out, vote, bin_rows, min_hits)
-        per_song = self.align(fp, songs, threshold, min_score, top, nodes, rerank, row_hop_s=row_hop_s, row_len_s=row_len_s)
+        per_song = self.align(fp, songs, threshold, min_score, top, nodes, rerank, row_hop_s=row_hop_s, row_len_s=row_len_s,
+                              normalize=normalize)
         flat = [(o, c, n) for c, occs in enumerate(per_song) for n, o in enumerate(occs)]
         flat.sort(key=lambda t: (-t[0].score, t[1], t[2]))
         return [t[0] for t in flat]
 
     @torch.no_grad()
     def paths(self, fp: torch.Tensor, occurrences: Sequence["Occurrence"], threshold: Optional[float] = None, row_hop_s=None,
-              row_len_s=None, s_budget_bytes: int = 1 << 30) -> List["AlignmentPath"]:
+              row_len_s=None, s_budget_bytes: int = 1 << 30, normalize: bool = False) -> List["AlignmentPath"]:
         """The alignment path of every occurrence, in order: which song row each query row of the occurrence was aligned to
         (AlignmentPath). occurrences: what align, locate, scan or links returned for these rows with this threshold, any selection of
         them in any order; fp: the query's rows as align / locate / scan(fp=...) took them (for a scan the whole recording's rows, since
@@ -816,7 +898,11 @@ class SampleIndex:
         leave fp or the song, an occurrence of more than ops.ALIGN_PATH_MAX rows on either side (not split). Refused afterwards
         (ValueError naming the occurrence): a box that is not an occurrence of these rows at this threshold, or whose last H differs in
         any bit from Occurrence.score; either means that the occurrences were not made from these rows with this threshold. That is
-        also what happens to the occurrences of rerank=True, whose cells are the classifier's scores: their paths are not built."""
+        also what happens to the occurrences of rerank=True, whose cells are the classifier's scores: their paths are not built.
+
+        normalize=True: the occurrences were found with normalize=True (same cohort); the boxes are recomputed by pair_sim with the
+        same statistics, and AlignmentPath's scores are normalised cells. Occurrences of one kind with the flag of the other fail
+        the score check above."""
         if threshold is None:
             raise ValueError("paths: threshold has no default: pass the one the occurrences were found with")
         threshold = float(threshold)
@@ -843,6 +929,7 @@ class SampleIndex:
         if P == 0:
             return out
         fp, ref, budget = fp.contiguous(), self.fingerprints, int(s_budget_bytes)
+        norm = self._norm("paths", fp) if normalize else None
         lo = 0
         while lo < P:
             hi, used = lo, 0
@@ -850,7 +937,7 @@ class SampleIndex:
                 used += 4 * int(box[hi, 1] * box[hi, 3])
                 hi += 1
             b = box[lo:hi]
-            S, s_off, s_ld = ops.pair_sim(fp, ref, b[:, 0], b[:, 1], b[:, 2], b[:, 3])
+            S, s_off, s_ld = ops.pair_sim(fp, ref, b[:, 0], b[:, 1], b[:, 2], b[:, 3], norm=norm)
             plen, poff, pi, pj, ps, end_h = ops.align_paths(S, s_off, s_ld, b[:, 1], b[:, 3], threshold, i_base=b[:, 0], j_base=b[:, 4])
             host = torch.cat([plen, end_h.view(torch.int32), pi, pj, ps.view(torch.int32)]).cpu().numpy()      # the one copy
             nb, total = hi - lo, int(pi.numel())
@@ -904,7 +991,7 @@ class SampleIndex:
     def scanner(self, threshold: Optional[float] = None, min_score: float = 0.0, k_probe: int = 20, n_songs: int = 5, top: int = 16,
                 window_rows: Optional[int] = None, songs: Optional[Sequence[str]] = None, exclude: Optional[str] = None,
                 max_active: int = 64, row_hop_s=None, row_len_s=None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
-                min_hits: int = DIAG_MIN_HITS) -> "Scanner":
+                min_hits: int = DIAG_MIN_HITS, normalize: bool = False) -> "Scanner":
         """A Scanner over this index: a recording of any length, pushed in pieces of any sizes, is voted on and aligned in windows of
         W = window_rows or VOTE_MAX_CAND // k_probe rows (at most min(VOTE_MAX_CAND // k_probe, ALIGN_MAX_ROWS)), aligned to the global
         row index, so the result depends on the rows alone. The alignment is locate's rule, carried from window to window
@@ -913,7 +1000,8 @@ class SampleIndex:
         align). exclude: a song name that never votes. threshold has no default, as in align. With long_songs a window whose active
         songs include one of more than ALIGN_MAX_COLS rows goes through local_align_panels. vote="diagonal", bin_rows, min_hits:
         locate's (the window's vote is diag_votes', so an excerpt that starts deep inside a window, or lies wholly inside one, is
-        aligned in that window). Every refusal comes before any launch."""
+        aligned in that window). normalize=True: align's; a window's rows get their cohort statistics in one launch, the
+        resident rows' are cached. Every refusal comes before any launch."""
         vote, bin_rows, min_hits = _vote_options("scanner", vote, bin_rows, min_hits)
         if threshold is None:
             raise ValueError("scanner: threshold has no default for fingerprint scores (the reference has no such number and none has "
@@ -943,8 +1031,11 @@ class SampleIndex:
                 raise ValueError("scanner: a song is named twice")
             for c in fixed:
                 self._scan_song_ok(c)
-        return Scanner(self, fixed, threshold, min_score, k, n_songs, top, min(W, cap), None if exclude is None else self.code(exclude),
-                       max_active, self._row_timing(row_hop_s, row_len_s), vote, bin_rows, min_hits)
+        timing, exclude = self._row_timing(row_hop_s, row_len_s), None if exclude is None else self.code(exclude)
+        if normalize:
+            self._need_cohort("scanner")
+        return Scanner(self, fixed, threshold, min_score, k, n_songs, top, min(W, cap), exclude, max_active, timing, vote, bin_rows,
+                       min_hits, bool(normalize))
 
     def _scan_song_ok(self, c):
         if self._song_rows[c][1] > self._max_cols:
@@ -965,7 +1056,7 @@ class SampleIndex:
     def links(self, names: Optional[Sequence[str]] = None, k_probe: int = 20, n_songs: int = 5, threshold: Optional[float] = None,
               min_score: float = 0.0, top: int = 16, block_rows: int = 1 << 16, s_budget_bytes: int = 1 << 30, row_hop_s=None,
               row_len_s=None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
-              min_hits: int = DIAG_MIN_HITS) -> "CatalogueLinks":
+              min_hits: int = DIAG_MIN_HITS, normalize: bool = False) -> "CatalogueLinks":
         """Which resident songs share material with which others? The self-join of the catalogue: for every named song (default: all,
         in add order) the query is the song's own resident fingerprint rows (nothing is encoded again or copied to the host), and
         occurrences[name] is what locate(fp=those rows, leave_out=name, k_probe=..., n_songs=..., threshold=..., min_score=..., top=...)
@@ -984,7 +1075,9 @@ class SampleIndex:
         [K | P] rows, not the queries' projection, so a song's rows cannot be the classifier's query side.
 
         vote="diagonal", bin_rows, min_hits: locate's; the block's windows go through one diag_vote instead of seq_scores + song_vote,
-        and a partner sampled in the middle of a long song is a candidate by its diagonal, not by chance."""
+        and a partner sampled in the middle of a long song is a candidate by its diagonal, not by chance.
+
+        normalize=True: locate's; both sides of every pair are resident rows, so both take the cached resident statistics."""
         vote, bin_rows, min_hits = _vote_options("links", vote, bin_rows, min_hits)
         if threshold is None:
             raise ValueError("links: threshold has no default for fingerprint scores (the reference has no such number and none has "
@@ -1015,6 +1108,7 @@ class SampleIndex:
         query = [c for c in codes if rows_of[c] <= self._max_q and c not in too_long]
         out = {self.names[c]: [] for c in query}
         vote_top = min(ops.VOTE_MAX_TOP, max(n_songs, 1))
+        norm = self._norm("links", None, resident_query=True) if normalize else None
         lo = 0
         while lo < len(query):
             hi, used = lo, 0
@@ -1022,12 +1116,12 @@ class SampleIndex:
                 used += rows_of[query[hi]]
                 hi += 1
             self._links_block(query[lo:hi], k, n_songs, vote_top, too_long, threshold, min_score, top, int(s_budget_bytes), timing, out,
-                              vote, bin_rows, min_hits)
+                              vote, bin_rows, min_hits, norm)
             lo = hi
         return CatalogueLinks(out, skipped)
 
     def _links_block(self, block, k, n_songs, vote_top, too_long, threshold, min_score, top, budget, timing, out, vote="sequence",
-                     bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS):
+                     bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS, norm=None):
         """one block of links: the songs `block` (codes) as queries; fills out[name]"""
         first = np.asarray([self._song_rows[c][0] for c in block], dtype=np.int64)
         count = np.asarray([self._song_rows[c][1] for c in block], dtype=np.int64)
@@ -1055,7 +1149,7 @@ class SampleIndex:
         found = {b: [] for b in range(len(block))}
         occ, sc = self._align_pairs(ref, np.asarray([first[b] for b, _ in pairs], dtype=np.int64),
                                     np.asarray([count[b] for b, _ in pairs], dtype=np.int64), [c for _, c in pairs], threshold, min_score,
-                                    top, budget)
+                                    top, budget, norm=norm)
         for p, (b, c) in enumerate(pairs):
             for n, ((i0, i1, j0, j1), s) in enumerate(zip(occ[p].tolist(), sc[p].tolist())):
                 if i0 < 0:
@@ -1094,11 +1188,12 @@ class Scanner:
     a run is at most ops.ALIGN_OCC_MAX_ROWS rows."""
 
     def __init__(self, index, fixed, threshold, min_score, k, n_songs, top, W, exclude, max_active, timing, vote="sequence",
-                 bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS):
+                 bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS, normalize=False):
         self.index, self._fixed, self._theta, self._min_score = index, fixed, threshold, min_score
         self._k, self._n_songs, self._top, self.window_rows, self._exclude, self._max_active = k, n_songs, top, W, exclude, max_active
         self._timing = timing
         self._vote, self._bin_rows, self._min_hits = vote, bin_rows, min_hits
+        self._normalize = normalize       # the cells are cohort-normalised: a window's rows get their statistics in one launch
         self._pend = None                 # rows pushed and not yet in a window
         self._next = 0                    # global index of the first pending row
         self._active: List[int] = []      # window t - 1
@@ -1182,7 +1277,9 @@ class Scanner:
             x_len = np.asarray([idx._song_rows[c][1] for c in want], dtype=np.int64)
             q_len = np.full(P, n, dtype=np.int64)
             panels = bool((x_len > ops.ALIGN_MAX_COLS).any())              # a long song among them: every pair in one panels launch
-            S, s_off, s_ld = ops.pair_sim(rows, idx.fingerprints, np.zeros(P, np.int64), q_len, x_start, x_len, long_songs=panels)
+            norm = idx._norm("scanner", rows) if self._normalize else None
+            S, s_off, s_ld = ops.pair_sim(rows, idx.fingerprints, np.zeros(P, np.int64), q_len, x_start, x_len, long_songs=panels,
+                                          norm=norm)
             carry_off = np.asarray([self._slot[c] for c in want], dtype=np.int64) * (2 * idx._max_cols)
             strip = ops.local_align_panels if panels else ops.local_align_strip
             *res, row_off, oh = strip(S, s_off, s_ld, q_len, x_len, self._theta, np.full(P, start, np.int64), fresh, pool, carry_off)

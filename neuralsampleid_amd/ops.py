@@ -2174,9 +2174,52 @@ def pair_sim_tiles(q_len, x_len) -> np.ndarray:
     return np.stack([pair, (local // w) * ALIGN_TILE, (local % w) * ALIGN_TILE], axis=1).astype(np.int32)
 
 
-def pair_sim(q, x, q_start, q_len, x_start, x_len, s_ld=None, out=None, long_songs=False):
+COHORT_MIN, COHORT_MAX, COHORT_CHUNK = _H["NSID_COHORT_MIN"], _H["NSID_COHORT_MAX"], _H["NSID_COHORT_CHUNK"]
+
+
+def cohort_stats(x, cohort) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The background statistics of every row of x (n, d) over the cohort (M, d), COHORT_MIN <= M <= COHORT_MAX: (mu, rs), fp32 device
+    tensors of n entries, the mean of the row's pair_sim scores against the cohort rows and 1 / their standard deviation, summed in
+    fp64 in the fixed order of include/nsid.h ("cohort score normalisation"): a row's bits depend on the row and the cohort alone."""
+    ldx, ldc = _search_rows(x, "cohort_stats x"), _search_rows(cohort, "cohort_stats cohort")
+    if x.shape[1] != cohort.shape[1]:
+        raise ValueError(f"cohort_stats: row d = {x.shape[1]} != cohort d = {cohort.shape[1]}")
+    (n, d), M = x.shape, cohort.shape[0]
+    if not COHORT_MIN <= M <= COHORT_MAX:
+        raise ValueError(f"cohort_stats: a cohort of {M} rows is outside [{COHORT_MIN}, {COHORT_MAX}]")
+    if n >= 2 ** 31:
+        raise ValueError("cohort_stats: x must have fewer than 2^31 rows")
+    mu = torch.empty((n,), device=x.device, dtype=torch.float32)
+    rs = torch.empty((n,), device=x.device, dtype=torch.float32)
+    if n == 0:
+        return mu, rs
+    ws = torch.empty((int(lib.nsid_workspace_bytes(b"cohort_stats", n, M)) // 8,), device=x.device, dtype=torch.float64)
+    _timed("cohort_partial_kernel", 2.0 * n * M * d, 4.0 * d * (n + M) + 8.0 * n, lambda: call(
+        "nsid_cohort_stats", _p(x), ldx, n, _p(cohort), ldc, M, d, _p(mu), _p(rs), _p(ws), _stream()), (n, M, d, 1))
+    return mu, rs
+
+
+def _norm_stats(norm, nq, nx):
+    """pair_sim's norm=(q_mu, q_rs, x_mu, x_rs): contiguous fp32 device vectors that cover every row of q / x"""
+    if not isinstance(norm, (tuple, list)) or len(norm) != 4:
+        raise ValueError("pair_sim: norm must be (q_mu, q_rs, x_mu, x_rs)")
+    for t, what, rows in zip(norm, ("q_mu", "q_rs", "x_mu", "x_rs"), (nq, nq, nx, nx)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"pair_sim: norm {what} must be a torch tensor on the GPU")
+        _chk(t)
+        if t.dim() != 1 or t.numel() < rows:
+            raise ValueError(f"pair_sim: norm {what} must be a vector with one entry per row ({rows}), got {tuple(t.shape)}: the "
+                             "statistics are indexed by the absolute row of q / x")
+    return tuple(norm)
+
+
+def pair_sim(q, x, q_start, q_len, x_start, x_len, s_ld=None, out=None, long_songs=False, norm=None):
     """The score matrices of many (query rows, song rows) pairs in one launch: S_p[i, j] = q[q_start[p] + i] . x[x_start[p] + j], the
     dot of flat_l2_topk (one k-ordered fp32 fmaf chain; an element's bits depend on its two rows alone).
+
+    norm=(q_mu, q_rs, x_mu, x_rs) (cohort_stats of ALL rows of q and of x, indexed by absolute row): the cohort-normalised cell
+    0.5 ((s - q_mu[i]) q_rs[i] + (s - x_mu[j]) x_rs[j]) is stored instead of the dot s (nsid_pair_sim_norm, the same tiles); None is
+    nsid_pair_sim itself.
 
     q (nq, d), x (nx, d): fp32 rows as the search takes them. q_start / q_len / x_start / x_len: host integer sequences, one entry per
     pair, checked here and then uploaded; lengths may be 0, and are at most ALIGN_MAX_ROWS / ALIGN_MAX_COLS. s_ld: per pair the row
@@ -2202,6 +2245,8 @@ def pair_sim(q, x, q_start, q_len, x_start, x_len, s_ld=None, out=None, long_son
         raise ValueError("pair_sim: s_ld must be >= x_len for every pair")
     if q.shape[0] >= 2 ** 31:
         raise ValueError("pair_sim: q must have fewer than 2^31 rows")
+    if norm is not None:
+        norm = _norm_stats(norm, q.shape[0], x.shape[0])
     size = q_len * s_ld
     s_off = np.cumsum(size) - size
     total = int(size.sum())
@@ -2220,9 +2265,15 @@ def pair_sim(q, x, q_start, q_len, x_start, x_len, s_ld=None, out=None, long_son
     tl = torch.from_numpy(np.ascontiguousarray(tiles)).to(dev)
     d = q.shape[1]
     cells = float((q_len * x_len).sum())
-    _timed("pair_sim_kernel", 2.0 * cells * d, 4.0 * cells + 4.0 * d * 2 * ALIGN_TILE * tiles.shape[0], lambda: call(
-        "nsid_pair_sim", _p(q), ldq, q.shape[0], _p(x), ldx, x.shape[0], d, _p(t32[0]), _p(t32[1]), _p(t64[0]), _p(t32[2]), _p(t64[1]),
-        _p(t32[3]), npairs, _p(tl), tiles.shape[0], _p(out), out.numel(), _stream()), (npairs, tiles.shape[0], d, 1))
+    args = (_p(q), ldq, q.shape[0], _p(x), ldx, x.shape[0], d, _p(t32[0]), _p(t32[1]), _p(t64[0]), _p(t32[2]), _p(t64[1]), _p(t32[3]),
+            npairs, _p(tl), tiles.shape[0], _p(out), out.numel())
+    nbytes = 4.0 * cells + 4.0 * d * 2 * ALIGN_TILE * tiles.shape[0]
+    if norm is None:
+        _timed("pair_sim_kernel", 2.0 * cells * d, nbytes, lambda: call("nsid_pair_sim", *args, _stream()),
+               (npairs, tiles.shape[0], d, 1))
+    else:
+        _timed("pair_sim_norm_kernel", 2.0 * cells * d, nbytes, lambda: call("nsid_pair_sim_norm", *args, *(_p(t) for t in norm), _stream()),
+               (npairs, tiles.shape[0], d, 1))
     return out, s_off, s_ld
 
 
