@@ -99,7 +99,7 @@ int nsid_row_tiles(int M);
  * "stem7_stat" and "stem7_bwd" (rows = clips * pooled rows B*Hp, cols = pooled columns Wp: the [2][nsid_stem7_partials(rows, cols, 0)][64]
  * statistics sums / nsid_stem7_partials(rows, cols, 1) sets of the backward's partial sums, one per workgroup);
  * "sumsq" (rows = gradient elements: nsid_sumsq_blocks partial sums), "flat_l2_topk" (rows = query rows, cols = database rows: the
- * per-split top-64 lists of its first phase), "flat_l2_topk_coarse" (the same rows / cols: the pre-filter's per-split lists),
+ * per-split top-64 lists of its first phase; "flat_norm_topk" is the same number), "flat_l2_topk_coarse" (the same rows / cols: the pre-filter's per-split lists),
  * "align_paths" (rows x cols = ONE box: its step codes, 2 bits a cell, rows x ceil(cols / 4) bytes; a launch needs the sum over its
  * boxes), "cohort_stats" (rows = the rows of the call, cols = the cohort's rows M: two fp64 sums per chunk of NSID_COHORT_CHUNK cohort
  * rows and row, the rows padded to a multiple of 32). */
@@ -926,6 +926,30 @@ int nsid_pair_sim_norm(const float* q, int ldq, int nq, const float* x, int ldx,
                        const int64_t* x_start, const int* x_len, const int64_t* s_off, const int* s_ld, int npairs, const int* tiles,
                        int ntiles, float* S, int64_t s_len, const float* q_mu, const float* q_rs, const float* x_mu, const float* x_rs,
                        void* stream);
+/* Normalised candidate search (csrc/search.hip): flat_l2_topk's exhaustive top-k under the normalised cell instead of the L2 key, so
+ * that a generic query row does not spend its k slots on the database's generic rows. q (nq x d), x (nx x d):
+ * widths, leading dimensions, alignment, 1 <= k <= NSID_SEARCH_MAX_K and the row counts are flat_l2_topk's. q_mu, q_rs: nq floats,
+ * x_mu, x_rs: nx floats (cohort_stats of the rows of q and of x), 4-byte aligned.
+ * The score of database row j for query row i is z[i][j] = pair_sim_norm's cell for the same two rows and statistics, bit for bit:
+ *     s = the k-ordered fp32 fmaf chain on v_mfma_f32_32x32x2_f32 (the split pairing up to d = 256, the wide pairing above: a cell's
+ *         bits depend on its two rows alone)
+ *     a = s - q_mu[i];  zq = a * q_rs[i];  b = s - x_mu[j];  zx = b * x_rs[j];  t = zq + zx;  z = 0.5f * t
+ *   each of the five one fp32 operation rounded once, nothing contracted.
+ * The order is by (-z, id) under fp32 comparison: the larger z first, equal z (+0 and -0 are equal) the smaller id first. A cell whose
+ *   z is NaN does not compete. Z (nq x k fp32) = the k largest z of the row, descending, I (nq x k int64) their row ids; where fewer
+ *   than k rows compete the tail is I = -1, Z = -inf.
+ * ex_lo, ex_hi: both NULL (every row competes) or both device int32 arrays of nq entries with flat_l2_topk_excl's meaning: row i's
+ *   result is the rule over x without rows [ex_lo[i], ex_hi[i]), ids unchanged; any pair of ints is memory-safe.
+ * ws: nsid_workspace_bytes("flat_norm_topk", nq, nx) bytes (= "flat_l2_topk"'s), 16-byte aligned. Phase 1 is flat_l2_topk's with
+ *   the key -z (the sign flip is exact), phase 2 its merge: no atomics, no scratch; a row's result depends on the row, the database
+ *   and the four vectors alone, not on the other rows of the call or on the split plan. A bad d or k, a null or misaligned pointer,
+ *   only one of ex_lo / ex_hi: NSID_EINVAL before any launch; nq == 0 launches nothing. Launch counters "flat_norm_topk" and, at
+ *   d > 256, "flat_norm_topk_wide"; flat_l2_topk's counters do not move. nsid_debug_last_kernel names the phase-1 kernel taken:
+ *   "l2_topk_split_kernel<norm>", "l2_topk_wide_kernel<1,norm>" (nq <= 32 and nx > 128) or "l2_topk_wide_kernel<4,norm>", with
+ *   "excl," in front of "norm" when ranges are given. */
+int nsid_flat_norm_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* q_mu, const float* q_rs,
+                        const float* x_mu, const float* x_rs, const int* ex_lo, const int* ex_hi, int d, int k, float* Z, int64_t* I,
+                        void* ws, size_t ws_bytes, void* stream);
 
 /* ---- classifier training (downstream.py:82-140 mine_hard_negatives and train: the CrossAttentionClassifier in training mode). fp32;
  * C = 512, 4 heads of 128, fc.0 width 128, 1 <= N <= 32; NSID_EINVAL (nothing launched) otherwise. Every sum runs in one fixed

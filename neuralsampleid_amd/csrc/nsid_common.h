@@ -294,6 +294,7 @@ static inline long nsid_tune(NsidTuneKey k) { return g_nsid_tune[k]; }
   X(align_paths)          /* align.hip: the paths of occurrences, traced back through their boxes */ \
   X(cohort_stats) X(pair_sim_norm)   /* cohort.hip, align.hip: the cohort statistics of rows, and the score matrices normalised by them */ \
   X(bf16_rows) X(flat_l2_topk_coarse) X(flat_l2_rescore)   /* search.hip: the certified bf16 pre-filter of the exact search */ \
+  X(flat_norm_topk) X(flat_norm_topk_wide)   /* search.hip: nsid_flat_norm_topk (_wide: its d > 256 kernel) */ \
   X(flat_l2_topk_excl) X(flat_l2_topk_wide_excl)   /* search.hip: nsid_flat_l2_topk_excl (_wide: its d > 256 kernel) */
 
 // nsid_stem7_stat leaves at most this many partial sums per channel (resnet.hip); nsid_bn_finalize accepts such a count next to

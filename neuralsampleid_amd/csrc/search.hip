@@ -17,6 +17,11 @@
 // as the query: its own rows would otherwise take every slot). Phase 1 runs its EX instantiations: an excluded (row, column) is a
 // column that does not exist for that row, decided ahead of the threshold compare, so the lists hold exactly what the plain search
 // holds over the database without those rows, under the same total order. The plain entry launches the EX = false instantiations.
+// nsid_flat_norm_topk is the same search under another key: the cohort-normalised cell of nsid_pair_sim_norm (five fp32 operations
+// on the dot, csrc/align.hip sim_norm_cell), negated, so that the largest z is the smallest key. Phase 1 runs its NM instantiations:
+// the column's (x_mu, x_rs) come where ||x_j||^2 comes, the wave's 32 (q_mu, q_rs) are staged in LDS once, as the ranges are. A NaN
+// key passes no compare and so never competes. Phase 2 is the same merge and writes Z = -key. The NM = false instantiations are
+// what they were.
 // No atomics anywhere on the ranking path.
 #include "nsid_common.h"
 
@@ -67,19 +72,38 @@ __device__ __forceinline__ void merge_queue(KI* list, const KI* queue, int cnt, 
   __builtin_amdgcn_wave_barrier();
 }
 
+// the four vectors of the normalised key (nsid_flat_norm_topk); all null for the L2 key
+struct L2Norm {
+  const float *q_mu, *q_rs, *x_mu, *x_rs;
+};
+
+// the key of the normalised search: -z, z the cell of nsid_pair_sim_norm bit for bit (five fp32 operations, each rounded once, none
+// contracted; the sign flip is exact). qs = (q_mu, q_rs) of the query row, (mx, rx) of the database row.
+__device__ __forceinline__ float norm_key(float s, float2 qs, float mx, float rx) {
+#pragma clang fp contract(off)
+  const float zq = (s - qs.x) * qs.y;
+  const float zx = (s - mx) * rx;
+  const float sum = zq + zx;
+  return -(0.5f * sum);
+}
+
 // one wave, one finished 32x32 tile: accumulator register g of lane (r, h) = (lane & 31, lane >> 5) is query row
 // (g & 3) + 8 (g >> 2) + 4 h of the tile against database row `col` (cv: the row exists, xv its squared norm). Scores that pass
 // their row's threshold (the k-th list entry) go to the row's queue, which is merged into the list when it would overflow.
 // EX: exr[row] = the row's excluded range {lo, hi}; exh (wave-uniform): this column tile meets the hull of the tile's ranges. A
 // half-wave's register g is one query row, so the range is one broadcast LDS read, and only on tiles inside the hull.
-template <bool EX>
+// NM: the key is norm_key; xv = x_mu[col], xr = x_rs[col], qst[row] = the row's (q_mu, q_rs), one broadcast LDS read likewise.
+template <bool EX, bool NM = false>
 __device__ __forceinline__ void offer_tile(KI (*list)[L2_LIST], KI (*queue)[L2_Q1], int* cnt, const f32x16& acc, int col, bool cv,
-                                           float xv, int k, int lane, const int2* exr = nullptr, bool exh = false) {
+                                           float xv, int k, int lane, const int2* exr = nullptr, bool exh = false, float xr = 0.f,
+                                           const float2* qst = nullptr) {
   const int h = lane >> 5;
 #pragma unroll
   for (int g = 0; g < 16; ++g) {
     const int row = (g & 3) + 8 * (g >> 2) + 4 * h;
-    const KI c{xv - (acc[g] + acc[g]), col};
+    KI c{0.f, col};
+    if constexpr (NM) c.k = norm_key(acc[g], qst[row], xv, xr);
+    else c.k = xv - (acc[g] + acc[g]);
     bool keep = cv;
     if constexpr (EX) {
       if (exh) {
@@ -132,6 +156,12 @@ __device__ __forceinline__ void stage_ranges(int2* exr, const int* __restrict__ 
 // does the column tile [c0, c0 + 32) meet the hull?
 __device__ __forceinline__ bool in_hull(int c0, int hlo, int hhi) { return c0 < hhi && (long)c0 + 31 >= (long)hlo; }
 
+// NM: (q_mu, q_rs) of the wave's 32 query rows q0.. go to LDS once (a row past nq: zeros; its threshold lets nothing pass). The
+// caller's wave barrier follows.
+__device__ __forceinline__ void stage_qstats(float2* qst, const L2Norm& nm, int q0, int nq, int lane) {
+  if (lane < L2_QT) qst[lane] = q0 + lane < nq ? float2{nm.q_mu[q0 + lane], nm.q_rs[q0 + lane]} : float2{0.f, 0.f};
+}
+
 // the wave's lists of query rows q0.. go to workspace slot `slot` of `nslot` per row
 __device__ __forceinline__ void flush_lists(KI (*list)[L2_LIST], KI (*queue)[L2_Q1], const int* cnt, int q0, int nq, int nslot, int slot,
                                             int k, int lane, float* __restrict__ wkey, int* __restrict__ wid) {
@@ -151,17 +181,18 @@ __device__ __forceinline__ void flush_lists(KI (*list)[L2_LIST], KI (*queue)[L2_
 // Lane (r, h) = (lane & 31, lane >> 5). MFMA step (b, e) pairs k = 8b + e (h = 0) with k = 8b + 4 + e (h = 1), so a lane reads
 // 16 contiguous bytes of its row per block and the two halves read the adjacent 32 bytes. Accumulator register g of lane (r, h)
 // is query row (g & 3) + 8 (g >> 2) + 4 h of the tile against database row j0 + r.
-template <int D, int CH, bool EX>
+template <int D, int CH, bool EX, bool NM>
 __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x,
                                                            int ldx, int nx, const float* __restrict__ xn, int k, int nqt, int S,
                                                            int chunk, float* __restrict__ wkey, int* __restrict__ wid,
-                                                           const int* __restrict__ exlo, const int* __restrict__ exhi) {
+                                                           const int* __restrict__ exlo, const int* __restrict__ exhi, L2Norm nm) {
   constexpr int NB = D / 8;          // 8-float blocks per row
   constexpr int NC = NB / CH;        // chunks per tile
   __shared__ KI list[L2_QT][L2_LIST];
   __shared__ KI queue[L2_QT][L2_Q1];
   __shared__ int cnt[L2_QT];
   __shared__ int2 exr[EX ? L2_QT : 1];            // never referenced, so not allocated, without EX
+  __shared__ float2 qst[NM ? L2_QT : 1];          // likewise without NM
 
   const int lane = lane_id();
   const int r = lane & 31, h = lane >> 5;
@@ -175,6 +206,7 @@ __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restri
   if (lane < L2_QT && q0 + lane >= nq) list[lane][k - 1] = KI{-__builtin_inff(), 0};
   int hlo = 0, hhi = 0;
   if constexpr (EX) stage_ranges(exr, exlo, exhi, q0, nq, lane, hlo, hhi);
+  if constexpr (NM) stage_qstats(qst, nm, q0, nq, lane);
   __builtin_amdgcn_wave_barrier();
 
   f32x4 a[NB];
@@ -211,7 +243,13 @@ __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restri
 
     const int col = lo + tile * 32 + r;
     const bool cv = col < hi;
-    if constexpr (EX)
+    if constexpr (NM) {
+      const float mx = cv ? nm.x_mu[col] : 0.f, rx = cv ? nm.x_rs[col] : 0.f;
+      if constexpr (EX)
+        offer_tile<true, true>(list, queue, cnt, acc, col, cv, mx, k, lane, exr, in_hull(lo + tile * 32, hlo, hhi), rx, qst);
+      else
+        offer_tile<false, true>(list, queue, cnt, acc, col, cv, mx, k, lane, nullptr, false, rx, qst);
+    } else if constexpr (EX)
       offer_tile<true>(list, queue, cnt, acc, col, cv, cv ? xn[col] : 0.f, k, lane, exr, in_hull(lo + tile * 32, hlo, hhi));
     else
       offer_tile<false>(list, queue, cnt, acc, col, cv, cv ? xn[col] : 0.f, k, lane);
@@ -235,7 +273,7 @@ __global__ __launch_bounds__(64) void l2_topk_split_kernel(const float* __restri
 // transposing store: a thread holds 4 consecutive k of one row, 8 threads share a row, and with a stride = 1 mod 32 the 32 lanes of
 // a half-wave (4 rows x 8 k-quads) write 32 different banks. One stage per operand, the next two chunks prefetched in registers.
 // LDS: the lists, queues and counters of the narrow kernel per wave (4 x 24.1 KB) + 2 x 16.1 KB (WQ = 4) or 4.1 + 32.1 KB of stages;
-// EX adds the waves' ranges behind them (4 x 256 B).
+// EX adds the waves' ranges behind them (4 x 256 B), NM the waves' (q_mu, q_rs) behind those (4 x 256 B).
 constexpr int L2W_KC = 32;           // floats of K per stage
 constexpr int L2W_UNITS = 512;       // workgroups phase 1 aims at: one per CU fits (LDS), two rounds of 256
 template <int WQ>
@@ -246,13 +284,14 @@ struct L2Wide {
   static constexpr size_t lds = 4 * (sizeof(KI) * L2_QT * (L2_LIST + L2_Q1) + sizeof(int) * L2_QT) + sizeof(float) * L2W_KC * (QS + XS);
   static constexpr size_t lds_ex = lds + 4 * sizeof(int2) * L2_QT;
   static_assert(lds % alignof(int2) == 0, "the ranges follow the stages");
+  static constexpr size_t bytes(bool ex, bool nm) { return (ex ? lds_ex : lds) + (nm ? 4 * sizeof(float2) * L2_QT : 0); }
 };
 
-template <int WQ, bool EX>
+template <int WQ, bool EX, bool NM>
 __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restrict__ q, int ldq, int nq, const float* __restrict__ x,
                                                            int ldx, int nx, const float* __restrict__ xn, int d, int k, int nqb, int S,
                                                            int chunk, float* __restrict__ wkey, int* __restrict__ wid,
-                                                           const int* __restrict__ exlo, const int* __restrict__ exhi) {
+                                                           const int* __restrict__ exlo, const int* __restrict__ exhi, L2Norm nm) {
   using C = L2Wide<WQ>;
   constexpr int WC = C::WC, NACC = C::NACC, BQ = C::BQ, BC = C::BC, QS = C::QS, XS = C::XS;
   constexpr int QL = BQ / 32, XL = BC / 32;      // f32x4 per thread and chunk
@@ -264,6 +303,7 @@ __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restri
   float* qs = reinterpret_cast<float*>(l2w_smem + 4 * (sizeof(KI) * L2_QT * (L2_LIST + L2_Q1) + sizeof(int) * L2_QT));
   float* xs = qs + L2W_KC * QS;
   [[maybe_unused]] int2* exr = reinterpret_cast<int2*>(l2w_smem + C::lds) + w * L2_QT;       // EX only: the launch sizes LDS by lds_ex
+  [[maybe_unused]] float2* qst = reinterpret_cast<float2*>(l2w_smem + (EX ? C::lds_ex : C::lds)) + w * L2_QT;   // NM only, likewise
 
   const int r = lane & 31, h = lane >> 5;
   const int wq = w % WQ, wc = w / WQ;
@@ -277,6 +317,7 @@ __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restri
   if (lane < L2_QT && wq0 + lane >= nq) list[lane][k - 1] = KI{-__builtin_inff(), 0};
   int hlo = 0, hhi = 0;
   if constexpr (EX) stage_ranges(exr, exlo, exhi, wq0, nq, lane, hlo, hhi);
+  if constexpr (NM) stage_qstats(qst, nm, wq0, nq, lane);
   __builtin_amdgcn_wave_barrier();
 
   const int nblk = hi > lo ? (hi - lo + BC - 1) / BC : 0;
@@ -360,7 +401,13 @@ __global__ __launch_bounds__(256) void l2_topk_wide_kernel(const float* __restri
       auto offer_n = [&](const f32x16& tile, int n) {
         const int col = lo + blk * BC + 32 * (NACC * wc + n) + r;
         const bool cv = col < hi;
-        if constexpr (EX)
+        if constexpr (NM) {
+          const float mx = cv ? nm.x_mu[col] : 0.f, rx = cv ? nm.x_rs[col] : 0.f;
+          if constexpr (EX)
+            offer_tile<true, true>(list, queue, cnt, tile, col, cv, mx, k, lane, exr, in_hull(__builtin_amdgcn_readfirstlane(col - r), hlo, hhi), rx, qst);
+          else
+            offer_tile<false, true>(list, queue, cnt, tile, col, cv, mx, k, lane, nullptr, false, rx, qst);
+        } else if constexpr (EX)
           offer_tile<true>(list, queue, cnt, tile, col, cv, cv ? xn[col] : 0.f, k, lane, exr, in_hull(__builtin_amdgcn_readfirstlane(col - r), hlo, hhi));
         else
           offer_tile<false>(list, queue, cnt, tile, col, cv, cv ? xn[col] : 0.f, k, lane);
@@ -395,8 +442,11 @@ __device__ __forceinline__ void offer(KI* list, KI* queue, int& cnt, int k, int 
   __builtin_amdgcn_wave_barrier();
 }
 
-// RAW (the pre-filter's coarse lists, IdT = int): D / I get the merged keys and ids as they are, pads included; qn is not read
-template <typename IdT, bool RAW>
+// what phase 2 writes. L2_OUT_DIST: D = max(0, ||q||^2 + key), pads I = -1, D = +inf. L2_OUT_RAW (the pre-filter's coarse lists,
+// IdT = int): D / I get the merged keys and ids as they are, pads included; qn is not read. L2_OUT_NEG (the normalised search):
+// D = -key, the score itself, pads I = -1, D = -inf; qn is not read.
+enum { L2_OUT_DIST = 0, L2_OUT_RAW = 1, L2_OUT_NEG = 2 };
+template <typename IdT, int OUT>
 __global__ __launch_bounds__(256) void l2_topk_merge_kernel(const float* __restrict__ wkey, const int* __restrict__ wid, int S, int k,
                                                             const float* __restrict__ qn, float* __restrict__ D, IdT* __restrict__ I) {
   __shared__ KI list[4][L2_LIST];
@@ -428,9 +478,13 @@ __global__ __launch_bounds__(256) void l2_topk_merge_kernel(const float* __restr
   if (cnt > 0) merge_queue(list[0], queue[0], cnt, k, lane);
   if (lane < k) {
     const KI e = list[0][lane];
-    if constexpr (RAW) {
+    if constexpr (OUT == L2_OUT_RAW) {
       D[(size_t)row * k + lane] = e.k;
       I[(size_t)row * k + lane] = e.i;
+    } else if constexpr (OUT == L2_OUT_NEG) {
+      const bool real = e.i != L2_PAD_ID;
+      D[(size_t)row * k + lane] = real ? -e.k : -__builtin_inff();
+      I[(size_t)row * k + lane] = real ? (int64_t)e.i : (int64_t)-1;
     } else {
       const bool real = e.i != L2_PAD_ID;
       D[(size_t)row * k + lane] = real ? fmaxf(0.f, qn[row] + e.k) : __builtin_inff();
@@ -493,21 +547,21 @@ __global__ __launch_bounds__(256) void seq_scores_kernel(const float* __restrict
 bool l2_wide(int d) { return d > 256; }
 bool l2_shape_ok(int d) { return (d % 16 == 0 && d >= 16 && d <= 256) || (d % 64 == 0 && l2_wide(d) && d <= 2048); }
 
-template <int D, bool EX>
+template <int D, bool EX, bool NM>
 int launch_split(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int k, int nqt, int S, int chunk,
-                 float* wkey, int* wid, const int* exlo, const int* exhi, hipStream_t st) {
+                 float* wkey, int* wid, const int* exlo, const int* exhi, const L2Norm& nm, hipStream_t st) {
   constexpr int NB = D / 8;
   constexpr int CH = (D <= 128 && NB % 8 == 0) ? 8 : (NB % 4 == 0 ? 4 : 2);
-  NSID_LAUNCH((l2_topk_split_kernel<D, CH, EX>), dim3(nqt * S), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey,
-              wid, exlo, exhi);
+  NSID_LAUNCH((l2_topk_split_kernel<D, CH, EX, NM>), dim3(nqt * S), dim3(64), 0, st, q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey,
+              wid, exlo, exhi, nm);
   return nsid_launch_status();
 }
 
-template <bool EX, int... Ds>
+template <bool EX, bool NM, int... Ds>
 int dispatch_split(int d, const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int k, int nqt, int S,
-                   int chunk, float* wkey, int* wid, const int* exlo, const int* exhi, hipStream_t st) {
+                   int chunk, float* wkey, int* wid, const int* exlo, const int* exhi, const L2Norm& nm, hipStream_t st) {
   int rc = NSID_EINVAL;
-  ((d == Ds ? (rc = launch_split<Ds, EX>(q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey, wid, exlo, exhi, st), 0) : 0), ...);
+  ((d == Ds ? (rc = launch_split<Ds, EX, NM>(q, ldq, nq, x, ldx, nx, xn, k, nqt, S, chunk, wkey, wid, exlo, exhi, nm, st), 0) : 0), ...);
   return rc;
 }
 
@@ -531,12 +585,12 @@ void l2_plan_wide(long nq, long nx, int* splits, int* chunk, int* slots) {
   *slots = (int)(S * (one ? L2Wide<1>::WC : L2Wide<4>::WC));
 }
 
-template <int WQ, bool EX>
+template <int WQ, bool EX, bool NM>
 int launch_wide(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* xn, int d, int k, int S, int chunk,
-                float* wkey, int* wid, const int* exlo, const int* exhi, hipStream_t st) {
+                float* wkey, int* wid, const int* exlo, const int* exhi, const L2Norm& nm, hipStream_t st) {
   const int nqb = (nq + L2Wide<WQ>::BQ - 1) / L2Wide<WQ>::BQ;
-  NSID_LAUNCH_LDS((l2_topk_wide_kernel<WQ, EX>), dim3(nqb * S), dim3(256), EX ? L2Wide<WQ>::lds_ex : L2Wide<WQ>::lds, st, q, ldq, nq, x,
-                  ldx, nx, xn, d, k, nqb, S, chunk, wkey, wid, exlo, exhi);
+  NSID_LAUNCH_LDS((l2_topk_wide_kernel<WQ, EX, NM>), dim3(nqb * S), dim3(256), L2Wide<WQ>::bytes(EX, NM), st, q, ldq, nq, x, ldx, nx, xn,
+                  d, k, nqb, S, chunk, wkey, wid, exlo, exhi, nm);
   return nsid_launch_status();
 }
 
@@ -573,14 +627,23 @@ extern "C" int nsid_row_sqnorm(const float* x, int ldx, int n, int d, float* out
 }
 
 namespace {
-// the body of both search entries; EX: with the per-row ranges exlo / exhi
-template <bool EX>
+bool l2_aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+// the body of the search entries; EX: with the per-row ranges exlo / exhi; NM: the normalised key of nm (x_sqnorm, q_sqnorm unused)
+template <bool EX, bool NM>
 int l2_topk_entry(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm, const float* q_sqnorm,
-                  const int* exlo, const int* exhi, int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream) {
+                  const int* exlo, const int* exhi, const L2Norm& nm, int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes,
+                  void* stream) {
   NSID_REQUIRE(nq >= 0 && nx >= 0 && l2_shape_ok(d) && k >= 1 && k <= L2_LIST);
   if (nq == 0) return NSID_OK;
-  NSID_REQUIRE(q && q_sqnorm && D && I && ws && ldq >= d && ldq % 4 == 0 && nsid_aligned16(q) && nsid_aligned16(ws));
-  NSID_REQUIRE(nx == 0 || (x && x_sqnorm && ldx >= d && ldx % 4 == 0 && nsid_aligned16(x)));
+  NSID_REQUIRE(q && D && I && ws && ldq >= d && ldq % 4 == 0 && nsid_aligned16(q) && nsid_aligned16(ws));
+  NSID_REQUIRE(nx == 0 || (x && ldx >= d && ldx % 4 == 0 && nsid_aligned16(x)));
+  if constexpr (NM) {
+    NSID_REQUIRE(nm.q_mu && nm.q_rs && l2_aligned4(nm.q_mu) && l2_aligned4(nm.q_rs));
+    NSID_REQUIRE(nx == 0 || (nm.x_mu && nm.x_rs && l2_aligned4(nm.x_mu) && l2_aligned4(nm.x_rs)));
+  } else {
+    NSID_REQUIRE(q_sqnorm && (nx == 0 || x_sqnorm));
+  }
   NSID_REQUIRE(!EX || (exlo && exhi));
   int S, chunk, slots;
   if (l2_wide(d)) {
@@ -595,31 +658,46 @@ int l2_topk_entry(const float* q, int ldq, int nq, const float* x, int ldx, int 
   int* wid = reinterpret_cast<int*>(wkey + per);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int nqt = (nq + L2_QT - 1) / L2_QT;
-  nsid_count(EX ? NSID_C_flat_l2_topk_excl : NSID_C_flat_l2_topk);
+  nsid_count(NM ? NSID_C_flat_norm_topk : EX ? NSID_C_flat_l2_topk_excl : NSID_C_flat_l2_topk);
   int rc;
   if (l2_wide(d)) {
-    nsid_count(EX ? NSID_C_flat_l2_topk_wide_excl : NSID_C_flat_l2_topk_wide);
-    rc = l2_wide_one(nq, nx) ? launch_wide<1, EX>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, exlo, exhi, st)
-                             : launch_wide<4, EX>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, exlo, exhi, st);
+    nsid_count(NM ? NSID_C_flat_norm_topk_wide : EX ? NSID_C_flat_l2_topk_wide_excl : NSID_C_flat_l2_topk_wide);
+    const bool one = l2_wide_one(nq, nx);
+    if constexpr (NM)
+      nsid_took(one ? (EX ? "l2_topk_wide_kernel<1,excl,norm>" : "l2_topk_wide_kernel<1,norm>")
+                    : (EX ? "l2_topk_wide_kernel<4,excl,norm>" : "l2_topk_wide_kernel<4,norm>"));
+    rc = one ? launch_wide<1, EX, NM>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, exlo, exhi, nm, st)
+             : launch_wide<4, EX, NM>(q, ldq, nq, x, ldx, nx, x_sqnorm, d, k, S, chunk, wkey, wid, exlo, exhi, nm, st);
   } else {
-    rc = dispatch_split<EX, 16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
-        d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, exlo, exhi, st);
+    if constexpr (NM) nsid_took(EX ? "l2_topk_split_kernel<excl,norm>" : "l2_topk_split_kernel<norm>");
+    rc = dispatch_split<EX, NM, 16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
+        d, q, ldq, nq, x, ldx, nx, x_sqnorm, k, nqt, S, chunk, wkey, wid, exlo, exhi, nm, st);
   }
   if (rc != NSID_OK) return rc;
-  NSID_LAUNCH((l2_topk_merge_kernel<int64_t, false>), dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
+  NSID_LAUNCH((l2_topk_merge_kernel<int64_t, NM ? L2_OUT_NEG : L2_OUT_DIST>), dim3(nq), dim3(256), 0, st, wkey, wid, slots, k, q_sqnorm, D, I);
   return nsid_launch_status();
 }
 }  // namespace
 
 extern "C" int nsid_flat_l2_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
                                  const float* q_sqnorm, int d, int k, float* D, int64_t* I, void* ws, size_t ws_bytes, void* stream) {
-  return l2_topk_entry<false>(q, ldq, nq, x, ldx, nx, x_sqnorm, q_sqnorm, nullptr, nullptr, d, k, D, I, ws, ws_bytes, stream);
+  return l2_topk_entry<false, false>(q, ldq, nq, x, ldx, nx, x_sqnorm, q_sqnorm, nullptr, nullptr, L2Norm{}, d, k, D, I, ws, ws_bytes,
+                                     stream);
 }
 
 extern "C" int nsid_flat_l2_topk_excl(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* x_sqnorm,
                                       const float* q_sqnorm, const int* ex_lo, const int* ex_hi, int d, int k, float* D, int64_t* I,
                                       void* ws, size_t ws_bytes, void* stream) {
-  return l2_topk_entry<true>(q, ldq, nq, x, ldx, nx, x_sqnorm, q_sqnorm, ex_lo, ex_hi, d, k, D, I, ws, ws_bytes, stream);
+  return l2_topk_entry<true, false>(q, ldq, nq, x, ldx, nx, x_sqnorm, q_sqnorm, ex_lo, ex_hi, L2Norm{}, d, k, D, I, ws, ws_bytes, stream);
+}
+
+extern "C" int nsid_flat_norm_topk(const float* q, int ldq, int nq, const float* x, int ldx, int nx, const float* q_mu, const float* q_rs,
+                                   const float* x_mu, const float* x_rs, const int* ex_lo, const int* ex_hi, int d, int k, float* Z,
+                                   int64_t* I, void* ws, size_t ws_bytes, void* stream) {
+  NSID_REQUIRE((ex_lo == nullptr) == (ex_hi == nullptr));
+  const L2Norm nm{q_mu, q_rs, x_mu, x_rs};
+  if (ex_lo) return l2_topk_entry<true, true>(q, ldq, nq, x, ldx, nx, nullptr, nullptr, ex_lo, ex_hi, nm, d, k, Z, I, ws, ws_bytes, stream);
+  return l2_topk_entry<false, true>(q, ldq, nq, x, ldx, nx, nullptr, nullptr, nullptr, nullptr, nm, d, k, Z, I, ws, ws_bytes, stream);
 }
 
 extern "C" int nsid_seq_scores(const float* q, int ldq, const float* x, int ldx, int nx, int d, const int64_t* I, int k,
@@ -1008,7 +1086,7 @@ extern "C" int nsid_flat_l2_topk_coarse(const void* qb, int ldq, int nq, const v
                        : dispatch_coarse<false, 16, 32, 48, 64, 80, 96, 112, 128, 144, 160, 176, 192, 208, 224, 240, 256>(
                              d, q, ldq, nq, x, ldx, nx, x_sqnorm, S, chunk, wkey, wid, nullptr, nullptr, st);
   if (rc != NSID_OK) return rc;
-  NSID_LAUNCH((l2_topk_merge_kernel<int, true>), dim3(nq), dim3(256), 0, st, wkey, wid, S, L2_LIST, nullptr, ckey, cid);
+  NSID_LAUNCH((l2_topk_merge_kernel<int, L2_OUT_RAW>), dim3(nq), dim3(256), 0, st, wkey, wid, S, L2_LIST, nullptr, ckey, cid);
   return nsid_launch_status();
 }
 

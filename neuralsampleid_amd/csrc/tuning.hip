@@ -103,7 +103,7 @@ extern "C" long nsid_workspace_bytes(const char* op, long rows, long cols) {
     return nsid_stem7_partials(rows, cols, 1) * nsid_stem7_bwd_set_floats() * (long)sizeof(float);
   if (strcmp(op, "sumsq") == 0)              // rows = elements of the flat gradient
     return (long)nsid_sumsq_blocks(rows) * (long)sizeof(float);
-  if (strcmp(op, "flat_l2_topk") == 0)       // rows = query rows, cols = database rows; for k = 64
+  if (strcmp(op, "flat_l2_topk") == 0 || strcmp(op, "flat_norm_topk") == 0)   // rows = query rows, cols = database rows; for k = 64
     return nsid_l2_ws_bytes(rows, cols, 64);
   if (strcmp(op, "flat_l2_topk_coarse") == 0)   // the same rows / cols: the pre-filter's candidate lists per (row, split)
     return nsid_l2_coarse_ws_bytes(rows, cols);

@@ -132,10 +132,15 @@ DIAG_BIN_ROWS = 16            # no measurement on real audio stands behind it: a
 DIAG_MIN_HITS = 2             # nor behind this: one hit is no diagonal
 
 
-def _vote_options(what, vote, bin_rows, min_hits, rerank=False):
+def _vote_options(what, vote, bin_rows, min_hits, rerank=False, norm_search=False):
     """the refusals of the vote keywords, before anything is launched; returns (vote, bin_rows, min_hits)"""
     if vote not in VOTES:
         raise ValueError(f"{what}: vote = {vote!r} is not one of {VOTES}")
+    if norm_search and rerank:
+        raise ValueError(f"{what}: norm_search=True is not offered with rerank=True: the re-rank's candidates come from the L2 search")
+    if norm_search and vote != "diagonal":
+        raise ValueError(f"{what}: norm_search=True needs vote='diagonal': the sequence vote sums per song, and a song with many "
+                         "generic rows wins it under normalised scores as well (there is no normalised sequence vote)")
     if vote == "diagonal" and rerank:
         raise ValueError(f"{what}: vote='diagonal' counts search hits and has no re-ranked form (the classifier vote is a different "
                          "rule): use vote='sequence' with rerank=True")
@@ -202,6 +207,8 @@ class SampleIndex:
         self._cohort = None                   # (M, d): the cohort of normalize=True, a copy (set_cohort)
         self._stat = None                     # (mu, rs), (capacity,) fp32 each: the cohort statistics of the first _stat_done ref rows
         self._stat_done = 0
+        self._istat = None                    # (mu, rs) likewise of the first _istat_done index rows (dummy ++ ref): norm_search=True
+        self._istat_done = 0
         if model is not None:
             from .fingerprint import embedding_dim
             self._d = int(embedding_dim(model))
@@ -387,7 +394,7 @@ class SampleIndex:
         """The cohort of normalize=True (include/nsid.h, "cohort score normalisation"): unrelated rows against which every row's
         scores are read, ops.COHORT_MIN <= M <= ops.COHORT_MAX of them. rows: an (M, d) device tensor, copied. Without rows:
         M = min(size, n_dummy) of the dummy rows, those at positions floor(m n_dummy / M), copied, so that later adds change nothing.
-        One cohort per index; setting it drops the cached statistics of the resident rows."""
+        One cohort per index; setting it drops the cached statistics of the resident rows and of the index rows."""
         if rows is not None:
             self._check_fp(rows, "set_cohort")
             M = int(rows.shape[0])
@@ -405,13 +412,14 @@ class SampleIndex:
             pos = (np.arange(M, dtype=np.int64) * self.n_dummy) // M
             cohort = self._index.xb.index_select(0, torch.from_numpy(pos).to(self.device)).contiguous()
         self._cohort, self._stat, self._stat_done = cohort, None, 0
+        self._istat, self._istat_done = None, 0
 
     def _need_cohort(self, what) -> torch.Tensor:
-        """the cohort of a normalize=True call: the one set, or the default one made now"""
+        """the cohort of a normalize=True or norm_search=True call: the one set, or the default one made now"""
         if self._cohort is None:
             if self.n_dummy < ops.COHORT_MIN:
-                raise RuntimeError(f"{what}: normalize=True needs a cohort and the index holds {self.n_dummy} dummy rows, fewer than "
-                                   f"the {ops.COHORT_MIN} of a default one: call set_cohort(rows=...) first")
+                raise RuntimeError(f"{what}: normalize=True / norm_search=True needs a cohort and the index holds {self.n_dummy} dummy "
+                                   f"rows, fewer than the {ops.COHORT_MIN} of a default one: call set_cohort(rows=...) first")
             self.set_cohort()
         if self._d is not None and self._cohort.shape[1] != self._d:
             raise ValueError(f"{what}: the cohort has d = {self._cohort.shape[1]}, the index d = {self._d}: call set_cohort again")
@@ -436,10 +444,41 @@ class SampleIndex:
             self._stat_done = self.n_ref
         return self._stat[0][: self.n_ref], self._stat[1][: self.n_ref]
 
-    def _norm(self, what, q, resident_query=False):
-        """ops.pair_sim's norm= for query rows q against the resident rows (resident_query: q is the resident rows themselves)"""
+    def _index_stats(self, what):
+        """(mu, rs) of all index rows, dummy ++ ref, which is what competes in a search (norm_search=True). Kept like the resident
+        rows': the dummy rows are computed once, the ref part is copied from _resident_stats (the same bits), and only the rows added
+        since the last call are touched."""
         ref = self._resident_stats(what)
-        return (ref if resident_query else ops.cohort_stats(q, self._cohort)) + ref
+        n = self.n_dummy + self.n_ref
+        if self._istat is None:
+            self._istat = tuple(torch.empty((0,), device=self.device, dtype=torch.float32) for _ in range(2))
+            self._istat_done = 0
+        if self._istat_done < n:
+            self._istat = tuple(self._grown(t, n) for t in self._istat)
+            if self._istat_done < self.n_dummy:
+                new = ops.cohort_stats(self._index.xb[self._istat_done:self.n_dummy], self._cohort)
+                for t, v in zip(self._istat, new):
+                    t[self._istat_done:self.n_dummy].copy_(v)
+                self._istat_done = self.n_dummy
+            for t, v in zip(self._istat, ref):
+                t[self._istat_done:n].copy_(v[self._istat_done - self.n_dummy:])
+            self._istat_done = n
+        return self._istat[0][:n], self._istat[1][:n]
+
+    def _norm_search_checks(self, what):
+        """the refusals of norm_search=True that do not depend on the vote keywords, before any search is launched"""
+        if self.prefilter:
+            raise ValueError(f"{what}: norm_search=True is not offered on a prefilter=True index: the pre-filter certifies L2 keys "
+                             "(there is no normalised pre-filter)")
+        self._need_cohort(what)
+
+    def _norm(self, what, q, resident_query=False, q_stats=None):
+        """ops.pair_sim's norm= for query rows q against the resident rows (resident_query: q is the resident rows themselves;
+        q_stats: the query rows' statistics where the call has them already)"""
+        ref = self._resident_stats(what)
+        if resident_query:
+            return ref + ref
+        return (ops.cohort_stats(q, self._cohort) if q_stats is None else tuple(q_stats)) + ref
 
     # ------------------------------------------------------------------------------------------------ asking
     def _query(self, specs, wave, fp, nodes, rerank):
@@ -547,29 +586,45 @@ class SampleIndex:
     @torch.no_grad()
     def diag_votes(self, fp: torch.Tensor, starts: Sequence[int], lens: Sequence[int], k_probe: int = 20, top: int = 10,
                    bin_rows: int = DIAG_BIN_ROWS, exclude: Optional[Sequence[Optional[str]]] = None,
-                   leave_out: Optional[Sequence[Optional[str]]] = None) -> DiagVotes:
+                   leave_out: Optional[Sequence[Optional[str]]] = None, norm_search: bool = False, _q_stats=None) -> DiagVotes:
         """The diagonal-histogram vote (include/nsid.h nsid_diag_vote) of many (start, length) pairs of one query table: one search and
         one ops.diag_vote, no seq_scores. A song's count is the largest number of its retrieved rows whose offset to the query row
         falls into one bin of 2 bin_rows rows, so an excerpt votes wherever in the pair's rows it starts, and under a time stretch of
         up to bin_rows rows of drift. fp, starts, lens, exclude, leave_out: identify_pairs'. bin_rows = 16 keeps an excerpt of up to 64
-        rows at 1.25x in one bin; no measurement on real audio stands behind the number."""
+        rows at 1.25x in one bin; no measurement on real audio stands behind the number.
+
+        norm_search=True: the k_probe rows of a query row are those of largest cohort-normalised score (FlatL2Index.search_norm: the
+        cell normalize=True aligns on) instead of smallest L2 distance, so a query row with a generic component does not spend its
+        slots on the catalogue's generic rows. The vote reads ids only and is the same. The query rows' statistics are one
+        ops.cohort_stats, the index rows' (dummy ++ ref) are cached; the cohort is normalize's (set_cohort). Refused on a
+        prefilter=True index."""
         self._check_fp(fp, "diag_votes")
         bin_rows = _vote_options("diag_votes", "diagonal", bin_rows, 1)[1]
+        if norm_search:
+            self._norm_search_checks("diag_votes")
         k, top, starts, lens, ex, left = self._pair_args("diag_votes", fp, starts, lens, k_probe, top, exclude, leave_out)
         if starts.size == 0:
             e = lambda: torch.empty((0, top), device=self.device, dtype=torch.int32)
             return DiagVotes(self.names, e(), e(), e(), e(), e(), e(), torch.empty((0,), device=self.device, dtype=torch.int32))
-        _, I = self._index.search(fp.contiguous(), k, exclude=left)
+        fp = fp.contiguous()
+        if norm_search:
+            x_stats = self._index_stats("diag_votes")
+            q_stats = ops.cohort_stats(fp, self._cohort) if _q_stats is None else tuple(_q_stats)
+            _, I = self._index.search_norm(fp, k, q_stats + x_stats, exclude=left)
+        else:
+            _, I = self._index.search(fp, k, exclude=left)
         return DiagVotes(self.names, *ops.diag_vote(I, starts, lens, self._song_of[: self.n_ref], self.n_dummy, ex, bin_rows, top))
 
-    def _window_votes(self, fp, starts, lens, k, top, exclude, leave_out, rerank, nodes, vote, bin_rows, min_hits):
+    def _window_votes(self, fp, starts, lens, k, top, exclude, leave_out, rerank, nodes, vote, bin_rows, min_hits, norm_search=False,
+                      q_stats=None):
         """the votes of some windows on the host: (codes (pairs, top), -1 = none; totals (pairs, top); hints (pairs, top, 4) = i_lo, i_hi,
         r_lo, r_hi, or None). vote='sequence': identify_pairs' totals. vote='diagonal': diag_votes' counts, and a song with fewer than
         min_hits hits in its best bin is no candidate."""
         if vote == "sequence":
             pv = self.identify_pairs(fp, starts, lens, k_probe=k, top=top, exclude=exclude, rerank=rerank, nodes=nodes, leave_out=leave_out)
             return pv.codes.cpu().numpy(), pv.totals.cpu().numpy(), None
-        dv = self.diag_votes(fp, starts, lens, k_probe=k, top=top, bin_rows=bin_rows, exclude=exclude, leave_out=leave_out)
+        dv = self.diag_votes(fp, starts, lens, k_probe=k, top=top, bin_rows=bin_rows, exclude=exclude, leave_out=leave_out,
+                             norm_search=norm_search, _q_stats=q_stats)
         packed = torch.stack([dv.codes, dv.counts, dv.i_lo, dv.i_hi, dv.r_lo, dv.r_hi], dim=2).cpu().numpy()      # one copy
         codes, counts = packed[:, :, 0], packed[:, :, 1]
         return np.where(counts >= min_hits, codes, -1), counts, packed[:, :, 2:]
@@ -687,7 +742,7 @@ class SampleIndex:
     @torch.no_grad()
     def align(self, fp: torch.Tensor, songs: Sequence[str], threshold: Optional[float] = None, min_score: float = 0.0, top: int = 16,
               nodes: Optional[torch.Tensor] = None, rerank: bool = False, return_rows: bool = False, row_hop_s=None, row_len_s=None,
-              s_budget_bytes: int = 1 << 30, normalize: bool = False):
+              s_budget_bytes: int = 1 << 30, normalize: bool = False, _q_stats=None):
         """Where in the query, and where in each named resident song, does the query sample the song? The local alignment of
         include/nsid.h ("locating a sample") of the query's rows against each song's rows, one pair per song, all songs in one
         pair_sim + local_align per chunk; a chunk's score workspace (4 Lq Lr bytes per song) stays under s_budget_bytes.
@@ -722,7 +777,7 @@ class SampleIndex:
         if not rerank:
             occ, sc = self._align_pairs(fp, np.zeros(len(codes), np.int64), np.full(len(codes), Lq, np.int64), codes, threshold,
                                         min_score, top, int(s_budget_bytes), chunks if return_rows else None,
-                                        self._norm("align", fp) if normalize else None)
+                                        self._norm("align", fp, q_stats=_q_stats) if normalize else None)
             for p, c in enumerate(codes):
                 for (i0, i1, j0, j1), s in zip(occ[p].tolist(), sc[p].tolist()):
                     if i0 < 0:
@@ -824,7 +879,7 @@ class SampleIndex:
                n_songs: int = 5, exclude: Optional[str] = None, threshold: Optional[float] = None, min_score: float = 0.0,
                top: int = 16, rerank: bool = False, row_hop_s=None, row_len_s=None,
                leave_out: Optional[str] = None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
-               min_hits: int = DIAG_MIN_HITS, normalize: bool = False) -> List["Occurrence"]:
+               min_hits: int = DIAG_MIN_HITS, normalize: bool = False, norm_search: bool = False) -> List["Occurrence"]:
         """The occurrences of resident songs in a query, one flat list sorted by score: encodes as identify does, finds the candidate
         songs (songs=None) and aligns the query against them.
 
@@ -841,9 +896,15 @@ class SampleIndex:
         diagonal vote sees it anywhere in the window. Refused with rerank=True. bin_rows and min_hits have no measurement on real
         audio behind them.
 
-        normalize=True: align's (threshold and scores in background sigmas; refused with rerank=True). The candidate search and
-        both votes run on L2 distances and are untouched."""
-        vote, bin_rows, min_hits = _vote_options("locate", vote, bin_rows, min_hits, rerank)
+        normalize=True: align's (threshold and scores in background sigmas; refused with rerank=True). It is the alignment's flag:
+        the candidate search and both votes run on L2 distances unless norm_search says otherwise.
+
+        norm_search=True (vote="diagonal" only): diag_votes' norm_search, the candidate search under the normalised score. Independent
+        of normalize; with both, the query rows' statistics are computed once. Refused with vote="sequence", with rerank=True and on
+        a prefilter=True index; ignored with songs= (nothing is searched)."""
+        vote, bin_rows, min_hits = _vote_options("locate", vote, bin_rows, min_hits, rerank, norm_search)
+        if norm_search:
+            self._norm_search_checks("locate")
         if normalize and rerank:
             raise ValueError("locate: normalize=True is not offered with rerank=True: the classifier's cells are probabilities and "
                              "their threshold already has a meaning")
@@ -868,15 +929,20 @@ class SampleIndex:
         if leave_out is not None:
             self.code(leave_out)
         fp, nodes = self._query(specs, wave, fp, nodes, rerank)
+        q_stats = None
         if songs is None:
             self._check_fp(fp, "locate", device=False)
             max_q = ops.ALIGN_MAX_ROWS if rerank else self._max_q
             if fp.shape[0] > max_q:
                 raise ValueError(f"locate: a query of {fp.shape[0]} rows is past the limit of {max_q}; longer inputs are "
                                  "refused, not split")
-            songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank, leave_out, vote, bin_rows, min_hits)
+            if norm_search and fp.shape[0] and self.n_ref:        # (an empty query or index is refused below, before any launch)
+                _need_cuda(fp, "locate")
+                fp = fp.contiguous()
+                q_stats = ops.cohort_stats(fp, self._cohort)
+            songs = self._candidates(fp, nodes, k, n_songs, exclude, rerank, leave_out, vote, bin_rows, min_hits, norm_search, q_stats)
         per_song = self.align(fp, songs, threshold, min_score, top, nodes, rerank, row_hop_s=row_hop_s, row_len_s=row_len_s,
-                              normalize=normalize)
+                              normalize=normalize, _q_stats=q_stats)
         flat = [(o, c, n) for c, occs in enumerate(per_song) for n, o in enumerate(occs)]
         flat.sort(key=lambda t: (-t[0].score, t[1], t[2]))
         return [t[0] for t in flat]
@@ -974,7 +1040,7 @@ class SampleIndex:
         return sorted(best, key=lambda c: (-best[c], c))
 
     def _candidates(self, fp, nodes, k, n_songs, exclude, rerank, leave_out=None, vote="sequence", bin_rows=DIAG_BIN_ROWS,
-                    min_hits=DIAG_MIN_HITS) -> List[str]:
+                    min_hits=DIAG_MIN_HITS, norm_search=False, q_stats=None) -> List[str]:
         """the songs of any window's top list, by their best window total (descending, then by code), at most n_songs"""
         Lq = int(fp.shape[0])
         if Lq == 0:
@@ -983,7 +1049,7 @@ class SampleIndex:
         codes, totals, _ = self._window_votes(fp, starts, [W] * len(starts), k, min(ops.VOTE_MAX_TOP, max(n_songs, 1)),
                                               None if exclude is None else [exclude] * len(starts),
                                               None if leave_out is None else [leave_out] * len(starts), rerank, nodes, vote, bin_rows,
-                                              min_hits)
+                                              min_hits, norm_search, q_stats)
         order = self._best_songs(codes.reshape(-1).tolist(), totals.reshape(-1).tolist())
         return [self.names[c] for c in order[:n_songs]]
 
@@ -991,7 +1057,7 @@ class SampleIndex:
     def scanner(self, threshold: Optional[float] = None, min_score: float = 0.0, k_probe: int = 20, n_songs: int = 5, top: int = 16,
                 window_rows: Optional[int] = None, songs: Optional[Sequence[str]] = None, exclude: Optional[str] = None,
                 max_active: int = 64, row_hop_s=None, row_len_s=None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
-                min_hits: int = DIAG_MIN_HITS, normalize: bool = False) -> "Scanner":
+                min_hits: int = DIAG_MIN_HITS, normalize: bool = False, norm_search: bool = False) -> "Scanner":
         """A Scanner over this index: a recording of any length, pushed in pieces of any sizes, is voted on and aligned in windows of
         W = window_rows or VOTE_MAX_CAND // k_probe rows (at most min(VOTE_MAX_CAND // k_probe, ALIGN_MAX_ROWS)), aligned to the global
         row index, so the result depends on the rows alone. The alignment is locate's rule, carried from window to window
@@ -1001,8 +1067,11 @@ class SampleIndex:
         songs include one of more than ALIGN_MAX_COLS rows goes through local_align_panels. vote="diagonal", bin_rows, min_hits:
         locate's (the window's vote is diag_votes', so an excerpt that starts deep inside a window, or lies wholly inside one, is
         aligned in that window). normalize=True: align's; a window's rows get their cohort statistics in one launch, the
-        resident rows' are cached. Every refusal comes before any launch."""
-        vote, bin_rows, min_hits = _vote_options("scanner", vote, bin_rows, min_hits)
+        resident rows' are cached. norm_search=True (vote="diagonal" only): locate's; a window's vote searches under the normalised
+        score, and the window's statistics are the one launch normalize=True uses. Every refusal comes before any launch."""
+        vote, bin_rows, min_hits = _vote_options("scanner", vote, bin_rows, min_hits, False, norm_search)
+        if norm_search:
+            self._norm_search_checks("scanner")
         if threshold is None:
             raise ValueError("scanner: threshold has no default for fingerprint scores (the reference has no such number and none has "
                              "been measured on real audio): pass one")
@@ -1035,7 +1104,7 @@ class SampleIndex:
         if normalize:
             self._need_cohort("scanner")
         return Scanner(self, fixed, threshold, min_score, k, n_songs, top, min(W, cap), exclude, max_active, timing, vote, bin_rows,
-                       min_hits, bool(normalize))
+                       min_hits, bool(normalize), bool(norm_search))
 
     def _scan_song_ok(self, c):
         if self._song_rows[c][1] > self._max_cols:
@@ -1056,7 +1125,7 @@ class SampleIndex:
     def links(self, names: Optional[Sequence[str]] = None, k_probe: int = 20, n_songs: int = 5, threshold: Optional[float] = None,
               min_score: float = 0.0, top: int = 16, block_rows: int = 1 << 16, s_budget_bytes: int = 1 << 30, row_hop_s=None,
               row_len_s=None, vote: str = "sequence", bin_rows: int = DIAG_BIN_ROWS,
-              min_hits: int = DIAG_MIN_HITS, normalize: bool = False) -> "CatalogueLinks":
+              min_hits: int = DIAG_MIN_HITS, normalize: bool = False, norm_search: bool = False) -> "CatalogueLinks":
         """Which resident songs share material with which others? The self-join of the catalogue: for every named song (default: all,
         in add order) the query is the song's own resident fingerprint rows (nothing is encoded again or copied to the host), and
         occurrences[name] is what locate(fp=those rows, leave_out=name, k_probe=..., n_songs=..., threshold=..., min_score=..., top=...)
@@ -1077,8 +1146,13 @@ class SampleIndex:
         vote="diagonal", bin_rows, min_hits: locate's; the block's windows go through one diag_vote instead of seq_scores + song_vote,
         and a partner sampled in the middle of a long song is a candidate by its diagonal, not by chance.
 
-        normalize=True: locate's; both sides of every pair are resident rows, so both take the cached resident statistics."""
-        vote, bin_rows, min_hits = _vote_options("links", vote, bin_rows, min_hits)
+        normalize=True: locate's; both sides of every pair are resident rows, so both take the cached resident statistics.
+
+        norm_search=True (vote="diagonal" only): locate's; a block's query rows are resident rows and take the cached resident
+        statistics, so nothing is computed per block."""
+        vote, bin_rows, min_hits = _vote_options("links", vote, bin_rows, min_hits, False, norm_search)
+        if norm_search:
+            self._norm_search_checks("links")
         if threshold is None:
             raise ValueError("links: threshold has no default for fingerprint scores (the reference has no such number and none has "
                              "been measured on real audio): pass one")
@@ -1109,6 +1183,7 @@ class SampleIndex:
         out = {self.names[c]: [] for c in query}
         vote_top = min(ops.VOTE_MAX_TOP, max(n_songs, 1))
         norm = self._norm("links", None, resident_query=True) if normalize else None
+        ref_stats = self._resident_stats("links") if norm_search else None
         lo = 0
         while lo < len(query):
             hi, used = lo, 0
@@ -1116,22 +1191,28 @@ class SampleIndex:
                 used += rows_of[query[hi]]
                 hi += 1
             self._links_block(query[lo:hi], k, n_songs, vote_top, too_long, threshold, min_score, top, int(s_budget_bytes), timing, out,
-                              vote, bin_rows, min_hits, norm)
+                              vote, bin_rows, min_hits, norm, ref_stats)
             lo = hi
         return CatalogueLinks(out, skipped)
 
     def _links_block(self, block, k, n_songs, vote_top, too_long, threshold, min_score, top, budget, timing, out, vote="sequence",
-                     bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS, norm=None):
-        """one block of links: the songs `block` (codes) as queries; fills out[name]"""
+                     bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS, norm=None, ref_stats=None):
+        """one block of links: the songs `block` (codes) as queries; fills out[name]. ref_stats: the resident rows' statistics for a
+        normalised candidate search (norm_search=True), else None."""
         first = np.asarray([self._song_rows[c][0] for c in block], dtype=np.int64)
         count = np.asarray([self._song_rows[c][1] for c in block], dtype=np.int64)
         base = np.cumsum(count) - count                           # a song's first row in the block's query table
         ref = self.fingerprints
+        q_stats = None
         if (first[1:] == first[:-1] + count[:-1]).all():           # neighbours in add order: the resident rows themselves
             fp = ref[int(first[0]): int(first[-1] + count[-1])]
+            if ref_stats is not None:
+                q_stats = tuple(t[int(first[0]): int(first[-1] + count[-1])] for t in ref_stats)
         else:
-            rows = np.repeat(first - base, count) + np.arange(int(count.sum()))
-            fp = ref.index_select(0, torch.from_numpy(rows).to(self.device))
+            rows = torch.from_numpy(np.repeat(first - base, count) + np.arange(int(count.sum()))).to(self.device)
+            fp = ref.index_select(0, rows)
+            if ref_stats is not None:
+                q_stats = tuple(t.index_select(0, rows) for t in ref_stats)
         starts, lens, owner = [], [], []
         for b, c in enumerate(block):
             s, W = self._windows(int(count[b]), k)
@@ -1139,7 +1220,7 @@ class SampleIndex:
             lens += [W] * len(s)
             owner += [b] * len(s)
         codes, totals, _ = self._window_votes(fp, starts, lens, k, vote_top, None, [self.names[block[b]] for b in owner], False, None,
-                                              vote, bin_rows, min_hits)
+                                              vote, bin_rows, min_hits, ref_stats is not None, q_stats)
         owner = np.asarray(owner)
         pairs = []                                                # (song of the block, candidate code), a song's candidates in order
         for b in range(len(block)):
@@ -1188,12 +1269,13 @@ class Scanner:
     a run is at most ops.ALIGN_OCC_MAX_ROWS rows."""
 
     def __init__(self, index, fixed, threshold, min_score, k, n_songs, top, W, exclude, max_active, timing, vote="sequence",
-                 bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS, normalize=False):
+                 bin_rows=DIAG_BIN_ROWS, min_hits=DIAG_MIN_HITS, normalize=False, norm_search=False):
         self.index, self._fixed, self._theta, self._min_score = index, fixed, threshold, min_score
         self._k, self._n_songs, self._top, self.window_rows, self._exclude, self._max_active = k, n_songs, top, W, exclude, max_active
         self._timing = timing
         self._vote, self._bin_rows, self._min_hits = vote, bin_rows, min_hits
         self._normalize = normalize       # the cells are cohort-normalised: a window's rows get their statistics in one launch
+        self._norm_search = norm_search   # the window's vote searches under the normalised score, on the same statistics
         self._pend = None                 # rows pushed and not yet in a window
         self._next = 0                    # global index of the first pending row
         self._active: List[int] = []      # window t - 1
@@ -1242,12 +1324,15 @@ class Scanner:
         idx, start, n = self.index, self._next, int(rows.shape[0])
         rows = rows.contiguous()
         vote_codes, vote_totals, vote_hints = [], [], []
+        q_stats = None                    # the window's statistics, once for the vote's search and for the cells
         if self._fixed is not None:
             want = list(self._fixed)
         else:
+            if self._norm_search:
+                q_stats = ops.cohort_stats(rows, idx._need_cohort("scanner"))
             codes, totals, hints = idx._window_votes(rows, [0], [n], self._k, min(ops.VOTE_MAX_TOP, self._n_songs),
                                                      None if self._exclude is None else [idx.names[self._exclude]], None, False, None,
-                                                     self._vote, self._bin_rows, self._min_hits)
+                                                     self._vote, self._bin_rows, self._min_hits, self._norm_search, q_stats)
             codes, totals = codes[0], totals[0]
             m = int((codes >= 0).sum())                              # the diagonal vote's songs below min_hits are a tail: counts descend
             vote_codes, vote_totals = codes[:m].tolist(), totals[:m].tolist()
@@ -1277,7 +1362,7 @@ class Scanner:
             x_len = np.asarray([idx._song_rows[c][1] for c in want], dtype=np.int64)
             q_len = np.full(P, n, dtype=np.int64)
             panels = bool((x_len > ops.ALIGN_MAX_COLS).any())              # a long song among them: every pair in one panels launch
-            norm = idx._norm("scanner", rows) if self._normalize else None
+            norm = idx._norm("scanner", rows, q_stats=q_stats) if self._normalize else None
             S, s_off, s_ld = ops.pair_sim(rows, idx.fingerprints, np.zeros(P, np.int64), q_len, x_start, x_len, long_songs=panels,
                                           norm=norm)
             carry_off = np.asarray([self._slot[c] for c in want], dtype=np.int64) * (2 * idx._max_cols)

@@ -1839,6 +1839,43 @@ def flat_l2_topk_excl(q, x, x_sqnorm, k, ex_lo, ex_hi, q_sqnorm=None) -> Tuple[t
     return _flat_l2_topk("flat_l2_topk_excl", q, x, x_sqnorm, k, q_sqnorm, (ex_lo, ex_hi))
 
 
+def flat_norm_topk(q, x, norm, k, ex=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exhaustive top-k of every row of q (nq, d) over the rows of x (nx, d) under the cohort-normalised score (include/nsid.h,
+    "normalised candidate search"): z[i][j] is the cell ops.pair_sim(norm=) stores for the same two rows, bit for bit, and row i gets
+    its k largest z. norm = (q_mu, q_rs, x_mu, x_rs) as pair_sim takes them (cohort_stats of the rows of q and of x). Z (nq, k) fp32
+    descending, I (nq, k) int64; equal z smaller id first, a NaN z does not compete, and where fewer than k rows compete the tail is
+    I = -1, Z = -inf. ex = (ex_lo, ex_hi): flat_l2_topk_excl's per-row ranges of database rows that do not compete, None for none.
+    The kernel taken is the library's to name (nsid_debug_last_kernel); there is no fallback."""
+    name = "flat_norm_topk"
+    k = int(k)
+    if not 1 <= k <= SEARCH_MAX_K:
+        raise ValueError(f"{name}: k = {k} is outside [1, {SEARCH_MAX_K}]")
+    ldq, ldx = _search_rows(q, f"{name} q"), _search_rows(x, f"{name} x")
+    if q.shape[1] != x.shape[1]:
+        raise ValueError(f"{name}: query d = {q.shape[1]} != database d = {x.shape[1]}")
+    nq, d = q.shape
+    nx = x.shape[0]
+    norm = _norm_stats(norm, nq, nx, name)
+    if ex is not None and (not isinstance(ex, (tuple, list)) or len(ex) != 2):
+        raise ValueError(f"{name}: ex must be (ex_lo, ex_hi) or None")
+    for t in ex or ():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or t.dim() != 1 or not t.is_contiguous() \
+                or t.numel() != nq:
+            raise ValueError(f"{name}: ex_lo and ex_hi must be contiguous int32 tensors of {nq} entries on the GPU")
+    Z = torch.empty((nq, k), device=q.device, dtype=torch.float32)
+    I = torch.empty((nq, k), device=q.device, dtype=torch.int64)
+    if nq == 0:
+        return Z, I
+    wsb = int(lib.nsid_workspace_bytes(b"flat_norm_topk", nq, nx))
+    ws = torch.empty((max(wsb, 16),), device=q.device, dtype=torch.uint8)
+    exp = (None, None) if ex is None else (_p(ex[0]), _p(ex[1]))
+    # flat_l2_topk's flop and bytes, and the two statistics of every row
+    _timed(None, 2.0 * nq * nx * d, 4.0 * nx * (d + 2) + 4.0 * nq * (d + 2) + 12.0 * nq * k,
+           lambda: call("nsid_flat_norm_topk", _p(q), ldq, nq, _p(x) if nx else None, ldx, nx, *(_p(t) for t in norm), *exp, d, k, _p(Z),
+                        _p(I), _p(ws), ws.numel(), _stream()), (nq, nx, d, k))
+    return Z, I
+
+
 # ---- the certified bf16 pre-filter (include/nsid.h; DESIGN.md section 7)
 PREFILTER_M = SEARCH_MAX_K          # candidates per query row
 PREFILTER_MAX_D = 256               # the coarse kernel's widest row; above it the plain search runs
@@ -2199,16 +2236,16 @@ def cohort_stats(x, cohort) -> Tuple[torch.Tensor, torch.Tensor]:
     return mu, rs
 
 
-def _norm_stats(norm, nq, nx):
-    """pair_sim's norm=(q_mu, q_rs, x_mu, x_rs): contiguous fp32 device vectors that cover every row of q / x"""
+def _norm_stats(norm, nq, nx, name="pair_sim"):
+    """pair_sim's (and flat_norm_topk's) norm=(q_mu, q_rs, x_mu, x_rs): contiguous fp32 device vectors that cover every row of q / x"""
     if not isinstance(norm, (tuple, list)) or len(norm) != 4:
-        raise ValueError("pair_sim: norm must be (q_mu, q_rs, x_mu, x_rs)")
+        raise ValueError(f"{name}: norm must be (q_mu, q_rs, x_mu, x_rs)")
     for t, what, rows in zip(norm, ("q_mu", "q_rs", "x_mu", "x_rs"), (nq, nq, nx, nx)):
         if not isinstance(t, torch.Tensor):
-            raise TypeError(f"pair_sim: norm {what} must be a torch tensor on the GPU")
+            raise TypeError(f"{name}: norm {what} must be a torch tensor on the GPU")
         _chk(t)
         if t.dim() != 1 or t.numel() < rows:
-            raise ValueError(f"pair_sim: norm {what} must be a vector with one entry per row ({rows}), got {tuple(t.shape)}: the "
+            raise ValueError(f"{name}: norm {what} must be a vector with one entry per row ({rows}), got {tuple(t.shape)}: the "
                              "statistics are indexed by the absolute row of q / x")
     return tuple(norm)
 

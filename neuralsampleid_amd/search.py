@@ -180,6 +180,40 @@ class FlatL2Index:
             return D.cpu().numpy(), I.cpu().numpy()
         return D, I
 
+    def search_norm(self, q, k: int, norm, exclude=None):
+        """(nq, d) device queries -> (Z, I): per row the k stored rows of largest cohort-normalised score (ops.flat_norm_topk: the
+        cell ops.pair_sim(norm=) stores, bit for bit), Z (nq, k) descending and the row ids; equal scores smaller id first, a NaN score
+        does not compete, and where fewer than k rows compete the tail is I = -1, Z = -inf. norm = (q_mu, q_rs, x_mu, x_rs): the
+        cohort statistics of the rows of q and of ALL stored rows (ops.cohort_stats), device fp32. exclude: search's. The exact search
+        itself is untouched; an index made with prefilter=True refuses (the certificate is a statement about L2 keys, and nothing
+        like it has been derived for the normalised score)."""
+        if getattr(self, "_prefilter", False):
+            raise ValueError("FlatL2Index.search_norm: the bf16 pre-filter certifies L2 keys; there is no normalised pre-filter "
+                             "(use an index made without prefilter=True)")
+        k = int(k)
+        if not 1 <= k <= ops.SEARCH_MAX_K:
+            raise ValueError(f"FlatL2Index.search_norm: k = {k} is outside [1, {ops.SEARCH_MAX_K}]")
+        if not isinstance(q, torch.Tensor) or q.ndim != 2 or q.shape[1] != self.d:
+            raise ValueError(f"FlatL2Index.search_norm: expected (nq, {self.d}) device queries, got {tuple(getattr(q, 'shape', ()))}")
+        if not isinstance(norm, (tuple, list)) or len(norm) != 4:
+            raise ValueError("FlatL2Index.search_norm: norm must be (q_mu, q_rs, x_mu, x_rs)")
+        nq = int(q.shape[0])
+        for t, what, rows in zip(norm, ("q_mu", "q_rs", "x_mu", "x_rs"), (nq, nq, self._n, self._n)):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1 or t.numel() != rows:
+                raise ValueError(f"FlatL2Index.search_norm: norm {what} must be a vector of {rows} entries")
+        ex = None if exclude is None else exclude_ranges(exclude, nq, self._n)
+        qt = q.to(device=self.device, dtype=torch.float32).contiguous()
+        if ex is not None:
+            ex = torch.from_numpy(ex).to(self.device)
+        Z = torch.empty((nq, k), device=self.device, dtype=torch.float32)
+        I = torch.empty((nq, k), device=self.device, dtype=torch.int64)
+        q_mu, q_rs, x_mu, x_rs = norm
+        for a in range(0, nq, QUERY_BLOCK):
+            b = min(nq, a + QUERY_BLOCK)
+            exb = None if ex is None else (ex[0, a:b], ex[1, a:b])
+            Z[a:b], I[a:b] = ops.flat_norm_topk(qt[a:b], self.xb, (q_mu[a:b], q_rs[a:b], x_mu, x_rs), k, exb)
+        return Z, I
+
 
 def exclude_ranges(exclude, nq: int, ntotal: int) -> np.ndarray:
     """FlatL2Index.search's exclude = (lo, hi) checked on the host: a (2, nq) int32 array, or ValueError"""
