@@ -132,6 +132,26 @@ class KnnTape:
 TAPE: Optional[KnnTape] = None
 
 
+class DecisionTape:
+    """Test hook: record, without touching the arithmetic, every tensor on which a forward pass takes a discontinuous decision:
+    the ReLU pre-activations (.relu) and the candidates `neighbour - centre` (B,N,k,C) of each max-relative aggregation (.cand).
+    A gradient is only comparable between two roundings of the same graph while every such decision falls the same way
+    (tests/oracle64.py measures how far each one is from flipping)."""
+
+    def __init__(self):
+        self.relu: List[Tensor] = []
+        self.cand: List[Tensor] = []
+
+
+DECISIONS: Optional[DecisionTape] = None
+
+
+def relu(v: Tensor) -> Tensor:
+    if DECISIONS is not None:
+        DECISIONS.relu.append(v.detach())
+    return torch.relu(v)
+
+
 def knn_graph(y: Tensor, k: int, dilation: int = 1) -> Tensor:
     """y (B,N,C) -> neighbour indices (B,N,k) int64, clip-local, ascending distance, self first.
     L2-normalise channels, D = |a|^2 - 2ab + |b|^2 in fp32, k*dilation smallest, every dilation-th."""
@@ -165,7 +185,10 @@ def mr_aggregate(y: Tensor, idx: Tensor) -> Tensor:
     B, N, C = y.shape
     k = idx.shape[-1]
     nbr = torch.gather(y.unsqueeze(1).expand(B, N, N, C), 2, idx.unsqueeze(-1).expand(B, N, k, C))
-    m = (nbr - y.unsqueeze(2)).max(dim=2).values
+    cand = nbr - y.unsqueeze(2)
+    if DECISIONS is not None:
+        DECISIONS.cand.append(cand.detach())
+    m = cand.max(dim=2).values
     return _q(torch.stack((y, m), dim=-1).reshape(B, N, 2 * C))
 
 
@@ -187,7 +210,7 @@ def grapher(x: Tensor, P, pre: str, k: int, dilation: int, training: bool, st) -
     y = batchnorm_rows(linear_rows(rows, P, pre + "fc1.0."), P, pre + "fc1.1.", training, st).reshape(B, N, C)
     idx = knn_graph(y.detach(), k, dilation)
     u = mr_aggregate(y, idx).reshape(B * N, 2 * C)
-    v = torch.relu(batchnorm_rows(grouped_linear(u, P, pre + "graph_conv.gconv.nn.0."),
+    v = relu(batchnorm_rows(grouped_linear(u, P, pre + "graph_conv.gconv.nn.0."),
                                   P, pre + "graph_conv.gconv.nn.1.", training, st))
     w = batchnorm_rows(linear_rows(v, P, pre + "fc2.0."), P, pre + "fc2.1.", training, st)
     return _q(w + rows).reshape(B, N, C)
@@ -196,7 +219,7 @@ def grapher(x: Tensor, P, pre: str, k: int, dilation: int, training: bool, st) -
 def ffn(x: Tensor, P, pre: str, training: bool, st) -> Tensor:
     B, N, C = x.shape
     rows = x.reshape(B * N, C)
-    hdn = torch.relu(batchnorm_rows(linear_rows(rows, P, pre + "fc1.0."), P, pre + "fc1.1.", training, st))
+    hdn = relu(batchnorm_rows(linear_rows(rows, P, pre + "fc1.0."), P, pre + "fc1.1.", training, st))
     out = batchnorm_rows(linear_rows(hdn, P, pre + "fc2.0."), P, pre + "fc2.1.", training, st)
     return _q(out + rows).reshape(B, N, C)
 
